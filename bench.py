@@ -6,12 +6,16 @@ metric  : inferences/sec at batch 256 (Model-A = embedding_47_krnl tables + FC 3
           model (Model-C, batch 4096) as the "gather" object.
 step    : one pass of the hot path (index rows -> gather+pack -> 4-GEMM FC chain -> scores) over one batch of 256 synthetic
           requests whose index rows are already resident in HBM when the timed region starts (bench contract).
-value   : STEADY-STATE rate: whatever --steps says, the timed region runs back-to-back batches for >= 2 s of wall clock
-          (SURVEY 8(d)); `timed_batches` / `timed_s` say how many and how long, `ms_per_step` = timed_s / timed_batches.  The
-          figure for EXACTLY --steps batches after --warmup batches is reported beside it as `burst` (with the driver's
-          --steps 20 that is a launch-latency number: 20 batches do not even fill one fused launch group).
-          `pcie_inclusive_streaming` is the same request stream starting in HOST memory with scores delivered to HOST memory
-          (the reference loop's H2D / D2H included, cuda_server.c:460-461,494-495): reported next to `value`, never as it.
+value   : the rate over EXACTLY --steps back-to-back batches after --warmup batches (and >= 0.5 s of warm-up); `timed_batches` (= --steps) / `timed_s` say how
+          many and how long, `ms_per_step` = timed_s / timed_batches.  With few steps that is a launch-latency number (a fused launch
+          carries 64 batches): a steady-state figure wants >= 2 s of them, which --full reports beside `value` as
+          `steady_state`.  `pcie_inclusive_streaming` (--full) is the same request stream starting in HOST memory with scores
+          delivered to HOST memory (the reference loop's H2D / D2H included, cuda_server.c:460-461,494-495): reported next to
+          `value`, never as it.
+--full  : a plain run sets up, warms up, times the --steps batches and prints the line; every other measurement (steady state, roofline,
+          PCIe / TCP / CPU legs, the other configurations, the N > 1 per-rank and sharded legs) runs only with --full (or an explicit --legs).
+--dump-outputs DIR : after the timed region, DIR/scores.npy = the float32 scores of its last batch (rank 0), taken from the driver's own
+          score rings; the inputs are seeded, so two builds can be compared output for output.
 N > 1   : the path shards by independent request batches -> one replica per GPU, no data-path collective ("scaling":
           "weak"); value = batches all ranks processed / max-over-ranks time.  The gather half of the metric follows as
           `gather_per_bank_all_ranks` (every rank on its own Model-C replica at the same time, summed on rank 0).  Launched by torchrun (RANK / WORLD_SIZE in
@@ -53,7 +57,9 @@ SEED_TABLES, SEED_IDX, SEED_WEIGHTS = 0xF1EE7, 1234, 99
 N_IDX_BUFFERS = 1024         # distinct index buffers rotated through (>= 32), so caches are not re-hit artificially.  Round 6: 64 of them
                              # (770 k distinct Model-A rows = 98 MB of lines) sit INSIDE the 256 MB Infinity Cache and read 0.9 % high (71.05 vs 70.4 M
                              # inf/s; the kernel's own time does not move: profiles/r06_headline_index_buffers.txt); 1024 = 1.6 GB of lines do not
-STEADY_S = 2.2               # minimum wall clock of the timed region behind `value`
+STEADY_S = 2.2               # minimum wall clock of the timed region behind `steady_state` (--full)
+WARMUP_MIN_S = 0.5           # minimum wall clock of the headline's warm-up (--warmup batches, then more if they took less): the shader clock
+                             # ramps over many milliseconds of load, and a short warm-up left the ramp inside the timed region (-0.4 %)
 PROFILE_ROUND = "r06"       # prefix of the committed rocprofv3 summaries the roofline objects quote (profiles/<round>_*_kernel_stats.csv)
 PMC_FILES = [os.path.join(ROOT, "profiles", n) for n in ("r06_pmc.json", "r05_pmc.json", "archive/r04_pmc.json", "archive/r03_pmc.json", "archive/r02_pmc.json")]   # newest first, entry by entry (see pmc())
 
@@ -400,6 +406,26 @@ def launch_pusher(wk, B, d_idx, d_dense, ring, per_launch, n_lists=8):
         lists.append(wk.make_push_list([B] * per_launch, [d_idx[i % len(d_idx)] for i in ii],
                                        [d_dense[i % len(d_dense)] for i in ii] if d_dense else None, [ring[i % len(ring)] for i in ii]))
     return lambda l: wk.push_device_list(lists[l % n_lists])
+
+
+def dump_last_step(fr, ctx, driver, B, d_idx, n_timed, threads, depth, out_dir):
+    """--dump-outputs: DIR/scores.npy = the scores the timed region's last batch (index buffer (n_timed - 1) % len(d_idx)) left in the driver's
+    score rings.  Which ring slot holds them depends on how the driver threads raced for batches, so the slot is found by its content: the
+    entry nearest to the same batch pushed once more through a fresh worker (the same fr_worker_push_device path)."""
+    wk = fr.Worker(ctx, B)
+    d_sc = fr.DeviceBuffer(ctx, B * 4)
+    wk.push_device(B, d_idx[(n_timed - 1) % len(d_idx)], None, d_sc)
+    wk.sync()
+    again = d_sc.download(np.float32, B)
+    d_sc.free()
+    wk.close()
+    rings = np.concatenate([driver.score_ring(t, s, B) for t in range(threads) for s in range(depth)])
+    dist = np.abs(rings - again[None, :]).max(axis=1)
+    k = int(np.argmin(dist))
+    if dist[k] != 0:
+        sys.stderr.write("bench.py: the last timed batch's scores differ from the same batch run again by up to %g\n" % dist[k])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), rings[k])
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1445,8 +1471,13 @@ def run_sharded_cpu(fr, dist_mod, env, args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20000)
-    ap.add_argument("--warmup", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=20000, help="timed batches behind `value` (per rank)")
+    ap.add_argument("--warmup", type=int, default=2000, help="batches run before the timed region (per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg of the line (steady state, roofline, pcie, groups, tcp, cpu, configs, gather, bank; at N > 1 the per-rank and "
+                         "sharded legs) besides the headline; a plain run times the --steps batches and nothing else")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write DIR/scores.npy: the float32 scores of the timed region's last batch (rank 0)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--threads", type=int, default=2, help="host driver threads (reference THREAD_NUM = 4, constant.h:42)")
     ap.add_argument("--depth", type=int, default=2, help="workers (streams) each driver thread keeps in flight")
@@ -1456,8 +1487,9 @@ def main():
     ap.add_argument("--model", choices=["A", "B", "C"], default="A", help="A = BASELINE configs[1] (default headline); B/C: one other config, throughput + roofline leg only")
     ap.add_argument("--precision", choices=["f32", "bf16", "fp8"], default="f32",
                     help="FC chain arithmetic (bf16 = BASELINE configs[2], fp8 = configs[4]: e4m3, calibrated on the first batch)")
-    ap.add_argument("--legs", default="all",
-                    help="comma list of the extra legs rank 0 runs at N = 1: roofline,groups,pcie,tcp,cpu,configs,gather,bank (default all; 'none' = headline only)")
+    ap.add_argument("--legs", default=None,
+                    help="comma list of the extra legs rank 0 runs at N = 1: roofline,groups,pcie,tcp,cpu,configs,gather,bank (default: all with --full, "
+                         "roofline with --roofline-only, none otherwise; 'none' = headline only)")
     ap.add_argument("--gather-law", choices=["all", "uniform", "zipf"], default="all", help="gather leg: per-table index law(s) to run (PMC passes: one law per kernel name)")
     ap.add_argument("--transport", choices=["f32", "lp"], default="lp",
                     help="sharded mode: slices travel as fp32, or (lp) in the chain's own operand type when --precision is bf16 / fp8")
@@ -1487,7 +1519,7 @@ def main():
     ap.add_argument("--per-bank", action="store_true", help="single-configuration runs (--model / --precision): FR_INDEX_PER_BANK context and indices")
     ap.add_argument("--no-multi-gather", action="store_true", help="N > 1: skip the per-rank legs (gather_per_bank_all_ranks, configs_all_ranks)")
     ap.add_argument("--no-multi-configs", action="store_true", help="N > 1: skip configs_all_ranks (Model-B bf16, Model-C bf16 / fp8 on every rank)")
-    ap.add_argument("--no-multi-sharded", action="store_true", help="N > 1: skip the table-sharded legs (`sharded`, `sharded_inflated_fp8`) of the default line")
+    ap.add_argument("--no-multi-sharded", action="store_true", help="N > 1: skip the table-sharded legs (`sharded`, `sharded_inflated_fp8`) of the --full line")
     ap.add_argument("--fail-rank", type=int, default=-1, help="--plumbing-only: this rank exits with status 3 before the first barrier (launcher fail-fast test)")
     ap.add_argument("--fail-sharded-rank", type=int, default=-1, help="--plumbing-only: this rank raises inside a guarded collective leg (line + non-zero exit status test)")
     ap.add_argument("--cabi-child", default=None, help=argparse.SUPPRESS)  # RANK/WORLD/DEVICE/IDHEX/OUT: one rank of the C-ABI RCCL leg (cabi_child_main)
@@ -1495,6 +1527,10 @@ def main():
     ap.add_argument("--plumbing-only", action="store_true",
                     help="launch / rendezvous / timing-rule check without touching a GPU or the library (CPU test of the multi-GPU launcher)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.legs is None:
+        args.legs = "roofline" if args.roofline_only else ("all" if args.full else "none")
     if args.cpu_child:   # a host-only helper process of leg_cpu_baseline: before anything could touch a GPU
         return cpu_child_main(args.cpu_child)
     if args.cabi_child:  # one rank of the C-ABI RCCL leg, in a process of its own
@@ -1600,20 +1636,31 @@ def main():
             legs.clear()
             legs.add("roofline")
     driver = fr.Driver(ctx, args.threads, args.depth, B)
-    driver.run_resident(B, max(args.warmup, 0), d_idx)
+    warm_s = driver.run_resident(B, args.warmup, d_idx)
+    while warm_s < WARMUP_MIN_S and not (args.roofline_only or cpu):
+        warm_s += driver.run_resident(B, 8192, d_idx)
     barrier()
+    n_timed = args.steps
     t0 = time.perf_counter()
-    driver.run_resident(B, max(args.steps, 1), d_idx)            # exactly --steps batches: the burst figure
-    barrier()
-    burst_dt = env.max_over_ranks(time.perf_counter() - t0)
-    # (the calibration run inside steady_run includes the ramp and overestimates the time per batch by ~8 %: size for 1.12 x the target)
-    n_timed = args.steps if (args.roofline_only or cpu) else max(steady_run(lambda k: driver.run_resident(B, k, d_idx), 0.3 if args.quick else 1.12 * STEADY_S, n_first=8192, env=env),
-                                                        args.steps)
-    barrier()
-    t0 = time.perf_counter()
-    driver.run_resident(B, n_timed, d_idx)                       # >= 2 s of back-to-back batches: `value`
+    driver.run_resident(B, n_timed, d_idx)                       # exactly --steps batches: `value`
     barrier()
     dt = env.max_over_ranks(time.perf_counter() - t0)
+    if rank == 0 and args.dump_outputs:
+        dump_last_step(fr, ctx, driver, B, d_idx, n_timed, args.threads, args.depth, args.dump_outputs)
+
+    steady = None
+    if args.full and not (args.roofline_only or cpu):
+        # the steady-state figure beside `value`: >= 2 s of back-to-back batches, sized by a calibration run (which includes
+        # the clock ramp and overestimates the time per batch by ~8 %: size for 1.12 x the target)
+        n_steady = steady_run(lambda k: driver.run_resident(B, k, d_idx), 0.3 if args.quick else 1.12 * STEADY_S, n_first=8192, env=env)
+        barrier()
+        t0 = time.perf_counter()
+        driver.run_resident(B, n_steady, d_idx)
+        barrier()
+        el = env.max_over_ranks(time.perf_counter() - t0)
+        steady = {"value": world * n_steady * B / el, "unit": "inferences/s", "ms_per_step": 1e3 * el / n_steady, "timed_batches": n_steady, "timed_s": el,
+                  "what": "steady state: %d back-to-back batches per rank over %.2f s (sized for >= %.1f s from a calibration run, whatever --steps says)"
+                          % (n_steady, el, 0.3 if args.quick else STEADY_S)}
 
     leg_done("headline")
     result = None
@@ -1630,12 +1677,11 @@ def main():
                        "batch": B, "driver_threads": args.threads, "workers_per_thread": args.depth,
                        "batches_per_launch": ctx.stream_group(), "parallelism": "replicas x%d" % world},
             "timed_batches": n_timed, "timed_s": dt, "leg_seconds": leg_s,
-            "value_is": "steady state: %d back-to-back batches per rank over %.2f s (sized for >= %.1f s from a calibration run, whatever --steps says)" % (n_timed, dt, STEADY_S),
-            "burst": {"steps": args.steps, "warmup": args.warmup, "value": world * args.steps * B / burst_dt, "unit": "inferences/s",
-                      "ms_per_step": 1e3 * burst_dt / max(args.steps, 1),
-                      "what": "EXACTLY --steps batches after --warmup batches, barrier + device sync on both sides: with few steps this is launch "
-                              "latency (a fused launch carries %d batches), not throughput" % ctx.stream_group()},
+            "value_is": "EXACTLY --steps = %d back-to-back batches per rank after --warmup batches (and >= %.1f s of warm-up), barrier + device sync on both sides (%.3f s): with "
+                        "few steps this is launch latency (a fused launch carries %d batches), not throughput" % (n_timed, WARMUP_MIN_S, dt, ctx.stream_group()),
         }
+        if steady:
+            result["steady_state"] = steady
 
     # (the host-fed twin of `value` is measured right behind it, before the other legs have created and destroyed their streams)
     if want("pcie"):
@@ -1662,9 +1708,10 @@ def main():
         el = hs.run_host(B, n, idx_host, streaming=True)
         hs.close()
         result["value_pcie_inclusive"] = n * B / el   # the same metric with the reference loop's H2D / D2H inside (never `value`: bench contract)
-        result["value_hbm_resident"] = result["value"]
+        # (beside the steady-state twin of `value` when there is one: both are >= 2 s of back-to-back batches)
+        result["value_hbm_resident"] = steady["value"] if steady else result["value"]
         result["pcie_inclusive_streaming"] = {"value": n * B / el, "unit": "inferences/s", "ms_per_step": 1e3 * el / n, "timed_batches": n, "timed_s": el,
-                                              "fraction_of_value": n * B / el / result["value"],
+                                              "fraction_of_value": n * B / el / result["value_hbm_resident"],
                                               "what": "host-resident request stream, scores delivered to host memory: blocks of 64 batches staged in pinned "
                                                       "memory, one H2D (copy stream) + one fused launch per block, scores written to pinned memory by the kernel "
                                                       "(fr_worker_push_host), %d threads x 1 worker" % ht}
@@ -1906,7 +1953,7 @@ def main():
             result.setdefault("gather", {})["error"] = repr(ex)
 
     leg_done("gather_and_configs_C")
-    if multi and not args.no_multi_gather:
+    if multi and args.full and not args.no_multi_gather:
         # N > 1: the other half of BASELINE.json's metric ("embedding-gather HBM GB/s vs peak, 1 -> 8 MI355X") and BASELINE.md section 3's
         # other models -- every rank runs the legs below on its own replicas at the same time, rank 0 reports the SUM of the per-rank rates.
         # Collectives sit OUTSIDE the try blocks and every rank reaches every one of them whatever happens to its own leg: a rank that
@@ -2012,7 +2059,7 @@ def main():
             holder["c"][1].close()
         leg_done("configs_all_ranks")
 
-    if multi and not args.no_multi_sharded:
+    if multi and args.full and not args.no_multi_sharded:
         # N > 1: the table-sharded split north_star names (BASELINE configs[3] / [4]) on the DEFAULT line -- Model-C batch 4096, tables
         # sharded by table-ID over the N ranks, one all-gather of the looked-up slices per step (bf16 transport), FC on B / N items per rank;
         # and, when the node holds it, configs[4]: every table 5 x its rows (316 GB: past one GPU's 288 GB), fp8 FC.  Fresh contexts (the

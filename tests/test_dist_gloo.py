@@ -270,7 +270,7 @@ def test_bench_failed_collective_leg_keeps_the_line_and_exits_non_zero(tmp_path)
 
 
 def test_bench_eight_ranks_rehearsal_on_the_cpu_back_end(tmp_path):
-    """the default `bench.py --gpus 8` line with EIGHT ranks before an 8-GPU node ever sees it.  The test boxes have one
+    """the `bench.py --gpus 8 --full` line with EIGHT ranks before an 8-GPU node ever sees it.  The test boxes have one
     GPU and their process guard allows at most six processes on it, so the eight ranks run on the library's CPU back-end (--device -1:
     fr_ctx_create(device = -1) on every rank, gloo, row-capped tables, token step counts): the same control flow -- self-launch, rendezvous,
     barriers and max-over-ranks timing of the headline, the voted per-rank legs (gather_per_bank_all_ranks, configs_all_ranks), the two
@@ -283,7 +283,7 @@ def test_bench_eight_ranks_rehearsal_on_the_cpu_back_end(tmp_path):
     detail = str(tmp_path / "detail.json")
     t0 = time.time()
     slow_build = "san.so" in os.path.basename(os.environ.get("FR_LIB", ""))   # tools/run_sanitizers.sh: instrumented host code, eight ranks of it on eight cores
-    rc, out, err = _run_bench(["--gpus", "8", "--device", "-1", "--backend", "gloo", "--rows-cap", "2000", "--steps", "4", "--warmup", "2"], timeout=1800 if slow_build else 600, detail=detail)
+    rc, out, err = _run_bench(["--gpus", "8", "--device", "-1", "--backend", "gloo", "--rows-cap", "2000", "--steps", "4", "--warmup", "2", "--full"], timeout=1800 if slow_build else 600, detail=detail)
     wall = time.time() - t0
     assert rc == 0, err[-3000:]
     line = _the_line(out)
@@ -308,6 +308,68 @@ def test_bench_eight_ranks_rehearsal_on_the_cpu_back_end(tmp_path):
     assert j["sharded"]["baseline_config"] == "configs[3]" and j["sharded_inflated_fp8"]["baseline_config"] == "configs[4]" and "rows x 5" in c4["workload"]
 
 
+def _last_batch_idx(fr, model, steps, B=256):
+    """The index rows of the last timed batch of a one-rank bench run: bench.py draws its rotating buffers from replica_seed(1234, 0)."""
+    rng = np.random.default_rng(1234)
+    rows = model.rows()
+    bufs = [(rng.random((B, len(rows))) * rows[None, :]).astype(np.int32) for _ in range(min(steps, 1024))]
+    return bufs[(steps - 1) % 1024]
+
+
+def _plain_bench_dumps(tmp_path, args, timeout):
+    """Two identical plain bench runs with --dump-outputs: -> (line, detail, scores) of the first; the two dumps must be equal."""
+    import json
+    got = []
+    for i in range(2):
+        detail = str(tmp_path / ("detail%d.json" % i))
+        rc, out, err = _run_bench(args + ["--dump-outputs", str(tmp_path / ("out%d" % i))], timeout=timeout, detail=detail)
+        assert rc == 0, err[-3000:]
+        got.append((_the_line(out), json.load(open(detail)), np.load(str(tmp_path / ("out%d" % i) / "scores.npy"))))
+    assert np.array_equal(got[0][2], got[1][2]), "the same arguments gave different outputs"
+    line, detail, s = got[0]
+    assert s.dtype == np.float32 and s.shape == (256,) and np.isfinite(s).all()
+    for k in ("steady_state", "pcie_inclusive", "launch_group_table", "cpu_backend", "configs", "gather", "gather_per_bank", "sharded"):
+        assert k not in detail, k      # a plain run measures the headline and nothing else
+    return line, detail, s
+
+
+def test_bench_plain_rehearsal_times_exactly_steps_and_dumps_the_last_batch(fr, tmp_path):
+    """A plain run (no --full) on the CPU back-end: exactly --steps timed batches behind `value` / `ms_per_step`, no other leg, and
+    --dump-outputs writes the scores of the last timed batch -- the same from run to run, and those of that batch computed on its own."""
+    steps = 37
+    line, detail, s = _plain_bench_dumps(tmp_path, ["--gpus", "1", "--device", "-1", "--rows-cap", "2000", "--steps", str(steps), "--warmup", "3"], 300)
+    assert line["steps"] == steps and line["timed_batches"] == steps and detail["timed_batches"] == steps
+    assert line["ms_per_step"] == pytest.approx(1e3 * line["timed_s"] / steps, rel=1e-4)
+    assert line["value"] == pytest.approx(steps * 256 / line["timed_s"], rel=1e-4)
+    m = fr.Model.builtin(fr.MODEL_A).clone(max_rows=2000)
+    c = fr.Context(m, device=fr.DEVICE_CPU)
+    try:
+        c.fill_tables(fr.FILL_HASH, 0xF1EE7)
+        c.fill_weights(fr.WEIGHTS_UNIFORM, 99)
+        wk = fr.Worker(c, 256)
+        ref = wk.infer(_last_batch_idx(fr, m, steps))
+        wk.close()
+    finally:
+        c.close()
+    np.testing.assert_allclose(s, ref, rtol=1e-5, atol=1e-6 * float(np.abs(ref).max()))
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_times_exactly_steps_and_dumps_the_last_batch(gpu, ctxs, fr, tmp_path):
+    """The plain GPU run the driver times: exactly --steps batches behind `value`, no other leg, and the dumped scores of the last timed batch
+    equal from run to run and within fp32 summation-order noise of that batch through the submit path of a context with the same seeds."""
+    from gpu_helpers import rel_err
+    steps = 5000
+    line, detail, s = _plain_bench_dumps(tmp_path, ["--gpus", "1", "--steps", str(steps), "--warmup", "500"], 600)
+    assert line["steps"] == steps and line["timed_batches"] == steps and line["dtype"] == "f32" and line["value"] > 0
+    assert line["ms_per_step"] == pytest.approx(1e3 * line["timed_s"] / steps, rel=1e-4)
+    m, ctx = ctxs(fr.MODEL_A)
+    wk = fr.Worker(ctx, 256)
+    ref = wk.infer(_last_batch_idx(fr, m, steps))
+    wk.close()
+    assert rel_err(s, ref) <= 1e-4, rel_err(s, ref)
+
+
 def test_bench_eight_rank_sharded_alltoall_rehearsal():
     """`bench.py --mode sharded --exchange alltoall` with eight ranks on the CPU back-end: each rank receives only ITS 512 items' slices."""
     import json
@@ -326,7 +388,7 @@ def test_bench_default_line_is_compact(gpu, tmp_path):
     roofline + cpu_baseline; the full result is in the detail file."""
     import json
     detail = str(tmp_path / "detail.json")
-    rc, out, err = _run_bench(["--gpus", "1", "--quick", "--steps", "20", "--warmup", "5"], timeout=1500, detail=detail)
+    rc, out, err = _run_bench(["--gpus", "1", "--full", "--quick", "--steps", "20", "--warmup", "5"], timeout=1500, detail=detail)
     assert rc == 0, err[-3000:]
     j = _the_line(out)
     rf, cb = j["roofline"], j["cpu_baseline"]
@@ -348,8 +410,8 @@ def test_bench_two_ranks_on_one_gpu(gpu, extra):
     (--share-device).  Replicas: value aggregates both ranks.  Sharded: 2-way table-ID shards, the exchange through gloo, scores
     of rank 0's items equal to an unsharded context (1e-5 in fp32, bit-identical in fp8) and the pipelined run equal to the stepwise one."""
     import json
-    # the DEFAULT line (extra == []) keeps its roofline leg: at N > 1 rank 0 prices the dominant kernel on its own replica
-    args = ["--gpus", "2", "--backend", "gloo", "--share-device", "--legs", "none" if extra else "roofline"] + (extra or ["--steps", "300", "--warmup", "100"])
+    # the --full line (extra == []) keeps its roofline leg: at N > 1 rank 0 prices the dominant kernel on its own replica
+    args = ["--gpus", "2", "--backend", "gloo", "--share-device", "--legs", "none" if extra else "roofline"] + (extra or ["--full", "--steps", "300", "--warmup", "100"])
     detail = None if extra else os.path.join(os.environ.get("TMPDIR", "/tmp"), "fr_bench_detail_%d.json" % os.getpid())
     rc, out, err = _run_bench(args, timeout=1200, detail=detail)
     assert rc == 0, err[-3000:]
@@ -357,7 +419,7 @@ def test_bench_two_ranks_on_one_gpu(gpu, extra):
     assert len(lines) == 1, out
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["value"] > 0
-    if not extra:   # the default line is the compact one; the objects checked below live in the detail file
+    if not extra:   # the --full line is the compact one; the objects checked below live in the detail file
         line = _the_line(out)
         assert line["sharded"]["value"] > 0 and line["gather_per_bank_all_ranks"]["ranks_measured"] == 2 and len(line["configs_all_ranks"]) == 3, line
         j = json.load(open(detail))
@@ -373,7 +435,9 @@ def test_bench_two_ranks_on_one_gpu(gpu, extra):
         else:                     # low-precision chains sum whole K per output in one order: bit for bit
             assert chk["bit_identical"] is True, c
     else:
-        assert j["timed_batches"] >= 300 and j["timed_s"] >= 2.0 and j["scaling"] == "weak"
+        assert j["timed_batches"] == 300 and j["scaling"] == "weak"
+        st = j["steady_state"]                 # --full: the steady-state figure beside `value`
+        assert st["timed_batches"] >= 300 and st["timed_s"] >= 2.0 and st["value"] > 0, st
         g = j["gather_per_bank_all_ranks"]     # N > 1: every rank gathers on its own Model-C replica, rank 0 reports the sum
         assert g["ranks_measured"] == 2 and g["achieved"] > 0 and g["peak"] == 16000.0, g
         ca = j["configs_all_ranks"]            # ... and Model-C bf16 / fp8 and Model-B bf16 on every rank's replica
@@ -399,7 +463,8 @@ def test_bench_four_ranks_on_one_gpu(gpu, tmp_path):
     transport) against an unsharded context -- and the printed wall-time budget.  (Eight ranks: the CPU-back-end rehearsal above.)"""
     import json
     detail = str(tmp_path / "detail.json")
-    rc, out, err = _run_bench(["--gpus", "4", "--backend", "gloo", "--share-device", "--rows-cap", "20000", "--legs", "roofline", "--steps", "300", "--warmup", "100", "--quick"],
+    rc, out, err = _run_bench(["--gpus", "4", "--backend", "gloo", "--share-device", "--rows-cap", "20000", "--legs", "roofline", "--steps", "300", "--warmup", "100", "--quick",
+                               "--full"],
                               timeout=1200, detail=detail)
     assert rc == 0, err[-3000:]
     line = _the_line(out)
@@ -422,7 +487,7 @@ def test_bench_rccl_code_path_on_one_rank(gpu, tmp_path):
     must be the ONLY thing on stdout."""
     import json
     detail = str(tmp_path / "detail.json")
-    rc, out, err = _run_bench(["--gpus", "1", "--backend", "nccl", "--force-process-group", "--legs", "none", "--quick", "--rows-cap", "200000"], timeout=900, detail=detail)
+    rc, out, err = _run_bench(["--gpus", "1", "--backend", "nccl", "--force-process-group", "--full", "--legs", "none", "--quick", "--rows-cap", "200000"], timeout=900, detail=detail)
     assert rc == 0, err[-3000:]
     assert len(out.strip().splitlines()) == 1, out[:2000]          # no RCCL banner in front of the line
     line = _the_line(out)
@@ -493,7 +558,8 @@ def test_bench_cabi_rccl_leg_child_and_failure_path(gpu, tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["FR_BENCH_CABI_RCCL"] = "force"
     env["FR_BENCH_DETAIL"] = str(tmp_path / "detail.json")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--legs", "none", "--steps", "300", "--warmup", "100"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-device", "--full", "--legs", "none", "--steps", "300",
+                        "--warmup", "100"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     line = _the_line(p.stdout.decode())
