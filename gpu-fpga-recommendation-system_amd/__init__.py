@@ -26,6 +26,7 @@ LAYOUT_SEMANTIC, LAYOUT_BLOCKED = 0, 1
 INDEX_PER_TABLE, INDEX_PER_ITEM, INDEX_PER_BANK = 0, 1, 2
 SEG_TABLE, SEG_COPY, SEG_DENSE = 0, 1, 2
 GATHER_WORD_MAJOR, GATHER_ITEM_TILE, GATHER_ITEM_TILE_DEDUP, GATHER_ITEM_TILE_DEDUP_COUNT, GATHER_WORD_MAJOR_ONE_CHUNK = 0, 1, 2, 3, 4
+EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step's slices travel (Comm.set_exchange)
 ABI_VERSION = 6   # include/fleetrec.h FR_ABI_VERSION this binding was written against
 MEM_CLASS_NAMES = {0: "HBM", 1: "DDR", 2: "PLRAM"}
 
@@ -70,6 +71,7 @@ ABI_SYMBOLS = [
     "fr_worker_timer_stop_ms", "fr_device_malloc", "fr_device_free", "fr_memcpy_h2d", "fr_memcpy_d2h",
     "fr_device_synchronize", "fr_ctx_shard_info", "fr_driver_create", "fr_driver_destroy", "fr_driver_run_resident",
     "fr_driver_worker", "fr_driver_score_ring", "fr_driver_run_host", "fr_driver_run_host_streaming", "fr_driver_host_score_ring", "fr_ctx_stream_group", "fr_ctx_set_stream_group", "fr_model_shard_plan", "fr_worker_fc_from_slices", "fr_worker_last_kernel", "fr_worker_inject_fc_failure", "fr_ctx_set_lp_bank_image", "fr_ctx_lp_bank_image_bytes",
+    "fr_comm_set_exchange", "fr_comm_exchange", "fr_comm_exchange_bytes",
 ]
 
 
@@ -134,6 +136,8 @@ def lib():
         "fr_worker_fc_from_slices": (i32, [vp, i32, i32, i32, vp, vp]),
         "fr_worker_last_kernel": (ctypes.c_char_p, [vp]), "fr_worker_inject_fc_failure": (i32, [vp, i32]),
         "fr_ctx_set_lp_bank_image": (i32, [vp, i32]), "fr_ctx_lp_bank_image_bytes": (ctypes.c_size_t, [vp]),
+        "fr_comm_set_exchange": (i32, [vp, i32]), "fr_comm_exchange": (i32, [vp]),
+        "fr_comm_exchange_bytes": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -780,6 +784,31 @@ class Comm:
     def set_wait_ms(self, ms):
         """Bound of fr_worker_sync's wait for a sharded step's collectives on this rank (default 60 s)."""
         _check(lib().fr_comm_set_wait_ms(self._h, int(ms)))
+
+    _EXCHANGES = {"allgather": EXCHANGE_ALLGATHER, "alltoall": EXCHANGE_ALLTOALL}
+
+    def set_exchange(self, mode):
+        """How this rank's sharded steps exchange the slices: "allgather" (default) or "alltoall" (or EXCHANGE_*); between steps, the same
+        mode on every rank of the communicator (fr_comm_set_exchange)."""
+        if isinstance(mode, str):
+            if mode not in self._EXCHANGES:
+                raise FleetRecError(FR_ERR_INVALID, "unknown exchange mode %r (allgather | alltoall)" % mode)
+            mode = self._EXCHANGES[mode]
+        _check(lib().fr_comm_set_exchange(self._h, int(mode)))
+
+    @property
+    def exchange(self):
+        """The current exchange mode: EXCHANGE_ALLGATHER or EXCHANGE_ALLTOALL."""
+        mode = lib().fr_comm_exchange(self._h)
+        if mode < 0:
+            _check(mode)
+        return mode
+
+    def exchange_bytes(self):
+        """-> (received, sent): slice bytes of the last sharded step this rank issued, peers only (fleetrec_diag.h; counted, not measured)."""
+        rx, tx = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(lib().fr_comm_exchange_bytes(self._h, ctypes.byref(rx), ctypes.byref(tx)))
+        return rx.value, tx.value
 
     def close(self):
         if self._h:

@@ -4,6 +4,10 @@
 // three sockets before its GEMMs (GPU/final_network_cublasLt_3_nodes_no_FIFO_scatter/cuda_server.c:513-591).  Here the "senders" are
 // the G GPUs that hold the table-ID shards: each gathers its slice of the record, ONE ncclAllGather over xGMI delivers all slices to
 // everybody, each GPU runs the FC chain on its B/G items, and a second (tiny) all-gather hands every rank all B scores.
+// EXCHANGE MODES (fr_comm_set_exchange): the all-gather above is the default; in all-to-all mode each rank receives from every rank only the
+// rows of its own items (grouped ncclSend / ncclRecv; the host exchange copies only those rows) -- 1/G of the all-gather's bytes, the same
+// readers (the receive buffer is the all-gather layout of a batch of n_r items), bit-identical scores.  The score exchange and the sharded fp8
+// calibration are all-gathers in both modes.
 // librccl.so is opened on first use (dlopen), so unsharded users never load it; every RCCL failure surfaces as FR_ERR_COMM.
 //
 // TWO TRANSPORTS under ONE protocol (round 6).  The step -- the uneven item split, the status word behind every score chunk, the
@@ -49,10 +53,16 @@ struct Rccl {
     decltype(&ncclGetErrorString) GetErrorString = nullptr;
     decltype(&ncclCommAbort) CommAbort = nullptr;  // optional: a rank that cannot take part in a collective aborts the communicator
     decltype(&ncclCommGetAsyncError) CommGetAsyncError = nullptr;  // optional: polled by the bounded wait of fr_comm_wait
+    // optional as a set: the all-to-all exchange mode (fr_comm_set_exchange refuses FR_EXCHANGE_ALLTOALL over RCCL without them)
+    decltype(&ncclSend) Send = nullptr;
+    decltype(&ncclRecv) Recv = nullptr;
+    decltype(&ncclGroupStart) GroupStart = nullptr;
+    decltype(&ncclGroupEnd) GroupEnd = nullptr;
 };
 Rccl g_rccl;
 std::once_flag g_rccl_once;
 bool g_rccl_ok = false;
+bool g_rccl_p2p = false;   // Send / Recv / GroupStart / GroupEnd all resolved
 char g_rccl_why[256] = "symbol missing";
 
 int rccl_load() {
@@ -78,6 +88,11 @@ int rccl_load() {
 #undef FR_SYM
         g_rccl.CommAbort = reinterpret_cast<decltype(g_rccl.CommAbort)>(dlsym(g_rccl.handle, "ncclCommAbort"));
         g_rccl.CommGetAsyncError = reinterpret_cast<decltype(g_rccl.CommGetAsyncError)>(dlsym(g_rccl.handle, "ncclCommGetAsyncError"));
+        g_rccl.Send = reinterpret_cast<decltype(g_rccl.Send)>(dlsym(g_rccl.handle, "ncclSend"));
+        g_rccl.Recv = reinterpret_cast<decltype(g_rccl.Recv)>(dlsym(g_rccl.handle, "ncclRecv"));
+        g_rccl.GroupStart = reinterpret_cast<decltype(g_rccl.GroupStart)>(dlsym(g_rccl.handle, "ncclGroupStart"));
+        g_rccl.GroupEnd = reinterpret_cast<decltype(g_rccl.GroupEnd)>(dlsym(g_rccl.handle, "ncclGroupEnd"));
+        g_rccl_p2p = g_rccl.Send && g_rccl.Recv && g_rccl.GroupStart && g_rccl.GroupEnd;
         g_rccl_ok = true;
     });
     if (!g_rccl_ok) FR_FAIL(FR_ERR_COMM, "librccl.so could not be loaded (dlopen / dlsym): %s", g_rccl_why);
@@ -89,16 +104,28 @@ int rccl_load() {
 // ---- transport 2: the in-process host exchange --------------------------------------------------------------------------------------
 namespace {
 constexpr int FR_HOST_MAX_RANKS = 64;
+// the uneven item split of a sharded step: rank q owns items [lo, lo + n) of a batch over G ranks
+inline void item_range(int batch, int G, int q, int *lo, int *n) {
+    const int base = batch / G, rem = batch % G;
+    *lo = q * base + (q < rem ? q : rem);
+    *n = base + (q < rem ? 1 : 0);
+}
+
 // One per fr_comm_init_all over CPU contexts (or over GPU contexts that share a device: the staged form), shared by its G handles.  all_gather: every rank publishes its send buffer and waits for the
 // others (barrier 1), copies all G buffers into its own receive buffer, and waits until everybody has copied (barrier 2: only then may a
 // send buffer be reused).  Barrier 1 ends early when the group is aborted; barrier 2 never does -- every rank that left barrier 1 is copying
-// from its peers' buffers and will count itself in, and no buffer may go away under a peer's memcpy.
+// from its peers' buffers and will count itself in, and no buffer may go away under a peer's memcpy.  all_to_all: the same rendezvous, but
+// each rank copies only the rows of its own items from every peer.  Every rank publishes the operation with its sizes: ranks that disagree
+// (another operation, another size) break the group.
 struct HostGroup {
+    enum Op { ALL_GATHER = 0, ALL_TO_ALL = 1 };
     const int n;
     std::mutex m;
     std::condition_variable cv;
     const void *send[FR_HOST_MAX_RANKS] = {};
     size_t bytes[FR_HOST_MAX_RANKS] = {};
+    size_t row[FR_HOST_MAX_RANKS] = {};
+    int op[FR_HOST_MAX_RANKS] = {};
     int arrived = 0, copied = 0;
     uint64_t gen_arrive = 0, gen_copy = 0;
     bool broken = false;            // under m
@@ -114,7 +141,13 @@ struct HostGroup {
         cv.notify_all();
     }
     // -> FR_OK, or FR_ERR_COMM when the group was aborted before everybody had arrived / the ranks disagree about the size
-    int all_gather(int rank, const void *sendbuf, void *recvbuf, size_t nbytes) {
+    int all_gather(int rank, const void *sendbuf, void *recvbuf, size_t nbytes) { return exchange(rank, ALL_GATHER, sendbuf, recvbuf, nbytes, nbytes); }
+    // every rank sends `batch` rows of row_bytes (nbytes = batch * row_bytes); rank r receives [G][n_r] rows: rows [lo_r, lo_r + n_r) of each
+    // rank's buffer, in rank order.  -> as all_gather
+    int all_to_all(int rank, const void *sendbuf, void *recvbuf, size_t nbytes, size_t row_bytes) { return exchange(rank, ALL_TO_ALL, sendbuf, recvbuf, nbytes, row_bytes); }
+
+  private:
+    int exchange(int rank, int op_, const void *sendbuf, void *recvbuf, size_t nbytes, size_t row_bytes) {
         const void *src[FR_HOST_MAX_RANKS];
         bool same = true;
         {
@@ -122,6 +155,8 @@ struct HostGroup {
             if (broken) return FR_ERR_COMM;
             send[rank] = sendbuf;
             bytes[rank] = nbytes;
+            row[rank] = row_bytes;
+            op[rank] = op_;
             const uint64_t g = gen_arrive;
             if (++arrived == n) {
                 arrived = 0;
@@ -136,15 +171,21 @@ struct HostGroup {
             }
             for (int q = 0; q < n; q++) {
                 src[q] = send[q];
-                same &= bytes[q] == nbytes;
+                same &= bytes[q] == nbytes && row[q] == row_bytes && op[q] == op_;
             }
             if (!same) {   // every rank reads the same table and takes the same decision: nobody copies, everybody still passes barrier 2
                 broken = true;
                 broken_flag.store(true, std::memory_order_release);
             }
         }
-        if (same)
+        if (same && op_ == ALL_GATHER) {
             for (int q = 0; q < n; q++) memcpy(static_cast<char *>(recvbuf) + (size_t)q * nbytes, src[q], nbytes);
+        } else if (same) {
+            int lo, rows;
+            item_range((int)(nbytes / row_bytes), n, rank, &lo, &rows);
+            const size_t part = (size_t)rows * row_bytes;
+            for (int q = 0; q < n && part; q++) memcpy(static_cast<char *>(recvbuf) + (size_t)q * part, static_cast<const char *>(src[q]) + (size_t)lo * row_bytes, part);
+        }
         {
             std::unique_lock<std::mutex> lk(m);
             const uint64_t g = gen_copy;
@@ -236,6 +277,8 @@ struct fr_comm {
     // runs on its host stream while fr_worker_sync polls)
     std::atomic<bool> broken{false};
     std::atomic<int> wait_ms{60000};  // bound of fr_comm_wait: how long fr_worker_sync lets a step's collectives take before it gives the peers up
+    std::atomic<int> exchange{FR_EXCHANGE_ALLGATHER};   // fr_comm_set_exchange: how the slices travel (the score chunks are always all-gathered)
+    std::atomic<uint64_t> x_received{0}, x_sent{0};     // fr_comm_exchange_bytes: slice bytes of the last step, peers only
     // one reference for the handle fr_comm_init_* gave out + one per worker with a sharded step in flight through this communicator
     // (fr_worker::sh_comm): fr_comm_destroy between a submit and its sync only drops the handle's reference, the communicator itself goes
     // when the last worker has synchronised (fr_comm_wait used to dereference a freed object in that sequence)
@@ -380,6 +423,30 @@ extern "C" int fr_comm_set_wait_ms(fr_comm *c, int wait_ms) {
     return FR_OK;
 }
 
+extern "C" int fr_comm_set_exchange(fr_comm *c, int exchange) {
+    if (!c) FR_FAIL(FR_ERR_INVALID, "comm is NULL");
+    if (exchange != FR_EXCHANGE_ALLGATHER && exchange != FR_EXCHANGE_ALLTOALL) FR_FAIL(FR_ERR_INVALID, "unknown exchange mode %d", exchange);
+    if (comm_is_broken(c)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
+    // refs > 1: a worker holds this communicator for a step it has not synchronised yet
+    if (c->refs.load(std::memory_order_acquire) > 1) FR_FAIL(FR_ERR_STATE, "a sharded step is in flight through this communicator: call fr_worker_sync first");
+    if (exchange == FR_EXCHANGE_ALLTOALL && c->comm && !g_rccl_p2p)
+        FR_FAIL(FR_ERR_COMM, "the all-to-all exchange needs ncclSend / ncclRecv / ncclGroupStart / ncclGroupEnd: librccl.so lacks at least one of them");
+    c->exchange.store(exchange, std::memory_order_release);
+    return FR_OK;
+}
+
+extern "C" int fr_comm_exchange(const fr_comm *c) {
+    if (!c) FR_FAIL(FR_ERR_INVALID, "comm is NULL");
+    return c->exchange.load(std::memory_order_acquire);
+}
+
+extern "C" int fr_comm_exchange_bytes(const fr_comm *c, uint64_t *received, uint64_t *sent) {
+    if (!c || !received || !sent) FR_FAIL(FR_ERR_INVALID, "NULL argument");
+    *received = c->x_received.load(std::memory_order_relaxed);
+    *sent = c->x_sent.load(std::memory_order_relaxed);
+    return FR_OK;
+}
+
 static void comm_release(fr_comm *c) {
     if (c->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
     if (c->comm && g_rccl_ok) {
@@ -488,6 +555,43 @@ static int step_all_gather(fr_worker *w, fr_comm *comm, const void *send, void *
     if (r != ncclSuccess) FR_FAIL(FR_ERR_COMM, "ncclAllGather(%zu bytes per rank) failed: %s", bytes, g_rccl.GetErrorString(r));
     return FR_OK;
 }
+// ONE all-to-all of the item-major slices ([batch][row] bytes per rank): rank r receives [G][n_r][row], the rows of its own items from every
+// rank in rank order -- the [n_shards][batch_total][P] layout of fr_worker_fc_from_slices(_lp) with batch_total = n_r, item0 = 0.  Rank q's
+// rows for rank r are contiguous in q's slice, so neither side packs anything.
+static int step_all_to_all(fr_worker *w, fr_comm *comm, const void *send, void *recv, int batch, size_t row) {
+    const int G = comm->n_ranks, r = comm->rank;
+    int lo_r, n_r;
+    item_range(batch, G, r, &lo_r, &n_r);
+    const size_t bytes = (size_t)batch * row, part = (size_t)n_r * row;
+    if (comm->grp) {
+        const void *h_send = send;
+        void *h_recv = recv;
+        if (!w->ctx->cpu) {   // staged: the whole slice comes off the device, only this rank's G parts go back
+            FR_HIP(hipMemcpyAsync(w->h_stage_send, send, bytes, hipMemcpyDeviceToHost, w->stream));
+            FR_HIP(hipStreamSynchronize(w->stream));
+            h_send = w->h_stage_send;
+            h_recv = w->h_stage_recv;
+        }
+        if (comm->grp->all_to_all(r, h_send, h_recv, bytes, row) != FR_OK)
+            FR_FAIL(FR_ERR_COMM, "host exchange: the all-to-all of %zu bytes per rank was aborted (a peer failed, never arrived, or sent another size or mode)", bytes);
+        if (!w->ctx->cpu && part) FR_HIP(hipMemcpyAsync(recv, w->h_stage_recv, part * (size_t)G, hipMemcpyHostToDevice, w->stream));
+        return FR_OK;
+    }
+    // zero-count transfers are skipped on both sides: rank q sends n_r rows to r exactly when r expects n_r rows from q
+    ncclResult_t r0 = g_rccl.GroupStart();
+    if (r0 != ncclSuccess) FR_FAIL(FR_ERR_COMM, "ncclGroupStart failed: %s", g_rccl.GetErrorString(r0));
+    ncclResult_t bad = ncclSuccess;
+    for (int q = 0; q < G && bad == ncclSuccess; q++) {
+        int lo_q, n_q;
+        item_range(batch, G, q, &lo_q, &n_q);
+        if (n_q > 0) bad = g_rccl.Send(static_cast<const char *>(send) + (size_t)lo_q * row, (size_t)n_q * row, ncclChar, q, comm->comm, w->stream);
+        if (bad == ncclSuccess && part) bad = g_rccl.Recv(static_cast<char *>(recv) + (size_t)q * part, part, ncclChar, q, comm->comm, w->stream);
+    }
+    const ncclResult_t end = g_rccl.GroupEnd();   // the group is closed whatever happened inside it
+    if (bad == ncclSuccess) bad = end;
+    if (bad != ncclSuccess) FR_FAIL(FR_ERR_COMM, "all-to-all (ncclSend / ncclRecv, %zu bytes per rank) failed: %s", bytes, g_rccl.GetErrorString(bad));
+    return FR_OK;
+}
 // -> 0 the step's stream is idle, 1 still working, < 0 the stream itself failed
 static int step_query(fr_worker *w) {
     if (w->sh_host_stream && !static_cast<HostStream *>(w->sh_host_stream)->done()) return 1;   // the step is still being issued (host exchange, plain or staged)
@@ -578,11 +682,11 @@ static int sharded_prologue(fr_worker *w, fr_comm *comm, int batch, const int32_
     return rc;
 }
 
-// THE STEP, on either transport: slice gather -> all-gather of the slices -> FC chain on this rank's items -> all-gather of the score
+// THE STEP, on either transport: slice gather -> all-gather (or all-to-all: `mode`) of the slices -> FC chain on this rank's items -> all-gather of the score
 // chunks (each followed by its rank's status word) -> every rank's pinned score buffer.  A GPU worker's fr_worker_submit_sharded calls it
 // inline (every line enqueues on the worker's stream); a host-exchange worker's (CPU, or staged GPU) posts it to the worker's host stream.  *enqueued is set once the
 // second collective is on its way: from then on fr_worker_sync has something to wait for, whatever this function returns.
-static int sharded_step(fr_worker *w, fr_comm *comm, int batch, bool *enqueued) {
+static int sharded_step(fr_worker *w, fr_comm *comm, int batch, int mode, bool *enqueued) {
     *enqueued = false;
     const int32_t *idx = nullptr;
     const float *dense = nullptr;
@@ -594,14 +698,20 @@ static int sharded_step(fr_worker *w, fr_comm *comm, int batch, bool *enqueued) 
     const size_t esz = transport == FR_FC_FP32 ? 4 : (transport == FR_FC_BF16 ? 2 : 1);
     rc = fr_worker_gather_slices(w, batch, idx, dense, w->d_slice, transport);
     if (rc) return comm_fail(comm, rc);
-    rc = step_all_gather(w, comm, w->d_slice, w->d_gathered, (size_t)batch * c->slice_padded * esz);
+    const size_t row = (size_t)c->slice_padded * esz;
+    const bool a2a = mode == FR_EXCHANGE_ALLTOALL;
+    rc = a2a ? step_all_to_all(w, comm, w->d_slice, w->d_gathered, batch, row) : step_all_gather(w, comm, w->d_slice, w->d_gathered, (size_t)batch * row);
     if (rc) return comm_fail(comm, rc);
     const int base = batch / G, rem = batch % G, chunk = base + (rem ? 1 : 0);
     const int lo = r * base + (r < rem ? r : rem), n_mine = base + (r < rem ? 1 : 0);
+    comm->x_received.store((uint64_t)(G - 1) * (uint64_t)(a2a ? n_mine : batch) * row, std::memory_order_relaxed);
+    comm->x_sent.store((a2a ? (uint64_t)(batch - n_mine) : (uint64_t)(G - 1) * (uint64_t)batch) * row, std::memory_order_relaxed);
     int fc_rc = FR_OK;
     if (n_mine > 0) {
         w->in_flight = false;  // fr_worker_fc_from_slices_lp is a public entry point with its own state checks
-        fc_rc = fr_worker_fc_from_slices_lp(w, batch, lo, n_mine, w->d_gathered, transport, w->d_score_part);
+        // all-to-all: d_gathered holds only this rank's items ([G][n_mine][P]), so they are items [0, n_mine) of a batch of n_mine
+        fc_rc = a2a ? fr_worker_fc_from_slices_lp(w, n_mine, 0, n_mine, w->d_gathered, transport, w->d_score_part)
+                    : fr_worker_fc_from_slices_lp(w, batch, lo, n_mine, w->d_gathered, transport, w->d_score_part);
         const int inject = FR_KNOB("SHARDED_INJECT_FC_FAIL", 0);   // experiments build only: the test of kind (2).  1 = every rank, 2 + q = rank q only
         if (!fc_rc && (inject == 1 || inject == 2 + r)) {
             fr_set_error("injected FC failure (FR_SHARDED_INJECT_FC_FAIL)");
@@ -645,16 +755,17 @@ extern "C" int fr_worker_submit_sharded(fr_worker *w, fr_comm *comm, int batch) 
     int rc = sharded_check_args(w, comm, batch);  // kind (1): returned as it is
     if (rc) return rc;
     w->sh_comm = comm;  // fr_worker_sync waits through fr_comm_wait and reads the G status words
-    comm->refs.fetch_add(1, std::memory_order_relaxed);
+    comm->refs.fetch_add(1, std::memory_order_acq_rel);   // (also what fr_comm_set_exchange reads as "a step in flight")
+    const int mode = comm->exchange.load(std::memory_order_acquire);
     if (comm->grp) {   // the host exchange (CPU worker, or staged GPU worker): the step runs behind this call on the worker's host stream -- its rendezvous blocks
-        host_stream(w)->post([w, comm, batch] {
+        host_stream(w)->post([w, comm, batch, mode] {
             bool enqueued = false;
-            return sharded_step(w, comm, batch, &enqueued);
+            return sharded_step(w, comm, batch, mode, &enqueued);
         });
         return FR_OK;
     }
     bool enqueued = false;
-    rc = sharded_step(w, comm, batch, &enqueued);
+    rc = sharded_step(w, comm, batch, mode, &enqueued);
     if (!enqueued) fr_comm_forget(w);   // kind (3) before the second collective: the communicator is aborted, there is no step to wait for
     return rc;
 }

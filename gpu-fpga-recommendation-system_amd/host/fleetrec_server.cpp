@@ -13,12 +13,13 @@
 // Usage: fleetrec_server --model A|B|C [--batch 256] [--threads 4] [--port 8080] [--total 1024] [--device 0]
 //        [--stream [--reply [--flush-us 50] [--flush-min 32]]]: streaming with score replies and adaptive batching -- see thread_consume
 //                        [--tables evenodd|hash] [--weights ones|uniform] [--per-item | --per-bank] [--reply] [--row-cap N]
-//                        [--shards G [--one-device] [--precision f32|bf16|fp8]]
+//                        [--shards G [--one-device] [--precision f32|bf16|fp8] [--exchange allgather|alltoall]]
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
 // all-gathered over RCCL, FC on batch / G items per GPU, scores all-gathered).  The counterpart of the 3-node server, whose batch
-// arrives in three parts from three senders (3-node cuda_server.c:513-591).
+// arrives in three parts from three senders (3-node cuda_server.c:513-591).  --exchange alltoall: every shard receives only the rows of
+// its own batch / G items from each shard (fr_comm_set_exchange; 1/G of the all-gather's bytes, the same scores).
 #include <arpa/inet.h>
 #include <netinet/in.h>
 #include <netinet/tcp.h>
@@ -50,6 +51,8 @@ struct Options {
     int shards = 0;            // > 0: table-sharded over `shards` GPUs
     bool one_device = false;   // --shards G --one-device: all G shard contexts on GPU `device` (the library's staged host exchange: a G-rank job rehearsed on one GPU)
     int precision = FR_FC_FP32;
+    int exchange = FR_EXCHANGE_ALLGATHER;   // --shards: how the slices travel (fr_comm_set_exchange)
+    bool exchange_given = false;
     bool stream = false;   // throughput mode: fr_worker_push_host (blocks of batches per launch) instead of submit + sync per batch
     long flush_us = 50;    // --stream --reply: how long the socket must stay dry before a partial block is launched
     int flush_min = 32;    // ... while earlier blocks are still in flight: only once this many requests are queued (with nothing in flight: any number)
@@ -416,8 +419,15 @@ int main(int argc, char **argv) {
         else if (a == "--flush-min") o.flush_min = atoi(next());
         else if (a == "--small-block") o.small_block = atoi(next());
         else if (a == "--row-cap") o.row_cap = atol(next());
+        else if (a == "--exchange") {
+            std::string v = next();
+            if (v != "allgather" && v != "alltoall") { fprintf(stderr, "--exchange: allgather or alltoall, not '%s'\n", v.c_str()); return 2; }
+            o.exchange = v == "alltoall" ? FR_EXCHANGE_ALLTOALL : FR_EXCHANGE_ALLGATHER;
+            o.exchange_given = true;
+        }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (o.exchange_given && o.shards <= 0) { fprintf(stderr, "--exchange needs --shards G\n"); return 2; }
     printf("HIP devices visible: %d\n", fr_device_count());  // device probe of cuda_server.c:508-522
     fr_model_desc *model = nullptr;
     if (fr_model_clone_scaled(fr_model_builtin(o.model), 1.0, 1, o.row_cap, &model) != FR_OK) { fprintf(stderr, "%s\n", fr_last_error()); return 1; }
@@ -444,14 +454,20 @@ int main(int argc, char **argv) {
             fprintf(stderr, "exchange set-up failed: %s\n", fr_last_error());
             return 1;
         }
+        for (int r = 0; r < o.shards; r++)
+            if (fr_comm_set_exchange(engine.comms[r], o.exchange) != FR_OK) {
+                fprintf(stderr, "exchange mode of shard %d: %s\n", r, fr_last_error());
+                return 1;
+            }
         engine.idx_bytes = (size_t)o.batch * (size_t)fr_model_index_cols(model) * sizeof(int32_t);
         engine.dense_bytes = (size_t)o.batch * model->dense_len * sizeof(float);
         for (int r = 0; r < o.shards; r++) engine.threads.emplace_back(&ShardedEngine::shard_loop, &engine, r);
         g_engine = &engine;
         ctx = engine.ctxs[0];
-        if (o.device < 0) printf("table-sharded over %d CPU shard contexts (in-process host exchange of the looked-up slices)\n", o.shards);
-        else if (o.one_device) printf("table-sharded over %d shard contexts on GPU %d (staged host exchange of the looked-up slices)\n", o.shards, o.device);
-        else printf("table-sharded over %d GPUs (RCCL all-gather of the looked-up slices)\n", o.shards);
+        const bool a2a = o.exchange == FR_EXCHANGE_ALLTOALL;
+        if (o.device < 0) printf("table-sharded over %d CPU shard contexts (in-process host %s of the looked-up slices)\n", o.shards, a2a ? "all-to-all" : "exchange");
+        else if (o.one_device) printf("table-sharded over %d shard contexts on GPU %d (staged host %s of the looked-up slices)\n", o.shards, o.device, a2a ? "all-to-all" : "exchange");
+        else printf("table-sharded over %d GPUs (RCCL %s of the looked-up slices)\n", o.shards, a2a ? "all-to-all" : "all-gather");
     } else if (fr_ctx_create(model, o.device, &ctx) != FR_OK || fr_ctx_fill_tables(ctx, o.tables, 0xF1EE7) != FR_OK ||
                fr_ctx_fill_weights(ctx, o.weights, 99) != FR_OK || fr_ctx_set_fc_precision(ctx, o.precision) != FR_OK) {
         fprintf(stderr, "set-up failed: %s\n", fr_last_error());

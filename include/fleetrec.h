@@ -35,7 +35,9 @@ extern "C" {
 
 /* 6 (round 6): fr_comm_init_all over CPU shard contexts = the in-process host exchange (the table-sharded step with G > 1 ranks without G GPUs);
  * fleetrec_diag.h gains fr_worker_inject_fc_failure, fr_ctx_set_lp_bank_image / fr_ctx_lp_bank_image_bytes (the operand-type bank image);
- * fr_ctx_set_fc_precision / fr_worker_create may succeed with a "note:" in fr_last_error().
+ * fr_ctx_set_fc_precision / fr_worker_create may succeed with a "note:" in fr_last_error().  Still 6, additive: the exchange mode of the
+ * table-sharded step (fr_exchange; fleetrec_serving.h fr_comm_set_exchange / fr_comm_exchange; fleetrec_diag.h fr_comm_exchange_bytes) -- the
+ * default all-gather is the step as before.
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile
  * shape of a chain model no longer follows the number of live workers).
  * 4 (round 4): the surface is three headers -- this one (the three spans of thread_consume() that SURVEY section 8(b) cuts, the request
@@ -410,10 +412,23 @@ void fr_comm_destroy(fr_comm *c);
  * stream is polled together with ncclCommGetAsyncError; past the bound the rank aborts its communicator and returns FR_ERR_COMM (from
  * then on for every call).  The reference blocks in read() for ever when a sender dies (3-node cuda_server.c:513-591). */
 int fr_comm_set_wait_ms(fr_comm *c, int wait_ms);
+/* Exchange mode of the slices (the first collective of fr_worker_submit_sharded):
+ *  ALLGATHER (default): every rank receives every rank's whole [batch x F] slice -- (G - 1) * batch * F elements per rank and step, of which
+ *                       the rank's FC chain reads its own batch / G items;
+ *  ALLTOALL           : rank r receives from every rank q only the rows of r's own items [lo_r, lo_r + n_r) of q's slice (the uneven split
+ *                       of the step: n_r = batch / G, + 1 for r < batch % G) -- (G - 1) * n_r * F elements.  RCCL: grouped ncclSend /
+ *                       ncclRecv; host exchange (plain or staged): each rank copies only its rows of every peer's slice.
+ * Scores are bit-identical in both modes (the same gather, transpose and FC kernels read the same elements).  The score exchange and
+ * fr_worker_calibrate_fp8_sharded are all-gathers in both modes.  Selected per communicator handle with fr_comm_set_exchange / read back with
+ * fr_comm_exchange (fleetrec_serving.h: this header keeps to the boundary's own entry points); fleetrec_diag.h fr_comm_exchange_bytes counts
+ * the bytes of the last step. */
+typedef enum fr_exchange { FR_EXCHANGE_ALLGATHER = 0, FR_EXCHANGE_ALLTOALL = 1 } fr_exchange;
 /* COLLECTIVE, asynchronous on the worker's stream: every rank holds the whole request batch in its worker's pinned idx / dense
  * buffers (as for fr_worker_submit).  Per rank: H2D -> gather of this shard's slice (in the chain's operand type: fp32, bf16 or e4m3)
- * -> ncclAllGather of the [batch x F] slices over xGMI -> FC chain on this rank's batch / G items -> ncclAllGather of the score
- * chunks -> D2H.  After fr_worker_sync() EVERY rank's fr_worker_score_ptr() holds all `batch` scores.  RCCL failures: FR_ERR_COMM.
+ * -> exchange of the slices over xGMI (fr_comm_set_exchange: ALLGATHER = ncclAllGather of the [batch x F] slices, every rank receives all
+ * of them; ALLTOALL = grouped ncclSend / ncclRecv, rank r receives only the [n_r x F] rows of its own items from every rank) -> FC chain on
+ * this rank's batch / G items -> ncclAllGather of the score chunks (both modes) -> D2H.  After fr_worker_sync() EVERY rank's
+ * fr_worker_score_ptr() holds all `batch` scores.  RCCL failures: FR_ERR_COMM.
  * Failure protocol: argument / state errors are returned before anything is enqueued and leave the communicator usable (the ranks of a job
  * are driven with the same arguments); a rank whose FC chain fails still takes part in both collectives, its score chunk travels as NaN
  * and its status word (one float all-gathered behind every chunk) makes EVERY rank's fr_worker_sync return FR_ERR_COMM naming it; a
@@ -425,7 +440,8 @@ int fr_comm_set_wait_ms(fr_comm *c, int wait_ms);
  * fr_worker_sync is safe: the worker keeps the communicator alive until it has synchronised. */
 int fr_worker_submit_sharded(fr_worker *w, fr_comm *comm, int batch);
 /* COLLECTIVE, synchronous: fp8 activation exponents of a sharded context from this batch -- every rank calibrates on the same
- * all-gathered fp32 slices, so all ranks end with identical exponents (a slice encoded by one rank is decoded by the others). */
+ * all-gathered fp32 slices, so all ranks end with identical exponents (a slice encoded by one rank is decoded by the others).  An
+ * all-gather in either exchange mode: every rank must see the WHOLE batch to reach the same exponents. */
 int fr_worker_calibrate_fp8_sharded(fr_worker *w, fr_comm *comm, int batch);
 
 #if defined(__GNUC__)

@@ -79,6 +79,12 @@ size_t fr_ctx_lp_bank_image_bytes(const fr_ctx *ctx);
  * ThreadSanitizer); nothing else reads the counter. */
 int fr_worker_inject_fc_failure(fr_worker *w, int steps);
 
+/* slice-exchange bytes of the last step this rank issued, peers only (own block excluded).
+ * Counted from what fr_worker_submit_sharded enqueued (not measured), P = slice_padded, esz = 4 / 2 / 1 (fp32 / bf16 / e4m3 transport):
+ * ALLGATHER received = sent = (G - 1) * batch * P * esz; ALLTOALL received = (G - 1) * n_r * P * esz, sent = (batch - n_r) * P * esz.
+ * The score chunks and fr_worker_calibrate_fp8_sharded are not counted.  0 / 0 before the first step. */
+int fr_comm_exchange_bytes(const fr_comm *c, uint64_t *received, uint64_t *sent);
+
 /* HIP-event timing on the worker's stream (the stream the kernels are launched on). */
 int fr_worker_timer_start(fr_worker *w);
 int fr_worker_timer_stop_ms(fr_worker *w, float *ms); /* records stop, synchronises, returns elapsed */

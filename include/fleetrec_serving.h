@@ -70,6 +70,14 @@ int fr_driver_run_host_streaming(fr_driver *d, int batch, int64_t total_batches,
                                  const float *const *h_dense_pool, int n_pool, double *elapsed_s);
 const float *fr_driver_host_score_ring(fr_driver *d, int thread, int slot, int *ring_len);
 
+/* Exchange mode of a table-sharded communicator (fr_exchange, fleetrec.h): how fr_worker_submit_sharded ships the slices.  Set between
+ * steps, the same mode on every rank of the communicator: FR_ERR_INVALID for an unknown mode, FR_ERR_STATE while a step is in flight
+ * through this handle (submitted, not yet synchronised), FR_ERR_COMM on a broken communicator or -- ALLTOALL over RCCL -- a librccl.so
+ * without ncclSend / ncclRecv / ncclGroupStart / ncclGroupEnd.  Ranks of a host exchange whose modes disagree break the group: every rank's
+ * fr_worker_sync returns FR_ERR_COMM (over RCCL such a job does not match its collectives: the bounded wait of fr_worker_sync ends it). */
+int fr_comm_set_exchange(fr_comm *c, int exchange);   /* between steps; every rank of the communicator sets the same mode */
+int fr_comm_exchange(const fr_comm *c);               /* the current mode (FR_EXCHANGE_ALLGATHER after init) */
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
