@@ -1,0 +1,218 @@
+"""The integer-valued exact-chain data (tests/exact_chain.py) on a machine without a GPU: the exactness premise holds for every case of the
+GPU matrix, the CPU back-end matches the exact reference bit for bit, the exact comparison rejects simulated kernel bugs that the old
+max-norm tolerances let through, and every FC-chain kernel compiled into libfleetrec.so is either named by a GPU-matrix case or listed
+as unreachable."""
+import os
+import shutil
+import sys
+
+import numpy as np
+import pytest
+
+import exact_chain as E
+from gpu_helpers import ROOT, bf16_round, e4m3_decode_table, e4m3_encode
+
+_CACHE = {}
+
+
+def _case_rec(fr, case, n=None):
+    key = (case["id"], n)
+    if key not in _CACHE:
+        sp, data, idx, dense = E.case_data(case, n or min(case["batch"], 512))
+        m = fr.Model.from_spec(sp)
+        _CACHE[key] = (m, data, idx, dense, E.records(m, data, idx, dense))
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("case", E.CASES, ids=[c["id"] for c in E.CASES])
+def test_premise_holds_for_every_gpu_case(fr, case):
+    """Every product a multiple of the layer's quantum, every sum of |products| below 2^24 quanta; the low-precision chains round (and
+    meet exact ties) in every hidden layer; exponents and scores are deterministic."""
+    m, data, idx, dense, rec = _case_rec(fr, case)
+    ws = data["ws"]
+    assert m.record_len == data["fc"][0] and list(m.fc) == data["fc"]
+    for l in range(4):   # every k row and every output column of every layer has a nonzero weight
+        assert (ws[l] != 0).any(axis=1).all() and (ws[l] != 0).any(axis=0).all()
+    ae = we = None
+    if case["prec"] == "fp8":
+        ae, we = E.act_exponents(rec, ws), E.w_exponents(ws)
+        assert we == [7, 7, 7]
+        for l, a in enumerate(E.fp32_acts(rec, ws)[0]):   # max|act| * 2^e lands in (112, 224]: one binade of headroom below 448
+            assert 112.0 < np.abs(a).max() * 2.0 ** ae[l] <= 224.0
+    E.premise(case["prec"], rec, ws, ae, we)
+    if case["prec"] != "f32":
+        for l, (inexact, ties) in enumerate(E.rounding_witnesses(case["prec"], rec, ws, ae, we)):
+            assert inexact > 0 and ties > 0, (case["id"], l, inexact, ties)
+    s1 = E.expected(case["prec"], rec, ws, ae, we)
+    sp, data2, idx2, dense2 = E.case_data(case, idx.shape[0])
+    assert np.array_equal(idx2, idx) and all(np.array_equal(a, b) for a, b in zip(data2["ws"], ws))
+    assert np.array_equal(E.expected(case["prec"], E.records(m, data2, idx2, dense2), data2["ws"], ae, we), s1)
+    assert np.isfinite(s1).all() and np.unique(s1).size > s1.size // 4
+
+
+@pytest.mark.parametrize("case_id", ["f32-A352-g16", "f32-C-b200", "f32-N192-5500", "f32-G256"])
+def test_cpu_backend_bit_exact(fr, O, case_id):
+    """The library's CPU back-end (fp32) on the exact data: every item bit for bit, and the oracle's fp64-accumulating chain agrees."""
+    case = next(c for c in E.CASES if c["id"] == case_id)
+    m, data, idx, dense, rec = _case_rec(fr, case, 96)
+    want = E.expected("f32", rec, data["ws"])
+    ctx = fr.Context(m, device=fr.DEVICE_CPU)
+    try:
+        E.load(ctx, data)
+        wk = fr.Worker(ctx, idx.shape[0])
+        got = wk.infer(idx, dense)
+        assert np.array_equal(got, want)
+        assert np.array_equal(wk.fc_scores(rec), want)
+        wk.close()
+    finally:
+        ctx.close()
+    assert np.array_equal(O.OracleModel("A").fc_chain(rec, [w.ravel() for w in data["ws"]], acc64=True, dims=data["fc"]), want)
+
+
+# ---- mutants: known kernel bugs restated in numpy ------------------------------------------------------------------------------------
+
+def _bf16_chain(rec, ws, x_hook=None, r_hook=None, w_hook=None, round3=True):
+    x = bf16_round(rec).astype(np.float64)
+    if x_hook:
+        x = x_hook(x)
+    for l in range(3):
+        W = bf16_round(ws[l]).astype(np.float64)
+        if w_hook:
+            W = w_hook(l, W)
+        r = (x @ W).astype(np.float32)
+        if r_hook:
+            r = r_hook(l, r)
+        x = (bf16_round(r) if (l < 2 or round3) else r).astype(np.float64)
+    return (x @ bf16_round(ws[3]).astype(np.float64)).astype(np.float32).ravel()
+
+
+def _fp8_chain(rec, ws, ae, we, q_hook=None):
+    dec = e4m3_decode_table()
+    x = dec[e4m3_encode(rec * np.float32(2.0 ** ae[0]))]
+    for l in range(3):
+        Wf = dec[e4m3_encode(ws[l] * np.float32(2.0 ** we[l]))]
+        r = ((x @ Wf) * 2.0 ** -(ae[l] + we[l])).astype(np.float32)
+        x = dec[e4m3_encode(r * np.float32(2.0 ** ae[l + 1]))]
+        if q_hook:
+            x = q_hook(l, x)
+    return ((x * 2.0 ** -ae[3]) @ ws[3].astype(np.float64)).astype(np.float32).ravel()
+
+
+def _drop_kgroup(x):
+    x = x.copy()
+    x[-32:, 8:16] = 0.0          # FC1's k-group 1 missing for the last 32-item tile
+    return x
+
+
+def _wrong_column(l, r):
+    if l == 0:
+        r = r.copy()
+        r[:, 3] += np.float32(1.0)   # one hidden output column off by one unit
+    return r
+
+
+def _swap_k(l, W):
+    if l == 0:
+        W = W.copy()
+        col = 5
+        nz = np.flatnonzero(W[:, col])
+        k1 = nz[0]
+        k2 = next(k for k in range(W.shape[0]) if W[k, col] != W[k1, col])
+        W[[k1, k2], col] = W[[k2, k1], col]
+    return W
+
+
+def _saturate_one(l, x):
+    if l == 1:
+        x = x.copy()
+        i, j = np.unravel_index(np.argmax(np.abs(x) * (np.abs(x) < 448)), x.shape)
+        x[i, j] = 448.0 * np.sign(x[i, j])   # one R2 value clamped to the e4m3 maximum
+    return x
+
+
+MUTANTS = {
+    "FC1 k-group dropped (last 32-item tile)": ("bf16", lambda rec, ws, ae, we: _bf16_chain(rec, ws, x_hook=_drop_kgroup)),
+    "one FC1 output column off by one": ("bf16", lambda rec, ws, ae, we: _bf16_chain(rec, ws, r_hook=_wrong_column)),
+    "FC3 not rounded to bf16": ("bf16", lambda rec, ws, ae, we: _bf16_chain(rec, ws, round3=False)),
+    "two k swapped in one W1 column": ("bf16", lambda rec, ws, ae, we: _bf16_chain(rec, ws, w_hook=_swap_k)),
+    "one fp8 R2 value saturated": ("fp8", lambda rec, ws, ae, we: _fp8_chain(rec, ws, ae, we, q_hook=_saturate_one)),
+}
+
+
+@pytest.mark.parametrize("name", list(MUTANTS))
+def test_exact_comparison_rejects_mutant(fr, name):
+    """Each simulated bug changes at least one score of the Model-C-shaped case data, so the bit-exact comparison rejects it; its max-norm
+    error is printed next to the tolerance the precision's score tests allow (the mutant table of the change's description)."""
+    prec, fn = MUTANTS[name]
+    case = next(c for c in E.CASES if c["id"] == "%s-C-b65" % prec)
+    m, data, idx, dense, rec = _case_rec(fr, case, 256)
+    ws = data["ws"]
+    ae, we = (E.act_exponents(rec, ws), E.w_exponents(ws)) if prec == "fp8" else (None, None)
+    want = E.expected(prec, rec, ws, ae, we)
+    bad = fn(rec, ws, ae, we)
+    assert not np.array_equal(bad, want), name
+    err = float(np.abs(bad.astype(np.float64) - want).max() / np.abs(want).max())
+    print("mutant %-42s %-4s items changed %4d  max-norm err %.2e  old tolerance %.0e  %s" % (
+        name, prec, int((bad != want).sum()), err, E.OLD_TOL[prec], "caught" if err > E.OLD_TOL[prec] else "MISSED by the tolerance"))
+
+
+def test_exponent_check_rejects_act_exp2_off_by_one(fr):
+    """A calibration that measures R2 without the binade of headroom (act_exp[2] one too large) returns an exponent vector that differs
+    from the predicted one, which the GPU tests compare with ctx.fp8_exponents() item for item.  Its scores alone would not show it: a
+    power-of-two scale one binade off changes no e4m3 rounding short of saturation or subnormals (printed below)."""
+    case = next(c for c in E.CASES if c["id"] == "fp8-C-b65")
+    m, data, idx, dense, rec = _case_rec(fr, case, 256)
+    ws = data["ws"]
+    ae, we = E.act_exponents(rec, ws), E.w_exponents(ws)
+    r2 = E.fp32_acts(rec, ws)[0][2]
+    bad_ae = list(ae)
+    bad_ae[2] = E.floor_log2_f32(np.float32(448.0) / np.float32(np.abs(r2).max()))
+    assert bad_ae != ae, (bad_ae, ae)
+    want, bad = E.expected("fp8", rec, ws, ae, we), _fp8_chain(rec, ws, bad_ae, we)
+    print("mutant %-42s fp8  items changed %4d  (exponents %s for %s)" % ("act_exp[2] off by one", int((bad != want).sum()), bad_ae, ae))
+
+
+def test_mutant_restatements_match_the_reference(fr):
+    """The mutants' chain restatements without a mutation are the exact reference (so a rejected mutant is rejected for its bug)."""
+    for prec in ("bf16", "fp8"):
+        case = next(c for c in E.CASES if c["id"] == "%s-C-b65" % prec)
+        m, data, idx, dense, rec = _case_rec(fr, case, 256)
+        ws = data["ws"]
+        if prec == "bf16":
+            assert np.array_equal(_bf16_chain(rec, ws), E.expected("bf16", rec, ws))
+        else:
+            ae, we = E.act_exponents(rec, ws), E.w_exponents(ws)
+            assert np.array_equal(_fp8_chain(rec, ws, ae, we), E.expected("fp8", rec, ws, ae, we))
+
+
+# ---- kernel completeness -------------------------------------------------------------------------------------------------------------
+
+def _fc_chain_kernels(fr):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import kernel_resources as KR
+    finally:
+        sys.path.pop(0)
+    if not (os.path.exists(KR.READELF) or shutil.which("llvm-readelf")):
+        pytest.skip("llvm-readelf not available")
+    names = {E.demangle(r["name"]) for r in KR.kernel_records(fr.LIB_PATH)}
+    if not names:
+        pytest.skip("no gfx950 code objects found in %s" % fr.LIB_PATH)
+    return {n for n in names if n.startswith(("fr_fused_tile", "fr_pipeline_kernel")) or (n.startswith("fc_") and "gemm" in n)}
+
+
+def test_every_fc_chain_kernel_is_accounted_for(fr):
+    """Each FC-chain kernel of libfleetrec.so is named by a GPU-matrix case or listed in UNREACHABLE with a reason -- and nothing else is."""
+    lib = _fc_chain_kernels(fr)
+    named = E.named_kernels()
+    assert not (named & set(E.UNREACHABLE)), sorted(named & set(E.UNREACHABLE))
+    assert sorted(lib - named - set(E.UNREACHABLE)) == [], "FC-chain kernels no GPU-matrix case names"
+    assert sorted((named | set(E.UNREACHABLE)) - lib) == [], "names the library does not contain"
+    assert all(E.UNREACHABLE.values())
+
+
+def test_demangle():
+    assert E.demangle("_Z17fc_lp_gemm_kernelILi0ELi1ELi128ELi2ELi8ELi32EEvPK15HIP_vector_typeIjLj4EES3_Pviiiiif") == "fc_lp_gemm_kernel<0, 1, 128, 2, 8, 32>"
+    assert E.demangle("_Z18fr_pipeline_kernelILin1ELi2EEv10FrPipeArgs") == "fr_pipeline_kernel<-1, 2>"
+    assert E.demangle("_Z20fr_fused_tile_kernelILi2ELi44ELi2ELb1EEv11FrFusedArgs") == "fr_fused_tile_kernel<2, 44, 2, true>"
+    assert E.demangle("void fr_pipeline_kernel<-1, 0>(FrPipeArgs)") == "fr_pipeline_kernel<-1, 0>"
