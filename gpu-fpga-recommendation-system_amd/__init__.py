@@ -27,6 +27,7 @@ INDEX_PER_TABLE, INDEX_PER_ITEM, INDEX_PER_BANK = 0, 1, 2
 SEG_TABLE, SEG_COPY, SEG_DENSE = 0, 1, 2
 GATHER_WORD_MAJOR, GATHER_ITEM_TILE, GATHER_ITEM_TILE_DEDUP, GATHER_ITEM_TILE_DEDUP_COUNT, GATHER_WORD_MAJOR_ONE_CHUNK = 0, 1, 2, 3, 4
 EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step's slices travel (Comm.set_exchange)
+POOL_MAX_HOTS = 64   # FR_POOL_MAX_HOTS (fleetrec_serving.h): slots per bag of a pooled lookup
 ABI_VERSION = 6   # include/fleetrec.h FR_ABI_VERSION this binding was written against
 MEM_CLASS_NAMES = {0: "HBM", 1: "DDR", 2: "PLRAM"}
 
@@ -72,6 +73,7 @@ ABI_SYMBOLS = [
     "fr_device_synchronize", "fr_ctx_shard_info", "fr_driver_create", "fr_driver_destroy", "fr_driver_run_resident",
     "fr_driver_worker", "fr_driver_score_ring", "fr_driver_run_host", "fr_driver_run_host_streaming", "fr_driver_host_score_ring", "fr_ctx_stream_group", "fr_ctx_set_stream_group", "fr_model_shard_plan", "fr_worker_fc_from_slices", "fr_worker_last_kernel", "fr_worker_inject_fc_failure", "fr_ctx_set_lp_bank_image", "fr_ctx_lp_bank_image_bytes",
     "fr_comm_set_exchange", "fr_comm_exchange", "fr_comm_exchange_bytes",
+    "fr_ctx_set_pooling", "fr_ctx_pooled_index_cols", "fr_worker_gather_pooled", "fr_worker_submit_pooled_device", "fr_worker_submit_pooled",
 ]
 
 
@@ -138,6 +140,9 @@ def lib():
         "fr_ctx_set_lp_bank_image": (i32, [vp, i32]), "fr_ctx_lp_bank_image_bytes": (ctypes.c_size_t, [vp]),
         "fr_comm_set_exchange": (i32, [vp, i32]), "fr_comm_exchange": (i32, [vp]),
         "fr_comm_exchange_bytes": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
+        "fr_ctx_set_pooling": (i32, [vp, pi, i32]), "fr_ctx_pooled_index_cols": (i32, [vp]),
+        "fr_worker_gather_pooled": (i32, [vp, i32, vp, vp, vp]), "fr_worker_submit_pooled_device": (i32, [vp, i32, vp, vp, vp]),
+        "fr_worker_submit_pooled": (i32, [vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -514,6 +519,21 @@ class Context:
         _check(lib().fr_ctx_gather_merged_lookups(self._h, ctypes.byref(v), 1 if reset else 0))
         return v.value
 
+    def set_pooling(self, hots):
+        """Multi-hot pooled lookups (fr_ctx_set_pooling): hots[c] = slots (1..POOL_MAX_HOTS) of index column c, for every index column
+        of the model's index mode; None clears.  The pooled index row of an item is int32 [sum(hots)], column by column, slot-minor;
+        a slot of -1 is empty; a bag is summed in fp32 in slot order."""
+        if hots is None:
+            _check(lib().fr_ctx_set_pooling(self._h, None, 0))
+            return
+        h = np.ascontiguousarray(np.asarray(hots, dtype=np.int32).ravel())
+        _check(lib().fr_ctx_set_pooling(self._h, h.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(h.size)))
+
+    @property
+    def pooled_index_cols(self):
+        """P = sum of hots: int32 columns of one item's pooled index row; 0 when no pooling is set."""
+        return int(lib().fr_ctx_pooled_index_cols(self._h))
+
     def synchronize(self):
         _check(lib().fr_device_synchronize(self._h))
 
@@ -534,6 +554,7 @@ class Worker:
         self.score = np.ctypeslib.as_array(lib().fr_worker_score_ptr(h), shape=(max_batch,))
         self.dense = (np.ctypeslib.as_array(lib().fr_worker_dense_ptr(h), shape=(max_batch, m.dense_len))
                       if m.dense_len else None)
+        self._pool_cap = max(m.idx_cols, ctx.pooled_index_cols)   # int32 columns per item the pinned index buffer holds
 
     def close(self):
         if self._h:
@@ -727,6 +748,57 @@ class Worker:
         ms = ctypes.c_float()
         _check(lib().fr_worker_timer_stop_ms(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # multi-hot pooled lookups (Context.set_pooling) ------------------------------------------------
+    def gather_pooled(self, batch, d_idx, d_dense, d_records):
+        """d_idx int32 [batch][ctx.pooled_index_cols] -> fp32 records in the model's layout (asynchronous; follow with sync())."""
+        _check(lib().fr_worker_gather_pooled(self._h, batch, self._ptr(d_idx), self._ptr(d_dense), self._ptr(d_records)))
+
+    def submit_pooled_device(self, batch, d_idx, d_dense, d_scores):
+        _check(lib().fr_worker_submit_pooled_device(self._h, batch, self._ptr(d_idx), self._ptr(d_dense), self._ptr(d_scores)))
+
+    def submit_pooled(self, batch):
+        """fr_worker_submit_pooled on the pooled rows already in the pinned index buffer (asynchronous; follow with sync())."""
+        _check(lib().fr_worker_submit_pooled(self._h, int(batch)))
+
+    def _pooled_rows(self, idx):
+        P = self.ctx.pooled_index_cols
+        if P <= 0:
+            raise FleetRecError(FR_ERR_STATE, "no pooling is set on the context: call Context.set_pooling first")
+        idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(len(idx), -1))
+        if idx.shape[1] != P:
+            raise FleetRecError(FR_ERR_INVALID, "pooled index rows have %d columns, the context's pooling needs %d" % (idx.shape[1], P))
+        return idx
+
+    def infer_pooled(self, idx, dense=None):
+        """Host-buffer path of the pooled lookup: idx int32 [B][pooled_index_cols] (-1 = empty slot) (+ dense) -> scores float32 [B].
+        The worker must have been created after Context.set_pooling (its pinned index buffer is sized then)."""
+        idx = self._pooled_rows(idx)
+        B, P = idx.shape
+        if P > self._pool_cap:
+            raise FleetRecError(FR_ERR_STATE, "the worker's index buffer holds %d columns per item, pooled rows have %d: create the worker "
+                                "after Context.set_pooling" % (self._pool_cap, P))
+        if B > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(B, P))[:] = idx
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        self.submit_pooled(B)
+        self.sync()
+        return self.score[:B].copy()
+
+    def gather_pooled_records(self, idx, dense=None):
+        """-> uint32 [flat B*K] record buffer in the model's layout: the pooled records of idx int32 [B][pooled_index_cols]."""
+        ctx, m = self.ctx, self.ctx.model
+        idx = self._pooled_rows(idx)
+        B = idx.shape[0]
+        d_idx = DeviceBuffer.from_numpy(ctx, idx)
+        d_dense = DeviceBuffer.from_numpy(ctx, np.asarray(dense, dtype=np.float32)) if m.dense_len else None
+        n = B * m.record_len
+        d_rec = DeviceBuffer(ctx, n * 4)
+        self.gather_pooled(B, d_idx, d_dense, d_rec)
+        self.sync()
+        return d_rec.download(np.uint32, n)
 
     # convenience used by the parity tests --------------------------------------------------------
     def gather_records(self, idx, dense=None):

@@ -102,6 +102,7 @@ static void ctx_free(fr_ctx *c) {
     if (c->d_passes) (void)hipFree(c->d_passes);
     if (c->d_chunks) (void)hipFree(c->d_chunks);
     if (c->d_merged) (void)hipFree(c->d_merged);
+    if (c->d_pool) (void)hipFree(c->d_pool);
     for (int i = 0; i < 4; i++) {
         if (c->d_w[i]) (void)hipFree(c->d_w[i]);
         if (i < 3 && c->d_wq[i]) (void)hipFree(c->d_wq[i]);
@@ -757,8 +758,23 @@ extern "C" int fr_ctx_set_fc_precision(fr_ctx *ctx, int precision) {
 }
 
 // ---- worker -----------------------------------------------------------------------------------------
+// the context's list of live workers (fr_ctx_set_pooling asks each whether it has work in flight)
+static void ctx_enlist(fr_ctx *c, fr_worker *w) {
+    std::lock_guard<std::mutex> g(c->workers_mutex);
+    c->workers.push_back(w);
+}
+static void ctx_delist(fr_ctx *c, fr_worker *w) {
+    std::lock_guard<std::mutex> g(c->workers_mutex);
+    for (size_t i = 0; i < c->workers.size(); i++)
+        if (c->workers[i] == w) {
+            c->workers.erase(c->workers.begin() + (long)i);
+            break;
+        }
+}
+
 extern "C" void fr_worker_destroy(fr_worker *w) {
     if (!w) return;
+    if (w->ctx && w->counted) ctx_delist(w->ctx, w);
     if (w->ctx && w->ctx->cpu) {
         fr_comm_worker_release(w);   // a sharded step still on the worker's host stream: waited for (bounded), its communicator let go
         if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
@@ -847,9 +863,11 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     w->max_batch = max_batch;
     const fr_model_desc &m = ctx->model;
     const size_t B = (size_t)max_batch;
+    // the index buffers hold one-hot rows and, when pooling is set already, pooled rows (fr_worker_submit_pooled)
+    w->idx_cap = (int)idx_cols(ctx) > ctx->pool_cols ? (int)idx_cols(ctx) : ctx->pool_cols;
     if (ctx->cpu) {   // the CPU back-end: plain host buffers behind the same accessors (fr_worker_idx_ptr / dense_ptr / score_ptr)
         auto host = [](size_t bytes) { return aligned_alloc(64, align_up(bytes ? bytes : 64, 64)); };
-        w->h_idx = (int32_t *)host(B * idx_cols(ctx) * sizeof(int32_t));
+        w->h_idx = (int32_t *)host(B * (size_t)w->idx_cap * sizeof(int32_t));
         if (m.dense_len) w->h_dense = (float *)host(B * m.dense_len * sizeof(float));
         w->h_score = (float *)host(B * sizeof(float));
         w->d_records = (float *)host(B * (size_t)ctx->slice_padded * sizeof(float));
@@ -862,6 +880,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
         w->h_err = w->d_err = &w->c_err;
         w->counted = true;
         fr_ctx_ref(ctx);
+        ctx_enlist(ctx, w);
         ctx->n_workers.fetch_add(1, std::memory_order_relaxed);
         *out = w;
         return FR_OK;
@@ -894,7 +913,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
         if (lo > hi) W_HIP(hipStreamCreateWithPriority(&w->stream, hipStreamNonBlocking, spread == 2 ? hi + k % (lo - hi + 1) : (k % 2 ? lo : hi)));
         else W_HIP(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
     }
-    W_HIP(hipHostMalloc((void **)&w->h_idx, B * idx_cols(ctx) * sizeof(int32_t), hipHostMallocDefault));
+    W_HIP(hipHostMalloc((void **)&w->h_idx, B * (size_t)w->idx_cap * sizeof(int32_t), hipHostMallocDefault));
     if (m.dense_len) W_HIP(hipHostMalloc((void **)&w->h_dense, B * m.dense_len * sizeof(float), hipHostMallocDefault));
     W_HIP(hipHostMalloc((void **)&w->h_score, B * sizeof(float), hipHostMallocDefault));
     // index-range flag: pinned, device-visible host word.  Kernels touch it only on the error path
@@ -902,7 +921,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     W_HIP(hipHostMalloc((void **)&w->h_err, sizeof(int), hipHostMallocMapped));
     *w->h_err = 0;
     W_HIP(hipHostGetDevicePointer((void **)&w->d_err, w->h_err, 0));
-    W_HIP(hipMalloc((void **)&w->d_idx, B * idx_cols(ctx) * sizeof(int32_t)));
+    W_HIP(hipMalloc((void **)&w->d_idx, B * (size_t)w->idx_cap * sizeof(int32_t)));
     if (m.dense_len) W_HIP(hipMalloc((void **)&w->d_dense, B * m.dense_len * sizeof(float)));
     W_HIP(hipMalloc((void **)&w->d_records, B * (size_t)ctx->slice_padded * sizeof(float) * (ctx->n_shards > 1 ? 1 : 1)));
     if (ctx->n_shards == 1 && ctx->slice_padded != m.record_len) {
@@ -917,6 +936,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     W_HIP(hipEventCreate(&w->ev_stop));
     w->counted = true;
     fr_ctx_ref(ctx);
+    ctx_enlist(ctx, w);
     const int live = ctx->n_workers.fetch_add(1, std::memory_order_relaxed) + 1;
     // A width frozen by an early launch is kept (scores in flight must not change), but the caller is told once per worker that outnumbers
     // it: the call succeeds and fr_last_error() carries the note.
@@ -1735,6 +1755,123 @@ extern "C" int fr_worker_gather_only(fr_worker *w, int batch, const int32_t *d_i
     if (rc) return rc;
     w->in_flight = true;
     return FR_OK;
+}
+
+// ---- multi-hot pooled lookups (fleetrec_serving.h) -------------------------------------------------------
+// Pooling is stated per index column; the pooled descriptors (one FrPoolDesc per FrWordDesc) follow from h_words: a TABLE / COPY word's bag
+// is its index column's, a DENSE word is a bag of one.
+extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    const int cols = (int)idx_cols(ctx);
+    if (hots) {
+        if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: n_cols %d, the context has %d index columns", n_cols, cols);
+        for (int c = 0; c < cols; c++)
+            if (hots[c] < 1 || hots[c] > FR_POOL_MAX_HOTS) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: hots[%d] = %d outside [1, %d]", c, hots[c], FR_POOL_MAX_HOTS);
+    }
+    {
+        std::lock_guard<std::mutex> g(ctx->workers_mutex);
+        for (const fr_worker *w : ctx->workers)
+            if (w->in_flight || w->n_active || w->n_pending || w->sh_comm)
+                FR_FAIL(FR_ERR_STATE, "fr_ctx_set_pooling: a worker of the context has work in flight: call fr_worker_sync first");
+    }
+    if (!ctx->cpu) FR_SET_DEVICE(ctx);
+    if (!hots) {
+        if (ctx->d_pool) FR_HIP(hipFree(ctx->d_pool));
+        ctx->d_pool = nullptr;
+        ctx->h_pool.clear();
+        ctx->pool_cols = ctx->pool_max_hots = 0;
+        ctx->pool_wide = false;
+        return FR_OK;
+    }
+    std::vector<uint32_t> prefix(cols + 1, 0);
+    int max_hots = 1;
+    bool wide = true;
+    for (int c = 0; c < cols; c++) {
+        prefix[c + 1] = prefix[c] + (uint32_t)hots[c];
+        max_hots = hots[c] > max_hots ? hots[c] : max_hots;
+        wide = wide && hots[c] % 4 == 0;   // then every bag starts on a multiple of 4 slots too, and so does every item's row
+    }
+    std::vector<FrPoolDesc> pool(ctx->h_words.size());
+    for (size_t i = 0; i < pool.size(); i++) {
+        const uint32_t col = ctx->h_words[i].idx_col;
+        pool[i] = (col & FR_DESC_DENSE) ? FrPoolDesc{0u, 1u} : FrPoolDesc{prefix[col], (uint32_t)hots[col]};
+    }
+    if (!ctx->cpu) {
+        FrPoolDesc *d = nullptr;
+        FR_HIP(hipMalloc((void **)&d, sizeof(FrPoolDesc) * (pool.empty() ? 1 : pool.size())));
+        const hipError_t e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * pool.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d);
+            FR_FAIL(FR_ERR_HIP, "hipMemcpy(pooled descriptors) failed: %s", hipGetErrorString(e));
+        }
+        if (ctx->d_pool) (void)hipFree(ctx->d_pool);
+        ctx->d_pool = d;
+    }
+    ctx->h_pool.swap(pool);
+    ctx->pool_cols = (int)prefix[cols];
+    ctx->pool_max_hots = max_hots;
+    ctx->pool_wide = wide;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_pooled_index_cols(const fr_ctx *ctx) { return ctx ? ctx->pool_cols : 0; }
+
+static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
+    fr_ctx *c = w->ctx;
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
+    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (!d_idx) FR_FAIL(FR_ERR_INVALID, "d_idx is NULL");
+    if (c->model.dense_len && !d_dense) {
+        bool needs = false;
+        for (const FrWordDesc &wd : c->h_words) needs |= (wd.idx_col & FR_DESC_DENSE) != 0;
+        if (needs) FR_FAIL(FR_ERR_INVALID, "model has dense features but d_dense is NULL");
+    }
+    if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, c->pool_cols, d_dense, d_records, batch, &w->c_err);
+    return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, c->pool_cols, c->pool_max_hots, c->pool_wide, d_dense, d_records, batch, w->d_err,
+                             w->stream, c->slice_padded / 4);
+}
+
+extern "C" int fr_worker_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
+    int rc = check_ready(w, batch, true, false);
+    if (rc) return rc;
+    if (!d_records) FR_FAIL(FR_ERR_INVALID, "d_records is NULL");
+    FR_SET_DEVICE(w->ctx);
+    rc = launch_gather_pooled(w, batch, d_idx, d_dense, d_records);
+    if (rc) return rc;
+    keep_kernel(w);
+    w->in_flight = true;
+    return FR_OK;
+}
+
+// pooled records into the worker's record buffer, then the chain fr_worker_fc_only runs from records (launch_fc), on the same stream
+static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
+    if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
+    int rc = launch_gather_pooled(w, batch, d_idx, d_dense, w->d_records);
+    if (rc) return rc;
+    w->in_flight = true;   // the gather is enqueued whatever the chain's launch says
+    return launch_fc(w, batch, w->d_records, d_scores);
+}
+
+extern "C" int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
+    int rc = check_ready(w, batch, true, true);
+    if (rc) return rc;
+    if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
+    FR_SET_DEVICE(w->ctx);
+    return submit_pooled_impl(w, batch, d_idx, d_dense, d_scores);
+}
+
+extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) {
+    int rc = check_ready(w, batch, true, true);
+    if (rc) return rc;
+    if (w->in_flight) FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
+    fr_ctx *c = w->ctx;
+    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (w->idx_cap < c->pool_cols)
+        FR_FAIL(FR_ERR_STATE, "the worker's index buffers hold %d columns per item, pooled rows have %d: create the worker after fr_ctx_set_pooling", w->idx_cap, c->pool_cols);
+    FR_SET_DEVICE(c);
+    // as fr_worker_submit: the gather reads the pinned index rows (and dense features) in place, the output layer writes the pinned scores
+    return submit_pooled_impl(w, batch, w->h_idx, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
 }
 
 // Sharded mode, low-precision transport: the shard's slice [batch][slice_padded] as bf16 or e4m3 (x 2^e of the context's X exponent)

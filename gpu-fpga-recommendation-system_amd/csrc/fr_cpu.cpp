@@ -254,6 +254,58 @@ int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx
     return FR_OK;
 }
 
+// The pooled (multi-hot) gather, exactly as gather_pooled_kernel (fr_gather.hip) folds a bag: slot -1 is empty, the first non-empty slot's
+// row word is taken as a bit copy, every further one is added to it in fp32, one add per lane, in ascending slot order; an all-empty
+// bag gives +0.0f.  Plain IEEE adds on both sides (no fast-math in either build): the records are bit-identical to the GPU's.
+int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, int pool_cols, const float *dense, float *out, int batch, int *err_flag) {
+    const int chunk = 32;
+    std::atomic<int> bad{0};
+    char *o = reinterpret_cast<char *>(out);
+    Pool::get().run((batch + chunk - 1) / chunk, [&](int u) {
+        const int b0 = u * chunk, b1 = b0 + chunk < batch ? b0 + chunk : batch;
+        int local_bad = 0;
+        for (int b = b0; b < b1; b++) {
+            const int32_t *row = idx + (size_t)b * pool_cols;
+            for (int w = 0; w < n_words; w++) {
+                const FrWordDesc &d = words[w];
+                char *dst = o + ((size_t)d.dst_blk * (size_t)batch + (size_t)b * d.dst_stride + d.dst_off) * 16;
+                if (d.idx_col & FR_DESC_DENSE) {
+                    memcpy(dst, reinterpret_cast<const char *>(dense) + d.src + (size_t)b * d.stride, 16);
+                    continue;
+                }
+                uint32_t acc[4] = {0u, 0u, 0u, 0u};
+                bool have = false;
+                for (uint32_t j = 0; j < pool[w].hots; j++) {
+                    uint32_t r = (uint32_t)row[pool[w].first + j];
+                    if (r == 0xFFFFFFFFu) continue;   // an empty slot
+                    if (r >= d.rows) {
+                        local_bad = 1;
+                        r = 0;
+                    }
+                    uint32_t x[4];
+                    memcpy(x, reinterpret_cast<const char *>(d.src) + (uint64_t)r * d.stride, 16);
+                    for (int k = 0; k < 4; k++) {
+                        if (have) {
+                            float a, v;
+                            memcpy(&a, &acc[k], 4);
+                            memcpy(&v, &x[k], 4);
+                            a = a + v;
+                            memcpy(&acc[k], &a, 4);
+                        } else {
+                            acc[k] = x[k];
+                        }
+                    }
+                    have = true;
+                }
+                memcpy(dst, acc, 16);
+            }
+        }
+        if (local_bad) bad.store(1, std::memory_order_relaxed);
+    });
+    if (bad.load() && err_flag) __atomic_store_n(err_flag, 1, __ATOMIC_RELEASE);
+    return FR_OK;
+}
+
 // ---- the FC chain: 4 x cublasLtMatmul, alpha = 1, beta = 0, no bias, no activation (cuda_server.c:211-217,468-491) ---------------------
 // Y[b][h] = sum over k, IN k ORDER, of W[h + k * H] * X[b][k], each step one fused multiply-add in fp32.  A tile of MB items x HT outputs
 // keeps its sums in registers while k runs; W is read in its own (column-major: h contiguous) order.

@@ -368,6 +368,183 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
 }
 
 // ---------------------------------------------------------------------------------------------------
+// gather_pooled_kernel: the multi-hot (pooled) form of gather_pack -- fr_worker_gather_pooled.
+//
+// Word-major like the kernels above: a thread owns one 16-byte record word (FrWordDesc + FrPoolDesc in registers), consecutive lanes own
+// consecutive words, so record stores stay coalesced.  The word's bag is `hots` consecutive int32 slots of the item's pooled index row
+// (idx[b][first .. first + hots)); the record word is the fp32 sum of the bag's row words under the contract of fleetrec_serving.h: the
+// FIRST non-empty slot's word is taken as a bit copy, every further non-empty slot's word is added to it, one v_add_f32 per lane, in
+// ascending slot order (the accumulator is a select between "take" and "add": no FMA, no tree); slot -1 is empty, an all-empty bag
+// gives +0.0f.  A DENSE word is a bag of one: the item's own dense row.
+// Per chunk of ITEMS items the bag is walked in windows of WIN slots: the window's index slots are loaded first (WIDE: as 16-byte
+// loads -- every bag starts and ends on a multiple of 4 slots and the row length is one), then all ITEMS x WIN row words are issued back
+// to back, then they are folded in slot order: a wave keeps ITEMS x WIN x 1 KiB of gathers in flight.  Lanes of a wave sit on different
+// columns and may have different `hots`: slots past a lane's bag are masked off the loads (exec mask), a lane whose bag is exhausted
+// idles through the wave's remaining windows.  Items past the batch cost no branch: their index loads and record stores go through
+// buffer resources whose bounds drop them (both buffers below 4000 MiB: the launcher checks).  XCD grouping as in gather_pack_xcd_kernel
+// (workgroup b serves group b % n_groups and chunk b / n_groups; n_groups = 8, or 1 for records too narrow for a plan); blockIdx.y walks
+// a group wider than one workgroup.
+// ---------------------------------------------------------------------------------------------------
+template <int ITEMS, int WIN, bool WIDE>
+__global__ void __launch_bounds__(256) gather_pooled_kernel(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, const FrGatherGroups groups,
+                                                            int n_groups, const int32_t *__restrict__ idx, int pool_cols, const float *__restrict__ dense,
+                                                            void *__restrict__ out, int batch, int *__restrict__ err_flag, unsigned out_bytes) {
+    static_assert(!WIDE || WIN % 4 == 0, "16-byte index loads need whole groups of 4 slots");
+    const int group = blockIdx.x & (n_groups - 1);
+    const int w0 = groups.start[group];
+    const int t = blockIdx.y * blockDim.x + threadIdx.x;
+    if (t >= groups.start[group + 1] - w0) return;
+    const int w = w0 + t;
+    const uint4 d0 = reinterpret_cast<const uint4 *>(words)[2 * w];
+    const uint4 d1 = reinterpret_cast<const uint4 *>(words)[2 * w + 1];
+    const uint2 pd = reinterpret_cast<const uint2 *>(pool)[w];
+    const uint64_t src = ((uint64_t)d0.y << 32) | d0.x;
+    const uint32_t stride = d0.z;
+    const bool is_dense = (d0.w & FR_DESC_DENSE) != 0;
+    const uint32_t rows = d1.x, dst_off = d1.y, dst_stride = d1.z, dst_blk = d1.w;
+    const uint32_t first = pd.x, hots = pd.y;
+    const uint64_t base = (is_dense ? (uint64_t)reinterpret_cast<uintptr_t>(dense) : 0ull) + src;
+    const unsigned blk = (dst_blk * (unsigned)batch + dst_off) * 16u;
+    const unsigned ostride = dst_stride * 16u;
+    const unsigned irow = (unsigned)pool_cols * 4u;
+    const __amdgpu_buffer_rsrc_t rs_idx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, (unsigned)batch * irow, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, out_bytes, 0x00020000);
+    typedef const u32x4_t __attribute__((address_space(1))) * gptr_t;   // a global_load (not a flat one)
+    bool bad = false;
+    const unsigned b0 = (blockIdx.x / (unsigned)n_groups) * ITEMS;   // the workgroup's chunk of ITEMS items
+    uint4 acc[ITEMS];
+    bool have[ITEMS];
+#pragma unroll
+    for (int i = 0; i < ITEMS; i++) acc[i] = make_uint4(0u, 0u, 0u, 0u), have[i] = false;
+    for (uint32_t j0 = 0; j0 < hots; j0 += WIN) {
+        // the window's slots: -1 (empty) past the bag; an item past the batch reads past the resource: 0 (row 0; its store is dropped)
+        int32_t sl[ITEMS][WIN];
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) {
+            const unsigned ioff = (b0 + i) * irow + (first + j0) * 4u;
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int q = 0; q < WIN / 4; q++) {
+                    u32x4_t v4 = {~0u, ~0u, ~0u, ~0u};
+                    if (!is_dense && j0 + 4 * q < hots) v4 = __builtin_amdgcn_raw_buffer_load_b128(rs_idx, ioff + 16u * q, 0, 0);
+                    sl[i][4 * q] = (int32_t)v4.x, sl[i][4 * q + 1] = (int32_t)v4.y, sl[i][4 * q + 2] = (int32_t)v4.z, sl[i][4 * q + 3] = (int32_t)v4.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < WIN; j++) {
+                    sl[i][j] = -1;
+                    if (!is_dense && j0 + j < hots) sl[i][j] = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_idx, ioff + 4u * j, 0, 0);
+                }
+            }
+        }
+        // all row words of the window, back to back
+        uint4 v[ITEMS][WIN];
+        bool on[ITEMS][WIN];
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) {
+            const unsigned b = b0 + i;
+#pragma unroll
+            for (int j = 0; j < WIN; j++) {
+                uint32_t r = (uint32_t)sl[i][j];
+                on[i][j] = is_dense ? (j0 + j == 0) : (r != 0xFFFFFFFFu);
+                const bool oob = !is_dense & on[i][j] & (r >= rows);  // reference: silent out-of-bounds read (embedding_47_krnl.cpp:927-933)
+                bad |= oob;
+                r = oob ? 0u : r;
+                r = is_dense ? (b < (unsigned)batch ? b : 0u) : r;
+                v[i][j] = make_uint4(0u, 0u, 0u, 0u);
+                if (on[i][j]) {
+                    const u32x4_t q = *(gptr_t)(base + (uint64_t)r * stride);
+                    v[i][j] = make_uint4(q.x, q.y, q.z, q.w);
+                }
+            }
+        }
+        // fold in slot order: take the first non-empty word as it is, add every further one
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) {
+#pragma unroll
+            for (int j = 0; j < WIN; j++) {
+                const uint4 a = acc[i], x = v[i][j];
+                uint4 sum;
+                sum.x = __float_as_uint(__uint_as_float(a.x) + __uint_as_float(x.x));
+                sum.y = __float_as_uint(__uint_as_float(a.y) + __uint_as_float(x.y));
+                sum.z = __float_as_uint(__uint_as_float(a.z) + __uint_as_float(x.z));
+                sum.w = __float_as_uint(__uint_as_float(a.w) + __uint_as_float(x.w));
+                const uint4 nxt = have[i] ? sum : x;
+                acc[i] = on[i][j] ? nxt : a;
+                have[i] |= on[i][j];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; i++) {
+        const unsigned b = b0 + i;
+        const unsigned off = b < (unsigned)batch ? blk + b * ostride : out_bytes;   // past the batch: dropped by the resource's bounds
+        u32x4_t x;
+        x.x = acc[i].x, x.y = acc[i].y, x.z = acc[i].z, x.w = acc[i].w;
+        __builtin_amdgcn_raw_buffer_store_b128(x, rs_out, off, 0, 0);
+    }
+    if (bad) atomicOr_system(err_flag, 1);  // pinned host word; error path only
+}
+
+template <int ITEMS, int WIN, bool WIDE>
+static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, int pool_cols, const float *dense,
+                                void *out, int batch, int *err_flag, unsigned out_bytes, hipStream_t s) {
+    const int n_chunks = (batch + ITEMS - 1) / ITEMS;
+    const int bx = groups.max_words >= 256 ? 256 : ((groups.max_words + 63) / 64) * 64;
+    dim3 grid(n_groups * n_chunks, (groups.max_words + bx - 1) / bx);
+    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, pool_cols, dense, out, batch, err_flag, out_bytes);
+    KCHECK();
+    fr_note_kernel("gather_pooled_kernel<%d, %d, %s>", ITEMS, WIN, WIDE ? "true" : "false");
+    return FR_OK;
+}
+
+// idx = [batch][pool_cols] int32; out = fp32 records in the model's layout, out_words 16-byte words per item.  max_hots picks the window.
+int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, int pool_cols, int max_hots, bool wide,
+                      const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words) {
+    if (n_words <= 0 || batch <= 0) return FR_OK;
+    if (out_words < n_words) out_words = n_words;
+    const size_t out_bytes = (size_t)batch * (size_t)out_words * 16, idx_bytes = (size_t)batch * (size_t)pool_cols * 4;
+    if (out_bytes >= ((size_t)4000 << 20) || idx_bytes >= ((size_t)4000 << 20))   // 32-bit resource offsets, with room for the chunk past the batch
+        FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's index rows (%zu bytes) or records (%zu bytes) reach 4000 MiB", idx_bytes, out_bytes);
+    FrGatherGroups groups = planned;
+    int n_groups = 8;
+    if (groups.max_words <= 0) {   // no XCD plan (a narrow record): one group, whole workgroups along the words
+        n_groups = 1;
+        groups.start[0] = 0;
+        for (int g = 1; g <= 8; g++) groups.start[g] = n_words;
+        groups.max_words = n_words;
+    }
+    wide = wide && (reinterpret_cast<uintptr_t>(idx) & 15) == 0;
+    // window x items per thread by the longest bag, from the sweep on the MI355X (profiles/pooled_gather_window_sweep.md: Model-C batch 4096, every
+    // window x items pair at hots 1 .. 16): the longest window that a bag fills wins by 1-5 %, with as few items per thread as keep 16 row words
+    // in flight; a one-slot window is 20 % slower than a two-slot one at hots = 1 and is not built.  FR_POOL_WIN / FR_POOL_ITEMS: experiments build only
+    int win = max_hots >= 16 ? 16 : max_hots >= 8 ? 8 : max_hots >= 4 ? 4 : 2;
+    int items = win >= 16 ? 1 : max_hots >= 2 ? 2 : 4;
+    win = FR_KNOB("POOL_WIN", win);
+    items = FR_KNOB("POOL_ITEMS", items);
+#define FR_GP(I, W)                                                                                                                                     \
+    if (items == I && win == W) {                                                                                                                       \
+        if constexpr (W % 4 == 0)                                                                                                                       \
+            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, s); \
+        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, s);   \
+    }
+    FR_GP(4, 2)
+    FR_GP(2, 2)
+    FR_GP(2, 4)
+    FR_GP(2, 8)
+    FR_GP(1, 16)
+#ifdef FR_EXPERIMENTS
+    FR_GP(1, 1) FR_GP(2, 1) FR_GP(4, 1) FR_GP(8, 1)
+    FR_GP(1, 2) FR_GP(8, 2)
+    FR_GP(1, 4) FR_GP(4, 4) FR_GP(8, 4)
+    FR_GP(1, 8) FR_GP(4, 8)
+    FR_GP(2, 16)
+#endif
+#undef FR_GP
+    FR_FAIL(FR_ERR_INVALID, "pooled gather: no kernel for %d items x a window of %d slots", items, win);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // gather_tile_kernel<DEDUP>: the item-tile form of the record-producing gather -- LDS-staged row packing, with (DEDUP) or without a
 // wave-level merge of duplicate lookups (north_star: "LDS-staged row packing and wavefront ballot/shuffle for index dedup").
 //

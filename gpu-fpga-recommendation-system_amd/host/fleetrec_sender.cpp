@@ -8,6 +8,9 @@
 //                        [--indices reference|uniform] [--per-item | --per-bank] [--row-cap N] [--max-blocks N] [--reply]
 //                        [--window W] (with --reply: up to W requests in flight per connection -- a reader thread takes the score replies and
 //                                      times request -> reply; W = 1 waits for every reply before the next request, the default)
+//                        [--hots N [--ragged]]  (pooled lookups, fleetrec_server --hots N: a bag of N slots on every index column, a block is
+//                                      B x (columns x N) int32, column by column, slot-minor.  reference indices: slot j of item b takes the fixed-index
+//                                      table's entry for item b + j; --ragged: slot j of column c of item b is empty (-1) when (b + 3 c + 5 j) % 4 == 3)
 //                        [--pool N]   (uniform indices: N distinct blocks per connection are generated up front and sent in rotation --
 //                                      drawing 12 k random indices per block is slower than the server; default 32, 0 = draw every block)
 #include <arpa/inet.h>
@@ -28,6 +31,7 @@
 #include <vector>
 
 #include "fleetrec.h"
+#include "fleetrec_serving.h"
 
 // load_access_idx's 32 fixed indices (embedding_47_krnl.cpp:899-914; identical in the 98/377 kernels)
 static const int kIdxRandom[32] = {3, 99, 38, 72, 29, 57, 1, 72, 36, 76, 35, 50, 37, 57, 13, 66,
@@ -37,7 +41,8 @@ int main(int argc, char **argv) {
     int which = FR_MODEL_A, batch = 256, threads = 4, port = 8080;
     long row_cap = 0, max_blocks = 1L << 40, interval_us = 0, pool = 32, window = 1;
     std::string host = "127.0.0.1", indices = "reference";
-    bool per_item = false, per_bank = false, reply = false;
+    bool per_item = false, per_bank = false, reply = false, ragged = false;
+    int hots = 0;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -55,8 +60,13 @@ int main(int argc, char **argv) {
         else if (a == "--interval-us") interval_us = atol(next());
         else if (a == "--pool") pool = atol(next());
         else if (a == "--window") window = atol(next());
+        else if (a == "--hots") hots = atoi(next());
+        else if (a == "--ragged") ragged = true;
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
+    if (hots < 0 || hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, hots); return 2; }
+    if (ragged && hots <= 0) { fprintf(stderr, "--ragged needs --hots N\n"); return 2; }
+    const size_t slots = hots > 0 ? (size_t)hots : 1;   // int32 per index column of an item
     fr_model_desc *m = nullptr;
     if (fr_model_clone_scaled(fr_model_builtin(which), 1.0, 1, row_cap, &m) != FR_OK) { fprintf(stderr, "%s\n", fr_last_error()); return 1; }
     if (per_item) m->index_mode = FR_INDEX_PER_ITEM;
@@ -75,7 +85,7 @@ int main(int argc, char **argv) {
     std::vector<std::vector<double>> lat_us(threads);  // --reply --window W: request sent -> reply received, per request
     for (int t = 0; t < threads; t++) {
         th.emplace_back([&, t]() {
-            std::vector<int32_t> idx((size_t)batch * cols);
+            std::vector<int32_t> idx((size_t)batch * cols * slots);
             std::vector<float> dense((size_t)batch * m->dense_len), scores(batch);
             std::mt19937_64 rng(1234 + t);
             int sock = socket(AF_INET, SOCK_STREAM, 0), one = 1;
@@ -91,12 +101,14 @@ int main(int argc, char **argv) {
             setsockopt(sock, IPPROTO_TCP, TCP_NODELAY, &one, sizeof(one));
             auto draw = [&](int32_t *ix, float *dn) {
                 for (int b = 0; b < batch; b++) {
-                    for (size_t c = 0; c < cols; c++) {
-                        int32_t v;
-                        if (indices == "reference") v = kIdxRandom[b % 32];  // same index for every table of the item (F4)
-                        else v = (int32_t)(rng() % (uint64_t)col_range[c]);
-                        ix[(size_t)b * cols + c] = v;
-                    }
+                    for (size_t c = 0; c < cols; c++)
+                        for (size_t j = 0; j < slots; j++) {
+                            int32_t v;
+                            if (indices == "reference") v = kIdxRandom[((size_t)b + j) % 32];  // same index for every table of the item (F4)
+                            else v = (int32_t)(rng() % (uint64_t)col_range[c]);
+                            if (ragged && ((size_t)b + 3 * c + 5 * j) % 4 == 3) v = -1;   // an empty slot
+                            ix[((size_t)b * cols + c) * slots + j] = v;
+                        }
                     for (int d = 0; d < m->dense_len; d++)
                         dn[(size_t)b * m->dense_len + d] = (indices == "reference") ? ((kIdxRandom[b % 32] % 2 == 0) ? 1.0f : 0.0f)
                                                                                      : (float)((rng() >> 11) * (2.0 / 9007199254740992.0) - 1.0);

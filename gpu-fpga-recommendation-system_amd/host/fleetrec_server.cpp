@@ -14,6 +14,8 @@
 //        [--stream [--reply [--flush-us 50] [--flush-min 32]]]: streaming with score replies and adaptive batching -- see thread_consume
 //                        [--tables evenodd|hash] [--weights ones|uniform] [--per-item | --per-bank] [--reply] [--row-cap N]
 //                        [--shards G [--one-device] [--precision f32|bf16|fp8] [--exchange allgather|alltoall]]
+//        [--hots N]: multi-hot pooled lookups (fr_ctx_set_pooling): a bag of N slots on every index column, a block is B x (index columns x N)
+//                        int32 (slot -1 = empty), every batch goes through fr_worker_submit_pooled + fr_worker_sync.  Not with --stream or --shards.
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
@@ -59,6 +61,7 @@ struct Options {
     int small_block = 8;   // --stream --reply: blocks of at most this many batches ride the stage pipeline, n + 4 launches (fr_ctx_set_small_block)
     bool latency = false;  // latency-measurement mode: per-batch recv -> enqueued -> scores times (measure_network_cuda_cp_latency_*/cuda_server.c)
     long row_cap = 0;
+    int hots = 0;          // --hots N: pooled lookups, N slots per index column (0: one-hot)
 };
 
 static bool read_exact(int fd, void *buf, size_t n) {  // the recv loop of cuda_server.c:425-450
@@ -171,7 +174,8 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
         t->error = fr_last_error();
         return;
     }
-    const size_t idx_cols = (size_t)fr_model_index_cols(m);
+    // --hots: the block carries the pooled index rows (the worker was created after fr_ctx_set_pooling: its pinned buffer holds them)
+    const size_t idx_cols = o.hots > 0 ? (size_t)fr_ctx_pooled_index_cols(t->ctx) : (size_t)fr_model_index_cols(m);
     const size_t idx_bytes = (size_t)o.batch * idx_cols * sizeof(int32_t);
     const size_t dense_bytes = (size_t)o.batch * m->dense_len * sizeof(float);
     int server_fd = socket(AF_INET, SOCK_STREAM, 0), opt = 1;
@@ -365,7 +369,7 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 break;
             }
             const auto t_recv = std::chrono::steady_clock::now();  // network_time / cuda_time pair of cuda_server.c:429,462
-            if (fr_worker_submit(wk, o.batch) != FR_OK) {
+            if ((o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
                 t->status = -5;
                 t->error = fr_last_error();
                 break;
@@ -419,6 +423,7 @@ int main(int argc, char **argv) {
         else if (a == "--flush-min") o.flush_min = atoi(next());
         else if (a == "--small-block") o.small_block = atoi(next());
         else if (a == "--row-cap") o.row_cap = atol(next());
+        else if (a == "--hots") o.hots = atoi(next());
         else if (a == "--exchange") {
             std::string v = next();
             if (v != "allgather" && v != "alltoall") { fprintf(stderr, "--exchange: allgather or alltoall, not '%s'\n", v.c_str()); return 2; }
@@ -428,6 +433,11 @@ int main(int argc, char **argv) {
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (o.exchange_given && o.shards <= 0) { fprintf(stderr, "--exchange needs --shards G\n"); return 2; }
+    if (o.hots < 0 || o.hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, o.hots); return 2; }
+    if (o.hots > 0 && (o.stream || o.shards > 0)) {
+        fprintf(stderr, "--hots (pooled lookups) serves the submit-and-sync path only: not with --stream or --shards (their producers are one-hot)\n");
+        return 2;
+    }
     printf("HIP devices visible: %d\n", fr_device_count());  // device probe of cuda_server.c:508-522
     fr_model_desc *model = nullptr;
     if (fr_model_clone_scaled(fr_model_builtin(o.model), 1.0, 1, o.row_cap, &model) != FR_OK) { fprintf(stderr, "%s\n", fr_last_error()); return 1; }
@@ -472,6 +482,14 @@ int main(int argc, char **argv) {
                fr_ctx_fill_weights(ctx, o.weights, 99) != FR_OK || fr_ctx_set_fc_precision(ctx, o.precision) != FR_OK) {
         fprintf(stderr, "set-up failed: %s\n", fr_last_error());
         return 1;
+    }
+    if (o.hots > 0) {   // before the threads create their workers: a worker sizes its index buffers for the pooled rows at creation
+        std::vector<int32_t> hots((size_t)fr_model_index_cols(model), o.hots);
+        if (fr_ctx_set_pooling(ctx, hots.data(), (int)hots.size()) != FR_OK) {
+            fprintf(stderr, "set-up failed: %s\n", fr_last_error());
+            return 1;
+        }
+        printf("pooled lookups: %d slots on each of %zu index columns, %d int32 per item\n", o.hots, hots.size(), fr_ctx_pooled_index_cols(ctx));
     }
     if (o.stream && o.reply && !g_engine && fr_ctx_set_small_block(ctx, o.small_block) != FR_OK) {
         fprintf(stderr, "set-up failed: %s\n", fr_last_error());

@@ -78,6 +78,31 @@ const float *fr_driver_host_score_ring(fr_driver *d, int thread, int slot, int *
 int fr_comm_set_exchange(fr_comm *c, int exchange);   /* between steps; every rank of the communicator sets the same mode */
 int fr_comm_exchange(const fr_comm *c);               /* the current mode (FR_EXCHANGE_ALLGATHER after init) */
 
+/* Multi-hot pooled lookups (additive in ABI 6).  Pooling is described per index COLUMN of the context's index mode: hots[c] (1 ..
+ * FR_POOL_MAX_HOTS) slots for column c < fr_model_index_cols(model) -- FR_INDEX_PER_TABLE: a bag per table; FR_INDEX_PER_BANK: a bag of bank-row
+ * indices per bank (every table of the bank is pooled with the same bag); FR_INDEX_PER_ITEM: one bag reused for every table.  The pooled
+ * index row of an item is int32 idx[P], P = sum of hots, ordered by column, slot-minor: column c's slots are idx[prefix[c] + j], j < hots[c],
+ * prefix = the exclusive prefix sum of hots.  A slot of -1 is EMPTY; any other negative value, or one >= the row count the one-hot gather checks,
+ * is FR_ERR_INDEX_RANGE at fr_worker_sync (the slot reads row 0).  Every TABLE and COPY word of the record becomes the pooled value of its
+ * column's bag: the first non-empty slot's row word as a bit copy, every further non-empty slot's word added to it in fp32, one add per lane,
+ * in ascending slot order; an all-empty bag gives +0.0f.  DENSE words are copied as by the one-hot gather.  With every hots == 1 and no empty
+ * slot the records are bit-identical to fr_worker_gather_only's.  Records are fp32 in the model's layout; the FC chain is the one
+ * fr_worker_fc_only runs from records, in the context's precision.  Not available (FR_ERR_STATE): sharded contexts, the streaming entry
+ * points (their producers stay one-hot).  An index or record buffer of 4000 MiB or more is FR_ERR_INVALID (32-bit buffer offsets). */
+#define FR_POOL_MAX_HOTS 64
+/* hots[n_cols], n_cols == fr_model_index_cols(fr_ctx_model(ctx)); hots == NULL clears.  Builds the pooled descriptors.
+ * FR_ERR_STATE while a worker of the context has work in flight, or on a sharded context.  One-hot entry points are unaffected.
+ * Like the other fr_ctx_set_* calls it is not to be raced against calls on the context's workers. */
+int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols);
+int fr_ctx_pooled_index_cols(const fr_ctx *ctx);          /* P; 0 when no pooling is set */
+/* d_idx int32 [batch][P]; d_records as for fr_worker_gather_only.  Asynchronous; follow with fr_worker_sync. */
+int fr_worker_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records);
+/* fr_worker_gather_pooled into the worker's record buffer, then the FC chain from those records. */
+int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores);
+/* Host form: the worker's pinned idx buffer holds [batch][P]; scores in fr_worker_score_ptr.  A worker created AFTER
+ * fr_ctx_set_pooling sizes its pinned and device index buffers for max(index_cols, P); an older worker gets FR_ERR_STATE here. */
+int fr_worker_submit_pooled(fr_worker *w, int batch);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -16,12 +16,14 @@ UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 FR_LIB=$PWD/$PKG/libfleetrec_as
 grep -q "ERROR: AddressSanitizer\|runtime error:" /tmp/fr_asan.log && { echo "ASan/UBSan reports: /tmp/fr_asan.log"; rc=1; }
 # TSan: the CPU back-end's tests (thread pool, workers on several host threads, the driver loops, and -- round 6 -- the table-sharded step
 # with G = 2, 3, 8 ranks on the in-process host exchange: rendezvous, host streams, status words, bounded wait, destroy in flight; both exchange
-# modes, all-gather and all-to-all, tests/test_cpu_alltoall.py).  Left out: the tests that start
+# modes, all-gather and all-to-all, tests/test_cpu_alltoall.py; the pooled gather, tests/test_cpu_pooled.py).  Left out: the tests that start
 # other programs or fork (TSan does not support new threads in the child of a multi-threaded fork; all run under ASan above).
 rm -f /tmp/fr_tsan_report.*
 LD_PRELOAD="$(gcc -print-file-name=libtsan.so)" TSAN_OPTIONS="halt_on_error=0 report_signal_unsafe=0 exitcode=0 log_path=/tmp/fr_tsan_report" \
 FR_LIB=$PWD/$PKG/libfleetrec_tsan.so \
-    timeout 900 python -m pytest tests/test_cpu_backend.py tests/test_cpu_alltoall.py -q -p no:cacheprovider \
+    timeout 900 python -m pytest tests/test_cpu_backend.py tests/test_cpu_alltoall.py tests/test_cpu_pooled.py -q -p no:cacheprovider \
+    --deselect tests/test_cpu_pooled.py::test_server_answers_pooled_requests_on_the_cpu_back_end \
+    --deselect tests/test_cpu_pooled.py::test_server_refuses_hots_with_stream_or_shards \
     --deselect tests/test_cpu_backend.py::test_server_answers_the_sender_on_the_cpu_back_end \
     --deselect tests/test_cpu_backend.py::test_server_shards_model_c_over_cpu_shard_contexts \
     --deselect tests/test_cpu_alltoall.py::test_server_shards_with_the_alltoall_exchange \
