@@ -413,10 +413,12 @@ bool frk_fused_ok(int K, int H1, int H2, int H3) {
     return frk_fused_lds_bytes(K, H2, 4) <= 160 * 1024;  // the single-buffer layout is the smallest
 }
 
-// two workgroups per CU need <= 80 KiB each (FR_FUSED_WPE=2 forces the one-workgroup build, for A/B measurements)
+// two workgroups per CU need <= 80 KiB each (experiments build: FR_FUSED_WPE=2 forces the one-workgroup build, for A/B measurements)
 static int fused_wpe(int K, int H2) {
+#ifdef FR_EXPERIMENTS
     const int forced = FR_KNOB_ONCE("FUSED_WPE", 0);
     if (forced == 2 || forced == 4) return forced == 4 && frk_fused_lds_bytes(K, H2, 4) > 80 * 1024 ? 2 : forced;
+#endif
     return frk_fused_lds_bytes(K, H2, 4) <= 80 * 1024 ? 4 : 2;
 }
 
@@ -436,9 +438,11 @@ int frk_fused_launch(const FrFusedArgs &a, hipStream_t s) {
     const size_t lds = frk_fused_lds_bytes(a.K, a.H2, db ? 2 : 4);
     dim3 grid(a.n_batches * a.tiles_per_batch);
     if (a.H2 == 512) {
-        if (a.K == 352) {  // Model-A: straight-line FC1
-            if (wpe == 4) return fused_launch_inst<2, 44, 4, false>(a, grid, lds, s);
-            return fused_launch_inst<2, 44, 2, true>(a, grid, lds, s);
+        if (a.K == 352) {  // Model-A: straight-line FC1; 78 KiB in the single-buffer layout, so WPE 4 unless FR_FUSED_WPE forces the other build
+#ifdef FR_EXPERIMENTS
+            if (wpe != 4) return fused_launch_inst<2, 44, 2, true>(a, grid, lds, s);
+#endif
+            return fused_launch_inst<2, 44, 4, false>(a, grid, lds, s);
         }
         if (a.K == 880) return fused_launch_inst<2, 110, 2, false>(a, grid, lds, s);  // Model-B: 150 KiB with one R1 buffer
         if (db) return fused_launch_inst<2, 0, 2, true>(a, grid, lds, s);

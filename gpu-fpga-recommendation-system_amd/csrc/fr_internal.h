@@ -301,12 +301,6 @@ struct fr_worker {
         const float *d_dense = nullptr;
         float *d_scores = nullptr;
     } ring[8];
-    // Large batches (transposing gather + GEMM-kernel FC layers: Model-C at batch 4096): the gather of batch L runs on a SECOND stream of the
-    // worker, beside the FC1 GEMM of batch L - 1 on the main one, ordered by events per activation-set parity: x_ready[p] = the gather into
-    // X[p] has finished (aux -> main), x_free[p] = the FC1 that read X[p] has finished (main -> aux).
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_x_ready[2] = {nullptr, nullptr}, ev_x_free[2] = {nullptr, nullptr};
-    bool x_ready_set[2] = {false, false}, x_free_set[2] = {false, false};
     uint64_t launch_no = 0;     // number of pipeline launches issued so far
     int n_active = 0;
     bool counted = false;       // in fr_ctx::n_workers
@@ -412,9 +406,6 @@ bool frk_fc_lp_gemm_ok(int precision, int K, int N, int ldm);
 // width: the context's chain width (fr_ctx::chain_width) -> the larger tile already when it covers 1 / width of the chip (lp_gemm_mu)
 int frk_fc_lp_gemm(int precision, const void *Wp, const void *Xp, void *Yp, int K, int N, int ldm, int e_w, int e_in, int e_out, int width, bool minor, hipStream_t s);
 bool frk_fused_hk_takes_lp_rows(int K);   // the persistent bf16 fused kernel has an instantiation that reads operand-type (bf16) rows for this record length
-bool frk_fc_gemm_gather_ok(int precision, int K, int N, int ldm);   // FC1 of batch L - 1 + the gather of batch L in one launch (fc_gemm_gather_kernel)
-int frk_fc_gemm_gather(int precision, const void *Wp, const void *Xp, void *Yp, int K, int N, int ldm, int e_w, int e_in, int e_out, const FrWordDesc *words, int n_words,
-                       int idx_stride, const int32_t *idx, const float *dense, int g_batch, int g_ldm, int g_K, void *g_out, int g_e_x, int *err_flag, hipStream_t s);
 bool frk_fc_tail_ok(int precision, int K, int N, int ldm);   // FC3 + output layer as one launch (fc_tail_kernel, fr_gemm.hip)
 int frk_fc_tail(int precision, const void *W3, const void *R2, const void *wout, float *scores, int K, int N, int ldm, int batch, int e_w, int e_in, int e_r3, hipStream_t s);
 int frk_records_to_q8_bf16(const float *X, void *Xh, int batch, int K, int ldm, hipStream_t s);

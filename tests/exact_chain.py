@@ -287,14 +287,7 @@ CASES = [
 ]
 
 # Kernels of libfleetrec.so that no shape, batch, chain width or stream group reaches (the product reads no environment variables).
-UNREACHABLE = {
-    "fr_fused_tile_kernel<2, 44, 2, true>": "K = 352 fits the single-buffer layout in 80 KiB, so fused_wpe always picks WPE 4 for it",
-    "fc_lp_gemm_kernel<0, 1, 64, 4, 8, 32>": "the 4-stage 64 x 128 tile is taken in bf16 only (2 stages in fp32 / fp8)",
-    "fc_lp_gemm_kernel<2, 1, 64, 4, 8, 32>": "the 4-stage 64 x 128 tile is taken in bf16 only (2 stages in fp32 / fp8)",
-    "fc_lp_gemm_kernel<1, 1, 64, 2, 8, 32>": "bf16 64 x 128 tiles always take 4 stages",
-    **{"fc_gemm_pipe_kernel<%d, %d, %d>" % (p, ns, g): "128 x 256 low-precision layers with KE/8 >= 3 take fc_pp_gemm_n128_kernel first and "
-       "pipe_shape_ok needs KE >= 40 (fp8 also needs an experiments-build knob)" for p in (1, 2) for ns, g in ((3, 2), (4, 1), (5, 1), (6, 1))},
-}
+UNREACHABLE = {}
 
 
 def named_kernels():

@@ -43,11 +43,11 @@ def test_exports_every_declared_symbol(fr):
 
 
 def test_product_library_reads_no_environment_variable(fr):
-    """the experiment knobs (FR_GEMM_ABLATE -- wrong results by design --, FR_GATHER_*, FR_FUSED_*, ...) exist only
+    """the experiment knobs (FR_PP_ABLATE -- wrong results by design --, FR_GATHER_*, FR_FUSED_*, ...) exist only
     in the -DFR_EXPERIMENTS build (`make -C csrc exp` -> libfleetrec_exp.so); the shipped library carries none of their names and does
     not import getenv at all (the GPU suite additionally checks that setting them changes no score bit)."""
     blob = open(fr.LIB_PATH, "rb").read()
-    for name in (b"FR_GEMM_ABLATE", b"FR_GEMM_ORDER", b"FR_GEMM_PRIO", b"FR_GEMM_PIPE", b"FR_GATHER_", b"FR_FUSED\0", b"FR_FUSED_HK", b"FR_FUSED_HS_ABLATE", b"FR_LP_GEMM_SPLITK", b"fc_splitk_gemm", b"FR_FUSED_GROUP", b"FR_FUSED_ITEMS",
+    for name in (b"FR_GEMM_ABLATE", b"FR_GEMM_ORDER", b"FR_GEMM_PRIO", b"FR_GEMM_PIPE", b"FR_GATHER_", b"FR_FUSED\0", b"FR_FUSED_HK", b"FR_FUSED_HS_ABLATE", b"FR_LP_GEMM_SPLITK", b"fc_splitk_gemm", b"fc_gemm_pipe", b"fc_gemm_gather", b"FR_PP_ABLATE", b"FR_FUSED_GROUP", b"FR_FUSED_ITEMS",
                  b"FR_FUSED_M2", b"FR_FUSED_WPE", b"FR_FUSED_R1D", b"FR_LP_GEMM", b"FR_SUBMIT_ZEROCOPY", b"FR_SMALL_BLOCK_SERIAL"):
         assert name not in blob, name     # (FR_FUSED_MAX_QUEUE, a constant's name inside an error string, is not a variable)
     und = subprocess.check_output(["nm", "-D", "--undefined-only", fr.LIB_PATH]).decode()
@@ -169,7 +169,7 @@ def test_lds_dma_kernels_touch_m0_only_through_the_asm(fr, tmp_path):
                     assert re.match(r"s_mov_b32 m0, s\d+$", t), "%s: unexpected M0 user `%s`" % (name, t)
             for k in dma:
                 assert k > 0 and re.match(r"s_mov_b32 m0, s\d+$", ins[k - 1]), "%s: LDS-DMA load not directly behind its M0 write: `%s` / `%s`" % (name, ins[k - 1], ins[k])
-    assert n_kernels >= 6 and n_loads >= 100, (n_kernels, n_loads)   # the fc_lp_gemm / fc_gemm_pipe instantiations of three precisions
+    assert n_kernels >= 6 and n_loads >= 100, (n_kernels, n_loads)   # the fc_lp_gemm / fc_lp_gemm_out / fc_pp_gemm instantiations: 19 LDS-DMA GEMM kernels
 
 def test_phased_waves_kernels_keep_their_mfmas_between_the_barriers(fr, tmp_path):
     """fc_pp_gemm_kernel / fc_pp_gemm_n128_kernel split a K sub-step into a fetching and a multiplying phase fenced by s_barrier, with the two

@@ -466,14 +466,14 @@ def test_committed_fc_fixtures_on_device(fr, O, ctxs, which):
 
 @pytest.mark.gpu
 def test_environment_cannot_change_a_score(fr, ctxs):
-    """the shipped library reads no environment variable -- the experiment knobs (among them FR_GEMM_ABLATE, whose
-    values make fc_gemm_pipe_kernel compute WRONG results on purpose) are compiled into libfleetrec_exp.so only.  Model-C batch 4096 bf16
-    (the path through that GEMM kernel) and Model-B bf16 through the fused kernels, with the variables set to their most destructive
+    """the shipped library reads no environment variable -- the experiment knobs (among them FR_PP_ABLATE, whose
+    values make the phased-waves GEMM kernels compute WRONG results on purpose) are compiled into libfleetrec_exp.so only.  Model-C batch 4096
+    bf16 (FC1 runs fc_pp_gemm_n128_kernel; the knobs of GEMM kernels that have since been removed stay in the list) and Model-B bf16 through the fused kernels, with the variables set to their most destructive
     values: bit-identical scores."""
     if os.path.basename(fr.LIB_PATH) != "libfleetrec.so":
         pytest.skip("FR_LIB points at another build")
     rng = np.random.default_rng(5)
-    knobs = {"FR_GEMM_ABLATE": "2", "FR_GEMM_ORDER": "0", "FR_GEMM_PRIO": "0", "FR_GEMM_PIPE": "0", "FR_LP_GEMM": "0", "FR_GATHER_STREAM": "0", "FR_GATHER_ITEMS": "16",
+    knobs = {"FR_PP_ABLATE": "4", "FR_GEMM_ABLATE": "2", "FR_GEMM_ORDER": "0", "FR_GEMM_PRIO": "0", "FR_GEMM_PIPE": "0", "FR_LP_GEMM": "0", "FR_GATHER_STREAM": "0", "FR_GATHER_ITEMS": "16",
              "FR_GATHER_XCD": "0", "FR_FUSED": "0", "FR_FUSED_HK": "0", "FR_FUSED_GROUP": "1", "FR_SUBMIT_ZEROCOPY": "0", "FR_GATHER_TR": "0"}
     for which, B in ((2, 4096), (1, 1024)):
         m, ctx = ctxs(which)

@@ -1,4 +1,4 @@
-// What a bf16 MFMA loop can reach on this chip, built up in the steps of fc_gemm_pipe_kernel's inner loop (random operands,
+// What a bf16 MFMA loop can reach on this chip, built up in the steps of a software-pipelined 128 x 256 GEMM tile's inner loop (random operands,
 // 256 workgroups x 8 waves, 16 accumulators of v_mfma_f32_16x16x32_bf16 or 4 of 32x32x16 per wave = a 64 x 64 wave tile):
 //   mode 0: MFMAs only, operands in registers
 //   mode 1: + 8 ds_read_b128 fragment reads per 16 MFMAs (double-buffered: reads of block i+1 beside the MFMAs of block i)
