@@ -306,7 +306,7 @@ static int gather_launch_xcd(const FrWordDesc *words, const FrGatherGroups &grou
 #endif
     gather_pack_xcd_kernel<ITEMS, TP><<<grid, dim3(bx), 0, s>>>(words, groups, idx, idx_stride, dense, out, batch, err_flag, scale, n_chunks);
     KCHECK();
-    fr_note_kernel("gather_pack_xcd_kernel<%d, %d>", ITEMS, TP);
+    fr_note_kernel("gather_pack_xcd_kernel<%d, %d, 0>", ITEMS, TP);   // the symbol's three arguments (AUX = 0), as rocprofv3 prints it
     return FR_OK;
 }
 

@@ -201,7 +201,9 @@ def rounding_witnesses(prec, rec, ws, act_exp=None, w_exp=None):
 # ---- the GPU matrix: (model, precision, batch, chain width, stream group) -> the kernels fr_worker_last_kernel must report ----------------
 # MODELS: name -> (K, hidden widths, dense_len).  A case's `stream` is the kernel of the streamed launch (push_device with `group` batches
 # queued; None = the stage pipeline, which no hook names), `layers` what fc_layer_only(batch, l) reports for l = 0..3 (None: not asserted),
-# `runs` the stage-pipeline kernels its submits and pushes launch that no hook reports.
+# `runs` the stage-pipeline kernels its submits and pushes launch that no hook reports, `gather_out` (one of them) what the fifth of five pushes
+# in flight launches: the gather of the fifth batch and the output layer of the first in one launch, every FC layer between them a GEMM launch
+# (fr_api.cpp pipeline_step, fr_pipeline.hip pipeline_launch_prec; a push on the stage pipeline leaves fr_worker_last_kernel untouched).
 MODELS = {
     "A352": (352, (1024, 512, 256), 0),
     "B880": (880, (1024, 512, 256), 16),
@@ -217,6 +219,7 @@ MODELS = {
     "K128": (128, (2048, 512, 256), 0),
     "K256": (256, (2048, 512, 256), 0),
     "N192": (512, (192, 256, 256), 0),
+    "R": (3968, (2048, 512, 512), 16),
 }
 
 
@@ -260,12 +263,16 @@ CASES = [
            runs=[PIPE % (0, i)] + ([PIPE % (-1, i)] if b >= 33 else []))
       for i, p in enumerate(PRECS) for b in ((1, 31, 33, 65, 200) if p == "f32" else (33, 65))],
     # GEMM tiles on the full chip (W = 1) at batch 4096: 128 x 256 FC1, 64 x 128 FC2, FC3 + output layer in one launch (bf16 / fp8)
-    dict(id="f32-C-4096", model="C", prec="f32", batch=4096, width=1, group=1, stream=None,
+    dict(id="f32-C-4096", model="C", prec="f32", batch=4096, width=1, group=1, stream=None, gather_out="fr_gather_out_kernel<0>",
          layers=["fc_lp_gemm_kernel<0, 2, 128, 2, 8, 32>", "fc_lp_gemm_kernel<0, 1, 64, 2, 8, 32>", "fc_lp_gemm_kernel<0, 1, 64, 2, 8, 32>", PIPE % (4, 0)]),
     dict(id="bf16-C-4096", model="C", prec="bf16", batch=4096, width=1, group=1, stream=None,
          layers=["fc_pp_gemm_n128_kernel<1, 2>", "fc_lp_gemm_kernel<1, 1, 64, 4, 8, 32>", "fc_lp_gemm_out_kernel<1, 2>", PIPE % (4, 1)]),
     dict(id="fp8-C-4096", model="C", prec="fp8", batch=4096, width=1, group=1, stream=None,
          layers=["fc_pp_gemm_n128_kernel<2, 2>", "fc_lp_gemm_kernel<2, 1, 64, 2, 8, 32>", "fc_lp_gemm_out_kernel<2, 2>", PIPE % (4, 2)]),
+    # FC3 with 512 outputs: a GEMM launch (64 x 128 tiles), but no fused FC3 + output tail (that one takes 256 outputs) -- the output layer stays a
+    # stage of the pipeline, so five batches in flight launch fr_gather_out_kernel in bf16 and fp8 too
+    *[dict(id="%s-R-4096" % p, model="R", prec=p, batch=4096, width=1, group=1, stream=None, gather_out="fr_gather_out_kernel<%d>" % i,
+           layers=[None, None, None, PIPE % (4, i)]) for i, p in ((1, "bf16"), (2, "fp8"))],
     # 128 x 128 tiles: ldm 1664 = 13 * 128 (26 pad items)
     *[dict(id="%s-C-1638" % p, model="C", prec=p, batch=1638, width=1, group=1, stream=None,
            layers=["fc_lp_gemm_kernel<%d, 1, 128, 2, 8, 32>" % i, PIPE % (2, i), PIPE % (3, i), PIPE % (4, i)]) for i, p in enumerate(PRECS)],
@@ -298,6 +305,8 @@ def named_kernels():
         out.update(c.get("runs") or [])
         if c.get("stream"):
             out.add(c["stream"])
+        if c.get("gather_out"):
+            out.add(c["gather_out"])
         out.update(n for n in (c.get("layers") or []) if n)
     return out
 

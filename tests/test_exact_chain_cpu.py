@@ -198,7 +198,7 @@ def _fc_chain_kernels(fr):
     names = {E.demangle(r["name"]) for r in KR.kernel_records(fr.LIB_PATH)}
     if not names:
         pytest.skip("no gfx950 code objects found in %s" % fr.LIB_PATH)
-    return {n for n in names if n.startswith(("fr_fused_tile", "fr_pipeline_kernel")) or (n.startswith("fc_") and "gemm" in n)}
+    return {n for n in names if n.startswith(("fr_fused_tile", "fr_pipeline_kernel", "fr_gather_out_kernel")) or (n.startswith("fc_") and "gemm" in n)}
 
 
 def test_every_fc_chain_kernel_is_accounted_for(fr):

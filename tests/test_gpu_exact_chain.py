@@ -91,6 +91,41 @@ def test_exact_case(fr, gpu, case):
         ctx.close()
 
 
+OUT_CASES = [c for c in E.CASES if c.get("gather_out")]
+
+
+@pytest.mark.parametrize("case", OUT_CASES, ids=[c["id"] for c in OUT_CASES])
+def test_exact_gather_out_launch(fr, gpu, case):
+    """Five pushes in flight on a chain whose FC layers are GEMM launches and whose output layer is a pipeline stage: the fifth push's step
+    is the gather of batch 5 and the output layer of batch 1 in ONE launch, fr_gather_out_kernel<P> (named by the case as a kernel no hook
+    reports: pushes on the stage pipeline leave fr_worker_last_kernel alone) -- every score of all five batches bit-exact, nothing written
+    past the batch."""
+    m, ctx, data, idx, dense, rec = _setup(fr, gpu, case)
+    B, ws = case["batch"], data["ws"]
+    ldm = (B + 31) // 32 * 32
+    wk = fr.Worker(ctx, B)
+    try:
+        want, _, _ = _expect(case, ctx, wk, idx, dense, rec, ws)
+        ctx.set_stream_group(case["group"])
+        d_i = fr.DeviceBuffer.from_numpy(ctx, np.ascontiguousarray(idx))
+        d_d = fr.DeviceBuffer.from_numpy(ctx, np.ascontiguousarray(dense)) if dense is not None else None
+        outs = []
+        for _ in range(5):
+            o = fr.DeviceBuffer(ctx, ldm * 4)
+            o.upload(np.full(ldm, np.nan, np.float32))
+            wk.push_device(B, d_i, d_d, o)
+            outs.append(o)
+        wk.sync()
+        for j, o in enumerate(outs):
+            got = o.download(np.float32, ldm)
+            _same(got[:B], want, "push %d of 5" % j)
+            assert np.isnan(got[B:]).all(), "push %d of 5 wrote past the batch" % j
+            o.free()
+    finally:
+        wk.close()
+        ctx.close()
+
+
 NAN_CASES = [c for c in E.CASES if c["id"] in ("bf16-C-4096", "f32-C-4096")]
 
 

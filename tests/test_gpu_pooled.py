@@ -48,7 +48,8 @@ def test_one_hot_identity_blocked_and_full_size(fr, gpu, ctxs):
                                                 (2, "table", True), (0, "item", False), ("spec", "table", False), ("spec", "bank", False),
                                                 ("spec", "item", False)])
 def test_even_odd_known_answer(fr, gpu, kind, mode, blocked):
-    """Check 2, mixed bags (hots 1 .. 64: the 8-slot window looped) and uniform bags of 4 and of 16 (16-byte index loads)."""
+    """Check 2, mixed bags (spread_hots, 1 .. 64: the 16-slot window looped, 4-byte index loads) and uniform bags of 2 (the 2-slot window),
+    of 4 and of 16 (16-byte index loads).  The 8-slot window and every other form: tests/test_gpu_gather_matrix.py::test_pooled_case."""
     m = P.make_model(fr, kind, index_mode=MODES[mode], layout=fr.LAYOUT_BLOCKED if blocked else None, max_rows=30000)
     ctx = fr.Context(m, device=gpu)
     try:
