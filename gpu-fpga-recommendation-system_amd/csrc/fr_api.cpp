@@ -778,7 +778,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->ctx && w->ctx->cpu) {
         fr_comm_worker_release(w);   // a sharded step still on the worker's host stream: waited for (bounded), its communicator let go
         if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
-        void *host[] = {w->h_idx, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
+        void *host[] = {w->h_idx, w->h_pool_w, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
         for (void *p : host) free(p);
         fr_ctx *held = w->counted ? w->ctx : nullptr;
         delete w;
@@ -790,6 +790,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->stream) (void)hipStreamSynchronize(w->stream);
     if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
     if (w->h_idx) (void)hipHostFree(w->h_idx);
+    if (w->h_pool_w) (void)hipHostFree(w->h_pool_w);
     if (w->h_dense) (void)hipHostFree(w->h_dense);
     if (w->h_score) (void)hipHostFree(w->h_score);
     if (w->h_err) (void)hipHostFree(w->h_err);
@@ -859,15 +860,17 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     const size_t B = (size_t)max_batch;
     // the index buffers hold one-hot rows and, when pooling is set already, pooled rows (fr_worker_submit_pooled)
     w->idx_cap = (int)idx_cols(ctx) > ctx->pool_cols ? (int)idx_cols(ctx) : ctx->pool_cols;
+    w->pool_w_cap = ctx->pool_cols;   // per-sample weights of the host form (fr_worker_submit_pooled_weighted): only when pooling is set already
     if (ctx->cpu) {   // the CPU back-end: plain host buffers behind the same accessors (fr_worker_idx_ptr / dense_ptr / score_ptr)
         auto host = [](size_t bytes) { return aligned_alloc(64, align_up(bytes ? bytes : 64, 64)); };
         w->h_idx = (int32_t *)host(B * (size_t)w->idx_cap * sizeof(int32_t));
+        if (w->pool_w_cap) w->h_pool_w = (float *)host(B * (size_t)w->pool_w_cap * sizeof(float));
         if (m.dense_len) w->h_dense = (float *)host(B * m.dense_len * sizeof(float));
         w->h_score = (float *)host(B * sizeof(float));
         w->d_records = (float *)host(B * (size_t)ctx->slice_padded * sizeof(float));
         w->c_scratch = (float *)host(B * ((size_t)m.fc[1] + m.fc[2] + m.fc[3]) * sizeof(float));
         if (ctx->n_shards > 1) w->c_x = (float *)host(B * (size_t)m.fc[0] * sizeof(float));
-        if (!w->h_idx || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
+        if (!w->h_idx || (w->pool_w_cap && !w->h_pool_w) || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
             fr_worker_destroy(w);
             FR_FAIL(FR_ERR_OOM, "out of host memory (worker buffers for batch %d)", max_batch);
         }
@@ -908,6 +911,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
         else W_HIP(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
     }
     W_HIP(hipHostMalloc((void **)&w->h_idx, B * (size_t)w->idx_cap * sizeof(int32_t), hipHostMallocDefault));
+    if (w->pool_w_cap) W_HIP(hipHostMalloc((void **)&w->h_pool_w, B * (size_t)w->pool_w_cap * sizeof(float), hipHostMallocDefault));   // read in place by the gather, like h_idx
     if (m.dense_len) W_HIP(hipHostMalloc((void **)&w->h_dense, B * m.dense_len * sizeof(float), hipHostMallocDefault));
     W_HIP(hipHostMalloc((void **)&w->h_score, B * sizeof(float), hipHostMallocDefault));
     // index-range flag: pinned, device-visible host word.  Kernels touch it only on the error path
@@ -943,6 +947,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
 }
 
 extern "C" int32_t *fr_worker_idx_ptr(fr_worker *w) { return w ? w->h_idx : nullptr; }
+extern "C" float *fr_worker_pool_weights_ptr(fr_worker *w) { return w ? w->h_pool_w : nullptr; }
 extern "C" float *fr_worker_dense_ptr(fr_worker *w) { return w ? w->h_dense : nullptr; }
 extern "C" float *fr_worker_score_ptr(fr_worker *w) { return w ? w->h_score : nullptr; }
 extern "C" void *fr_worker_stream(fr_worker *w) { return w ? (void *)w->stream : nullptr; }
@@ -1653,43 +1658,32 @@ extern "C" int fr_worker_gather_only(fr_worker *w, int batch, const int32_t *d_i
 
 // ---- multi-hot pooled lookups (fleetrec_serving.h) -------------------------------------------------------
 // Pooling is stated per index column; the pooled descriptors (one FrPoolDesc per FrWordDesc) follow from h_words: a TABLE / COPY word's bag
-// is its index column's, a DENSE word is a bag of one.
-extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+// is its index column's, a DENSE word is a bag of one.  The column's mode (fr_ctx_set_pooling_modes) rides in the descriptor's hots word.
+static int pooling_busy(fr_ctx *ctx, const char *who) {
+    std::lock_guard<std::mutex> g(ctx->workers_mutex);
+    for (const fr_worker *w : ctx->workers)
+        if (w->in_flight || w->n_active || w->n_pending || w->sh_comm)
+            FR_FAIL(FR_ERR_STATE, "%s: a worker of the context has work in flight: call fr_worker_sync first", who);
+    return FR_OK;
+}
+
+// the descriptors of hots[] x modes[] (modes == NULL: every column SUM), uploaded; the context's copies are replaced only when all of it worked
+static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *modes) {
     const int cols = (int)idx_cols(ctx);
-    if (hots) {
-        if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: n_cols %d, the context has %d index columns", n_cols, cols);
-        for (int c = 0; c < cols; c++)
-            if (hots[c] < 1 || hots[c] > FR_POOL_MAX_HOTS) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: hots[%d] = %d outside [1, %d]", c, hots[c], FR_POOL_MAX_HOTS);
-    }
-    {
-        std::lock_guard<std::mutex> g(ctx->workers_mutex);
-        for (const fr_worker *w : ctx->workers)
-            if (w->in_flight || w->n_active || w->n_pending || w->sh_comm)
-                FR_FAIL(FR_ERR_STATE, "fr_ctx_set_pooling: a worker of the context has work in flight: call fr_worker_sync first");
-    }
-    if (!ctx->cpu) FR_SET_DEVICE(ctx);
-    if (!hots) {
-        if (ctx->d_pool) FR_HIP(hipFree(ctx->d_pool));
-        ctx->d_pool = nullptr;
-        ctx->h_pool.clear();
-        ctx->pool_cols = ctx->pool_max_hots = 0;
-        ctx->pool_wide = false;
-        return FR_OK;
-    }
     std::vector<uint32_t> prefix(cols + 1, 0);
     int max_hots = 1;
-    bool wide = true;
+    bool wide = true, any_mean = false;
     for (int c = 0; c < cols; c++) {
         prefix[c + 1] = prefix[c] + (uint32_t)hots[c];
         max_hots = hots[c] > max_hots ? hots[c] : max_hots;
         wide = wide && hots[c] % 4 == 0;   // then every bag starts on a multiple of 4 slots too, and so does every item's row
+        any_mean = any_mean || (modes && modes[c] == FR_POOL_MEAN);
     }
     std::vector<FrPoolDesc> pool(ctx->h_words.size());
     for (size_t i = 0; i < pool.size(); i++) {
         const uint32_t col = ctx->h_words[i].idx_col;
-        pool[i] = (col & FR_DESC_DENSE) ? FrPoolDesc{0u, 1u} : FrPoolDesc{prefix[col], (uint32_t)hots[col]};
+        pool[i] = (col & FR_DESC_DENSE) ? FrPoolDesc{0u, 1u}
+                                        : FrPoolDesc{prefix[col], (uint32_t)hots[col] | (modes && modes[col] == FR_POOL_MEAN ? FR_POOL_DESC_MEAN : 0u)};
     }
     if (!ctx->cpu) {
         FrPoolDesc *d = nullptr;
@@ -1702,60 +1696,133 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
         if (ctx->d_pool) (void)hipFree(ctx->d_pool);
         ctx->d_pool = d;
     }
+    std::vector<int32_t> h(hots, hots + cols), md(cols, FR_POOL_SUM);   // (hots may be ctx->pool_hots itself: copied before it is replaced)
+    if (modes) md.assign(modes, modes + cols);
     ctx->h_pool.swap(pool);
+    ctx->pool_hots.swap(h);
+    ctx->pool_modes.swap(md);
+    ctx->pool_any_mean = any_mean;
     ctx->pool_cols = (int)prefix[cols];
     ctx->pool_max_hots = max_hots;
     ctx->pool_wide = wide;
     return FR_OK;
 }
 
+extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    const int cols = (int)idx_cols(ctx);
+    if (hots) {
+        if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: n_cols %d, the context has %d index columns", n_cols, cols);
+        for (int c = 0; c < cols; c++)
+            if (hots[c] < 1 || hots[c] > FR_POOL_MAX_HOTS) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: hots[%d] = %d outside [1, %d]", c, hots[c], FR_POOL_MAX_HOTS);
+    }
+    const int rc = pooling_busy(ctx, "fr_ctx_set_pooling");
+    if (rc) return rc;
+    if (!ctx->cpu) FR_SET_DEVICE(ctx);
+    if (!hots) {
+        if (ctx->d_pool) FR_HIP(hipFree(ctx->d_pool));
+        ctx->d_pool = nullptr;
+        ctx->h_pool.clear();
+        ctx->pool_hots.clear();
+        ctx->pool_modes.clear();
+        ctx->pool_any_mean = false;
+        ctx->pool_cols = ctx->pool_max_hots = 0;
+        ctx->pool_wide = false;
+        return FR_OK;
+    }
+    return pooling_install(ctx, hots, nullptr);   // every mode is SUM again
+}
+
+extern "C" int fr_ctx_set_pooling_modes(fr_ctx *ctx, const int32_t *modes, int n_cols) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    if (ctx->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    const int cols = (int)idx_cols(ctx);
+    if (modes) {
+        if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling_modes: n_cols %d, the context has %d index columns", n_cols, cols);
+        for (int c = 0; c < cols; c++)
+            if (modes[c] != FR_POOL_SUM && modes[c] != FR_POOL_MEAN) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling_modes: modes[%d] = %d is no pooling mode", c, modes[c]);
+    }
+    const int rc = pooling_busy(ctx, "fr_ctx_set_pooling_modes");
+    if (rc) return rc;
+    if (!ctx->cpu) FR_SET_DEVICE(ctx);
+    return pooling_install(ctx, ctx->pool_hots.data(), modes);   // the descriptors are rebuilt and uploaded again
+}
+
+extern "C" int fr_ctx_pooling_mode(const fr_ctx *ctx, int col) {
+    if (!ctx || col < 0 || (size_t)col >= ctx->pool_modes.size()) return FR_POOL_SUM;
+    return ctx->pool_modes[(size_t)col];
+}
+
 extern "C" int fr_ctx_pooled_index_cols(const fr_ctx *ctx) { return ctx ? ctx->pool_cols : 0; }
 
-static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
+// weighted = the call is one of the *_weighted entry points: d_weights must be there, and every column's mode SUM
+static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records) {
     fr_ctx *c = w->ctx;
     if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
     if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
     if (!d_idx) FR_FAIL(FR_ERR_INVALID, "d_idx is NULL");
+    if (weighted) {
+        if (!d_weights) FR_FAIL(FR_ERR_INVALID, "d_weights is NULL");
+        if (c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
+    }
     if (c->model.dense_len && !d_dense) {
         bool needs = false;
         for (const FrWordDesc &wd : c->h_words) needs |= (wd.idx_col & FR_DESC_DENSE) != 0;
         if (needs) FR_FAIL(FR_ERR_INVALID, "model has dense features but d_dense is NULL");
     }
-    if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, c->pool_cols, d_dense, d_records, batch, &w->c_err);
-    return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, c->pool_cols, c->pool_max_hots, c->pool_wide, d_dense, d_records, batch, w->d_err,
-                             w->stream, c->slice_padded / 4);
+    if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err);
+    return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, c->pool_wide, c->pool_any_mean, d_dense, d_records, batch,
+                             w->d_err, w->stream, c->slice_padded / 4);
 }
 
-extern "C" int fr_worker_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
+static int gather_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records) {
     int rc = check_ready(w, batch, true, false);
     if (rc) return rc;
     if (!d_records) FR_FAIL(FR_ERR_INVALID, "d_records is NULL");
     FR_SET_DEVICE(w->ctx);
-    rc = launch_gather_pooled(w, batch, d_idx, d_dense, d_records);
+    rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, d_records);
     if (rc) return rc;
     keep_kernel(w);
     w->in_flight = true;
     return FR_OK;
 }
 
+extern "C" int fr_worker_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
+    return gather_pooled_impl(w, batch, d_idx, nullptr, false, d_dense, d_records);
+}
+
+extern "C" int fr_worker_gather_pooled_weighted(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_records) {
+    return gather_pooled_impl(w, batch, d_idx, d_weights, true, d_dense, d_records);
+}
+
 // pooled records into the worker's record buffer, then the chain fr_worker_fc_only runs from records (launch_fc), on the same stream
-static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
+static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores) {
     if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
-    int rc = launch_gather_pooled(w, batch, d_idx, d_dense, w->d_records);
+    int rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records);
     if (rc) return rc;
     w->in_flight = true;   // the gather is enqueued whatever the chain's launch says
     return launch_fc(w, batch, w->d_records, d_scores);
 }
 
-extern "C" int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
+static int submit_pooled_device_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores) {
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
     if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
     FR_SET_DEVICE(w->ctx);
-    return submit_pooled_impl(w, batch, d_idx, d_dense, d_scores);
+    return submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores);
 }
 
-extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) {
+extern "C" int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
+    return submit_pooled_device_impl(w, batch, d_idx, nullptr, false, d_dense, d_scores);
+}
+
+extern "C" int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores) {
+    return submit_pooled_device_impl(w, batch, d_idx, d_weights, true, d_dense, d_scores);
+}
+
+static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
     if (w->in_flight) FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
@@ -1763,10 +1830,15 @@ extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) {
     if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
     if (w->idx_cap < c->pool_cols)
         FR_FAIL(FR_ERR_STATE, "the worker's index buffers hold %d columns per item, pooled rows have %d: create the worker after fr_ctx_set_pooling", w->idx_cap, c->pool_cols);
+    if (weighted && (!w->h_pool_w || w->pool_w_cap < c->pool_cols))
+        FR_FAIL(FR_ERR_STATE, "the worker's weight buffer holds %d columns per item, pooled rows have %d: create the worker after fr_ctx_set_pooling", w->pool_w_cap, c->pool_cols);
     FR_SET_DEVICE(c);
-    // as fr_worker_submit: the gather reads the pinned index rows (and dense features) in place, the output layer writes the pinned scores
-    return submit_pooled_impl(w, batch, w->h_idx, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
+    // as fr_worker_submit: the gather reads the pinned index rows (weights, dense features) in place, the output layer writes the pinned scores
+    return submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
 }
+
+extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, false); }
+extern "C" int fr_worker_submit_pooled_weighted(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, true); }
 
 // Sharded mode, low-precision transport: the shard's slice [batch][slice_padded] as bf16 or e4m3 (x 2^e of the context's X exponent)
 // instead of fp32 -- what travels through the all-gather.  transport = FR_FC_FP32 is fr_worker_gather_only.

@@ -256,8 +256,15 @@ int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx
 
 // The pooled (multi-hot) gather, exactly as gather_pooled_kernel (fr_gather.hip) folds a bag: slot -1 is empty, the first non-empty slot's
 // row word is taken as a bit copy, every further one is added to it in fp32, one add per lane, in ascending slot order; an all-empty
-// bag gives +0.0f.  Plain IEEE adds on both sides (no fast-math in either build): the records are bit-identical to the GPU's.
-int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, int pool_cols, const float *dense, float *out, int batch, int *err_flag) {
+// bag gives +0.0f.  A MEAN word (FR_POOL_DESC_MEAN in its descriptor) is that fold divided once by the count of non-empty slots when the
+// count is 2 or more.  With weights (float [batch][pool_cols], parallel to idx) every non-empty slot's word is first multiplied by the slot's
+// weight -- a product rounded to fp32 on its own; the product build compiles this file for baseline x86-64, which has no FMA to contract into,
+// and fp-contract=off below only keeps that true should the file ever be built with -mfma / -march -- and the first product starts the accumulator; an empty slot's weight is never read.  Plain IEEE operations on both sides (no
+// fast-math in either build): the records are bit-identical to the GPU's (a NaN's payload excepted).
+#pragma GCC push_options
+#pragma GCC optimize("fp-contract=off")
+int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
+                      int *err_flag) {
     const int chunk = 32;
     std::atomic<int> bad{0};
     char *o = reinterpret_cast<char *>(out);
@@ -266,6 +273,7 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
         int local_bad = 0;
         for (int b = b0; b < b1; b++) {
             const int32_t *row = idx + (size_t)b * pool_cols;
+            const float *wrow = weights ? weights + (size_t)b * pool_cols : nullptr;
             for (int w = 0; w < n_words; w++) {
                 const FrWordDesc &d = words[w];
                 char *dst = o + ((size_t)d.dst_blk * (size_t)batch + (size_t)b * d.dst_stride + d.dst_off) * 16;
@@ -273,9 +281,10 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
                     memcpy(dst, reinterpret_cast<const char *>(dense) + d.src + (size_t)b * d.stride, 16);
                     continue;
                 }
+                const uint32_t hots = pool[w].hots & ~FR_POOL_DESC_MEAN;
                 uint32_t acc[4] = {0u, 0u, 0u, 0u};
-                bool have = false;
-                for (uint32_t j = 0; j < pool[w].hots; j++) {
+                uint32_t cnt = 0;
+                for (uint32_t j = 0; j < hots; j++) {
                     uint32_t r = (uint32_t)row[pool[w].first + j];
                     if (r == 0xFFFFFFFFu) continue;   // an empty slot
                     if (r >= d.rows) {
@@ -284,8 +293,17 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
                     }
                     uint32_t x[4];
                     memcpy(x, reinterpret_cast<const char *>(d.src) + (uint64_t)r * d.stride, 16);
+                    if (wrow) {
+                        const float wj = wrow[pool[w].first + j];
+                        for (int k = 0; k < 4; k++) {
+                            float v;
+                            memcpy(&v, &x[k], 4);
+                            v = wj * v;
+                            memcpy(&x[k], &v, 4);
+                        }
+                    }
                     for (int k = 0; k < 4; k++) {
-                        if (have) {
+                        if (cnt) {
                             float a, v;
                             memcpy(&a, &acc[k], 4);
                             memcpy(&v, &x[k], 4);
@@ -295,7 +313,16 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
                             acc[k] = x[k];
                         }
                     }
-                    have = true;
+                    cnt++;
+                }
+                if ((pool[w].hots & FR_POOL_DESC_MEAN) && cnt > 1) {
+                    const float n = (float)cnt;
+                    for (int k = 0; k < 4; k++) {
+                        float a;
+                        memcpy(&a, &acc[k], 4);
+                        a = a / n;
+                        memcpy(&acc[k], &a, 4);
+                    }
                 }
                 memcpy(dst, acc, 16);
             }
@@ -305,6 +332,7 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
     if (bad.load() && err_flag) __atomic_store_n(err_flag, 1, __ATOMIC_RELEASE);
     return FR_OK;
 }
+#pragma GCC pop_options
 
 // ---- the FC chain: 4 x cublasLtMatmul, alpha = 1, beta = 0, no bias, no activation (cuda_server.c:211-217,468-491) ---------------------
 // Y[b][h] = sum over k, IN k ORDER, of W[h + k * H] * X[b][k], each step one fused multiply-add in fp32.  A tile of MB items x HT outputs

@@ -385,16 +385,24 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
 // (workgroup b serves group b % n_groups and chunk b / n_groups; n_groups = 8, or 1 for records too narrow for a plan); blockIdx.y walks
 // a group wider than one workgroup.
 // ---------------------------------------------------------------------------------------------------
-template <int ITEMS, int WIN, bool WIDE>
-__global__ void __launch_bounds__(256) gather_pooled_kernel(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, const FrGatherGroups groups,
-                                                            int n_groups, const int32_t *__restrict__ idx, int pool_cols, const float *__restrict__ dense,
-                                                            void *__restrict__ out, int batch, int *__restrict__ err_flag, unsigned out_bytes) {
+// The fold has three forms (fleetrec_serving.h).  SUM: as above.  MEAN (bit FR_POOL_DESC_MEAN of the word's `hots`): the SUM fold, then ONE IEEE fp32
+// division by the bag's count of non-empty slots, under a per-lane predicate (count >= 2: a bag of one stays a bit copy, an empty one +0.0f;
+// DENSE words never carry the bit).  WEIGHTED (weights != NULL: float [batch][pool_cols], a slot's weight sits where the slot sits): the
+// window's weights are loaded exactly as its slots are (the same offsets through a resource of their own, 16-byte loads in the WIDE form,
+// masked past the lane's bag), every row word is multiplied by its weight -- one v_mul_f32 per lane, rounded on its own: contraction is off
+// in this body, the product and the add that follows are never an FMA -- and the FIRST non-empty slot's product starts the accumulator
+// (not a bit copy).  An empty slot's weight is dropped by the same select that drops its word; DENSE words are copied unweighted.
+// `weights` and `any_mean` (a column of the context is MEAN) are uniform over the launch: the kernel branches on them once, around the whole
+// body, so the unweighted SUM window loop holds no trace of weights, counts or quotients.  A kernel's register count is that of its larger arm, and it decides the occupancy of both: the weighted arm
+// therefore runs the chunk in two passes of half as many row words in flight (gather_pooled_kernel below) and takes its weights in units of
+// at most 4 slots, one unit ahead of the fold, so that it stays inside the unweighted arm's registers (no spill, no scratch in either).
+template <int ITEMS, int WIN, bool WIDE, bool WEIGHTED, bool COUNT>
+__device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, int w, unsigned b0,
+                                                   const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
+                                                   const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
+                                                   unsigned out_bytes) {
+#pragma clang fp contract(off)
     static_assert(!WIDE || WIN % 4 == 0, "16-byte index loads need whole groups of 4 slots");
-    const int group = blockIdx.x & (n_groups - 1);
-    const int w0 = groups.start[group];
-    const int t = blockIdx.y * blockDim.x + threadIdx.x;
-    if (t >= groups.start[group + 1] - w0) return;
-    const int w = w0 + t;
     const uint4 d0 = reinterpret_cast<const uint4 *>(words)[2 * w];
     const uint4 d1 = reinterpret_cast<const uint4 *>(words)[2 * w + 1];
     const uint2 pd = reinterpret_cast<const uint2 *>(pool)[w];
@@ -402,20 +410,26 @@ __global__ void __launch_bounds__(256) gather_pooled_kernel(const FrWordDesc *__
     const uint32_t stride = d0.z;
     const bool is_dense = (d0.w & FR_DESC_DENSE) != 0;
     const uint32_t rows = d1.x, dst_off = d1.y, dst_stride = d1.z, dst_blk = d1.w;
-    const uint32_t first = pd.x, hots = pd.y;
+    const uint32_t first = pd.x, hots = pd.y & ~FR_POOL_DESC_MEAN;
+    const bool mean = COUNT && (pd.y & FR_POOL_DESC_MEAN) != 0;
     const uint64_t base = (is_dense ? (uint64_t)reinterpret_cast<uintptr_t>(dense) : 0ull) + src;
     const unsigned blk = (dst_blk * (unsigned)batch + dst_off) * 16u;
     const unsigned ostride = dst_stride * 16u;
     const unsigned irow = (unsigned)pool_cols * 4u;
     const __amdgpu_buffer_rsrc_t rs_idx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, (unsigned)batch * irow, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, out_bytes, 0x00020000);
+    // the weights' resource has the index rows' shape and bounds (WEIGHTED only; the unweighted body never touches it)
+    const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(weights), 0, WEIGHTED ? (unsigned)batch * irow : 0u, 0x00020000);
     typedef const u32x4_t __attribute__((address_space(1))) * gptr_t;   // a global_load (not a flat one)
     bool bad = false;
-    const unsigned b0 = (blockIdx.x / (unsigned)n_groups) * ITEMS;   // the workgroup's chunk of ITEMS items
+    uint32_t badv = 0u;   // WEIGHTED: `bad` as a vector register
     uint4 acc[ITEMS];
     bool have[ITEMS];
+    uint32_t cnt[(ITEMS + 3) / 4];   // COUNT: the MEAN divisors -- non-empty slots folded so far, one byte per item (a bag has at most 64 slots)
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) acc[i] = make_uint4(0u, 0u, 0u, 0u), have[i] = false;
+#pragma unroll
+    for (int i = 0; i < (ITEMS + 3) / 4; i++) cnt[i] = 0u;
     for (uint32_t j0 = 0; j0 < hots; j0 += WIN) {
         // the window's slots: -1 (empty) past the bag; an item past the batch reads past the resource: 0 (row 0; its store is dropped)
         int32_t sl[ITEMS][WIN];
@@ -448,7 +462,12 @@ __global__ void __launch_bounds__(256) gather_pooled_kernel(const FrWordDesc *__
                 uint32_t r = (uint32_t)sl[i][j];
                 on[i][j] = is_dense ? (j0 + j == 0) : (r != 0xFFFFFFFFu);
                 const bool oob = !is_dense & on[i][j] & (r >= rows);  // reference: silent out-of-bounds read (embedding_47_krnl.cpp:927-933)
-                bad |= oob;
+                if constexpr (WEIGHTED) {   // the flag goes to a vector register at once: kept as masks until the window's end, the 16 comparisons
+                    badv |= oob ? 1u : 0u;  // cost 32 scalar registers that the weighted fold (a fourth resource) does not have
+                    asm volatile("" : "+v"(badv));
+                } else {
+                    bad |= oob;
+                }
                 r = oob ? 0u : r;
                 r = is_dense ? (b < (unsigned)batch ? b : 0u) : r;
                 v[i][j] = make_uint4(0u, 0u, 0u, 0u);
@@ -458,54 +477,142 @@ __global__ void __launch_bounds__(256) gather_pooled_kernel(const FrWordDesc *__
                 }
             }
         }
-        // fold in slot order: take the first non-empty word as it is, add every further one
+        // WEIGHTED: the window's weights, loaded as its slots were -- the same offsets and masks through a resource of their own, 16-byte loads
+        // in the WIDE form, an item past the batch reads past the resource -- but in units of G slots, each issued one unit ahead of its fold
+        // (the first behind the row loads): the weights then sit in registers the folded row words have left, not next to a full window
+        constexpr int G = WIN < 4 ? WIN : 4, UPI = WIN / G;   // slots per unit, units per item
+        uint32_t wt[WEIGHTED ? ITEMS : 1][WEIGHTED ? WIN : 1];
+        // the slots left in the lane's bag, through an empty asm: the masks are then compared afresh at each load instead of being kept
+        // from the index loads across the row-load phase (scalar registers the weighted fold does not have)
+        uint32_t left = is_dense ? 0u : hots - j0;
+        if constexpr (WEIGHTED) asm volatile("" : "+v"(left));
+        auto load_weights = [&](int u) {
+            const int i = u / UPI, g = u % UPI;
+            const unsigned woff = (b0 + i) * irow + (first + j0) * 4u + 4u * G * g;
+            if constexpr (WIDE) {
+                u32x4_t w4 = {0u, 0u, 0u, 0u};
+                if (4u * g < left) w4 = __builtin_amdgcn_raw_buffer_load_b128(rs_wt, woff, 0, 0);
+                wt[i][4 * g] = w4.x, wt[i][4 * g + 1] = w4.y, wt[i][4 * g + 2] = w4.z, wt[i][4 * g + 3] = w4.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < G; k++) {
+                    wt[i][G * g + k] = 0u;
+                    if ((unsigned)(G * g + k) < left) wt[i][G * g + k] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_wt, woff + 4u * k, 0, 0);
+                }
+            }
+        };
+        if constexpr (WEIGHTED) load_weights(0);
+        // fold in slot order: take the first non-empty word as it is (WEIGHTED: its product), add every further one
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
 #pragma unroll
             for (int j = 0; j < WIN; j++) {
-                const uint4 a = acc[i], x = v[i][j];
+                if constexpr (WEIGHTED)
+                    if (j % G == 0 && i * UPI + j / G + 1 < ITEMS * UPI) load_weights(i * UPI + j / G + 1);
+                const uint4 a = acc[i];
+                uint4 x = v[i][j];
+                const bool o = on[i][j];
+                if constexpr (WEIGHTED) {   // w * x, rounded to fp32 before the add sees it; a DENSE word stays the bit copy it is
+                    const float wj = __uint_as_float(wt[i][j]);
+                    const uint32_t px = __float_as_uint(wj * __uint_as_float(x.x)), py = __float_as_uint(wj * __uint_as_float(x.y));
+                    const uint32_t pz = __float_as_uint(wj * __uint_as_float(x.z)), pw = __float_as_uint(wj * __uint_as_float(x.w));
+                    x.x = is_dense ? x.x : px, x.y = is_dense ? x.y : py, x.z = is_dense ? x.z : pz, x.w = is_dense ? x.w : pw;
+                }
                 uint4 sum;
                 sum.x = __float_as_uint(__uint_as_float(a.x) + __uint_as_float(x.x));
                 sum.y = __float_as_uint(__uint_as_float(a.y) + __uint_as_float(x.y));
                 sum.z = __float_as_uint(__uint_as_float(a.z) + __uint_as_float(x.z));
                 sum.w = __float_as_uint(__uint_as_float(a.w) + __uint_as_float(x.w));
                 const uint4 nxt = have[i] ? sum : x;
-                acc[i] = on[i][j] ? nxt : a;
-                have[i] |= on[i][j];
+                acc[i] = o ? nxt : a;
+                have[i] |= o;
+                if constexpr (COUNT) cnt[i / 4] += o ? 1u << (8 * (i % 4)) : 0u;
             }
         }
     }
 #pragma unroll
     for (int i = 0; i < ITEMS; i++) {
         const unsigned b = b0 + i;
+        if constexpr (COUNT) {   // (never with weights: they are legal on all-SUM contexts only, the C-ABI refuses the mix)
+            const uint32_t n_i = (cnt[i / 4] >> (8 * (i % 4))) & 0xFFu;
+            if (mean && n_i > 1u) {   // MEAN: one correctly rounded division per lane; the count converts exactly (<= 64)
+                const float n = (float)n_i;
+                acc[i].x = __float_as_uint(__uint_as_float(acc[i].x) / n);
+                acc[i].y = __float_as_uint(__uint_as_float(acc[i].y) / n);
+                acc[i].z = __float_as_uint(__uint_as_float(acc[i].z) / n);
+                acc[i].w = __float_as_uint(__uint_as_float(acc[i].w) / n);
+            }
+        }
         const unsigned off = b < (unsigned)batch ? blk + b * ostride : out_bytes;   // past the batch: dropped by the resource's bounds
         u32x4_t x;
         x.x = acc[i].x, x.y = acc[i].y, x.z = acc[i].z, x.w = acc[i].w;
         __builtin_amdgcn_raw_buffer_store_b128(x, rs_out, off, 0, 0);
     }
-    if (bad) atomicOr_system(err_flag, 1);  // pinned host word; error path only
+    if (bad || badv) atomicOr_system(err_flag, 1);  // pinned host word; error path only
+}
+
+// Waves per SIMD the register allocation must leave room for: what the five product shapes (ITEMS x WIN = 8 row words in flight: 8 waves,
+// 64 registers; 16: 5 waves, 96 registers) had before the kernel grew its MEAN and weighted arms, so that no arm costs the plain SUM fold a
+// wave (tools/kernel_resources.py: 64 / 50 / 60 / 64 / 93 / 94 / 81 / 79 VGPRs, no spill, no scratch).  Experiment shapes: no floor.
+constexpr int pooled_min_waves(int items, int win) { return items * win <= 8 ? 8 : items * win == 16 ? 5 : 1; }
+
+template <int ITEMS, int WIN, bool WIDE>
+__global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pooled_kernel(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, const FrGatherGroups groups,
+                                                            int n_groups, const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
+                                                            const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
+                                                            unsigned out_bytes, int any_mean) {
+    const int group = blockIdx.x & (n_groups - 1);
+    const int w0 = groups.start[group];
+    const int t = blockIdx.y * blockDim.x + threadIdx.x;
+    if (t >= groups.start[group + 1] - w0) return;
+    const unsigned b0 = (blockIdx.x / (unsigned)n_groups) * ITEMS;   // the workgroup's chunk of ITEMS items
+    if (weights) {
+        // the weighted fold keeps half as many row words in flight per pass (half the items, or half the window for one item), so that
+        // its weights and products fit the registers the unweighted fold needs anyway: the kernel's register count, hence the unweighted
+        // path's occupancy, is the unweighted fold's
+        if constexpr (ITEMS >= 2) {
+            for (unsigned h = 0; h < 2; h++)
+                gather_pooled_body<ITEMS / 2, WIN, WIDE, true, false>(words, pool, w0 + t, b0 + h * (ITEMS / 2), idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes);
+        } else {
+            constexpr int HALF = WIN >= 8 ? WIN / 2 : WIN;   // (whole groups of 4 slots for the 16-byte loads; the product's one-item form has 16)
+            gather_pooled_body<1, HALF, WIDE, true, false>(words, pool, w0 + t, b0, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes);
+        }
+    } else if (any_mean) {
+        // a context with a MEAN column: the fold that also counts each bag and divides, in half passes like the weighted fold and for the
+        // same reason (its count and quotients cost the 4-item form 72 registers against 64: a wave less per SIMD for every SUM context)
+        if constexpr (ITEMS >= 2) {
+            for (unsigned h = 0; h < 2; h++)
+                gather_pooled_body<ITEMS / 2, WIN, WIDE, false, true>(words, pool, w0 + t, b0 + h * (ITEMS / 2), idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes);
+        } else {
+            constexpr int HALF = WIN >= 8 ? WIN / 2 : WIN;
+            gather_pooled_body<1, HALF, WIDE, false, true>(words, pool, w0 + t, b0, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes);
+        }
+    } else {   // every column SUM, no weights: the fold as it was before there were modes
+        gather_pooled_body<ITEMS, WIN, WIDE, false, false>(words, pool, w0 + t, b0, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes);
+    }
 }
 
 template <int ITEMS, int WIN, bool WIDE>
-static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, int pool_cols, const float *dense,
-                                void *out, int batch, int *err_flag, unsigned out_bytes, hipStream_t s) {
+static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, const float *weights, int pool_cols,
+                                const float *dense, void *out, int batch, int *err_flag, unsigned out_bytes, bool any_mean, hipStream_t s) {
     const int n_chunks = (batch + ITEMS - 1) / ITEMS;
     const int bx = groups.max_words >= 256 ? 256 : ((groups.max_words + 63) / 64) * 64;
     dim3 grid(n_groups * n_chunks, (groups.max_words + bx - 1) / bx);
-    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, pool_cols, dense, out, batch, err_flag, out_bytes);
+    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, any_mean ? 1 : 0);
     KCHECK();
     fr_note_kernel("gather_pooled_kernel<%d, %d, %s>", ITEMS, WIN, WIDE ? "true" : "false");
     return FR_OK;
 }
 
-// idx = [batch][pool_cols] int32; out = fp32 records in the model's layout, out_words 16-byte words per item.  max_hots picks the window.
-int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, int pool_cols, int max_hots, bool wide,
-                      const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words) {
+// idx = [batch][pool_cols] int32; weights = NULL or float [batch][pool_cols] (the weighted fold); out = fp32 records in the model's layout,
+// out_words 16-byte words per item.  max_hots picks the window; any_mean: a word of `pool` carries FR_POOL_DESC_MEAN.
+int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, const float *weights, int pool_cols,
+                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words) {
     if (n_words <= 0 || batch <= 0) return FR_OK;
     if (out_words < n_words) out_words = n_words;
     const size_t out_bytes = (size_t)batch * (size_t)out_words * 16, idx_bytes = (size_t)batch * (size_t)pool_cols * 4;
     if (out_bytes >= ((size_t)4000 << 20) || idx_bytes >= ((size_t)4000 << 20))   // 32-bit resource offsets, with room for the chunk past the batch
-        FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's index rows (%zu bytes) or records (%zu bytes) reach 4000 MiB", idx_bytes, out_bytes);
+        FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's index rows%s (%zu bytes) or records (%zu bytes) reach 4000 MiB", weights ? " / weights" : "", idx_bytes, out_bytes);
     FrGatherGroups groups = planned;
     int n_groups = 8;
     if (groups.max_words <= 0) {   // no XCD plan (a narrow record): one group, whole workgroups along the words
@@ -514,7 +621,7 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
         for (int g = 1; g <= 8; g++) groups.start[g] = n_words;
         groups.max_words = n_words;
     }
-    wide = wide && (reinterpret_cast<uintptr_t>(idx) & 15) == 0;
+    wide = wide && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;   // 16-byte loads of both arrays
     // window x items per thread by the longest bag, from the sweep on the MI355X (profiles/pooled_gather_window_sweep.md: Model-C batch 4096, every
     // window x items pair at hots 1 .. 16): the longest window that a bag fills wins by 1-5 %, with as few items per thread as keep 16 row words
     // in flight; a one-slot window is 20 % slower than a two-slot one at hots = 1 and is not built.  FR_POOL_WIN / FR_POOL_ITEMS: experiments build only
@@ -525,8 +632,8 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
 #define FR_GP(I, W)                                                                                                                                     \
     if (items == I && win == W) {                                                                                                                       \
         if constexpr (W % 4 == 0)                                                                                                                       \
-            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, s); \
-        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, s);   \
+            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s); \
+        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s);   \
     }
     FR_GP(4, 2)
     FR_GP(2, 2)

@@ -77,10 +77,12 @@ struct FrGatherGroups {
 
 // Pooled (multi-hot) gather, gather_pooled_kernel: one per FrWordDesc, in the same order.  The word's bag of the item's pooled index
 // row idx[P] is idx[first .. first + hots); a DENSE word has hots == 1 (its one "slot" is the item itself).  FrWordDesc::idx_col is not
-// read by the pooled kernel but for its DENSE bit.
+// read by the pooled kernel but for its DENSE bit.  The word's pooling mode rides in the spare high bit of `hots` (its maximum is 64):
+// FR_POOL_DESC_MEAN set = the fold is divided by the bag's count of non-empty slots (never set on a DENSE word).
+constexpr uint32_t FR_POOL_DESC_MEAN = 0x80000000u;
 struct FrPoolDesc {
     uint32_t first;   // first pooled index column of the word's bag
-    uint32_t hots;    // slots of the bag (1 .. FR_POOL_MAX_HOTS)
+    uint32_t hots;    // slots of the bag (1 .. FR_POOL_MAX_HOTS) | FR_POOL_DESC_MEAN
 };
 static_assert(sizeof(FrPoolDesc) == 8, "FrPoolDesc must be 8 bytes");
 
@@ -226,6 +228,9 @@ struct fr_ctx {
     int pool_cols = 0;                     // P
     int pool_max_hots = 0;
     bool pool_wide = false;                // every bag starts and ends on a multiple of 4 slots and P % 4 == 0: 16-byte index loads
+    std::vector<int32_t> pool_hots;        // hots per index column, as set
+    std::vector<int32_t> pool_modes;       // FR_POOL_SUM / FR_POOL_MEAN per index column (fr_ctx_set_pooling_modes); in the descriptors as FR_POOL_DESC_MEAN
+    bool pool_any_mean = false;            // a column is MEAN: the weighted entry points refuse
     std::mutex workers_mutex;              // guards `workers`
     std::vector<struct fr_worker *> workers;   // live workers (fr_ctx_set_pooling asks each whether it has work in flight)
     unsigned long long *d_merged = nullptr;  // lookups merged by the dedup gather (FR_GATHER_ITEM_TILE_DEDUP_COUNT)
@@ -273,6 +278,8 @@ struct fr_worker {
     fr_ctx *ctx = nullptr;
     int max_batch = 0;
     int idx_cap = 0;             // int32 columns per item its pinned and device index buffers hold: max(index columns, pooled columns at creation)
+    float *h_pool_w = nullptr;   // pinned [max_batch][pool_w_cap] per-sample weights of the host form (fr_worker_pool_weights_ptr); NULL without pooling at creation
+    int pool_w_cap = 0;          // pooled columns at creation
     // CPU back-end: a call computes before it returns; an index-range error stays in c_err until fr_worker_sync reports it
     float *c_scratch = nullptr;  // [max_batch][H1 + H2 + H3]
     float *c_x = nullptr;        // records of the sharded FC entry points, [max_batch][K]
@@ -369,7 +376,8 @@ void frc_arena_free(void *p, size_t bytes);
 int frc_fill_table(float *base, int64_t row0, int64_t rows, int dim, int64_t row_stride_bytes, int mode, uint32_t seed, uint32_t uid);
 int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale);
 int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx_stride, const float *dense, float *out, int batch, int *err_flag);
-int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, int pool_cols, const float *dense, float *out, int batch, int *err_flag);
+int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
+                      int *err_flag);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \
@@ -392,9 +400,10 @@ int frk_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t l
 int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void *dst, size_t dst_stride, int64_t rows, int floats, int e_x, hipStream_t s);
 int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &groups, const int32_t *idx, int idx_stride, const float *dense, void *out, int batch, int *err_flag,
                int transport, int e_x, hipStream_t s, int out_words, bool one_chunk = false);
-// pooled (multi-hot) gather: idx = [batch][pool_cols]; bag of word w = pool[w]; fp32 records in the model's layout.  max_hots / wide: fr_ctx::pool_*
-int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &groups, const int32_t *idx, int pool_cols, int max_hots, bool wide,
-                      const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words);
+// pooled (multi-hot) gather: idx = [batch][pool_cols]; weights = NULL or float [batch][pool_cols] (the weighted fold); bag and mode of word w =
+// pool[w]; fp32 records in the model's layout.  max_hots / wide / any_mean: fr_ctx::pool_*
+int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &groups, const int32_t *idx, const float *weights, int pool_cols,
+                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words);
 int frk_gather_tile(const FrPassDesc *passes, const FrChunkDesc *chunks, int n_chunks, const int32_t *idx, int idx_stride, const float *dense, void *out,
                     int out_stride_words, int batch, int *err_flag, bool dedup, unsigned long long *dup_counter, hipStream_t s);
 int frk_transpose_slices_lp(int precision, const void *gathered, int n_shards, int batch_total, int slice_padded, const int *h_offsets, const int *h_lens,

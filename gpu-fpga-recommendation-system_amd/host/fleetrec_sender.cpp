@@ -11,6 +11,9 @@
 //                        [--hots N [--ragged]]  (pooled lookups, fleetrec_server --hots N: a bag of N slots on every index column, a block is
 //                                      B x (columns x N) int32, column by column, slot-minor.  reference indices: slot j of item b takes the fixed-index
 //                                      table's entry for item b + j; --ragged: slot j of column c of item b is empty (-1) when (b + 3 c + 5 j) % 4 == 3)
+//                        [--pool weighted]  (with --hots N, for fleetrec_server --hots N --pool weighted: every block's index rows are followed by
+//                                      float32 [B][columns x N] per-sample weights, 0.25 * (1 + (b + c + 2 j) % 4) for item b, column c, slot j;
+//                                      --pool sum | mean send what --hots alone sends: those folds are the server's business)
 //                        [--pool N]   (uniform indices: N distinct blocks per connection are generated up front and sent in rotation --
 //                                      drawing 12 k random indices per block is slower than the server; default 32, 0 = draw every block)
 #include <arpa/inet.h>
@@ -43,6 +46,7 @@ int main(int argc, char **argv) {
     std::string host = "127.0.0.1", indices = "reference";
     bool per_item = false, per_bank = false, reply = false, ragged = false;
     int hots = 0;
+    bool weighted = false, pool_mode = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -58,7 +62,11 @@ int main(int argc, char **argv) {
         else if (a == "--row-cap") row_cap = atol(next());
         else if (a == "--max-blocks") max_blocks = atol(next());
         else if (a == "--interval-us") interval_us = atol(next());
-        else if (a == "--pool") pool = atol(next());
+        else if (a == "--pool") {   // a pooling mode (with --hots) or, as ever, a number of blocks
+            const std::string v = next();
+            if (v == "weighted" || v == "sum" || v == "mean") pool_mode = true, weighted = v == "weighted";
+            else pool = atol(v.c_str());
+        }
         else if (a == "--window") window = atol(next());
         else if (a == "--hots") hots = atoi(next());
         else if (a == "--ragged") ragged = true;
@@ -66,6 +74,7 @@ int main(int argc, char **argv) {
     }
     if (hots < 0 || hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, hots); return 2; }
     if (ragged && hots <= 0) { fprintf(stderr, "--ragged needs --hots N\n"); return 2; }
+    if (pool_mode && hots <= 0) { fprintf(stderr, "--pool sum|mean|weighted needs --hots N\n"); return 2; }
     const size_t slots = hots > 0 ? (size_t)hots : 1;   // int32 per index column of an item
     fr_model_desc *m = nullptr;
     if (fr_model_clone_scaled(fr_model_builtin(which), 1.0, 1, row_cap, &m) != FR_OK) { fprintf(stderr, "%s\n", fr_last_error()); return 1; }
@@ -86,6 +95,11 @@ int main(int argc, char **argv) {
     for (int t = 0; t < threads; t++) {
         th.emplace_back([&, t]() {
             std::vector<int32_t> idx((size_t)batch * cols * slots);
+            std::vector<float> wts(weighted ? idx.size() : 0);   // --pool weighted: the same weights in every block
+            for (size_t q = 0; q < wts.size(); q++) {
+                const size_t b = q / (cols * slots), c = q / slots % cols, j = q % slots;
+                wts[q] = 0.25f * (float)(1 + (b + c + 2 * j) % 4);
+            }
             std::vector<float> dense((size_t)batch * m->dense_len), scores(batch);
             std::mt19937_64 rng(1234 + t);
             int sock = socket(AF_INET, SOCK_STREAM, 0), one = 1;
@@ -157,6 +171,7 @@ int main(int argc, char **argv) {
                 }
                 const auto t_req = std::chrono::steady_clock::now();
                 if (send(sock, bi, idx.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                if (!wts.empty() && send(sock, wts.data(), wts.size() * 4, MSG_NOSIGNAL) <= 0) break;
                 if (!dense.empty() && send(sock, bd, dense.size() * 4, MSG_NOSIGNAL) <= 0) break;
                 sent[t]++;
                 n_sent.fetch_add(1, std::memory_order_release);

@@ -16,6 +16,9 @@
 //                        [--shards G [--one-device] [--precision f32|bf16|fp8] [--exchange allgather|alltoall]]
 //        [--hots N]: multi-hot pooled lookups (fr_ctx_set_pooling): a bag of N slots on every index column, a block is B x (index columns x N)
 //                        int32 (slot -1 = empty), every batch goes through fr_worker_submit_pooled + fr_worker_sync.  Not with --stream or --shards.
+//        [--pool sum|mean|weighted] (with --hots N; sum is the default): mean = every column FR_POOL_MEAN (fr_ctx_set_pooling_modes); weighted = the
+//                        block's index rows are followed by float32 [B][index columns x N] per-sample weights, read into fr_worker_pool_weights_ptr,
+//                        and every batch goes through fr_worker_submit_pooled_weighted (fleetrec_sender --hots N --pool weighted).
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
@@ -62,6 +65,7 @@ struct Options {
     bool latency = false;  // latency-measurement mode: per-batch recv -> enqueued -> scores times (measure_network_cuda_cp_latency_*/cuda_server.c)
     long row_cap = 0;
     int hots = 0;          // --hots N: pooled lookups, N slots per index column (0: one-hot)
+    int pool = -1;         // --pool: 0 sum, 1 mean, 2 weighted (-1: not given)
 };
 
 static bool read_exact(int fd, void *buf, size_t n) {  // the recv loop of cuda_server.c:425-450
@@ -178,6 +182,7 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
     const size_t idx_cols = o.hots > 0 ? (size_t)fr_ctx_pooled_index_cols(t->ctx) : (size_t)fr_model_index_cols(m);
     const size_t idx_bytes = (size_t)o.batch * idx_cols * sizeof(int32_t);
     const size_t dense_bytes = (size_t)o.batch * m->dense_len * sizeof(float);
+    const size_t weight_bytes = o.pool == 2 ? (size_t)o.batch * idx_cols * sizeof(float) : 0;   // --pool weighted: the weights follow the index rows
     int server_fd = socket(AF_INET, SOCK_STREAM, 0), opt = 1;
     setsockopt(server_fd, SOL_SOCKET, SO_REUSEADDR, &opt, sizeof(opt));
     sockaddr_in addr{};
@@ -362,14 +367,14 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 if (g_global_batch_count >= o.total) break;
                 g_global_batch_count++;
             }
-            if (!read_exact(sock, fr_worker_idx_ptr(wk), idx_bytes) ||
+            if (!read_exact(sock, fr_worker_idx_ptr(wk), idx_bytes) || (weight_bytes && !read_exact(sock, fr_worker_pool_weights_ptr(wk), weight_bytes)) ||
                 (dense_bytes && !read_exact(sock, fr_worker_dense_ptr(wk), dense_bytes))) {
                 t->status = -4;
                 t->error = "Receiving data UNSUCCESSFUL (peer closed before the batch was complete)";
                 break;
             }
             const auto t_recv = std::chrono::steady_clock::now();  // network_time / cuda_time pair of cuda_server.c:429,462
-            if ((o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
+            if ((weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
                 t->status = -5;
                 t->error = fr_last_error();
                 break;
@@ -424,6 +429,11 @@ int main(int argc, char **argv) {
         else if (a == "--small-block") o.small_block = atoi(next());
         else if (a == "--row-cap") o.row_cap = atol(next());
         else if (a == "--hots") o.hots = atoi(next());
+        else if (a == "--pool") {
+            std::string v = next();
+            if (v != "sum" && v != "mean" && v != "weighted") { fprintf(stderr, "--pool: sum, mean or weighted, not '%s'\n", v.c_str()); return 2; }
+            o.pool = v == "sum" ? 0 : v == "mean" ? 1 : 2;
+        }
         else if (a == "--exchange") {
             std::string v = next();
             if (v != "allgather" && v != "alltoall") { fprintf(stderr, "--exchange: allgather or alltoall, not '%s'\n", v.c_str()); return 2; }
@@ -438,6 +448,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--hots (pooled lookups) serves the submit-and-sync path only: not with --stream or --shards (their producers are one-hot)\n");
         return 2;
     }
+    if (o.pool >= 0 && o.hots <= 0) { fprintf(stderr, "--pool sum|mean|weighted needs --hots N\n"); return 2; }
     printf("HIP devices visible: %d\n", fr_device_count());  // device probe of cuda_server.c:508-522
     fr_model_desc *model = nullptr;
     if (fr_model_clone_scaled(fr_model_builtin(o.model), 1.0, 1, o.row_cap, &model) != FR_OK) { fprintf(stderr, "%s\n", fr_last_error()); return 1; }
@@ -489,7 +500,15 @@ int main(int argc, char **argv) {
             fprintf(stderr, "set-up failed: %s\n", fr_last_error());
             return 1;
         }
+        if (o.pool == 1) {
+            std::vector<int32_t> modes(hots.size(), FR_POOL_MEAN);
+            if (fr_ctx_set_pooling_modes(ctx, modes.data(), (int)modes.size()) != FR_OK) {
+                fprintf(stderr, "set-up failed: %s\n", fr_last_error());
+                return 1;
+            }
+        }
         printf("pooled lookups: %d slots on each of %zu index columns, %d int32 per item\n", o.hots, hots.size(), fr_ctx_pooled_index_cols(ctx));
+        if (o.pool > 0) printf("pooling: %s\n", o.pool == 1 ? "mean" : "weighted (float32 weights follow every block's index rows)");
     }
     if (o.stream && o.reply && !g_engine && fr_ctx_set_small_block(ctx, o.small_block) != FR_OK) {
         fprintf(stderr, "set-up failed: %s\n", fr_last_error());

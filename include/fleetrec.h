@@ -39,6 +39,7 @@ extern "C" {
  * table-sharded step (fr_exchange; fleetrec_serving.h fr_comm_set_exchange / fr_comm_exchange; fleetrec_diag.h fr_comm_exchange_bytes) -- the
  * default all-gather is the step as before.  Still 6, additive: multi-hot pooled lookups (fleetrec_serving.h: fr_ctx_set_pooling,
  * fr_ctx_pooled_index_cols, fr_worker_gather_pooled, fr_worker_submit_pooled_device, fr_worker_submit_pooled) -- every one-hot entry point is as before.
+ * Still 6, additive: pooling modes (SUM / MEAN) and per-sample weights of those lookups (fleetrec_serving.h: fr_ctx_set_pooling_modes, fr_worker_*_pooled_weighted*).
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile
  * shape of a chain model no longer follows the number of live workers).
  * 4 (round 4): the surface is three headers -- this one (the three spans of thread_consume() that SURVEY section 8(b) cuts, the request

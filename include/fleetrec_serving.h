@@ -103,6 +103,33 @@ int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx
  * fr_ctx_set_pooling sizes its pinned and device index buffers for max(index_cols, P); an older worker gets FR_ERR_STATE here. */
 int fr_worker_submit_pooled(fr_worker *w, int batch);
 
+/* Pooling modes and per-sample weights (additive in ABI 6).  Every index column has a pooling mode: FR_POOL_SUM (the default: the fold above)
+ * or FR_POOL_MEAN.  A MEAN column's TABLE and COPY words are the SUM fold of the bag divided by n, the number of non-empty slots of the bag:
+ * one IEEE fp32 division, correctly rounded, per lane, n converted exactly; n == 1 leaves the word the bit copy it is (no division), n == 0
+ * gives +0.0f.  DENSE words are never divided.  MEAN takes effect through the unweighted pooled entry points above.
+ * modes[n_cols], n_cols == fr_model_index_cols; modes == NULL makes every column SUM again, and so does every fr_ctx_set_pooling (also with
+ * NULL).  FR_ERR_STATE when no pooling is set, on a sharded context, or while a worker of the context has work in flight (the rule of
+ * fr_ctx_set_pooling); FR_ERR_INVALID for a wrong n_cols or an unknown mode.  The pooled descriptors are rebuilt and uploaded again. */
+#define FR_POOL_SUM 0
+#define FR_POOL_MEAN 1
+int fr_ctx_set_pooling_modes(fr_ctx *ctx, const int32_t *modes, int n_cols);
+int fr_ctx_pooling_mode(const fr_ctx *ctx, int col);      /* the mode of index column col (FR_POOL_SUM when no pooling is set) */
+/* Per-sample weights: float d_weights[batch][P], parallel to the pooled index rows -- the weight of a slot sits where the slot sits.  For a
+ * non-empty slot the term is w * x: one fp32 multiply per lane, rounded to fp32, never fused with the add that follows.  The FIRST non-empty
+ * slot's term becomes the accumulator (in the weighted fold the first word is NOT a bit copy); every further term is added in fp32, in
+ * ascending slot order, one add per lane.  The weight of an empty slot is never read into arithmetic (it may be a NaN and does not show); an
+ * all-empty bag gives +0.0f; DENSE words are copied unweighted; COPY words follow their source column's bag and weights.  Bits are pinned for
+ * every result that is not a NaN (a NaN result is a NaN of unspecified payload); with every weight 1.0f the records equal the unweighted ones
+ * bit for bit wherever no row word is a NaN.  Weights are legal only while every column's mode is FR_POOL_SUM: FR_ERR_STATE on a context
+ * with a MEAN column.  d_weights == NULL is FR_ERR_INVALID.  Index-range errors, the 4000 MiB bound (the weight array is as large as the index
+ * rows) and the sharded refusal are those of the unweighted calls, which behave exactly as before. */
+int fr_worker_gather_pooled_weighted(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_records);
+int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores);
+/* Host form: indices in fr_worker_idx_ptr, weights in fr_worker_pool_weights_ptr -- pinned float [max_batch][P] (host memory on the CPU
+ * back-end), there on a worker created AFTER fr_ctx_set_pooling; NULL on an older worker, where the host form returns FR_ERR_STATE. */
+float *fr_worker_pool_weights_ptr(fr_worker *w);
+int fr_worker_submit_pooled_weighted(fr_worker *w, int batch);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

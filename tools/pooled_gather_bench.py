@@ -16,6 +16,10 @@ bytes + index bytes) / time.  Expectation recorded (not asserted): at hots >= 4 
 one-hot kernel's of the same run.
 
     python tools/pooled_gather_bench.py [--modes table,bank] [--hots 1,2,4,8,16] [--reps 400] [--rounds 3] [--out profiles/pooled_gather.json]
+    --pool sum[,mean,weighted]: the folds to time at every hots (default sum, the shapes "pooled_hotsN" as ever; "mean_hotsN": every column
+    FR_POOL_MEAN; "weighted_hotsN": fr_worker_gather_pooled_weighted with a float32 weight per slot in (0.5, 1.5), one weight buffer per index
+    buffer -- the weighted fold reads 4 more bytes per slot, counted in its algorithmic bytes).  FR_LIB=<another build of the same ABI> times
+    that build (an A/B run against an older commit can only ask it for the folds it has).
     --rehearse: tiny tables on the CPU back-end, to check the plumbing without a GPU (its times are not measurements and say so).
 Experiments build (FR_LIB=.../libfleetrec_exp.so): --sweep times FR_POOL_WIN x FR_POOL_ITEMS instead (profiles/pooled_gather_window_sweep.md).
 """
@@ -79,30 +83,41 @@ def run_mode(fr, args, mode_name, device, rehearse):
     shapes = {}   # name -> (launch, bufs, hots or 0)
     one_bufs = make_buffers(fr, ctx, model, rng, B, 1, min_bytes)
     shapes["gather_only"] = (lambda i, d: wk.gather_only(B, i, d, rec), one_bufs, 0)
+    fold_of = {"gather_only": "sum"}
     for h in args.hots:
-        shapes["pooled_hots%d" % h] = (lambda i, d: wk.gather_pooled(B, i, d, rec), one_bufs if h == 1 else make_buffers(fr, ctx, model, rng, B, h, min_bytes), h)
+        bufs = one_bufs if h == 1 else make_buffers(fr, ctx, model, rng, B, h, min_bytes)
+        for pool in args.pool:
+            name = ("pooled" if pool == "sum" else pool) + "_hots%d" % h
+            fold_of[name] = pool
+            if pool == "weighted":   # a weight buffer per index buffer, found through the index buffer's address
+                wts = {b.ptr.value: fr.DeviceBuffer.from_numpy(ctx, rng.uniform(0.5, 1.5, (B, model.idx_cols * h)).astype(np.float32)) for b in bufs}
+                shapes[name] = (lambda i, d, wts=wts: wk.gather_pooled(B, i, d, rec, weights=wts[i.ptr.value]), bufs, h)
+            else:
+                shapes[name] = (lambda i, d: wk.gather_pooled(B, i, d, rec), bufs, h)
     kernels, times = {}, {n: [] for n in shapes}
 
-    def select(h):
+    def select(name, h):
         ctx.set_pooling(np.full(model.idx_cols, h, np.int32) if h else None)
+        if fold_of[name] == "mean":
+            ctx.set_pooling_modes(np.full(model.idx_cols, fr.POOL_MEAN, np.int32))
 
     for name, (launch, bufs, h) in shapes.items():   # warm-up of every shape: code objects, the tables' first touch
-        select(h)
+        select(name, h)
         window(wk, launch, bufs, dns, min(args.reps, 4 * len(bufs)), 0)
         kernels[name] = wk.last_kernel()
     for r in range(args.rounds):
         for name, (launch, bufs, h) in shapes.items():
-            select(h)
+            select(name, h)
             times[name].append(window(wk, launch, bufs, dns, args.reps, r * args.reps))
-    select(0)
+    select("gather_only", 0)
     out = {"index_mode": mode_name, "index_cols": int(model.idx_cols), "record_floats": int(K), "table_words_per_record": int(tw), "shapes": {}}
     t0 = float(np.median(times["gather_only"]))
     for name, (launch, bufs, h) in shapes.items():
         slots = max(h, 1)
         us = float(np.median(times[name]))
         fetched = B * tw * slots
-        by = fetched * 16 + B * K * 4 + B * dense_len * 4 + B * model.idx_cols * slots * 4
-        e = {"kernel": kernels[name], "hots": h, "index_buffers": len(bufs), "index_bytes_per_batch": B * model.idx_cols * slots * 4,
+        by = fetched * 16 + B * K * 4 + B * dense_len * 4 + B * model.idx_cols * slots * 4 * (2 if fold_of[name] == "weighted" else 1)
+        e = {"kernel": kernels[name], "hots": h, "pool": fold_of[name], "index_buffers": len(bufs), "index_bytes_per_batch": B * model.idx_cols * slots * 4,
              "us_per_batch_rounds": [round(t, 3) for t in times[name]], "us_per_batch": round(us, 3),
              "row_words_fetched_per_s": fetched / (us * 1e-6), "algorithmic_bytes_per_batch": by, "algorithmic_TBs": by / (us * 1e-6) / 1e12,
              "frac_of_8TBs": by / (us * 1e-6) / 1e12 / HBM_PEAK_TBS}
@@ -160,11 +175,15 @@ def main():
     ap.add_argument("--reps", type=int, default=400)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pooled_gather.json"))
+    ap.add_argument("--pool", default="sum")
     ap.add_argument("--rehearse", action="store_true")
     ap.add_argument("--sweep", action="store_true")
     args = ap.parse_args()
     args.modes = [m for m in args.modes.split(",") if m]
     args.hots = [int(h) for h in args.hots.split(",") if h]
+    args.pool = [p for p in args.pool.split(",") if p]
+    if not args.pool or any(p not in ("sum", "mean", "weighted") for p in args.pool):
+        sys.exit("--pool: a comma-separated list of sum, mean, weighted")
     fr = graft.load_package()
     if not args.rehearse and fr.device_count() < 1:
         sys.exit("pooled_gather_bench: no MI355X visible -- a timing needs the GPU (--rehearse checks the plumbing on the CPU back-end)")
@@ -177,7 +196,7 @@ def main():
         return
     t_start = time.time()
     res = {"tool": "tools/pooled_gather_bench.py", "model": "C", "batch": args.batch, "fill": "FR_FILL_HASH", "index_law": "uniform", "timed_launches_per_window": args.reps,
-           "rounds": args.rounds, "timing": "HIP events on the worker's stream around each window; median over the rounds", "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse),
+           "rounds": args.rounds, "pool": args.pool, "library": os.environ.get("FR_LIB", "libfleetrec.so"), "timing": "HIP events on the worker's stream around each window; median over the rounds", "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse),
            "modes": [run_mode(fr, args, m, device, args.rehearse) for m in args.modes]}
     res["wall_s"] = round(time.time() - t_start, 1)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
