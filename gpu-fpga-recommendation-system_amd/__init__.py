@@ -77,11 +77,13 @@ ABI_SYMBOLS = [
     "fr_ctx_set_pooling", "fr_ctx_pooled_index_cols", "fr_worker_gather_pooled", "fr_worker_submit_pooled_device", "fr_worker_submit_pooled",
     "fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device", "fr_worker_pool_weights_ptr",
     "fr_worker_submit_pooled_weighted",
+    "fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
 ]
 
 
-# the entry points ABI 6 gained last (pooling modes and per-sample weights): the only names an FR_LIB build of the same ABI may lack
-_ADDED_IN_ABI_6 = ("fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device",
+# the entry points ABI 6 gained last (pooling modes and per-sample weights, sparse row updates): the only names an FR_LIB build of the same ABI may lack
+_ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
+                   "fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device",
                    "fr_worker_pool_weights_ptr", "fr_worker_submit_pooled_weighted")
 
 
@@ -154,6 +156,8 @@ def lib():
         "fr_ctx_set_pooling_modes": (i32, [vp, pi, i32]), "fr_ctx_pooling_mode": (i32, [vp, i32]),
         "fr_worker_gather_pooled_weighted": (i32, [vp, i32, vp, vp, vp, vp]), "fr_worker_submit_pooled_weighted_device": (i32, [vp, i32, vp, vp, vp, vp]),
         "fr_worker_pool_weights_ptr": (pf, [vp]), "fr_worker_submit_pooled_weighted": (i32, [vp, i32]),
+        "fr_worker_update_rows": (i32, [vp, i32, i32, vp, vp]), "fr_ctx_update_rows": (i32, [vp, i32, i32, vp, vp]),
+        "fr_ctx_lp_bank_image_builds": (ctypes.c_longlong, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -464,6 +468,22 @@ class Context:
         _check(lib().fr_ctx_download_table(self._h, table, row0, nrows, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def update_rows(self, table, row_ids, rows_f32):
+        """fr_ctx_update_rows, the host form of the sparse row update: row i of rows_f32 (float32 or uint32 bit patterns, [len(row_ids)][dim])
+        becomes table row row_ids[i].  Synchronous; legal beside workers in flight; an id outside the table raises FR_ERR_INDEX_RANGE after
+        every in-range row was written."""
+        ids = np.ascontiguousarray(np.asarray(row_ids, dtype=np.int32).ravel())
+        a = np.ascontiguousarray(rows_f32)
+        assert a.dtype in (np.float32, np.uint32)
+        dim = self.model.desc.tables[table].dim if 0 <= table < self.model.n_tables else -1
+        if dim >= 0 and a.shape != (ids.size, dim):
+            raise FleetRecError(FR_ERR_INVALID, "rows are %s, %d listed ids of table %d need (%d, %d)" % (a.shape, ids.size, table, ids.size, dim))
+        _check(lib().fr_ctx_update_rows(self._h, table, int(ids.size), ids.ctypes.data_as(ctypes.c_void_p), a.ctypes.data_as(ctypes.c_void_p)))
+
+    def lp_bank_image_builds(self):
+        """fleetrec_diag.h: full builds of the operand-type bank image so far (an update_rows patch never counts)."""
+        return int(lib().fr_ctx_lp_bank_image_builds(self._h))
+
     def set_weights(self, layer, w_colmajor):
         w = np.ascontiguousarray(w_colmajor, dtype=np.float32).ravel()
         _check(lib().fr_ctx_set_weights(self._h, layer, w.ctypes.data_as(ctypes.c_void_p), w.size))
@@ -701,6 +721,11 @@ class Worker:
         n = ctypes.c_longlong()
         _check(lib().fr_worker_host_poll(self._h, ctypes.byref(n)))
         return n.value
+
+    def update_rows(self, table, n, d_row_ids, d_rows):
+        """fr_worker_update_rows: n listed rows of one table from DeviceBuffers (int32 [n] ids, float32 [n][dim] rows), asynchronous on the
+        worker's stream, ordered against its batches; both buffers stay untouched until sync()."""
+        _check(lib().fr_worker_update_rows(self._h, table, int(n), self._ptr(d_row_ids), self._ptr(d_rows)))
 
     def push_device(self, batch, d_idx, d_dense, d_scores):
         _check(lib().fr_worker_push_device(self._h, batch, self._ptr(d_idx), self._ptr(d_dense), self._ptr(d_scores)))

@@ -111,6 +111,9 @@ static void ctx_free(fr_ctx *c) {
         if (i < 3 && c->d_w_fp8h[i]) (void)hipFree(c->d_w_fp8h[i]);
     }
     if (c->d_stats) (void)hipFree(c->d_stats);
+    if (c->d_up_ids) (void)hipFree(c->d_up_ids);
+    if (c->d_up_rows) (void)hipFree(c->d_up_rows);
+    if (c->h_up_err) (void)hipHostFree(c->h_up_err);
     if (c->setup_stream) (void)hipStreamDestroy(c->setup_stream);
     delete c;
 }
@@ -818,6 +821,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->d_blist) (void)hipFree(w->d_blist);
     for (hipEvent_t e : w->ev_blist)
         if (e) (void)hipEventDestroy(e);
+    if (w->ev_update) (void)hipEventDestroy(w->ev_update);
     if (w->ev_start) (void)hipEventDestroy(w->ev_start);
     if (w->ev_stop) (void)hipEventDestroy(w->ev_stop);
     if (w->stream) (void)hipStreamDestroy(w->stream);
@@ -932,6 +936,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     W_HIP(hipMalloc((void **)&w->d_score, B * sizeof(float)));
     W_HIP(hipEventCreate(&w->ev_start));
     W_HIP(hipEventCreate(&w->ev_stop));
+    W_HIP(hipEventCreateWithFlags(&w->ev_update, hipEventDisableTiming));
     w->counted = true;
     fr_ctx_ref(ctx);
     ctx_enlist(ctx, w);
@@ -1137,10 +1142,13 @@ extern "C" int fr_ctx_set_lp_bank_image(fr_ctx *ctx, int on) {
     return FR_OK;
 }
 extern "C" size_t fr_ctx_lp_bank_image_bytes(const fr_ctx *ctx) { return (ctx && ctx->lp_prec) ? ctx->lp_arena_bytes : 0; }
+extern "C" long long fr_ctx_lp_bank_image_builds(const fr_ctx *ctx) { return ctx ? ctx->lp_builds.load(std::memory_order_relaxed) : 0; }
 
 // Make the image current for (prec, X exponent, table contents).  Called by the launch path right before a gather that reads it; the
 // rebuild runs on the context's set-up stream and is waited for (tens of milliseconds for Model-C, once per change of precision /
-// calibration / table contents -- set-up calls, which by contract do not run beside a stream in flight).
+// calibration / table contents -- set-up calls, which by contract do not run beside a stream in flight).  Row updates (fr_worker_update_rows)
+// DO run beside streams in flight and never make the image stale; a rebuild that some other change asks for first makes the set-up stream
+// wait for the last update of every live worker, so that it does not read the arena under a scatter still running on another stream.
 static int lp_ensure_image(fr_ctx *c, int prec) {
     const int e_x = prec == FR_FC_FP8 ? c->f8_e_act[0] : 0;
     std::lock_guard<std::mutex> lk(c->lp_mutex);
@@ -1182,6 +1190,11 @@ static int lp_ensure_image(fr_ctx *c, int prec) {
     }
     off = align_up(off, 256);
     FR_SET_DEVICE(c);
+    {
+        std::lock_guard<std::mutex> g(c->workers_mutex);
+        for (fr_worker *w : c->workers)
+            if (w->update_recorded) FR_HIP(hipStreamWaitEvent(c->setup_stream, w->ev_update, 0));
+    }
     if (off != c->lp_arena_bytes) {
         if (c->lp_arena) (void)hipFree(c->lp_arena);
         c->lp_arena = nullptr;
@@ -1194,6 +1207,7 @@ static int lp_ensure_image(fr_ctx *c, int prec) {
         c->lp_arena_bytes = off;
     }
     std::vector<size_t> lp_base(m.n_tables, 0);   // offset of (row 0, column 0) of every resident table inside lp_arena
+    c->lp_tables.assign(m.n_tables, fr_ctx::LpTable{});
     for (Bank &b : banks) {
         size_t col = 0;
         for (int t : b.members) {
@@ -1203,6 +1217,9 @@ static int lp_ensure_image(fr_ctx *c, int prec) {
             int rc = frk_convert_rows_lp(prec, c->table_arena + tm.byte_offset, (size_t)tm.row_stride, c->lp_arena + lp_base[t], b.lp_stride, (int64_t)b.rows, m.tables[t].dim, e_x,
                                          c->setup_stream);
             if (rc) return rc;
+            c->lp_tables[t].base = lp_base[t];
+            c->lp_tables[t].stride = b.lp_stride;
+            c->lp_tables[t].rows = b.rows;
             col += (size_t)m.tables[t].dim;
         }
     }
@@ -1219,6 +1236,7 @@ static int lp_ensure_image(fr_ctx *c, int prec) {
     c->lp_prec = prec;
     c->lp_e_x = e_x;
     c->lp_tables_gen = c->tables_gen;
+    c->lp_builds.fetch_add(1, std::memory_order_relaxed);
     return FR_OK;
 }
 
@@ -2356,6 +2374,101 @@ extern "C" int fr_worker_calibrate_fp8_slices(fr_worker *w, int batch_total, int
     w->calibrating = false;
     if (rc) return rc;
     return f8_calibrate_finish(w, L1 - 1, n_items);
+}
+
+// ---- sparse row updates (fleetrec_serving.h) ---------------------------------------------------------------------------------------
+static int update_check(fr_ctx *ctx, int table, int n, const void *ids, const void *rows) {
+    if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (n < 0) FR_FAIL(FR_ERR_INVALID, "n = %d rows", n);
+    if (n > 0 && (!ids || !rows)) FR_FAIL(FR_ERR_INVALID, "row_ids / rows is NULL");
+    if ((int64_t)n * ctx->tables[table].dim / 4 >= (1ll << 31)) FR_FAIL(FR_ERR_INVALID, "%d rows of %d floats exceed one update (2^31 16-byte words)", n, ctx->tables[table].dim);
+    if (!ctx->table_mem[table].resident) FR_FAIL(FR_ERR_STATE, "table %d is not resident on shard %d", table, ctx->shard_rank);
+    return FR_OK;
+}
+
+// The two launches of an update on stream s, under lp_mutex: the scatter into the fp32 arena, then -- when an operand-type bank image exists and is
+// current for the table contents -- the conversion of the same listed rows, read back from the arena, at the image's own X exponent.
+static int update_enqueue(fr_ctx *c, int table, int n, const int32_t *d_ids, const float *d_rows, int *d_err, hipStream_t s) {
+    const fr_table_desc &d = c->tables[table];
+    const FrTableMem &tm = c->table_mem[table];
+    const int64_t head_rows = tm.il_rows ? (int64_t)tm.il_rows : d.rows;
+    int rc = frk_scatter_rows((float *)(c->table_arena + tm.byte_offset), (int64_t)tm.row_stride, (float *)(c->table_arena + tm.tail_offset), head_rows, d.rows, d.dim, n, d_ids, d_rows,
+                              d_err, s);
+    if (rc) return rc;
+    if (c->lp_prec != 0 && c->lp_tables_gen == c->tables_gen && c->d_words_lp && (size_t)table < c->lp_tables.size() && c->lp_tables[table].rows) {
+        const fr_ctx::LpTable &lt = c->lp_tables[table];
+        const int64_t image_rows = (int64_t)lt.rows < head_rows ? (int64_t)lt.rows : head_rows;   // (always lt.rows: the image holds rows of the head region only)
+        rc = frk_convert_rows_lp(c->lp_prec, c->table_arena + tm.byte_offset, (size_t)tm.row_stride, c->lp_arena + lt.base, lt.stride, n, d.dim, c->lp_e_x, s, d_ids, image_rows);
+    }
+    return rc;
+}
+
+extern "C" int fr_worker_update_rows(fr_worker *w, int table, int n, const int32_t *d_row_ids, const float *d_rows) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    fr_ctx *c = w->ctx;
+    int rc = update_check(c, table, n, d_row_ids, d_rows);
+    if (rc) return rc;
+    if (n == 0) return FR_OK;
+    if (c->cpu) {   // computed before the call returns; a range error waits in c_err for fr_worker_sync, like the gathers'
+        if (frc_update_rows(c->table_arena, c->table_mem[table], c->tables[table].dim, c->tables[table].rows, n, d_row_ids, d_rows)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+        return FR_OK;
+    }
+    if ((uintptr_t)d_rows % 16) FR_FAIL(FR_ERR_INVALID, "d_rows must be 16-byte aligned");
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then update");
+    FR_SET_DEVICE(c);
+    rc = fused_flush(w);   // batches fr_worker_push_device queued for a fused launch were pushed BEFORE the update: they gather the old rows
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->lp_mutex);
+    rc = update_enqueue(c, table, n, d_row_ids, d_rows, w->d_err, w->stream);
+    // (recorded even when the second launch failed: the first may be running)
+    if (hipEventRecord(w->ev_update, w->stream) == hipSuccess) w->update_recorded = true;
+    return rc;
+}
+
+extern "C" int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *h_row_ids, const float *h_rows) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    int rc = update_check(ctx, table, n, h_row_ids, h_rows);
+    if (rc) return rc;
+    if (n == 0) return FR_OK;
+    const int dim = ctx->tables[table].dim;
+    if (ctx->cpu) {
+        if (frc_update_rows(ctx->table_arena, ctx->table_mem[table], dim, ctx->tables[table].rows, n, h_row_ids, h_rows))
+            FR_FAIL(FR_ERR_INDEX_RANGE, "a listed row id was outside table %d (that row was not written, the others were)", table);
+        return FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // also serialises the set-up stream and the staging buffers against other updates and an image build
+    if (!ctx->h_up_err) {
+        FR_HIP(hipHostMalloc((void **)&ctx->h_up_err, sizeof(int), hipHostMallocMapped));
+        *ctx->h_up_err = 0;
+        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
+    }
+    const size_t n_floats = (size_t)n * (size_t)dim;
+    if ((size_t)n > ctx->up_ids_cap) {
+        if (ctx->d_up_ids) (void)hipFree(ctx->d_up_ids);
+        ctx->d_up_ids = nullptr, ctx->up_ids_cap = 0;
+        FR_HIP(hipMalloc((void **)&ctx->d_up_ids, (size_t)n * sizeof(int32_t)));
+        ctx->up_ids_cap = (size_t)n;
+    }
+    if (n_floats > ctx->up_rows_cap) {
+        if (ctx->d_up_rows) (void)hipFree(ctx->d_up_rows);
+        ctx->d_up_rows = nullptr, ctx->up_rows_cap = 0;
+        FR_HIP(hipMalloc((void **)&ctx->d_up_rows, n_floats * sizeof(float)));
+        ctx->up_rows_cap = n_floats;
+    }
+    FR_HIP(hipMemcpyAsync(ctx->d_up_ids, h_row_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->setup_stream));
+    FR_HIP(hipMemcpyAsync(ctx->d_up_rows, h_rows, n_floats * sizeof(float), hipMemcpyHostToDevice, ctx->setup_stream));
+    rc = update_enqueue(ctx, table, n, ctx->d_up_ids, ctx->d_up_rows, ctx->d_up_err, ctx->setup_stream);
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    if (rc) return rc;
+    if (__atomic_load_n(ctx->h_up_err, __ATOMIC_ACQUIRE)) {
+        __atomic_store_n(ctx->h_up_err, 0, __ATOMIC_RELEASE);
+        FR_FAIL(FR_ERR_INDEX_RANGE, "a listed row id was outside table %d (that row was not written, the others were)", table);
+    }
+    return FR_OK;
 }
 
 // Launch what is queued -- the partially filled host block, the batches queued by fr_worker_push_device -- without waiting for it.

@@ -209,6 +209,30 @@ int frc_fill_table(float *base, int64_t row0, int64_t rows, int dim, int64_t row
     return FR_OK;
 }
 
+// Row updates: the work is dealt by DESTINATION (blocks of 64 table rows, round-robin over the units), every unit walks the whole id list in
+// order -- two listings of one row are then written by one thread, the later one last, and no two threads ever write the same bytes.
+int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src) {
+    const size_t row_bytes = (size_t)dim * 4;
+    const int64_t head_rows = tm.il_rows ? (int64_t)tm.il_rows : rows;
+    const int units = n < 4096 ? 1 : Pool::get().size();
+    std::atomic<int> bad{0};
+    Pool::get().run(units, [&](int u) {
+        int any_bad = 0;
+        for (int i = 0; i < n; i++) {
+            const int64_t r = ids[i];
+            if (r < 0 || r >= rows) {
+                any_bad = 1;
+                continue;
+            }
+            if ((int)((r >> 6) % units) != u) continue;
+            char *a = r < head_rows ? arena + tm.byte_offset + (size_t)r * tm.row_stride : arena + tm.tail_offset + (size_t)(r - head_rows) * row_bytes;
+            memcpy(a, src + (size_t)i * dim, row_bytes);
+        }
+        if (any_bad) bad.store(1, std::memory_order_relaxed);
+    });
+    return bad.load(std::memory_order_relaxed);
+}
+
 int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale) {
     const uint32_t h0 = fr_weight_hash_seed(seed, layer);
     const size_t chunk = 1 << 16;

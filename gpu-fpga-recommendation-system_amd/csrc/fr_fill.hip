@@ -8,10 +8,38 @@
 // one thread per 16-byte word, grid-stride; stores are 16 B/lane fully coalesced.  Row r of the table (r = row0 + local row) lives at
 // base + local_row * row_stride_words: row_stride_words == words_per_row for a table stored on its own, larger for a table that is one
 // column block of a bank-interleaved region (FR_INDEX_PER_BANK, fr_api.cpp build_words).
+// The "rows from a list" arm (sc.ids != NULL; fr_worker_update_rows / fr_ctx_update_rows): word w is word wc of LISTED row i = w / words_per_row,
+// its content the 16 bytes sc.src[w] of the caller's dense rows, its row sc.ids[i] of the WHOLE table -- base + r * row_stride_words below
+// sc.head_rows, sc.tail + (r - head_rows) * words_per_row from there on (table_copy's arithmetic).  An id outside [0, sc.rows) raises the
+// worker's error word and writes nothing.  Consecutive lanes read consecutive source words; a row lands as one dim * 4-byte segment.  The
+// branch is uniform over the launch and taken once, around the loop.
+struct FrScatterArgs {
+    const int32_t *ids;    // [n] listed rows; NULL = a procedural fill
+    const uint4 *src;      // [n][words_per_row]
+    uint4 *tail;           // row head_rows of the table (unused when head_rows == rows)
+    uint64_t head_rows;    // rows at `base` (all of them unless the table is bank-interleaved)
+    uint64_t rows;         // the table's rows: the range check
+    int *err_flag;
+};
 __global__ void __launch_bounds__(256) fill_table_kernel(uint4 *base, uint64_t n_words, uint32_t words_per_row, uint64_t row_stride_words, uint64_t row0,
-                                                          int mode, uint32_t seed, uint32_t uid) {
-    const uint32_t h0 = fr_table_hash_seed(seed, uid);
+                                                          int mode, uint32_t seed, uint32_t uid, const FrScatterArgs sc) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    if (sc.ids) {
+        for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += stride) {
+            const uint64_t i = w / words_per_row;
+            const uint32_t wc = (uint32_t)(w - i * words_per_row);
+            const int32_t id = sc.ids[i];
+            if (id < 0 || (uint64_t)id >= sc.rows) {
+                if (wc == 0) atomicOr_system(sc.err_flag, 1);  // pinned host word; error path only
+                continue;
+            }
+            const uint64_t r = (uint64_t)id;
+            uint4 *dst = r < sc.head_rows ? base + r * row_stride_words + wc : sc.tail + (r - sc.head_rows) * words_per_row + wc;
+            *dst = sc.src[w];
+        }
+        return;
+    }
+    const uint32_t h0 = fr_table_hash_seed(seed, uid);
     for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n_words; w += stride) {
         const uint64_t lrow = w / words_per_row, row = row0 + lrow;
         const uint32_t wc = (uint32_t)(w - lrow * words_per_row), c0 = wc * 4;
@@ -30,7 +58,27 @@ int frk_fill_table(float *base, int64_t row0, int64_t rows, int dim, int64_t row
     if (blocks > 256 * 16) blocks = 256 * 16;
     if (blocks == 0) return FR_OK;
     fill_table_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>((uint4 *)base, n_words, (uint32_t)(dim / 4), (uint64_t)row_stride_bytes / 16, (uint64_t)row0, mode, seed,
-                                                                 uid);
+                                                                 uid, FrScatterArgs{});
+    KCHECK();
+    return FR_OK;
+}
+
+// n listed rows of one table (fill_table_kernel's list arm): ids int32 [n], src float [n][dim]; head / tail: where rows [0, head_rows) and
+// [head_rows, rows) of the table start.  n * dim / 4 < 2^31 is the caller's check.
+int frk_scatter_rows(float *head, int64_t row_stride_bytes, float *tail, int64_t head_rows, int64_t rows, int dim, int n, const int32_t *ids, const float *src, int *err_flag,
+                     hipStream_t s) {
+    const uint64_t n_words = (uint64_t)n * (uint64_t)(dim / 4);
+    uint64_t blocks = (n_words + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (blocks == 0) return FR_OK;
+    FrScatterArgs sc{};
+    sc.ids = ids;
+    sc.src = reinterpret_cast<const uint4 *>(src);
+    sc.tail = reinterpret_cast<uint4 *>(tail);
+    sc.head_rows = (uint64_t)head_rows;
+    sc.rows = (uint64_t)rows;
+    sc.err_flag = err_flag;
+    fill_table_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>((uint4 *)head, n_words, (uint32_t)(dim / 4), (uint64_t)row_stride_bytes / 16, 0, 0, 0, 0, sc);
     KCHECK();
     return FR_OK;
 }

@@ -221,6 +221,19 @@ struct fr_ctx {
     uint64_t lp_tables_gen = 0;            // tables_gen the image was made from
     uint64_t tables_gen = 1;               // bumped by every fill / upload
     std::mutex lp_mutex;
+    // Row updates (fr_worker_update_rows / fr_ctx_update_rows) patch the image in place: where lp_ensure_image put every table, kept under lp_mutex
+    struct LpTable {
+        size_t base = 0;       // inside lp_arena: (row 0, column 0) of the table
+        size_t stride = 0;     // bytes between image rows
+        uint64_t rows = 0;     // rows the image holds of it: the bank's common range (FR_INDEX_PER_BANK), the table's own otherwise; 0: not in the image
+    };
+    std::vector<LpTable> lp_tables;
+    std::atomic<long long> lp_builds{0};   // full builds of the image so far (fr_ctx_lp_bank_image_builds); a patch never counts
+    // staging of fr_ctx_update_rows (grown on demand, used under lp_mutex on the set-up stream) and its index-range word (pinned, device-visible)
+    int32_t *d_up_ids = nullptr;
+    float *d_up_rows = nullptr;
+    size_t up_ids_cap = 0, up_rows_cap = 0;   // elements
+    int *h_up_err = nullptr, *d_up_err = nullptr;
     std::atomic<int> lp_image_on{1};       // fr_ctx_set_lp_bank_image (fleetrec_diag.h): 0 = the in-chain gather reads the fp32 rows and converts them itself
     // Pooled (multi-hot) lookups (fr_ctx_set_pooling): the descriptors made of the hots per index column, P = sum of hots (0: no pooling)
     std::vector<FrPoolDesc> h_pool;
@@ -355,6 +368,10 @@ struct fr_worker {
     int *h_err = nullptr;  // sticky index-range flag: pinned host word ...
     int *d_err = nullptr;  // ... and its device-side alias
     bool in_flight = false;
+    // fr_worker_update_rows: recorded on the stream behind the update's launches; a rebuild of the operand-type bank image makes the set-up
+    // stream wait for it (lp_ensure_image).  Both touched under fr_ctx::lp_mutex only.
+    hipEvent_t ev_update = nullptr;
+    bool update_recorded = false;
     char last_kernel[96] = "";  // fr_worker_last_kernel: the dominant kernel of the most recent launch this worker enqueued
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
@@ -378,6 +395,9 @@ int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t l
 int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx_stride, const float *dense, float *out, int batch, int *err_flag);
 int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
                       int *err_flag);
+// n listed rows of one table <- src [n][dim], into the host arena with table_copy's head / tail addressing, over the pool's threads; a listed
+// id outside [0, rows) writes nothing and -> 1 (else 0).  A row listed twice ends up as the LAST of its listed sources.
+int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \
@@ -397,7 +417,13 @@ int frk_fill_table(float *base, int64_t row0, int64_t rows, int dim, int64_t row
 int frk_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale, hipStream_t s);
 // rows [0, rows) of an fp32 region (row r at src + r * src_stride, `floats` floats wide) -> the same rows in the operand type of `precision`
 // (bf16: RNE; fp8: x 2^e_x, saturated, e4m3) at dst + r * dst_stride: the rounding of the gather kernels themselves (fr_device.h)
-int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void *dst, size_t dst_stride, int64_t rows, int floats, int e_x, hipStream_t s);
+// ids != NULL: the `rows` listed rows ids[0 .. rows) instead, those inside [0, image_rows) (the patch behind fr_worker_update_rows)
+int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void *dst, size_t dst_stride, int64_t rows, int floats, int e_x, hipStream_t s,
+                        const int32_t *ids = nullptr, int64_t image_rows = 0);
+// fill_table_kernel's "rows from a list" arm: n listed rows ids[n] of one table <- src [n][dim]; head / tail: rows [0, head_rows) at `head`
+// (row_stride_bytes apart), rows [head_rows, rows) dense at `tail`; an id outside [0, rows) raises *err_flag (system-scope) and writes nothing
+int frk_scatter_rows(float *head, int64_t row_stride_bytes, float *tail, int64_t head_rows, int64_t rows, int dim, int n, const int32_t *ids, const float *src, int *err_flag,
+                     hipStream_t s);
 int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &groups, const int32_t *idx, int idx_stride, const float *dense, void *out, int batch, int *err_flag,
                int transport, int e_x, hipStream_t s, int out_words, bool one_chunk = false);
 // pooled (multi-hot) gather: idx = [batch][pool_cols]; weights = NULL or float [batch][pool_cols] (the weighted fold); bag and mode of word w =

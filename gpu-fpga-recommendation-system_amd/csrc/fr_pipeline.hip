@@ -1079,12 +1079,21 @@ int frk_stage_blocks(int stage, int n_words, int K, int N, int ldm, int nsplit) 
 // ---- operand-type bank image: rows of an fp32 region -> the same rows as bf16 / e4m3 (fr_api.cpp lp_ensure_image) ------------------------
 // One thread per (row, 16-byte fp32 word): the rounding functions are the gather's own (pack_bf16x2: RNE; pack_fp8_word: x 2^e_x,
 // saturated, e4m3), so a row converted here and gathered as it is equals the fp32 row gathered and converted then, bit for bit.
+// With a row-id list (ids != NULL; the patch behind fr_worker_update_rows) thread i converts row ids[i / words] instead of row i / words;
+// `rows` is then the list's length and an id outside [0, image_rows) -- outside the table, or a tail row the image does not hold -- does
+// nothing.  The fp32 word is read from the arena either way, never from the caller's rows: a patched image row is what a rebuild would make
+// of the arena, whichever of two duplicate ids won there.
 template <int PREC>
-__global__ void __launch_bounds__(256) convert_rows_lp_kernel(const char *src, size_t src_stride, char *dst, size_t dst_stride, long long rows, int words, float scale) {
+__global__ void __launch_bounds__(256) convert_rows_lp_kernel(const char *src, size_t src_stride, char *dst, size_t dst_stride, long long rows, int words, float scale,
+                                                              const int32_t *ids, long long image_rows) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long r = i / words;
+    long long r = i / words;
     const int w = (int)(i - r * words);
     if (r >= rows) return;
+    if (ids) {
+        r = ids[r];
+        if (r < 0 || r >= image_rows) return;
+    }
     const uint4 v = *reinterpret_cast<const uint4 *>(src + (size_t)r * src_stride + (size_t)w * 16);
     if constexpr (PREC == 1) {
         *reinterpret_cast<uint2 *>(dst + (size_t)r * dst_stride + (size_t)w * 8) =
@@ -1094,7 +1103,9 @@ __global__ void __launch_bounds__(256) convert_rows_lp_kernel(const char *src, s
     }
 }
 
-int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void *dst, size_t dst_stride, int64_t rows, int floats, int e_x, hipStream_t s) {
+// ids == NULL: rows [0, rows).  Otherwise: the `rows` listed rows ids[0 .. rows) that lie inside [0, image_rows).
+int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void *dst, size_t dst_stride, int64_t rows, int floats, int e_x, hipStream_t s, const int32_t *ids,
+                        int64_t image_rows) {
     if (rows <= 0 || floats <= 0) return FR_OK;
     if (floats % 4) FR_FAIL(FR_ERR_INVALID, "internal: a table row of %d floats is not whole 16-byte words", floats);
     const int words = floats / 4;
@@ -1102,10 +1113,11 @@ int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void 
     const long long blocks = (total + 255) / 256;
     if (blocks > 0x7fffffffLL) FR_FAIL(FR_ERR_INVALID, "internal: %lld rows x %d words exceed one conversion launch", (long long)rows, words);
     if (precision == FR_FC_BF16)
-        convert_rows_lp_kernel<1><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(static_cast<const char *>(src), src_stride, static_cast<char *>(dst), dst_stride, rows, words, 1.0f);
+        convert_rows_lp_kernel<1><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(static_cast<const char *>(src), src_stride, static_cast<char *>(dst), dst_stride, rows, words, 1.0f,
+                                                                                  ids, image_rows);
     else if (precision == FR_FC_FP8)
         convert_rows_lp_kernel<2><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(static_cast<const char *>(src), src_stride, static_cast<char *>(dst), dst_stride, rows, words,
-                                                                                  ldexpf(1.0f, e_x));
+                                                                                  ldexpf(1.0f, e_x), ids, image_rows);
     else
         FR_FAIL(FR_ERR_INVALID, "internal: no operand-type rows for precision %d", precision);
     KCHECK();

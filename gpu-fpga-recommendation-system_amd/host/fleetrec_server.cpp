@@ -19,6 +19,14 @@
 //        [--pool sum|mean|weighted] (with --hots N; sum is the default): mean = every column FR_POOL_MEAN (fr_ctx_set_pooling_modes); weighted = the
 //                        block's index rows are followed by float32 [B][index columns x N] per-sample weights, read into fr_worker_pool_weights_ptr,
 //                        and every batch goes through fr_worker_submit_pooled_weighted (fleetrec_sender --hots N --pool weighted).
+//        [--update-port P]: sparse row updates of the tables while serving (fr_ctx_update_rows).  A second listening socket, served by one thread of its
+//                        own beside the serving threads.  One message = int32 table, int32 n, int32 ids[n], float32 rows[n x dim of that table],
+//                        little-endian: row i of `rows` becomes table row ids[i]; the answer is one int32 status (0, or the library's FR_ERR_* --
+//                        FR_ERR_INDEX_RANGE for an id outside the table, whose other rows were still written).  Messages are taken until the peer
+//                        closes, then the next connection is accepted; a malformed header (table out of range, n < 0 or beyond 2^24 rows) closes
+//                        the connection.  Legal with every serving mode (submit-and-sync, --stream, --hots, --device -1); with --shards the message
+//                        is applied on every shard context the table is resident on.  Requests in flight meanwhile see old or new 16-byte row
+//                        words; every request received after the status came back sees the new rows.
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
@@ -66,6 +74,7 @@ struct Options {
     long row_cap = 0;
     int hots = 0;          // --hots N: pooled lookups, N slots per index column (0: one-hot)
     int pool = -1;         // --pool: 0 sum, 1 mean, 2 weighted (-1: not given)
+    int update_port = 0;   // --update-port P: the row-update socket (0: none)
 };
 
 static bool read_exact(int fd, void *buf, size_t n) {  // the recv loop of cuda_server.c:425-450
@@ -158,6 +167,67 @@ struct ShardedEngine {
     }
 };
 static ShardedEngine *g_engine = nullptr;
+
+// --update-port: one thread, one connection at a time, one message at a time (see the usage comment).  `ctxs`: the context, or every shard context.
+static std::atomic<bool> g_update_stop{false};
+static bool read_exact_or_stop(int fd, void *buf, size_t n) {   // read_exact that gives up when the server is shutting down
+    char *p = (char *)buf;
+    while (n) {
+        pollfd pfd{fd, POLLIN, 0};
+        const int pr = poll(&pfd, 1, 100);
+        if (g_update_stop.load()) return false;
+        if (pr == 0 || (pr < 0 && errno == EINTR)) continue;
+        if (pr < 0) return false;
+        ssize_t r = read(fd, p, n);
+        if (r <= 0) return false;
+        p += r;
+        n -= (size_t)r;
+    }
+    return true;
+}
+static void thread_update(int port, std::vector<fr_ctx *> ctxs) {
+    const fr_model_desc *m = fr_ctx_model(ctxs[0]);
+    int server_fd = socket(AF_INET, SOCK_STREAM, 0), opt = 1;
+    setsockopt(server_fd, SOL_SOCKET, SO_REUSEADDR, &opt, sizeof(opt));
+    sockaddr_in addr{};
+    addr.sin_family = AF_INET;
+    addr.sin_addr.s_addr = INADDR_ANY;
+    addr.sin_port = htons((uint16_t)port);
+    if (server_fd < 0 || bind(server_fd, (sockaddr *)&addr, sizeof(addr)) < 0 || listen(server_fd, 3) < 0) {
+        fprintf(stderr, "update port %d: socket/bind/listen: %s\n", port, strerror(errno));
+        if (server_fd >= 0) close(server_fd);
+        return;
+    }
+    std::vector<int32_t> ids;
+    std::vector<float> rows;
+    while (!g_update_stop.load()) {
+        pollfd pfd{server_fd, POLLIN, 0};
+        if (poll(&pfd, 1, 100) <= 0) continue;
+        const int sock = accept(server_fd, nullptr, nullptr);
+        if (sock < 0) continue;
+        setsockopt(sock, IPPROTO_TCP, TCP_NODELAY, &opt, sizeof(opt));
+        for (;;) {
+            int32_t head[2];
+            if (!read_exact_or_stop(sock, head, sizeof(head))) break;   // the peer closed (or the server is done)
+            const int32_t table = head[0], n = head[1];
+            if (table < 0 || table >= m->n_tables || n < 0 || n > (1 << 24)) break;   // malformed: the stream cannot be followed any further
+            ids.resize((size_t)n);
+            rows.resize((size_t)n * (size_t)m->tables[table].dim);
+            if (n && (!read_exact_or_stop(sock, ids.data(), ids.size() * sizeof(int32_t)) || !read_exact_or_stop(sock, rows.data(), rows.size() * sizeof(float)))) break;
+            // a shard context the table is not resident on answers FR_ERR_STATE and changes nothing: the message goes to every context, the
+            // status is that of the contexts that hold the table
+            int32_t status = FR_ERR_STATE;
+            for (fr_ctx *c : ctxs) {
+                const int rc = fr_ctx_update_rows(c, table, n, ids.data(), rows.data());
+                if (rc == FR_ERR_STATE && ctxs.size() > 1) continue;
+                if (status == FR_ERR_STATE || status == FR_OK) status = rc;
+            }
+            if (!write_exact(sock, &status, sizeof(status))) break;
+        }
+        close(sock);
+    }
+    close(server_fd);
+}
 
 struct ThreadInfo {  // struct CUDA_thread_info (cuda_server.c:91-98)
     int port;
@@ -429,6 +499,7 @@ int main(int argc, char **argv) {
         else if (a == "--small-block") o.small_block = atoi(next());
         else if (a == "--row-cap") o.row_cap = atol(next());
         else if (a == "--hots") o.hots = atoi(next());
+        else if (a == "--update-port") o.update_port = atoi(next());
         else if (a == "--pool") {
             std::string v = next();
             if (v != "sum" && v != "mean" && v != "weighted") { fprintf(stderr, "--pool: sum, mean or weighted, not '%s'\n", v.c_str()); return 2; }
@@ -517,6 +588,12 @@ int main(int argc, char **argv) {
     printf("model %s: %d tables, %.3f GB, record %d floats; batch %d, %d threads, ports %d..%d, %ld batches\n", model->name, model->n_tables,
            fr_model_table_bytes(model) / 1e9, model->record_len, o.batch, o.threads, o.port, o.port + o.threads - 1, o.total);
     fflush(stdout);
+    std::thread updater;
+    if (o.update_port > 0) {
+        updater = std::thread(thread_update, o.update_port, g_engine ? engine.ctxs : std::vector<fr_ctx *>{ctx});
+        printf("row updates on port %d\n", o.update_port);
+    }
+    fflush(stdout);
     std::vector<ThreadInfo> info(o.threads);
     std::vector<std::thread> th;
     const auto t0 = std::chrono::steady_clock::now();
@@ -526,6 +603,10 @@ int main(int argc, char **argv) {
         th.emplace_back(thread_consume, &info[i], std::cref(o));
     }
     for (auto &t : th) t.join();
+    if (updater.joinable()) {
+        g_update_stop.store(true);
+        updater.join();
+    }
     const auto t_end = std::chrono::steady_clock::now();
     const double secs = std::chrono::duration<double>(t_end - t0).count();
     int rc = 0;

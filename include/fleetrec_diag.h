@@ -71,6 +71,9 @@ float *fr_worker_features_dptr(fr_worker *w, int *ld_max);
  * scores).  fr_ctx_lp_bank_image_bytes: HBM the image holds now (0: none). */
 int fr_ctx_set_lp_bank_image(fr_ctx *ctx, int on);
 size_t fr_ctx_lp_bank_image_bytes(const fr_ctx *ctx);
+/* Full builds of the image this context has done so far: + 1 whenever a launch found it missing or stale and rebuilt it, never for the in-place
+ * patch of fr_worker_update_rows / fr_ctx_update_rows (fleetrec_serving.h). */
+long long fr_ctx_lp_bank_image_builds(const fr_ctx *ctx);
 
 /* Failure-injection hook for the table-sharded step's failure protocol (fleetrec.h, kind (2)): the FC chains of this worker's next `steps`
  * fr_worker_submit_sharded calls are reported as failed (FR_ERR_STATE) AFTER they ran -- the rank still joins both collectives, its score

@@ -130,6 +130,32 @@ int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, const int32
 float *fr_worker_pool_weights_ptr(fr_worker *w);
 int fr_worker_submit_pooled_weighted(fr_worker *w, int batch);
 
+/* Sparse row updates of the embedding tables (additive in ABI 6): the write side of the lookups.  n listed rows of ONE table: row_ids int32 [n],
+ * rows float [n][dim], dense -- row i of `rows` is the new content of table row row_ids[i].  Unlike fr_ctx_upload_table these are not set-up
+ * calls: they run beside streams in flight, leave an operand-type bank image current (its listed rows are converted again in place, from the
+ * fp32 arena, at the image's X exponent -- nothing is rebuilt) and touch neither tables_filled nor pooling or FC state.
+ * fr_worker_update_rows: device pointers (host pointers on the CPU back-end, which computes before it returns), asynchronous on the worker's
+ * stream; d_row_ids and d_rows (16-byte aligned) stay valid and untouched until fr_worker_sync(w) has returned.
+ *   Order on the worker: every batch submitted or pushed on w BEFORE the call gathers the old rows, every batch submitted or pushed on w AFTER
+ *   it the new ones -- one-hot and pooled entry points alike.  Batches fr_worker_push_device has queued for a fused launch are launched first
+ *   (not waited for), as fr_worker_sync does before it waits; the stage pipeline needs no draining (a batch's gather is launched by its own
+ *   push).  Host-fed batches still queued in a block (fr_worker_push_host / push_staged) make the call FR_ERR_STATE: flush first.
+ *   Across workers and contexts there is no order until fr_worker_sync(w) has returned; from then on every batch submitted on any worker of
+ *   the context sees the new rows.  A batch in flight on another worker meanwhile reads, per 16-byte row word, the old or the new word --
+ *   each word whole, rows not atomic across words.  (Visibility is that of kernel boundaries; no cache-control instruction is involved.)
+ *   Range: an id < 0 or >= the table's rows is FR_ERR_INDEX_RANGE at fr_worker_sync (the worker's sticky error word); that id writes nothing,
+ *   every in-range id of the call is still written.  Rows at or past a bank's common range (the tail of a bank-interleaved table) are
+ *   updatable as they are uploadable: no lookup reads them, fr_ctx_download_table does.
+ *   Duplicates: an id listed twice ends up, per 16-byte word, as that word of ONE of its listed source rows -- which one is unspecified (the
+ *   CPU back-end: the last); the bank image equals the conversion of whatever the fp32 arena ends up holding.
+ *   Arguments: n == 0 is FR_OK and does nothing; n < 0, a NULL pointer with n > 0, a table out of range, n * dim / 4 >= 2^31: FR_ERR_INVALID;
+ *   a table that is not resident on this shard: FR_ERR_STATE (fr_ctx_upload_table's text) -- resident tables of a sharded context are updatable.
+ *   fr_worker_sync after an update alone (no batch) succeeds; fr_worker_last_kernel keeps naming the last batch's kernel.
+ * fr_ctx_update_rows: the host form -- host arrays, synchronous: staged, the same launches on the context's set-up stream, waited for;
+ * returns FR_ERR_INDEX_RANGE itself.  It may be called beside workers in flight (the cross-worker paragraph applies to it). */
+int fr_worker_update_rows(fr_worker *w, int table, int n, const int32_t *d_row_ids, const float *d_rows);
+int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *h_row_ids, const float *h_rows);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
