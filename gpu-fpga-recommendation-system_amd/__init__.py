@@ -394,8 +394,21 @@ class Model:
         return None
 
 
+_ptr_generation = 0   # bumped whenever any DeviceBuffer's `ptr` changes (free() included): pointer arrays marshalled earlier are stale (Driver._pool_array)
+
+
 class DeviceBuffer:
     """Raw HBM allocation made through the C-ABI (no torch involved)."""
+
+    @property
+    def ptr(self):
+        return self._ptr
+
+    @ptr.setter
+    def ptr(self, p):
+        global _ptr_generation
+        _ptr_generation += 1
+        self._ptr = p
 
     def __init__(self, ctx, nbytes):
         self.ctx, self.nbytes = ctx, int(nbytes)
@@ -982,12 +995,26 @@ class Driver:
         h = ctypes.c_void_p()
         _check(lib().fr_driver_create(ctx._h, n_threads, depth, max_batch, ctypes.byref(h)))
         self._h = h
+        self._pools = {}   # "idx" / "dense" -> (pointer generation, the pool's buffers, their ctypes pointer array): see _pool_array
+
+    def _pool_array(self, which, pool):
+        """The ctypes array of a pool's device pointers.  A request stream rotates through ONE pool for its whole life, and marshalling 1024 pointers
+        costs as much as a short run: the array of the last pool is kept (with the buffers it was built from, so none of them can be collected and its
+        address reused) and handed out again while the list holds the same objects and no DeviceBuffer anywhere was freed or re-pointed since."""
+        key = tuple(pool)
+        gen = _ptr_generation
+        c = self._pools.get(which)
+        if c is not None and c[0] == gen and c[1] == key:   # (DeviceBuffer defines no __eq__: the tuples compare by identity)
+            return c[2]
+        arr = (ctypes.c_void_p * len(key))(*[b.ptr.value for b in key])
+        self._pools[which] = (gen, key, arr)
+        return arr
 
     def run_resident(self, batch, total_batches, idx_pool, dense_pool=None):
         """idx_pool / dense_pool: lists of DeviceBuffer.  -> elapsed seconds."""
         n = len(idx_pool)
-        ip = (ctypes.c_void_p * n)(*[b.ptr.value for b in idx_pool])
-        dp = (ctypes.c_void_p * n)(*[b.ptr.value for b in dense_pool]) if dense_pool else None
+        ip = self._pool_array("idx", idx_pool)
+        dp = self._pool_array("dense", dense_pool) if dense_pool else None
         el = ctypes.c_double()
         _check(lib().fr_driver_run_resident(self._h, batch, total_batches, ip, dp, n, ctypes.byref(el)))
         return el.value

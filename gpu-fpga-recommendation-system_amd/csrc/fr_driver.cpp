@@ -96,21 +96,50 @@ extern "C" int fr_driver_create(fr_ctx *ctx, int n_threads, int depth, int max_b
     return FR_OK;
 }
 
+// How many of the driver's workers a run of `total_batches` is spread over: no more than it has launch groups (a fused launch carries
+// fr_ctx_stream_group batches and takes one tile time however few of them it has, so a short run split over every worker ends in
+// several small launches, two of them back to back per thread, where one launch would have held all of it).  A CPU context and every
+// non-fused one report a group of 1: they use every worker from n_threads * depth batches on, as before.
+static int driver_workers_used(const fr_driver *d, int64_t total_batches) {
+    const int64_t group = fr_ctx_stream_group(d->ctx), all = (int64_t)d->n_threads * d->depth;
+    const int64_t want = (total_batches + group - 1) / group;
+    return (int)(want < 1 ? 1 : (want > all ? all : want));
+}
+
 extern "C" int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_batches, const int32_t *const *d_idx_pool,
                                       const float *const *d_dense_pool, int n_pool, double *elapsed_s) {
     if (!d || !d_idx_pool || n_pool < 1 || !elapsed_s) FR_FAIL(FR_ERR_INVALID, "bad argument");
     if (batch < 1 || batch > d->max_batch || total_batches < 0) FR_FAIL(FR_ERR_INVALID, "batch %d / total %lld out of range", batch, (long long)total_batches);
-    std::mutex mtx;               // pthread_mutex_t mtx (cuda_server.c:25)
-    int64_t global_batch_count = 0;  // cuda_server.c:23
-    std::vector<int> status(d->n_threads, FR_OK);
-    std::vector<std::string> messages(d->n_threads);
-    std::vector<std::thread> threads;
+    const int workers_used = driver_workers_used(d, total_batches);
+    const int threads_used = (workers_used + d->depth - 1) / d->depth;  // thread t owns workers t * depth ...; the first workers_used take batches
+    std::vector<int> status(threads_used, FR_OK);
+    std::vector<std::string> messages(threads_used);
     FR_DRAIN_DEVICE(d->ctx);
     const auto t0 = std::chrono::steady_clock::now();
-    for (int t = 0; t < d->n_threads; t++) {
+    if (workers_used == 1) {
+        // the whole run fits one launch group (or the driver has one worker): the calling thread pushes the batches in id order to
+        // worker (0, 0) and syncs once -- no thread to start, no counter to lock, one launch instead of one per worker
+        fr_worker *w = d->workers[0];
+        int rc = FR_OK;
+        for (int64_t id = 0; id < total_batches && rc == FR_OK; id++) {
+            const int p = (int)(id % n_pool);
+            rc = fr_worker_push_device(w, batch, d_idx_pool[p], d_dense_pool ? d_dense_pool[p] : nullptr,
+                                       d->score_rings[0] + (size_t)(id % FR_SCORE_RING) * d->max_batch);
+            if (rc == FR_OK && (id + 1) % FR_SCORE_RING == 0) rc = fr_worker_sync(w);  // once per trip round the ring, as below
+        }
+        const int r2 = fr_worker_sync(w);
+        if (rc == FR_OK) rc = r2;
+        status[0] = rc;
+        if (rc) messages[0] = fr_last_error();
+    }
+    std::mutex mtx;               // pthread_mutex_t mtx (cuda_server.c:25)
+    int64_t global_batch_count = 0;  // cuda_server.c:23
+    std::vector<std::thread> threads;
+    for (int t = 0; workers_used > 1 && t < threads_used; t++) {
         threads.emplace_back([&, t]() {
             fr_worker **wk = &d->workers[(size_t)t * d->depth];
             float **rings = &d->score_rings[(size_t)t * d->depth];
+            const int n_wk = workers_used - t * d->depth < d->depth ? workers_used - t * d->depth : d->depth;  // workers this thread uses
             int64_t local = 0;
             int rc = FR_OK;
 #ifdef FR_EXPERIMENTS
@@ -124,8 +153,8 @@ extern "C" int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_bat
                     id = global_batch_count++;
                 }
                 // enqueue without synchronising, like the reference's loop body (cuda_server.c:460-495)
-                const int slot = (int)(local % d->depth);
-                float *scores = rings[slot] + (size_t)((local / d->depth) % FR_SCORE_RING) * d->max_batch;
+                const int slot = (int)(local % n_wk);
+                float *scores = rings[slot] + (size_t)((local / n_wk) % FR_SCORE_RING) * d->max_batch;
                 local++;
                 const int p = (int)(id % n_pool);
 #ifdef FR_EXPERIMENTS
@@ -140,8 +169,8 @@ extern "C" int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_bat
 #endif
                 // bound the host's run-ahead (and keep score buffers unique): a worker is synchronised once per trip round its
                 // ring, the workers of a thread at staggered points so that one of them always has launches queued
-                const int64_t mine = (local - 1) / d->depth + 1;  // pushes this worker has received
-                if (rc == FR_OK && (mine + (int64_t)slot * (FR_SCORE_RING / d->depth)) % FR_SCORE_RING == 0) rc = fr_worker_sync(wk[slot]);
+                const int64_t mine = (local - 1) / n_wk + 1;  // pushes this worker has received
+                if (rc == FR_OK && (mine + (int64_t)slot * (FR_SCORE_RING / n_wk)) % FR_SCORE_RING == 0) rc = fr_worker_sync(wk[slot]);
 #ifdef FR_EXPERIMENTS
                 t_sync += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp1).count();
 #endif
@@ -150,7 +179,7 @@ extern "C" int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_bat
             if (FR_KNOB_ONCE("DRIVER_TIMING", 0))
                 fprintf(stderr, "driver thread %d: %lld pushes, in push %.3f s (max %.1f us), in sync %.3f s\n", t, (long long)local, t_push, 1e6 * t_push_max, t_sync);
 #endif
-            for (int s = 0; s < d->depth; s++) {
+            for (int s = 0; s < n_wk; s++) {
                 int r2 = fr_worker_sync(wk[s]);
                 if (rc == FR_OK) rc = r2;
             }
@@ -161,7 +190,7 @@ extern "C" int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_bat
     for (auto &th : threads) th.join();
     FR_DRAIN_DEVICE(d->ctx);
     *elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int t = 0; t < d->n_threads; t++)
+    for (int t = 0; t < threads_used; t++)
         if (status[t]) FR_FAIL(status[t], "driver thread %d: %s", t, messages[t].c_str());
     return FR_OK;
 }

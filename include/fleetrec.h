@@ -351,6 +351,9 @@ void fr_driver_destroy(fr_driver *d);
 /* Processes `total_batches` batches of `batch` items: threads draw batch ids from a mutex-guarded global
  * counter (cuda_server.c:408-417); batch id i reads the HBM-resident index rows d_idx_pool[i % n_pool]
  * (and d_dense_pool[i % n_pool] when the model has dense features; may be NULL otherwise).
+ * A run is spread over no more workers than it has launch groups: ceil(total_batches / fr_ctx_stream_group(ctx)) of them, at most
+ * n_threads * depth, thread t owning workers t * depth ...; a run of ONE worker (a single launch group, or a one-worker driver) is
+ * pushed in id order by the calling thread to worker (0, 0) and synchronised once, without a thread or a lock.
  * Returns wall time from first submit to last completion (device drained on both sides). */
 int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_batches, const int32_t *const *d_idx_pool,
                            const float *const *d_dense_pool, int n_pool, double *elapsed_s);
