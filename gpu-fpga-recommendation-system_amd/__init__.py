@@ -77,14 +77,16 @@ ABI_SYMBOLS = [
     "fr_ctx_set_pooling", "fr_ctx_pooled_index_cols", "fr_worker_gather_pooled", "fr_worker_submit_pooled_device", "fr_worker_submit_pooled",
     "fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device", "fr_worker_pool_weights_ptr",
     "fr_worker_submit_pooled_weighted",
+    "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr",
     "fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
 ]
 
 
-# the entry points ABI 6 gained last (pooling modes and per-sample weights, sparse row updates): the only names an FR_LIB build of the same ABI may lack
+# the entry points ABI 6 gained last (pooling modes and per-sample weights, sparse row updates, the offsets form of the pooled lookups): the only names an FR_LIB build of the same ABI may lack
 _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
                    "fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device",
-                   "fr_worker_pool_weights_ptr", "fr_worker_submit_pooled_weighted")
+                   "fr_worker_pool_weights_ptr", "fr_worker_submit_pooled_weighted",
+                   "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr")
 
 
 def lib():
@@ -156,6 +158,8 @@ def lib():
         "fr_ctx_set_pooling_modes": (i32, [vp, pi, i32]), "fr_ctx_pooling_mode": (i32, [vp, i32]),
         "fr_worker_gather_pooled_weighted": (i32, [vp, i32, vp, vp, vp, vp]), "fr_worker_submit_pooled_weighted_device": (i32, [vp, i32, vp, vp, vp, vp]),
         "fr_worker_pool_weights_ptr": (pf, [vp]), "fr_worker_submit_pooled_weighted": (i32, [vp, i32]),
+        "fr_worker_gather_pooled_csr": (i32, [vp, i32, vp, vp, i64, vp, vp, vp]), "fr_worker_submit_pooled_csr_device": (i32, [vp, i32, vp, vp, i64, vp, vp, vp]),
+        "fr_worker_pool_offsets_ptr": (pi, [vp]), "fr_worker_submit_pooled_csr": (i32, [vp, i32, i32]),
         "fr_worker_update_rows": (i32, [vp, i32, i32, vp, vp]), "fr_ctx_update_rows": (i32, [vp, i32, i32, vp, vp]),
         "fr_ctx_lp_bank_image_builds": (ctypes.c_longlong, [vp]),
     }
@@ -171,6 +175,29 @@ def lib():
         raise FleetRecError(FR_ERR_STATE, "%s reports ABI version %d, this binding needs %d" % (LIB_PATH, got, ABI_VERSION))
     _lib = L
     return L
+
+
+def bags_to_csr(padded_idx, hots, weights=None, keep_empty=False):
+    """The padded rectangle of the pooled lookups (int32 [B][sum(hots)], -1 = empty slot; weights float32 of the same shape or None) ->
+    (offsets int32 [B * C + 1], indices int32 [nnz], weights float32 [nnz] or None): the same bags in the offsets form, item-major and
+    column-minor, every bag's entries in slot order.  The -1 slots are dropped unless keep_empty (then every bag keeps its hots[c] slots)."""
+    idx = np.ascontiguousarray(np.asarray(padded_idx, dtype=np.int32).reshape(len(padded_idx), -1))
+    hots = np.asarray(hots, dtype=np.int64).reshape(-1)
+    if idx.shape[1] != int(hots.sum()):
+        raise FleetRecError(FR_ERR_INVALID, "padded index rows have %d columns, hots sum to %d" % (idx.shape[1], int(hots.sum())))
+    keep = np.ones(idx.shape, bool) if keep_empty else idx != -1
+    if len(hots) == 0 or int(hots.min()) < 1:
+        raise FleetRecError(FR_ERR_INVALID, "hots must be at least 1 for every index column")
+    pre = np.concatenate([[0], np.cumsum(hots)[:-1]])                 # every column's first padded slot: its slots are contiguous
+    lens = np.add.reduceat(keep, pre, axis=1, dtype=np.int64)       # [B][C]: the kept slots of every bag
+    offsets = np.zeros(lens.size + 1, np.int64)
+    np.cumsum(lens.reshape(-1), out=offsets[1:])
+    if int(offsets[-1]) > np.iinfo(np.int32).max:
+        raise FleetRecError(FR_ERR_INVALID, "%d entries do not fit int32 offsets" % int(offsets[-1]))
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(idx.shape))[keep]
+    return offsets.astype(np.int32), idx[keep], w
 
 
 def _check(status):
@@ -898,6 +925,85 @@ class Worker:
         self.gather_pooled(B, d_idx, d_dense, d_rec, weights=d_w)
         self.sync()
         return d_rec.download(np.uint32, n)
+
+    # the offsets (CSR) form of the pooled lookups: bag (b, c) = indices[offsets[b * C + c] : offsets[b * C + c + 1]], C = model.idx_cols ----
+    def gather_pooled_csr(self, batch, d_offsets, d_indices, nnz, d_dense, d_records, weights=None):
+        """d_offsets int32 [batch * C + 1], d_indices int32 [nnz] (None when nnz == 0), weights: device float32 [nnz] or None -> fp32 records in
+        the model's layout (fr_worker_gather_pooled_csr; asynchronous, follow with sync())."""
+        _check(lib().fr_worker_gather_pooled_csr(self._h, batch, self._ptr(d_offsets), self._ptr(d_indices), int(nnz), self._ptr(weights), self._ptr(d_dense),
+                                                 self._ptr(d_records)))
+
+    def submit_pooled_csr_device(self, batch, d_offsets, d_indices, nnz, d_dense, d_scores, weights=None):
+        _check(lib().fr_worker_submit_pooled_csr_device(self._h, batch, self._ptr(d_offsets), self._ptr(d_indices), int(nnz), self._ptr(weights), self._ptr(d_dense),
+                                                        self._ptr(d_scores)))
+
+    def submit_pooled_csr(self, batch, weighted=False):
+        """fr_worker_submit_pooled_csr on the offsets in pool_offsets, the flat entries in the pinned index buffer and (weighted) the flat weights
+        in the pinned weight buffer (asynchronous; follow with sync())."""
+        _check(lib().fr_worker_submit_pooled_csr(self._h, int(batch), 1 if weighted else 0))
+
+    @property
+    def pool_offsets(self):
+        """int32 [max_batch * C + 1] view of the pinned offsets buffer (fr_worker_pool_offsets_ptr); None on a worker created before
+        Context.set_pooling."""
+        p = lib().fr_worker_pool_offsets_ptr(self._h)
+        if not p:
+            return None
+        return np.ctypeslib.as_array(p, shape=(self.max_batch * self.ctx.model.idx_cols + 1,))
+
+    def _csr_arrays(self, offsets, indices, weights):
+        if self.ctx.pooled_index_cols <= 0:
+            raise FleetRecError(FR_ERR_STATE, "no pooling is set on the context: call Context.set_pooling first")
+        C = self.ctx.model.idx_cols
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32).reshape(-1))
+        if off.size < 1 or (off.size - 1) % C:
+            raise FleetRecError(FR_ERR_INVALID, "%d offsets are not batch x %d index columns + 1" % (off.size, C))
+        ind = np.ascontiguousarray(np.asarray(indices, dtype=np.int32).reshape(-1))
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+            if w.size != ind.size:
+                raise FleetRecError(FR_ERR_INVALID, "%d per-sample weights for %d indices" % (w.size, ind.size))
+        return (off.size - 1) // C, off, ind, w
+
+    def infer_pooled_csr(self, offsets, indices, dense=None, weights=None):
+        """Host-buffer path of the offsets-form pooled lookup: offsets int32 [B * C + 1], indices int32 [nnz] (-1 = empty slot), weights float32
+        [nnz] or None (+ dense) -> scores float32 [B].  The worker must have been created after Context.set_pooling."""
+        B, off, ind, w = self._csr_arrays(offsets, indices, weights)
+        if self.pool_offsets is None or (w is not None and self.pool_weights is None):
+            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after Context.set_pooling")
+        if B > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
+        if ind.size > self.max_batch * self._pool_cap:
+            raise FleetRecError(FR_ERR_INVALID, "%d indices exceed the worker's index buffer (%d x %d)" % (ind.size, self.max_batch, self._pool_cap))
+        self.pool_offsets[:off.size] = off
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:ind.size] = ind
+        if w is not None:
+            self.pool_weights.reshape(-1)[:w.size] = w
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        self.submit_pooled_csr(B, weighted=w is not None)
+        self.sync()
+        return self.score[:B].copy()
+
+    def gather_pooled_csr_records(self, offsets, indices, dense=None, weights=None):
+        """-> uint32 [flat B*K] record buffer in the model's layout: the pooled records of the bags offsets / indices (/ weights) describe."""
+        ctx, m = self.ctx, self.ctx.model
+        B, off, ind, w = self._csr_arrays(offsets, indices, weights)
+        d_off = DeviceBuffer.from_numpy(ctx, off)
+        d_ind = DeviceBuffer.from_numpy(ctx, ind) if ind.size else None
+        d_w = DeviceBuffer.from_numpy(ctx, w if w.size else np.zeros(1, np.float32)) if w is not None else None
+        d_dense = DeviceBuffer.from_numpy(ctx, np.asarray(dense, dtype=np.float32)) if m.dense_len else None
+        n = B * m.record_len
+        d_rec = DeviceBuffer(ctx, n * 4)
+        try:
+            self.gather_pooled_csr(B, d_off, d_ind, ind.size, d_dense, d_rec, weights=d_w)
+            self.sync()
+            return d_rec.download(np.uint32, n)
+        finally:
+            for b in (d_off, d_ind, d_w, d_dense, d_rec):
+                if b is not None:
+                    b.free()
 
     # convenience used by the parity tests --------------------------------------------------------
     def gather_records(self, idx, dense=None):

@@ -781,7 +781,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->ctx && w->ctx->cpu) {
         fr_comm_worker_release(w);   // a sharded step still on the worker's host stream: waited for (bounded), its communicator let go
         if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
-        void *host[] = {w->h_idx, w->h_pool_w, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
+        void *host[] = {w->h_idx, w->h_pool_w, w->h_pool_off, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
         for (void *p : host) free(p);
         fr_ctx *held = w->counted ? w->ctx : nullptr;
         delete w;
@@ -794,6 +794,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
     if (w->h_idx) (void)hipHostFree(w->h_idx);
     if (w->h_pool_w) (void)hipHostFree(w->h_pool_w);
+    if (w->h_pool_off) (void)hipHostFree(w->h_pool_off);
     if (w->h_dense) (void)hipHostFree(w->h_dense);
     if (w->h_score) (void)hipHostFree(w->h_score);
     if (w->h_err) (void)hipHostFree(w->h_err);
@@ -869,12 +870,13 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
         auto host = [](size_t bytes) { return aligned_alloc(64, align_up(bytes ? bytes : 64, 64)); };
         w->h_idx = (int32_t *)host(B * (size_t)w->idx_cap * sizeof(int32_t));
         if (w->pool_w_cap) w->h_pool_w = (float *)host(B * (size_t)w->pool_w_cap * sizeof(float));
+        if (w->pool_w_cap) w->h_pool_off = (int32_t *)host((B * idx_cols(ctx) + 1) * sizeof(int32_t));
         if (m.dense_len) w->h_dense = (float *)host(B * m.dense_len * sizeof(float));
         w->h_score = (float *)host(B * sizeof(float));
         w->d_records = (float *)host(B * (size_t)ctx->slice_padded * sizeof(float));
         w->c_scratch = (float *)host(B * ((size_t)m.fc[1] + m.fc[2] + m.fc[3]) * sizeof(float));
         if (ctx->n_shards > 1) w->c_x = (float *)host(B * (size_t)m.fc[0] * sizeof(float));
-        if (!w->h_idx || (w->pool_w_cap && !w->h_pool_w) || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
+        if (!w->h_idx || (w->pool_w_cap && (!w->h_pool_w || !w->h_pool_off)) || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
             fr_worker_destroy(w);
             FR_FAIL(FR_ERR_OOM, "out of host memory (worker buffers for batch %d)", max_batch);
         }
@@ -916,6 +918,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     }
     W_HIP(hipHostMalloc((void **)&w->h_idx, B * (size_t)w->idx_cap * sizeof(int32_t), hipHostMallocDefault));
     if (w->pool_w_cap) W_HIP(hipHostMalloc((void **)&w->h_pool_w, B * (size_t)w->pool_w_cap * sizeof(float), hipHostMallocDefault));   // read in place by the gather, like h_idx
+    if (w->pool_w_cap) W_HIP(hipHostMalloc((void **)&w->h_pool_off, (B * idx_cols(ctx) + 1) * sizeof(int32_t), hipHostMallocDefault));   // bag offsets of the offsets-form host call
     if (m.dense_len) W_HIP(hipHostMalloc((void **)&w->h_dense, B * m.dense_len * sizeof(float), hipHostMallocDefault));
     W_HIP(hipHostMalloc((void **)&w->h_score, B * sizeof(float), hipHostMallocDefault));
     // index-range flag: pinned, device-visible host word.  Kernels touch it only on the error path
@@ -953,6 +956,7 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
 
 extern "C" int32_t *fr_worker_idx_ptr(fr_worker *w) { return w ? w->h_idx : nullptr; }
 extern "C" float *fr_worker_pool_weights_ptr(fr_worker *w) { return w ? w->h_pool_w : nullptr; }
+extern "C" int32_t *fr_worker_pool_offsets_ptr(fr_worker *w) { return w ? w->h_pool_off : nullptr; }
 extern "C" float *fr_worker_dense_ptr(fr_worker *w) { return w ? w->h_dense : nullptr; }
 extern "C" float *fr_worker_score_ptr(fr_worker *w) { return w ? w->h_score : nullptr; }
 extern "C" void *fr_worker_stream(fr_worker *w) { return w ? (void *)w->stream : nullptr; }
@@ -1697,26 +1701,32 @@ static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *mode
         wide = wide && hots[c] % 4 == 0;   // then every bag starts on a multiple of 4 slots too, and so does every item's row
         any_mean = any_mean || (modes && modes[c] == FR_POOL_MEAN);
     }
-    std::vector<FrPoolDesc> pool(ctx->h_words.size());
+    // a second array for the offsets (CSR) form: the word needs its COLUMN there (its bag is found through offsets[b * cols + col]), hots is the cap
+    std::vector<FrPoolDesc> pool(ctx->h_words.size()), csr(ctx->h_words.size());
     for (size_t i = 0; i < pool.size(); i++) {
         const uint32_t col = ctx->h_words[i].idx_col;
         pool[i] = (col & FR_DESC_DENSE) ? FrPoolDesc{0u, 1u}
                                         : FrPoolDesc{prefix[col], (uint32_t)hots[col] | (modes && modes[col] == FR_POOL_MEAN ? FR_POOL_DESC_MEAN : 0u)};
+        csr[i] = (col & FR_DESC_DENSE) ? FrPoolDesc{0u, 1u} : FrPoolDesc{col, pool[i].hots};
     }
     if (!ctx->cpu) {
         FrPoolDesc *d = nullptr;
-        FR_HIP(hipMalloc((void **)&d, sizeof(FrPoolDesc) * (pool.empty() ? 1 : pool.size())));
-        const hipError_t e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * pool.size(), hipMemcpyHostToDevice);
+        const size_t n = pool.size();
+        FR_HIP(hipMalloc((void **)&d, sizeof(FrPoolDesc) * (n ? 2 * n : 1)));
+        hipError_t e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d + n, csr.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(d);
             FR_FAIL(FR_ERR_HIP, "hipMemcpy(pooled descriptors) failed: %s", hipGetErrorString(e));
         }
         if (ctx->d_pool) (void)hipFree(ctx->d_pool);
         ctx->d_pool = d;
+        ctx->d_pool_csr = d + n;
     }
     std::vector<int32_t> h(hots, hots + cols), md(cols, FR_POOL_SUM);   // (hots may be ctx->pool_hots itself: copied before it is replaced)
     if (modes) md.assign(modes, modes + cols);
     ctx->h_pool.swap(pool);
+    ctx->h_pool_csr.swap(csr);
     ctx->pool_hots.swap(h);
     ctx->pool_modes.swap(md);
     ctx->pool_any_mean = any_mean;
@@ -1740,8 +1750,9 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
     if (!hots) {
         if (ctx->d_pool) FR_HIP(hipFree(ctx->d_pool));
-        ctx->d_pool = nullptr;
+        ctx->d_pool = ctx->d_pool_csr = nullptr;
         ctx->h_pool.clear();
+        ctx->h_pool_csr.clear();
         ctx->pool_hots.clear();
         ctx->pool_modes.clear();
         ctx->pool_any_mean = false;
@@ -1776,11 +1787,24 @@ extern "C" int fr_ctx_pooling_mode(const fr_ctx *ctx, int col) {
 extern "C" int fr_ctx_pooled_index_cols(const fr_ctx *ctx) { return ctx ? ctx->pool_cols : 0; }
 
 // weighted = the call is one of the *_weighted entry points: d_weights must be there, and every column's mode SUM
-static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records) {
+// d_offsets != NULL: the offsets (CSR) form -- d_idx / d_weights are the nnz flat entries (weighted = d_weights != NULL), the descriptors the second array;
+// its three 4000 MiB bounds are checked here, once, for both back-ends
+static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
+                                const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
     fr_ctx *c = w->ctx;
+    const bool csr = d_offsets != nullptr;   // (the offsets-form entry points refuse a NULL d_offsets themselves)
     if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
     if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
-    if (!d_idx) FR_FAIL(FR_ERR_INVALID, "d_idx is NULL");
+    if (csr) {
+        if (nnz < 0) FR_FAIL(FR_ERR_INVALID, "nnz %lld is negative", (long long)nnz);
+        if (nnz > 0 && !d_idx) FR_FAIL(FR_ERR_INVALID, "d_indices is NULL with nnz %lld", (long long)nnz);
+        const size_t off_bytes = ((size_t)batch * idx_cols(c) + 1) * 4, rec_bytes = (size_t)batch * (size_t)c->slice_padded * 4;
+        if (off_bytes >= ((size_t)4000 << 20) || (uint64_t)nnz * 4 >= ((uint64_t)4000 << 20) || rec_bytes >= ((size_t)4000 << 20))
+            FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's offsets (%zu bytes), entries%s (%llu bytes) or records (%zu bytes) reach 4000 MiB", off_bytes, d_weights ? " / weights" : "",
+                    (unsigned long long)nnz * 4, rec_bytes);
+    } else if (!d_idx) {
+        FR_FAIL(FR_ERR_INVALID, "d_idx is NULL");
+    }
     if (weighted) {
         if (!d_weights) FR_FAIL(FR_ERR_INVALID, "d_weights is NULL");
         if (c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
@@ -1790,17 +1814,25 @@ static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, c
         for (const FrWordDesc &wd : c->h_words) needs |= (wd.idx_col & FR_DESC_DENSE) != 0;
         if (needs) FR_FAIL(FR_ERR_INVALID, "model has dense features but d_dense is NULL");
     }
+    if (csr) {
+        if (nnz == 0) d_idx = nullptr;   // (no entry is ever read: the resource is empty)
+        if (c->cpu)
+            return frc_gather_pooled(c->h_words.data(), c->h_pool_csr.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err, d_offsets, (int)idx_cols(c), nnz);
+        return frk_gather_pooled(c->d_words, c->d_pool_csr, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, false, c->pool_any_mean, d_dense, d_records, batch,
+                                 w->d_err, w->stream, c->slice_padded / 4, d_offsets, (int)idx_cols(c), nnz);
+    }
     if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err);
     return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, c->pool_wide, c->pool_any_mean, d_dense, d_records, batch,
                              w->d_err, w->stream, c->slice_padded / 4);
 }
 
-static int gather_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records) {
+static int gather_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
+                              const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
     int rc = check_ready(w, batch, true, false);
     if (rc) return rc;
     if (!d_records) FR_FAIL(FR_ERR_INVALID, "d_records is NULL");
     FR_SET_DEVICE(w->ctx);
-    rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, d_records);
+    rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, d_records, d_offsets, nnz);
     if (rc) return rc;
     keep_kernel(w);
     w->in_flight = true;
@@ -1816,20 +1848,22 @@ extern "C" int fr_worker_gather_pooled_weighted(fr_worker *w, int batch, const i
 }
 
 // pooled records into the worker's record buffer, then the chain fr_worker_fc_only runs from records (launch_fc), on the same stream
-static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores) {
+static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores,
+                              const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
     if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
-    int rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records);
+    int rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records, d_offsets, nnz);
     if (rc) return rc;
     w->in_flight = true;   // the gather is enqueued whatever the chain's launch says
     return launch_fc(w, batch, w->d_records, d_scores);
 }
 
-static int submit_pooled_device_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores) {
+static int submit_pooled_device_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores,
+                                     const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
     if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
     FR_SET_DEVICE(w->ctx);
-    return submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores);
+    return submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores, d_offsets, nnz);
 }
 
 extern "C" int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
@@ -1840,7 +1874,8 @@ extern "C" int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, 
     return submit_pooled_device_impl(w, batch, d_idx, d_weights, true, d_dense, d_scores);
 }
 
-static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
+// what both host forms (padded and offsets) ask of the worker before they read its pinned buffers
+static int pooled_host_ready(fr_worker *w, int batch, bool weighted) {
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
     if (w->in_flight) FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
@@ -1850,6 +1885,13 @@ static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
         FR_FAIL(FR_ERR_STATE, "the worker's index buffers hold %d columns per item, pooled rows have %d: create the worker after fr_ctx_set_pooling", w->idx_cap, c->pool_cols);
     if (weighted && (!w->h_pool_w || w->pool_w_cap < c->pool_cols))
         FR_FAIL(FR_ERR_STATE, "the worker's weight buffer holds %d columns per item, pooled rows have %d: create the worker after fr_ctx_set_pooling", w->pool_w_cap, c->pool_cols);
+    return FR_OK;
+}
+
+static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
+    int rc = pooled_host_ready(w, batch, weighted);
+    if (rc) return rc;
+    fr_ctx *c = w->ctx;
     FR_SET_DEVICE(c);
     // as fr_worker_submit: the gather reads the pinned index rows (weights, dense features) in place, the output layer writes the pinned scores
     return submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
@@ -1857,6 +1899,33 @@ static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
 
 extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, false); }
 extern "C" int fr_worker_submit_pooled_weighted(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, true); }
+
+// ---- the offsets (CSR) form of the pooled lookups: the same gather, fold and chain; only the way a bag is found differs ----
+extern "C" int fr_worker_gather_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
+                                           float *d_records) {
+    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
+    return gather_pooled_impl(w, batch, d_indices, d_weights, d_weights != nullptr, d_dense, d_records, d_offsets, nnz);
+}
+
+extern "C" int fr_worker_submit_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
+                                                  float *d_scores) {
+    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
+    return submit_pooled_device_impl(w, batch, d_indices, d_weights, d_weights != nullptr, d_dense, d_scores, d_offsets, nnz);
+}
+
+extern "C" int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted) {
+    int rc = pooled_host_ready(w, batch, weighted != 0);
+    if (rc) return rc;
+    fr_ctx *c = w->ctx;
+    if (!w->h_pool_off) FR_FAIL(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after fr_ctx_set_pooling");
+    // the host knows the offsets: the first and the last are checked here, before anything is enqueued (the per-bag checks are the gather's)
+    const int64_t nnz = w->h_pool_off[(size_t)batch * idx_cols(c)];
+    if (w->h_pool_off[0] != 0) FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_pooled_csr: offsets[0] is %d, not 0", w->h_pool_off[0]);
+    if (nnz < 0 || nnz > (int64_t)batch * c->pool_cols)
+        FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_pooled_csr: offsets[batch * cols] = %lld entries, outside [0, batch %d x %d pooled columns]", (long long)nnz, batch, c->pool_cols);
+    FR_SET_DEVICE(c);
+    return submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted != 0, c->model.dense_len ? w->h_dense : nullptr, w->h_score, w->h_pool_off, nnz);
+}
 
 // Sharded mode, low-precision transport: the shard's slice [batch][slice_padded] as bf16 or e4m3 (x 2^e of the context's X exponent)
 // instead of fp32 -- what travels through the all-gather.  transport = FR_FC_FP32 is fr_worker_gather_only.

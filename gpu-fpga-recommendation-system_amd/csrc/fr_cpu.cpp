@@ -288,7 +288,9 @@ int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx
 #pragma GCC push_options
 #pragma GCC optimize("fp-contract=off")
 int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
-                      int *err_flag) {
+                      int *err_flag, const int32_t *offsets, int n_icols, long long nnz) {
+    // offsets != NULL: the offsets form -- bag (b, c) = idx[offsets[b * n_icols + c] .. offsets[b * n_icols + c + 1]), c = pool[w].first, cap = pool[w].hots;
+    // a malformed bag (fleetrec_serving.h) raises the flag and is folded as an empty one: nothing outside the three arrays is read
     const int chunk = 32;
     std::atomic<int> bad{0};
     char *o = reinterpret_cast<char *>(out);
@@ -296,8 +298,8 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
         const int b0 = u * chunk, b1 = b0 + chunk < batch ? b0 + chunk : batch;
         int local_bad = 0;
         for (int b = b0; b < b1; b++) {
-            const int32_t *row = idx + (size_t)b * pool_cols;
-            const float *wrow = weights ? weights + (size_t)b * pool_cols : nullptr;
+            const int32_t *row = offsets ? nullptr : idx + (size_t)b * pool_cols;
+            const float *wrow = weights && !offsets ? weights + (size_t)b * pool_cols : nullptr;
             for (int w = 0; w < n_words; w++) {
                 const FrWordDesc &d = words[w];
                 char *dst = o + ((size_t)d.dst_blk * (size_t)batch + (size_t)b * d.dst_stride + d.dst_off) * 16;
@@ -305,11 +307,24 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
                     memcpy(dst, reinterpret_cast<const char *>(dense) + d.src + (size_t)b * d.stride, 16);
                     continue;
                 }
-                const uint32_t hots = pool[w].hots & ~FR_POOL_DESC_MEAN;
+                uint32_t hots = pool[w].hots & ~FR_POOL_DESC_MEAN;
+                const int32_t *bag = row ? row + pool[w].first : nullptr;
+                const float *wbag = wrow ? wrow + pool[w].first : nullptr;
+                if (offsets) {
+                    const int64_t s0 = offsets[(size_t)b * n_icols + pool[w].first], s1 = offsets[(size_t)b * n_icols + pool[w].first + 1];
+                    if (s0 < 0 || s1 < s0 || s1 > nnz || s1 - s0 > (int64_t)hots) {
+                        local_bad = 1;
+                        hots = 0;
+                    } else {
+                        hots = (uint32_t)(s1 - s0);
+                        bag = hots ? idx + s0 : nullptr;
+                        wbag = weights && hots ? weights + s0 : nullptr;
+                    }
+                }
                 uint32_t acc[4] = {0u, 0u, 0u, 0u};
                 uint32_t cnt = 0;
                 for (uint32_t j = 0; j < hots; j++) {
-                    uint32_t r = (uint32_t)row[pool[w].first + j];
+                    uint32_t r = (uint32_t)bag[j];
                     if (r == 0xFFFFFFFFu) continue;   // an empty slot
                     if (r >= d.rows) {
                         local_bad = 1;
@@ -317,8 +332,8 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
                     }
                     uint32_t x[4];
                     memcpy(x, reinterpret_cast<const char *>(d.src) + (uint64_t)r * d.stride, 16);
-                    if (wrow) {
-                        const float wj = wrow[pool[w].first + j];
+                    if (wbag) {
+                        const float wj = wbag[j];
                         for (int k = 0; k < 4; k++) {
                             float v;
                             memcpy(&v, &x[k], 4);

@@ -396,13 +396,23 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
 // body, so the unweighted SUM window loop holds no trace of weights, counts or quotients.  A kernel's register count is that of its larger arm, and it decides the occupancy of both: the weighted arm
 // therefore runs the chunk in two passes of half as many row words in flight (gather_pooled_kernel below) and takes its weights in units of
 // at most 4 slots, one unit ahead of the fold, so that it stays inside the unweighted arm's registers (no spill, no scratch in either).
-template <int ITEMS, int WIN, bool WIDE, bool WEIGHTED, bool COUNT>
+// The OFFSETS form (CSR = true; offsets != NULL at the launch): the bags are not a padded rectangle but indices[offsets[b * n_icols + c] ..
+// offsets[b * n_icols + c + 1]), weights parallel to indices, nnz entries in all; the word's FrPoolDesc then holds its index COLUMN in `first` and the
+// column's CAP in `hots`.  Per item the thread loads its bag's two offsets through a resource bounded at (batch * n_icols + 1) * 4 bytes (an item
+// past the batch is sent past the bounds and reads 0, 0: an empty bag), checks them (start < 0, end < start, end > nnz, longer than the cap: the
+// error flag, and the bag is taken as empty, so a malformed bag issues no slot load at all), and walks windows up to the LONGEST bag among its
+// items; the slot and weight loads go at (start + slot) * 4 through resources bounded at nnz * 4 bytes, masked by the bag's own length.  Rows,
+// the clamp of a bad row to 0 and the fold are the code of the padded form, so the bits are those of the same bags padded with -1.  Only
+// 4-byte alignment is given: the form has no 16-byte index loads (the WIDE instantiations compile it out), and it always runs in the half
+// passes of the MEAN / weighted arms, with its offsets and lengths in the registers the other half's row words would have taken.
+template <int ITEMS, int WIN, bool WIDE, bool WEIGHTED, bool COUNT, bool CSR = false>
 __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, int w, unsigned b0,
                                                    const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
                                                    const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
-                                                   unsigned out_bytes) {
+                                                   unsigned out_bytes, const int32_t *__restrict__ offsets = nullptr, int n_icols = 0, unsigned nnz = 0u) {
 #pragma clang fp contract(off)
     static_assert(!WIDE || WIN % 4 == 0, "16-byte index loads need whole groups of 4 slots");
+    static_assert(!(CSR && WIDE), "the offsets form has no 16-byte index loads");
     const uint4 d0 = reinterpret_cast<const uint4 *>(words)[2 * w];
     const uint4 d1 = reinterpret_cast<const uint4 *>(words)[2 * w + 1];
     const uint2 pd = reinterpret_cast<const uint2 *>(pool)[w];
@@ -416,10 +426,11 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
     const unsigned blk = (dst_blk * (unsigned)batch + dst_off) * 16u;
     const unsigned ostride = dst_stride * 16u;
     const unsigned irow = (unsigned)pool_cols * 4u;
-    const __amdgpu_buffer_rsrc_t rs_idx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, (unsigned)batch * irow, 0x00020000);
+    const unsigned idx_bytes = CSR ? nnz * 4u : (unsigned)batch * irow;   // CSR: the flat entries (the launcher keeps nnz * 4 below 4000 MiB)
+    const __amdgpu_buffer_rsrc_t rs_idx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, idx_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, out_bytes, 0x00020000);
     // the weights' resource has the index rows' shape and bounds (WEIGHTED only; the unweighted body never touches it)
-    const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(weights), 0, WEIGHTED ? (unsigned)batch * irow : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(weights), 0, WEIGHTED ? idx_bytes : 0u, 0x00020000);
     typedef const u32x4_t __attribute__((address_space(1))) * gptr_t;   // a global_load (not a flat one)
     bool bad = false;
     uint32_t badv = 0u;   // WEIGHTED: `bad` as a vector register
@@ -430,12 +441,38 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
     for (int i = 0; i < ITEMS; i++) acc[i] = make_uint4(0u, 0u, 0u, 0u), have[i] = false;
 #pragma unroll
     for (int i = 0; i < (ITEMS + 3) / 4; i++) cnt[i] = 0u;
-    for (uint32_t j0 = 0; j0 < hots; j0 += WIN) {
+    // CSR: where each item's bag starts (in entries) and how long it is; `bound` = the longest of them (the padded form: the word's hots)
+    uint32_t st[CSR ? ITEMS : 1], ln[CSR ? ITEMS : 1];
+    uint32_t bound = hots;
+    if constexpr (CSR) {
+        const unsigned off_bytes = ((unsigned)batch * (unsigned)n_icols + 1u) * 4u;
+        const __amdgpu_buffer_rsrc_t rs_off = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(offsets), 0, off_bytes, 0x00020000);
+        bound = is_dense ? 1u : 0u;   // a DENSE word is a bag of one and has no offsets
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) {
+            const unsigned b = b0 + i;
+            st[i] = 0u, ln[i] = 0u;
+            if (!is_dense) {
+                // an item past the batch goes to the resource's end: both loads are dropped by its bounds and give 0
+                const unsigned ooff = b < (unsigned)batch ? (b * (unsigned)n_icols + first) * 4u : off_bytes;
+                const int32_t s0 = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_off, ooff, 0, 0);
+                const int32_t s1 = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_off, ooff + 4u, 0, 0);
+                // 0 <= s0 <= s1 <= nnz and s1 - s0 <= cap, in unsigned compares (a negative value is a huge one)
+                const bool mal = ((uint32_t)s0 > (uint32_t)s1) | ((uint32_t)s1 > nnz) | ((uint32_t)s1 - (uint32_t)s0 > hots);
+                badv |= mal ? 1u : 0u;
+                st[i] = (uint32_t)s0;
+                ln[i] = mal ? 0u : (uint32_t)s1 - (uint32_t)s0;
+                bound = ln[i] > bound ? ln[i] : bound;
+            }
+        }
+    }
+    for (uint32_t j0 = 0; j0 < bound; j0 += WIN) {
         // the window's slots: -1 (empty) past the bag; an item past the batch reads past the resource: 0 (row 0; its store is dropped)
         int32_t sl[ITEMS][WIN];
 #pragma unroll
         for (int i = 0; i < ITEMS; i++) {
-            const unsigned ioff = (b0 + i) * irow + (first + j0) * 4u;
+            const unsigned ioff = CSR ? (st[i] + j0) * 4u : (b0 + i) * irow + (first + j0) * 4u;
+            const uint32_t fill = CSR ? ln[i] : hots;   // slots of this item's bag
             if constexpr (WIDE) {
 #pragma unroll
                 for (int q = 0; q < WIN / 4; q++) {
@@ -447,7 +484,7 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
 #pragma unroll
                 for (int j = 0; j < WIN; j++) {
                     sl[i][j] = -1;
-                    if (!is_dense && j0 + j < hots) sl[i][j] = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_idx, ioff + 4u * j, 0, 0);
+                    if (!is_dense && j0 + j < fill) sl[i][j] = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_idx, ioff + 4u * j, 0, 0);
                 }
             }
         }
@@ -488,7 +525,8 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
         if constexpr (WEIGHTED) asm volatile("" : "+v"(left));
         auto load_weights = [&](int u) {
             const int i = u / UPI, g = u % UPI;
-            const unsigned woff = (b0 + i) * irow + (first + j0) * 4u + 4u * G * g;
+            const unsigned woff = (CSR ? (st[i] + j0) * 4u : (b0 + i) * irow + (first + j0) * 4u) + 4u * G * g;
+            if constexpr (CSR) left = ln[i] > j0 ? ln[i] - j0 : 0u;   // this item's own bag (0 for a DENSE word)
             if constexpr (WIDE) {
                 u32x4_t w4 = {0u, 0u, 0u, 0u};
                 if (4u * g < left) w4 = __builtin_amdgcn_raw_buffer_load_b128(rs_wt, woff, 0, 0);
@@ -560,13 +598,29 @@ template <int ITEMS, int WIN, bool WIDE>
 __global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pooled_kernel(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, const FrGatherGroups groups,
                                                             int n_groups, const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
                                                             const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
-                                                            unsigned out_bytes, int any_mean) {
+                                                            unsigned out_bytes, int any_mean, const int32_t *__restrict__ offsets, int n_icols, unsigned nnz) {
     const int group = blockIdx.x & (n_groups - 1);
     const int w0 = groups.start[group];
     const int t = blockIdx.y * blockDim.x + threadIdx.x;
     if (t >= groups.start[group + 1] - w0) return;
     const unsigned b0 = (blockIdx.x / (unsigned)n_groups) * ITEMS;   // the workgroup's chunk of ITEMS items
-    if (weights) {
+    bool csr = false;   // uniform over the launch, like `weights` and `any_mean`; the 16-byte-index instantiations hold no offsets arm
+    if constexpr (!WIDE) csr = offsets != nullptr;
+    if (__builtin_expect(csr, false)) {   // (out of the padded arms' way)
+        // the offsets form (`pool` is then the context's second descriptor array: column and cap per word): two arms, the weighted fold and
+        // the counting fold (which is the SUM fold on a word without the MEAN bit), both in the half passes of the arms below
+        if constexpr (!WIDE) {
+            constexpr int HI = ITEMS >= 2 ? ITEMS / 2 : 1, HW = ITEMS >= 2 ? WIN : (WIN >= 8 ? WIN / 2 : WIN);
+            constexpr unsigned NH = ITEMS >= 2 ? 2u : 1u;
+            if (weights) {
+                for (unsigned h = 0; h < NH; h++)
+                    gather_pooled_body<HI, HW, false, true, false, true>(words, pool, w0 + t, b0 + h * HI, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz);
+            } else {
+                for (unsigned h = 0; h < NH; h++)
+                    gather_pooled_body<HI, HW, false, false, true, true>(words, pool, w0 + t, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz);
+            }
+        }
+    } else if (weights) {
         // the weighted fold keeps half as many row words in flight per pass (half the items, or half the window for one item), so that
         // its weights and products fit the registers the unweighted fold needs anyway: the kernel's register count, hence the unweighted
         // path's occupancy, is the unweighted fold's
@@ -594,11 +648,13 @@ __global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pool
 
 template <int ITEMS, int WIN, bool WIDE>
 static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, const float *weights, int pool_cols,
-                                const float *dense, void *out, int batch, int *err_flag, unsigned out_bytes, bool any_mean, hipStream_t s) {
+                                const float *dense, void *out, int batch, int *err_flag, unsigned out_bytes, bool any_mean, hipStream_t s,
+                                const int32_t *offsets, int n_icols, unsigned nnz) {
     const int n_chunks = (batch + ITEMS - 1) / ITEMS;
     const int bx = groups.max_words >= 256 ? 256 : ((groups.max_words + 63) / 64) * 64;
     dim3 grid(n_groups * n_chunks, (groups.max_words + bx - 1) / bx);
-    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, any_mean ? 1 : 0);
+    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, any_mean ? 1 : 0,
+                                                                   offsets, n_icols, nnz);
     KCHECK();
     fr_note_kernel("gather_pooled_kernel<%d, %d, %s>", ITEMS, WIN, WIDE ? "true" : "false");
     return FR_OK;
@@ -606,12 +662,18 @@ static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool,
 
 // idx = [batch][pool_cols] int32; weights = NULL or float [batch][pool_cols] (the weighted fold); out = fp32 records in the model's layout,
 // out_words 16-byte words per item.  max_hots picks the window; any_mean: a word of `pool` carries FR_POOL_DESC_MEAN.
+// The offsets form (offsets != NULL): offsets = int32 [batch * n_icols + 1], idx / weights = the nnz flat entries (NULL when nnz == 0), `pool` = the
+// context's offsets-form descriptors (column and cap per word); the narrow instantiation of the window always (4-byte alignment only).
 int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, const float *weights, int pool_cols,
-                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words) {
+                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
+                      const int32_t *offsets, int n_icols, long long nnz) {
     if (n_words <= 0 || batch <= 0) return FR_OK;
     if (out_words < n_words) out_words = n_words;
-    const size_t out_bytes = (size_t)batch * (size_t)out_words * 16, idx_bytes = (size_t)batch * (size_t)pool_cols * 4;
-    if (out_bytes >= ((size_t)4000 << 20) || idx_bytes >= ((size_t)4000 << 20))   // 32-bit resource offsets, with room for the chunk past the batch
+    const size_t out_bytes = (size_t)batch * (size_t)out_words * 16;
+    const size_t idx_bytes = offsets ? (size_t)nnz * 4 : (size_t)batch * (size_t)pool_cols * 4;
+    const size_t off_bytes = offsets ? ((size_t)batch * (size_t)n_icols + 1) * 4 : 0;
+    // 32-bit resource offsets, with room for the chunk past the batch (the offsets form's three sizes are refused by the C-ABI, for both back-ends, before it gets here)
+    if (out_bytes >= ((size_t)4000 << 20) || idx_bytes >= ((size_t)4000 << 20) || off_bytes >= ((size_t)4000 << 20))
         FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's index rows%s (%zu bytes) or records (%zu bytes) reach 4000 MiB", weights ? " / weights" : "", idx_bytes, out_bytes);
     FrGatherGroups groups = planned;
     int n_groups = 8;
@@ -621,7 +683,7 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
         for (int g = 1; g <= 8; g++) groups.start[g] = n_words;
         groups.max_words = n_words;
     }
-    wide = wide && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;   // 16-byte loads of both arrays
+    wide = wide && !offsets && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;   // 16-byte loads of both arrays
     // window x items per thread by the longest bag, from the sweep on the MI355X (profiles/pooled_gather_window_sweep.md: Model-C batch 4096, every
     // window x items pair at hots 1 .. 16): the longest window that a bag fills wins by 1-5 %, with as few items per thread as keep 16 row words
     // in flight; a one-slot window is 20 % slower than a two-slot one at hots = 1 and is not built.  FR_POOL_WIN / FR_POOL_ITEMS: experiments build only
@@ -632,8 +694,8 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
 #define FR_GP(I, W)                                                                                                                                     \
     if (items == I && win == W) {                                                                                                                       \
         if constexpr (W % 4 == 0)                                                                                                                       \
-            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s); \
-        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s);   \
+            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, nullptr, 0, 0u); \
+        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, offsets, n_icols, (unsigned)nnz);   \
     }
     FR_GP(4, 2)
     FR_GP(2, 2)

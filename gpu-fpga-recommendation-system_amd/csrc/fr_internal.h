@@ -237,7 +237,10 @@ struct fr_ctx {
     std::atomic<int> lp_image_on{1};       // fr_ctx_set_lp_bank_image (fleetrec_diag.h): 0 = the in-chain gather reads the fp32 rows and converts them itself
     // Pooled (multi-hot) lookups (fr_ctx_set_pooling): the descriptors made of the hots per index column, P = sum of hots (0: no pooling)
     std::vector<FrPoolDesc> h_pool;
-    FrPoolDesc *d_pool = nullptr;          // [n_words]
+    FrPoolDesc *d_pool = nullptr;          // [2 * n_words]: the padded form's descriptors, then the offsets form's (d_pool_csr)
+    // the offsets (CSR) form's descriptors: first = the word's index COLUMN, hots = the column's cap | FR_POOL_DESC_MEAN
+    std::vector<FrPoolDesc> h_pool_csr;
+    FrPoolDesc *d_pool_csr = nullptr;      // = d_pool + n_words
     int pool_cols = 0;                     // P
     int pool_max_hots = 0;
     bool pool_wide = false;                // every bag starts and ends on a multiple of 4 slots and P % 4 == 0: 16-byte index loads
@@ -293,6 +296,7 @@ struct fr_worker {
     int idx_cap = 0;             // int32 columns per item its pinned and device index buffers hold: max(index columns, pooled columns at creation)
     float *h_pool_w = nullptr;   // pinned [max_batch][pool_w_cap] per-sample weights of the host form (fr_worker_pool_weights_ptr); NULL without pooling at creation
     int pool_w_cap = 0;          // pooled columns at creation
+    int32_t *h_pool_off = nullptr;   // pinned [max_batch * index columns + 1] bag offsets of the offsets-form host call (fr_worker_pool_offsets_ptr); NULL without pooling at creation
     // CPU back-end: a call computes before it returns; an index-range error stays in c_err until fr_worker_sync reports it
     float *c_scratch = nullptr;  // [max_batch][H1 + H2 + H3]
     float *c_x = nullptr;        // records of the sharded FC entry points, [max_batch][K]
@@ -394,7 +398,7 @@ int frc_fill_table(float *base, int64_t row0, int64_t rows, int dim, int64_t row
 int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale);
 int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx_stride, const float *dense, float *out, int batch, int *err_flag);
 int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
-                      int *err_flag);
+                      int *err_flag, const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0);   // offsets != NULL: the offsets form, pool = fr_ctx::h_pool_csr
 // n listed rows of one table <- src [n][dim], into the host arena with table_copy's head / tail addressing, over the pool's threads; a listed
 // id outside [0, rows) writes nothing and -> 1 (else 0).  A row listed twice ends up as the LAST of its listed sources.
 int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src);
@@ -428,8 +432,10 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
                int transport, int e_x, hipStream_t s, int out_words, bool one_chunk = false);
 // pooled (multi-hot) gather: idx = [batch][pool_cols]; weights = NULL or float [batch][pool_cols] (the weighted fold); bag and mode of word w =
 // pool[w]; fp32 records in the model's layout.  max_hots / wide / any_mean: fr_ctx::pool_*
+// offsets != NULL: the offsets (CSR) form -- offsets = int32 [batch * n_icols + 1], idx / weights = nnz flat entries, pool = fr_ctx::d_pool_csr
 int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &groups, const int32_t *idx, const float *weights, int pool_cols,
-                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words);
+                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
+                      const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0);
 int frk_gather_tile(const FrPassDesc *passes, const FrChunkDesc *chunks, int n_chunks, const int32_t *idx, int idx_stride, const float *dense, void *out,
                     int out_stride_words, int batch, int *err_flag, bool dedup, unsigned long long *dup_counter, hipStream_t s);
 int frk_transpose_slices_lp(int precision, const void *gathered, int n_shards, int batch_total, int slice_padded, const int *h_offsets, const int *h_lens,

@@ -14,6 +14,9 @@
 //                        [--pool weighted]  (with --hots N, for fleetrec_server --hots N --pool weighted: every block's index rows are followed by
 //                                      float32 [B][columns x N] per-sample weights, 0.25 * (1 + (b + c + 2 j) % 4) for item b, column c, slot j;
 //                                      --pool sum | mean send what --hots alone sends: those folds are the server's business)
+//                        [--csr]  (with --hots N, for fleetrec_server --hots N --csr: the very bags --hots N [--ragged] sends, compacted into the offsets
+//                                      form -- a block is int32 offsets[B x columns + 1], int32 indices[nnz] (the non-empty slots, bag by bag), float32
+//                                      weights[nnz] with --pool weighted (the weights of those slots), then the dense rows)
 //                        [--pool N]   (uniform indices: N distinct blocks per connection are generated up front and sent in rotation --
 //                                      drawing 12 k random indices per block is slower than the server; default 32, 0 = draw every block)
 #include <arpa/inet.h>
@@ -46,7 +49,7 @@ int main(int argc, char **argv) {
     std::string host = "127.0.0.1", indices = "reference";
     bool per_item = false, per_bank = false, reply = false, ragged = false;
     int hots = 0;
-    bool weighted = false, pool_mode = false;
+    bool weighted = false, pool_mode = false, csr = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -70,10 +73,12 @@ int main(int argc, char **argv) {
         else if (a == "--window") window = atol(next());
         else if (a == "--hots") hots = atoi(next());
         else if (a == "--ragged") ragged = true;
+        else if (a == "--csr") csr = true;
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (hots < 0 || hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, hots); return 2; }
     if (ragged && hots <= 0) { fprintf(stderr, "--ragged needs --hots N\n"); return 2; }
+    if (csr && hots <= 0) { fprintf(stderr, "--csr needs --hots N\n"); return 2; }
     if (pool_mode && hots <= 0) { fprintf(stderr, "--pool sum|mean|weighted needs --hots N\n"); return 2; }
     const size_t slots = hots > 0 ? (size_t)hots : 1;   // int32 per index column of an item
     fr_model_desc *m = nullptr;
@@ -100,6 +105,8 @@ int main(int argc, char **argv) {
                 const size_t b = q / (cols * slots), c = q / slots % cols, j = q % slots;
                 wts[q] = 0.25f * (float)(1 + (b + c + 2 * j) % 4);
             }
+            std::vector<int32_t> c_off, c_ind;   // --csr: the block in the offsets form
+            std::vector<float> c_wt;
             std::vector<float> dense((size_t)batch * m->dense_len), scores(batch);
             std::mt19937_64 rng(1234 + t);
             int sock = socket(AF_INET, SOCK_STREAM, 0), one = 1;
@@ -170,8 +177,24 @@ int main(int argc, char **argv) {
                     t_send[(size_t)(n_sent.load(std::memory_order_relaxed) % window)] = std::chrono::steady_clock::now();
                 }
                 const auto t_req = std::chrono::steady_clock::now();
-                if (send(sock, bi, idx.size() * 4, MSG_NOSIGNAL) <= 0) break;
-                if (!wts.empty() && send(sock, wts.data(), wts.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                if (csr) {   // the block's bags without their empty slots: offsets, entries (, the entries' weights)
+                    c_off.clear(), c_ind.clear(), c_wt.clear();
+                    c_off.push_back(0);
+                    for (size_t bag = 0; bag < (size_t)batch * cols; bag++) {
+                        for (size_t j = 0; j < slots; j++)
+                            if (bi[bag * slots + j] != -1) {
+                                c_ind.push_back(bi[bag * slots + j]);
+                                if (weighted) c_wt.push_back(wts[bag * slots + j]);
+                            }
+                        c_off.push_back((int32_t)c_ind.size());
+                    }
+                    if (send(sock, c_off.data(), c_off.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                    if (!c_ind.empty() && send(sock, c_ind.data(), c_ind.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                    if (!c_wt.empty() && send(sock, c_wt.data(), c_wt.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                } else {
+                    if (send(sock, bi, idx.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                    if (!wts.empty() && send(sock, wts.data(), wts.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                }
                 if (!dense.empty() && send(sock, bd, dense.size() * 4, MSG_NOSIGNAL) <= 0) break;
                 sent[t]++;
                 n_sent.fetch_add(1, std::memory_order_release);

@@ -19,6 +19,10 @@
 //        [--pool sum|mean|weighted] (with --hots N; sum is the default): mean = every column FR_POOL_MEAN (fr_ctx_set_pooling_modes); weighted = the
 //                        block's index rows are followed by float32 [B][index columns x N] per-sample weights, read into fr_worker_pool_weights_ptr,
 //                        and every batch goes through fr_worker_submit_pooled_weighted (fleetrec_sender --hots N --pool weighted).
+//        [--csr] (with --hots N, any --pool): the blocks come in the offsets form -- int32 offsets[B x index columns + 1], then int32 indices[nnz]
+//                        with nnz taken from the last offset, then float32 weights[nnz] with --pool weighted, then the dense rows -- and every batch goes
+//                        through fr_worker_submit_pooled_csr; N is the cap of every column.  A block whose offsets[0] is not 0 or whose nnz is outside
+//                        [0, B x columns x N] ends the connection with an error status before anything more is read (fleetrec_sender --hots N --csr).
 //        [--update-port P]: sparse row updates of the tables while serving (fr_ctx_update_rows).  A second listening socket, served by one thread of its
 //                        own beside the serving threads.  One message = int32 table, int32 n, int32 ids[n], float32 rows[n x dim of that table],
 //                        little-endian: row i of `rows` becomes table row ids[i]; the answer is one int32 status (0, or the library's FR_ERR_* --
@@ -74,6 +78,7 @@ struct Options {
     long row_cap = 0;
     int hots = 0;          // --hots N: pooled lookups, N slots per index column (0: one-hot)
     int pool = -1;         // --pool: 0 sum, 1 mean, 2 weighted (-1: not given)
+    bool csr = false;      // --csr: blocks in the offsets form (with --hots)
     int update_port = 0;   // --update-port P: the row-update socket (0: none)
 };
 
@@ -437,14 +442,36 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 if (g_global_batch_count >= o.total) break;
                 g_global_batch_count++;
             }
-            if (!read_exact(sock, fr_worker_idx_ptr(wk), idx_bytes) || (weight_bytes && !read_exact(sock, fr_worker_pool_weights_ptr(wk), weight_bytes)) ||
-                (dense_bytes && !read_exact(sock, fr_worker_dense_ptr(wk), dense_bytes))) {
+            if (o.csr) {   // offsets first: they say how many entries follow; a block that lies about them is refused before its entries are read
+                const size_t n_off = (size_t)o.batch * (size_t)fr_model_index_cols(m) + 1;
+                int32_t *off = fr_worker_pool_offsets_ptr(wk);
+                if (!off || !read_exact(sock, off, n_off * sizeof(int32_t))) {
+                    t->status = -4;
+                    t->error = off ? "Receiving data UNSUCCESSFUL (peer closed before the batch was complete)" : "the worker has no offsets buffer";
+                    break;
+                }
+                const int64_t nnz = off[n_off - 1];
+                if (off[0] != 0 || nnz < 0 || nnz > (int64_t)o.batch * (int64_t)idx_cols) {
+                    t->status = -8;
+                    t->error = "malformed offsets-form block: offsets[0] = " + std::to_string(off[0]) + ", nnz = " + std::to_string(nnz) + " outside [0, " +
+                               std::to_string((int64_t)o.batch * (int64_t)idx_cols) + "]";
+                    break;
+                }
+                const size_t nz = (size_t)nnz * 4;
+                if ((nz && !read_exact(sock, fr_worker_idx_ptr(wk), nz)) || (nz && o.pool == 2 && !read_exact(sock, fr_worker_pool_weights_ptr(wk), nz)) ||
+                    (dense_bytes && !read_exact(sock, fr_worker_dense_ptr(wk), dense_bytes))) {
+                    t->status = -4;
+                    t->error = "Receiving data UNSUCCESSFUL (peer closed before the batch was complete)";
+                    break;
+                }
+            } else if (!read_exact(sock, fr_worker_idx_ptr(wk), idx_bytes) || (weight_bytes && !read_exact(sock, fr_worker_pool_weights_ptr(wk), weight_bytes)) ||
+                       (dense_bytes && !read_exact(sock, fr_worker_dense_ptr(wk), dense_bytes))) {
                 t->status = -4;
                 t->error = "Receiving data UNSUCCESSFUL (peer closed before the batch was complete)";
                 break;
             }
             const auto t_recv = std::chrono::steady_clock::now();  // network_time / cuda_time pair of cuda_server.c:429,462
-            if ((weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
+            if ((o.csr ? fr_worker_submit_pooled_csr(wk, o.batch, o.pool == 2) : weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
                 t->status = -5;
                 t->error = fr_last_error();
                 break;
@@ -499,6 +526,7 @@ int main(int argc, char **argv) {
         else if (a == "--small-block") o.small_block = atoi(next());
         else if (a == "--row-cap") o.row_cap = atol(next());
         else if (a == "--hots") o.hots = atoi(next());
+        else if (a == "--csr") o.csr = true;
         else if (a == "--update-port") o.update_port = atoi(next());
         else if (a == "--pool") {
             std::string v = next();
@@ -519,6 +547,7 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--hots (pooled lookups) serves the submit-and-sync path only: not with --stream or --shards (their producers are one-hot)\n");
         return 2;
     }
+    if (o.csr && o.hots <= 0) { fprintf(stderr, "--csr (offsets-form blocks) needs --hots N\n"); return 2; }
     if (o.pool >= 0 && o.hots <= 0) { fprintf(stderr, "--pool sum|mean|weighted needs --hots N\n"); return 2; }
     printf("HIP devices visible: %d\n", fr_device_count());  // device probe of cuda_server.c:508-522
     fr_model_desc *model = nullptr;
@@ -579,6 +608,7 @@ int main(int argc, char **argv) {
             }
         }
         printf("pooled lookups: %d slots on each of %zu index columns, %d int32 per item\n", o.hots, hots.size(), fr_ctx_pooled_index_cols(ctx));
+        if (o.csr) printf("offsets-form blocks: int32 offsets[batch x %zu + 1], indices[nnz]%s\n", hots.size(), o.pool == 2 ? ", float32 weights[nnz]" : "");
         if (o.pool > 0) printf("pooling: %s\n", o.pool == 1 ? "mean" : "weighted (float32 weights follow every block's index rows)");
     }
     if (o.stream && o.reply && !g_engine && fr_ctx_set_small_block(ctx, o.small_block) != FR_OK) {

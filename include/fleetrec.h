@@ -40,6 +40,8 @@ extern "C" {
  * default all-gather is the step as before.  Still 6, additive: multi-hot pooled lookups (fleetrec_serving.h: fr_ctx_set_pooling,
  * fr_ctx_pooled_index_cols, fr_worker_gather_pooled, fr_worker_submit_pooled_device, fr_worker_submit_pooled) -- every one-hot entry point is as before.
  * Still 6, additive: pooling modes (SUM / MEAN) and per-sample weights of those lookups (fleetrec_serving.h: fr_ctx_set_pooling_modes, fr_worker_*_pooled_weighted*).
+ * Still 6, additive: the offsets (CSR) input form of the pooled lookups (fleetrec_serving.h: fr_worker_gather_pooled_csr, fr_worker_submit_pooled_csr_device,
+ * fr_worker_pool_offsets_ptr, fr_worker_submit_pooled_csr) -- the padded entry points are as before.
  * Still 6, additive: stream-ordered sparse row updates of the tables (fleetrec_serving.h: fr_worker_update_rows, fr_ctx_update_rows; fleetrec_diag.h:
  * fr_ctx_lp_bank_image_builds) -- fr_ctx_upload_table and every lookup are as before.
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile

@@ -130,6 +130,35 @@ int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, const int32
 float *fr_worker_pool_weights_ptr(fr_worker *w);
 int fr_worker_submit_pooled_weighted(fr_worker *w, int batch);
 
+/* Offsets-form (CSR) pooled lookups (additive in ABI 6): a second INPUT form of the pooled lookups above -- what a caller holding
+ * `indices + offsets` (EmbeddingBag(offsets=...), a table-batched embedding) has.  Pooling is configured as above (fr_ctx_set_pooling, optionally
+ * fr_ctx_set_pooling_modes); here hots[c] is the CAP of column c: the longest bag the column may carry.  C = fr_model_index_cols(model).  A context
+ * may use the padded and the offsets entry points side by side.
+ *   offsets  int32 [batch * C + 1], item-major, column-minor: bag (b, c) is indices[offsets[b * C + c] .. offsets[b * C + c + 1])
+ *   indices  int32 [nnz];  weights (optional) float [nnz], parallel to indices.  Only 4-byte alignment of the three arrays is assumed.
+ * An entry of -1 is an empty slot, as in the padded form.  Every TABLE and COPY word is the fold defined above over the bag's entries in
+ * ascending position: SUM, MEAN over the non-empty entries, or (weights != NULL) the weighted sum with each product rounded on its own; an empty
+ * bag (start == end, or only -1s) gives +0.0f; DENSE words are copied.  The records equal, BIT FOR BIT, those of the padded entry points on the same
+ * context for the same bags padded with -1 up to hots[c] (weights padded with anything).
+ * A bag is MALFORMED when start < 0, end < start, end > nnz, end - start > hots[c], or an entry is < -1 or >= the row count the one-hot gather
+ * checks: FR_ERR_INDEX_RANGE at fr_worker_sync (sticky word, the worker is usable afterwards).  The malformed bag's own record words are
+ * unspecified, every other bag's are as specified, and no byte outside offsets[0 .. batch * C], indices[0 .. nnz), weights[0 .. nnz), the tables
+ * and the record buffer is read or written.
+ * nnz == 0 is legal (indices / weights may then be NULL).  FR_ERR_INVALID: nnz < 0, offsets == NULL, indices == NULL with nnz > 0, or
+ * (batch * C + 1) * 4, nnz * 4 or the record bytes reaching 4000 MiB (32-bit buffer offsets).  FR_ERR_STATE: weights on a context with a MEAN
+ * column, no pooling set, a sharded context -- the rules of the padded calls.  weights == NULL means unweighted: one entry point per shape. */
+int fr_worker_gather_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz,
+                                const float *d_weights /* NULL: unweighted */, const float *d_dense, float *d_records);
+int fr_worker_submit_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz,
+                                       const float *d_weights, const float *d_dense, float *d_scores);
+/* Host form: offsets in fr_worker_pool_offsets_ptr -- pinned int32 [max_batch * C + 1] (host memory on the CPU back-end), NULL on a worker created
+ * before fr_ctx_set_pooling, where the host form returns FR_ERR_STATE; indices flat in fr_worker_idx_ptr (its max_batch x max(index cols, P) ints
+ * always hold nnz <= batch x P), weights flat in fr_worker_pool_weights_ptr (read when weighted != 0).  nnz = offsets[batch * C], read on the host:
+ * offsets[0] != 0 or nnz outside [0, batch x P] is FR_ERR_INVALID before anything is enqueued; the per-bag checks remain the gather's.  Order
+ * against fr_worker_update_rows is that of the padded pooled calls. */
+int32_t *fr_worker_pool_offsets_ptr(fr_worker *w);
+int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted);
+
 /* Sparse row updates of the embedding tables (additive in ABI 6): the write side of the lookups.  n listed rows of ONE table: row_ids int32 [n],
  * rows float [n][dim], dense -- row i of `rows` is the new content of table row row_ids[i].  Unlike fr_ctx_upload_table these are not set-up
  * calls: they run beside streams in flight, leave an operand-type bank image current (its listed rows are converted again in place, from the

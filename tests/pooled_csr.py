@@ -1,0 +1,631 @@
+"""Shared by tests/test_cpu_pooled_csr.py and tests/test_gpu_pooled_csr.py: the offsets (CSR) input form of the pooled lookups
+(include/fleetrec_serving.h: fr_worker_gather_pooled_csr, fr_worker_submit_pooled_csr_device, fr_worker_submit_pooled_csr), checked once for
+both back-ends (device = -1: the CPU back-end).
+
+The form changes how a bag is FOUND, not what is folded: bag (b, c) = indices[offsets[b * C + c] : offsets[b * C + c + 1]].  So every check has
+three sides that must agree bit for bit: (a) the contract folded in numpy on the padded rectangle of the same bags (pooled_helpers /
+pooled_modes), (b) the padded entry point on the same context, (c) the offsets form.  All inputs are finite (N(0, 3) tables with a subnormal
+and a -0.0; weights in (0.5, 1.5) plus +-0 and a denormal), no expected word is a NaN: every word of every case is compared, into guarded
+destinations, with np.array_equal.  No tolerance anywhere."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import gather_matrix as GM
+import pooled_helpers as P
+import pooled_modes as PM
+
+CPU = -1
+SUM, MEAN = 0, 1
+KINDS = ("sum", "mean", "weighted")
+NARROW = [k for k in GM.POOLED_HOTS if k.endswith("false>")]   # the five narrow instantiations: <4,2> <2,2> <2,4> <2,8> <1,16>
+
+
+def _case(kernel, model, mode, batches=GM.POOLED_BATCHES):
+    k = kernel[len("gather_pooled_kernel<"):-1].replace(", ", "-")
+    return dict(id="csr-%s-%s-%s" % (k, model, mode), kernel=kernel, model=model, mode=mode, batches=tuple(batches), hots=GM.POOLED_HOTS[kernel])
+
+
+# one case per narrow instantiation on the record with a plan (8 XCD groups) and on the mixed-width model (one group), index modes spread as
+# gather_matrix.POOLED_CASES spreads them; once without a plan on a record wider than a workgroup (blockIdx.y > 0)
+CASES = ([_case(k, "wide", ("table", "bank")[i % 2]) for i, k in enumerate(NARROW)]
+         + [_case(k, "mixed", ("table", "bank", "item", "bank", "table")[i]) for i, k in enumerate(NARROW)]
+         + [_case("gather_pooled_kernel<2, 8, false>", "noplan", "table", (3, 131))])
+CASE_IDS = [c["id"] for c in CASES]
+# every cap a multiple of 4: the padded form takes the 16-byte kernel there, the offsets form still the narrow one
+CASE_CAPS4 = dict(id="csr-caps4-wide-table", kernel="gather_pooled_kernel<2, 8, false>", model="wide", mode="table", batches=(3, 37), hots=(4, 8, 12))
+
+
+def window_of(hots):
+    mx = int(max(hots))
+    return 16 if mx >= 16 else 8 if mx >= 8 else 4 if mx >= 4 else 2
+
+
+def finite_tables(model, rng):
+    tables = []
+    for t in model.tables():
+        a = (3.0 * rng.standard_normal((int(t.rows), t.dim))).astype(np.float32)
+        u = a.view(np.uint32)
+        u[0, 0], u[-1, -1], u[min(6, int(t.rows) - 1), 1] = 0x00000007, 0x80000000, 0x807FFFFF
+        tables.append(a)
+    return tables
+
+
+def bag_lengths(rng, caps, B):
+    """int [B][C]: per (item, column) one of {0, 1, WIN - 1, WIN, WIN + 1, cap - 1, cap} within [0, cap]; item 4 all empty, item 5 all at the
+    cap, items 6 / 7 and 8 / 9 (neighbours of one thread's chunk) 0 and cap, cap and 0; the last column's bag of items 0, 1, 2 and of the last
+    item is full, so that every batch of the case ends its last bag exactly at nnz with something in it."""
+    win = window_of(caps)
+    L = np.zeros((B, len(caps)), np.int64)
+    for c, cap in enumerate(caps):
+        pick = sorted({v for v in (0, 1, win - 1, win, win + 1, int(cap) - 1, int(cap)) if 0 <= v <= int(cap)})
+        L[:, c] = rng.choice(pick, size=B)
+    for b, v in ((4, 0), (5, None), (6, 0), (7, None), (8, None), (9, 0)):
+        if b < B:
+            L[b] = np.asarray(caps) if v is None else v
+    for b in (0, 1, 2, B - 1):
+        if 0 <= b < B:
+            L[b, -1] = caps[-1]
+    return L
+
+
+def padded_bags(rng, ranges, caps, L, holes):
+    """int32 [B][sum(caps)]: bag (b, c) holds L[b][c] uniform rows in its first slots, -1 behind them; holes: a fifth of the filled slots -1 too."""
+    B = L.shape[0]
+    pre = P.prefix_of(caps)
+    idx = np.full((B, int(np.sum(caps))), -1, np.int32)
+    for c, cap in enumerate(caps):
+        bag = (rng.random((B, int(cap))) * ranges[c]).astype(np.int32)
+        if holes:
+            bag[rng.random(bag.shape) < 0.2] = -1
+        bag[np.arange(int(cap))[None, :] >= L[:, c][:, None]] = -1
+        idx[:, pre[c]:pre[c] + int(cap)] = bag
+    return idx
+
+
+def csr_weights(rng, shape):
+    """Weights in (0.5, 1.5), with +0.0, -0.0 and a denormal sprinkled in: every product and sum stays finite."""
+    w = rng.uniform(0.5, 1.5, shape).astype(np.float32)
+    kind = rng.random(shape)
+    w[kind < 0.03] = 0.0
+    w[(kind >= 0.03) & (kind < 0.06)] = -0.0
+    w.view(np.uint32)[(kind >= 0.06) & (kind < 0.09)] = 0x00012345
+    return w
+
+
+@functools.lru_cache(maxsize=2)
+def _inputs(fr, case_id):
+    case = CASE_CAPS4 if case_id == CASE_CAPS4["id"] else next(c for c in CASES if c["id"] == case_id)
+    m = GM.make_model(fr, case["model"], case["mode"])
+    rng = np.random.default_rng(GM.case_seed(case))
+    B = max(case["batches"])
+    tables = finite_tables(m, rng)
+    ranges = m.index_ranges()
+    caps = GM.pooled_hots(case, len(ranges))
+    L = bag_lengths(rng, caps, B)
+    rect = padded_bags(rng, ranges, caps, L, holes=False)     # offsets form: exactly the drawn lengths
+    rect_h = padded_bags(rng, ranges, caps, L, holes=True)    # ... and with -1 entries kept inside the bags (every bag then as long as its cap)
+    dense = (3.0 * rng.standard_normal((B, m.dense_len))).astype(np.float32) if m.dense_len else None
+    weights = csr_weights(rng, rect.shape)
+    onehot = lambda one: GM.expected_records(m, tables, one, dense)
+    want = {}
+    for name, r in (("plain", rect), ("holes", rect_h)):
+        s = GM.pooled_expected(fr, m, tables, caps, r, dense)
+        modes = (np.arange(len(caps)) % 2 == 0).astype(np.int32)
+        want[name] = {"sum": s, "mean": PM.expected_modes(fr, m, caps, modes, r, dense, onehot, sum_records=s),
+                      "weighted": PM.expected_weighted(fr, m, caps, r, weights, dense, onehot)}
+        assert not any(PM.is_nan_bits(v).any() for v in want[name].values())
+    return case, tables, caps, L, {"plain": rect, "holes": rect_h}, dense, weights, want
+
+
+def inputs(fr, case_id):
+    """The case's model, tables, caps, drawn lengths, the two padded rectangles, dense features, weights and the numpy expectations per fold
+    kind: computed once per case, shared by its tests, never modified."""
+    case, tables, caps, L, rects, dense, weights, want = _inputs(fr, case_id)
+    return case, GM.make_model(fr, case["model"], case["mode"]), tables, caps, L, rects, dense, weights, want
+
+
+class Csr:
+    """offsets / indices / weights on the device, each `shift` bytes past a 16-byte boundary (only 4-byte alignment may be assumed)."""
+
+    def __init__(self, fr, ctx, offsets, indices, weights=None, shifts=(0, 0, 0)):
+        self.nnz = int(np.asarray(indices).size)
+        self.raw = []
+        self.off = self._put(fr, ctx, np.asarray(offsets, np.int32), shifts[0])
+        self.ind = self._put(fr, ctx, np.asarray(indices, np.int32), shifts[1]) if self.nnz else None
+        self.w = self._put(fr, ctx, np.asarray(weights, np.float32) if self.nnz else np.zeros(1, np.float32), shifts[2]) if weights is not None else None
+
+    def _put(self, fr, ctx, arr, shift):
+        # the allocation ends right behind the array (rounded to 4 bytes by construction): nothing to spare behind the last entry
+        flat = np.ascontiguousarray(arr)
+        raw = fr.DeviceBuffer(ctx, 16 + shift + flat.nbytes)
+        base = (raw.ptr.value + 15) // 16 * 16 + shift
+        assert base + flat.nbytes <= raw.ptr.value + raw.nbytes
+        fr._check(fr.lib().fr_memcpy_h2d(ctx._h, ctypes.c_void_p(base), flat.ctypes.data_as(ctypes.c_void_p), flat.nbytes))
+        self.raw.append(raw)
+        return base
+
+    def free(self):
+        for r in self.raw:
+            r.free()
+
+
+def _setup(fr, device, m, tables, caps, kind, B):
+    ctx = fr.Context(m, device=device)
+    for t, a in enumerate(tables):
+        ctx.upload_table(t, a)
+    ctx.set_pooling(caps, modes=(np.arange(len(caps)) % 2 == 0).astype(np.int32) if kind == "mean" else None)
+    return ctx, fr.Worker(ctx, B)
+
+
+def run_case(fr, device, case_id, kind, shifts=((0, 0, 0),), batches=None):
+    """One case x one fold kind: every batch of the case through (b) the padded entry point and (c) the offsets form, without and with -1
+    entries kept inside the bags, into guarded destinations, against (a) the numpy fold.  On the GPU the offsets form's kernel is the
+    narrow instantiation of the window.  shifts: byte offsets past a 16-byte boundary of (offsets, indices, weights)."""
+    case, m, tables, caps, L, rects, dense, weights, want = inputs(fr, case_id)
+    K = m.record_len
+    batches = batches or case["batches"]
+    ctx, wk = _setup(fr, device, m, tables, caps, kind, max(batches))
+    narrow = GM.pooled_kernel_for(caps, aligned=False)
+    assert narrow == case["kernel"], (narrow, case["kernel"])
+    try:
+        d_dense = fr.DeviceBuffer.from_numpy(ctx, dense) if dense is not None else None
+        for B in batches:
+            for name, keep in (("plain", False), ("holes", True)):
+                rect, w = rects[name][:B], (weights[:B] if kind == "weighted" else None)
+                exp = want[name][kind][:B]
+                off, ind, wf = fr.bags_to_csr(rect, caps, weights=w, keep_empty=keep)
+                assert off[0] == 0 and off[-1] == ind.size and off.size == B * len(caps) + 1
+                if not keep:
+                    assert np.array_equal(np.diff(off.astype(np.int64)).reshape(B, -1), L[:B]) and (ind != -1).all()
+                else:
+                    assert (ind == -1).any() or int(max(caps)) == 1
+                dst = GM.Guarded(fr, ctx, B, K * 4)
+                # (b) the padded entry point on the same context
+                ri, pi = PM._device_rows(fr, ctx, rect)
+                rw, pw = PM._device_rows(fr, ctx, w) if w is not None else (None, None)
+                wk.gather_pooled(B, pi, d_dense, dst.ptr, weights=pw)
+                wk.sync()
+                dst.check(lambda b0, n: exp[b0:b0 + n], K * 4)
+                ri.free()
+                if rw is not None:
+                    rw.free()
+                # (c) the offsets form
+                for sh in shifts:
+                    dst.fill()
+                    c = Csr(fr, ctx, off, ind, wf, sh)
+                    try:
+                        wk.gather_pooled_csr(B, c.off, c.ind, c.nnz, d_dense, dst.ptr, weights=c.w)
+                        kname = wk.last_kernel()
+                        wk.sync()
+                    finally:
+                        c.free()
+                    if device != CPU:
+                        assert kname == narrow, (kname, narrow)
+                    dst.check(lambda b0, n: exp[b0:b0 + n], K * 4)
+                dst.free()
+        wk.close()
+    finally:
+        ctx.close()
+
+
+def check_cap1_is_gather_only(fr, device, kind, mode, B=70):
+    """Every cap 1, every bag of length 1: the records are fr_worker_gather_only's bit for bit, in all three fill modes and all three folds
+    (weights 1.0f: a product by one is the word itself for every finite word)."""
+    m = P.make_model(fr, kind, index_mode=mode, max_rows=3000)
+    ctx = fr.Context(m, device=device)
+    try:
+        rng = np.random.default_rng(211)
+        for fill in (fr.FILL_HASH, fr.FILL_EVEN_ODD, fr.FILL_TAGGED):
+            ctx.fill_tables(fill, P.SEED_TABLES)
+            ctx.set_pooling(None)
+            wk = fr.Worker(ctx, B)
+            idx = (rng.random((B, m.idx_cols)) * m.index_ranges()[None, :]).astype(np.int32)
+            dense = P.dense_for(rng, m, B)
+            want = wk.gather_records(idx, dense)
+            off = np.arange(B * m.idx_cols + 1, dtype=np.int32)
+            for modes, w in ((None, None), (np.full(m.idx_cols, MEAN, np.int32), None), (None, np.ones(idx.size, np.float32))):
+                ctx.set_pooling(np.ones(m.idx_cols, np.int32), modes=modes)
+                assert np.array_equal(wk.gather_pooled_csr_records(off, idx.ravel(), dense, weights=w), want)
+            wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- malformed bags ------------------------------------------------------------------------------------------------------------------------
+
+MALFORMED = ("too_long", "end_past_nnz", "decreasing", "negative_start", "row_count", "minus_two")
+
+
+def check_malformed(fr, device, what, place, kind="sum", case_id=None, B=None):
+    """One malformed bag of class `what` in item 0 (place = "first") or in the last item of a batch that is no multiple of any chunk (place =
+    "last"): FR_ERR_INDEX_RANGE at sync, the guard words intact, every word outside the malformed bag's column of that item as expected, and a
+    clean batch right after with the expected bits.  An offset is shared by two neighbouring bags, so a tampered offset makes TWO bags
+    malformed or misread (the one it ends and the one it starts): both are left out of the comparison, every other bag is compared."""
+    case_id = case_id or ("csr-2-4-false-wide-table" if kind != "weighted" else "csr-1-16-false-mixed-table")
+    case, m, tables, caps, L, rects, dense, weights, want = inputs(fr, case_id)
+    B = B or (37 if case["model"] == "wide" else 3)   # 37: no multiple of 2 or 4 items per thread, nor of their half passes
+    C = len(caps)
+    K = m.record_len
+    ranges = m.index_ranges()
+    rect, exp = rects["plain"][:B], want["plain"][kind][:B]
+    w = weights[:B] if kind == "weighted" else None
+    off, ind, wf = fr.bags_to_csr(rect, caps, weights=w)
+    off = off.astype(np.int64)
+    item = 0 if place == "first" else B - 1
+    lens = np.diff(off).reshape(B, C)
+    nnz = None
+    if what == "too_long":        # a bag of cap + 1 valid entries: one entry (and weight) inserted behind the bag's last
+        c = 0 if place == "first" else C - 1
+        k = item * C + c
+        fill = int(caps[c]) + 1 - int(lens[item, c])
+        ind = np.insert(ind, int(off[k + 1]), np.zeros(fill, np.int32))
+        wf = None if wf is None else np.insert(wf, int(off[k + 1]), np.ones(fill, np.float32))
+        off[k + 1:] += fill
+        skip = [(item, c)]
+    elif what == "end_past_nnz":
+        if place == "last":       # the very last offset says one entry more than there are: only the last bag is touched (made shorter than its cap first)
+            k = B * C - 1
+            drop = min(max(2 - (int(caps[-1]) - int(lens[item, C - 1])), 0), int(lens[item, C - 1]))
+            if drop:
+                ind, wf = ind[:-drop], (None if wf is None else wf[:-drop])
+            nnz = int(ind.size)
+            off[-1] = nnz + 1
+            skip = [(item, C - 1)]
+        else:                     # bag (0, 0) ends past nnz; bag (0, 1) then starts there and ends before it starts
+            off[1] = ind.size + 5
+            skip = [(0, 0), (0, 1)]
+    elif what == "decreasing":    # bag k ends before it starts; bag k + 1 starts one entry early (misread, or longer than its cap)
+        c = next(c for c in range(C - 1) if off[item * C + c] >= 1) if place == "first" else C - 2
+        k = item * C + c
+        off[k + 1] = off[k] - 1
+        skip = [(item, c), (item, c + 1)]
+    elif what == "negative_start":
+        if place == "first":
+            off[0] = -1
+            skip = [(0, 0)]
+        else:                     # bag k - 1 ends at -1 (before its start), bag k starts at -1
+            k = item * C + C - 1
+            off[k] = -1
+            skip = [(item, C - 2), (item, C - 1)]
+    else:
+        c = next(c for c in (range(C) if place == "first" else range(C - 1, -1, -1)) if lens[item, c] > 0)
+        k = item * C + c
+        ind = ind.copy()
+        ind[int(off[k + 1]) - 1] = int(ranges[c]) if what == "row_count" else -2
+        skip = [(item, c)]
+    col_of = P.column_of_float(fr, m)
+    mask = np.zeros((B, K * 4), bool)
+    for b, c in skip:
+        mask[b] |= np.repeat(col_of == c, 4)
+    assert 0 < mask.sum() < mask[item].size
+    ctx, wk = _setup(fr, device, m, tables, caps, kind, B)
+    try:
+        d_dense = fr.DeviceBuffer.from_numpy(ctx, dense[:B]) if dense is not None else None
+        dst = GM.Guarded(fr, ctx, B, K * 4)
+        bad = Csr(fr, ctx, off.astype(np.int32), ind, wf, (4, 8, 12))
+        if nnz is not None:
+            bad.nnz = nnz
+        good_off, good_ind, good_w = fr.bags_to_csr(rect, caps, weights=w)
+        good = Csr(fr, ctx, good_off, good_ind, good_w)
+        with pytest.raises(fr.FleetRecError) as e:
+            wk.gather_pooled_csr(B, bad.off, bad.ind, bad.nnz, d_dense, dst.ptr, weights=bad.w)
+            wk.sync()
+        assert e.value.status == fr.FR_ERR_INDEX_RANGE, e.value
+        dst.check(lambda b0, n: exp[b0:b0 + n], K * 4, skip=mask)
+        dst.fill()
+        wk.gather_pooled_csr(B, good.off, good.ind, good.nnz, d_dense, dst.ptr, weights=good.w)   # the flag does not stick
+        wk.sync()
+        dst.check(lambda b0, n: exp[b0:b0 + n], K * 4)
+        bad.free()
+        good.free()
+        dst.free()
+        wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- arguments and state -------------------------------------------------------------------------------------------------------------------
+
+def check_errors(fr, device, kind, mode):
+    m = P.make_model(fr, kind, index_mode=mode, max_rows=2000)
+    ctx = fr.Context(m, device=device)
+    L = fr.lib()
+    C = m.idx_cols
+    B = 16
+    try:
+        ctx.fill_tables(fr.FILL_HASH, 1)
+        ctx.fill_weights(fr.WEIGHTS_UNIFORM, 2)
+        rng = np.random.default_rng(223)
+        caps = np.full(C, 2, np.int32)
+        rect = P.random_bags(rng, m.index_ranges(), caps, B, empty_share=0.3)
+        dense = P.dense_for(rng, m, B)
+        w = csr_weights(rng, rect.shape)
+        off, ind, wf = fr.bags_to_csr(rect, caps, weights=w)
+        d_d = fr.DeviceBuffer.from_numpy(ctx, dense) if dense is not None else None
+        d_r = fr.DeviceBuffer(ctx, B * m.record_len * 4)
+        d_s = fr.DeviceBuffer(ctx, B * 4)
+        c = Csr(fr, ctx, off, ind, wf)
+        vp = lambda b: b.ptr if b is not None else None
+        gather = lambda wkr, o, i, n, ww: L.fr_worker_gather_pooled_csr(wkr._h, B, o, i, n, ww, vp(d_d), vp(d_r))
+        submit = lambda wkr, o, i, n, ww: L.fr_worker_submit_pooled_csr_device(wkr._h, B, o, i, n, ww, vp(d_d), vp(d_s))
+        # no pooling set: every entry point refuses; a worker from before set_pooling has no offsets buffer
+        wk_old = fr.Worker(ctx, B)
+        assert wk_old.pool_offsets is None and not L.fr_worker_pool_offsets_ptr(wk_old._h)
+        for call in (gather, submit):
+            assert call(wk_old, c.off, c.ind, c.nnz, None) == fr.FR_ERR_STATE
+        assert L.fr_worker_submit_pooled_csr(wk_old._h, B, 0) == fr.FR_ERR_STATE
+        ctx.set_pooling(caps)
+        assert L.fr_worker_submit_pooled_csr(wk_old._h, B, 0) == fr.FR_ERR_STATE       # ... and still has none
+        assert L.fr_worker_submit_pooled_csr(wk_old._h, B, 1) == fr.FR_ERR_STATE
+        with pytest.raises(fr.FleetRecError) as e:
+            wk_old.infer_pooled_csr(off, ind, dense)
+        assert e.value.status == fr.FR_ERR_STATE
+        wk = fr.Worker(ctx, B)
+        assert wk.pool_offsets.shape == (B * C + 1,)
+        for call in (gather, submit):
+            assert call(wk, c.off, c.ind, -1, None) == fr.FR_ERR_INVALID                # nnz < 0
+            assert call(wk, None, c.ind, c.nnz, None) == fr.FR_ERR_INVALID              # no offsets
+            assert call(wk, c.off, None, c.nnz, None) == fr.FR_ERR_INVALID              # no indices with nnz > 0
+            assert call(wk, c.off, c.ind, 1000 << 20, None) == fr.FR_ERR_INVALID        # nnz * 4 reaches 4000 MiB (nothing is launched)
+            assert call(wk, c.off, c.ind, c.nnz, c.w) == fr.FR_OK                       # weights: legal on an all-SUM context
+            wk.sync()
+        assert L.fr_worker_gather_pooled_csr(wk._h, B, c.off, c.ind, c.nnz, None, vp(d_d), None) == fr.FR_ERR_INVALID
+        assert L.fr_worker_submit_pooled_csr_device(wk._h, B, c.off, c.ind, c.nnz, None, vp(d_d), None) == fr.FR_ERR_INVALID
+        # nnz == 0 is legal with NULL indices and weights: every bag empty, every table word +0.0f
+        zero = Csr(fr, ctx, np.zeros(B * C + 1, np.int32), np.zeros(0, np.int32))
+        for ww in (None, c.w):
+            assert L.fr_worker_gather_pooled_csr(wk._h, B, zero.off, None, 0, ww, vp(d_d), vp(d_r)) == fr.FR_OK
+            wk.sync()
+            got = d_r.download(np.uint32, B * m.record_len)
+            empty = wk.gather_pooled_records(np.full(rect.shape, -1, np.int32), dense)
+            assert np.array_equal(got, empty)
+        assert np.array_equal(wk.gather_pooled_csr_records(np.zeros(B * C + 1, np.int32), np.zeros(0, np.int32), dense), empty)
+        # weights on a context with a MEAN column
+        one_mean = np.zeros(C, np.int32)
+        one_mean[C - 1] = MEAN
+        ctx.set_pooling_modes(one_mean)
+        for call in (gather, submit):
+            assert call(wk, c.off, c.ind, c.nnz, c.w) == fr.FR_ERR_STATE
+            assert call(wk, c.off, c.ind, c.nnz, None) == fr.FR_OK
+            wk.sync()
+        wk.pool_offsets[:off.size] = off
+        assert L.fr_worker_submit_pooled_csr(wk._h, B, 1) == fr.FR_ERR_STATE
+        ctx.set_pooling_modes(None)
+        # the host form: offsets[0] != 0, nnz > batch x P, nnz < 0 -- FR_ERR_INVALID with nothing enqueued, the worker usable right away
+        good = wk.infer_pooled_csr(off, ind, dense)
+        assert np.array_equal(good, wk.infer_pooled(rect, dense))
+        for pos, val in ((0, 1), (B * C, B * int(caps.sum()) + 1), (B * C, -1)):
+            wk.pool_offsets[:off.size] = off
+            wk.pool_offsets[pos] = val
+            assert L.fr_worker_submit_pooled_csr(wk._h, B, 0) == fr.FR_ERR_INVALID
+            assert L.fr_worker_sync(wk._h) == fr.FR_OK
+            assert np.array_equal(wk.infer_pooled_csr(off, ind, dense), good)
+        # the binding refuses weights that are not parallel to the indices, and offsets that are no batch x C + 1
+        with pytest.raises(fr.FleetRecError) as e:
+            wk.gather_pooled_csr_records(off, ind, dense, weights=wf[:-1])
+        assert e.value.status == fr.FR_ERR_INVALID
+        with pytest.raises(fr.FleetRecError) as e:
+            wk.gather_pooled_csr_records(off[:-1], ind, dense)
+        assert e.value.status == fr.FR_ERR_INVALID
+        c.free()
+        zero.free()
+        wk.close()
+        wk_old.close()
+    finally:
+        ctx.close()
+
+
+def check_sharded_refuses(fr, device):
+    m = fr.Model.builtin(fr.MODEL_C).clone(max_rows=500)
+    ctx = fr.Context(m, device=device, shard_rank=1, n_shards=3)
+    try:
+        ctx.fill_tables(fr.FILL_HASH, 1)
+        ctx.fill_weights(fr.WEIGHTS_UNIFORM, 2)
+        wk = fr.Worker(ctx, 4)
+        off = np.zeros(4 * m.idx_cols + 1, np.int32)
+        with pytest.raises(fr.FleetRecError) as e:
+            wk.gather_pooled_csr(4, off.ctypes.data, None, 0, None, off.ctypes.data)
+        assert e.value.status == fr.FR_ERR_STATE
+        assert fr.lib().fr_worker_submit_pooled_csr(wk._h, 4, 0) == fr.FR_ERR_STATE
+        wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- scores --------------------------------------------------------------------------------------------------------------------------------
+
+def check_scores(fr, device, kind, precision=None, B=48):
+    """submit_pooled_csr_device and the host form against the padded submit on the same context: the same records into the same chain, so the
+    scores are equal bit for bit, for SUM, weighted and MEAN, in whatever precision the chain has."""
+    m = P.make_model(fr, kind, max_rows=3000)
+    ctx = fr.Context(m, device=device)
+    try:
+        ctx.fill_tables(fr.FILL_HASH, P.SEED_TABLES)
+        ctx.fill_weights(fr.WEIGHTS_UNIFORM, P.SEED_WEIGHTS)
+        if precision is not None:
+            ctx.set_fc_precision(precision)
+        rng = np.random.default_rng(227)
+        caps = P.spread_hots(m.idx_cols)
+        rect = P.random_bags(rng, m.index_ranges(), caps, B, empty_share=0.2, empty_bags=5)
+        dense = P.dense_for(rng, m, B)
+        w = csr_weights(rng, rect.shape)
+        ctx.set_pooling(caps)
+        wk = fr.Worker(ctx, B)
+        if precision == fr.FC_FP8:   # activation exponents from a one-hot batch of the same tables
+            wk.calibrate_fp8((rng.random((B, m.idx_cols)) * m.index_ranges()[None, :]).astype(np.int32), dense)
+        d_d = fr.DeviceBuffer.from_numpy(ctx, dense) if dense is not None else None
+        d_s = fr.DeviceBuffer(ctx, B * 4)
+        seen = []
+        for modes, ww in ((None, None), (None, w), ((np.arange(len(caps)) % 2 == 0).astype(np.int32), None)):
+            ctx.set_pooling_modes(modes)
+            ref = wk.infer_pooled(rect, dense, weights=ww)
+            assert np.isfinite(ref).all() and len(set(ref.tolist())) > 1
+            seen.append(ref)
+            assert np.array_equal(wk.gather_pooled_csr_records(*fr.bags_to_csr(rect, caps)[:2], dense, weights=fr.bags_to_csr(rect, caps, ww)[2]),
+                                  wk.gather_pooled_records(rect, dense, weights=ww))
+            for keep in (False, True):
+                off, ind, wf = fr.bags_to_csr(rect, caps, weights=ww, keep_empty=keep)
+                assert np.array_equal(wk.infer_pooled_csr(off, ind, dense, weights=wf), ref)
+                c = Csr(fr, ctx, off, ind, wf, (12, 4, 8))
+                wk.submit_pooled_csr_device(B, c.off, c.ind, c.nnz, d_d, d_s, weights=c.w)
+                wk.sync()
+                c.free()
+                assert np.array_equal(d_s.download(np.float32, B), ref)
+        assert not np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[0], seen[2])
+        wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- order against fr_worker_update_rows -----------------------------------------------------------------------------------------------------
+
+def check_order_against_update_rows(fr, device):
+    """One table, 3 rows, batch 8, on one worker's stream: an offsets-form batch submitted BEFORE fr_worker_update_rows sees the old rows, one
+    submitted after it the new ones (nothing is synced in between)."""
+    m = fr.Model.from_spec({"name": "csr_order", "tables": [{"dim": 8, "rows": 3}], "fc": [64, 32, 32]})
+    ctx = fr.Context(m, device=device)
+    try:
+        rng = np.random.default_rng(229)
+        old = rng.standard_normal((3, 8)).astype(np.float32)
+        new = (old + 100.0).astype(np.float32)
+        ctx.upload_table(0, old)
+        ctx.set_pooling(np.array([3], np.int32))
+        B = 8
+        wk = fr.Worker(ctx, B)
+        rect = P.random_bags(rng, m.index_ranges(), [3], B, empty_share=0.3)
+        rect[0] = (0, 1, 2)
+        off, ind, _ = fr.bags_to_csr(rect, [3])
+        c = Csr(fr, ctx, off, ind)
+        d_ids = fr.DeviceBuffer.from_numpy(ctx, np.arange(3, dtype=np.int32))
+        d_new = fr.DeviceBuffer.from_numpy(ctx, new)
+        r0, r1 = fr.DeviceBuffer(ctx, B * m.record_len * 4), fr.DeviceBuffer(ctx, B * m.record_len * 4)
+        wk.gather_pooled_csr(B, c.off, c.ind, c.nnz, None, r0)
+        wk.update_rows(0, 3, d_ids, d_new)
+        wk.gather_pooled_csr(B, c.off, c.ind, c.nnz, None, r1)
+        wk.sync()
+        n = B * m.record_len
+        want_old = GM.pooled_expected(fr, m, [old], np.array([3]), rect, None)
+        want_new = GM.pooled_expected(fr, m, [new], np.array([3]), rect, None)
+        assert not np.array_equal(want_old, want_new)
+        assert np.array_equal(r0.download(np.uint32, n), want_old.ravel())
+        assert np.array_equal(r1.download(np.uint32, n), want_new.ravel())
+        c.free()
+        wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- hosts -----------------------------------------------------------------------------------------------------------------------------------
+
+def _host_dir():
+    import os
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpu-fpga-recommendation-system_amd", "host")
+
+
+def _serve(device, pool, csr, free_port_block, batch=64, total=8, threads=2, H=3):
+    """fleetrec_server --hots H [--csr] fed by fleetrec_sender --hots H --ragged [--csr] --reply -> the printed score rows (text)."""
+    import os
+    import re
+    import subprocess
+    host = _host_dir()
+    port = free_port_block(threads)
+    flag = ["--csr"] if csr else []
+    srv = subprocess.Popen([os.path.join(host, "fleetrec_server"), "--model", "A", "--batch", str(batch), "--threads", str(threads), "--port", str(port),
+                            "--total", str(total), "--tables", "evenodd", "--weights", "ones", "--device", str(device), "--hots", str(H), "--pool", pool, "--reply"]
+                           + flag, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    snd = subprocess.Popen([os.path.join(host, "fleetrec_sender"), "--model", "A", "--batch", str(batch), "--threads", str(threads), "--port", str(port),
+                            "--indices", "reference", "--hots", str(H), "--ragged", "--reply"] + (["--pool", "weighted"] if pool == "weighted" else []) + flag,
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    try:
+        out, _ = srv.communicate(timeout=300)
+        snd.communicate(timeout=60)
+    finally:
+        for p in (srv, snd):
+            if p.poll() is None:
+                p.kill()
+    out = out.decode()
+    assert srv.returncode == 0, out
+    assert "processed %d batches" % total in out, out
+    rows = re.findall(r"thread \d+ scores:((?: [-0-9.e+]+)+)", out)
+    assert rows, out
+    return rows
+
+
+def check_server(fr, device, pool, free_port_block):
+    """The sender's bags compacted (--csr on both hosts) give the scores the same pair gives with the padded blocks, and the binding's
+    offsets form gives them too (Model-A, even/odd tables, all-ones FC weights, 3 slots per column, ragged)."""
+    H = 3
+    padded = _serve(device, pool, False, free_port_block)
+    csr = _serve(device, pool, True, free_port_block)
+    assert [r.split() for r in csr] == [r.split() for r in padded], (csr, padded)
+    m = fr.Model.builtin(fr.MODEL_A)
+    idx = P.sender_rows(5, m.n_tables, H, True)
+    w = PM.sender_weights(5, m.n_tables, H) if pool == "weighted" else None
+    ctx = fr.Context(m, device=device)
+    try:
+        ctx.fill_tables(fr.FILL_EVEN_ODD, 0)
+        ctx.fill_weights(fr.WEIGHTS_ONES, 0)
+        ctx.set_pooling(np.full(m.idx_cols, H, np.int32), modes=np.full(m.idx_cols, MEAN, np.int32) if pool == "mean" else None)
+        wk = fr.Worker(ctx, 8)
+        off, ind, wf = fr.bags_to_csr(idx, np.full(m.idx_cols, H), weights=w)
+        assert ind.size < idx.size
+        mine = wk.infer_pooled_csr(off, ind, weights=wf)
+        assert np.array_equal(mine, wk.infer_pooled(idx, weights=w))
+        wk.close()
+    finally:
+        ctx.close()
+    assert len(set(mine.tolist())) > 1
+    for r in csr:
+        assert np.array_equal(np.array([float(x) for x in r.split()], dtype=np.float32), mine), (r, mine)
+
+
+def check_server_refuses_bad_block(fr, device, free_port_block, which):
+    """A block whose last offset says more entries than batch x P (which = "nnz"), or whose first offset is not 0 (which = "first"): the
+    server ends the connection with its error status, having read the offsets and nothing behind them."""
+    import os
+    import socket
+    import subprocess
+    import time
+    batch, H = 16, 3
+    m = fr.Model.builtin(fr.MODEL_A)
+    C = m.idx_cols
+    port = free_port_block(1)
+    srv = subprocess.Popen([os.path.join(_host_dir(), "fleetrec_server"), "--model", "A", "--batch", str(batch), "--threads", "1", "--port", str(port), "--total", "4",
+                            "--tables", "evenodd", "--weights", "ones", "--device", str(device), "--hots", str(H), "--csr"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    try:
+        sk = None
+        deadline = time.monotonic() + 120
+        while sk is None:
+            try:
+                sk = socket.create_connection(("127.0.0.1", port), timeout=5)
+            except OSError:
+                assert srv.poll() is None and time.monotonic() < deadline, "the server did not come up"
+                time.sleep(0.05)
+        off = np.zeros(batch * C + 1, np.int32)
+        if which == "nnz":
+            off[-1] = batch * C * H + 1
+        else:
+            off[0] = 1
+        sk.sendall(off.tobytes())
+        out, _ = srv.communicate(timeout=120)
+        sk.close()
+    finally:
+        if srv.poll() is None:
+            srv.kill()
+    out = out.decode()
+    assert srv.returncode == 1 and "malformed offsets-form block" in out, out
+
+
+def check_hosts_csr_needs_hots(fr):
+    import os
+    import subprocess
+    for prog, extra in (("fleetrec_server", ["--device", "-1"]), ("fleetrec_sender", [])):
+        p = subprocess.run([os.path.join(_host_dir(), prog), "--model", "A", "--csr"] + extra, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+        assert p.returncode != 0 and "--hots" in p.stdout.decode(), p.stdout.decode()
+    for extra in (["--stream"], ["--shards", "2"]):     # the refusal of tests/pooled_helpers.py, word for word, with --csr as well
+        p = subprocess.run([os.path.join(_host_dir(), "fleetrec_server"), "--model", "A", "--device", "-1", "--hots", "4", "--csr"] + extra,
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+        assert p.returncode != 0 and "not with --stream or --shards" in p.stdout.decode(), p.stdout.decode()

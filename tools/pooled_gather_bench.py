@@ -21,6 +21,12 @@ one-hot kernel's of the same run.
     buffer -- the weighted fold reads 4 more bytes per slot, counted in its algorithmic bytes).  FR_LIB=<another build of the same ABI> times
     that build (an A/B run against an older commit can only ask it for the folds it has).
     --rehearse: tiny tables on the CPU back-end, to check the plumbing without a GPU (its times are not measurements and say so).
+    --csr: the offsets (CSR) form against the padded form on the SAME bags -> profiles/pooled_gather_csr.json.  Caps 16 and 64 (--caps), two seeded
+    bag-length laws: "full" (every bag at the cap) and "skewed" (a geometric law clipped to the cap, mean about cap / 8, empty bags included);
+    unweighted SUM, plus the weighted fold at cap 16.  The padded buffers hold the bags padded with -1, the offsets-form buffers the same bags
+    compacted (fleetrec_amd.bags_to_csr); the two forms alternate within every round.  Per shape: us per batch, fetched row words per second (the
+    bags' non-empty entries x the words of their rows), algorithmic bytes (rows + records + dense + indices + offsets + weights) and TB/s, the
+    spread between rounds; per pair the offsets form's time over the padded form's.
 Experiments build (FR_LIB=.../libfleetrec_exp.so): --sweep times FR_POOL_WIN x FR_POOL_ITEMS instead (profiles/pooled_gather_window_sweep.md).
 """
 import argparse
@@ -133,6 +139,92 @@ def run_mode(fr, args, mode_name, device, rehearse):
     return out
 
 
+def bag_lengths(rng, law, B, cols, cap):
+    """int64 [B][cols].  full: the cap.  skewed: geometric on 0, 1, 2, ... with mean cap / 8, clipped to the cap (a long tail, empty bags included)."""
+    if law == "full":
+        return np.full((B, cols), cap, np.int64)
+    mean = cap / 8.0
+    return np.minimum(rng.geometric(1.0 / (1.0 + mean), size=(B, cols)) - 1, cap)
+
+
+def run_csr(fr, args, mode_name, device, rehearse):
+    imode = {"table": fr.INDEX_PER_TABLE, "bank": fr.INDEX_PER_BANK}[mode_name]
+    base = fr.Model.builtin(fr.MODEL_C)
+    model = base.clone(max_rows=2000, index_mode=imode) if rehearse else base.clone(index_mode=imode)
+    B, C = args.batch, model.idx_cols
+    ctx = fr.Context(model, device=device)
+    ctx.fill_tables(fr.FILL_HASH, SEED_TABLES)
+    rng = np.random.default_rng(20270 + imode)
+    ranges = model.index_ranges()
+    words_of_col = np.zeros(C, np.int64)   # 16-byte TABLE / COPY words of a record that every entry of the column's bag fetches
+    bank_of = model.bank_map()[0] if imode == fr.INDEX_PER_BANK else None
+    for sg in model.segments():
+        if sg.kind != 2:
+            words_of_col[sg.src if bank_of is None else int(bank_of[sg.src])] += sg.len // 4
+    K, dense_len = model.record_len, model.dense_len
+    out = {"index_mode": mode_name, "index_cols": int(C), "record_floats": int(K), "shapes": {}, "pairs": {}}
+    for cap in args.caps:
+        ctx.set_pooling(np.full(C, cap, np.int32))
+        wk = fr.Worker(ctx, B)
+        rec = wk.records_dptr()
+        dns = [fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (B, dense_len)).astype(np.float32)) for _ in range(4)] if dense_len else None
+        nbuf = 2 if rehearse else max(2, min(4, -(-(512 << 20) // (B * C * cap * 4))))
+        for law in ("full", "skewed"):
+            folds = ["sum"] + (["weighted"] if cap == args.caps[0] else [])
+            sets, nnz_sum, fetched = [], 0, 0
+            for _ in range(nbuf):   # the same bags in both forms
+                L = bag_lengths(rng, law, B, C, cap)
+                rect = (rng.random((B, C, cap)) * ranges[None, :, None]).astype(np.int32)
+                rect[np.arange(cap)[None, None, :] >= L[:, :, None]] = -1
+                rect = rect.reshape(B, C * cap)
+                w = rng.uniform(0.5, 1.5, rect.shape).astype(np.float32) if "weighted" in folds else None
+                off, ind, wf = fr.bags_to_csr(rect, np.full(C, cap), weights=w)
+                nnz_sum += int(ind.size)
+                fetched += int((L * words_of_col[None, :]).sum())
+                up = lambda a: fr.DeviceBuffer.from_numpy(ctx, a if a.size else np.zeros(1, a.dtype))
+                sets.append({"rect": up(rect), "w": up(w) if w is not None else None, "off": up(off), "ind": up(ind), "wf": up(wf) if wf is not None else None,
+                             "nnz": int(ind.size)})
+            nnz, fetched = nnz_sum / nbuf, fetched / nbuf
+            shapes = {}
+            for fold in folds:
+                wt = fold == "weighted"
+                shapes["%s_cap%d_%s_padded" % (fold, cap, law)] = (
+                    lambda s, d, wt=wt: wk.gather_pooled(B, s["rect"], d, rec, weights=s["w"] if wt else None), "padded", fold)
+                shapes["%s_cap%d_%s_offsets" % (fold, cap, law)] = (
+                    lambda s, d, wt=wt: wk.gather_pooled_csr(B, s["off"], s["ind"], s["nnz"], d, rec, weights=s["wf"] if wt else None), "offsets", fold)
+            kernels, times = {}, {n: [] for n in shapes}
+            for name, (launch, form, fold) in shapes.items():   # warm-up of every shape
+                window(wk, launch, sets, dns, min(args.reps, 4 * nbuf), 0)
+                kernels[name] = wk.last_kernel()
+            for r in range(args.rounds):   # the two forms alternate within a round
+                for name, (launch, form, fold) in shapes.items():
+                    times[name].append(window(wk, launch, sets, dns, args.reps, r * args.reps))
+            for name, (launch, form, fold) in shapes.items():
+                us = float(np.median(times[name]))
+                wt = 2 if fold == "weighted" else 1
+                idx_bytes = (B * C * cap * 4 * wt) if form == "padded" else (nnz * 4 * wt + (B * C + 1) * 4)
+                by = fetched * 16 + B * K * 4 + B * dense_len * 4 + idx_bytes
+                out["shapes"][name] = {"kernel": kernels[name], "cap": cap, "law": law, "form": form, "pool": fold, "buffer_sets": nbuf, "mean_bag_length": nnz / (B * C),
+                                       "index_offsets_weights_bytes_per_batch": idx_bytes, "us_per_batch_rounds": [round(t, 3) for t in times[name]],
+                                       "us_per_batch": round(us, 3), "us_spread_max_minus_min": round(max(times[name]) - min(times[name]), 3),
+                                       "row_words_fetched_per_s": fetched / (us * 1e-6), "algorithmic_bytes_per_batch": by, "algorithmic_TBs": by / (us * 1e-6) / 1e12}
+                print("%-5s %-34s %10.2f us  %7.2f G row words/s  %5.2f TB/s  %s" % (mode_name, name, us, fetched / (us * 1e-6) / 1e9, by / (us * 1e-6) / 1e12,
+                                                                                 kernels[name]), flush=True)
+            for fold in folds:
+                pn, on = "%s_cap%d_%s_padded" % (fold, cap, law), "%s_cap%d_%s_offsets" % (fold, cap, law)
+                tp, to = times[pn], times[on]
+                out["pairs"]["%s_cap%d_%s" % (fold, cap, law)] = {
+                    "offsets_over_padded": float(np.median(to) / np.median(tp)),
+                    "offsets_median_below_padded_median_minus_padded_spread": bool(np.median(to) < np.median(tp) - (max(tp) - min(tp)))}
+            for s_ in sets:
+                for b in s_.values():
+                    if isinstance(b, fr.DeviceBuffer):
+                        b.free()
+        wk.close()
+    ctx.close()
+    return out
+
+
 def run_sweep(fr, args, device):
     """Experiments build: FR_POOL_WIN x FR_POOL_ITEMS at every hots, per-bank and per-table -> a markdown table on stdout."""
     combos = [(1, 4), (1, 8), (2, 2), (2, 4), (2, 8), (4, 1), (4, 2), (4, 4), (4, 8), (8, 1), (8, 2), (8, 4), (16, 1), (16, 2)]
@@ -178,6 +270,8 @@ def main():
     ap.add_argument("--pool", default="sum")
     ap.add_argument("--rehearse", action="store_true")
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--csr", action="store_true")
+    ap.add_argument("--caps", default="16,64")
     args = ap.parse_args()
     args.modes = [m for m in args.modes.split(",") if m]
     args.hots = [int(h) for h in args.hots.split(",") if h]
@@ -193,6 +287,22 @@ def main():
             sys.exit("--sweep needs the experiments build: FR_LIB=.../libfleetrec_exp.so (make -C gpu-fpga-recommendation-system_amd/csrc exp)")
         print("| mode | hots | window | items | us median | min | max | kernel |\n|---|---|---|---|---|---|---|---|", flush=True)
         run_sweep(fr, args, device)
+        return
+    if args.csr:
+        args.caps = [int(c) for c in args.caps.split(",") if c]
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "pooled_gather_csr.json")
+        t_start = time.time()
+        res = {"tool": "tools/pooled_gather_bench.py --csr", "model": "C", "batch": args.batch, "fill": "FR_FILL_HASH", "index_law": "uniform rows; bag lengths: full / skewed (clipped geometric, mean cap / 8)",
+               "timed_launches_per_window": args.reps, "rounds": args.rounds, "caps": args.caps, "library": os.environ.get("FR_LIB", "libfleetrec.so"),
+               "timing": "HIP events on the worker's stream around each window; the padded and the offsets form alternate within a round; median over the rounds",
+               "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse), "modes": [run_csr(fr, args, m, device, args.rehearse) for m in args.modes]}
+        res["wall_s"] = round(time.time() - t_start, 1)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+        print("wrote", args.out)
         return
     t_start = time.time()
     res = {"tool": "tools/pooled_gather_bench.py", "model": "C", "batch": args.batch, "fill": "FR_FILL_HASH", "index_law": "uniform", "timed_launches_per_window": args.reps,
