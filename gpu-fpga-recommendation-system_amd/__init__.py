@@ -79,14 +79,16 @@ ABI_SYMBOLS = [
     "fr_worker_submit_pooled_weighted",
     "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr",
     "fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
+    "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
 ]
 
 
-# the entry points ABI 6 gained last (pooling modes and per-sample weights, sparse row updates, the offsets form of the pooled lookups): the only names an FR_LIB build of the same ABI may lack
+# the entry points ABI 6 gained last (pooling modes and per-sample weights, sparse row updates, the offsets form of the pooled lookups, their streaming pushes): the only names an FR_LIB build of the same ABI may lack
 _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
                    "fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device",
                    "fr_worker_pool_weights_ptr", "fr_worker_submit_pooled_weighted",
-                   "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr")
+                   "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr",
+                   "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list")
 
 
 def lib():
@@ -159,6 +161,8 @@ def lib():
         "fr_worker_gather_pooled_weighted": (i32, [vp, i32, vp, vp, vp, vp]), "fr_worker_submit_pooled_weighted_device": (i32, [vp, i32, vp, vp, vp, vp]),
         "fr_worker_pool_weights_ptr": (pf, [vp]), "fr_worker_submit_pooled_weighted": (i32, [vp, i32]),
         "fr_worker_gather_pooled_csr": (i32, [vp, i32, vp, vp, i64, vp, vp, vp]), "fr_worker_submit_pooled_csr_device": (i32, [vp, i32, vp, vp, i64, vp, vp, vp]),
+        "fr_worker_push_pooled_device": (i32, [vp, i32, vp, vp, vp, vp]), "fr_worker_push_pooled_csr_device": (i32, [vp, i32, vp, vp, i64, vp, vp, vp]),
+        "fr_worker_push_pooled_device_list": (i32, [vp, i32, vp, vp, vp, vp, vp]),
         "fr_worker_pool_offsets_ptr": (pi, [vp]), "fr_worker_submit_pooled_csr": (i32, [vp, i32, i32]),
         "fr_worker_update_rows": (i32, [vp, i32, i32, vp, vp]), "fr_ctx_update_rows": (i32, [vp, i32, i32, vp, vp]),
         "fr_ctx_lp_bank_image_builds": (ctypes.c_longlong, [vp]),
@@ -936,6 +940,30 @@ class Worker:
     def submit_pooled_csr_device(self, batch, d_offsets, d_indices, nnz, d_dense, d_scores, weights=None):
         _check(lib().fr_worker_submit_pooled_csr_device(self._h, batch, self._ptr(d_offsets), self._ptr(d_indices), int(nnz), self._ptr(weights), self._ptr(d_dense),
                                                         self._ptr(d_scores)))
+
+    # streaming pushes of pooled batches: nothing waits, sync() is the completion point; every buffer stays valid (scores distinct) until then ----
+    def push_pooled_device(self, batch, d_idx, d_dense, d_scores, weights=None):
+        """fr_worker_push_pooled_device: push_device for a pooled batch (d_idx int32 [batch][ctx.pooled_index_cols]; weights: device float32 of
+        the same shape, or None for the unweighted fold)."""
+        _check(lib().fr_worker_push_pooled_device(self._h, batch, self._ptr(d_idx), self._ptr(weights), self._ptr(d_dense), self._ptr(d_scores)))
+
+    def push_pooled_csr_device(self, batch, d_offsets, d_indices, nnz, d_dense, d_scores, weights=None):
+        """fr_worker_push_pooled_csr_device: the offsets form (arguments as submit_pooled_csr_device)."""
+        _check(lib().fr_worker_push_pooled_csr_device(self._h, batch, self._ptr(d_offsets), self._ptr(d_indices), int(nnz), self._ptr(weights), self._ptr(d_dense),
+                                                      self._ptr(d_scores)))
+
+    def make_pooled_push_list(self, batches, d_idx, d_dense, d_scores, weights=None):
+        """Pre-built argument arrays for push_pooled_device_list: batches [n] ints, d_idx / d_scores [n] DeviceBuffers (or pointers), d_dense [n] or
+        None, weights [n] (entries may be None) or None."""
+        n = len(batches)
+        vp = ctypes.c_void_p
+        arr = lambda xs: (vp * n)(*[self._ptr(x) for x in xs])
+        return (n, (ctypes.c_int * n)(*[int(b) for b in batches]), arr(d_idx), arr(weights) if weights is not None else None,
+                arr(d_dense) if d_dense is not None else None, arr(d_scores), (d_idx, weights, d_dense, d_scores))   # (the buffers stay referenced)
+
+    def push_pooled_device_list(self, plist):
+        """n consecutive push_pooled_device calls in one native call (fr_worker_push_pooled_device_list); plist from make_pooled_push_list."""
+        _check(lib().fr_worker_push_pooled_device_list(self._h, plist[0], plist[1], plist[2], plist[3], plist[4], plist[5]))
 
     def submit_pooled_csr(self, batch, weighted=False):
         """fr_worker_submit_pooled_csr on the offsets in pool_offsets, the flat entries in the pinned index buffer and (weighted) the flat weights

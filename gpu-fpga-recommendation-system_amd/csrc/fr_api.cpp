@@ -1789,9 +1789,12 @@ extern "C" int fr_ctx_pooled_index_cols(const fr_ctx *ctx) { return ctx ? ctx->p
 // weighted = the call is one of the *_weighted entry points: d_weights must be there, and every column's mode SUM
 // d_offsets != NULL: the offsets (CSR) form -- d_idx / d_weights are the nnz flat entries (weighted = d_weights != NULL), the descriptors the second array;
 // its three 4000 MiB bounds are checked here, once, for both back-ends
+// operand != 0 (GPU only; 1 + the chain's precision): d_records is the chain's stage-1 operand of ldm items instead (frk_gather_pooled); the call may then
+// return FR_POOL_NO_OPERAND_ARM, with nothing launched
 static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
-                                const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
+                                const int32_t *d_offsets = nullptr, int64_t nnz = 0, int operand = 0, int ldm = 0) {
     fr_ctx *c = w->ctx;
+    const int out_words = operand ? c->model.fc[0] / 4 : c->slice_padded / 4;
     const bool csr = d_offsets != nullptr;   // (the offsets-form entry points refuse a NULL d_offsets themselves)
     if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
     if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
@@ -1819,11 +1822,11 @@ static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, c
         if (c->cpu)
             return frc_gather_pooled(c->h_words.data(), c->h_pool_csr.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err, d_offsets, (int)idx_cols(c), nnz);
         return frk_gather_pooled(c->d_words, c->d_pool_csr, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, false, c->pool_any_mean, d_dense, d_records, batch,
-                                 w->d_err, w->stream, c->slice_padded / 4, d_offsets, (int)idx_cols(c), nnz);
+                                 w->d_err, w->stream, out_words, d_offsets, (int)idx_cols(c), nnz, operand, ldm, c->f8_e_act[0]);
     }
     if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err);
     return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, c->pool_wide, c->pool_any_mean, d_dense, d_records, batch,
-                             w->d_err, w->stream, c->slice_padded / 4);
+                             w->d_err, w->stream, out_words, nullptr, 0, 0, operand, ldm, c->f8_e_act[0]);
 }
 
 static int gather_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
@@ -2094,6 +2097,87 @@ extern "C" int fr_worker_push_device_list(fr_worker *w, int n, const int *batch,
     if (n < 0 || (n > 0 && (!batch || !d_idx || !d_scores))) FR_FAIL(FR_ERR_INVALID, "push_device_list: n = %d needs batch, d_idx and d_scores arrays", n);
     for (int i = 0; i < n; i++) {
         const int rc = fr_worker_push_device(w, batch[i], d_idx[i], d_dense ? d_dense[i] : nullptr, d_scores[i]);
+        if (rc) return rc;
+    }
+    return FR_OK;
+}
+
+// ---- streaming pushes of pooled lookups: the pooled gather writes the chain's stage-1 operand itself and the batch enters the stage pipeline at
+// stage 1 of the next launch, un-flushed -- its FC1 shares that launch with FC2 / FC3 / the output layer of the pushes before it ----
+static int push_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores, const int32_t *d_offsets = nullptr,
+                            int64_t nnz = 0) {
+    int rc = check_ready(w, batch, true, true);
+    if (rc) return rc;
+    if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
+    fr_ctx *c = w->ctx;
+    const bool weighted = d_weights != nullptr;
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
+    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (c->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "a pooled push needs a SEMANTIC-layout context");
+    if (c->cpu) {   // the CPU back-end has nothing to queue behind: the batch is computed before the call returns
+        rc = submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores, d_offsets, nnz);
+        if (rc) return rc;
+        w->in_flight = true;
+        return FR_OK;
+    }
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then push");
+    if (c->slice_padded != c->model.fc[0]) FR_FAIL(FR_ERR_STATE, "internal: a record of %d floats on a chain of K = %d", c->slice_padded, c->model.fc[0]);
+    FR_SET_DEVICE(c);
+    rc = fused_flush(w);   // batches fr_worker_push_device queued for a fused launch were pushed before this one: launched first, not waited for
+    if (rc) return rc;
+    if (w->launch_no == 0) w->launch_no = 1;   // stage 1 of the next launch reads the set the (virtual) previous launch wrote
+    // a one-hot batch gathered by the previous launch holds the slot (and the X operand) this batch would take: one launch without a new batch
+    // moves it on -- at most once, nothing entered the launch that this makes the previous one
+    while (w->ring[(w->launch_no - 1) % 8].active) {
+        rc = pipeline_step(w);
+        if (rc) return rc;
+    }
+    const int ldm = round_up(batch, 32);
+    const int par_prev = (int)((w->launch_no - 1) & 1);
+    float *x = act_set(w, par_prev).x;
+    // experiments build only: FR_POOL_PUSH_TWO_LAUNCH = 1 takes the two-launch form for every shape (tools/pooled_stream_bench.py, form (c))
+    rc = FR_KNOB("POOL_PUSH_TWO_LAUNCH", 0) ? FR_POOL_NO_OPERAND_ARM : launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, x, d_offsets, nnz, 1 + c->fc_precision, ldm);
+    if (rc == FR_POOL_NO_OPERAND_ARM) {
+        // the two-launch form: fp32 records into the worker's record buffer, then the conversion launch of fr_worker_fc_only -- for the (shape,
+        // operand type) pairs of gather_pooled_kernel that carry no operand-store arm (fr_gather.hip, pooled_operand_forms: <4, 2, false> and
+        // <2, 4, false> on a bf16 / fp8 chain); stream order keeps the buffer safe
+        rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records, d_offsets, nnz);
+        if (rc) return rc;
+        keep_kernel(w);
+        w->in_flight = true;
+        if (c->fc_precision == FR_FC_FP8) rc = frk_records_to_q16_fp8(w->d_records, x, batch, c->model.fc[0], ldm, c->f8_e_act[0], w->stream);
+        else if (c->fc_precision == FR_FC_BF16) rc = frk_records_to_q8_bf16(w->d_records, x, batch, c->model.fc[0], ldm, w->stream);
+        else rc = frk_transpose_records(w->d_records, x, batch, c->model.fc[0], ldm, w->stream);
+    } else if (rc == FR_OK) {
+        keep_kernel(w);   // the gather, as launched (fr_worker_last_kernel)
+        w->in_flight = true;
+    }
+    if (rc) return rc;
+    rc = pipeline_push(w, batch, 1, nullptr, nullptr, d_scores);   // no flush: fr_worker_sync drains
+    if (rc) return rc;
+    w->last_x_parity = par_prev;   // fr_worker_features_dptr names this operand
+    return FR_OK;
+}
+
+extern "C" int fr_worker_push_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores) {
+    return push_pooled_impl(w, batch, d_idx, d_weights, d_dense, d_scores);
+}
+
+extern "C" int fr_worker_push_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
+                                                float *d_scores) {
+    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
+    return push_pooled_impl(w, batch, d_indices, d_weights, d_dense, d_scores, d_offsets, nnz);
+}
+
+extern "C" int fr_worker_push_pooled_device_list(fr_worker *w, int n, const int *batch, const int32_t *const *d_idx, const float *const *d_weights, const float *const *d_dense,
+                                                 float *const *d_scores) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    if (n < 0 || (n > 0 && (!batch || !d_idx || !d_scores))) FR_FAIL(FR_ERR_INVALID, "push_pooled_device_list: n = %d needs batch, d_idx and d_scores arrays", n);
+    for (int i = 0; i < n; i++) {
+        const int rc = push_pooled_impl(w, batch[i], d_idx[i], d_weights ? d_weights[i] : nullptr, d_dense ? d_dense[i] : nullptr, d_scores[i]);
         if (rc) return rc;
     }
     return FR_OK;

@@ -405,11 +405,11 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
 // the clamp of a bad row to 0 and the fold are the code of the padded form, so the bits are those of the same bags padded with -1.  Only
 // 4-byte alignment is given: the form has no 16-byte index loads (the WIDE instantiations compile it out), and it always runs in the half
 // passes of the MEAN / weighted arms, with its offsets and lengths in the registers the other half's row words would have taken.
-template <int ITEMS, int WIN, bool WIDE, bool WEIGHTED, bool COUNT, bool CSR = false>
+template <int ITEMS, int WIN, bool WIDE, bool WEIGHTED, bool COUNT, bool CSR = false, int OPND = 0>
 __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, int w, unsigned b0,
                                                    const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
                                                    const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
-                                                   unsigned out_bytes, const int32_t *__restrict__ offsets = nullptr, int n_icols = 0, unsigned nnz = 0u) {
+                                                   unsigned out_bytes, const FrPoolDest &dst, const int32_t *__restrict__ offsets = nullptr, int n_icols = 0, unsigned nnz = 0u) {
 #pragma clang fp contract(off)
     static_assert(!WIDE || WIN % 4 == 0, "16-byte index loads need whole groups of 4 slots");
     static_assert(!(CSR && WIDE), "the offsets form has no 16-byte index loads");
@@ -423,8 +423,17 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
     const uint32_t first = pd.x, hots = pd.y & ~FR_POOL_DESC_MEAN;
     const bool mean = COUNT && (pd.y & FR_POOL_DESC_MEAN) != 0;
     const uint64_t base = (is_dense ? (uint64_t)reinterpret_cast<uintptr_t>(dense) : 0ull) + src;
-    const unsigned blk = (dst_blk * (unsigned)batch + dst_off) * 16u;
-    const unsigned ostride = dst_stride * 16u;
+    // where the word goes: the item's fp32 record, or (OPND) the chain's feature-major stage-1 operand -- element (w >> sh, b) of 16 bytes, the
+    // word's 16 >> sh bytes at (w & mask) inside it; both are `blk + b * ostride`.  The operand's zeros (pad k-rows, chunks of pad items) are stored by
+    // gather_pooled_operand_zeros before the fold, so that the fold keeps two scalars more than the record arm (dst.ldm, dst.code)
+    constexpr unsigned sh = OPND ? (unsigned)OPND - 1u : 0u;   // OPND = the operand's form (FrPoolDest), fixed per arm
+    const unsigned blk = OPND ? ((dst_off >> sh) * dst.ldm) * 16u + (dst_off & ((1u << sh) - 1u)) * (16u >> sh) : (dst_blk * (unsigned)batch + dst_off) * 16u;
+    const unsigned ostride = OPND ? 16u : dst_stride * 16u;
+    unsigned lim = OPND ? dst.ldm : (unsigned)batch;   // items the stores cover: the operand's pad items [batch, ldm) are stored as zeros
+    float scale = OPND == 3 ? __builtin_ldexpf(1.0f, dst.code >> FR_PD_EX_SHIFT) : 1.0f;   // 2^e_x, exact
+    // OPND: both in vector registers from here on (the half passes leave some; the fold's masks leave no scalar one)
+    if constexpr (OPND != 0) asm volatile("" : "+v"(lim));
+    if constexpr (OPND == 3) asm volatile("" : "+v"(scale));
     const unsigned irow = (unsigned)pool_cols * 4u;
     const unsigned idx_bytes = CSR ? nnz * 4u : (unsigned)batch * irow;   // CSR: the flat entries (the launcher keeps nnz * 4 below 4000 MiB)
     const __amdgpu_buffer_rsrc_t rs_idx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, idx_bytes, 0x00020000);
@@ -432,6 +441,22 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
     // the weights' resource has the index rows' shape and bounds (WEIGHTED only; the unweighted body never touches it)
     const __amdgpu_buffer_rsrc_t rs_wt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(weights), 0, WEIGHTED ? idx_bytes : 0u, 0x00020000);
     typedef const u32x4_t __attribute__((address_space(1))) * gptr_t;   // a global_load (not a flat one)
+    // one folded word of item b out, in the destination's type: a bit copy, two pack_bf16x2 or pack_fp8_word (the rounding of store_word)
+    auto store_out = [&](unsigned b, unsigned o, uint32_t ax, uint32_t ay, uint32_t az, uint32_t aw) __attribute__((always_inline)) {
+        const unsigned off = b < lim ? o + b * ostride : out_bytes;   // past the batch (the operand: past ldm): dropped by the resource's bounds
+        if constexpr (sh == 0u) {
+            u32x4_t x;
+            x.x = ax, x.y = ay, x.z = az, x.w = aw;
+            __builtin_amdgcn_raw_buffer_store_b128(x, rs_out, off, 0, 0);
+        } else if constexpr (sh == 1u) {
+            typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+            u32x2_t x;
+            x.x = pack_bf16x2(__uint_as_float(ax), __uint_as_float(ay)), x.y = pack_bf16x2(__uint_as_float(az), __uint_as_float(aw));
+            __builtin_amdgcn_raw_buffer_store_b64(x, rs_out, off, 0, 0);
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b32(pack_fp8x4(__uint_as_float(ax), __uint_as_float(ay), __uint_as_float(az), __uint_as_float(aw), scale), rs_out, off, 0, 0);
+        }
+    };
     bool bad = false;
     uint32_t badv = 0u;   // WEIGHTED: `bad` as a vector register
     uint4 acc[ITEMS];
@@ -581,24 +606,101 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
                 acc[i].w = __float_as_uint(__uint_as_float(acc[i].w) / n);
             }
         }
-        const unsigned off = b < (unsigned)batch ? blk + b * ostride : out_bytes;   // past the batch: dropped by the resource's bounds
-        u32x4_t x;
-        x.x = acc[i].x, x.y = acc[i].y, x.z = acc[i].z, x.w = acc[i].w;
-        __builtin_amdgcn_raw_buffer_store_b128(x, rs_out, off, 0, 0);
+        const bool pad = OPND && b >= (unsigned)batch;   // a pad item of the operand (its lookups read row 0): zeros
+        store_out(b, blk, pad ? 0u : acc[i].x, pad ? 0u : acc[i].y, pad ? 0u : acc[i].z, pad ? 0u : acc[i].w);
     }
     if (bad || badv) atomicOr_system(err_flag, 1);  // pinned host word; error path only
 }
 
-// Waves per SIMD the register allocation must leave room for: what the five product shapes (ITEMS x WIN = 8 row words in flight: 8 waves,
-// 64 registers; 16: 5 waves, 96 registers) had before the kernel grew its MEAN and weighted arms, so that no arm costs the plain SUM fold a
-// wave (tools/kernel_resources.py: 64 / 50 / 60 / 64 / 93 / 94 / 81 / 79 VGPRs, no spill, no scratch).  Experiment shapes: no floor.
+// The zeros of the operand form (FrPoolDest), stored by the word threads before their fold: the pad words behind the record in the operand's
+// k-rows (the last FR_PD_PAD words of FrPoolDest::code: e4m3 rows are 64 k long), dealt over the n_words word threads, for every item of the chunk below
+// ldm -- and, for a chunk of pad items only (b0 >= batch, uniform over the workgroup), the thread's own word too: -> true, the thread is done.
+template <int ITEMS>
+__device__ __forceinline__ bool gather_pooled_operand_zeros(const FrWordDesc *__restrict__ words, int w, unsigned n_words, unsigned b0, void *__restrict__ out, int batch,
+                                                            unsigned out_bytes, const FrPoolDest &dst) {
+    const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(out, 0, out_bytes, 0x00020000);
+    const unsigned sh = ((unsigned)dst.code & FR_PD_FORM_MASK) - 1u, esz = 16u >> sh;
+    auto zeros = [&](unsigned word) __attribute__((always_inline)) {
+        const unsigned o = ((word >> sh) * dst.ldm) * 16u + (word & ((1u << sh) - 1u)) * esz;
+#pragma unroll
+        for (int i = 0; i < ITEMS; i++) {
+            const unsigned b = b0 + i, off = b < dst.ldm ? o + b * 16u : out_bytes;   // past ldm: dropped by the resource's bounds
+            if (sh == 0u) {
+                const u32x4_t z = {0u, 0u, 0u, 0u};
+                __builtin_amdgcn_raw_buffer_store_b128(z, rs_out, off, 0, 0);
+            } else if (sh == 1u) {
+                typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+                const u32x2_t z = {0u, 0u};
+                __builtin_amdgcn_raw_buffer_store_b64(z, rs_out, off, 0, 0);
+            } else {
+                __builtin_amdgcn_raw_buffer_store_b32(0u, rs_out, off, 0, 0);
+            }
+        }
+    };
+    const unsigned pad_hi = (out_bytes / (dst.ldm * 16u)) << sh, n_pad = ((unsigned)dst.code >> FR_PD_PAD_SHIFT) & FR_PD_PAD_MASK;
+    for (unsigned p = pad_hi - n_pad + (unsigned)w; p < pad_hi; p += n_words) zeros(p);
+    if (b0 < (unsigned)batch) return false;
+    zeros(words[w].dst_off);
+    return true;
+}
+
+// The folds of gather_pooled_kernel once more, for the operand form F (FrPoolDest: 1 fp32, 2 bf16, 3 e4m3).  All of them run in the half passes of
+// the MEAN / weighted / offsets arms -- the SUM fold too -- so that the operand's scalars fit the registers of the record arms.
+// The half passes of the MEAN / weighted / offsets arms and of every operand arm: half the items, or half the window for one item
+template <int ITEMS, int WIN>
+struct PooledHalf {
+    static constexpr int HI = ITEMS >= 2 ? ITEMS / 2 : 1, HW = ITEMS >= 2 ? WIN : (WIN >= 8 ? WIN / 2 : WIN);
+    static constexpr unsigned NH = ITEMS >= 2 ? 2u : 1u;
+};
+
+template <int ITEMS, int WIN, bool WIDE, int F>
+__device__ __forceinline__ void gather_pooled_operand_arms(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, int wd, unsigned b0,
+                                                           const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
+                                                           const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
+                                                           unsigned out_bytes, const int32_t *__restrict__ offsets, int n_icols, unsigned nnz, const FrPoolDest &dst) {
+    constexpr int HI = PooledHalf<ITEMS, WIN>::HI, HW = PooledHalf<ITEMS, WIN>::HW;
+    constexpr unsigned NH = PooledHalf<ITEMS, WIN>::NH;
+    // which fold: decided by the launcher (FrPoolDest::code), one scalar to branch on instead of the record arms' three
+    const unsigned fold = ((unsigned)dst.code >> FR_PD_FOLD_SHIFT) & FR_PD_FOLD_MASK;
+    if (fold == FR_PD_FOLD_CSR_WEIGHTED) {
+        if constexpr (!WIDE)
+            for (unsigned h = 0; h < NH; h++)
+                gather_pooled_body<HI, HW, false, true, false, true, F>(words, pool, wd, b0 + h * HI, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, dst, offsets, n_icols, nnz);
+    } else if (fold == FR_PD_FOLD_CSR) {
+        if constexpr (!WIDE)
+            for (unsigned h = 0; h < NH; h++)
+                gather_pooled_body<HI, HW, false, false, true, true, F>(words, pool, wd, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, dst, offsets, n_icols, nnz);
+    } else if (fold == FR_PD_FOLD_WEIGHTED) {
+        for (unsigned h = 0; h < NH; h++)
+            gather_pooled_body<HI, HW, WIDE, true, false, false, F>(words, pool, wd, b0 + h * HI, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, dst);
+    } else if (fold == FR_PD_FOLD_MEAN) {
+        for (unsigned h = 0; h < NH; h++)
+            gather_pooled_body<HI, HW, WIDE, false, true, false, F>(words, pool, wd, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, dst);
+    } else {
+        for (unsigned h = 0; h < NH; h++)
+            gather_pooled_body<HI, HW, WIDE, false, false, false, F>(words, pool, wd, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, dst);
+    }
+}
+
+// Which operand forms (bit F of the result: FrPoolDest form F) an instantiation carries arms for.  Six product shapes carry all three.  <4, 2, false>
+// and <2, 4, false>, whose record folds sit at 76 and 74 of the 78 scalar registers that 8 waves leave, carry the fp32 arms only: with the bf16 or the
+// e4m3 arms next to them (<2, 4, false> holds fp32 or bf16, not both; <4, 2, false> fp32 alone) the compiler carries the dispatch in scalar registers
+// the folds have no room for, and spills.  A pooled push of those shapes on a bf16 / fp8 chain writes records and converts them (fr_api.cpp).
+// Experiment shapes: none.
+constexpr unsigned pooled_operand_forms(int items, int win, bool wide) {
+    if ((items == 2 && win == 2) || (items == 2 && win == 4 && wide) || (items == 2 && win == 8) || (items == 1 && win == 16)) return 0xEu;
+    if ((items == 4 && win == 2) || (items == 2 && win == 4)) return 0x2u;
+    return 0u;
+}
+// Waves per SIMD the register allocation must leave room for (ITEMS x WIN = 8 row words in flight: 8 waves, 64 registers; 16: 5 waves, 96
+// registers): what the shapes had with the plain SUM fold alone, so that no later arm costs that fold a wave.  Experiment shapes: no floor.
 constexpr int pooled_min_waves(int items, int win) { return items * win <= 8 ? 8 : items * win == 16 ? 5 : 1; }
 
 template <int ITEMS, int WIN, bool WIDE>
 __global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pooled_kernel(const FrWordDesc *__restrict__ words, const FrPoolDesc *__restrict__ pool, const FrGatherGroups groups,
                                                             int n_groups, const int32_t *__restrict__ idx, const float *__restrict__ weights, int pool_cols,
                                                             const float *__restrict__ dense, void *__restrict__ out, int batch, int *__restrict__ err_flag,
-                                                            unsigned out_bytes, int any_mean, const int32_t *__restrict__ offsets, int n_icols, unsigned nnz) {
+                                                            unsigned out_bytes, int any_mean, const int32_t *__restrict__ offsets, int n_icols, unsigned nnz, const FrPoolDest dst) {
     const int group = blockIdx.x & (n_groups - 1);
     const int w0 = groups.start[group];
     const int t = blockIdx.y * blockDim.x + threadIdx.x;
@@ -606,70 +708,92 @@ __global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pool
     const unsigned b0 = (blockIdx.x / (unsigned)n_groups) * ITEMS;   // the workgroup's chunk of ITEMS items
     bool csr = false;   // uniform over the launch, like `weights` and `any_mean`; the 16-byte-index instantiations hold no offsets arm
     if constexpr (!WIDE) csr = offsets != nullptr;
-    if (__builtin_expect(csr, false)) {   // (out of the padded arms' way)
+    constexpr int HI = PooledHalf<ITEMS, WIN>::HI, HW = PooledHalf<ITEMS, WIN>::HW;
+    constexpr unsigned NH = PooledHalf<ITEMS, WIN>::NH;
+    const int wd = w0 + t;
+    constexpr unsigned FORMS = pooled_operand_forms(ITEMS, WIN, WIDE);
+    if (FORMS != 0u && __builtin_expect(dst.ldm != 0u, false)) {
+        // the operand-store arms (FrPoolDest; uniform over the launch): every fold once more per operand type, its words stored straight into the
+        // chain's stage-1 operand.  The operand's zeros come first, while the fold's registers are still free; a chunk of pad items only (uniform
+        // over the workgroup) has no fold.  (The launcher sends no form here that the instantiation has no arm for.)
+        if constexpr (FORMS != 0u) {
+            if (gather_pooled_operand_zeros<ITEMS>(words, wd, (unsigned)groups.start[n_groups], b0, out, batch, out_bytes, dst)) return;
+            const unsigned form = (unsigned)dst.code & FR_PD_FORM_MASK;
+            if constexpr ((FORMS & 2u) != 0u)
+                if (form == 1u) gather_pooled_operand_arms<ITEMS, WIN, WIDE, 1>(words, pool, wd, b0, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz, dst);
+            if constexpr ((FORMS & 4u) != 0u)
+                if (form == 2u) gather_pooled_operand_arms<ITEMS, WIN, WIDE, 2>(words, pool, wd, b0, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz, dst);
+            if constexpr ((FORMS & 8u) != 0u)
+                if (form == 3u) gather_pooled_operand_arms<ITEMS, WIN, WIDE, 3>(words, pool, wd, b0, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz, dst);
+        }
+    } else if (__builtin_expect(csr, false)) {   // (out of the padded arms' way)
         // the offsets form (`pool` is then the context's second descriptor array: column and cap per word): two arms, the weighted fold and
         // the counting fold (which is the SUM fold on a word without the MEAN bit), both in the half passes of the arms below
         if constexpr (!WIDE) {
-            constexpr int HI = ITEMS >= 2 ? ITEMS / 2 : 1, HW = ITEMS >= 2 ? WIN : (WIN >= 8 ? WIN / 2 : WIN);
-            constexpr unsigned NH = ITEMS >= 2 ? 2u : 1u;
             if (weights) {
                 for (unsigned h = 0; h < NH; h++)
-                    gather_pooled_body<HI, HW, false, true, false, true>(words, pool, w0 + t, b0 + h * HI, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz);
+                    gather_pooled_body<HI, HW, false, true, false, true>(words, pool, wd, b0 + h * HI, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, dst, offsets, n_icols, nnz);
             } else {
                 for (unsigned h = 0; h < NH; h++)
-                    gather_pooled_body<HI, HW, false, false, true, true>(words, pool, w0 + t, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, offsets, n_icols, nnz);
+                    gather_pooled_body<HI, HW, false, false, true, true>(words, pool, wd, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, dst, offsets, n_icols, nnz);
             }
         }
     } else if (weights) {
         // the weighted fold keeps half as many row words in flight per pass (half the items, or half the window for one item), so that
         // its weights and products fit the registers the unweighted fold needs anyway: the kernel's register count, hence the unweighted
         // path's occupancy, is the unweighted fold's
-        if constexpr (ITEMS >= 2) {
-            for (unsigned h = 0; h < 2; h++)
-                gather_pooled_body<ITEMS / 2, WIN, WIDE, true, false>(words, pool, w0 + t, b0 + h * (ITEMS / 2), idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes);
-        } else {
-            constexpr int HALF = WIN >= 8 ? WIN / 2 : WIN;   // (whole groups of 4 slots for the 16-byte loads; the product's one-item form has 16)
-            gather_pooled_body<1, HALF, WIDE, true, false>(words, pool, w0 + t, b0, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes);
-        }
+        for (unsigned h = 0; h < NH; h++)
+            gather_pooled_body<HI, HW, WIDE, true, false>(words, pool, wd, b0 + h * HI, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, dst);
     } else if (any_mean) {
         // a context with a MEAN column: the fold that also counts each bag and divides, in half passes like the weighted fold and for the
         // same reason (its count and quotients cost the 4-item form 72 registers against 64: a wave less per SIMD for every SUM context)
-        if constexpr (ITEMS >= 2) {
-            for (unsigned h = 0; h < 2; h++)
-                gather_pooled_body<ITEMS / 2, WIN, WIDE, false, true>(words, pool, w0 + t, b0 + h * (ITEMS / 2), idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes);
-        } else {
-            constexpr int HALF = WIN >= 8 ? WIN / 2 : WIN;
-            gather_pooled_body<1, HALF, WIDE, false, true>(words, pool, w0 + t, b0, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes);
-        }
+        for (unsigned h = 0; h < NH; h++)
+            gather_pooled_body<HI, HW, WIDE, false, true>(words, pool, wd, b0 + h * HI, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, dst);
     } else {   // every column SUM, no weights: the fold as it was before there were modes
-        gather_pooled_body<ITEMS, WIN, WIDE, false, false>(words, pool, w0 + t, b0, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes);
+        gather_pooled_body<ITEMS, WIN, WIDE, false, false>(words, pool, wd, b0, idx, nullptr, pool_cols, dense, out, batch, err_flag, out_bytes, dst);
     }
 }
 
 template <int ITEMS, int WIN, bool WIDE>
 static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, const float *weights, int pool_cols,
                                 const float *dense, void *out, int batch, int *err_flag, unsigned out_bytes, bool any_mean, hipStream_t s,
-                                const int32_t *offsets, int n_icols, unsigned nnz) {
-    const int n_chunks = (batch + ITEMS - 1) / ITEMS;
+                                const int32_t *offsets, int n_icols, unsigned nnz, const FrPoolDest &dst) {
+    const int n_chunks = ((dst.ldm ? (int)dst.ldm : batch) + ITEMS - 1) / ITEMS;   // the operand form covers the pad items [batch, ldm) too
     const int bx = groups.max_words >= 256 ? 256 : ((groups.max_words + 63) / 64) * 64;
     dim3 grid(n_groups * n_chunks, (groups.max_words + bx - 1) / bx);
     gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, any_mean ? 1 : 0,
-                                                                   offsets, n_icols, nnz);
+                                                                   offsets, n_icols, nnz, dst);
     KCHECK();
     fr_note_kernel("gather_pooled_kernel<%d, %d, %s>", ITEMS, WIN, WIDE ? "true" : "false");
     return FR_OK;
 }
 
 // idx = [batch][pool_cols] int32; weights = NULL or float [batch][pool_cols] (the weighted fold); out = fp32 records in the model's layout,
-// out_words 16-byte words per item.  max_hots picks the window; any_mean: a word of `pool` carries FR_POOL_DESC_MEAN.
+// out_words 16-byte words per item -- or, operand != 0, the chain's stage-1 operand (below; SEMANTIC records only: a word's place is its dst_off).  max_hots picks the window; any_mean: a word of `pool` carries FR_POOL_DESC_MEAN.
 // The offsets form (offsets != NULL): offsets = int32 [batch * n_icols + 1], idx / weights = the nnz flat entries (NULL when nnz == 0), `pool` = the
 // context's offsets-form descriptors (column and cap per word); the narrow instantiation of the window always (4-byte alignment only).
 int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, const float *weights, int pool_cols,
                       int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
-                      const int32_t *offsets, int n_icols, long long nnz) {
+                      const int32_t *offsets, int n_icols, long long nnz, int operand, int ldm, int e_x) {
     if (n_words <= 0 || batch <= 0) return FR_OK;
     if (out_words < n_words) out_words = n_words;
-    const size_t out_bytes = (size_t)batch * (size_t)out_words * 16;
+    // operand = 1 + the chain's fr_fc_precision (1 fp32, 2 bf16, 3 e4m3): `out` is the chain's feature-major stage-1 operand of ldm items and out_words record words
+    // (K / 4) -- Xq[K/4][ldm], Xh[K/8][ldm] or Xf[KE][ldm] in 16-byte elements -- written whole, pad items and pad k-rows as zeros
+    FrPoolDest dst{};
+    size_t out_bytes = (size_t)batch * (size_t)out_words * 16;
+    if (operand) {
+        if (ldm < batch || ldm % 32) FR_FAIL(FR_ERR_INVALID, "pooled gather: operand of %d items for a batch of %d", ldm, batch);
+        if (operand < 1 || operand > 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no operand form %d", operand);
+        dst.ldm = (unsigned)ldm;
+        const unsigned per_row = 1u << (operand - 1);   // record words per 16-byte element
+        const size_t k_rows = operand == 3 ? ((size_t)out_words * 4 + 63) / 64 * 4 : ((size_t)out_words + per_row - 1) / per_row;
+        const unsigned n_pad = (unsigned)(k_rows * per_row - (size_t)out_words);   // at most 15
+        if (e_x < -126 || e_x > 127) FR_FAIL(FR_ERR_INVALID, "pooled gather: X exponent %d", e_x);
+        const unsigned fold = offsets ? (weights ? FR_PD_FOLD_CSR_WEIGHTED : FR_PD_FOLD_CSR) : weights ? FR_PD_FOLD_WEIGHTED : any_mean ? FR_PD_FOLD_MEAN : FR_PD_FOLD_SUM;
+        static_assert(15u <= FR_PD_PAD_MASK, "an e4m3 row pads at most 15 words");
+        dst.code = operand | (int)(n_pad << FR_PD_PAD_SHIFT) | (int)(fold << FR_PD_FOLD_SHIFT) | (int)((unsigned)(operand == 3 ? e_x : 0) << FR_PD_EX_SHIFT);   // (arithmetic shift in the kernel: the exponent's sign survives)
+        out_bytes = k_rows * (size_t)ldm * 16;
+    }
     const size_t idx_bytes = offsets ? (size_t)nnz * 4 : (size_t)batch * (size_t)pool_cols * 4;
     const size_t off_bytes = offsets ? ((size_t)batch * (size_t)n_icols + 1) * 4 : 0;
     // 32-bit resource offsets, with room for the chunk past the batch (the offsets form's three sizes are refused by the C-ABI, for both back-ends, before it gets here)
@@ -693,9 +817,10 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
     items = FR_KNOB("POOL_ITEMS", items);
 #define FR_GP(I, W)                                                                                                                                     \
     if (items == I && win == W) {                                                                                                                       \
+        if (dst.ldm && !((pooled_operand_forms(I, W, W % 4 == 0 && wide) >> operand) & 1u)) return FR_POOL_NO_OPERAND_ARM;                                 \
         if constexpr (W % 4 == 0)                                                                                                                       \
-            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, nullptr, 0, 0u); \
-        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, offsets, n_icols, (unsigned)nnz);   \
+            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, nullptr, 0, 0u, dst); \
+        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, offsets, n_icols, (unsigned)nnz, dst);   \
     }
     FR_GP(4, 2)
     FR_GP(2, 2)

@@ -85,6 +85,22 @@ struct FrPoolDesc {
     uint32_t hots;    // slots of the bag (1 .. FR_POOL_MAX_HOTS) | FR_POOL_DESC_MEAN
 };
 static_assert(sizeof(FrPoolDesc) == 8, "FrPoolDesc must be 8 bytes");
+// Where gather_pooled_kernel stores its folded words, uniform over the launch.  ldm == 0: the item's fp32 record (16 bytes at the word's place in the
+// model's layout).  form 1 / 2 / 3: straight into the chain's feature-major stage-1 operand of `ldm` items, in the chain's operand type -- fp32
+// Xq[K/4][ldm] (16 bytes, a bit copy), bf16 Xh[K/8][ldm] (8 bytes, RNE), e4m3 Xf[KE][ldm] (4 bytes, x scale, saturated); 16-byte elements, element
+// (w >> (form - 1), b) holds word w of item b.  The launch writes the whole region a stage reads: pad items [batch, ldm) and the pad words
+// of the k-rows past the record are zeros.
+constexpr int FR_POOL_NO_OPERAND_ARM = 1;   // frk_gather_pooled: not an error, not a launch
+struct FrPoolDest {
+    unsigned ldm;   // 0: records
+    int code;       // the FR_PD_* fields below, packed by frk_gather_pooled: one scalar register in the kernel instead of four
+};
+// fields of FrPoolDest::code, shared by the launcher and the kernel
+constexpr unsigned FR_PD_FORM_MASK = 3u;                            // bits 0-1: the form (1 fp32, 2 bf16, 3 e4m3)
+constexpr unsigned FR_PD_PAD_SHIFT = 2, FR_PD_PAD_MASK = 63u;       // bits 2-7: pad words behind the record in the operand's k-rows
+constexpr unsigned FR_PD_FOLD_SHIFT = 8, FR_PD_FOLD_MASK = 7u;      // bits 8-10: the fold, FR_PD_FOLD_*
+constexpr unsigned FR_PD_EX_SHIFT = 16;                             // bits 16-31, signed: form 3's X exponent e_x (scale 2^e_x; an arithmetic shift recovers it)
+constexpr unsigned FR_PD_FOLD_SUM = 0u, FR_PD_FOLD_MEAN = 1u, FR_PD_FOLD_WEIGHTED = 2u, FR_PD_FOLD_CSR = 3u, FR_PD_FOLD_CSR_WEIGHTED = 4u;
 
 // One wave-instruction of the item-tile gather (gather_tile_kernel, fr_gather.hip): 64 / n_words items x n_words consecutive
 // 16-byte words of ONE source row each (n_words = 1, 2, 4, 8 or 16: a whole table row, or a power-of-two piece of one).  A record
@@ -433,9 +449,11 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
 // pooled (multi-hot) gather: idx = [batch][pool_cols]; weights = NULL or float [batch][pool_cols] (the weighted fold); bag and mode of word w =
 // pool[w]; fp32 records in the model's layout.  max_hots / wide / any_mean: fr_ctx::pool_*
 // offsets != NULL: the offsets (CSR) form -- offsets = int32 [batch * n_icols + 1], idx / weights = nnz flat entries, pool = fr_ctx::d_pool_csr
+// -> FR_POOL_NO_OPERAND_ARM (nothing launched) when the shape this batch takes has no operand-store arm: the caller writes records and converts them.
+// operand = 1 + the chain's fr_fc_precision (0: records): out = the chain's stage-1 operand of ldm items instead of records (FrPoolDest), e_x = the X exponent of the fp8 chain
 int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &groups, const int32_t *idx, const float *weights, int pool_cols,
                       int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
-                      const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0);
+                      const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0, int operand = 0, int ldm = 0, int e_x = 0);
 int frk_gather_tile(const FrPassDesc *passes, const FrChunkDesc *chunks, int n_chunks, const int32_t *idx, int idx_stride, const float *dense, void *out,
                     int out_stride_words, int batch, int *err_flag, bool dedup, unsigned long long *dup_counter, hipStream_t s);
 int frk_transpose_slices_lp(int precision, const void *gathered, int n_shards, int batch_total, int slice_padded, const int *h_offsets, const int *h_lens,

@@ -87,8 +87,9 @@ int fr_comm_exchange(const fr_comm *c);               /* the current mode (FR_EX
  * column's bag: the first non-empty slot's row word as a bit copy, every further non-empty slot's word added to it in fp32, one add per lane,
  * in ascending slot order; an all-empty bag gives +0.0f.  DENSE words are copied as by the one-hot gather.  With every hots == 1 and no empty
  * slot the records are bit-identical to fr_worker_gather_only's.  Records are fp32 in the model's layout; the FC chain is the one
- * fr_worker_fc_only runs from records, in the context's precision.  Not available (FR_ERR_STATE): sharded contexts, the streaming entry
- * points (their producers stay one-hot).  An index or record buffer of 4000 MiB or more is FR_ERR_INVALID (32-bit buffer offsets). */
+ * fr_worker_fc_only runs from records, in the context's precision.  Not available (FR_ERR_STATE): sharded contexts.  Streaming: the
+ * fr_worker_push_pooled* entry points below; the fused kernels' producers and the host-fed path (fr_worker_push_host / push_staged) stay
+ * one-hot.  An index or record buffer of 4000 MiB or more is FR_ERR_INVALID (32-bit buffer offsets). */
 #define FR_POOL_MAX_HOTS 64
 /* hots[n_cols], n_cols == fr_model_index_cols(fr_ctx_model(ctx)); hots == NULL clears.  Builds the pooled descriptors.
  * FR_ERR_STATE while a worker of the context has work in flight, or on a sharded context.  One-hot entry points are unaffected.
@@ -158,6 +159,34 @@ int fr_worker_submit_pooled_csr_device(fr_worker *w, int batch, const int32_t *d
  * against fr_worker_update_rows is that of the padded pooled calls. */
 int32_t *fr_worker_pool_offsets_ptr(fr_worker *w);
 int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted);
+
+/* Streaming pushes of pooled lookups (additive in ABI 6): fr_worker_push_device for a pooled batch, in the padded and the offsets input form.
+ * Nothing waits: the pooled gather writes the FC chain's first operand itself, in the chain's operand type, and the batch enters the stage
+ * pipeline behind it -- its FC1 shares a launch with FC2 / FC3 / the output layer of the batches pushed before it.  A pooled push always rides the
+ * stage pipeline, also on a context whose one-hot pushes go through the fused kernel (launch groups of 12 or more).
+ *   d_weights NULL: the unweighted fold (SUM / MEAN by the context's modes); non-NULL: the weighted fold (FR_ERR_STATE on a context with a MEAN
+ *   column).  Arguments, ranges and malformed bags: the rules of fr_worker_submit_pooled*_device / fr_worker_submit_pooled_csr_device.
+ *   Scores: those of fr_worker_submit_pooled*_device for the same batch, BIT FOR BIT, in every precision (the same stage kernels over the same
+ *   operand bytes).  fr_worker_sync is the only completion point; the buffer-lifetime rule of fr_worker_push_device applies -- d_idx / d_offsets /
+ *   d_indices / d_weights / d_dense / d_scores stay valid, and d_scores distinct, for every batch still in the pipeline.
+ *   One-hot and pooled pushes may alternate on one worker: batches fr_worker_push_device has queued for a fused launch are launched first (not
+ *   waited for), a later one-hot push that goes fused drains the stage pipeline first.  Order against fr_worker_update_rows is the one stated
+ *   there (a batch's gather is launched by its own push).  fr_ctx_set_pooling / fr_ctx_set_pooling_modes see pushed batches as work in flight.
+ *   An index-range error (or a malformed bag) is FR_ERR_INDEX_RANGE at fr_worker_sync: sticky word, the worker is usable afterwards, every
+ *   well-formed bag of every pushed batch is as specified.
+ *   FR_ERR_STATE: no pooling set, a sharded context, a layout other than FR_LAYOUT_SEMANTIC, host-fed batches still queued in a block (flush
+ *   first, as for fr_worker_update_rows).  The CPU back-end computes a push before it returns.
+ *   Speed, not results: on a bf16 / fp8 chain two shapes of the gather keep the record round trip inside the push (one launch more, the same scores) --
+ *   every bag of ONE slot, and a longest bag of 4 .. 7 slots unless every hots[c] is a multiple of 4 AND d_idx / d_weights are 16-byte aligned (the
+ *   offsets form at those caps always: it assumes 4-byte alignment only).  Keep pooled index rows and weights 16-byte aligned.
+ * fr_worker_push_pooled_device_list: n pushes in one call, stopping at the first error -- the pooled sibling of fr_worker_push_device_list
+ * (padded form; the d_weights / d_dense arrays or any entry of them may be NULL). */
+int fr_worker_push_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights /* NULL: unweighted */, const float *d_dense,
+                                 float *d_scores);
+int fr_worker_push_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz,
+                                     const float *d_weights /* NULL: unweighted */, const float *d_dense, float *d_scores);
+int fr_worker_push_pooled_device_list(fr_worker *w, int n, const int *batch, const int32_t *const *d_idx, const float *const *d_weights,
+                                      const float *const *d_dense, float *const *d_scores);
 
 /* Sparse row updates of the embedding tables (additive in ABI 6): the write side of the lookups.  n listed rows of ONE table: row_ids int32 [n],
  * rows float [n][dim], dense -- row i of `rows` is the new content of table row row_ids[i].  Unlike fr_ctx_upload_table these are not set-up
