@@ -80,6 +80,8 @@ ABI_SYMBOLS = [
     "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr",
     "fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_bank_image_builds",
     "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
+    "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
+    "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
 ]
 
 
@@ -88,7 +90,9 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_ctx_set_pooling_modes", "fr_ctx_pooling_mode", "fr_worker_gather_pooled_weighted", "fr_worker_submit_pooled_weighted_device",
                    "fr_worker_pool_weights_ptr", "fr_worker_submit_pooled_weighted",
                    "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr",
-                   "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list")
+                   "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
+                   "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
+                   "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled")
 
 
 def lib():
@@ -166,6 +170,11 @@ def lib():
         "fr_worker_pool_offsets_ptr": (pi, [vp]), "fr_worker_submit_pooled_csr": (i32, [vp, i32, i32]),
         "fr_worker_update_rows": (i32, [vp, i32, i32, vp, vp]), "fr_ctx_update_rows": (i32, [vp, i32, i32, vp, vp]),
         "fr_ctx_lp_bank_image_builds": (ctypes.c_longlong, [vp]),
+        "fr_ctx_create_sharded_pooled": (i32, [ctypes.POINTER(ModelDesc), i32, i32, i32, pi, pi, i32, ctypes.POINTER(vp)]),
+        "fr_worker_gather_slices_pooled": (i32, [vp, i32, vp, vp, vp, vp, i32]),
+        "fr_worker_gather_slices_pooled_csr": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i32]),
+        "fr_worker_submit_sharded_pooled": (i32, [vp, vp, i32, i32]), "fr_worker_submit_sharded_pooled_csr": (i32, [vp, vp, i32, i32]),
+        "fr_worker_calibrate_fp8_sharded_pooled": (i32, [vp, vp, i32, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -480,10 +489,23 @@ class DeviceBuffer:
 class Context:
     """Device + model + tables + weights; shared by all workers (one per GPU)."""
 
-    def __init__(self, model, device=0, shard_rank=0, n_shards=1):
+    def __init__(self, model, device=0, shard_rank=0, n_shards=1, hots=None, modes=None):
+        """hots (/ modes): pooling stated at creation (fr_ctx_create_sharded_pooled) -- the only way to pool on a sharded context, whose pooling
+        never changes afterwards; the arrays of set_pooling, the same on every rank."""
         self.model = model
         h = ctypes.c_void_p()
-        _check(lib().fr_ctx_create_sharded(model._ptr, device, shard_rank, n_shards, ctypes.byref(h)))
+        if hots is None:
+            if modes is not None:
+                raise FleetRecError(FR_ERR_INVALID, "pooling modes without hots")
+            _check(lib().fr_ctx_create_sharded(model._ptr, device, shard_rank, n_shards, ctypes.byref(h)))
+        else:
+            hh = np.ascontiguousarray(np.asarray(hots, dtype=np.int32).ravel())
+            md = None if modes is None else np.ascontiguousarray(np.asarray(modes, dtype=np.int32).ravel())
+            if md is not None and md.size != hh.size:
+                raise FleetRecError(FR_ERR_INVALID, "%d pooling modes for %d hots" % (md.size, hh.size))
+            pi = ctypes.POINTER(ctypes.c_int32)
+            _check(lib().fr_ctx_create_sharded_pooled(model._ptr, device, shard_rank, n_shards, hh.ctypes.data_as(pi),
+                                                      md.ctypes.data_as(pi) if md is not None else None, int(hh.size), ctypes.byref(h)))
         self._h = h
 
     def close(self):
@@ -721,6 +743,59 @@ class Worker:
         if self.dense is not None:
             self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
         _check(lib().fr_worker_calibrate_fp8_sharded(self._h, comm._h, B))
+
+    # pooled lookups on sharded contexts (Context(..., hots=...)) ------------------------------------
+    def gather_slices_pooled(self, batch, d_idx, d_dense, d_slice, transport, weights=None):
+        """fr_worker_gather_slices_pooled: the pooled slice [batch][slice_padded] in the transport type (asynchronous; follow with sync())."""
+        _check(lib().fr_worker_gather_slices_pooled(self._h, batch, self._ptr(d_idx), self._ptr(weights), self._ptr(d_dense), self._ptr(d_slice), transport))
+
+    def gather_slices_pooled_csr(self, batch, d_offsets, d_indices, nnz, d_dense, d_slice, transport, weights=None):
+        """fr_worker_gather_slices_pooled_csr: the same from the offsets form."""
+        _check(lib().fr_worker_gather_slices_pooled_csr(self._h, batch, self._ptr(d_offsets), self._ptr(d_indices), int(nnz), self._ptr(weights), self._ptr(d_dense),
+                                                        self._ptr(d_slice), transport))
+
+    def load_pooled(self, idx, dense=None, weights=None):
+        """The padded host form of a pooled batch into the pinned buffers: idx int32 [B][P] (+ dense, + weights float32 [B][P]); -> B."""
+        idx = self._pooled_rows(idx)
+        B, P = idx.shape
+        if P > self._pool_cap or (weights is not None and P > self._pool_w_cap):
+            raise FleetRecError(FR_ERR_STATE, "the worker's pooled buffers hold %d columns per item, pooled rows have %d" % (self._pool_cap, P))
+        if B > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(B, P))[:] = idx
+        if weights is not None:
+            np.ctypeslib.as_array(lib().fr_worker_pool_weights_ptr(self._h), shape=(B, P))[:] = self._pooled_weights(weights, idx)
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        return B
+
+    def load_pooled_csr(self, offsets, indices, dense=None, weights=None):
+        """The offsets host form of a pooled batch into the pinned buffers (offsets int32 [B * C + 1], indices int32 [nnz], weights float32 [nnz]); -> B."""
+        B, off, ind, w = self._csr_arrays(offsets, indices, weights)
+        if self.pool_offsets is None or (w is not None and self.pool_weights is None):
+            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker on a context with pooling set")
+        if B > self.max_batch or ind.size > self.max_batch * self._pool_cap:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d / %d indices exceed the worker's buffers" % (B, ind.size))
+        self.pool_offsets[:off.size] = off
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:ind.size] = ind
+        if w is not None:
+            self.pool_weights.reshape(-1)[:w.size] = w
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        return B
+
+    def submit_sharded_pooled(self, comm, batch, weighted=False):
+        """fr_worker_submit_sharded_pooled on the pooled rows already in the pinned buffers (load_pooled; asynchronous, follow with sync())."""
+        _check(lib().fr_worker_submit_sharded_pooled(self._h, comm._h, int(batch), 1 if weighted else 0))
+
+    def submit_sharded_pooled_csr(self, comm, batch, weighted=False):
+        """fr_worker_submit_sharded_pooled_csr on the offsets-form batch already in the pinned buffers (load_pooled_csr)."""
+        _check(lib().fr_worker_submit_sharded_pooled_csr(self._h, comm._h, int(batch), 1 if weighted else 0))
+
+    def calibrate_fp8_sharded_pooled(self, comm, idx, dense=None, weights=None):
+        """fr_worker_calibrate_fp8_sharded_pooled (a synchronous collective: one thread per rank on the host exchange)."""
+        B = self.load_pooled(idx, dense, weights)
+        _check(lib().fr_worker_calibrate_fp8_sharded_pooled(self._h, comm._h, B, 1 if weights is not None else 0))
 
     def submit_device(self, batch, d_idx, d_dense, d_scores):
         _check(lib().fr_worker_submit_device(self._h, batch, self._ptr(d_idx), self._ptr(d_dense), self._ptr(d_scores)))

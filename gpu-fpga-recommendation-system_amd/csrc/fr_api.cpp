@@ -1577,7 +1577,7 @@ static int check_gather_args(fr_worker *w, const int32_t *d_idx, const float *d_
 // fc_only diagnostic: item-major records in the model's layout -> scores (pipeline must be idle)
 static int launch_fc(fr_worker *w, int batch, const float *d_records, float *d_scores) {
     fr_ctx *c = w->ctx;
-    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fc on a sharded ctx needs the all-gathered records (use the sharded driver)");
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fc on a sharded ctx needs the all-gathered records (use the sharded driver: fr_worker_submit_sharded, fr_worker_submit_sharded_pooled)");
     if (c->cpu) {
         frc_fc_chain(c->model.fc, c->d_w, d_records, batch, w->c_scratch, d_scores);
         return FR_OK;
@@ -1736,9 +1736,43 @@ static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *mode
     return FR_OK;
 }
 
+// A sharded context's pooling is stated when the context is created and never changes: every rank of a job must agree on the pooled row layout, and
+// exchange and worker buffers are sized once.  fr_ctx_create_sharded followed by pooling_install -- the descriptors follow the shard's own h_words.
+extern "C" int fr_ctx_create_sharded_pooled(const fr_model_desc *m, int device, int shard_rank, int n_shards, const int32_t *hots, const int32_t *modes, int n_cols, fr_ctx **out) {
+    if (!out) FR_FAIL(FR_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!hots) FR_FAIL(FR_ERR_INVALID, "fr_ctx_create_sharded_pooled: hots is NULL");
+    int rc = fr_model_validate(m);
+    if (rc) return rc;
+    const int cols = fr_model_index_cols(m);
+    if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_create_sharded_pooled: n_cols %d, the model has %d index columns", n_cols, cols);
+    for (int c = 0; c < cols; c++) {
+        if (hots[c] < 1 || hots[c] > FR_POOL_MAX_HOTS) FR_FAIL(FR_ERR_INVALID, "fr_ctx_create_sharded_pooled: hots[%d] = %d outside [1, %d]", c, hots[c], FR_POOL_MAX_HOTS);
+        if (modes && modes[c] != FR_POOL_SUM && modes[c] != FR_POOL_MEAN) FR_FAIL(FR_ERR_INVALID, "fr_ctx_create_sharded_pooled: modes[%d] = %d is no pooling mode", c, modes[c]);
+    }
+    fr_ctx *c = nullptr;
+    rc = fr_ctx_create_sharded(m, device, shard_rank, n_shards, &c);
+    if (rc) return rc;
+    const int ctx_cols = (int)idx_cols(c);
+    if (ctx_cols != cols) {
+        fr_ctx_destroy(c);
+        FR_FAIL(FR_ERR_STATE, "internal: the context has %d index columns, the model %d", ctx_cols, cols);
+    }
+    rc = pooling_install(c, hots, modes);
+    if (rc) {
+        char text[400];
+        snprintf(text, sizeof(text), "%s", fr_last_error());
+        fr_ctx_destroy(c);
+        fr_set_error("%s", text);
+        return rc;
+    }
+    *out = c;
+    return FR_OK;
+}
+
 extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) {
     if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "the pooling of a sharded context (%d shards) is fixed when it is created: fr_ctx_create_sharded_pooled", ctx->n_shards);
     const int cols = (int)idx_cols(ctx);
     if (hots) {
         if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: n_cols %d, the context has %d index columns", n_cols, cols);
@@ -1765,7 +1799,7 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
 
 extern "C" int fr_ctx_set_pooling_modes(fr_ctx *ctx, const int32_t *modes, int n_cols) {
     if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "the pooling of a sharded context (%d shards) is fixed when it is created: fr_ctx_create_sharded_pooled", ctx->n_shards);
     if (ctx->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
     const int cols = (int)idx_cols(ctx);
     if (modes) {
@@ -1791,13 +1825,18 @@ extern "C" int fr_ctx_pooled_index_cols(const fr_ctx *ctx) { return ctx ? ctx->p
 // its three 4000 MiB bounds are checked here, once, for both back-ends
 // operand != 0 (GPU only; 1 + the chain's precision): d_records is the chain's stage-1 operand of ldm items instead (frk_gather_pooled); the call may then
 // return FR_POOL_NO_OPERAND_ARM, with nothing launched
-static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
-                                const int32_t *d_offsets = nullptr, int64_t nnz = 0, int operand = 0, int ldm = 0) {
+// transport != FR_FC_FP32 (GPU only, operand == 0): d_records is the item-major slice [batch][slice_padded] of bf16 / e4m3 elements instead (fr_worker_gather_slices_pooled)
+// On a sharded context (pooling set at creation) the words are the shard's own: what is written is the shard's slice, as by fr_worker_gather_only.
+static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, void *d_records,
+                                const int32_t *d_offsets = nullptr, int64_t nnz = 0, int operand = 0, int ldm = 0, int transport = FR_FC_FP32) {
     fr_ctx *c = w->ctx;
     const int out_words = operand ? c->model.fc[0] / 4 : c->slice_padded / 4;
     const bool csr = d_offsets != nullptr;   // (the offsets-form entry points refuse a NULL d_offsets themselves)
-    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
-    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    const bool lp_slice = transport != FR_FC_FP32;
+    if (c->pool_cols <= 0)
+        FR_FAIL(FR_ERR_STATE, c->n_shards > 1 ? "no pooling is set on the sharded context: create it with fr_ctx_create_sharded_pooled" : "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (lp_slice && c->cpu) FR_FAIL(FR_ERR_STATE, "the CPU back-end gathers fp32 records only");
+    if (lp_slice) operand = 1 + transport;   // the item-major form of the operand-store arms (frk_gather_pooled)
     if (csr) {
         if (nnz < 0) FR_FAIL(FR_ERR_INVALID, "nnz %lld is negative", (long long)nnz);
         if (nnz > 0 && !d_idx) FR_FAIL(FR_ERR_INVALID, "d_indices is NULL with nnz %lld", (long long)nnz);
@@ -1820,13 +1859,14 @@ static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, c
     if (csr) {
         if (nnz == 0) d_idx = nullptr;   // (no entry is ever read: the resource is empty)
         if (c->cpu)
-            return frc_gather_pooled(c->h_words.data(), c->h_pool_csr.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err, d_offsets, (int)idx_cols(c), nnz);
+            return frc_gather_pooled(c->h_words.data(), c->h_pool_csr.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, static_cast<float *>(d_records), batch, &w->c_err, d_offsets,
+                                     (int)idx_cols(c), nnz);
         return frk_gather_pooled(c->d_words, c->d_pool_csr, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, false, c->pool_any_mean, d_dense, d_records, batch,
-                                 w->d_err, w->stream, out_words, d_offsets, (int)idx_cols(c), nnz, operand, ldm, c->f8_e_act[0]);
+                                 w->d_err, w->stream, out_words, d_offsets, (int)idx_cols(c), nnz, operand, ldm, c->f8_e_act[0], lp_slice);
     }
-    if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, d_records, batch, &w->c_err);
+    if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, static_cast<float *>(d_records), batch, &w->c_err);
     return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, c->pool_wide, c->pool_any_mean, d_dense, d_records, batch,
-                             w->d_err, w->stream, out_words, nullptr, 0, 0, operand, ldm, c->f8_e_act[0]);
+                             w->d_err, w->stream, out_words, nullptr, 0, 0, operand, ldm, c->f8_e_act[0], lp_slice);
 }
 
 static int gather_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
@@ -1854,6 +1894,8 @@ extern "C" int fr_worker_gather_pooled_weighted(fr_worker *w, int batch, const i
 static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores,
                               const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
     if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
+    if (w->ctx->n_shards > 1)   // (before the gather is enqueued: launch_fc would refuse the shard behind it)
+        FR_FAIL(FR_ERR_STATE, "a pooled submit on a sharded ctx: the chain needs the all-gathered slices (fr_worker_submit_sharded_pooled on a context created by fr_ctx_create_sharded_pooled)");
     int rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records, d_offsets, nnz);
     if (rc) return rc;
     w->in_flight = true;   // the gather is enqueued whatever the chain's launch says
@@ -1944,6 +1986,33 @@ extern "C" int fr_worker_gather_slices(fr_worker *w, int batch, const int32_t *d
     if (rc) return rc;
     w->in_flight = true;
     return FR_OK;
+}
+
+// The pooled siblings: the slice of a pooled batch (padded or offsets form) in the transport type.  fp32 is the record arm of gather_pooled_kernel (a
+// shard's words place themselves in its slice); bf16 / e4m3 are the item-major form of its operand-store arms, rounded as store_word rounds.
+static int gather_slices_pooled_impl(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_idx, int64_t nnz, const float *d_weights, const float *d_dense, void *d_slice,
+                                     int transport) {
+    int rc = check_ready(w, batch, true, false);
+    if (rc) return rc;
+    if (!d_slice) FR_FAIL(FR_ERR_INVALID, "d_slice is NULL");
+    if (transport != FR_FC_FP32 && transport != FR_FC_BF16 && transport != FR_FC_FP8) FR_FAIL(FR_ERR_INVALID, "bad transport %d", transport);
+    if (transport != FR_FC_FP32 && w->ctx->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "low-precision transport: SEMANTIC layout only");
+    FR_SET_DEVICE(w->ctx);
+    rc = launch_gather_pooled(w, batch, d_idx, d_weights, d_weights != nullptr, d_dense, d_slice, d_offsets, nnz, 0, 0, transport);
+    if (rc) return rc;
+    keep_kernel(w);
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_worker_gather_slices_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, void *d_slice, int transport) {
+    return gather_slices_pooled_impl(w, batch, nullptr, d_idx, 0, d_weights, d_dense, d_slice, transport);
+}
+
+extern "C" int fr_worker_gather_slices_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
+                                                  void *d_slice, int transport) {
+    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
+    return gather_slices_pooled_impl(w, batch, d_offsets, d_indices, nnz, d_weights, d_dense, d_slice, transport);
 }
 
 // ... and the receiving side: d_gathered = [n_shards][batch_total][slice_padded] elements of the transport type.  The transport must
@@ -2111,8 +2180,9 @@ static int push_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const
     if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
     fr_ctx *c = w->ctx;
     const bool weighted = d_weights != nullptr;
-    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "pooled lookups are not available on a sharded context");
-    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (c->pool_cols <= 0)
+        FR_FAIL(FR_ERR_STATE, c->n_shards > 1 ? "no pooling is set on the sharded context: create it with fr_ctx_create_sharded_pooled" : "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "a pooled push on a sharded ctx: the chain needs the all-gathered slices (fr_worker_submit_sharded_pooled)");
     if (c->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "a pooled push needs a SEMANTIC-layout context");
     if (c->cpu) {   // the CPU back-end has nothing to queue behind: the batch is computed before the call returns
         rc = submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores, d_offsets, nnz);

@@ -427,9 +427,23 @@ __device__ __forceinline__ void gather_pooled_body(const FrWordDesc *__restrict_
     // word's 16 >> sh bytes at (w & mask) inside it; both are `blk + b * ostride`.  The operand's zeros (pad k-rows, chunks of pad items) are stored by
     // gather_pooled_operand_zeros before the fold, so that the fold keeps two scalars more than the record arm (dst.ldm, dst.code)
     constexpr unsigned sh = OPND ? (unsigned)OPND - 1u : 0u;   // OPND = the operand's form (FrPoolDest), fixed per arm
-    const unsigned blk = OPND ? ((dst_off >> sh) * dst.ldm) * 16u + (dst_off & ((1u << sh) - 1u)) * (16u >> sh) : (dst_blk * (unsigned)batch + dst_off) * 16u;
-    const unsigned ostride = OPND ? 16u : dst_stride * 16u;
-    unsigned lim = OPND ? dst.ldm : (unsigned)batch;   // items the stores cover: the operand's pad items [batch, ldm) are stored as zeros
+    // FR_PD_ROWS (forms 2 / 3, uniform over the launch): the item-major low-precision slice of a shard -- item b's row of dst.ldm words of 16 >> sh bytes,
+    // the word at its dst_off inside the row; only the batch's items are stored
+    // Decided in vector registers by a mask, not by a scalar branch or select: the folds leave no scalar register for the choice.  With a k-row
+    // stride of ONE item the feature-major formula below is dst_off * (16 >> sh), the word's place in the row.
+    unsigned rmask = 0u;   // all ones in the item-major form
+    if constexpr (OPND >= 2) {
+        rmask = (unsigned)dst.code;
+        asm volatile("" : "+v"(rmask));
+        rmask = 0u - ((rmask >> 11) & 1u);
+        static_assert(FR_PD_ROWS == 1u << 11, "the shift above");
+    }
+    unsigned ldmv = dst.ldm;
+    if constexpr (OPND >= 2) asm volatile("" : "+v"(ldmv));
+    const unsigned kstride = OPND >= 2 ? (ldmv & ~rmask) | (1u & rmask) : dst.ldm;
+    const unsigned blk = OPND ? ((dst_off >> sh) * kstride) * 16u + (dst_off & ((1u << sh) - 1u)) * (16u >> sh) : (dst_blk * (unsigned)batch + dst_off) * 16u;
+    const unsigned ostride = OPND >= 2 ? (16u & ~rmask) | ((ldmv << (4u - sh)) & rmask) : OPND ? 16u : dst_stride * 16u;
+    unsigned lim = OPND >= 2 ? (ldmv & ~rmask) | ((unsigned)batch & rmask) : OPND ? dst.ldm : (unsigned)batch;   // items the stores cover: the operand's pad items [batch, ldm) are stored as zeros
     float scale = OPND == 3 ? __builtin_ldexpf(1.0f, dst.code >> FR_PD_EX_SHIFT) : 1.0f;   // 2^e_x, exact
     // OPND: both in vector registers from here on (the half passes leave some; the fold's masks leave no scalar one)
     if constexpr (OPND != 0) asm volatile("" : "+v"(lim));
@@ -717,6 +731,8 @@ __global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pool
         // chain's stage-1 operand.  The operand's zeros come first, while the fold's registers are still free; a chunk of pad items only (uniform
         // over the workgroup) has no fold.  (The launcher sends no form here that the instantiation has no arm for.)
         if constexpr (FORMS != 0u) {
+            // (the item-major slice form, FR_PD_ROWS, stores no zeros and needs no test here: its code names no pad word and its grid ends with the
+            // batch, so the call below stores nothing and returns false)
             if (gather_pooled_operand_zeros<ITEMS>(words, wd, (unsigned)groups.start[n_groups], b0, out, batch, out_bytes, dst)) return;
             const unsigned form = (unsigned)dst.code & FR_PD_FORM_MASK;
             if constexpr ((FORMS & 2u) != 0u)
@@ -758,7 +774,8 @@ template <int ITEMS, int WIN, bool WIDE>
 static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, const float *weights, int pool_cols,
                                 const float *dense, void *out, int batch, int *err_flag, unsigned out_bytes, bool any_mean, hipStream_t s,
                                 const int32_t *offsets, int n_icols, unsigned nnz, const FrPoolDest &dst) {
-    const int n_chunks = ((dst.ldm ? (int)dst.ldm : batch) + ITEMS - 1) / ITEMS;   // the operand form covers the pad items [batch, ldm) too
+    const bool feature_major = dst.ldm && !((unsigned)dst.code & FR_PD_ROWS);
+    const int n_chunks = ((feature_major ? (int)dst.ldm : batch) + ITEMS - 1) / ITEMS;   // the operand form covers the pad items [batch, ldm) too
     const int bx = groups.max_words >= 256 ? 256 : ((groups.max_words + 63) / 64) * 64;
     dim3 grid(n_groups * n_chunks, (groups.max_words + bx - 1) / bx);
     gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, any_mean ? 1 : 0,
@@ -774,14 +791,22 @@ static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool,
 // context's offsets-form descriptors (column and cap per word); the narrow instantiation of the window always (4-byte alignment only).
 int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, const float *weights, int pool_cols,
                       int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
-                      const int32_t *offsets, int n_icols, long long nnz, int operand, int ldm, int e_x) {
+                      const int32_t *offsets, int n_icols, long long nnz, int operand, int ldm, int e_x, bool item_major) {
     if (n_words <= 0 || batch <= 0) return FR_OK;
     if (out_words < n_words) out_words = n_words;
     // operand = 1 + the chain's fr_fc_precision (1 fp32, 2 bf16, 3 e4m3): `out` is the chain's feature-major stage-1 operand of ldm items and out_words record words
     // (K / 4) -- Xq[K/4][ldm], Xh[K/8][ldm] or Xf[KE][ldm] in 16-byte elements -- written whole, pad items and pad k-rows as zeros
     FrPoolDest dst{};
     size_t out_bytes = (size_t)batch * (size_t)out_words * 16;
-    if (operand) {
+    if (item_major) {
+        // the item-major low-precision slice (FR_PD_ROWS): [batch][out_words] words of 8 (bf16) or 4 (e4m3) bytes; fp32 slices are the record arm's layout already
+        if (operand != 2 && operand != 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no item-major form %d", operand);
+        if (e_x < -126 || e_x > 127) FR_FAIL(FR_ERR_INVALID, "pooled gather: X exponent %d", e_x);
+        dst.ldm = (unsigned)out_words;
+        const unsigned fold = offsets ? (weights ? FR_PD_FOLD_CSR_WEIGHTED : FR_PD_FOLD_CSR) : weights ? FR_PD_FOLD_WEIGHTED : any_mean ? FR_PD_FOLD_MEAN : FR_PD_FOLD_SUM;
+        dst.code = operand | (int)FR_PD_ROWS | (int)(fold << FR_PD_FOLD_SHIFT) | (int)((unsigned)(operand == 3 ? e_x : 0) << FR_PD_EX_SHIFT);
+        out_bytes = (size_t)batch * (size_t)out_words * (16u >> (operand - 1));   // the resource ends with the batch: the chunk past it is dropped
+    } else if (operand) {
         if (ldm < batch || ldm % 32) FR_FAIL(FR_ERR_INVALID, "pooled gather: operand of %d items for a batch of %d", ldm, batch);
         if (operand < 1 || operand > 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no operand form %d", operand);
         dst.ldm = (unsigned)ldm;
@@ -815,6 +840,12 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
     int items = win >= 16 ? 1 : max_hots >= 2 ? 2 : 4;
     win = FR_KNOB("POOL_WIN", win);
     items = FR_KNOB("POOL_ITEMS", items);
+    if (item_major && !((pooled_operand_forms(items, win, win % 4 == 0 && wide) >> operand) & 1u)) {
+        // <4, 2, false> and <2, 4, false> carry no bf16 / e4m3 arm: the slice takes the neighbouring shape that does -- any shape folds any bag with the
+        // same bits (a longest bag of 1: a window of 2 x 2 items; of 4 .. 7 in the narrow form: a window of 8 x 2 items)
+        if (items == 4 && win == 2) items = 2;
+        else if (items == 2 && win == 4) win = 8;
+    }
 #define FR_GP(I, W)                                                                                                                                     \
     if (items == I && win == W) {                                                                                                                       \
         if (dst.ldm && !((pooled_operand_forms(I, W, W % 4 == 0 && wide) >> operand) & 1u)) return FR_POOL_NO_OPERAND_ARM;                                 \

@@ -92,13 +92,17 @@ static_assert(sizeof(FrPoolDesc) == 8, "FrPoolDesc must be 8 bytes");
 // of the k-rows past the record are zeros.
 constexpr int FR_POOL_NO_OPERAND_ARM = 1;   // frk_gather_pooled: not an error, not a launch
 struct FrPoolDest {
-    unsigned ldm;   // 0: records
+    unsigned ldm;   // 0: records; FR_PD_ROWS: 16-byte words per item of the item-major destination
     int code;       // the FR_PD_* fields below, packed by frk_gather_pooled: one scalar register in the kernel instead of four
 };
 // fields of FrPoolDest::code, shared by the launcher and the kernel
 constexpr unsigned FR_PD_FORM_MASK = 3u;                            // bits 0-1: the form (1 fp32, 2 bf16, 3 e4m3)
 constexpr unsigned FR_PD_PAD_SHIFT = 2, FR_PD_PAD_MASK = 63u;       // bits 2-7: pad words behind the record in the operand's k-rows
 constexpr unsigned FR_PD_FOLD_SHIFT = 8, FR_PD_FOLD_MASK = 7u;      // bits 8-10: the fold, FR_PD_FOLD_*
+// bit 11: the ITEM-MAJOR destination of forms 2 / 3 -- a shard's low-precision slice [batch][ldm words] (fr_worker_gather_slices_pooled): `ldm` is then
+// the destination's 16-byte-word count per item (slice_padded / 4), word w of item b goes to b * ldm * (16 >> sh) + w * (16 >> sh) bytes, nothing is
+// zero-filled and no item past the batch is written
+constexpr unsigned FR_PD_ROWS = 1u << 11;
 constexpr unsigned FR_PD_EX_SHIFT = 16;                             // bits 16-31, signed: form 3's X exponent e_x (scale 2^e_x; an arithmetic shift recovers it)
 constexpr unsigned FR_PD_FOLD_SUM = 0u, FR_PD_FOLD_MEAN = 1u, FR_PD_FOLD_WEIGHTED = 2u, FR_PD_FOLD_CSR = 3u, FR_PD_FOLD_CSR_WEIGHTED = 4u;
 
@@ -451,9 +455,11 @@ int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &group
 // offsets != NULL: the offsets (CSR) form -- offsets = int32 [batch * n_icols + 1], idx / weights = nnz flat entries, pool = fr_ctx::d_pool_csr
 // -> FR_POOL_NO_OPERAND_ARM (nothing launched) when the shape this batch takes has no operand-store arm: the caller writes records and converts them.
 // operand = 1 + the chain's fr_fc_precision (0: records): out = the chain's stage-1 operand of ldm items instead of records (FrPoolDest), e_x = the X exponent of the fp8 chain
+// item_major (operand 2 / 3 only; ldm unused): out = the item-major low-precision slice [batch][out_words] of 8- / 4-byte words instead (FR_PD_ROWS); a shape
+// without the arm is replaced by its neighbour, so the call never returns FR_POOL_NO_OPERAND_ARM
 int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &groups, const int32_t *idx, const float *weights, int pool_cols,
                       int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
-                      const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0, int operand = 0, int ldm = 0, int e_x = 0);
+                      const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0, int operand = 0, int ldm = 0, int e_x = 0, bool item_major = false);
 int frk_gather_tile(const FrPassDesc *passes, const FrChunkDesc *chunks, int n_chunks, const int32_t *idx, int idx_stride, const float *dense, void *out,
                     int out_stride_words, int batch, int *err_flag, bool dedup, unsigned long long *dup_counter, hipStream_t s);
 int frk_transpose_slices_lp(int precision, const void *gathered, int n_shards, int batch_total, int slice_padded, const int *h_offsets, const int *h_lens,

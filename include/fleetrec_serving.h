@@ -87,12 +87,12 @@ int fr_comm_exchange(const fr_comm *c);               /* the current mode (FR_EX
  * column's bag: the first non-empty slot's row word as a bit copy, every further non-empty slot's word added to it in fp32, one add per lane,
  * in ascending slot order; an all-empty bag gives +0.0f.  DENSE words are copied as by the one-hot gather.  With every hots == 1 and no empty
  * slot the records are bit-identical to fr_worker_gather_only's.  Records are fp32 in the model's layout; the FC chain is the one
- * fr_worker_fc_only runs from records, in the context's precision.  Not available (FR_ERR_STATE): sharded contexts.  Streaming: the
+ * fr_worker_fc_only runs from records, in the context's precision.  Sharded contexts: pooling is stated at creation (fr_ctx_create_sharded_pooled, below), never by fr_ctx_set_pooling.  Streaming: the
  * fr_worker_push_pooled* entry points below; the fused kernels' producers and the host-fed path (fr_worker_push_host / push_staged) stay
  * one-hot.  An index or record buffer of 4000 MiB or more is FR_ERR_INVALID (32-bit buffer offsets). */
 #define FR_POOL_MAX_HOTS 64
 /* hots[n_cols], n_cols == fr_model_index_cols(fr_ctx_model(ctx)); hots == NULL clears.  Builds the pooled descriptors.
- * FR_ERR_STATE while a worker of the context has work in flight, or on a sharded context.  One-hot entry points are unaffected.
+ * FR_ERR_STATE while a worker of the context has work in flight, or on a sharded context (its pooling is fixed at creation).  One-hot entry points are unaffected.
  * Like the other fr_ctx_set_* calls it is not to be raced against calls on the context's workers. */
 int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols);
 int fr_ctx_pooled_index_cols(const fr_ctx *ctx);          /* P; 0 when no pooling is set */
@@ -109,7 +109,7 @@ int fr_worker_submit_pooled(fr_worker *w, int batch);
  * one IEEE fp32 division, correctly rounded, per lane, n converted exactly; n == 1 leaves the word the bit copy it is (no division), n == 0
  * gives +0.0f.  DENSE words are never divided.  MEAN takes effect through the unweighted pooled entry points above.
  * modes[n_cols], n_cols == fr_model_index_cols; modes == NULL makes every column SUM again, and so does every fr_ctx_set_pooling (also with
- * NULL).  FR_ERR_STATE when no pooling is set, on a sharded context, or while a worker of the context has work in flight (the rule of
+ * NULL).  FR_ERR_STATE when no pooling is set, on a sharded context (its modes are fixed at creation), or while a worker of the context has work in flight (the rule of
  * fr_ctx_set_pooling); FR_ERR_INVALID for a wrong n_cols or an unknown mode.  The pooled descriptors are rebuilt and uploaded again. */
 #define FR_POOL_SUM 0
 #define FR_POOL_MEAN 1
@@ -123,7 +123,7 @@ int fr_ctx_pooling_mode(const fr_ctx *ctx, int col);      /* the mode of index c
  * every result that is not a NaN (a NaN result is a NaN of unspecified payload); with every weight 1.0f the records equal the unweighted ones
  * bit for bit wherever no row word is a NaN.  Weights are legal only while every column's mode is FR_POOL_SUM: FR_ERR_STATE on a context
  * with a MEAN column.  d_weights == NULL is FR_ERR_INVALID.  Index-range errors, the 4000 MiB bound (the weight array is as large as the index
- * rows) and the sharded refusal are those of the unweighted calls, which behave exactly as before. */
+ * rows) and the behaviour on a sharded context are those of the unweighted calls, which behave exactly as before. */
 int fr_worker_gather_pooled_weighted(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_records);
 int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores);
 /* Host form: indices in fr_worker_idx_ptr, weights in fr_worker_pool_weights_ptr -- pinned float [max_batch][P] (host memory on the CPU
@@ -147,7 +147,7 @@ int fr_worker_submit_pooled_weighted(fr_worker *w, int batch);
  * and the record buffer is read or written.
  * nnz == 0 is legal (indices / weights may then be NULL).  FR_ERR_INVALID: nnz < 0, offsets == NULL, indices == NULL with nnz > 0, or
  * (batch * C + 1) * 4, nnz * 4 or the record bytes reaching 4000 MiB (32-bit buffer offsets).  FR_ERR_STATE: weights on a context with a MEAN
- * column, no pooling set, a sharded context -- the rules of the padded calls.  weights == NULL means unweighted: one entry point per shape. */
+ * column, no pooling set, a submit on a sharded context -- the rules of the padded calls.  weights == NULL means unweighted: one entry point per shape. */
 int fr_worker_gather_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz,
                                 const float *d_weights /* NULL: unweighted */, const float *d_dense, float *d_records);
 int fr_worker_submit_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz,
@@ -174,7 +174,7 @@ int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted);
  *   there (a batch's gather is launched by its own push).  fr_ctx_set_pooling / fr_ctx_set_pooling_modes see pushed batches as work in flight.
  *   An index-range error (or a malformed bag) is FR_ERR_INDEX_RANGE at fr_worker_sync: sticky word, the worker is usable afterwards, every
  *   well-formed bag of every pushed batch is as specified.
- *   FR_ERR_STATE: no pooling set, a sharded context, a layout other than FR_LAYOUT_SEMANTIC, host-fed batches still queued in a block (flush
+ *   FR_ERR_STATE: no pooling set, a sharded context (fr_worker_submit_sharded_pooled is its step), a layout other than FR_LAYOUT_SEMANTIC, host-fed batches still queued in a block (flush
  *   first, as for fr_worker_update_rows).  The CPU back-end computes a push before it returns.
  *   Speed, not results: on a bf16 / fp8 chain two shapes of the gather keep the record round trip inside the push (one launch more, the same scores) --
  *   every bag of ONE slot, and a longest bag of 4 .. 7 slots unless every hots[c] is a multiple of 4 AND d_idx / d_weights are 16-byte aligned (the
@@ -187,6 +187,47 @@ int fr_worker_push_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_o
                                      const float *d_weights /* NULL: unweighted */, const float *d_dense, float *d_scores);
 int fr_worker_push_pooled_device_list(fr_worker *w, int n, const int *batch, const int32_t *const *d_idx, const float *const *d_weights,
                                       const float *const *d_dense, float *const *d_scores);
+
+/* Pooled lookups on table-sharded contexts (additive in ABI 6).  A sharded context's pooling is fixed WHEN THE CONTEXT IS CREATED and cannot be changed
+ * afterwards: every rank of a job must agree on the pooled row layout, exchange and worker buffers are sized once, and no rank may re-describe its bags
+ * while a peer is inside a step.  fr_ctx_create_sharded_pooled is fr_ctx_create_sharded followed by the installation of the pooled descriptors, which
+ * follow the shard's own words.  hots / modes (NULL: every column SUM) / n_cols have the length, range and meaning of fr_ctx_set_pooling[_modes]: the
+ * GLOBAL index columns of the model's index mode, the same arrays on every rank (FR_ERR_INVALID for a wrong n_cols, a NULL hots, a value out of range:
+ * no context is returned).  The pooled index row of an item is the whole [P] row on every rank, exactly as every rank receives the whole one-hot index
+ * row; a shard reads only the bags of its own words.  n_shards == 1 gives a plain context with pooling set.  On the resulting context
+ * fr_ctx_set_pooling / fr_ctx_set_pooling_modes keep returning FR_ERR_STATE when n_shards > 1, the getters answer, one-hot entry points are unaffected and
+ * workers get the pooled buffer sizes.  The existing pooled entry points then behave as their one-hot siblings do on a shard: fr_worker_gather_pooled*
+ * writes the shard's fp32 slice [batch][slice_padded] as fr_worker_gather_only does; fr_worker_submit_pooled* and fr_worker_push_pooled* stay
+ * FR_ERR_STATE (the chain needs the all-gathered slices), with nothing enqueued.  A sharded context created WITHOUT pooling answers as before. */
+int fr_ctx_create_sharded_pooled(const fr_model_desc *m, int device, int shard_rank, int n_shards, const int32_t *hots, const int32_t *modes /* NULL: every column SUM */,
+                                 int n_cols, fr_ctx **out);
+/* The pooled siblings of fr_worker_gather_slices: [batch][slice_padded] elements of `transport` (FR_FC_FP32, FR_FC_BF16, FR_FC_FP8 = e4m3 of x * 2^e of the
+ * context's X exponent), item-major; every element is the pooled fold defined above (SUM, MEAN, weighted; the offsets form with its malformed-bag rules),
+ * rounded with the one-hot slice gather's own rounding.  Legal on an unsharded context too, where the slice is the whole record.  Nothing past
+ * batch x slice_padded elements is written.  Arguments, ranges, alignment and the 4000 MiB bounds: fr_worker_gather_pooled[_weighted] /
+ * fr_worker_gather_pooled_csr (d_weights NULL: unweighted); transport: the rules of fr_worker_gather_slices (the CPU back-end: fp32 only, FR_ERR_STATE
+ * otherwise).  Speed, not results: with a low-precision transport a longest bag of ONE slot, and one of 4 .. 7 slots in the narrow form (see the
+ * streaming pushes), run through the neighbouring shape of the gather kernel that carries the store (fr_worker_last_kernel names it). */
+int fr_worker_gather_slices_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights /* NULL: unweighted */, const float *d_dense, void *d_slice,
+                                   int transport);
+int fr_worker_gather_slices_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
+                                       void *d_slice, int transport);
+/* fr_worker_submit_sharded with its first line replaced by the pooled slice gather: slice gather (pooled) -> exchange -> FC on this rank's items ->
+ * score all-gather; both exchange modes, all three transports, the uneven item split, the status words, the bounded wait and the byte accounting of
+ * fr_comm_exchange_bytes are those of fr_worker_submit_sharded.  Inputs are the host forms of the pooled calls: indices in fr_worker_idx_ptr ([batch][P];
+ * the offsets form: flat), weights in fr_worker_pool_weights_ptr when weighted != 0, offsets in fr_worker_pool_offsets_ptr (offsets[0] != 0 or nnz =
+ * offsets[batch * C] outside [0, batch x P]: FR_ERR_INVALID before anything is enqueued).  The index entries are copied to the worker's device index
+ * buffer (sized at worker creation); the device reads the pinned WEIGHTS and OFFSETS IN PLACE, so all the worker's pinned buffers stay untouched until
+ * fr_worker_sync has returned.  Errors found before anything is enqueued (kind (1) of the step's failure protocol, the communicator stays usable): no
+ * pooling on the context, weighted with a MEAN column, a worker without the pooled buffers -- all FR_ERR_STATE.  An index-range error or a malformed bag is
+ * reported as the one-hot step reports an out-of-range index: FR_ERR_INDEX_RANGE at fr_worker_sync of the rank(s) whose words read it; every rank's step
+ * completes. */
+int fr_worker_submit_sharded_pooled(fr_worker *w, fr_comm *comm, int batch, int weighted);
+int fr_worker_submit_sharded_pooled_csr(fr_worker *w, fr_comm *comm, int batch, int weighted);
+/* fr_worker_calibrate_fp8_sharded on a pooled batch (padded host form): the fp32 slices are pooled, so the activation exponents see the bags -- a SUM over
+ * a 16-slot bag can be many times a single row, and a job calibrated on one-hot rows would clip its pooled operand at +-448.  A synchronous collective
+ * (one thread per rank on the host exchange); identical exponents on every rank. */
+int fr_worker_calibrate_fp8_sharded_pooled(fr_worker *w, fr_comm *comm, int batch, int weighted);
 
 /* Sparse row updates of the embedding tables (additive in ABI 6): the write side of the lookups.  n listed rows of ONE table: row_ids int32 [n],
  * rows float [n][dim], dense -- row i of `rows` is the new content of table row row_ids[i].  Unlike fr_ctx_upload_table these are not set-up
