@@ -28,6 +28,7 @@ SEG_TABLE, SEG_COPY, SEG_DENSE = 0, 1, 2
 GATHER_WORD_MAJOR, GATHER_ITEM_TILE, GATHER_ITEM_TILE_DEDUP, GATHER_ITEM_TILE_DEDUP_COUNT, GATHER_WORD_MAJOR_ONE_CHUNK = 0, 1, 2, 3, 4
 EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step's slices travel (Comm.set_exchange)
 POOL_MAX_HOTS = 64   # FR_POOL_MAX_HOTS (fleetrec_serving.h): slots per bag of a pooled lookup
+TOPK_MAX_K = 256   # FR_TOPK_MAX_K (fleetrec_serving.h): the largest k of a top-K ranking
 POOL_SUM, POOL_MEAN = 0, 1   # FR_POOL_SUM / FR_POOL_MEAN: the pooling mode of an index column (Context.set_pooling(hots, modes))
 ABI_VERSION = 6   # include/fleetrec.h FR_ABI_VERSION this binding was written against
 MEM_CLASS_NAMES = {0: "HBM", 1: "DDR", 2: "PLRAM"}
@@ -82,6 +83,7 @@ ABI_SYMBOLS = [
     "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
     "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
     "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
+    "fr_worker_topk_device", "fr_worker_topk",
 ]
 
 
@@ -92,7 +94,8 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_gather_pooled_csr", "fr_worker_submit_pooled_csr_device", "fr_worker_pool_offsets_ptr", "fr_worker_submit_pooled_csr",
                    "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
                    "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
-                   "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled")
+                   "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
+                   "fr_worker_topk_device", "fr_worker_topk")
 
 
 def lib():
@@ -175,6 +178,7 @@ def lib():
         "fr_worker_gather_slices_pooled_csr": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i32]),
         "fr_worker_submit_sharded_pooled": (i32, [vp, vp, i32, i32]), "fr_worker_submit_sharded_pooled_csr": (i32, [vp, vp, i32, i32]),
         "fr_worker_calibrate_fp8_sharded_pooled": (i32, [vp, vp, i32, i32]),
+        "fr_worker_topk_device": (i32, [vp, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_topk": (i32, [vp, i32, i32, vp, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -1107,6 +1111,76 @@ class Worker:
             for b in (d_off, d_ind, d_w, d_dense, d_rec):
                 if b is not None:
                     b.free()
+
+    # segmented top-K ranking of scores (fr_worker_topk_device / fr_worker_topk) ------------------------------------------------
+    def topk_device(self, n, d_scores, k, d_top_idx, d_top_scores=None, d_seg_offsets=None, n_seg=1):
+        """fr_worker_topk_device: ranks the n device scores in n_seg segments (d_seg_offsets int32 [n_seg + 1]; None: one segment [0, n)) on the
+        worker's stream, behind everything submitted or pushed before; d_top_idx int32 [n_seg][k] (positions inside the segment, -1 past its
+        length), d_top_scores float32 [n_seg][k] or None.  Asynchronous: sync() is the completion point, the buffers stay valid until then."""
+        _check(lib().fr_worker_topk_device(self._h, int(n), self._ptr(d_scores), int(n_seg), self._ptr(d_seg_offsets), int(k), self._ptr(d_top_idx), self._ptr(d_top_scores)))
+
+    def _topk_host(self, B, k, seg_offsets):
+        """fr_worker_topk on the host-form batch in flight, then sync() -> (idx int32 [n_seg][k], scores float32 [n_seg][k])"""
+        off = None if seg_offsets is None else np.ascontiguousarray(np.asarray(seg_offsets, dtype=np.int32).reshape(-1))
+        n_seg = 1 if off is None else off.size - 1
+        out_i, out_s = np.empty((max(n_seg, 0), int(k)), np.int32), np.empty((max(n_seg, 0), int(k)), np.float32)
+        try:
+            _check(lib().fr_worker_topk(self._h, B, n_seg, None if off is None else off.ctypes.data_as(ctypes.c_void_p), int(k),
+                                        out_i.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
+        except FleetRecError:
+            try:
+                self.sync()   # the batch that was submitted is not left in flight
+            except FleetRecError:
+                pass
+            raise
+        self.sync()
+        return out_i, out_s
+
+    def infer_topk(self, idx, k, seg_offsets=None, dense=None):
+        """infer() with the ranking on the device: idx int32 [B][idx_cols] (+ dense) -> (positions int32 [n_seg][k], scores float32 [n_seg][k]) of the
+        batch's scores ranked in the segments seg_offsets int32 [n_seg + 1] describes (None: the whole batch is one segment)."""
+        idx = np.asarray(idx, dtype=np.int32).reshape(len(idx), -1)
+        B = idx.shape[0]
+        self.idx[:B] = idx
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        self.submit(B)
+        return self._topk_host(B, k, seg_offsets)
+
+    def infer_pooled_topk(self, idx, k, seg_offsets=None, dense=None, weights=None):
+        """infer_pooled() with the ranking on the device (arguments of infer_pooled; k / seg_offsets / result of infer_topk)."""
+        idx = self._pooled_rows(idx)
+        B, P = idx.shape
+        if P > self._pool_cap or (weights is not None and P > self._pool_w_cap):
+            raise FleetRecError(FR_ERR_STATE, "the worker's index buffer holds %d columns per item, pooled rows have %d: create the worker "
+                                "after Context.set_pooling" % (self._pool_cap, P))
+        if B > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(B, P))[:] = idx
+        if weights is not None:
+            np.ctypeslib.as_array(lib().fr_worker_pool_weights_ptr(self._h), shape=(B, P))[:] = self._pooled_weights(weights, idx)
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        self.submit_pooled(B, weighted=weights is not None)
+        return self._topk_host(B, k, seg_offsets)
+
+    def infer_pooled_csr_topk(self, offsets, indices, k, seg_offsets=None, dense=None, weights=None):
+        """infer_pooled_csr() with the ranking on the device (arguments of infer_pooled_csr; k / seg_offsets / result of infer_topk)."""
+        B, off, ind, w = self._csr_arrays(offsets, indices, weights)
+        if self.pool_offsets is None or (w is not None and self.pool_weights is None):
+            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after Context.set_pooling")
+        if B > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
+        if ind.size > self.max_batch * self._pool_cap:
+            raise FleetRecError(FR_ERR_INVALID, "%d indices exceed the worker's index buffer (%d x %d)" % (ind.size, self.max_batch, self._pool_cap))
+        self.pool_offsets[:off.size] = off
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:ind.size] = ind
+        if w is not None:
+            self.pool_weights.reshape(-1)[:w.size] = w
+        if self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        self.submit_pooled_csr(B, weighted=w is not None)
+        return self._topk_host(B, k, seg_offsets)
 
     # convenience used by the parity tests --------------------------------------------------------
     def gather_records(self, idx, dense=None):

@@ -801,6 +801,10 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->h_sh_status) (void)hipHostFree(w->h_sh_status);
     if (w->h_stage_send) (void)hipHostFree(w->h_stage_send);
     if (w->h_stage_recv) (void)hipHostFree(w->h_stage_recv);
+    if (w->h_tk_off) (void)hipHostFree(w->h_tk_off);
+    if (w->h_tk_idx) (void)hipHostFree(w->h_tk_idx);
+    if (w->h_tk_sc) (void)hipHostFree(w->h_tk_sc);
+    if (w->d_rank) (void)hipFree(w->d_rank);
     void *dev[] = {w->d_idx, w->d_dense, w->d_records, w->d_act[0], w->d_act[1], w->d_score, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all};
     for (void *p : dev)
         if (p) (void)hipFree(p);
@@ -1939,7 +1943,9 @@ static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
     fr_ctx *c = w->ctx;
     FR_SET_DEVICE(c);
     // as fr_worker_submit: the gather reads the pinned index rows (weights, dense features) in place, the output layer writes the pinned scores
-    return submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
+    rc = submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
+    if (!rc) w->host_batch = batch;   // (fr_worker_topk ranks it)
+    return rc;
 }
 
 extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, false); }
@@ -1969,7 +1975,9 @@ extern "C" int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted
     if (nnz < 0 || nnz > (int64_t)batch * c->pool_cols)
         FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_pooled_csr: offsets[batch * cols] = %lld entries, outside [0, batch %d x %d pooled columns]", (long long)nnz, batch, c->pool_cols);
     FR_SET_DEVICE(c);
-    return submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted != 0, c->model.dense_len ? w->h_dense : nullptr, w->h_score, w->h_pool_off, nnz);
+    rc = submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted != 0, c->model.dense_len ? w->h_dense : nullptr, w->h_score, w->h_pool_off, nnz);
+    if (!rc) w->host_batch = batch;
+    return rc;
 }
 
 // Sharded mode, low-precision transport: the shard's slice [batch][slice_padded] as bf16 or e4m3 (x 2^e of the context's X exponent)
@@ -2273,7 +2281,7 @@ extern "C" int fr_worker_submit(fr_worker *w, int batch) {
     if (c->cpu) {
         rc = launch_pipeline(w, batch, w->h_idx, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
         if (rc) return rc;
-        w->in_flight = true;
+        w->in_flight = true, w->host_batch = batch;
         return FR_OK;
     }
     FR_SET_DEVICE(c);
@@ -2286,7 +2294,7 @@ extern "C" int fr_worker_submit(fr_worker *w, int batch) {
     if (zero_copy) {
         rc = launch_pipeline(w, batch, w->h_idx, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
         if (rc) return rc;
-        w->in_flight = true;
+        w->in_flight = true, w->host_batch = batch;
         return FR_OK;
     }
     // input H2D (cuda_server.c:460-461) -- indices instead of the already-gathered features
@@ -2297,7 +2305,7 @@ extern "C" int fr_worker_submit(fr_worker *w, int batch) {
     if (rc) return rc;
     // output D2H (cuda_server.c:494-495)
     FR_HIP(hipMemcpyAsync(w->h_score, w->d_score, (size_t)batch * sizeof(float), hipMemcpyDeviceToHost, w->stream));
-    w->in_flight = true;
+    w->in_flight = true, w->host_batch = batch;
     return FR_OK;
 }
 
@@ -2694,6 +2702,106 @@ extern "C" int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *
     return FR_OK;
 }
 
+// ---- segmented top-K ranking (fleetrec_serving.h) -----------------------------------------------------------------------------------------
+// The kernels are the companion code object's (fr_rank.hip -> libfleetrec_rank.so, linked with an $ORIGIN rpath); state, order and the CPU twin are here.
+static int topk_check(fr_worker *w, int n, const void *scores, int n_seg, int k, const void *top_idx) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    if (k < 1 || k > FR_TOPK_MAX_K) FR_FAIL(FR_ERR_INVALID, "k = %d outside [1, %d]", k, FR_TOPK_MAX_K);
+    if (n < 1 || n > (1 << 24)) FR_FAIL(FR_ERR_INVALID, "n = %d scores outside [1, 2^24]", n);
+    if (n_seg < 1 || n_seg > n + 1) FR_FAIL(FR_ERR_INVALID, "n_seg = %d outside [1, n + 1 = %d]", n_seg, n + 1);
+    if (!scores || !top_idx) FR_FAIL(FR_ERR_INVALID, "d_scores / d_top_idx is NULL");
+    return FR_OK;
+}
+
+// behind everything submitted or pushed on w: queued fused batches are launched, the stage pipeline is drained by launches; nothing is waited for
+static int topk_enqueue(fr_worker *w, int n, const float *d_scores, int n_seg, const int32_t *d_off, int k, int32_t *d_top_idx, float *d_top_scores) {
+    fr_ctx *c = w->ctx;
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then rank");
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then rank");
+    FR_SET_DEVICE(c);
+    FrRankArgs a{};
+    a.scores = d_scores, a.off = d_off, a.n = n, a.n_seg = n_seg, a.k = k;
+    a.top_idx = d_top_idx, a.top_scores = d_top_scores, a.err_flag = w->d_err;
+    a.u_cap = fr_rank_units(n);
+    if (a.u_cap) {   // a segment may be longer than one workgroup streams: unit records and candidate lists in the worker's scratch
+        const size_t map_bytes = align_up((size_t)a.u_cap * sizeof(int4), 256);
+        const size_t need = 256 + map_bytes + (size_t)a.u_cap * FR_TOPK_MAX_K * sizeof(unsigned long long);
+        if (need > w->rank_bytes) {
+            if (w->d_rank) {   // an earlier ranking may still read it
+                FR_HIP(hipStreamSynchronize(w->stream));
+                (void)hipFree(w->d_rank);
+                w->d_rank = nullptr, w->rank_bytes = 0;
+            }
+            FR_HIP(hipMalloc((void **)&w->d_rank, need));
+            w->rank_bytes = need;
+        }
+        a.hdr = reinterpret_cast<int *>(w->d_rank);
+        a.unitmap = reinterpret_cast<int4 *>(w->d_rank + 256);
+        a.cand = reinterpret_cast<unsigned long long *>(w->d_rank + 256 + map_bytes);
+    }
+    int rc = fused_flush(w);
+    if (!rc) rc = pipeline_flush(w);
+    if (rc) return rc;
+    // a wave per segment when the segments are short on average (the host does not know the offsets: any length is ranked correctly by either form)
+    const int wave_form = n / n_seg <= 512;
+    const int e = fr_rank_launch(&a, wave_form, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the ranking launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_worker_topk_device(fr_worker *w, int n, const float *d_scores, int n_seg, const int32_t *d_seg_offsets, int k, int32_t *d_top_idx, float *d_top_scores) {
+    int rc = topk_check(w, n, d_scores, n_seg, k, d_top_idx);
+    if (rc) return rc;
+    if (w->ctx->cpu) {   // computed before the call returns; a malformed segment waits in c_err for fr_worker_sync
+        if (frc_rank_topk(d_scores, n, n_seg, d_seg_offsets, k, d_top_idx, d_top_scores)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+        return FR_OK;
+    }
+    return topk_enqueue(w, n, d_scores, n_seg, d_seg_offsets, k, d_top_idx, d_top_scores);
+}
+
+extern "C" int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t *h_seg_offsets, int k, int32_t *h_top_idx, float *h_top_scores) {
+    int rc = topk_check(w, batch, w ? w->h_score : nullptr, n_seg, k, h_top_idx);
+    if (rc) return rc;
+    if (w->sh_comm || w->ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_worker_topk ranks a host-form batch; a table-sharded step is not one");
+    if (!w->host_batch)
+        FR_FAIL(FR_ERR_STATE, "no host-form batch is in flight on this worker (fr_worker_submit, fr_worker_submit_pooled, _pooled_weighted, _pooled_csr): submit first, rank, then sync");
+    if (batch != w->host_batch) FR_FAIL(FR_ERR_INVALID, "batch %d, but the host-form batch in flight has %d items", batch, w->host_batch);
+    if (w->ctx->cpu) {
+        if (frc_rank_topk(w->h_score, batch, n_seg, h_seg_offsets, k, h_top_idx, h_top_scores)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+        return FR_OK;
+    }
+    if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking is already in flight on this worker: call fr_worker_sync first");
+    FR_SET_DEVICE(w->ctx);
+    const size_t n_off = h_seg_offsets ? (size_t)n_seg + 1 : 0, n_out = (size_t)n_seg * (size_t)k;
+    if (n_off > w->tk_off_cap || n_out > w->tk_out_cap) {   // a grow waits for the stream before pinned memory is released (the header says so)
+        FR_HIP(hipStreamSynchronize(w->stream));
+        if (n_off > w->tk_off_cap) {
+            if (w->h_tk_off) (void)hipHostFree(w->h_tk_off);
+            w->h_tk_off = nullptr, w->tk_off_cap = 0;
+            FR_HIP(hipHostMalloc((void **)&w->h_tk_off, n_off * sizeof(int32_t), hipHostMallocDefault));
+            w->tk_off_cap = n_off;
+        }
+        if (n_out > w->tk_out_cap) {
+            if (w->h_tk_idx) (void)hipHostFree(w->h_tk_idx);
+            if (w->h_tk_sc) (void)hipHostFree(w->h_tk_sc);
+            w->h_tk_idx = nullptr, w->h_tk_sc = nullptr, w->tk_out_cap = 0;
+            FR_HIP(hipHostMalloc((void **)&w->h_tk_idx, n_out * sizeof(int32_t), hipHostMallocDefault));
+            FR_HIP(hipHostMalloc((void **)&w->h_tk_sc, n_out * sizeof(float), hipHostMallocDefault));
+            w->tk_out_cap = n_out;
+        }
+    }
+    if (n_off) memcpy(w->h_tk_off, h_seg_offsets, n_off * sizeof(int32_t));
+    // as fr_worker_submit's scores: the kernels read the pinned scores and offsets in place and write the pinned results
+    rc = topk_enqueue(w, batch, w->h_score, n_seg, n_off ? w->h_tk_off : nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc : nullptr);
+    if (rc) return rc;
+    w->tk_dst_idx = h_top_idx, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
+    return FR_OK;
+}
+
 // Launch what is queued -- the partially filled host block, the batches queued by fr_worker_push_device -- without waiting for it.
 extern "C" int fr_worker_flush(fr_worker *w) {
     if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
@@ -2745,6 +2853,11 @@ extern "C" int fr_worker_host_pending(const fr_worker *w, int *queued, int *in_f
 
 extern "C" int fr_worker_sync(fr_worker *w) {
     if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    // whatever this sync returns, the host-form batch is no longer in flight and an undelivered host-form ranking is dropped
+    struct TopkDone {
+        fr_worker *w;
+        ~TopkDone() { w->host_batch = 0, w->tk_count = 0; }
+    } topk_done{w};
     if (w->ctx->cpu) {   // everything was computed inside the calls -- but for a table-sharded step, which runs on the worker's host stream
         const int crc = fr_comm_wait(w);   // (bounded wait + the ranks' status words, fr_comm.cpp; FR_OK at once when no such step is in flight)
         w->in_flight = false;
@@ -2776,6 +2889,10 @@ extern "C" int fr_worker_sync(fr_worker *w) {
     }
     FR_HIP(hipStreamSynchronize(w->stream));
     w->in_flight = false;
+    if (w->tk_count) {   // the host-form ranking: out of the pinned staging, as a host-fed block's scores are delivered
+        memcpy(w->tk_dst_idx, w->h_tk_idx, w->tk_count * sizeof(int32_t));
+        if (w->tk_dst_sc) memcpy(w->tk_dst_sc, w->h_tk_sc, w->tk_count * sizeof(float));
+    }
     if (__atomic_load_n(w->h_err, __ATOMIC_ACQUIRE)) {
         __atomic_store_n(w->h_err, 0, __ATOMIC_RELEASE);
         FR_FAIL(FR_ERR_INDEX_RANGE, "a lookup index was outside its table (row 0 was read instead)");

@@ -12,6 +12,7 @@
 
 #include <cstdio>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
@@ -229,6 +230,42 @@ int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, in
             memcpy(a, src + (size_t)i * dim, row_bytes);
         }
         if (any_bad) bad.store(1, std::memory_order_relaxed);
+    });
+    return bad.load(std::memory_order_relaxed);
+}
+
+// Segmented top-K ranking: the composites of fr_rank.hip -- (key << 32) | (0xffffffff - position), all distinct inside a segment -- and a partial
+// sort of them per segment; contiguous runs of segments are dealt to the pool's threads.  The score is copied through the winning position (a NaN's
+// payload is not in its key).
+int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int k, int32_t *top_idx, float *top_scores) {
+    const int units = (n < 8192 || n_seg < 2) ? 1 : (Pool::get().size() < n_seg ? Pool::get().size() : n_seg);
+    std::atomic<int> bad{0};
+    Pool::get().run(units, [&](int u) {
+        std::vector<uint64_t> comp;
+        const int s0 = (int)((int64_t)n_seg * u / units), s1 = (int)((int64_t)n_seg * (u + 1) / units);
+        for (int s = s0; s < s1; s++) {
+            int64_t a = off ? off[s] : 0, b = off ? off[s + 1] : n;
+            if (a < 0 || b < a || b > n) {
+                bad.store(1, std::memory_order_relaxed);
+                a = b = 0;
+            }
+            const size_t len = (size_t)(b - a), top = len < (size_t)k ? len : (size_t)k;
+            comp.resize(len);
+            for (size_t i = 0; i < len; i++) {
+                uint32_t bits;
+                memcpy(&bits, scores + a + i, 4);
+                comp[i] = ((uint64_t)fr_rank_key(bits) << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
+            }
+            std::partial_sort(comp.begin(), comp.begin() + (ptrdiff_t)top, comp.end(), std::greater<uint64_t>());
+            int32_t *oi = top_idx + (size_t)s * (size_t)k;
+            float *os = top_scores ? top_scores + (size_t)s * (size_t)k : nullptr;
+            const uint32_t ninf = 0xff800000u;
+            for (size_t j = 0; j < (size_t)k; j++) {
+                const uint32_t pos = j < top ? 0xffffffffu - (uint32_t)comp[j] : 0u;
+                oi[j] = j < top ? (int32_t)pos : -1;
+                if (os) memcpy(os + j, j < top ? (const void *)(scores + a + pos) : (const void *)&ninf, 4);
+            }
+        }
     });
     return bad.load(std::memory_order_relaxed);
 }

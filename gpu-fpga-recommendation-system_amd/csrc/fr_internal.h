@@ -192,6 +192,30 @@ struct FrFusedArgs {
     unsigned long long *stamps;  // diagnostics only (NULL normally): 16 s_memrealtime stamps per workgroup
 };
 
+// ---- segmented top-K ranking (fr_rank.hip -> libfleetrec_rank.so, the companion code object; fr_cpu.cpp has the twin) ------------------------
+// The rank order of fleetrec_serving.h on a score's 32 bits: a larger key ranks first; every NaN has key 0, behind -inf (0x007fffff).
+static inline __host__ __device__ uint32_t fr_rank_key(uint32_t u) { return (u & 0x7fffffffu) > 0x7f800000u ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u)); }
+constexpr int FR_RANK_PART = 16384;      // scores one workgroup streams: a longer segment is cut into units of this many
+constexpr int FR_RANK_FAN = 16;          // candidate lists one merge workgroup folds (16 x FR_TOPK_MAX_K composites = one LDS tile)
+constexpr size_t FR_RANK_HDR_BYTES = 16; // the scratch's head: [0] units reserved so far
+struct FrRankArgs {
+    const float *scores;
+    const int32_t *off;      // [n_seg + 1], or NULL: one segment [0, n)
+    int n, n_seg, k;
+    int u_cap;               // unit records / candidate lists the scratch holds (0 without scratch)
+    int32_t *top_idx;        // [n_seg][k]
+    float *top_scores;       // [n_seg][k] or NULL
+    int *err_flag;
+    // worker-owned scratch of segments longer than FR_RANK_PART (all NULL when n <= FR_RANK_PART: no segment can be)
+    int *hdr;
+    int4 *unitmap;                // [u_cap] {segment, part, parts of the segment, 0}; x < 0: no unit
+    unsigned long long *cand;     // [u_cap][k] composites, descending, 0-padded
+};
+// units a call over n scores can need when no two segments overlap (they can beside malformed ones; the surplus is ranked by one workgroup each)
+static inline int fr_rank_units(int n) { return n > FR_RANK_PART ? 2 * ((n + FR_RANK_PART - 1) / FR_RANK_PART) + 2 : 0; }
+// Enqueues the ranking on `stream` (a hipStream_t); wave_form: one wave per segment instead of a 256-thread workgroup.  -> 0 or the hipError_t value.
+extern "C" int fr_rank_launch(const FrRankArgs *args, int wave_form, void *stream);
+
 // ---- host objects -------------------------------------------------------------------------------
 // Where a table's rows live inside ctx->table_arena.  A table stored on its own: row r at byte_offset + r * dim * 4 (il_rows == 0).
 // FR_INDEX_PER_BANK contexts interleave the tables of one memory bank: rows [0, il_rows) of every table of the bank share one
@@ -396,6 +420,18 @@ struct fr_worker {
     // stream wait for it (lp_ensure_image).  Both touched under fr_ctx::lp_mutex only.
     hipEvent_t ev_update = nullptr;
     bool update_recorded = false;
+    // Segmented top-K ranking (fr_worker_topk_device / fr_worker_topk).  d_rank: the scratch of segments longer than FR_RANK_PART (head, unit records,
+    // candidate lists), allocated by the first call over more than FR_RANK_PART scores, grown (behind a wait for the stream) when a call needs more.
+    char *d_rank = nullptr;
+    size_t rank_bytes = 0;
+    int host_batch = 0;          // items of the host-form batch in flight (fr_worker_submit, the three host-form pooled submits); 0: none
+    // host form: pinned staging of the offsets and of the results, which fr_worker_sync copies to where the caller wants them
+    int32_t *h_tk_off = nullptr, *h_tk_idx = nullptr;
+    float *h_tk_sc = nullptr;
+    size_t tk_off_cap = 0, tk_out_cap = 0;   // elements
+    int32_t *tk_dst_idx = nullptr;
+    float *tk_dst_sc = nullptr;
+    size_t tk_count = 0;         // n_seg * k of the host-form ranking in flight; 0: none
     char last_kernel[96] = "";  // fr_worker_last_kernel: the dominant kernel of the most recent launch this worker enqueued
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
@@ -422,6 +458,8 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
 // n listed rows of one table <- src [n][dim], into the host arena with table_copy's head / tail addressing, over the pool's threads; a listed
 // id outside [0, rows) writes nothing and -> 1 (else 0).  A row listed twice ends up as the LAST of its listed sources.
 int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src);
+// the CPU twin of fr_rank_launch: the same outputs bit for bit, segments over the pool's threads; -> 1 when a segment was malformed (ranked as empty), else 0
+int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int k, int32_t *top_idx, float *top_scores);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \

@@ -17,6 +17,8 @@
 //                        [--csr]  (with --hots N, for fleetrec_server --hots N --csr: the very bags --hots N [--ragged] sends, compacted into the offsets
 //                                      form -- a block is int32 offsets[B x columns + 1], int32 indices[nnz] (the non-empty slots, bag by bag), float32
 //                                      weights[nnz] with --pool weighted (the weights of those slots), then the dense rows)
+//                        [--topk K [--segments S]]  (with --reply, for fleetrec_server --topk K --segments S: a block's reply is S x K (int32 position, float32
+//                                      score) pairs instead of B scores; only the size of what is read changes)
 //                        [--pool N]   (uniform indices: N distinct blocks per connection are generated up front and sent in rotation --
 //                                      drawing 12 k random indices per block is slower than the server; default 32, 0 = draw every block)
 #include <arpa/inet.h>
@@ -48,6 +50,7 @@ int main(int argc, char **argv) {
     long row_cap = 0, max_blocks = 1L << 40, interval_us = 0, pool = 32, window = 1;
     std::string host = "127.0.0.1", indices = "reference";
     bool per_item = false, per_bank = false, reply = false, ragged = false;
+    int topk = 0, segments = 1;   // --topk K --segments S: the size of a block's reply
     int hots = 0;
     bool weighted = false, pool_mode = false, csr = false;
     for (int i = 1; i < argc; i++) {
@@ -74,9 +77,17 @@ int main(int argc, char **argv) {
         else if (a == "--hots") hots = atoi(next());
         else if (a == "--ragged") ragged = true;
         else if (a == "--csr") csr = true;
+        else if (a == "--topk") topk = atoi(next());
+        else if (a == "--segments") segments = atoi(next());
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (hots < 0 || hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, hots); return 2; }
+    if (topk < 0 || topk > FR_TOPK_MAX_K || segments < 1 || (topk == 0 && segments != 1)) {
+        fprintf(stderr, "--topk K --segments S: K = 1 .. %d, S >= 1 (with --topk), not %d / %d\n", FR_TOPK_MAX_K, topk, segments);
+        return 2;
+    }
+    // the reply of a block: B scores, or (fleetrec_server --topk K --segments S) S x K (int32 position, float32 score) pairs
+    const size_t reply_floats = topk > 0 ? 2 * (size_t)segments * (size_t)topk : (size_t)batch;
     if (ragged && hots <= 0) { fprintf(stderr, "--ragged needs --hots N\n"); return 2; }
     if (csr && hots <= 0) { fprintf(stderr, "--csr needs --hots N\n"); return 2; }
     if (pool_mode && hots <= 0) { fprintf(stderr, "--pool sum|mean|weighted needs --hots N\n"); return 2; }
@@ -107,7 +118,7 @@ int main(int argc, char **argv) {
             }
             std::vector<int32_t> c_off, c_ind;   // --csr: the block in the offsets form
             std::vector<float> c_wt;
-            std::vector<float> dense((size_t)batch * m->dense_len), scores(batch);
+            std::vector<float> dense((size_t)batch * m->dense_len), scores(reply_floats);
             std::mt19937_64 rng(1234 + t);
             int sock = socket(AF_INET, SOCK_STREAM, 0), one = 1;
             sockaddr_in addr{};
@@ -147,7 +158,7 @@ int main(int argc, char **argv) {
             std::thread reader;
             if (async_reply)
                 reader = std::thread([&]() {  // score replies arrive in request order
-                    std::vector<float> sc(batch);
+                    std::vector<float> sc(reply_floats);
                     for (;;) {
                         size_t got = 0;
                         while (got < sc.size() * 4) {

@@ -31,6 +31,12 @@
 //                        the connection.  Legal with every serving mode (submit-and-sync, --stream, --hots, --device -1); with --shards the message
 //                        is applied on every shard context the table is resident on.  Requests in flight meanwhile see old or new 16-byte row
 //                        words; every request received after the status came back sees the new rows.
+//        [--topk K [--segments S]]: the block is ranked on the device (fr_worker_topk, behind the block's own submit, before its sync) as S requests of
+//                        batch / S candidates each (batch % S == 0; S defaults to 1; K = 1 .. 256).  With --reply the block's answer is S x K little-endian
+//                        (int32 position inside the request, float32 score) pairs instead of B floats; a request shorter than K is padded with (-1, -inf).
+//                        Legal on the submit-and-sync path, with --hots in every --pool form and --csr, and with --device -1.  Not with --stream
+//                        (its blocks are host-fed: no host-form batch is in flight to rank) and not with --shards (the scores of a sharded step are
+//                        gathered over the communicator, outside the worker's stream order) (fleetrec_sender --topk K --segments S).
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
@@ -80,6 +86,9 @@ struct Options {
     int pool = -1;         // --pool: 0 sum, 1 mean, 2 weighted (-1: not given)
     bool csr = false;      // --csr: blocks in the offsets form (with --hots)
     int update_port = 0;   // --update-port P: the row-update socket (0: none)
+    int topk = 0;          // --topk K: every block is ranked on the device, K per request (0: plain scores)
+    bool topk_given = false;
+    int segments = 1;      // --segments S: requests per block (with --topk)
 };
 
 static bool read_exact(int fd, void *buf, size_t n) {  // the recv loop of cuda_server.c:425-450
@@ -258,6 +267,11 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
     const size_t idx_bytes = (size_t)o.batch * idx_cols * sizeof(int32_t);
     const size_t dense_bytes = (size_t)o.batch * m->dense_len * sizeof(float);
     const size_t weight_bytes = o.pool == 2 ? (size_t)o.batch * idx_cols * sizeof(float) : 0;   // --pool weighted: the weights follow the index rows
+    // --topk K --segments S: the requests of a block, what fr_worker_sync delivers for them and the (position, score) pairs of the reply
+    std::vector<int32_t> seg_off((size_t)o.segments + 1), top_idx(o.topk > 0 ? (size_t)o.segments * (size_t)o.topk : 0);
+    std::vector<float> top_sc(top_idx.size());
+    std::vector<uint32_t> top_pairs(2 * top_idx.size());
+    for (int sg = 0; sg <= o.segments; sg++) seg_off[(size_t)sg] = sg * (o.batch / o.segments);
     int server_fd = socket(AF_INET, SOCK_STREAM, 0), opt = 1;
     setsockopt(server_fd, SOL_SOCKET, SO_REUSEADDR, &opt, sizeof(opt));
     sockaddr_in addr{};
@@ -476,6 +490,11 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 t->error = fr_last_error();
                 break;
             }
+            if (o.topk > 0 && fr_worker_topk(wk, o.batch, o.segments, o.segments > 1 ? seg_off.data() : nullptr, o.topk, top_idx.data(), top_sc.data()) != FR_OK) {
+                t->status = -5;
+                t->error = fr_last_error();
+                break;
+            }
             t->recv_to_submit_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_recv).count());
             if (fr_worker_sync(wk) != FR_OK) {
                 t->status = -6;
@@ -483,7 +502,13 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 break;
             }
             if (o.latency) t->recv_to_scores_us.push_back(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_recv).count());
-            if (o.reply && !write_exact(sock, fr_worker_score_ptr(wk), (size_t)o.batch * sizeof(float))) {
+            if (o.topk > 0) {   // S x K (position, score) pairs, the scores as bit copies
+                for (size_t j = 0; j < top_idx.size(); j++) {
+                    memcpy(&top_pairs[2 * j], &top_idx[j], 4);
+                    memcpy(&top_pairs[2 * j + 1], &top_sc[j], 4);
+                }
+            }
+            if (o.reply && !(o.topk > 0 ? write_exact(sock, top_pairs.data(), top_pairs.size() * 4) : write_exact(sock, fr_worker_score_ptr(wk), (size_t)o.batch * sizeof(float)))) {
                 t->status = -7;
                 t->error = "sending scores failed";
                 break;
@@ -528,6 +553,8 @@ int main(int argc, char **argv) {
         else if (a == "--hots") o.hots = atoi(next());
         else if (a == "--csr") o.csr = true;
         else if (a == "--update-port") o.update_port = atoi(next());
+        else if (a == "--topk") { o.topk = atoi(next()); o.topk_given = true; }
+        else if (a == "--segments") o.segments = atoi(next());
         else if (a == "--pool") {
             std::string v = next();
             if (v != "sum" && v != "mean" && v != "weighted") { fprintf(stderr, "--pool: sum, mean or weighted, not '%s'\n", v.c_str()); return 2; }
@@ -545,6 +572,20 @@ int main(int argc, char **argv) {
     if (o.hots < 0 || o.hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, o.hots); return 2; }
     if (o.hots > 0 && (o.stream || o.shards > 0)) {
         fprintf(stderr, "--hots (pooled lookups) serves the submit-and-sync path only: not with --stream or --shards (their producers are one-hot)\n");
+        return 2;
+    }
+    if (o.segments != 1 && o.topk <= 0) { fprintf(stderr, "--segments S needs --topk K\n"); return 2; }
+    if (o.topk_given && (o.topk < 1 || o.topk > FR_TOPK_MAX_K)) { fprintf(stderr, "--topk: 1 .. %d ranked scores per request, not %d\n", FR_TOPK_MAX_K, o.topk); return 2; }
+    if (o.topk > 0 && (o.segments < 1 || o.batch % o.segments != 0)) {
+        fprintf(stderr, "--topk --segments %d: a block of --batch %d candidates must divide into S >= 1 equal requests (batch %% S == 0)\n", o.segments, o.batch);
+        return 2;
+    }
+    if (o.topk > 0 && o.stream) {
+        fprintf(stderr, "--topk ranks the host-form batch in flight (fr_worker_topk); not with --stream: its blocks are host-fed, no such batch is in flight to rank\n");
+        return 2;
+    }
+    if (o.topk > 0 && o.shards > 0) {
+        fprintf(stderr, "--topk is not served with --shards: a sharded step's scores are gathered over the communicator, outside the worker's stream order\n");
         return 2;
     }
     if (o.csr && o.hots <= 0) { fprintf(stderr, "--csr (offsets-form blocks) needs --hots N\n"); return 2; }

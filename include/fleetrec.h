@@ -46,6 +46,7 @@ extern "C" {
  * fr_ctx_lp_bank_image_builds) -- fr_ctx_upload_table and every lookup are as before.
  * Still 6, additive: streaming pushes of the pooled lookups (fleetrec_serving.h: fr_worker_push_pooled_device, fr_worker_push_pooled_csr_device,
  * fr_worker_push_pooled_device_list) -- the submit forms and every one-hot push are as before.
+ * Still 6, additive: segmented device-side top-K ranking of scores (fleetrec_serving.h: fr_worker_topk_device, fr_worker_topk) -- every score is as before.
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile
  * shape of a chain model no longer follows the number of live workers).
  * 4 (round 4): the surface is three headers -- this one (the three spans of thread_consume() that SURVEY section 8(b) cuts, the request

@@ -255,6 +255,36 @@ int fr_worker_calibrate_fp8_sharded_pooled(fr_worker *w, fr_comm *comm, int batc
 int fr_worker_update_rows(fr_worker *w, int table, int n, const int32_t *d_row_ids, const float *d_rows);
 int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *h_row_ids, const float *h_rows);
 
+/* Segmented top-K ranking of scores on the device (additive in ABI 6): a recommender's last step -- rank each request's candidates, return the best
+ * k -- without fr_worker_sync, a D2H copy of every score and a host sort.
+ * Segments: segment s is d_scores[off[s] .. off[s + 1]), off = d_seg_offsets int32 [n_seg + 1] (NULL: one segment [0, n)): one request's candidate
+ * list inside a batch, or a span of several batches whose score buffers are contiguous.  Empty segments are legal; offsets need not start at 0 or end at n.
+ * Rank order: a total order on bit patterns.  With u the score's 32 bits: key = 0 if (u & 0x7fffffff) > 0x7f800000 (every NaN), else ~u if the sign
+ * bit is set, else u | 0x80000000.  A larger key ranks first; equal keys rank by LOWER POSITION first.  So NaNs rank last, behind -inf (key 0x007fffff),
+ * in position order among themselves; +0 ranks above -0; the answer is unique for every input.
+ * Outputs: d_top_idx[s][j] = the position INSIDE segment s of its j-th ranked score, d_top_scores[s][j] (the array may be NULL) = that score as a bit
+ * copy; for j >= the segment's length -1 and -inf (0xff800000).  Nothing past [n_seg][k] is written.
+ * Stream order: asynchronous on the worker's stream, behind everything submitted or pushed on w before the call -- batches fr_worker_push_device has
+ * queued for a fused launch are launched first and the stage pipeline is drained by launches, neither waited for (the rule of fr_worker_update_rows;
+ * host-fed batches still queued in a block make the call FR_ERR_STATE: flush first; so does a table-sharded step in flight).  fr_worker_sync is the
+ * completion point; every buffer stays valid until then.  fr_worker_last_kernel keeps naming the last batch's kernel.
+ * A segment is MALFORMED when off[s] < 0, off[s + 1] < off[s] or off[s + 1] > n: FR_ERR_INDEX_RANGE at fr_worker_sync (the sticky word, the worker is
+ * usable afterwards); it is ranked as empty, every other segment is as specified, and no byte outside d_scores[0 .. n) and offsets[0 .. n_seg] is read.
+ * FR_ERR_INVALID: k outside 1 .. FR_TOPK_MAX_K, n outside 1 .. 2^24, n_seg < 1 or > n + 1, a NULL d_scores or d_top_idx.  Nothing is enqueued on an
+ * argument or state error.  A call over more than 16384 scores uses a scratch the worker allocates at the first such call; a later call that needs a
+ * larger one waits for the worker's stream before it replaces it.  The CPU back-end computes before it returns, the same bits. */
+#define FR_TOPK_MAX_K 256
+int fr_worker_topk_device(fr_worker *w, int n, const float *d_scores, int n_seg, const int32_t *d_seg_offsets /* [n_seg + 1]; NULL: one segment [0, n) */,
+                          int k, int32_t *d_top_idx /* [n_seg][k] */, float *d_top_scores /* [n_seg][k] or NULL */);
+/* Host form: ranks the `batch` scores (fr_worker_score_ptr) of the host-form batch in flight on w -- fr_worker_submit, fr_worker_submit_pooled,
+ * fr_worker_submit_pooled_weighted or fr_worker_submit_pooled_csr, not yet synchronised; FR_ERR_STATE when there is none, or after a sharded step;
+ * FR_ERR_INVALID when batch is not that batch's size.  h_seg_offsets (NULL: one segment) is copied into pinned staging inside the call;
+ * h_top_idx / h_top_scores (the latter may be NULL) receive the results in fr_worker_sync, the way fr_worker_push_host delivers h_scores, and stay
+ * valid until then.  One host-form ranking may be in flight per worker (a second is FR_ERR_STATE).  The staging is allocated on first use and grows when
+ * n_seg * k needs it; a grow waits for the worker's stream. */
+int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t *h_seg_offsets /* NULL: one segment */,
+                   int k, int32_t *h_top_idx, float *h_top_scores /* or NULL */);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
