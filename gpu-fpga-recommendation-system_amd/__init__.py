@@ -29,6 +29,7 @@ GATHER_WORD_MAJOR, GATHER_ITEM_TILE, GATHER_ITEM_TILE_DEDUP, GATHER_ITEM_TILE_DE
 EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step's slices travel (Comm.set_exchange)
 POOL_MAX_HOTS = 64   # FR_POOL_MAX_HOTS (fleetrec_serving.h): slots per bag of a pooled lookup
 TOPK_MAX_K = 256   # FR_TOPK_MAX_K (fleetrec_serving.h): the largest k of a top-K ranking
+REQ_ONE_HOT, REQ_POOLED, REQ_DENSE = 0, 1, 2   # FR_REQ_* (fleetrec_serving.h): the forms of a request-form expansion
 POOL_SUM, POOL_MEAN = 0, 1   # FR_POOL_SUM / FR_POOL_MEAN: the pooling mode of an index column (Context.set_pooling(hots, modes))
 ABI_VERSION = 6   # include/fleetrec.h FR_ABI_VERSION this binding was written against
 MEM_CLASS_NAMES = {0: "HBM", 1: "DDR", 2: "PLRAM"}
@@ -84,6 +85,8 @@ ABI_SYMBOLS = [
     "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
     "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
     "fr_worker_topk_device", "fr_worker_topk",
+    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
+    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
 ]
 
 
@@ -95,7 +98,9 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
                    "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
                    "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
-                   "fr_worker_topk_device", "fr_worker_topk")
+                   "fr_worker_topk_device", "fr_worker_topk",
+                   "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
+                   "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests")
 
 
 def lib():
@@ -179,6 +184,10 @@ def lib():
         "fr_worker_submit_sharded_pooled": (i32, [vp, vp, i32, i32]), "fr_worker_submit_sharded_pooled_csr": (i32, [vp, vp, i32, i32]),
         "fr_worker_calibrate_fp8_sharded_pooled": (i32, [vp, vp, i32, i32]),
         "fr_worker_topk_device": (i32, [vp, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_topk": (i32, [vp, i32, i32, vp, i32, vp, vp]),
+        "fr_ctx_set_request_columns": (i32, [vp, pi, i32, i32]), "fr_ctx_request_words": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
+        "fr_worker_request_idx_ptr": (pi, [vp]), "fr_worker_request_weights_ptr": (pf, [vp]), "fr_worker_request_dense_ptr": (pf, [vp]),
+        "fr_worker_request_offsets_ptr": (pi, [vp]), "fr_worker_submit_requests": (i32, [vp, i32, i32, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -655,6 +664,21 @@ class Context:
         """P = sum of hots: int32 columns of one item's pooled index row; 0 when no pooling is set."""
         return int(lib().fr_ctx_pooled_index_cols(self._h))
 
+    def set_request_columns(self, shared, dense_shared=False):
+        """Request-form batches (fr_ctx_set_request_columns): shared[c] = 1 when index column c belongs to the request (one row per request), 0 when
+        it stays per item, for every index column of the model's index mode; dense_shared: the dense features are the request's too.  None clears."""
+        if shared is None:
+            _check(lib().fr_ctx_set_request_columns(self._h, None, 0, 0))
+            return
+        sh = np.ascontiguousarray(np.asarray(shared, dtype=np.int32).ravel())
+        _check(lib().fr_ctx_set_request_columns(self._h, sh.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(sh.size), int(dense_shared)))
+
+    def request_words(self, form):
+        """-> (request words, candidate words, row words) of a form (REQ_ONE_HOT, REQ_POOLED, REQ_DENSE): fr_ctx_request_words."""
+        r, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _check(lib().fr_ctx_request_words(self._h, int(form), ctypes.byref(r), ctypes.byref(c), ctypes.byref(w)))
+        return r.value, c.value, w.value
+
     def synchronize(self):
         _check(lib().fr_device_synchronize(self._h))
 
@@ -677,6 +701,11 @@ class Worker:
                       if m.dense_len else None)
         self._pool_cap = max(m.idx_cols, ctx.pooled_index_cols)   # int32 columns per item the pinned index buffer holds
         self._pool_w_cap = ctx.pooled_index_cols                  # floats per item the pinned weight buffer holds (0: there is none)
+        self._req_caps = (1, 1)                                   # words per request the pinned request index / weight buffers hold (request_buffers)
+        req_ptr = getattr(lib(), "fr_worker_request_idx_ptr", None)   # (None: an FR_LIB build from before the request form)
+        if req_ptr is not None and req_ptr(h):
+            rp = ctx.request_words(REQ_POOLED)[0] if ctx.pooled_index_cols > 0 else 0
+            self._req_caps = (max(ctx.request_words(REQ_ONE_HOT)[0], rp, 1), max(rp, 1))
 
     def close(self):
         if self._h:
@@ -1181,6 +1210,86 @@ class Worker:
             self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
         self.submit_pooled_csr(B, weighted=w is not None)
         return self._topk_host(B, k, seg_offsets)
+
+    # request-form batches (Context.set_request_columns): request rows + candidate rows + segment offsets, expanded on the device ----------------
+    def expand_requests_device(self, batch, n_req, d_req, d_cand, d_out, form, d_seg_offsets=None):
+        """fr_worker_expand_requests_device: d_req [n_req][request words] + d_cand [batch][candidate words] (None for REQ_DENSE) -> d_out
+        [batch][row words] of the form, 32-bit bit copies; d_seg_offsets int32 [n_req + 1] (None: n_req equal requests).  Asynchronous on the
+        worker's stream: a following gather / submit / push on this worker with d_out as its rows reads the expanded rows; sync() completes it."""
+        _check(lib().fr_worker_expand_requests_device(self._h, int(batch), int(n_req), self._ptr(d_seg_offsets), self._ptr(d_req), self._ptr(d_cand), int(form),
+                                                      self._ptr(d_out)))
+
+    def request_buffers(self):
+        """-> (idx int32, weights float32 or None, dense float32 or None, offsets int32): flat numpy views of the four pinned request buffers
+        (fr_worker_request_*_ptr), max_batch x the words per request the worker was created for (offsets: max_batch + 1); request rows are packed
+        [n_req][request words of the form].  (None, None, None, None) on a worker created before Context.set_request_columns."""
+        L, B = lib(), self.max_batch
+        p = L.fr_worker_request_idx_ptr(self._h)
+        if not p:
+            return None, None, None, None
+        ri, rw = self._req_caps   # words per request the buffers were sized for when the worker was created
+        pw, pd = L.fr_worker_request_weights_ptr(self._h), L.fr_worker_request_dense_ptr(self._h)
+        return (np.ctypeslib.as_array(p, shape=(B * ri,)),
+                np.ctypeslib.as_array(pw, shape=(B * rw,)) if pw else None,
+                np.ctypeslib.as_array(pd, shape=(B * self.ctx.model.dense_len,)) if pd else None,
+                np.ctypeslib.as_array(L.fr_worker_request_offsets_ptr(self._h), shape=(B + 1,)))
+
+    def submit_requests(self, batch, n_req, pooled=0):
+        """fr_worker_submit_requests on what the pinned buffers hold (candidate side: the index / pool-weight / dense buffers; request side:
+        request_buffers()); pooled: 0 one-hot, 1 pooled, 2 pooled weighted.  Asynchronous; follow with sync()."""
+        _check(lib().fr_worker_submit_requests(self._h, int(batch), int(n_req), int(pooled)))
+
+    def _load_requests(self, req_idx, cand_idx, seg_offsets, req_dense, dense, req_weights, weights, pooled):
+        """fills the pinned buffers of a request-form host call -> (batch, n_req, pooled, offsets)"""
+        ctx = self.ctx
+        off = np.ascontiguousarray(np.asarray(seg_offsets, dtype=np.int32).reshape(-1))
+        n_req = off.size - 1
+        weighted = weights is not None or req_weights is not None
+        cand = np.asarray(cand_idx, dtype=np.int32)
+        B = len(cand)
+        if pooled is None:   # the pooled form on a context whose pooling is set
+            pooled = 1 if ctx.pooled_index_cols > 0 or weighted else 0
+        pooled = 2 if pooled and weighted else int(pooled)
+        rs, rc, _ = ctx.request_words(REQ_POOLED if pooled else REQ_ONE_HOT)
+        b_idx, b_w, b_dense, b_off = self.request_buffers()
+        if b_idx is None:
+            raise FleetRecError(FR_ERR_STATE, "the worker has no request buffers: create the worker after Context.set_request_columns")
+        if B > self.max_batch or n_req < 1 or n_req > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d / %d requests exceed the worker's max_batch %d" % (B, n_req, self.max_batch))
+        req = np.asarray(req_idx, dtype=np.int32).reshape(-1) if rs else np.zeros(0, np.int32)
+        cand = cand.reshape(-1)
+        if req.size != n_req * rs or cand.size != B * rc or req.size > b_idx.size or cand.size > self.max_batch * self._pool_cap:
+            raise FleetRecError(FR_ERR_INVALID, "request rows of %d words and candidate rows of %d words do not match the split's %d x %d and %d x %d" % (req.size, cand.size, n_req, rs, B, rc))
+        b_off[:off.size] = off
+        b_idx[:req.size] = req
+        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:cand.size] = cand
+        if pooled == 2:
+            if b_w is None or self.pool_weights is None:
+                raise FleetRecError(FR_ERR_STATE, "the worker has no weight buffers: create the worker after Context.set_pooling")
+            b_w[:req.size] = np.asarray(req_weights, dtype=np.float32).reshape(-1) if rs else np.zeros(0, np.float32)
+            self.pool_weights.reshape(-1)[:cand.size] = np.asarray(weights, dtype=np.float32).reshape(-1)
+        if b_dense is not None:
+            b_dense[:n_req * ctx.model.dense_len] = np.asarray(req_dense, dtype=np.float32).reshape(-1)
+        elif self.dense is not None:
+            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        return B, n_req, pooled, off
+
+    def infer_requests(self, req_idx, cand_idx, seg_offsets, req_dense=None, dense=None, req_weights=None, weights=None, pooled=None):
+        """Host-buffer path of a request-form batch: req_idx int32 [n_req][request words], cand_idx int32 [B][candidate words], seg_offsets int32
+        [n_req + 1] (+ req_dense [n_req][dense_len] when the dense features are shared, else dense [B][dense_len]) -> scores float32 [B].  On a
+        context whose pooling is set the rows are pooled rows (pooled=0 forces the one-hot form); weights / req_weights: float32 of the shapes of
+        cand_idx / req_idx, the weight of every slot (all-SUM contexts only)."""
+        B, n_req, pooled, _ = self._load_requests(req_idx, cand_idx, seg_offsets, req_dense, dense, req_weights, weights, pooled)
+        self.submit_requests(B, n_req, pooled)
+        self.sync()
+        return self.score[:B].copy()
+
+    def infer_requests_topk(self, req_idx, cand_idx, seg_offsets, k, req_dense=None, dense=None, req_weights=None, weights=None, pooled=None):
+        """infer_requests() with the ranking on the device: -> (positions int32 [n_req][k], scores float32 [n_req][k]), every request's candidates
+        ranked (fr_worker_topk over the same offsets)."""
+        B, n_req, pooled, off = self._load_requests(req_idx, cand_idx, seg_offsets, req_dense, dense, req_weights, weights, pooled)
+        self.submit_requests(B, n_req, pooled)
+        return self._topk_host(B, k, off)
 
     # convenience used by the parity tests --------------------------------------------------------
     def gather_records(self, idx, dense=None):

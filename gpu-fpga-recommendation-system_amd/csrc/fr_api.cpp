@@ -103,6 +103,7 @@ static void ctx_free(fr_ctx *c) {
     if (c->d_chunks) (void)hipFree(c->d_chunks);
     if (c->d_merged) (void)hipFree(c->d_merged);
     if (c->d_pool) (void)hipFree(c->d_pool);
+    if (c->d_req_desc) (void)hipFree(c->d_req_desc);
     for (int i = 0; i < 4; i++) {
         if (c->d_w[i]) (void)hipFree(c->d_w[i]);
         if (i < 3 && c->d_wq[i]) (void)hipFree(c->d_wq[i]);
@@ -781,7 +782,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->ctx && w->ctx->cpu) {
         fr_comm_worker_release(w);   // a sharded step still on the worker's host stream: waited for (bounded), its communicator let go
         if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
-        void *host[] = {w->h_idx, w->h_pool_w, w->h_pool_off, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
+        void *host[] = {w->h_idx, w->h_pool_w, w->h_pool_off, w->h_req_idx, w->h_req_w, w->h_req_dense, w->h_req_off, w->d_idx, w->d_dense, w->d_pool_w, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
         for (void *p : host) free(p);
         fr_ctx *held = w->counted ? w->ctx : nullptr;
         delete w;
@@ -795,6 +796,8 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->h_idx) (void)hipHostFree(w->h_idx);
     if (w->h_pool_w) (void)hipHostFree(w->h_pool_w);
     if (w->h_pool_off) (void)hipHostFree(w->h_pool_off);
+    for (void *p : {(void *)w->h_req_idx, (void *)w->h_req_w, (void *)w->h_req_dense, (void *)w->h_req_off})
+        if (p) (void)hipHostFree(p);
     if (w->h_dense) (void)hipHostFree(w->h_dense);
     if (w->h_score) (void)hipHostFree(w->h_score);
     if (w->h_err) (void)hipHostFree(w->h_err);
@@ -805,7 +808,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     if (w->h_tk_idx) (void)hipHostFree(w->h_tk_idx);
     if (w->h_tk_sc) (void)hipHostFree(w->h_tk_sc);
     if (w->d_rank) (void)hipFree(w->d_rank);
-    void *dev[] = {w->d_idx, w->d_dense, w->d_records, w->d_act[0], w->d_act[1], w->d_score, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all};
+    void *dev[] = {w->d_idx, w->d_dense, w->d_pool_w, w->d_records, w->d_act[0], w->d_act[1], w->d_score, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     if (w->hr.h_idx) (void)hipHostFree(w->hr.h_idx);
@@ -838,6 +841,14 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
 static size_t idx_cols(const fr_ctx *c) {
     const int mode = c->model.index_mode;
     return mode == FR_INDEX_PER_TABLE ? (size_t)c->model.n_tables : (mode == FR_INDEX_PER_BANK ? (size_t)c->n_banks : 1);
+}
+
+// request words per request the worker's pinned request buffers hold: max(Rs, Rs') ints (at least one), Rs' floats -- as the split and the pooling stand now
+static void request_caps(const fr_ctx *c, fr_worker *w) {
+    const int rs = c->req_form[FR_REQ_ONE_HOT].req_words, rp = c->req_form[FR_REQ_POOLED].desc.empty() ? 0 : c->req_form[FR_REQ_POOLED].req_words;
+    w->req_idx_cap = rs > rp ? rs : rp;
+    if (w->req_idx_cap < 1) w->req_idx_cap = 1;
+    w->req_w_cap = w->pool_w_cap ? (rp > 0 ? rp : 1) : 0;
 }
 
 #define W_HIP(call)                                                                       \
@@ -880,7 +891,20 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
         w->d_records = (float *)host(B * (size_t)ctx->slice_padded * sizeof(float));
         w->c_scratch = (float *)host(B * ((size_t)m.fc[1] + m.fc[2] + m.fc[3]) * sizeof(float));
         if (ctx->n_shards > 1) w->c_x = (float *)host(B * (size_t)m.fc[0] * sizeof(float));
-        if (!w->h_idx || (w->pool_w_cap && (!w->h_pool_w || !w->h_pool_off)) || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
+        bool req_ok = true;
+        if (!ctx->req_shared.empty()) {   // request-form host call: the request side's buffers, and host stand-ins for the device buffers the expansion writes
+            request_caps(ctx, w);
+            w->h_req_idx = (int32_t *)host(B * (size_t)w->req_idx_cap * sizeof(int32_t));
+            if (w->req_w_cap) w->h_req_w = (float *)host(B * (size_t)w->req_w_cap * sizeof(float));
+            if (ctx->req_dense_shared) w->h_req_dense = (float *)host(B * m.dense_len * sizeof(float));
+            w->h_req_off = (int32_t *)host((B + 1) * sizeof(int32_t));
+            w->d_idx = (int32_t *)host(B * (size_t)w->idx_cap * sizeof(int32_t));
+            if (m.dense_len) w->d_dense = (float *)host(B * m.dense_len * sizeof(float));
+            if (w->pool_w_cap) w->d_pool_w = (float *)host(B * (size_t)w->pool_w_cap * sizeof(float));
+            req_ok = w->h_req_idx && (!w->req_w_cap || w->h_req_w) && (!ctx->req_dense_shared || w->h_req_dense) && w->h_req_off && w->d_idx && (!m.dense_len || w->d_dense) &&
+                     (!w->pool_w_cap || w->d_pool_w);
+        }
+        if (!req_ok || !w->h_idx || (w->pool_w_cap && (!w->h_pool_w || !w->h_pool_off)) || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
             fr_worker_destroy(w);
             FR_FAIL(FR_ERR_OOM, "out of host memory (worker buffers for batch %d)", max_batch);
         }
@@ -941,6 +965,14 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     for (int p = 0; p < 2; p++)
         W_HIP(hipMalloc((void **)&w->d_act[p], (size_t)w->ld_max * ((size_t)m.fc[0] + 2 * ((size_t)m.fc[1] + m.fc[2] + m.fc[3])) * sizeof(float)));
     W_HIP(hipMalloc((void **)&w->d_score, B * sizeof(float)));
+    if (!ctx->req_shared.empty()) {   // request-form host call: the request side's pinned buffers (read in place by the expansion) and the expanded weights
+        request_caps(ctx, w);
+        W_HIP(hipHostMalloc((void **)&w->h_req_idx, B * (size_t)w->req_idx_cap * sizeof(int32_t), hipHostMallocDefault));
+        if (w->req_w_cap) W_HIP(hipHostMalloc((void **)&w->h_req_w, B * (size_t)w->req_w_cap * sizeof(float), hipHostMallocDefault));
+        if (ctx->req_dense_shared) W_HIP(hipHostMalloc((void **)&w->h_req_dense, B * m.dense_len * sizeof(float), hipHostMallocDefault));
+        W_HIP(hipHostMalloc((void **)&w->h_req_off, (B + 1) * sizeof(int32_t), hipHostMallocDefault));
+        if (w->pool_w_cap) W_HIP(hipMalloc((void **)&w->d_pool_w, B * (size_t)w->pool_w_cap * sizeof(float)));
+    }
     W_HIP(hipEventCreate(&w->ev_start));
     W_HIP(hipEventCreate(&w->ev_stop));
     W_HIP(hipEventCreateWithFlags(&w->ev_update, hipEventDisableTiming));
@@ -960,6 +992,10 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
 
 extern "C" int32_t *fr_worker_idx_ptr(fr_worker *w) { return w ? w->h_idx : nullptr; }
 extern "C" float *fr_worker_pool_weights_ptr(fr_worker *w) { return w ? w->h_pool_w : nullptr; }
+extern "C" int32_t *fr_worker_request_idx_ptr(fr_worker *w) { return w ? w->h_req_idx : nullptr; }
+extern "C" float *fr_worker_request_weights_ptr(fr_worker *w) { return w ? w->h_req_w : nullptr; }
+extern "C" float *fr_worker_request_dense_ptr(fr_worker *w) { return w ? w->h_req_dense : nullptr; }
+extern "C" int32_t *fr_worker_request_offsets_ptr(fr_worker *w) { return w ? w->h_req_off : nullptr; }
 extern "C" int32_t *fr_worker_pool_offsets_ptr(fr_worker *w) { return w ? w->h_pool_off : nullptr; }
 extern "C" float *fr_worker_dense_ptr(fr_worker *w) { return w ? w->h_dense : nullptr; }
 extern "C" float *fr_worker_score_ptr(fr_worker *w) { return w ? w->h_score : nullptr; }
@@ -1693,9 +1729,23 @@ static int pooling_busy(fr_ctx *ctx, const char *who) {
     return FR_OK;
 }
 
+// The request-form descriptor tables (further below) follow the pooling: they are PREPARED for the hots about to be installed -- built and
+// uploaded beside the ones in use -- before any pooling state changes, and committed together with it (a commit cannot fail).
+struct RequestTables {
+    fr_ctx::ReqForm f[3];
+    int32_t *d = nullptr;   // the new device allocation (GPU contexts with a split)
+    bool made = false;      // false: the context has no split, nothing to commit
+};
+static int request_prepare(fr_ctx *ctx, const std::vector<int32_t> &shared, bool dense_shared, const int32_t *hots, RequestTables &t);   // hots NULL: no pooling
+static void request_commit(fr_ctx *ctx, RequestTables &t);
+static void request_discard(RequestTables &t);
+
 // the descriptors of hots[] x modes[] (modes == NULL: every column SUM), uploaded; the context's copies are replaced only when all of it worked
 static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *modes) {
     const int cols = (int)idx_cols(ctx);
+    RequestTables rt;   // a request split survives: its pooled widths follow the new hots
+    const int rrc = request_prepare(ctx, ctx->req_shared, ctx->req_dense_shared, hots, rt);
+    if (rrc) return rrc;
     std::vector<uint32_t> prefix(cols + 1, 0);
     int max_hots = 1;
     bool wide = true, any_mean = false;
@@ -1716,11 +1766,16 @@ static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *mode
     if (!ctx->cpu) {
         FrPoolDesc *d = nullptr;
         const size_t n = pool.size();
-        FR_HIP(hipMalloc((void **)&d, sizeof(FrPoolDesc) * (n ? 2 * n : 1)));
-        hipError_t e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
+        hipError_t e = hipMalloc((void **)&d, sizeof(FrPoolDesc) * (n ? 2 * n : 1));
+        if (e != hipSuccess) {
+            request_discard(rt);
+            FR_FAIL(e == hipErrorOutOfMemory ? FR_ERR_OOM : FR_ERR_HIP, "hipMalloc(pooled descriptors) failed: %s", hipGetErrorString(e));
+        }
+        e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(d + n, csr.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(d);
+            request_discard(rt);
             FR_FAIL(FR_ERR_HIP, "hipMemcpy(pooled descriptors) failed: %s", hipGetErrorString(e));
         }
         if (ctx->d_pool) (void)hipFree(ctx->d_pool);
@@ -1737,6 +1792,7 @@ static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *mode
     ctx->pool_cols = (int)prefix[cols];
     ctx->pool_max_hots = max_hots;
     ctx->pool_wide = wide;
+    request_commit(ctx, rt);
     return FR_OK;
 }
 
@@ -1787,7 +1843,10 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
     if (rc) return rc;
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
     if (!hots) {
-        if (ctx->d_pool) FR_HIP(hipFree(ctx->d_pool));
+        RequestTables rt;   // (a request split keeps its one-hot and dense forms)
+        const int rrc = request_prepare(ctx, ctx->req_shared, ctx->req_dense_shared, nullptr, rt);
+        if (rrc) return rrc;
+        if (ctx->d_pool) (void)hipFree(ctx->d_pool);
         ctx->d_pool = ctx->d_pool_csr = nullptr;
         ctx->h_pool.clear();
         ctx->h_pool_csr.clear();
@@ -1796,6 +1855,7 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
         ctx->pool_any_mean = false;
         ctx->pool_cols = ctx->pool_max_hots = 0;
         ctx->pool_wide = false;
+        request_commit(ctx, rt);
         return FR_OK;
     }
     return pooling_install(ctx, hots, nullptr);   // every mode is SUM again
@@ -2799,6 +2859,200 @@ extern "C" int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t 
     rc = topk_enqueue(w, batch, w->h_score, n_seg, n_off ? w->h_tk_off : nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc : nullptr);
     if (rc) return rc;
     w->tk_dst_idx = h_top_idx, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
+    return FR_OK;
+}
+
+// ---- request-form batches (fleetrec_serving.h) -------------------------------------------------------------------------------------------------
+// The kernel is the second companion code object's (fr_request.hip -> libfleetrec_request.so, linked with an $ORIGIN rpath); the descriptor tables,
+// state and the host form are here, the CPU twin in fr_cpu.cpp.
+// The tables of the three forms from a mask, dense_shared and the hots (NULL: no pooling) they are to serve: word w of a full row is word desc[w] of the candidate row
+// (desc[w] >= 0) or word ~desc[w] of the request row (desc[w] < 0); both sides keep their columns in ascending order, a pooled column its slots.
+static int request_prepare(fr_ctx *ctx, const std::vector<int32_t> &shared, bool dense_shared, const int32_t *hots, RequestTables &t) {
+    if (shared.empty()) return FR_OK;
+    const int cols = (int)idx_cols(ctx);
+    for (int form = FR_REQ_ONE_HOT; form <= FR_REQ_POOLED; form++) {
+        if (form == FR_REQ_POOLED && !hots) continue;
+        for (int c = 0; c < cols; c++)
+            for (int h = 0, n = form == FR_REQ_POOLED ? hots[c] : 1; h < n; h++)
+                t.f[form].desc.push_back(shared[(size_t)c] ? ~(t.f[form].req_words++) : t.f[form].cand_words++);
+    }
+    if (dense_shared) {
+        for (int k = 0; k < ctx->model.dense_len; k++) t.f[FR_REQ_DENSE].desc.push_back(~k);
+        t.f[FR_REQ_DENSE].req_words = ctx->model.dense_len;
+    }
+    size_t total = 0;
+    for (int form = 0; form < 3; form++) t.f[form].d_first = total, total += t.f[form].desc.size();
+    if (!ctx->cpu) {
+        FR_HIP(hipMalloc((void **)&t.d, sizeof(int32_t) * (total ? total : 1)));
+        for (int form = 0; form < 3; form++) {
+            if (t.f[form].desc.empty()) continue;
+            const hipError_t e = hipMemcpy(t.d + t.f[form].d_first, t.f[form].desc.data(), sizeof(int32_t) * t.f[form].desc.size(), hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                request_discard(t);
+                FR_FAIL(FR_ERR_HIP, "hipMemcpy(request-form descriptors) failed: %s", hipGetErrorString(e));
+            }
+        }
+    }
+    t.made = true;
+    return FR_OK;
+}
+
+static void request_commit(fr_ctx *ctx, RequestTables &t) {
+    if (!t.made) return;
+    if (ctx->d_req_desc) (void)hipFree(ctx->d_req_desc);
+    ctx->d_req_desc = t.d;
+    t.d = nullptr;
+    for (int form = 0; form < 3; form++) std::swap(ctx->req_form[form], t.f[form]);
+}
+
+static void request_discard(RequestTables &t) {
+    if (t.d) (void)hipFree(t.d);
+    t.d = nullptr;
+}
+
+extern "C" int fr_ctx_set_request_columns(fr_ctx *ctx, const int32_t *shared, int n_cols, int dense_shared) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_request_columns: request-form batches are not available on a sharded context (%d shards)", ctx->n_shards);
+    const int cols = (int)idx_cols(ctx);
+    if (shared) {
+        if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: n_cols %d, the context has %d index columns", n_cols, cols);
+        if (dense_shared != 0 && dense_shared != 1) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: dense_shared = %d is neither 0 nor 1", dense_shared);
+        if (dense_shared && !ctx->model.dense_len) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: dense_shared on a model without dense features");
+        int n_shared = 0;
+        for (int c = 0; c < cols; c++) {
+            if (shared[c] != 0 && shared[c] != 1) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: shared[%d] = %d is neither 0 nor 1", c, shared[c]);
+            n_shared += shared[c];
+        }
+        if (!n_shared && !dense_shared) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: nothing is shared (no shared column, no shared dense features)");
+        if (n_shared == cols && (!ctx->model.dense_len || dense_shared))
+            FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: nothing is left per item (every column is shared and there are no per-item dense features)");
+    }
+    const int rc = pooling_busy(ctx, "fr_ctx_set_request_columns");
+    if (rc) return rc;
+    if (!ctx->cpu) FR_SET_DEVICE(ctx);
+    if (!shared) {
+        if (ctx->d_req_desc) FR_HIP(hipFree(ctx->d_req_desc));
+        ctx->d_req_desc = nullptr;
+        ctx->req_shared.clear();
+        ctx->req_dense_shared = false;
+        for (fr_ctx::ReqForm &f : ctx->req_form) f = fr_ctx::ReqForm{};
+        return FR_OK;
+    }
+    std::vector<int32_t> mask(shared, shared + cols);
+    RequestTables rt;
+    const int irc = request_prepare(ctx, mask, dense_shared != 0, ctx->pool_cols > 0 ? ctx->pool_hots.data() : nullptr, rt);
+    if (irc) return irc;   // the split that was set stays
+    ctx->req_shared.swap(mask);
+    ctx->req_dense_shared = dense_shared != 0;
+    request_commit(ctx, rt);
+    return FR_OK;
+}
+
+// the form's table, or the reason there is none (FR_ERR_STATE)
+static int request_form(const fr_ctx *c, int form, const fr_ctx::ReqForm **out) {
+    if (c->req_shared.empty()) FR_FAIL(FR_ERR_STATE, "no request split is set on the context: call fr_ctx_set_request_columns first");
+    if (form == FR_REQ_POOLED && c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "the pooled request form needs pooling: call fr_ctx_set_pooling first");
+    if (form == FR_REQ_DENSE && !c->req_dense_shared) FR_FAIL(FR_ERR_STATE, "the dense request form needs dense_shared (fr_ctx_set_request_columns)");
+    *out = &c->req_form[form];
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_request_words(const fr_ctx *ctx, int form, int *req_words, int *cand_words, int *row_words) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (form < FR_REQ_ONE_HOT || form > FR_REQ_DENSE) FR_FAIL(FR_ERR_INVALID, "form %d is no request form", form);
+    const fr_ctx::ReqForm *f = nullptr;
+    const int rc = request_form(ctx, form, &f);
+    if (rc) return rc;
+    if (req_words) *req_words = f->req_words;
+    if (cand_words) *cand_words = f->cand_words;
+    if (row_words) *row_words = (int)f->desc.size();
+    return FR_OK;
+}
+
+// the one launch (the CPU back-end: the twin, computed here; malformed offsets wait in the sticky word)
+static int request_enqueue(fr_worker *w, const fr_ctx::ReqForm &f, int batch, int n_req, const int32_t *off, const void *req, const void *cand, void *out) {
+    fr_ctx *c = w->ctx;
+    FrRequestArgs a{};
+    a.off = off, a.req = static_cast<const uint32_t *>(req), a.cand = static_cast<const uint32_t *>(cand), a.out = static_cast<uint32_t *>(out);
+    a.batch = batch, a.n_req = n_req, a.W = (int)f.desc.size(), a.Rs = f.req_words, a.Rc = f.cand_words;
+    a.tile = fr_request_tile(a.W);
+    if (c->cpu) {
+        a.desc = f.desc.data(), a.err_flag = &w->c_err;
+        if (frc_expand_requests(a)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+        return FR_OK;
+    }
+    a.desc = c->d_req_desc + f.d_first, a.err_flag = w->d_err;
+    const int e = fr_request_launch(&a, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the request expansion launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_worker_expand_requests_device(fr_worker *w, int batch, int n_req, const int32_t *d_seg_offsets, const void *d_req_rows, const void *d_cand_rows, int form,
+                                                void *d_rows_out) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    if (batch <= 0 || batch > w->max_batch) FR_FAIL(FR_ERR_INVALID, "batch %d outside (0, max_batch=%d]", batch, w->max_batch);
+    if (n_req < 1 || n_req > (1 << 24)) FR_FAIL(FR_ERR_INVALID, "n_req = %d outside [1, 2^24]", n_req);
+    if (form < FR_REQ_ONE_HOT || form > FR_REQ_DENSE) FR_FAIL(FR_ERR_INVALID, "form %d is no request form", form);
+    if (!d_req_rows || !d_rows_out) FR_FAIL(FR_ERR_INVALID, "d_req_rows / d_rows_out is NULL");
+    const fr_ctx::ReqForm *f = nullptr;
+    const int rc = request_form(w->ctx, form, &f);
+    if (rc) return rc;
+    if (f->cand_words && !d_cand_rows) FR_FAIL(FR_ERR_INVALID, "d_cand_rows is NULL, the form has %d candidate words per item", f->cand_words);
+    if (!d_seg_offsets && batch % n_req) FR_FAIL(FR_ERR_INVALID, "NULL offsets ask for %d equal requests, batch %d is no multiple", n_req, batch);
+    const uint64_t bound = (uint64_t)4000 << 20;
+    if ((uint64_t)batch * f->desc.size() * 4 >= bound || (uint64_t)batch * (uint64_t)f->cand_words * 4 >= bound || (uint64_t)n_req * (uint64_t)f->req_words * 4 >= bound ||
+        ((uint64_t)n_req + 1) * 4 >= bound)
+        FR_FAIL(FR_ERR_INVALID, "request expansion: the expanded rows (%d x %zu words), the candidate rows, the request rows (%d x %d words) or the offsets reach 4000 MiB", batch,
+                f->desc.size(), n_req, f->req_words);
+    if (!w->ctx->cpu) FR_SET_DEVICE(w->ctx);
+    return request_enqueue(w, *f, batch, n_req, d_seg_offsets, d_req_rows, d_cand_rows, d_rows_out);
+}
+
+extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int pooled) {
+    int rc = check_ready(w, batch, true, true);
+    if (rc) return rc;
+    if (pooled < 0 || pooled > 2) FR_FAIL(FR_ERR_INVALID, "pooled = %d: 0 one-hot, 1 pooled, 2 pooled weighted", pooled);
+    if (n_req < 1 || n_req > w->max_batch) FR_FAIL(FR_ERR_INVALID, "n_req = %d outside [1, max_batch=%d]", n_req, w->max_batch);
+    fr_ctx *c = w->ctx;
+    const bool weighted = pooled == 2;
+    const fr_ctx::ReqForm *f = nullptr, *fd = nullptr;
+    rc = request_form(c, pooled ? FR_REQ_POOLED : FR_REQ_ONE_HOT, &f);
+    if (rc) return rc;
+    if (!w->h_req_idx || !w->h_req_off || (c->req_dense_shared && !w->h_req_dense) || !w->d_idx)
+        FR_FAIL(FR_ERR_STATE, "the worker has no request buffers: create the worker after fr_ctx_set_request_columns");
+    if (pooled) {
+        rc = pooled_host_ready(w, batch, weighted);
+        if (rc) return rc;
+        if (weighted && c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
+        if (weighted && (!w->h_req_w || !w->d_pool_w || w->req_w_cap < f->req_words))
+            FR_FAIL(FR_ERR_STATE, "the worker's request weight buffer holds %d words per request, the split needs %d: create the worker after fr_ctx_set_pooling and fr_ctx_set_request_columns",
+                    w->req_w_cap, f->req_words);
+    } else if (w->in_flight) {
+        FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
+    }
+    if (w->req_idx_cap < f->req_words)
+        FR_FAIL(FR_ERR_STATE, "the worker's request index buffer holds %d words per request, the split needs %d: create the worker after the split and the pooling are set", w->req_idx_cap,
+                f->req_words);
+    if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
+    if (c->req_dense_shared) {
+        rc = request_form(c, FR_REQ_DENSE, &fd);
+        if (rc) return rc;
+    }
+    // the host knows the offsets: the two ends are checked here, before anything is enqueued (the pair checks are the expansion's)
+    if (w->h_req_off[0] != 0) FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_requests: offsets[0] is %d, not 0", w->h_req_off[0]);
+    if (w->h_req_off[n_req] != batch) FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_requests: offsets[n_req] is %d, the batch has %d items", w->h_req_off[n_req], batch);
+    if (!c->cpu) FR_SET_DEVICE(c);
+    // up to three expansions read the pinned arrays in place and write the worker's device buffers; the unchanged submit runs behind them
+    rc = request_enqueue(w, *f, batch, n_req, w->h_req_off, w->h_req_idx, w->h_idx, w->d_idx);
+    if (!rc && weighted) rc = request_enqueue(w, *f, batch, n_req, w->h_req_off, w->h_req_w, w->h_pool_w, w->d_pool_w);
+    if (!rc && fd) rc = request_enqueue(w, *fd, batch, n_req, w->h_req_off, w->h_req_dense, nullptr, w->d_dense);
+    if (rc) return rc;
+    const float *dense = fd ? w->d_dense : (c->model.dense_len ? w->h_dense : nullptr);
+    if (pooled) rc = submit_pooled_impl(w, batch, w->d_idx, weighted ? w->d_pool_w : nullptr, weighted, dense, w->h_score);
+    else rc = launch_pipeline(w, batch, w->d_idx, dense, w->h_score);
+    if (rc) return rc;
+    w->in_flight = true, w->host_batch = batch;   // (fr_worker_topk ranks it)
     return FR_OK;
 }
 

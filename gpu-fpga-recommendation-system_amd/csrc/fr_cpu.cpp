@@ -525,3 +525,38 @@ void frc_slices_to_records(const float *gathered, int n_shards, int batch_total,
             memcpy(X + (size_t)i * K + offs[g], gathered + ((size_t)g * batch_total + item0 + i) * slice_padded, (size_t)lens[g] * sizeof(float));
     });
 }
+
+// ---- request-form batches: the CPU twin of request_expand_kernel (fr_request.hip) ------------------------------------------------------------
+// The same words for every input: the owner of item i is the same clamped binary search over off[0 .. n_req), so no byte outside off[0 .. n_req],
+// req[0 .. n_req * Rs), cand[0 .. batch * Rc) is read and none outside out[0 .. batch * W) written, whatever off holds.  -> 1: off was malformed.
+int frc_expand_requests(const FrRequestArgs &a) {
+    int bad = 0;
+    if (a.off) {
+        bad = a.off[0] != 0 || a.off[a.n_req] != a.batch;
+        for (int j = 0; j < a.n_req && !bad; j++) bad = a.off[j] > a.off[j + 1];
+    }
+    auto owner = [&](int i) {
+        int r = a.off ? 0 : i / (a.batch / a.n_req);
+        if (a.off) {
+            int lo = 0, hi = a.n_req;
+            while (lo < hi) {
+                const int mid = lo + ((hi - lo) >> 1);
+                if (a.off[mid] <= i) lo = mid + 1;
+                else hi = mid;
+            }
+            r = lo - 1;
+        }
+        return r < 0 ? 0 : (r >= a.n_req ? a.n_req - 1 : r);
+    };
+    Pool::get().run((a.batch + 255) / 256, [&](int u) {   // a unit = 256 items
+        for (int i = u * 256; i < a.batch && i < (u + 1) * 256; i++) {
+            const uint32_t *rq = a.req + (size_t)owner(i) * (size_t)a.Rs, *cd = a.Rc ? a.cand + (size_t)i * (size_t)a.Rc : nullptr;
+            uint32_t *o = a.out + (size_t)i * (size_t)a.W;
+            for (int w = 0; w < a.W; w++) {
+                const int d = a.desc[w];
+                o[w] = d >= 0 ? cd[d] : rq[~d];
+            }
+        }
+    });
+    return bad;
+}

@@ -216,6 +216,30 @@ static inline int fr_rank_units(int n) { return n > FR_RANK_PART ? 2 * ((n + FR_
 // Enqueues the ranking on `stream` (a hipStream_t); wave_form: one wave per segment instead of a 256-thread workgroup.  -> 0 or the hipError_t value.
 extern "C" int fr_rank_launch(const FrRankArgs *args, int wave_form, void *stream);
 
+// ---- request-form batches (fr_request.hip -> libfleetrec_request.so, the second companion code object; fr_cpu.cpp has the twin) ----------------
+// Row i of `out` ([batch][W] 32-bit words) is put together word by word: desc[w] >= 0 names word desc[w] of candidate row i ([batch][Rc]),
+// desc[w] < 0 names word ~desc[w] of the request row ([n_req][Rs]) of the request that owns item i -- the last r with off[r] <= i, clamped into
+// [0, n_req); off == NULL: n_req equal requests of batch / n_req items.  Words are bit copies.
+constexpr int FR_REQ_TILE_MAX = 64;      // items one workgroup expands at most (their owners sit in LDS)
+constexpr int FR_REQ_TILE_WORDS = 8192;  // output words a workgroup aims at: the tile is FR_REQ_TILE_WORDS / W items, 1 .. FR_REQ_TILE_MAX
+struct FrRequestArgs {
+    const int32_t *off;      // [n_req + 1] or NULL
+    const uint32_t *req;     // [n_req][Rs]
+    const uint32_t *cand;    // [batch][Rc]; may be NULL when Rc == 0
+    uint32_t *out;           // [batch][W]
+    const int32_t *desc;     // [W]
+    int batch, n_req;
+    int W, Rs, Rc;
+    int tile;                // items per workgroup, 1 .. FR_REQ_TILE_MAX
+    int *err_flag;           // raised when off is malformed (off[0] != 0, a decreasing pair, off[n_req] != batch)
+};
+static inline int fr_request_tile(int W) {
+    const int t = FR_REQ_TILE_WORDS / (W > 0 ? W : 1);
+    return t < 1 ? 1 : (t > FR_REQ_TILE_MAX ? FR_REQ_TILE_MAX : t);
+}
+// Enqueues the one expansion launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_request_launch(const FrRequestArgs *args, void *stream);
+
 // ---- host objects -------------------------------------------------------------------------------
 // Where a table's rows live inside ctx->table_arena.  A table stored on its own: row r at byte_offset + r * dim * 4 (il_rows == 0).
 // FR_INDEX_PER_BANK contexts interleave the tables of one memory bank: rows [0, il_rows) of every table of the bank share one
@@ -291,6 +315,16 @@ struct fr_ctx {
     std::vector<int32_t> pool_hots;        // hots per index column, as set
     std::vector<int32_t> pool_modes;       // FR_POOL_SUM / FR_POOL_MEAN per index column (fr_ctx_set_pooling_modes); in the descriptors as FR_POOL_DESC_MEAN
     bool pool_any_mean = false;            // a column is MEAN: the weighted entry points refuse
+    // Request-form batches (fr_ctx_set_request_columns): which index columns are the request's, and per form (FR_REQ_*) the per-word
+    // descriptor table of the expansion (FrRequestArgs::desc) with its three widths.  Rebuilt when the split or the pooling changes.
+    std::vector<int32_t> req_shared;       // [index columns] 0/1; empty: no split is set
+    bool req_dense_shared = false;
+    struct ReqForm {
+        std::vector<int32_t> desc;         // [row_words]; empty: the form is not available
+        int req_words = 0, cand_words = 0;
+        size_t d_first = 0;                // where the table starts inside d_req_desc
+    } req_form[3];
+    int32_t *d_req_desc = nullptr;         // the three tables, one after the other
     std::mutex workers_mutex;              // guards `workers`
     std::vector<struct fr_worker *> workers;   // live workers (fr_ctx_set_pooling asks each whether it has work in flight)
     unsigned long long *d_merged = nullptr;  // lookups merged by the dedup gather (FR_GATHER_ITEM_TILE_DEDUP_COUNT)
@@ -341,6 +375,13 @@ struct fr_worker {
     float *h_pool_w = nullptr;   // pinned [max_batch][pool_w_cap] per-sample weights of the host form (fr_worker_pool_weights_ptr); NULL without pooling at creation
     int pool_w_cap = 0;          // pooled columns at creation
     int32_t *h_pool_off = nullptr;   // pinned [max_batch * index columns + 1] bag offsets of the offsets-form host call (fr_worker_pool_offsets_ptr); NULL without pooling at creation
+    // Request-form host call (fr_worker_submit_requests): the request side's pinned buffers, there on a worker created after fr_ctx_set_request_columns
+    int32_t *h_req_idx = nullptr;    // [max_batch][req_idx_cap]
+    float *h_req_w = nullptr;        // [max_batch][req_w_cap]; NULL without pooling at creation
+    float *h_req_dense = nullptr;    // [max_batch][dense_len]; NULL unless dense_shared
+    int32_t *h_req_off = nullptr;    // [max_batch + 1]
+    int req_idx_cap = 0, req_w_cap = 0;   // request words per request at creation: max(Rs, Rs') and Rs'
+    float *d_pool_w = nullptr;       // [max_batch][pool_w_cap]: the expanded per-sample weights (host memory on the CPU back-end)
     // CPU back-end: a call computes before it returns; an index-range error stays in c_err until fr_worker_sync reports it
     float *c_scratch = nullptr;  // [max_batch][H1 + H2 + H3]
     float *c_x = nullptr;        // records of the sharded FC entry points, [max_batch][K]
@@ -460,6 +501,8 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
 int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src);
 // the CPU twin of fr_rank_launch: the same outputs bit for bit, segments over the pool's threads; -> 1 when a segment was malformed (ranked as empty), else 0
 int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int k, int32_t *top_idx, float *top_scores);
+// the CPU twin of fr_request_launch: the same words, items over the pool's threads; -> 1 when the offsets were malformed, else 0
+int frc_expand_requests(const FrRequestArgs &a);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \

@@ -19,6 +19,11 @@
 //                                      weights[nnz] with --pool weighted (the weights of those slots), then the dense rows)
 //                        [--topk K [--segments S]]  (with --reply, for fleetrec_server --topk K --segments S: a block's reply is S x K (int32 position, float32
 //                                      score) pairs instead of B scores; only the size of what is read changes)
+//                        [--requests S --shared-cols N [--shared-dense]]  (for fleetrec_server with the same three options: request-form blocks.  The block
+//                                      that would have been sent is cut into S equal requests; the first N index columns (x the --hots slots) of a
+//                                      request's first item, and with --shared-dense that item's dense row, become the request's row.  On the wire:
+//                                      int32 [S][request words], float32 [S][dense_len] with --shared-dense, int32 [B][candidate words], then the
+//                                      per-item dense rows where they are not shared.  With --topk the reply is S x K pairs: --segments defaults to S)
 //                        [--pool N]   (uniform indices: N distinct blocks per connection are generated up front and sent in rotation --
 //                                      drawing 12 k random indices per block is slower than the server; default 32, 0 = draw every block)
 #include <arpa/inet.h>
@@ -53,6 +58,8 @@ int main(int argc, char **argv) {
     int topk = 0, segments = 1;   // --topk K --segments S: the size of a block's reply
     int hots = 0;
     bool weighted = false, pool_mode = false, csr = false;
+    int requests = 0, shared_cols = 0;   // --requests S --shared-cols N [--shared-dense]: request-form blocks
+    bool shared_dense = false, segments_given = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> const char * { return (i + 1 < argc) ? argv[++i] : ""; };
@@ -78,10 +85,18 @@ int main(int argc, char **argv) {
         else if (a == "--ragged") ragged = true;
         else if (a == "--csr") csr = true;
         else if (a == "--topk") topk = atoi(next());
-        else if (a == "--segments") segments = atoi(next());
+        else if (a == "--segments") segments = atoi(next()), segments_given = true;
+        else if (a == "--requests") requests = atoi(next());
+        else if (a == "--shared-cols") shared_cols = atoi(next());
+        else if (a == "--shared-dense") shared_dense = true;
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     if (hots < 0 || hots > FR_POOL_MAX_HOTS) { fprintf(stderr, "--hots: 1 .. %d slots per index column, not %d\n", FR_POOL_MAX_HOTS, hots); return 2; }
+    if (requests == 0 && (shared_cols != 0 || shared_dense)) { fprintf(stderr, "--shared-cols / --shared-dense need --requests S\n"); return 2; }
+    if (requests != 0 && (requests < 1 || batch % requests != 0)) { fprintf(stderr, "--requests %d: a block of --batch %d items must divide into S >= 1 equal requests\n", requests, batch); return 2; }
+    if (requests > 0 && (csr || weighted)) { fprintf(stderr, "--requests is not sent with --csr or --pool weighted\n"); return 2; }
+    if (requests > 0 && topk > 0 && segments_given && segments != requests) { fprintf(stderr, "--requests %d with --segments %d: the segments of the ranking are the requests\n", requests, segments); return 2; }
+    if (requests > 0 && topk > 0) segments = requests;
     if (topk < 0 || topk > FR_TOPK_MAX_K || segments < 1 || (topk == 0 && segments != 1)) {
         fprintf(stderr, "--topk K --segments S: K = 1 .. %d, S >= 1 (with --topk), not %d / %d\n", FR_TOPK_MAX_K, topk, segments);
         return 2;
@@ -105,6 +120,11 @@ int main(int argc, char **argv) {
     } else if (!per_item) {
         for (size_t c = 0; c < cols; c++) col_range[c] = m->tables[c].rows;
     }
+    if (requests > 0 && (shared_cols < (shared_dense ? 0 : 1) || shared_cols > (int)cols - 1 || (shared_dense && !m->dense_len))) {
+        fprintf(stderr, "--shared-cols %d%s: the model has %zu index columns and %d dense floats; something must be shared and something left per item\n", shared_cols,
+                shared_dense ? " --shared-dense" : "", cols, m->dense_len);
+        return 2;
+    }
     std::vector<std::thread> th;
     std::vector<long> sent(threads, 0);
     std::vector<std::vector<double>> lat_us(threads);  // --reply --window W: request sent -> reply received, per request
@@ -116,6 +136,8 @@ int main(int argc, char **argv) {
                 const size_t b = q / (cols * slots), c = q / slots % cols, j = q % slots;
                 wts[q] = 0.25f * (float)(1 + (b + c + 2 * j) % 4);
             }
+            std::vector<int32_t> r_req, r_cand;   // --requests: the block in the request form
+            std::vector<float> r_dense;
             std::vector<int32_t> c_off, c_ind;   // --csr: the block in the offsets form
             std::vector<float> c_wt;
             std::vector<float> dense((size_t)batch * m->dense_len), scores(reply_floats);
@@ -188,7 +210,18 @@ int main(int argc, char **argv) {
                     t_send[(size_t)(n_sent.load(std::memory_order_relaxed) % window)] = std::chrono::steady_clock::now();
                 }
                 const auto t_req = std::chrono::steady_clock::now();
-                if (csr) {   // the block's bags without their empty slots: offsets, entries (, the entries' weights)
+                if (requests > 0) {   // request rows, their dense rows, candidate rows; the per-item dense rows follow below
+                    const size_t W = cols * slots, rs = (size_t)shared_cols * slots, per = (size_t)(batch / requests);
+                    r_req.clear(), r_cand.clear(), r_dense.clear();
+                    for (size_t r = 0; r < (size_t)requests; r++) {
+                        r_req.insert(r_req.end(), bi + r * per * W, bi + r * per * W + rs);
+                        if (shared_dense) r_dense.insert(r_dense.end(), bd + r * per * m->dense_len, bd + (r * per + 1) * m->dense_len);
+                    }
+                    for (size_t b = 0; b < (size_t)batch; b++) r_cand.insert(r_cand.end(), bi + b * W + rs, bi + (b + 1) * W);
+                    if (!r_req.empty() && send(sock, r_req.data(), r_req.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                    if (!r_dense.empty() && send(sock, r_dense.data(), r_dense.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                    if (!r_cand.empty() && send(sock, r_cand.data(), r_cand.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                } else if (csr) {   // the block's bags without their empty slots: offsets, entries (, the entries' weights)
                     c_off.clear(), c_ind.clear(), c_wt.clear();
                     c_off.push_back(0);
                     for (size_t bag = 0; bag < (size_t)batch * cols; bag++) {
@@ -206,7 +239,7 @@ int main(int argc, char **argv) {
                     if (send(sock, bi, idx.size() * 4, MSG_NOSIGNAL) <= 0) break;
                     if (!wts.empty() && send(sock, wts.data(), wts.size() * 4, MSG_NOSIGNAL) <= 0) break;
                 }
-                if (!dense.empty() && send(sock, bd, dense.size() * 4, MSG_NOSIGNAL) <= 0) break;
+                if (!dense.empty() && !shared_dense && send(sock, bd, dense.size() * 4, MSG_NOSIGNAL) <= 0) break;
                 sent[t]++;
                 n_sent.fetch_add(1, std::memory_order_release);
                 if (interval_us > 0 && !(reply && !async_reply)) usleep((useconds_t)interval_us);  // rate limit of the latency experiment (reference sender: usleep(useconds))

@@ -37,6 +37,14 @@
 //                        Legal on the submit-and-sync path, with --hots in every --pool form and --csr, and with --device -1.  Not with --stream
 //                        (its blocks are host-fed: no host-form batch is in flight to rank) and not with --shards (the scores of a sharded step are
 //                        gathered over the communicator, outside the worker's stream order) (fleetrec_sender --topk K --segments S).
+//        [--requests S --shared-cols N [--shared-dense]]: request-form blocks (fr_ctx_set_request_columns / fr_worker_submit_requests).  The first N index
+//                        columns are the request's, with --shared-dense the dense features too; a block is S equal requests of batch / S candidates
+//                        (batch % S == 0).  On the wire: int32 [S][Rs] request rows, then float32 [S][dense_len] with --shared-dense, then int32 [B][Rc]
+//                        candidate rows, then the per-item dense rows where they are not shared (Rs = N, Rc = index columns - N; with --hots H both x H,
+//                        and the call is fr_worker_submit_requests(..., pooled = 1) in the sum or mean fold).  The rows are expanded on the device; the
+//                        scores, and with --topk K the S x K pairs of the reply (--segments, if given, must equal S; omitted it is S), are those of the
+//                        expanded block.  Not with --stream, --shards, --csr or --pool weighted; N = 1 .. index columns - 1 unless --shared-dense
+//                        (fleetrec_sender takes the same three options).
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
@@ -89,6 +97,10 @@ struct Options {
     int topk = 0;          // --topk K: every block is ranked on the device, K per request (0: plain scores)
     bool topk_given = false;
     int segments = 1;      // --segments S: requests per block (with --topk)
+    bool segments_given = false;
+    int requests = 0;      // --requests S: request-form blocks of S equal requests (0: full rows)
+    int shared_cols = 0;   // --shared-cols N: the first N index columns are the request's
+    bool shared_cols_given = false, shared_dense = false;   // --shared-dense: the dense features are the request's too
 };
 
 static bool read_exact(int fd, void *buf, size_t n) {  // the recv loop of cuda_server.c:425-450
@@ -266,6 +278,20 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
     const size_t idx_cols = o.hots > 0 ? (size_t)fr_ctx_pooled_index_cols(t->ctx) : (size_t)fr_model_index_cols(m);
     const size_t idx_bytes = (size_t)o.batch * idx_cols * sizeof(int32_t);
     const size_t dense_bytes = (size_t)o.batch * m->dense_len * sizeof(float);
+    // --requests: what a block carries per request and per candidate, and the (equal) requests' offsets in the worker's pinned buffer
+    int rq_words = 0, cand_words = 0;
+    if (o.requests > 0) {
+        int32_t *roff = fr_worker_request_offsets_ptr(wk);
+        if (fr_ctx_request_words(t->ctx, o.hots > 0 ? FR_REQ_POOLED : FR_REQ_ONE_HOT, &rq_words, &cand_words, nullptr) != FR_OK || !roff) {
+            t->status = -1;
+            t->error = roff ? fr_last_error() : "the worker has no request buffers";
+            fr_worker_destroy(wk);
+            return;
+        }
+        for (int r = 0; r <= o.requests; r++) roff[r] = r * (o.batch / o.requests);
+    }
+    const size_t rq_bytes = (size_t)o.requests * (size_t)rq_words * sizeof(int32_t), rq_dense_bytes = o.shared_dense ? (size_t)o.requests * m->dense_len * sizeof(float) : 0;
+    const size_t cand_bytes = (size_t)o.batch * (size_t)cand_words * sizeof(int32_t);
     const size_t weight_bytes = o.pool == 2 ? (size_t)o.batch * idx_cols * sizeof(float) : 0;   // --pool weighted: the weights follow the index rows
     // --topk K --segments S: the requests of a block, what fr_worker_sync delivers for them and the (position, score) pairs of the reply
     std::vector<int32_t> seg_off((size_t)o.segments + 1), top_idx(o.topk > 0 ? (size_t)o.segments * (size_t)o.topk : 0);
@@ -478,6 +504,13 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                     t->error = "Receiving data UNSUCCESSFUL (peer closed before the batch was complete)";
                     break;
                 }
+            } else if (o.requests > 0) {   // request rows (, their dense rows), candidate rows (, the per-item dense rows)
+                if ((rq_bytes && !read_exact(sock, fr_worker_request_idx_ptr(wk), rq_bytes)) || (rq_dense_bytes && !read_exact(sock, fr_worker_request_dense_ptr(wk), rq_dense_bytes)) ||
+                    (cand_bytes && !read_exact(sock, fr_worker_idx_ptr(wk), cand_bytes)) || (dense_bytes && !o.shared_dense && !read_exact(sock, fr_worker_dense_ptr(wk), dense_bytes))) {
+                    t->status = -4;
+                    t->error = "Receiving data UNSUCCESSFUL (peer closed before the batch was complete)";
+                    break;
+                }
             } else if (!read_exact(sock, fr_worker_idx_ptr(wk), idx_bytes) || (weight_bytes && !read_exact(sock, fr_worker_pool_weights_ptr(wk), weight_bytes)) ||
                        (dense_bytes && !read_exact(sock, fr_worker_dense_ptr(wk), dense_bytes))) {
                 t->status = -4;
@@ -485,7 +518,7 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 break;
             }
             const auto t_recv = std::chrono::steady_clock::now();  // network_time / cuda_time pair of cuda_server.c:429,462
-            if ((o.csr ? fr_worker_submit_pooled_csr(wk, o.batch, o.pool == 2) : weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
+            if ((o.requests > 0 ? fr_worker_submit_requests(wk, o.batch, o.requests, o.hots > 0 ? 1 : 0) : o.csr ? fr_worker_submit_pooled_csr(wk, o.batch, o.pool == 2) : weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
                 t->status = -5;
                 t->error = fr_last_error();
                 break;
@@ -554,7 +587,10 @@ int main(int argc, char **argv) {
         else if (a == "--csr") o.csr = true;
         else if (a == "--update-port") o.update_port = atoi(next());
         else if (a == "--topk") { o.topk = atoi(next()); o.topk_given = true; }
-        else if (a == "--segments") o.segments = atoi(next());
+        else if (a == "--segments") { o.segments = atoi(next()); o.segments_given = true; }
+        else if (a == "--requests") o.requests = atoi(next());
+        else if (a == "--shared-cols") { o.shared_cols = atoi(next()); o.shared_cols_given = true; }
+        else if (a == "--shared-dense") o.shared_dense = true;
         else if (a == "--pool") {
             std::string v = next();
             if (v != "sum" && v != "mean" && v != "weighted") { fprintf(stderr, "--pool: sum, mean or weighted, not '%s'\n", v.c_str()); return 2; }
@@ -573,6 +609,21 @@ int main(int argc, char **argv) {
     if (o.hots > 0 && (o.stream || o.shards > 0)) {
         fprintf(stderr, "--hots (pooled lookups) serves the submit-and-sync path only: not with --stream or --shards (their producers are one-hot)\n");
         return 2;
+    }
+    if (o.requests == 0 && (o.shared_cols_given || o.shared_dense)) { fprintf(stderr, "--shared-cols / --shared-dense need --requests S\n"); return 2; }
+    if (o.requests != 0) {   // request-form blocks: the submit-and-sync path, full or padded pooled rows, unweighted
+        const char *with = o.stream ? "--stream (its blocks are host-fed full rows)" : o.shards > 0 ? "--shards (a sharded context takes no request split)" :
+                           o.csr ? "--csr (the request form cuts padded rows)" : o.pool == 2 ? "--pool weighted" : nullptr;
+        if (with) { fprintf(stderr, "--requests is not served with %s\n", with); return 2; }
+        if (o.requests < 1 || o.batch % o.requests != 0) {
+            fprintf(stderr, "--requests %d: a block of --batch %d candidates must divide into S >= 1 equal requests (batch %% S == 0)\n", o.requests, o.batch);
+            return 2;
+        }
+        if (o.topk > 0 && o.segments_given && o.segments != o.requests) {
+            fprintf(stderr, "--requests %d with --topk --segments %d: the segments of the ranking are the requests (omit --segments, or give S)\n", o.requests, o.segments);
+            return 2;
+        }
+        if (o.topk > 0) o.segments = o.requests;
     }
     if (o.segments != 1 && o.topk <= 0) { fprintf(stderr, "--segments S needs --topk K\n"); return 2; }
     if (o.topk_given && (o.topk < 1 || o.topk > FR_TOPK_MAX_K)) { fprintf(stderr, "--topk: 1 .. %d ranked scores per request, not %d\n", FR_TOPK_MAX_K, o.topk); return 2; }
@@ -651,6 +702,26 @@ int main(int argc, char **argv) {
         printf("pooled lookups: %d slots on each of %zu index columns, %d int32 per item\n", o.hots, hots.size(), fr_ctx_pooled_index_cols(ctx));
         if (o.csr) printf("offsets-form blocks: int32 offsets[batch x %zu + 1], indices[nnz]%s\n", hots.size(), o.pool == 2 ? ", float32 weights[nnz]" : "");
         if (o.pool > 0) printf("pooling: %s\n", o.pool == 1 ? "mean" : "weighted (float32 weights follow every block's index rows)");
+    }
+    if (o.requests > 0) {   // before the threads create their workers: a worker gets its request buffers at creation
+        const int cols = fr_model_index_cols(model);
+        if (o.shared_cols < (o.shared_dense ? 0 : 1) || o.shared_cols > cols - 1) {
+            fprintf(stderr, "--requests with --shared-cols %d: the model has %d index columns, N = 1 .. %d (from 0 with --shared-dense)\n", o.shared_cols, cols, cols - 1);
+            return 2;
+        }
+        std::vector<int32_t> shared((size_t)cols, 0);
+        for (int c = 0; c < o.shared_cols; c++) shared[(size_t)c] = 1;
+        int rs = 0, rc = 0, w = 0;
+        if (fr_ctx_set_request_columns(ctx, shared.data(), cols, o.shared_dense ? 1 : 0) != FR_OK ||
+            fr_ctx_request_words(ctx, o.hots > 0 ? FR_REQ_POOLED : FR_REQ_ONE_HOT, &rs, &rc, &w) != FR_OK) {
+            fprintf(stderr, "set-up failed (--requests --shared-cols %d%s): %s\n", o.shared_cols, o.shared_dense ? " --shared-dense" : "", fr_last_error());
+            return 2;
+        }
+        const size_t full = (size_t)o.batch * ((size_t)w + (size_t)model->dense_len) * 4;
+        const size_t form = ((size_t)o.requests * (size_t)rs + (size_t)o.batch * (size_t)rc) * 4 +
+                            (size_t)(o.shared_dense ? o.requests : o.batch) * (size_t)model->dense_len * 4;
+        printf("request-form blocks: %d requests of %d candidates, %d request + %d candidate words%s; %zu bytes per block (%zu as full rows)\n", o.requests,
+               o.batch / o.requests, rs, rc, o.shared_dense ? ", dense features shared" : "", form, full);
     }
     if (o.stream && o.reply && !g_engine && fr_ctx_set_small_block(ctx, o.small_block) != FR_OK) {
         fprintf(stderr, "set-up failed: %s\n", fr_last_error());

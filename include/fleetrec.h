@@ -47,6 +47,9 @@ extern "C" {
  * Still 6, additive: streaming pushes of the pooled lookups (fleetrec_serving.h: fr_worker_push_pooled_device, fr_worker_push_pooled_csr_device,
  * fr_worker_push_pooled_device_list) -- the submit forms and every one-hot push are as before.
  * Still 6, additive: segmented device-side top-K ranking of scores (fleetrec_serving.h: fr_worker_topk_device, fr_worker_topk) -- every score is as before.
+ * Still 6, additive: request-form batches, request rows + candidate rows + segment offsets expanded on the device (fleetrec_serving.h:
+ * fr_ctx_set_request_columns, fr_ctx_request_words, fr_worker_expand_requests_device, fr_worker_request_*_ptr, fr_worker_submit_requests) -- every
+ * existing entry point is as before, with or without a split.
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile
  * shape of a chain model no longer follows the number of live workers).
  * 4 (round 4): the surface is three headers -- this one (the three spans of thread_consume() that SURVEY section 8(b) cuts, the request

@@ -285,6 +285,66 @@ int fr_worker_topk_device(fr_worker *w, int n, const float *d_scores, int n_seg,
 int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t *h_seg_offsets /* NULL: one segment */,
                    int k, int32_t *h_top_idx, float *h_top_scores /* or NULL */);
 
+/* Request-form batches (additive in ABI 6): the input side of the segments above.  A request is one user and N candidate items; without this its
+ * batch arrives as N complete index rows, the user's columns (and dense features) repeated N times.  With a SPLIT set on the context a batch arrives
+ * as request rows + candidate rows + segment offsets, and one small launch expands them on the device into the rows every existing lookup path takes.
+ * The expanded rows are, bit for bit, the rows a host-side expansion would have produced; nothing downstream changes.
+ * Split: C = fr_model_index_cols(model); shared[C] of 0/1 says which index columns are the request's -- tables, banks or the single per-item column.
+ *   One-hot form (FR_REQ_ONE_HOT): the request row is int32 [Rs], the shared columns in ascending column order; the candidate row int32 [Rc], the
+ *   others in ascending order; Rs + Rc = C.
+ *   Pooled form (FR_REQ_POOLED): column c contributes hots[c] consecutive words, slot-minor, exactly as in the pooled row: request row [Rs'],
+ *   candidate row [Rc'], Rs' + Rc' = P.  Per-sample weights have the same shape, as float, and take the same call.
+ *   Dense form (FR_REQ_DENSE): when the context says dense_shared the request carries float [dense_len] once; otherwise dense rows stay per item.
+ * Segments: seg_offsets int32 [n_req + 1] is the array fr_worker_topk* takes: request r owns items [off[r], off[r + 1]).  Well formed: off[0] == 0,
+ *   non-decreasing, off[n_req] == batch.  Empty requests are legal.  NULL: n_req equal requests of batch / n_req items.
+ * Expansion: row i of the output ([batch][C], [batch][P] or [batch][dense_len]) is the full row the existing entry points define: every word of a
+ *   shared column from the request row of the request that owns item i, every other word from candidate row i.  Words are 32-BIT BIT COPIES, never
+ *   interpreted: a -1 (empty slot), any negative value, a NaN weight, an out-of-range index arrive as they were, and the gather behind the expansion
+ *   keeps reporting what it reports today.  Only 4-byte alignment of every array is assumed.
+ * Malformed offsets (any of the three conditions violated): FR_ERR_INDEX_RANGE at fr_worker_sync (the worker's sticky word; the worker is usable
+ *   afterwards).  The expanded rows of that call are unspecified but for this: every word written is a copy of some word of the request or
+ *   candidate arrays passed in; no byte is read outside off[0 .. n_req], req[0 .. n_req x Rs), cand[0 .. batch x Rc); no byte is written outside
+ *   out[0 .. batch x W) -- the owning request is always some r in [0, n_req), clamped, never trusted.
+ * fr_ctx_set_request_columns: shared == NULL clears the split.  FR_ERR_INVALID: a wrong n_cols, a mask value other than 0/1, dense_shared other
+ *   than 0/1 or 1 on a model without dense features, nothing shared at all (no shared column and no shared dense), nothing left per item (every
+ *   column shared and no per-item dense).  FR_ERR_STATE: a worker of the context has work in flight (the rule of fr_ctx_set_pooling), a context
+ *   with n_shards > 1.  The split survives fr_ctx_set_pooling / fr_ctx_set_pooling_modes: pooled widths always follow the current hots.  Every
+ *   existing entry point behaves exactly as before, whether or not a split is set.
+ * fr_ctx_request_words: the three widths of a form (any pointer may be NULL).  FR_ERR_STATE: no split set, the pooled form without pooling, the
+ *   dense form without dense_shared.
+ * fr_worker_expand_requests_device: the primitive.  Asynchronous on the worker's stream, fr_worker_sync is the completion point (the CPU back-end
+ *   computes before it returns; malformed offsets wait in the sticky word, as the ranking's do).  It enqueues the one launch and nothing else: queued
+ *   fused batches are not flushed and the stage pipeline is not drained -- it orders nothing behind earlier work.  The caller owns d_rows_out under
+ *   the buffer-lifetime rule of fr_worker_push_device.  A following fr_worker_gather_only, submit_device, push_device, gather_pooled*,
+ *   submit_pooled*_device or push_pooled_device* ON THE SAME WORKER with d_rows_out as its d_idx / d_weights / d_dense reads the expanded rows: that
+ *   is the streaming form, no new push entry point is needed.
+ *   FR_ERR_INVALID: a NULL worker, batch outside 1 .. max_batch, n_req outside 1 .. 2^24, an unknown form, a NULL d_req_rows or d_rows_out, a NULL
+ *   d_cand_rows where the form has candidate words, NULL offsets with batch % n_req != 0, an array reaching the 4000 MiB bound of the pooled calls.
+ *   FR_ERR_STATE: the cases of fr_ctx_request_words.  Nothing is enqueued on an argument or state error.  fr_worker_last_kernel keeps naming the last
+ *   batch's kernel.
+ * fr_worker_submit_requests: the host form.  Candidate rows packed [batch][Rc or Rc'] in fr_worker_idx_ptr, candidate weights in
+ *   fr_worker_pool_weights_ptr (pooled weighted only), per-item dense in fr_worker_dense_ptr unless dense_shared; the request side packed
+ *   [n_req][Rs or Rs'] / [n_req][dense_len] in the four buffers below; offsets always explicit.  On the host, before anything is enqueued: off[0] != 0,
+ *   off[n_req] != batch or n_req outside 1 .. max_batch is FR_ERR_INVALID; the pair checks remain the kernel's.  The expansion reads the pinned arrays
+ *   in place and writes worker-owned device buffers; the existing chain (fr_worker_submit_device's, or fr_worker_submit_pooled*_device's) then runs on
+ *   them with the pinned score buffer as destination: up to three expansion launches plus the unchanged submit.  It counts as the host-form batch in
+ *   flight, so fr_worker_topk(w, batch, n_req, the same offsets, k, ...) ranks every request's candidates.  One batch in flight per worker, as for
+ *   fr_worker_submit.  The four buffers exist on a worker created AFTER fr_ctx_set_request_columns (pinned; host memory on the CPU back-end): on an
+ *   older worker the accessors return NULL and the call returns FR_ERR_STATE; for the pooled forms the worker must also be created after
+ *   fr_ctx_set_pooling, as today.  Pooled weighted on a context with a MEAN column: FR_ERR_STATE, as today. */
+#define FR_REQ_ONE_HOT 0
+#define FR_REQ_POOLED  1   /* pooled index rows AND per-sample weight rows (same shape, bit copies) */
+#define FR_REQ_DENSE   2   /* request dense rows -> per-item dense rows; needs dense_shared */
+int fr_ctx_set_request_columns(fr_ctx *ctx, const int32_t *shared /* [n_cols] 0/1; NULL clears */, int n_cols, int dense_shared);
+int fr_ctx_request_words(const fr_ctx *ctx, int form, int *req_words, int *cand_words, int *row_words);
+int fr_worker_expand_requests_device(fr_worker *w, int batch, int n_req, const int32_t *d_seg_offsets /* NULL: equal */, const void *d_req_rows,
+                                     const void *d_cand_rows /* NULL for FR_REQ_DENSE */, int form, void *d_rows_out);
+int32_t *fr_worker_request_idx_ptr(fr_worker *w);      /* pinned int32 [max_batch][max(Rs, Rs')] */
+float *fr_worker_request_weights_ptr(fr_worker *w);    /* pinned float [max_batch][Rs'], NULL without pooling at creation */
+float *fr_worker_request_dense_ptr(fr_worker *w);      /* pinned float [max_batch][dense_len], NULL unless dense_shared */
+int32_t *fr_worker_request_offsets_ptr(fr_worker *w);  /* pinned int32 [max_batch + 1] */
+int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int pooled /* 0 one-hot, 1 pooled, 2 pooled weighted */);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
