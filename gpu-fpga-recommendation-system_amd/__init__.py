@@ -9,6 +9,7 @@ FleetRecError; Context(model, device=DEVICE_CPU) asks for the library's own CPU 
 Vocabulary follows the reference: tables, banks, rounds, records (the per-item concatenated
 feature vector the FPGA sends), workers (thread_consume), batches.
 """
+import contextlib
 import ctypes
 import os
 
@@ -792,7 +793,8 @@ class Worker:
         idx = self._pooled_rows(idx)
         B, P = idx.shape
         if P > self._pool_cap or (weights is not None and P > self._pool_w_cap):
-            raise FleetRecError(FR_ERR_STATE, "the worker's pooled buffers hold %d columns per item, pooled rows have %d" % (self._pool_cap, P))
+            raise FleetRecError(FR_ERR_STATE, "the worker's index buffer holds %d columns per item, pooled rows have %d: create the worker "
+                                "after Context.set_pooling" % (self._pool_cap, P))
         if B > self.max_batch:
             raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
         np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(B, P))[:] = idx
@@ -806,9 +808,11 @@ class Worker:
         """The offsets host form of a pooled batch into the pinned buffers (offsets int32 [B * C + 1], indices int32 [nnz], weights float32 [nnz]); -> B."""
         B, off, ind, w = self._csr_arrays(offsets, indices, weights)
         if self.pool_offsets is None or (w is not None and self.pool_weights is None):
-            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker on a context with pooling set")
-        if B > self.max_batch or ind.size > self.max_batch * self._pool_cap:
-            raise FleetRecError(FR_ERR_INVALID, "batch %d / %d indices exceed the worker's buffers" % (B, ind.size))
+            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after Context.set_pooling")
+        if B > self.max_batch:
+            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
+        if ind.size > self.max_batch * self._pool_cap:
+            raise FleetRecError(FR_ERR_INVALID, "%d indices exceed the worker's index buffer (%d x %d)" % (ind.size, self.max_batch, self._pool_cap))
         self.pool_offsets[:off.size] = off
         np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:ind.size] = ind
         if w is not None:
@@ -1007,18 +1011,7 @@ class Worker:
         """Host-buffer path of the pooled lookup: idx int32 [B][pooled_index_cols] (-1 = empty slot) (+ dense) -> scores float32 [B].
         weights: float32 [B][pooled_index_cols], the weight of every slot (all-SUM contexts only).
         The worker must have been created after Context.set_pooling (its pinned index and weight buffers are sized then)."""
-        idx = self._pooled_rows(idx)
-        B, P = idx.shape
-        if P > self._pool_cap or (weights is not None and P > self._pool_w_cap):
-            raise FleetRecError(FR_ERR_STATE, "the worker's index buffer holds %d columns per item, pooled rows have %d: create the worker "
-                                "after Context.set_pooling" % (self._pool_cap, P))
-        if B > self.max_batch:
-            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
-        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(B, P))[:] = idx
-        if weights is not None:
-            np.ctypeslib.as_array(lib().fr_worker_pool_weights_ptr(self._h), shape=(B, P))[:] = self._pooled_weights(weights, idx)
-        if self.dense is not None:
-            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        B = self.load_pooled(idx, dense, weights)
         self.submit_pooled(B, weighted=weights is not None)
         self.sync()
         return self.score[:B].copy()
@@ -1026,17 +1019,28 @@ class Worker:
     def gather_pooled_records(self, idx, dense=None, weights=None):
         """-> uint32 [flat B*K] record buffer in the model's layout: the pooled records of idx int32 [B][pooled_index_cols]
         (weights: float32 of the same shape, the weight of every slot)."""
-        ctx, m = self.ctx, self.ctx.model
         idx = self._pooled_rows(idx)
-        B = idx.shape[0]
-        d_idx = DeviceBuffer.from_numpy(ctx, idx)
-        d_w = DeviceBuffer.from_numpy(ctx, self._pooled_weights(weights, idx)) if weights is not None else None
-        d_dense = DeviceBuffer.from_numpy(ctx, np.asarray(dense, dtype=np.float32)) if m.dense_len else None
-        n = B * m.record_len
-        d_rec = DeviceBuffer(ctx, n * 4)
-        self.gather_pooled(B, d_idx, d_dense, d_rec, weights=d_w)
-        self.sync()
-        return d_rec.download(np.uint32, n)
+        n = len(idx) * self.ctx.model.record_len
+        with self._on_device(n, dense, idx=idx, w=self._pooled_weights(weights, idx) if weights is not None else None) as d:
+            self.gather_pooled(len(idx), d["idx"], d["dense"], d["rec"], weights=d["w"])
+            self.sync()
+            return d["rec"].download(np.uint32, n)
+
+    @contextlib.contextmanager
+    def _on_device(self, n_rec, dense, **arrays):
+        """-> {name: device copy of the host array (None stays None)} + "dense" (the dense features, None without) + "rec" (room for n_rec record
+        words); every buffer is freed on the way out, also when an allocation fails part-way"""
+        ctx, d = self.ctx, {}
+        try:
+            for name, a in arrays.items():
+                d[name] = DeviceBuffer.from_numpy(ctx, a) if a is not None else None
+            d["dense"] = DeviceBuffer.from_numpy(ctx, np.asarray(dense, dtype=np.float32)) if ctx.model.dense_len else None
+            d["rec"] = DeviceBuffer(ctx, n_rec * 4)
+            yield d
+        finally:
+            for b in d.values():
+                if b is not None:
+                    b.free()
 
     # the offsets (CSR) form of the pooled lookups: bag (b, c) = indices[offsets[b * C + c] : offsets[b * C + c + 1]], C = model.idx_cols ----
     def gather_pooled_csr(self, batch, d_offsets, d_indices, nnz, d_dense, d_records, weights=None):
@@ -1105,41 +1109,19 @@ class Worker:
     def infer_pooled_csr(self, offsets, indices, dense=None, weights=None):
         """Host-buffer path of the offsets-form pooled lookup: offsets int32 [B * C + 1], indices int32 [nnz] (-1 = empty slot), weights float32
         [nnz] or None (+ dense) -> scores float32 [B].  The worker must have been created after Context.set_pooling."""
-        B, off, ind, w = self._csr_arrays(offsets, indices, weights)
-        if self.pool_offsets is None or (w is not None and self.pool_weights is None):
-            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after Context.set_pooling")
-        if B > self.max_batch:
-            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
-        if ind.size > self.max_batch * self._pool_cap:
-            raise FleetRecError(FR_ERR_INVALID, "%d indices exceed the worker's index buffer (%d x %d)" % (ind.size, self.max_batch, self._pool_cap))
-        self.pool_offsets[:off.size] = off
-        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:ind.size] = ind
-        if w is not None:
-            self.pool_weights.reshape(-1)[:w.size] = w
-        if self.dense is not None:
-            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
-        self.submit_pooled_csr(B, weighted=w is not None)
+        B = self.load_pooled_csr(offsets, indices, dense, weights)
+        self.submit_pooled_csr(B, weighted=weights is not None)
         self.sync()
         return self.score[:B].copy()
 
     def gather_pooled_csr_records(self, offsets, indices, dense=None, weights=None):
         """-> uint32 [flat B*K] record buffer in the model's layout: the pooled records of the bags offsets / indices (/ weights) describe."""
-        ctx, m = self.ctx, self.ctx.model
         B, off, ind, w = self._csr_arrays(offsets, indices, weights)
-        d_off = DeviceBuffer.from_numpy(ctx, off)
-        d_ind = DeviceBuffer.from_numpy(ctx, ind) if ind.size else None
-        d_w = DeviceBuffer.from_numpy(ctx, w if w.size else np.zeros(1, np.float32)) if w is not None else None
-        d_dense = DeviceBuffer.from_numpy(ctx, np.asarray(dense, dtype=np.float32)) if m.dense_len else None
-        n = B * m.record_len
-        d_rec = DeviceBuffer(ctx, n * 4)
-        try:
-            self.gather_pooled_csr(B, d_off, d_ind, ind.size, d_dense, d_rec, weights=d_w)
+        n = B * self.ctx.model.record_len
+        with self._on_device(n, dense, off=off, ind=ind if ind.size else None, w=(w if w.size else np.zeros(1, np.float32)) if w is not None else None) as d:
+            self.gather_pooled_csr(B, d["off"], d["ind"], ind.size, d["dense"], d["rec"], weights=d["w"])
             self.sync()
-            return d_rec.download(np.uint32, n)
-        finally:
-            for b in (d_off, d_ind, d_w, d_dense, d_rec):
-                if b is not None:
-                    b.free()
+            return d["rec"].download(np.uint32, n)
 
     # segmented top-K ranking of scores (fr_worker_topk_device / fr_worker_topk) ------------------------------------------------
     def topk_device(self, n, d_scores, k, d_top_idx, d_top_scores=None, d_seg_offsets=None, n_seg=1):
@@ -1178,37 +1160,14 @@ class Worker:
 
     def infer_pooled_topk(self, idx, k, seg_offsets=None, dense=None, weights=None):
         """infer_pooled() with the ranking on the device (arguments of infer_pooled; k / seg_offsets / result of infer_topk)."""
-        idx = self._pooled_rows(idx)
-        B, P = idx.shape
-        if P > self._pool_cap or (weights is not None and P > self._pool_w_cap):
-            raise FleetRecError(FR_ERR_STATE, "the worker's index buffer holds %d columns per item, pooled rows have %d: create the worker "
-                                "after Context.set_pooling" % (self._pool_cap, P))
-        if B > self.max_batch:
-            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
-        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(B, P))[:] = idx
-        if weights is not None:
-            np.ctypeslib.as_array(lib().fr_worker_pool_weights_ptr(self._h), shape=(B, P))[:] = self._pooled_weights(weights, idx)
-        if self.dense is not None:
-            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
+        B = self.load_pooled(idx, dense, weights)
         self.submit_pooled(B, weighted=weights is not None)
         return self._topk_host(B, k, seg_offsets)
 
     def infer_pooled_csr_topk(self, offsets, indices, k, seg_offsets=None, dense=None, weights=None):
         """infer_pooled_csr() with the ranking on the device (arguments of infer_pooled_csr; k / seg_offsets / result of infer_topk)."""
-        B, off, ind, w = self._csr_arrays(offsets, indices, weights)
-        if self.pool_offsets is None or (w is not None and self.pool_weights is None):
-            raise FleetRecError(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after Context.set_pooling")
-        if B > self.max_batch:
-            raise FleetRecError(FR_ERR_INVALID, "batch %d exceeds the worker's max_batch %d" % (B, self.max_batch))
-        if ind.size > self.max_batch * self._pool_cap:
-            raise FleetRecError(FR_ERR_INVALID, "%d indices exceed the worker's index buffer (%d x %d)" % (ind.size, self.max_batch, self._pool_cap))
-        self.pool_offsets[:off.size] = off
-        np.ctypeslib.as_array(lib().fr_worker_idx_ptr(self._h), shape=(self.max_batch * self._pool_cap,))[:ind.size] = ind
-        if w is not None:
-            self.pool_weights.reshape(-1)[:w.size] = w
-        if self.dense is not None:
-            self.dense[:B] = np.asarray(dense, dtype=np.float32).reshape(B, -1)
-        self.submit_pooled_csr(B, weighted=w is not None)
+        B = self.load_pooled_csr(offsets, indices, dense, weights)
+        self.submit_pooled_csr(B, weighted=weights is not None)
         return self._topk_host(B, k, seg_offsets)
 
     # request-form batches (Context.set_request_columns): request rows + candidate rows + segment offsets, expanded on the device ----------------

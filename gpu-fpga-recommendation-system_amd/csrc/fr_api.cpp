@@ -838,7 +838,7 @@ extern "C" void fr_worker_destroy(fr_worker *w) {
     fr_ctx_unref(held);   // (the last worker of a context that was already destroyed releases it)
 }
 
-static size_t idx_cols(const fr_ctx *c) {
+size_t idx_cols(const fr_ctx *c) {
     const int mode = c->model.index_mode;
     return mode == FR_INDEX_PER_TABLE ? (size_t)c->model.n_tables : (mode == FR_INDEX_PER_BANK ? (size_t)c->n_banks : 1);
 }
@@ -1015,14 +1015,30 @@ static int check_ready(fr_worker *w, int batch, bool need_tables, bool need_weig
     return FR_OK;
 }
 
+// what a record or slice gather (one-hot or pooled) checks before it launches anything, its transport and layout rule included; sets the device
+static int gather_ready(fr_worker *w, int batch, const void *d_out, const char *out_name, int transport) {
+    const int rc = check_ready(w, batch, true, false);
+    if (rc) return rc;
+    if (!d_out) FR_FAIL(FR_ERR_INVALID, "%s is NULL", out_name);
+    if (transport != FR_FC_FP32 && transport != FR_FC_BF16 && transport != FR_FC_FP8) FR_FAIL(FR_ERR_INVALID, "bad transport %d", transport);
+    if (transport != FR_FC_FP32 && w->ctx->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "low-precision transport: SEMANTIC layout only");
+    FR_SET_DEVICE(w->ctx);
+    return FR_OK;
+}
+
+// a gather (one-hot or pooled) of a context whose words read the dense features needs them
+static int dense_check(const fr_ctx *c, const float *d_dense) {
+    if (c->model.dense_len && !d_dense)
+        for (const FrWordDesc &wd : c->h_words)
+            if (wd.idx_col & FR_DESC_DENSE) FR_FAIL(FR_ERR_INVALID, "model has dense features but d_dense is NULL");
+    return FR_OK;
+}
+
 static int launch_gather(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, void *d_records, int transport = FR_FC_FP32) {
     fr_ctx *c = w->ctx;
     if (!d_idx) FR_FAIL(FR_ERR_INVALID, "d_idx is NULL");
-    if (c->model.dense_len && !d_dense) {
-        bool needs = false;
-        for (const FrWordDesc &wd : c->h_words) needs |= (wd.idx_col & FR_DESC_DENSE) != 0;
-        if (needs) FR_FAIL(FR_ERR_INVALID, "model has dense features but d_dense is NULL");
-    }
+    const int drc = dense_check(c, d_dense);
+    if (drc) return drc;
     if (c->cpu) {
         if (transport != FR_FC_FP32) FR_FAIL(FR_ERR_STATE, "the CPU back-end gathers fp32 records only");
         return frc_gather(c->h_words.data(), c->n_words, d_idx, (int)idx_cols(c), d_dense, reinterpret_cast<float *>(d_records), batch, &w->c_err);
@@ -1707,10 +1723,8 @@ static int launch_pipeline(fr_worker *w, int batch, const int32_t *d_idx, const 
 }
 
 extern "C" int fr_worker_gather_only(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
-    int rc = check_ready(w, batch, true, false);
+    int rc = gather_ready(w, batch, d_records, "d_records", FR_FC_FP32);
     if (rc) return rc;
-    if (!d_records) FR_FAIL(FR_ERR_INVALID, "d_records is NULL");
-    FR_SET_DEVICE(w->ctx);
     rc = launch_gather(w, batch, d_idx, d_dense, d_records);
     keep_kernel(w);
     if (rc) return rc;
@@ -1864,7 +1878,7 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
 extern "C" int fr_ctx_set_pooling_modes(fr_ctx *ctx, const int32_t *modes, int n_cols) {
     if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
     if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "the pooling of a sharded context (%d shards) is fixed when it is created: fr_ctx_create_sharded_pooled", ctx->n_shards);
-    if (ctx->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (ctx->pool_cols <= 0) return fr_pooling_unset(FR_NO_POOLING_PLAIN);
     const int cols = (int)idx_cols(ctx);
     if (modes) {
         if (n_cols != cols) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling_modes: n_cols %d, the context has %d index columns", n_cols, cols);
@@ -1884,112 +1898,144 @@ extern "C" int fr_ctx_pooling_mode(const fr_ctx *ctx, int col) {
 
 extern "C" int fr_ctx_pooled_index_cols(const fr_ctx *ctx) { return ctx ? ctx->pool_cols : 0; }
 
-// weighted = the call is one of the *_weighted entry points: d_weights must be there, and every column's mode SUM
-// d_offsets != NULL: the offsets (CSR) form -- d_idx / d_weights are the nnz flat entries (weighted = d_weights != NULL), the descriptors the second array;
-// its three 4000 MiB bounds are checked here, once, for both back-ends
-// operand != 0 (GPU only; 1 + the chain's precision): d_records is the chain's stage-1 operand of ldm items instead (frk_gather_pooled); the call may then
-// return FR_POOL_NO_OPERAND_ARM, with nothing launched
-// transport != FR_FC_FP32 (GPU only, operand == 0): d_records is the item-major slice [batch][slice_padded] of bf16 / e4m3 elements instead (fr_worker_gather_slices_pooled)
-// On a sharded context (pooling set at creation) the words are the shard's own: what is written is the shard's slice, as by fr_worker_gather_only.
-static int launch_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, void *d_records,
-                                const int32_t *d_offsets = nullptr, int64_t nnz = 0, int operand = 0, int ldm = 0, int transport = FR_FC_FP32) {
-    fr_ctx *c = w->ctx;
-    const int out_words = operand ? c->model.fc[0] / 4 : c->slice_padded / 4;
-    const bool csr = d_offsets != nullptr;   // (the offsets-form entry points refuse a NULL d_offsets themselves)
-    const bool lp_slice = transport != FR_FC_FP32;
-    if (c->pool_cols <= 0)
-        FR_FAIL(FR_ERR_STATE, c->n_shards > 1 ? "no pooling is set on the sharded context: create it with fr_ctx_create_sharded_pooled" : "no pooling is set on the context: call fr_ctx_set_pooling first");
-    if (lp_slice && c->cpu) FR_FAIL(FR_ERR_STATE, "the CPU back-end gathers fp32 records only");
-    if (lp_slice) operand = 1 + transport;   // the item-major form of the operand-store arms (frk_gather_pooled)
-    if (csr) {
-        if (nnz < 0) FR_FAIL(FR_ERR_INVALID, "nnz %lld is negative", (long long)nnz);
-        if (nnz > 0 && !d_idx) FR_FAIL(FR_ERR_INVALID, "d_indices is NULL with nnz %lld", (long long)nnz);
-        const size_t off_bytes = ((size_t)batch * idx_cols(c) + 1) * 4, rec_bytes = (size_t)batch * (size_t)c->slice_padded * 4;
-        if (off_bytes >= ((size_t)4000 << 20) || (uint64_t)nnz * 4 >= ((uint64_t)4000 << 20) || rec_bytes >= ((size_t)4000 << 20))
-            FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's offsets (%zu bytes), entries%s (%llu bytes) or records (%zu bytes) reach 4000 MiB", off_bytes, d_weights ? " / weights" : "",
-                    (unsigned long long)nnz * 4, rec_bytes);
-    } else if (!d_idx) {
+// ---- a pooled batch on its way to the gather (FrPooledBatch, FrPooledOut: fr_internal.h).  First the refusals its entry points share, fr_comm.cpp's too ----
+int fr_pooling_unset(FrNoPooling who) {
+    const char *advice = who == FR_NO_POOLING_PLAIN ? "call fr_ctx_set_pooling first" : "create it with fr_ctx_create_sharded_pooled";
+    FR_FAIL(FR_ERR_STATE, "no pooling is set on the %scontext: %s", who == FR_NO_POOLING_SHARD ? "sharded " : "", advice);
+}
+int fr_pooled_weights_need_sum(const fr_ctx *c) {
+    if (c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
+    return FR_OK;
+}
+// the host knows the offsets of its offsets-form batch: the first and the last are checked before anything is enqueued (the per-bag checks are the gather's)
+int fr_pooled_host_offsets(const fr_worker *w, int batch, const char *who, int64_t *nnz) {
+    const fr_ctx *c = w->ctx;
+    *nnz = w->h_pool_off[(size_t)batch * idx_cols(c)];
+    if (w->h_pool_off[0] != 0) FR_FAIL(FR_ERR_INVALID, "%s: offsets[0] is %d, not 0", who, w->h_pool_off[0]);
+    if (*nnz < 0 || *nnz > (int64_t)batch * c->pool_cols)
+        FR_FAIL(FR_ERR_INVALID, "%s: offsets[batch * cols] = %lld entries, outside [0, batch %d x %d pooled columns]", who, (long long)*nnz, batch, c->pool_cols);
+    return FR_OK;
+}
+// Everything a pooled gather refuses, for both back-ends and every destination.  A batch with weights takes the weighted fold, which needs every column's
+// mode SUM; the offsets form's three 4000 MiB bounds are checked here, once (its entry points refuse a NULL d_offsets themselves).
+static int pooled_check(const fr_worker *w, const FrPooledBatch &b, const FrPooledOut &o) {
+    const fr_ctx *c = w->ctx;
+    if (c->pool_cols <= 0) return fr_pooling_unset(c->n_shards > 1 ? FR_NO_POOLING_SHARD : FR_NO_POOLING_PLAIN);
+    if (o.kind == FrPooledOut::LP_SLICE && c->cpu) FR_FAIL(FR_ERR_STATE, "the CPU back-end gathers fp32 records only");
+    if (b.offsets) {
+        if (b.nnz < 0) FR_FAIL(FR_ERR_INVALID, "nnz %lld is negative", (long long)b.nnz);
+        if (b.nnz > 0 && !b.idx) FR_FAIL(FR_ERR_INVALID, "d_indices is NULL with nnz %lld", (long long)b.nnz);
+        const size_t off_bytes = ((size_t)b.batch * idx_cols(c) + 1) * 4, rec_bytes = (size_t)b.batch * (size_t)c->slice_padded * 4;
+        if (off_bytes >= ((size_t)4000 << 20) || (uint64_t)b.nnz * 4 >= ((uint64_t)4000 << 20) || rec_bytes >= ((size_t)4000 << 20))
+            FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's offsets (%zu bytes), entries%s (%llu bytes) or records (%zu bytes) reach 4000 MiB", off_bytes, b.weights ? " / weights" : "",
+                    (unsigned long long)b.nnz * 4, rec_bytes);
+    } else if (!b.idx) {
         FR_FAIL(FR_ERR_INVALID, "d_idx is NULL");
     }
-    if (weighted) {
-        if (!d_weights) FR_FAIL(FR_ERR_INVALID, "d_weights is NULL");
-        if (c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
+    if (b.need_weights && !b.weights) FR_FAIL(FR_ERR_INVALID, "d_weights is NULL");
+    if (b.weights) {
+        const int rc = fr_pooled_weights_need_sum(c);
+        if (rc) return rc;
     }
-    if (c->model.dense_len && !d_dense) {
-        bool needs = false;
-        for (const FrWordDesc &wd : c->h_words) needs |= (wd.idx_col & FR_DESC_DENSE) != 0;
-        if (needs) FR_FAIL(FR_ERR_INVALID, "model has dense features but d_dense is NULL");
-    }
-    if (csr) {
-        if (nnz == 0) d_idx = nullptr;   // (no entry is ever read: the resource is empty)
-        if (c->cpu)
-            return frc_gather_pooled(c->h_words.data(), c->h_pool_csr.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, static_cast<float *>(d_records), batch, &w->c_err, d_offsets,
-                                     (int)idx_cols(c), nnz);
-        return frk_gather_pooled(c->d_words, c->d_pool_csr, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, false, c->pool_any_mean, d_dense, d_records, batch,
-                                 w->d_err, w->stream, out_words, d_offsets, (int)idx_cols(c), nnz, operand, ldm, c->f8_e_act[0], lp_slice);
-    }
-    if (c->cpu) return frc_gather_pooled(c->h_words.data(), c->h_pool.data(), c->n_words, d_idx, d_weights, c->pool_cols, d_dense, static_cast<float *>(d_records), batch, &w->c_err);
-    return frk_gather_pooled(c->d_words, c->d_pool, c->n_words, c->gather_groups, d_idx, d_weights, c->pool_cols, c->pool_max_hots, c->pool_wide, c->pool_any_mean, d_dense, d_records, batch,
-                             w->d_err, w->stream, out_words, nullptr, 0, 0, operand, ldm, c->f8_e_act[0], lp_slice);
+    return dense_check(c, b.dense);
 }
 
-static int gather_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_records,
-                              const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
-    int rc = check_ready(w, batch, true, false);
+// The context's and the worker's part of a pooled launch, for both back-ends: the one place that picks the padded or the offsets form's descriptors
+static FrPooledPlan pooled_plan(fr_worker *w, const FrPooledBatch &b, const FrPooledOut &o) {
+    const fr_ctx *c = w->ctx;
+    const bool csr = b.offsets != nullptr;
+    FrPooledPlan p;
+    p.words = c->cpu ? c->h_words.data() : c->d_words;
+    p.pool = c->cpu ? (csr ? c->h_pool_csr : c->h_pool).data() : (csr ? c->d_pool_csr : c->d_pool);
+    p.groups = &c->gather_groups;
+    p.n_words = c->n_words;
+    p.out_words = (o.kind == FrPooledOut::OPERAND ? c->model.fc[0] : c->slice_padded) / 4;
+    p.pool_cols = c->pool_cols, p.max_hots = c->pool_max_hots;
+    p.n_icols = csr ? (int)idx_cols(c) : 0;
+    p.wide = c->pool_wide && !csr;   // the offsets form gives 4-byte alignment only
+    p.any_mean = c->pool_any_mean, p.e_x = c->f8_e_act[0];
+    p.err_flag = c->cpu ? &w->c_err : w->d_err;
+    return p;
+}
+
+// check, then the one launch (-> FR_POOL_NO_OPERAND_ARM: frk_gather_pooled).  On a sharded context the words are the shard's own: its slice is written.
+static int gather_pooled(fr_worker *w, FrPooledBatch b, const FrPooledOut &o) {
+    const int rc = pooled_check(w, b, o);
     if (rc) return rc;
-    if (!d_records) FR_FAIL(FR_ERR_INVALID, "d_records is NULL");
-    FR_SET_DEVICE(w->ctx);
-    rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, d_records, d_offsets, nnz);
+    if (b.offsets && b.nnz == 0) b.idx = nullptr;   // (no entry is ever read: the resource is empty)
+    const FrPooledPlan p = pooled_plan(w, b, o);
+    return w->ctx->cpu ? frc_gather_pooled(p, b, o) : frk_gather_pooled(p, b, o, w->stream);
+}
+
+// fp32 records, or a shard's slice in the transport type: fp32 is the record arm of gather_pooled_kernel (a shard's words place themselves in its slice);
+// bf16 / e4m3 are the item-major form of its operand-store arms, rounded as store_word rounds
+static int gather_pooled_impl(fr_worker *w, const FrPooledBatch &b, void *d_out, const char *out_name, int transport) {
+    int rc = gather_ready(w, b.batch, d_out, out_name, transport);
+    if (rc) return rc;
+    FrPooledOut o{d_out};
+    if (transport != FR_FC_FP32) o.kind = FrPooledOut::LP_SLICE, o.precision = transport;
+    rc = gather_pooled(w, b, o);
     if (rc) return rc;
     keep_kernel(w);
     w->in_flight = true;
     return FR_OK;
 }
 
+static FrPooledBatch pooled_batch_weighted(int batch, const int32_t *idx, const float *weights, const float *dense) {
+    FrPooledBatch b{batch, idx, weights, dense};
+    b.need_weights = true;
+    return b;
+}
+
+// the offsets form's entry points refuse a NULL d_offsets before anything else
+static int pooled_batch_csr(FrPooledBatch *b, int batch, const int32_t *offsets, const int32_t *idx, int64_t nnz, const float *weights, const float *dense) {
+    if (!offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
+    *b = FrPooledBatch{batch, idx, weights, dense, offsets, nnz};
+    return FR_OK;
+}
+
 extern "C" int fr_worker_gather_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_records) {
-    return gather_pooled_impl(w, batch, d_idx, nullptr, false, d_dense, d_records);
+    return gather_pooled_impl(w, FrPooledBatch{batch, d_idx, nullptr, d_dense}, d_records, "d_records", FR_FC_FP32);
 }
 
 extern "C" int fr_worker_gather_pooled_weighted(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_records) {
-    return gather_pooled_impl(w, batch, d_idx, d_weights, true, d_dense, d_records);
+    return gather_pooled_impl(w, pooled_batch_weighted(batch, d_idx, d_weights, d_dense), d_records, "d_records", FR_FC_FP32);
 }
 
 // pooled records into the worker's record buffer, then the chain fr_worker_fc_only runs from records (launch_fc), on the same stream
-static int submit_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores,
-                              const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
+static int submit_pooled_impl(fr_worker *w, const FrPooledBatch &b, float *d_scores) {
     if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
     if (w->ctx->n_shards > 1)   // (before the gather is enqueued: launch_fc would refuse the shard behind it)
         FR_FAIL(FR_ERR_STATE, "a pooled submit on a sharded ctx: the chain needs the all-gathered slices (fr_worker_submit_sharded_pooled on a context created by fr_ctx_create_sharded_pooled)");
-    int rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records, d_offsets, nnz);
+    int rc = gather_pooled(w, b, FrPooledOut{w->d_records});
     if (rc) return rc;
     w->in_flight = true;   // the gather is enqueued whatever the chain's launch says
-    return launch_fc(w, batch, w->d_records, d_scores);
+    return launch_fc(w, b.batch, w->d_records, d_scores);
 }
 
-static int submit_pooled_device_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, bool weighted, const float *d_dense, float *d_scores,
-                                     const int32_t *d_offsets = nullptr, int64_t nnz = 0) {
-    int rc = check_ready(w, batch, true, true);
+static int submit_pooled_device_impl(fr_worker *w, const FrPooledBatch &b, float *d_scores) {
+    int rc = check_ready(w, b.batch, true, true);
     if (rc) return rc;
     if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
     FR_SET_DEVICE(w->ctx);
-    return submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores, d_offsets, nnz);
+    return submit_pooled_impl(w, b, d_scores);
 }
 
 extern "C" int fr_worker_submit_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, float *d_scores) {
-    return submit_pooled_device_impl(w, batch, d_idx, nullptr, false, d_dense, d_scores);
+    return submit_pooled_device_impl(w, FrPooledBatch{batch, d_idx, nullptr, d_dense}, d_scores);
 }
 
 extern "C" int fr_worker_submit_pooled_weighted_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores) {
-    return submit_pooled_device_impl(w, batch, d_idx, d_weights, true, d_dense, d_scores);
+    return submit_pooled_device_impl(w, pooled_batch_weighted(batch, d_idx, d_weights, d_dense), d_scores);
 }
 
-// what both host forms (padded and offsets) ask of the worker before they read its pinned buffers
+// what both host forms (padded and offsets) ask of the worker before they read its pinned buffers (a shard is refused further down, by submit_pooled_impl)
 static int pooled_host_ready(fr_worker *w, int batch, bool weighted) {
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
     if (w->in_flight) FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
     fr_ctx *c = w->ctx;
-    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (c->pool_cols <= 0) return fr_pooling_unset(FR_NO_POOLING_PLAIN);
     if (w->idx_cap < c->pool_cols)
         FR_FAIL(FR_ERR_STATE, "the worker's index buffers hold %d columns per item, pooled rows have %d: create the worker after fr_ctx_set_pooling", w->idx_cap, c->pool_cols);
     if (weighted && (!w->h_pool_w || w->pool_w_cap < c->pool_cols))
@@ -1997,58 +2043,49 @@ static int pooled_host_ready(fr_worker *w, int batch, bool weighted) {
     return FR_OK;
 }
 
-static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted) {
+// the host forms: as fr_worker_submit, the gather reads the pinned index rows (weights, offsets, dense features) in place, the output layer writes the pinned scores
+static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted, const char *csr_who) {
     int rc = pooled_host_ready(w, batch, weighted);
     if (rc) return rc;
     fr_ctx *c = w->ctx;
+    FrPooledBatch b{batch, w->h_idx, weighted ? w->h_pool_w : nullptr, c->model.dense_len ? w->h_dense : nullptr};
+    b.need_weights = weighted;
+    if (csr_who) {
+        if (!w->h_pool_off) FR_FAIL(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after fr_ctx_set_pooling");
+        b.offsets = w->h_pool_off;
+        rc = fr_pooled_host_offsets(w, batch, csr_who, &b.nnz);
+        if (rc) return rc;
+    }
     FR_SET_DEVICE(c);
-    // as fr_worker_submit: the gather reads the pinned index rows (weights, dense features) in place, the output layer writes the pinned scores
-    rc = submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
+    rc = submit_pooled_impl(w, b, w->h_score);
     if (!rc) w->host_batch = batch;   // (fr_worker_topk ranks it)
     return rc;
 }
 
-extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, false); }
-extern "C" int fr_worker_submit_pooled_weighted(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, true); }
+extern "C" int fr_worker_submit_pooled(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, false, nullptr); }
+extern "C" int fr_worker_submit_pooled_weighted(fr_worker *w, int batch) { return submit_pooled_host_impl(w, batch, true, nullptr); }
+extern "C" int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted) { return submit_pooled_host_impl(w, batch, weighted != 0, "fr_worker_submit_pooled_csr"); }
 
 // ---- the offsets (CSR) form of the pooled lookups: the same gather, fold and chain; only the way a bag is found differs ----
 extern "C" int fr_worker_gather_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
                                            float *d_records) {
-    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
-    return gather_pooled_impl(w, batch, d_indices, d_weights, d_weights != nullptr, d_dense, d_records, d_offsets, nnz);
+    FrPooledBatch b;
+    const int rc = pooled_batch_csr(&b, batch, d_offsets, d_indices, nnz, d_weights, d_dense);
+    return rc ? rc : gather_pooled_impl(w, b, d_records, "d_records", FR_FC_FP32);
 }
 
 extern "C" int fr_worker_submit_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
                                                   float *d_scores) {
-    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
-    return submit_pooled_device_impl(w, batch, d_indices, d_weights, d_weights != nullptr, d_dense, d_scores, d_offsets, nnz);
-}
-
-extern "C" int fr_worker_submit_pooled_csr(fr_worker *w, int batch, int weighted) {
-    int rc = pooled_host_ready(w, batch, weighted != 0);
-    if (rc) return rc;
-    fr_ctx *c = w->ctx;
-    if (!w->h_pool_off) FR_FAIL(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after fr_ctx_set_pooling");
-    // the host knows the offsets: the first and the last are checked here, before anything is enqueued (the per-bag checks are the gather's)
-    const int64_t nnz = w->h_pool_off[(size_t)batch * idx_cols(c)];
-    if (w->h_pool_off[0] != 0) FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_pooled_csr: offsets[0] is %d, not 0", w->h_pool_off[0]);
-    if (nnz < 0 || nnz > (int64_t)batch * c->pool_cols)
-        FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_pooled_csr: offsets[batch * cols] = %lld entries, outside [0, batch %d x %d pooled columns]", (long long)nnz, batch, c->pool_cols);
-    FR_SET_DEVICE(c);
-    rc = submit_pooled_impl(w, batch, w->h_idx, weighted ? w->h_pool_w : nullptr, weighted != 0, c->model.dense_len ? w->h_dense : nullptr, w->h_score, w->h_pool_off, nnz);
-    if (!rc) w->host_batch = batch;
-    return rc;
+    FrPooledBatch b;
+    const int rc = pooled_batch_csr(&b, batch, d_offsets, d_indices, nnz, d_weights, d_dense);
+    return rc ? rc : submit_pooled_device_impl(w, b, d_scores);
 }
 
 // Sharded mode, low-precision transport: the shard's slice [batch][slice_padded] as bf16 or e4m3 (x 2^e of the context's X exponent)
 // instead of fp32 -- what travels through the all-gather.  transport = FR_FC_FP32 is fr_worker_gather_only.
 extern "C" int fr_worker_gather_slices(fr_worker *w, int batch, const int32_t *d_idx, const float *d_dense, void *d_slice, int transport) {
-    int rc = check_ready(w, batch, true, false);
+    int rc = gather_ready(w, batch, d_slice, "d_slice", transport);
     if (rc) return rc;
-    if (!d_slice) FR_FAIL(FR_ERR_INVALID, "d_slice is NULL");
-    if (transport != FR_FC_FP32 && transport != FR_FC_BF16 && transport != FR_FC_FP8) FR_FAIL(FR_ERR_INVALID, "bad transport %d", transport);
-    if (transport != FR_FC_FP32 && w->ctx->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "low-precision transport: SEMANTIC layout only");
-    FR_SET_DEVICE(w->ctx);
     rc = launch_gather(w, batch, d_idx, d_dense, d_slice, transport);
     keep_kernel(w);
     if (rc) return rc;
@@ -2056,31 +2093,16 @@ extern "C" int fr_worker_gather_slices(fr_worker *w, int batch, const int32_t *d
     return FR_OK;
 }
 
-// The pooled siblings: the slice of a pooled batch (padded or offsets form) in the transport type.  fp32 is the record arm of gather_pooled_kernel (a
-// shard's words place themselves in its slice); bf16 / e4m3 are the item-major form of its operand-store arms, rounded as store_word rounds.
-static int gather_slices_pooled_impl(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_idx, int64_t nnz, const float *d_weights, const float *d_dense, void *d_slice,
-                                     int transport) {
-    int rc = check_ready(w, batch, true, false);
-    if (rc) return rc;
-    if (!d_slice) FR_FAIL(FR_ERR_INVALID, "d_slice is NULL");
-    if (transport != FR_FC_FP32 && transport != FR_FC_BF16 && transport != FR_FC_FP8) FR_FAIL(FR_ERR_INVALID, "bad transport %d", transport);
-    if (transport != FR_FC_FP32 && w->ctx->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "low-precision transport: SEMANTIC layout only");
-    FR_SET_DEVICE(w->ctx);
-    rc = launch_gather_pooled(w, batch, d_idx, d_weights, d_weights != nullptr, d_dense, d_slice, d_offsets, nnz, 0, 0, transport);
-    if (rc) return rc;
-    keep_kernel(w);
-    w->in_flight = true;
-    return FR_OK;
-}
-
+// The pooled siblings: the slice of a pooled batch (padded or offsets form) in the transport type (gather_pooled_impl)
 extern "C" int fr_worker_gather_slices_pooled(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, void *d_slice, int transport) {
-    return gather_slices_pooled_impl(w, batch, nullptr, d_idx, 0, d_weights, d_dense, d_slice, transport);
+    return gather_pooled_impl(w, FrPooledBatch{batch, d_idx, d_weights, d_dense}, d_slice, "d_slice", transport);
 }
 
 extern "C" int fr_worker_gather_slices_pooled_csr(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
                                                   void *d_slice, int transport) {
-    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
-    return gather_slices_pooled_impl(w, batch, d_offsets, d_indices, nnz, d_weights, d_dense, d_slice, transport);
+    FrPooledBatch b;
+    const int rc = pooled_batch_csr(&b, batch, d_offsets, d_indices, nnz, d_weights, d_dense);
+    return rc ? rc : gather_pooled_impl(w, b, d_slice, "d_slice", transport);
 }
 
 // ... and the receiving side: d_gathered = [n_shards][batch_total][slice_padded] elements of the transport type.  The transport must
@@ -2241,19 +2263,17 @@ extern "C" int fr_worker_push_device_list(fr_worker *w, int n, const int *batch,
 
 // ---- streaming pushes of pooled lookups: the pooled gather writes the chain's stage-1 operand itself and the batch enters the stage pipeline at
 // stage 1 of the next launch, un-flushed -- its FC1 shares that launch with FC2 / FC3 / the output layer of the pushes before it ----
-static int push_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores, const int32_t *d_offsets = nullptr,
-                            int64_t nnz = 0) {
+static int push_pooled_impl(fr_worker *w, const FrPooledBatch &b, float *d_scores) {
+    const int batch = b.batch;
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
     if (!d_scores) FR_FAIL(FR_ERR_INVALID, "d_scores is NULL");
     fr_ctx *c = w->ctx;
-    const bool weighted = d_weights != nullptr;
-    if (c->pool_cols <= 0)
-        FR_FAIL(FR_ERR_STATE, c->n_shards > 1 ? "no pooling is set on the sharded context: create it with fr_ctx_create_sharded_pooled" : "no pooling is set on the context: call fr_ctx_set_pooling first");
+    if (c->pool_cols <= 0) return fr_pooling_unset(c->n_shards > 1 ? FR_NO_POOLING_SHARD : FR_NO_POOLING_PLAIN);
     if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "a pooled push on a sharded ctx: the chain needs the all-gathered slices (fr_worker_submit_sharded_pooled)");
     if (c->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "a pooled push needs a SEMANTIC-layout context");
     if (c->cpu) {   // the CPU back-end has nothing to queue behind: the batch is computed before the call returns
-        rc = submit_pooled_impl(w, batch, d_idx, d_weights, weighted, d_dense, d_scores, d_offsets, nnz);
+        rc = submit_pooled_impl(w, b, d_scores);
         if (rc) return rc;
         w->in_flight = true;
         return FR_OK;
@@ -2277,12 +2297,14 @@ static int push_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const
     const int par_prev = (int)((w->launch_no - 1) & 1);
     float *x = act_set(w, par_prev).x;
     // experiments build only: FR_POOL_PUSH_TWO_LAUNCH = 1 takes the two-launch form for every shape (tools/pooled_stream_bench.py, form (c))
-    rc = FR_KNOB("POOL_PUSH_TWO_LAUNCH", 0) ? FR_POOL_NO_OPERAND_ARM : launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, x, d_offsets, nnz, 1 + c->fc_precision, ldm);
+    FrPooledOut operand{x};
+    operand.kind = FrPooledOut::OPERAND, operand.precision = c->fc_precision, operand.ldm = ldm;
+    rc = FR_KNOB("POOL_PUSH_TWO_LAUNCH", 0) ? FR_POOL_NO_OPERAND_ARM : gather_pooled(w, b, operand);
     if (rc == FR_POOL_NO_OPERAND_ARM) {
         // the two-launch form: fp32 records into the worker's record buffer, then the conversion launch of fr_worker_fc_only -- for the (shape,
         // operand type) pairs of gather_pooled_kernel that carry no operand-store arm (fr_gather.hip, pooled_operand_forms: <4, 2, false> and
         // <2, 4, false> on a bf16 / fp8 chain); stream order keeps the buffer safe
-        rc = launch_gather_pooled(w, batch, d_idx, d_weights, weighted, d_dense, w->d_records, d_offsets, nnz);
+        rc = gather_pooled(w, b, FrPooledOut{w->d_records});
         if (rc) return rc;
         keep_kernel(w);
         w->in_flight = true;
@@ -2301,13 +2323,14 @@ static int push_pooled_impl(fr_worker *w, int batch, const int32_t *d_idx, const
 }
 
 extern "C" int fr_worker_push_pooled_device(fr_worker *w, int batch, const int32_t *d_idx, const float *d_weights, const float *d_dense, float *d_scores) {
-    return push_pooled_impl(w, batch, d_idx, d_weights, d_dense, d_scores);
+    return push_pooled_impl(w, FrPooledBatch{batch, d_idx, d_weights, d_dense}, d_scores);
 }
 
 extern "C" int fr_worker_push_pooled_csr_device(fr_worker *w, int batch, const int32_t *d_offsets, const int32_t *d_indices, int64_t nnz, const float *d_weights, const float *d_dense,
                                                 float *d_scores) {
-    if (!d_offsets) FR_FAIL(FR_ERR_INVALID, "d_offsets is NULL");
-    return push_pooled_impl(w, batch, d_indices, d_weights, d_dense, d_scores, d_offsets, nnz);
+    FrPooledBatch b;
+    const int rc = pooled_batch_csr(&b, batch, d_offsets, d_indices, nnz, d_weights, d_dense);
+    return rc ? rc : push_pooled_impl(w, b, d_scores);
 }
 
 extern "C" int fr_worker_push_pooled_device_list(fr_worker *w, int n, const int *batch, const int32_t *const *d_idx, const float *const *d_weights, const float *const *d_dense,
@@ -2315,7 +2338,7 @@ extern "C" int fr_worker_push_pooled_device_list(fr_worker *w, int n, const int 
     if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
     if (n < 0 || (n > 0 && (!batch || !d_idx || !d_scores))) FR_FAIL(FR_ERR_INVALID, "push_pooled_device_list: n = %d needs batch, d_idx and d_scores arrays", n);
     for (int i = 0; i < n; i++) {
-        const int rc = push_pooled_impl(w, batch[i], d_idx[i], d_weights ? d_weights[i] : nullptr, d_dense ? d_dense[i] : nullptr, d_scores[i]);
+        const int rc = push_pooled_impl(w, FrPooledBatch{batch[i], d_idx[i], d_weights ? d_weights[i] : nullptr, d_dense ? d_dense[i] : nullptr}, d_scores[i]);
         if (rc) return rc;
     }
     return FR_OK;
@@ -3024,7 +3047,8 @@ extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int
     if (pooled) {
         rc = pooled_host_ready(w, batch, weighted);
         if (rc) return rc;
-        if (weighted && c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
+        if (weighted) rc = fr_pooled_weights_need_sum(c);
+        if (rc) return rc;
         if (weighted && (!w->h_req_w || !w->d_pool_w || w->req_w_cap < f->req_words))
             FR_FAIL(FR_ERR_STATE, "the worker's request weight buffer holds %d words per request, the split needs %d: create the worker after fr_ctx_set_pooling and fr_ctx_set_request_columns",
                     w->req_w_cap, f->req_words);
@@ -3049,7 +3073,7 @@ extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int
     if (!rc && fd) rc = request_enqueue(w, *fd, batch, n_req, w->h_req_off, w->h_req_dense, nullptr, w->d_dense);
     if (rc) return rc;
     const float *dense = fd ? w->d_dense : (c->model.dense_len ? w->h_dense : nullptr);
-    if (pooled) rc = submit_pooled_impl(w, batch, w->d_idx, weighted ? w->d_pool_w : nullptr, weighted, dense, w->h_score);
+    if (pooled) rc = submit_pooled_impl(w, weighted ? pooled_batch_weighted(batch, w->d_idx, w->d_pool_w, dense) : FrPooledBatch{batch, w->d_idx, nullptr, dense}, w->h_score);
     else rc = launch_pipeline(w, batch, w->d_idx, dense, w->h_score);
     if (rc) return rc;
     w->in_flight = true, w->host_batch = batch;   // (fr_worker_topk ranks it)

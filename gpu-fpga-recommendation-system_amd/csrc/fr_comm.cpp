@@ -663,66 +663,55 @@ static int sharded_check_args(fr_worker *w, fr_comm *comm, int batch) {
     return FR_OK;
 }
 
-// What the first line of a step gathers: the one-hot rows of fr_worker_submit_sharded, or a pooled batch in the padded or the offsets (CSR) form
-// (fr_worker_submit_sharded_pooled[_csr]); nnz: the entries of the offsets form, read from the pinned offsets by the submit.
-struct ShGather {
-    enum Kind { ONE_HOT = 0, POOLED = 1, POOLED_CSR = 2 };
-    int kind = ONE_HOT;
-    bool weighted = false;
-    int64_t nnz = 0;
+// What the first line of a step gathers: the one-hot rows of fr_worker_submit_sharded (`pooled` false: batch, idx and dense alone count), or a pooled batch
+// in the padded or the offsets (CSR) form (fr_worker_submit_sharded_pooled[_csr]).  The submit states batch, need_weights (a weighted step) and, in the
+// offsets form, the pinned offsets with their nnz; sharded_prologue fills in where the gather reads the rest.
+struct ShBatch {
+    FrPooledBatch b;
+    bool pooled = false;
 };
-struct ShInputs {   // where the gather reads: device copies (a CPU worker: its host rows); weights and offsets are read in place (pinned)
-    const int32_t *idx = nullptr, *offsets = nullptr;
-    const float *dense = nullptr, *weights = nullptr;
-};
-static size_t comm_idx_cols(const fr_ctx *c) {
-    return c->model.index_mode == FR_INDEX_PER_TABLE ? (size_t)c->model.n_tables : (c->model.index_mode == FR_INDEX_PER_BANK ? (size_t)c->n_banks : 1);
-}
 
 // buffers + the request's H2D copies: a failure here is a device failure (kind (3)).  A CPU worker's "device" rows are its host rows.
 // Index rows travel to the worker's device index buffer (one-hot: batch x index columns; pooled: batch x P; offsets form: the nnz flat entries -- the
 // buffer holds max_batch x max(index columns, P)); a pooled step's weights and offsets are read by the gather in place, from the pinned buffers.
-static int sharded_prologue(fr_worker *w, fr_comm *comm, int batch, const ShGather &g, ShInputs *in) {
+static int sharded_prologue(fr_worker *w, fr_comm *comm, ShBatch *what) {
     fr_ctx *c = w->ctx;
+    FrPooledBatch &b = what->b;
     if (!c->cpu) FR_HIP(hipSetDevice(c->device));
     int rc = shard_buffers(w, comm->n_ranks, comm->grp != nullptr);
     if (rc) return rc;
-    in->weights = g.weighted ? w->h_pool_w : nullptr;
-    in->offsets = g.kind == ShGather::POOLED_CSR ? w->h_pool_off : nullptr;
-    if (c->cpu) {
-        in->idx = w->h_idx;
-        in->dense = w->h_dense;
-        return FR_OK;
-    }
-    const size_t n_idx = g.kind == ShGather::ONE_HOT ? (size_t)batch * comm_idx_cols(c) : g.kind == ShGather::POOLED ? (size_t)batch * (size_t)c->pool_cols : (size_t)g.nnz;
+    b.weights = b.need_weights ? w->h_pool_w : nullptr;
+    b.idx = c->cpu ? w->h_idx : w->d_idx;
+    b.dense = c->cpu ? w->h_dense : w->d_dense;
+    if (c->cpu) return FR_OK;
+    const size_t n_idx = !what->pooled ? (size_t)b.batch * idx_cols(c) : !b.offsets ? (size_t)b.batch * (size_t)c->pool_cols : (size_t)b.nnz;
     if (n_idx) rc = step_copy(w, w->d_idx, w->h_idx, n_idx * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (!rc && c->model.dense_len) rc = step_copy(w, w->d_dense, w->h_dense, (size_t)batch * c->model.dense_len * sizeof(float), hipMemcpyHostToDevice);
-    in->idx = w->d_idx;
-    in->dense = w->d_dense;
+    if (!rc && c->model.dense_len) rc = step_copy(w, w->d_dense, w->h_dense, (size_t)b.batch * c->model.dense_len * sizeof(float), hipMemcpyHostToDevice);
     return rc;
 }
 
 // the slice gather of a step: one-hot rows, or a pooled batch -- every form in the transport type, item-major
-static int sharded_gather(fr_worker *w, int batch, const ShGather &g, const ShInputs &in, void *d_slice, int transport) {
-    if (g.kind == ShGather::POOLED) return fr_worker_gather_slices_pooled(w, batch, in.idx, in.weights, in.dense, d_slice, transport);
-    if (g.kind == ShGather::POOLED_CSR) return fr_worker_gather_slices_pooled_csr(w, batch, in.offsets, in.idx, g.nnz, in.weights, in.dense, d_slice, transport);
-    return fr_worker_gather_slices(w, batch, in.idx, in.dense, d_slice, transport);
+static int sharded_gather(fr_worker *w, const ShBatch &what, void *d_slice, int transport) {
+    const FrPooledBatch &b = what.b;
+    if (!what.pooled) return fr_worker_gather_slices(w, b.batch, b.idx, b.dense, d_slice, transport);
+    if (b.offsets) return fr_worker_gather_slices_pooled_csr(w, b.batch, b.offsets, b.idx, b.nnz, b.weights, b.dense, d_slice, transport);
+    return fr_worker_gather_slices_pooled(w, b.batch, b.idx, b.weights, b.dense, d_slice, transport);
 }
 
 // THE STEP, on either transport: slice gather -> all-gather (or all-to-all: `mode`) of the slices -> FC chain on this rank's items -> all-gather of the score
 // chunks (each followed by its rank's status word) -> every rank's pinned score buffer.  A GPU worker's fr_worker_submit_sharded calls it
 // inline (every line enqueues on the worker's stream); a host-exchange worker's (CPU, or staged GPU) posts it to the worker's host stream.  *enqueued is set once the
 // second collective is on its way: from then on fr_worker_sync has something to wait for, whatever this function returns.
-static int sharded_step(fr_worker *w, fr_comm *comm, int batch, int mode, const ShGather &what, bool *enqueued) {
+static int sharded_step(fr_worker *w, fr_comm *comm, int mode, ShBatch what, bool *enqueued) {
     *enqueued = false;
-    ShInputs in;
-    int rc = sharded_prologue(w, comm, batch, what, &in);        // from here on: whatever fails aborts the communicator (kind (3))
+    const int batch = what.b.batch;
+    int rc = sharded_prologue(w, comm, &what);        // from here on: whatever fails aborts the communicator (kind (3))
     if (rc) return comm_fail(comm, rc);
     fr_ctx *c = w->ctx;
     const int G = comm->n_ranks, r = comm->rank;
     const int transport = c->fc_precision;  // slices travel in the chain's own operand type: fp32, bf16 (half) or e4m3 (a quarter of the bytes)
     const size_t esz = transport == FR_FC_FP32 ? 4 : (transport == FR_FC_BF16 ? 2 : 1);
-    rc = sharded_gather(w, batch, what, in, w->d_slice, transport);
+    rc = sharded_gather(w, what, w->d_slice, transport);
     if (rc) return comm_fail(comm, rc);
     const size_t row = (size_t)c->slice_padded * esz;
     const bool a2a = mode == FR_EXCHANGE_ALLTOALL;
@@ -777,36 +766,46 @@ static int sharded_step(fr_worker *w, fr_comm *comm, int batch, int mode, const 
 }
 
 // the checked step, handed to its transport: enqueued inline on the worker's HIP stream (RCCL), or posted to the worker's host stream
-static int sharded_submit(fr_worker *w, fr_comm *comm, int batch, const ShGather &what) {
+static int sharded_submit(fr_worker *w, fr_comm *comm, const ShBatch &what) {
     w->sh_comm = comm;  // fr_worker_sync waits through fr_comm_wait and reads the G status words
     comm->refs.fetch_add(1, std::memory_order_acq_rel);   // (also what fr_comm_set_exchange reads as "a step in flight")
     const int mode = comm->exchange.load(std::memory_order_acquire);
     if (comm->grp) {   // the host exchange (CPU worker, or staged GPU worker): the step runs behind this call on the worker's host stream -- its rendezvous blocks
-        host_stream(w)->post([w, comm, batch, mode, what] {
+        host_stream(w)->post([w, comm, mode, what] {
             bool enqueued = false;
-            return sharded_step(w, comm, batch, mode, what, &enqueued);
+            return sharded_step(w, comm, mode, what, &enqueued);
         });
         return FR_OK;
     }
     bool enqueued = false;
-    const int rc = sharded_step(w, comm, batch, mode, what, &enqueued);
+    const int rc = sharded_step(w, comm, mode, what, &enqueued);
     if (!enqueued) fr_comm_forget(w);   // kind (3) before the second collective: the communicator is aborted, there is no step to wait for
     return rc;
+}
+
+static ShBatch sharded_batch(int batch, bool pooled, bool weighted) {
+    ShBatch what{FrPooledBatch{batch}, pooled};
+    what.b.need_weights = weighted;
+    return what;
 }
 
 extern "C" int fr_worker_submit_sharded(fr_worker *w, fr_comm *comm, int batch) {
     if (comm && comm_is_broken(comm)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
     int rc = sharded_check_args(w, comm, batch);  // kind (1): returned as it is
     if (rc) return rc;
-    return sharded_submit(w, comm, batch, ShGather{});
+    return sharded_submit(w, comm, sharded_batch(batch, false, false));
 }
 
-// kind (1) of a pooled step, on top of sharded_check_args: everything the slice gather would refuse is refused here, before anything is enqueued (inside
+// kind (1) of a pooled step, sharded_check_args included: everything the slice gather would refuse is refused here, before anything is enqueued (inside
 // the step a refusal would abort the communicator)
-static int sharded_check_pooled(fr_worker *w, bool weighted, bool csr) {
+static int sharded_check_pooled(fr_worker *w, fr_comm *comm, int batch, bool weighted, bool csr) {
+    if (comm && comm_is_broken(comm)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
+    int rc = sharded_check_args(w, comm, batch);
+    if (rc) return rc;
     fr_ctx *c = w->ctx;
-    if (c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "no pooling is set on the context: create it with fr_ctx_create_sharded_pooled");
-    if (weighted && c->pool_any_mean) FR_FAIL(FR_ERR_STATE, "per-sample weights need every column's pooling mode to be FR_POOL_SUM: the context has a FR_POOL_MEAN column");
+    if (c->pool_cols <= 0) return fr_pooling_unset(FR_NO_POOLING_SHARDED_STEP);
+    if (weighted) rc = fr_pooled_weights_need_sum(c);
+    if (rc) return rc;
     if (w->idx_cap < c->pool_cols || (weighted && (!w->h_pool_w || w->pool_w_cap < c->pool_cols)) || (csr && !w->h_pool_off))
         FR_FAIL(FR_ERR_STATE, "the worker lacks the pooled buffers (%d index columns per item, pooled rows have %d): create the worker after the context's pooling is set", w->idx_cap,
                 c->pool_cols);
@@ -814,32 +813,19 @@ static int sharded_check_pooled(fr_worker *w, bool weighted, bool csr) {
 }
 
 extern "C" int fr_worker_submit_sharded_pooled(fr_worker *w, fr_comm *comm, int batch, int weighted) {
-    if (comm && comm_is_broken(comm)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
-    int rc = sharded_check_args(w, comm, batch);
-    if (!rc) rc = sharded_check_pooled(w, weighted != 0, false);
+    const int rc = sharded_check_pooled(w, comm, batch, weighted != 0, false);
     if (rc) return rc;
-    ShGather what;
-    what.kind = ShGather::POOLED;
-    what.weighted = weighted != 0;
-    return sharded_submit(w, comm, batch, what);
+    return sharded_submit(w, comm, sharded_batch(batch, true, weighted != 0));
 }
 
 extern "C" int fr_worker_submit_sharded_pooled_csr(fr_worker *w, fr_comm *comm, int batch, int weighted) {
-    if (comm && comm_is_broken(comm)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
-    int rc = sharded_check_args(w, comm, batch);
-    if (!rc) rc = sharded_check_pooled(w, weighted != 0, true);
+    int rc = sharded_check_pooled(w, comm, batch, weighted != 0, true);
     if (rc) return rc;
-    fr_ctx *c = w->ctx;
-    // the host knows the offsets: the first and the last are checked here (fr_worker_submit_pooled_csr's rule); the per-bag checks remain the gather's
-    const int64_t nnz = w->h_pool_off[(size_t)batch * comm_idx_cols(c)];
-    if (w->h_pool_off[0] != 0) FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_sharded_pooled_csr: offsets[0] is %d, not 0", w->h_pool_off[0]);
-    if (nnz < 0 || nnz > (int64_t)batch * c->pool_cols)
-        FR_FAIL(FR_ERR_INVALID, "fr_worker_submit_sharded_pooled_csr: offsets[batch * cols] = %lld entries, outside [0, batch %d x %d pooled columns]", (long long)nnz, batch, c->pool_cols);
-    ShGather what;
-    what.kind = ShGather::POOLED_CSR;
-    what.weighted = weighted != 0;
-    what.nnz = nnz;
-    return sharded_submit(w, comm, batch, what);
+    ShBatch what = sharded_batch(batch, true, weighted != 0);
+    what.b.offsets = w->h_pool_off;
+    rc = fr_pooled_host_offsets(w, batch, "fr_worker_submit_sharded_pooled_csr", &what.b.nnz);   // (fr_worker_submit_pooled_csr's rule)
+    if (rc) return rc;
+    return sharded_submit(w, comm, what);
 }
 
 extern "C" int fr_worker_inject_fc_failure(fr_worker *w, int steps) {
@@ -918,12 +904,12 @@ static int comm_wait_step(fr_worker *w, fr_comm *comm) {
 
 // fp8 chain on sharded contexts: every rank calibrates on the SAME all-gathered fp32 slices of the whole batch with the same
 // (replicated) weights, so all ranks arrive at identical activation exponents without a further reduction.
-static int sharded_calibrate(fr_worker *w, fr_comm *comm, int batch, const ShGather &what) {
-    ShInputs in;
-    int rc = sharded_prologue(w, comm, batch, what, &in);
+static int sharded_calibrate(fr_worker *w, fr_comm *comm, ShBatch what) {
+    const int batch = what.b.batch;
+    int rc = sharded_prologue(w, comm, &what);
     if (rc) return comm_fail(comm, rc);
     fr_ctx *c = w->ctx;
-    rc = sharded_gather(w, batch, what, in, w->d_slice, FR_FC_FP32);   // (fp32: fr_worker_gather_only / fr_worker_gather_pooled[_weighted])
+    rc = sharded_gather(w, what, w->d_slice, FR_FC_FP32);   // (fp32: fr_worker_gather_only / fr_worker_gather_pooled[_weighted])
     if (rc) return comm_fail(comm, rc);
     rc = step_all_gather(w, comm, w->d_slice, w->d_gathered, (size_t)batch * c->slice_padded * sizeof(float));
     if (rc) return comm_fail(comm, rc);
@@ -936,19 +922,14 @@ extern "C" int fr_worker_calibrate_fp8_sharded(fr_worker *w, fr_comm *comm, int 
     if (comm && comm_is_broken(comm)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
     int rc = sharded_check_args(w, comm, batch);
     if (rc) return rc;
-    return sharded_calibrate(w, comm, batch, ShGather{});
+    return sharded_calibrate(w, comm, sharded_batch(batch, false, false));
 }
 
 // The pooled sibling (padded form): the calibration sees the BAGS -- a SUM over a 16-slot bag can be many times a single row, and the X exponent
 // leaves one binade of headroom, so an fp8 job calibrated on one-hot rows clips its pooled operand.
 extern "C" int fr_worker_calibrate_fp8_sharded_pooled(fr_worker *w, fr_comm *comm, int batch, int weighted) {
     if (w && w->ctx) FR_NOT_ON_CPU(w->ctx, "fr_worker_calibrate_fp8_sharded_pooled");
-    if (comm && comm_is_broken(comm)) FR_FAIL(FR_ERR_COMM, FR_BROKEN_TEXT);
-    int rc = sharded_check_args(w, comm, batch);
-    if (!rc) rc = sharded_check_pooled(w, weighted != 0, false);
+    const int rc = sharded_check_pooled(w, comm, batch, weighted != 0, false);
     if (rc) return rc;
-    ShGather what;
-    what.kind = ShGather::POOLED;
-    what.weighted = weighted != 0;
-    return sharded_calibrate(w, comm, batch, what);
+    return sharded_calibrate(w, comm, sharded_batch(batch, true, weighted != 0));
 }

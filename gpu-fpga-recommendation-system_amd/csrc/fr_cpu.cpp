@@ -324,38 +324,37 @@ int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx
 // fast-math in either build): the records are bit-identical to the GPU's (a NaN's payload excepted).
 #pragma GCC push_options
 #pragma GCC optimize("fp-contract=off")
-int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
-                      int *err_flag, const int32_t *offsets, int n_icols, long long nnz) {
-    // offsets != NULL: the offsets form -- bag (b, c) = idx[offsets[b * n_icols + c] .. offsets[b * n_icols + c + 1]), c = pool[w].first, cap = pool[w].hots;
+int frc_gather_pooled(const FrPooledPlan &p, const FrPooledBatch &pb, const FrPooledOut &po) {
+    // pb.offsets != NULL: the offsets form -- bag (b, c) = idx[offsets[b * n_icols + c] .. offsets[b * n_icols + c + 1]), c = pool[w].first, cap = pool[w].hots;
     // a malformed bag (fleetrec_serving.h) raises the flag and is folded as an empty one: nothing outside the three arrays is read
     const int chunk = 32;
     std::atomic<int> bad{0};
-    char *o = reinterpret_cast<char *>(out);
-    Pool::get().run((batch + chunk - 1) / chunk, [&](int u) {
-        const int b0 = u * chunk, b1 = b0 + chunk < batch ? b0 + chunk : batch;
+    char *o = static_cast<char *>(po.ptr);
+    Pool::get().run((pb.batch + chunk - 1) / chunk, [&](int u) {
+        const int b0 = u * chunk, b1 = b0 + chunk < pb.batch ? b0 + chunk : pb.batch;
         int local_bad = 0;
         for (int b = b0; b < b1; b++) {
-            const int32_t *row = offsets ? nullptr : idx + (size_t)b * pool_cols;
-            const float *wrow = weights && !offsets ? weights + (size_t)b * pool_cols : nullptr;
-            for (int w = 0; w < n_words; w++) {
-                const FrWordDesc &d = words[w];
-                char *dst = o + ((size_t)d.dst_blk * (size_t)batch + (size_t)b * d.dst_stride + d.dst_off) * 16;
+            const int32_t *row = pb.offsets ? nullptr : pb.idx + (size_t)b * p.pool_cols;
+            const float *wrow = pb.weights && !pb.offsets ? pb.weights + (size_t)b * p.pool_cols : nullptr;
+            for (int w = 0; w < p.n_words; w++) {
+                const FrWordDesc &d = p.words[w];
+                char *dst = o + ((size_t)d.dst_blk * (size_t)pb.batch + (size_t)b * d.dst_stride + d.dst_off) * 16;
                 if (d.idx_col & FR_DESC_DENSE) {
-                    memcpy(dst, reinterpret_cast<const char *>(dense) + d.src + (size_t)b * d.stride, 16);
+                    memcpy(dst, reinterpret_cast<const char *>(pb.dense) + d.src + (size_t)b * d.stride, 16);
                     continue;
                 }
-                uint32_t hots = pool[w].hots & ~FR_POOL_DESC_MEAN;
-                const int32_t *bag = row ? row + pool[w].first : nullptr;
-                const float *wbag = wrow ? wrow + pool[w].first : nullptr;
-                if (offsets) {
-                    const int64_t s0 = offsets[(size_t)b * n_icols + pool[w].first], s1 = offsets[(size_t)b * n_icols + pool[w].first + 1];
-                    if (s0 < 0 || s1 < s0 || s1 > nnz || s1 - s0 > (int64_t)hots) {
+                uint32_t hots = p.pool[w].hots & ~FR_POOL_DESC_MEAN;
+                const int32_t *bag = row ? row + p.pool[w].first : nullptr;
+                const float *wbag = wrow ? wrow + p.pool[w].first : nullptr;
+                if (pb.offsets) {
+                    const int64_t s0 = pb.offsets[(size_t)b * p.n_icols + p.pool[w].first], s1 = pb.offsets[(size_t)b * p.n_icols + p.pool[w].first + 1];
+                    if (s0 < 0 || s1 < s0 || s1 > pb.nnz || s1 - s0 > (int64_t)hots) {
                         local_bad = 1;
                         hots = 0;
                     } else {
                         hots = (uint32_t)(s1 - s0);
-                        bag = hots ? idx + s0 : nullptr;
-                        wbag = weights && hots ? weights + s0 : nullptr;
+                        bag = hots ? pb.idx + s0 : nullptr;
+                        wbag = pb.weights && hots ? pb.weights + s0 : nullptr;
                     }
                 }
                 uint32_t acc[4] = {0u, 0u, 0u, 0u};
@@ -391,7 +390,7 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
                     }
                     cnt++;
                 }
-                if ((pool[w].hots & FR_POOL_DESC_MEAN) && cnt > 1) {
+                if ((p.pool[w].hots & FR_POOL_DESC_MEAN) && cnt > 1) {
                     const float n = (float)cnt;
                     for (int k = 0; k < 4; k++) {
                         float a;
@@ -405,7 +404,7 @@ int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
         }
         if (local_bad) bad.store(1, std::memory_order_relaxed);
     });
-    if (bad.load() && err_flag) __atomic_store_n(err_flag, 1, __ATOMIC_RELEASE);
+    if (bad.load() && p.err_flag) __atomic_store_n(p.err_flag, 1, __ATOMIC_RELEASE);
     return FR_OK;
 }
 #pragma GCC pop_options

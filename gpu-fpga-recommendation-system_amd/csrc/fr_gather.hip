@@ -770,74 +770,80 @@ __global__ void __launch_bounds__(256, pooled_min_waves(ITEMS, WIN)) gather_pool
     }
 }
 
+// what frk_gather_pooled has worked out for the launch, whatever the instantiation
+struct PooledLaunch {
+    FrGatherGroups groups;
+    int n_groups;
+    unsigned out_bytes;
+    FrPoolDest dst;
+};
+
 template <int ITEMS, int WIN, bool WIDE>
-static int gather_pooled_launch(const FrWordDesc *words, const FrPoolDesc *pool, const FrGatherGroups &groups, int n_groups, const int32_t *idx, const float *weights, int pool_cols,
-                                const float *dense, void *out, int batch, int *err_flag, unsigned out_bytes, bool any_mean, hipStream_t s,
-                                const int32_t *offsets, int n_icols, unsigned nnz, const FrPoolDest &dst) {
-    const bool feature_major = dst.ldm && !((unsigned)dst.code & FR_PD_ROWS);
-    const int n_chunks = ((feature_major ? (int)dst.ldm : batch) + ITEMS - 1) / ITEMS;   // the operand form covers the pad items [batch, ldm) too
-    const int bx = groups.max_words >= 256 ? 256 : ((groups.max_words + 63) / 64) * 64;
-    dim3 grid(n_groups * n_chunks, (groups.max_words + bx - 1) / bx);
-    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, out_bytes, any_mean ? 1 : 0,
-                                                                   offsets, n_icols, nnz, dst);
+static int gather_pooled_launch(const FrPooledPlan &p, const FrPooledBatch &b, const FrPooledOut &o, const PooledLaunch &l, hipStream_t s) {
+    const bool feature_major = l.dst.ldm && !((unsigned)l.dst.code & FR_PD_ROWS);
+    const int n_chunks = ((feature_major ? (int)l.dst.ldm : b.batch) + ITEMS - 1) / ITEMS;   // the operand form covers the pad items [batch, ldm) too
+    const int bx = l.groups.max_words >= 256 ? 256 : ((l.groups.max_words + 63) / 64) * 64;
+    dim3 grid(l.n_groups * n_chunks, (l.groups.max_words + bx - 1) / bx);
+    // (the padded form: offsets NULL, n_icols and nnz 0 -- the only form the 16-byte-index instantiations are launched for)
+    gather_pooled_kernel<ITEMS, WIN, WIDE><<<grid, dim3(bx), 0, s>>>(p.words, p.pool, l.groups, l.n_groups, b.idx, b.weights, p.pool_cols, b.dense, o.ptr, b.batch, p.err_flag, l.out_bytes,
+                                                                   p.any_mean ? 1 : 0, b.offsets, p.n_icols, (unsigned)b.nnz, l.dst);
     KCHECK();
     fr_note_kernel("gather_pooled_kernel<%d, %d, %s>", ITEMS, WIN, WIDE ? "true" : "false");
     return FR_OK;
 }
 
-// idx = [batch][pool_cols] int32; weights = NULL or float [batch][pool_cols] (the weighted fold); out = fp32 records in the model's layout,
-// out_words 16-byte words per item -- or, operand != 0, the chain's stage-1 operand (below; SEMANTIC records only: a word's place is its dst_off).  max_hots picks the window; any_mean: a word of `pool` carries FR_POOL_DESC_MEAN.
-// The offsets form (offsets != NULL): offsets = int32 [batch * n_icols + 1], idx / weights = the nnz flat entries (NULL when nnz == 0), `pool` = the
-// context's offsets-form descriptors (column and cap per word); the narrow instantiation of the window always (4-byte alignment only).
-int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &planned, const int32_t *idx, const float *weights, int pool_cols,
-                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
-                      const int32_t *offsets, int n_icols, long long nnz, int operand, int ldm, int e_x, bool item_major) {
+// The batch, the destination and the context's part: fr_internal.h.  A RECORDS destination holds p.out_words 16-byte words per item; an OPERAND (SEMANTIC
+// records only: a word's place is its dst_off) is Xq[K/4][ldm], Xh[K/8][ldm] or Xf[KE][ldm] in 16-byte elements, p.out_words = K / 4 record words, written
+// whole, pad items and pad k-rows as zeros.  p.max_hots picks the window; the offsets form always takes the narrow instantiation (4-byte alignment only).
+int frk_gather_pooled(const FrPooledPlan &p, const FrPooledBatch &b, const FrPooledOut &o, hipStream_t s) {
+    const int n_words = p.n_words, batch = b.batch;
     if (n_words <= 0 || batch <= 0) return FR_OK;
-    if (out_words < n_words) out_words = n_words;
-    // operand = 1 + the chain's fr_fc_precision (1 fp32, 2 bf16, 3 e4m3): `out` is the chain's feature-major stage-1 operand of ldm items and out_words record words
-    // (K / 4) -- Xq[K/4][ldm], Xh[K/8][ldm] or Xf[KE][ldm] in 16-byte elements -- written whole, pad items and pad k-rows as zeros
-    FrPoolDest dst{};
+    const int out_words = p.out_words < n_words ? n_words : p.out_words;
+    const int operand = o.kind == FrPooledOut::RECORDS ? 0 : 1 + o.precision;   // FrPoolDest's form: 1 fp32, 2 bf16, 3 e4m3
+    const bool item_major = o.kind == FrPooledOut::LP_SLICE;
+    PooledLaunch l{};
     size_t out_bytes = (size_t)batch * (size_t)out_words * 16;
-    if (item_major) {
-        // the item-major low-precision slice (FR_PD_ROWS): [batch][out_words] words of 8 (bf16) or 4 (e4m3) bytes; fp32 slices are the record arm's layout already
-        if (operand != 2 && operand != 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no item-major form %d", operand);
-        if (e_x < -126 || e_x > 127) FR_FAIL(FR_ERR_INVALID, "pooled gather: X exponent %d", e_x);
-        dst.ldm = (unsigned)out_words;
-        const unsigned fold = offsets ? (weights ? FR_PD_FOLD_CSR_WEIGHTED : FR_PD_FOLD_CSR) : weights ? FR_PD_FOLD_WEIGHTED : any_mean ? FR_PD_FOLD_MEAN : FR_PD_FOLD_SUM;
-        dst.code = operand | (int)FR_PD_ROWS | (int)(fold << FR_PD_FOLD_SHIFT) | (int)((unsigned)(operand == 3 ? e_x : 0) << FR_PD_EX_SHIFT);
-        out_bytes = (size_t)batch * (size_t)out_words * (16u >> (operand - 1));   // the resource ends with the batch: the chunk past it is dropped
-    } else if (operand) {
-        if (ldm < batch || ldm % 32) FR_FAIL(FR_ERR_INVALID, "pooled gather: operand of %d items for a batch of %d", ldm, batch);
-        if (operand < 1 || operand > 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no operand form %d", operand);
-        dst.ldm = (unsigned)ldm;
-        const unsigned per_row = 1u << (operand - 1);   // record words per 16-byte element
-        const size_t k_rows = operand == 3 ? ((size_t)out_words * 4 + 63) / 64 * 4 : ((size_t)out_words + per_row - 1) / per_row;
-        const unsigned n_pad = (unsigned)(k_rows * per_row - (size_t)out_words);   // at most 15
-        if (e_x < -126 || e_x > 127) FR_FAIL(FR_ERR_INVALID, "pooled gather: X exponent %d", e_x);
-        const unsigned fold = offsets ? (weights ? FR_PD_FOLD_CSR_WEIGHTED : FR_PD_FOLD_CSR) : weights ? FR_PD_FOLD_WEIGHTED : any_mean ? FR_PD_FOLD_MEAN : FR_PD_FOLD_SUM;
-        static_assert(15u <= FR_PD_PAD_MASK, "an e4m3 row pads at most 15 words");
-        dst.code = operand | (int)(n_pad << FR_PD_PAD_SHIFT) | (int)(fold << FR_PD_FOLD_SHIFT) | (int)((unsigned)(operand == 3 ? e_x : 0) << FR_PD_EX_SHIFT);   // (arithmetic shift in the kernel: the exponent's sign survives)
-        out_bytes = k_rows * (size_t)ldm * 16;
+    if (operand) {
+        const unsigned fold = b.offsets ? (b.weights ? FR_PD_FOLD_CSR_WEIGHTED : FR_PD_FOLD_CSR) : b.weights ? FR_PD_FOLD_WEIGHTED : p.any_mean ? FR_PD_FOLD_MEAN : FR_PD_FOLD_SUM;
+        unsigned n_pad = 0;
+        if (item_major) {
+            // the item-major low-precision slice (FR_PD_ROWS): [batch][out_words] words of 8 (bf16) or 4 (e4m3) bytes; fp32 slices are the record arm's layout already
+            if (operand != 2 && operand != 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no item-major form %d", operand);
+            l.dst.ldm = (unsigned)out_words;
+            out_bytes = (size_t)batch * (size_t)out_words * (16u >> (operand - 1));   // the resource ends with the batch: the chunk past it is dropped
+        } else {
+            if (o.ldm < batch || o.ldm % 32) FR_FAIL(FR_ERR_INVALID, "pooled gather: operand of %d items for a batch of %d", o.ldm, batch);
+            if (operand < 1 || operand > 3) FR_FAIL(FR_ERR_INVALID, "pooled gather: no operand form %d", operand);
+            l.dst.ldm = (unsigned)o.ldm;
+            const unsigned per_row = 1u << (operand - 1);   // record words per 16-byte element
+            const size_t k_rows = operand == 3 ? ((size_t)out_words * 4 + 63) / 64 * 4 : ((size_t)out_words + per_row - 1) / per_row;
+            n_pad = (unsigned)(k_rows * per_row - (size_t)out_words);   // at most 15
+            static_assert(15u <= FR_PD_PAD_MASK, "an e4m3 row pads at most 15 words");
+            out_bytes = k_rows * (size_t)o.ldm * 16;
+        }
+        if (p.e_x < -126 || p.e_x > 127) FR_FAIL(FR_ERR_INVALID, "pooled gather: X exponent %d", p.e_x);   // (behind the form's own checks, as ever)
+        l.dst.code = operand | (int)(item_major ? FR_PD_ROWS : n_pad << FR_PD_PAD_SHIFT) | (int)(fold << FR_PD_FOLD_SHIFT) | (int)((unsigned)(operand == 3 ? p.e_x : 0) << FR_PD_EX_SHIFT);   // (arithmetic shift in the kernel: the exponent's sign survives)
     }
-    const size_t idx_bytes = offsets ? (size_t)nnz * 4 : (size_t)batch * (size_t)pool_cols * 4;
-    const size_t off_bytes = offsets ? ((size_t)batch * (size_t)n_icols + 1) * 4 : 0;
+    const size_t idx_bytes = b.offsets ? (size_t)b.nnz * 4 : (size_t)batch * (size_t)p.pool_cols * 4;
+    const size_t off_bytes = b.offsets ? ((size_t)batch * (size_t)p.n_icols + 1) * 4 : 0;
     // 32-bit resource offsets, with room for the chunk past the batch (the offsets form's three sizes are refused by the C-ABI, for both back-ends, before it gets here)
     if (out_bytes >= ((size_t)4000 << 20) || idx_bytes >= ((size_t)4000 << 20) || off_bytes >= ((size_t)4000 << 20))
-        FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's index rows%s (%zu bytes) or records (%zu bytes) reach 4000 MiB", weights ? " / weights" : "", idx_bytes, out_bytes);
-    FrGatherGroups groups = planned;
-    int n_groups = 8;
-    if (groups.max_words <= 0) {   // no XCD plan (a narrow record): one group, whole workgroups along the words
-        n_groups = 1;
-        groups.start[0] = 0;
-        for (int g = 1; g <= 8; g++) groups.start[g] = n_words;
-        groups.max_words = n_words;
+        FR_FAIL(FR_ERR_INVALID, "pooled gather: the batch's index rows%s (%zu bytes) or records (%zu bytes) reach 4000 MiB", b.weights ? " / weights" : "", idx_bytes, out_bytes);
+    l.out_bytes = (unsigned)out_bytes;
+    l.groups = *p.groups;
+    l.n_groups = 8;
+    if (l.groups.max_words <= 0) {   // no XCD plan (a narrow record): one group, whole workgroups along the words
+        l.n_groups = 1;
+        l.groups.start[0] = 0;
+        for (int g = 1; g <= 8; g++) l.groups.start[g] = n_words;
+        l.groups.max_words = n_words;
     }
-    wide = wide && !offsets && ((reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;   // 16-byte loads of both arrays
+    const bool wide = p.wide && !b.offsets && ((reinterpret_cast<uintptr_t>(b.idx) | reinterpret_cast<uintptr_t>(b.weights)) & 15) == 0;   // 16-byte loads of both arrays
     // window x items per thread by the longest bag, from the sweep on the MI355X (profiles/pooled_gather_window_sweep.md: Model-C batch 4096, every
     // window x items pair at hots 1 .. 16): the longest window that a bag fills wins by 1-5 %, with as few items per thread as keep 16 row words
     // in flight; a one-slot window is 20 % slower than a two-slot one at hots = 1 and is not built.  FR_POOL_WIN / FR_POOL_ITEMS: experiments build only
-    int win = max_hots >= 16 ? 16 : max_hots >= 8 ? 8 : max_hots >= 4 ? 4 : 2;
-    int items = win >= 16 ? 1 : max_hots >= 2 ? 2 : 4;
+    int win = p.max_hots >= 16 ? 16 : p.max_hots >= 8 ? 8 : p.max_hots >= 4 ? 4 : 2;
+    int items = win >= 16 ? 1 : p.max_hots >= 2 ? 2 : 4;
     win = FR_KNOB("POOL_WIN", win);
     items = FR_KNOB("POOL_ITEMS", items);
     if (item_major && !((pooled_operand_forms(items, win, win % 4 == 0 && wide) >> operand) & 1u)) {
@@ -846,12 +852,12 @@ int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_wor
         if (items == 4 && win == 2) items = 2;
         else if (items == 2 && win == 4) win = 8;
     }
-#define FR_GP(I, W)                                                                                                                                     \
-    if (items == I && win == W) {                                                                                                                       \
-        if (dst.ldm && !((pooled_operand_forms(I, W, W % 4 == 0 && wide) >> operand) & 1u)) return FR_POOL_NO_OPERAND_ARM;                                 \
-        if constexpr (W % 4 == 0)                                                                                                                       \
-            if (wide) return gather_pooled_launch<I, W, true>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, nullptr, 0, 0u, dst); \
-        return gather_pooled_launch<I, W, false>(words, pool, groups, n_groups, idx, weights, pool_cols, dense, out, batch, err_flag, (unsigned)out_bytes, any_mean, s, offsets, n_icols, (unsigned)nnz, dst);   \
+#define FR_GP(I, W)                                                                                                                 \
+    if (items == I && win == W) {                                                                                                   \
+        if (l.dst.ldm && !((pooled_operand_forms(I, W, W % 4 == 0 && wide) >> operand) & 1u)) return FR_POOL_NO_OPERAND_ARM;        \
+        if constexpr (W % 4 == 0)                                                                                                   \
+            if (wide) return gather_pooled_launch<I, W, true>(p, b, o, l, s);                                                       \
+        return gather_pooled_launch<I, W, false>(p, b, o, l, s);                                                                    \
     }
     FR_GP(4, 2)
     FR_GP(2, 2)

@@ -85,12 +85,12 @@ struct FrPoolDesc {
     uint32_t hots;    // slots of the bag (1 .. FR_POOL_MAX_HOTS) | FR_POOL_DESC_MEAN
 };
 static_assert(sizeof(FrPoolDesc) == 8, "FrPoolDesc must be 8 bytes");
-// Where gather_pooled_kernel stores its folded words, uniform over the launch.  ldm == 0: the item's fp32 record (16 bytes at the word's place in the
+// Where gather_pooled_kernel stores its folded words, uniform over the launch: the kernel's view of FrPooledOut, packed by frk_gather_pooled.  ldm == 0: the item's fp32 record (16 bytes at the word's place in the
 // model's layout).  form 1 / 2 / 3: straight into the chain's feature-major stage-1 operand of `ldm` items, in the chain's operand type -- fp32
 // Xq[K/4][ldm] (16 bytes, a bit copy), bf16 Xh[K/8][ldm] (8 bytes, RNE), e4m3 Xf[KE][ldm] (4 bytes, x scale, saturated); 16-byte elements, element
 // (w >> (form - 1), b) holds word w of item b.  The launch writes the whole region a stage reads: pad items [batch, ldm) and the pad words
 // of the k-rows past the record are zeros.
-constexpr int FR_POOL_NO_OPERAND_ARM = 1;   // frk_gather_pooled: not an error, not a launch
+constexpr int FR_POOL_NO_OPERAND_ARM = 1;   // frk_gather_pooled into an OPERAND: not an error, not a launch
 struct FrPoolDest {
     unsigned ldm;   // 0: records; FR_PD_ROWS: 16-byte words per item of the item-major destination
     int code;       // the FR_PD_* fields below, packed by frk_gather_pooled: one scalar register in the kernel instead of four
@@ -105,6 +105,37 @@ constexpr unsigned FR_PD_FOLD_SHIFT = 8, FR_PD_FOLD_MASK = 7u;      // bits 8-10
 constexpr unsigned FR_PD_ROWS = 1u << 11;
 constexpr unsigned FR_PD_EX_SHIFT = 16;                             // bits 16-31, signed: form 3's X exponent e_x (scale 2^e_x; an arithmetic shift recovers it)
 constexpr unsigned FR_PD_FOLD_SUM = 0u, FR_PD_FOLD_MEAN = 1u, FR_PD_FOLD_WEIGHTED = 2u, FR_PD_FOLD_CSR = 3u, FR_PD_FOLD_CSR_WEIGHTED = 4u;
+
+// A pooled batch as the caller handed it in, from the C-ABI's entry points down to both gather back-ends (device pointers; host memory on the CPU
+// back-end).  Padded form: idx = int32 [batch][P] (-1: an empty slot), weights = NULL or float [batch][P].  Offsets (CSR) form (offsets != NULL):
+// offsets = int32 [batch * index columns + 1], idx / weights = the nnz flat entries.  weights != NULL selects the weighted fold.
+struct FrPooledBatch {   // (brace-initialised in this order by the entry points)
+    int batch = 0;
+    const int32_t *idx = nullptr;
+    const float *weights = nullptr, *dense = nullptr;
+    const int32_t *offsets = nullptr;
+    int64_t nnz = 0;
+    bool need_weights = false;   // the call came through a *_weighted entry point: weights must be there
+};
+// Where the folded words go.  RECORDS: fp32 records in the model's layout (a shard: its fp32 slice).  OPERAND: the chain's feature-major stage-1 operand of
+// `ldm` items in `precision` (FrPoolDest forms 1 / 2 / 3), written whole.  LP_SLICE: a shard's item-major slice in the transport `precision` (bf16 / e4m3).
+struct FrPooledOut {
+    enum Kind { RECORDS, OPERAND, LP_SLICE };
+    void *ptr = nullptr;
+    Kind kind = RECORDS;
+    int precision = FR_FC_FP32, ldm = 0;
+};
+// What the context and the worker add to a launch (fr_ctx's fields of the same names; host arrays on the CPU back-end): filled by pooled_plan
+// (fr_api.cpp), the one place that picks the padded or the offsets form's descriptors (`pool`) and clears `wide` for the latter
+struct FrPooledPlan {
+    const FrWordDesc *words = nullptr;
+    const FrPoolDesc *pool = nullptr;
+    const FrGatherGroups *groups = nullptr;   // GPU only
+    int n_words = 0, out_words = 0;           // record words gathered / 16-byte words per item of the destination
+    int pool_cols = 0, max_hots = 0, n_icols = 0, e_x = 0;
+    bool wide = false, any_mean = false;
+    int *err_flag = nullptr;
+};
 
 // One wave-instruction of the item-tile gather (gather_tile_kernel, fr_gather.hip): 64 / n_words items x n_words consecutive
 // 16-byte words of ONE source row each (n_words = 1, 2, 4, 8 or 16: a whole table row, or a power-of-two piece of one).  A record
@@ -477,6 +508,13 @@ struct fr_worker {
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
 };
 
+size_t idx_cols(const fr_ctx *c);   // int32 index columns per item of a one-hot batch (fr_api.cpp)
+// refusals fr_api.cpp and fr_comm.cpp share (fr_api.cpp): no pooling set (always fails; its three texts: an unsharded context or a host form, a shard on
+// an unsharded entry point, the sharded step), weights against a FR_POOL_MEAN column, the two ends of `who`'s pinned bag offsets (*nnz = the last)
+enum FrNoPooling { FR_NO_POOLING_PLAIN, FR_NO_POOLING_SHARD, FR_NO_POOLING_SHARDED_STEP };
+int fr_pooling_unset(FrNoPooling who);
+int fr_pooled_weights_need_sum(const fr_ctx *c);
+int fr_pooled_host_offsets(const fr_worker *w, int batch, const char *who, int64_t *nnz);
 void fr_ctx_ref(fr_ctx *c);     // + 1 reference (a worker, a communicator handle)
 void fr_ctx_unref(fr_ctx *c);   // - 1; the last one releases the context
 
@@ -494,8 +532,7 @@ void frc_arena_free(void *p, size_t bytes);
 int frc_fill_table(float *base, int64_t row0, int64_t rows, int dim, int64_t row_stride_bytes, int mode, uint32_t seed, uint32_t uid);
 int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale);
 int frc_gather(const FrWordDesc *words, int n_words, const int32_t *idx, int idx_stride, const float *dense, float *out, int batch, int *err_flag);
-int frc_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const int32_t *idx, const float *weights, int pool_cols, const float *dense, float *out, int batch,
-                      int *err_flag, const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0);   // offsets != NULL: the offsets form, pool = fr_ctx::h_pool_csr
+int frc_gather_pooled(const FrPooledPlan &p, const FrPooledBatch &b, const FrPooledOut &o);   // fp32 records only (FrPooledOut::RECORDS)
 // n listed rows of one table <- src [n][dim], into the host arena with table_copy's head / tail addressing, over the pool's threads; a listed
 // id outside [0, rows) writes nothing and -> 1 (else 0).  A row listed twice ends up as the LAST of its listed sources.
 int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src);
@@ -531,16 +568,10 @@ int frk_scatter_rows(float *head, int64_t row_stride_bytes, float *tail, int64_t
                      hipStream_t s);
 int frk_gather(const FrWordDesc *words, int n_words, const FrGatherGroups &groups, const int32_t *idx, int idx_stride, const float *dense, void *out, int batch, int *err_flag,
                int transport, int e_x, hipStream_t s, int out_words, bool one_chunk = false);
-// pooled (multi-hot) gather: idx = [batch][pool_cols]; weights = NULL or float [batch][pool_cols] (the weighted fold); bag and mode of word w =
-// pool[w]; fp32 records in the model's layout.  max_hots / wide / any_mean: fr_ctx::pool_*
-// offsets != NULL: the offsets (CSR) form -- offsets = int32 [batch * n_icols + 1], idx / weights = nnz flat entries, pool = fr_ctx::d_pool_csr
-// -> FR_POOL_NO_OPERAND_ARM (nothing launched) when the shape this batch takes has no operand-store arm: the caller writes records and converts them.
-// operand = 1 + the chain's fr_fc_precision (0: records): out = the chain's stage-1 operand of ldm items instead of records (FrPoolDest), e_x = the X exponent of the fp8 chain
-// item_major (operand 2 / 3 only; ldm unused): out = the item-major low-precision slice [batch][out_words] of 8- / 4-byte words instead (FR_PD_ROWS); a shape
-// without the arm is replaced by its neighbour, so the call never returns FR_POOL_NO_OPERAND_ARM
-int frk_gather_pooled(const FrWordDesc *words, const FrPoolDesc *pool, int n_words, const FrGatherGroups &groups, const int32_t *idx, const float *weights, int pool_cols,
-                      int max_hots, bool wide, bool any_mean, const float *dense, void *out, int batch, int *err_flag, hipStream_t s, int out_words,
-                      const int32_t *offsets = nullptr, int n_icols = 0, long long nnz = 0, int operand = 0, int ldm = 0, int e_x = 0, bool item_major = false);
+// pooled (multi-hot) gather of the batch `b` (padded or offsets form) by the descriptors of `p` into `o`, one launch on `s`
+// -> FR_POOL_NO_OPERAND_ARM (nothing launched) when `o` is the chain's OPERAND and the shape this batch takes has no operand-store arm: the caller writes
+// records and converts them.  An LP_SLICE without the arm takes the neighbouring shape instead, so that call never returns FR_POOL_NO_OPERAND_ARM.
+int frk_gather_pooled(const FrPooledPlan &p, const FrPooledBatch &b, const FrPooledOut &o, hipStream_t s);
 int frk_gather_tile(const FrPassDesc *passes, const FrChunkDesc *chunks, int n_chunks, const int32_t *idx, int idx_stride, const float *dense, void *out,
                     int out_stride_words, int batch, int *err_flag, bool dedup, unsigned long long *dup_counter, hipStream_t s);
 int frk_transpose_slices_lp(int precision, const void *gathered, int n_shards, int batch_total, int slice_padded, const int *h_offsets, const int *h_lens,
