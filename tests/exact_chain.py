@@ -5,8 +5,10 @@ Tables and dense features are integers in [-3, 3], weights integers in {-2 .. 2}
 reaches 2^24 times the products' common power-of-two quantum (premise(), asserted before any comparison).  Every fp32 partial sum is
 then exact in any order and any split, bf16 / e4m3 products are exact in fp32, the fp8 scales are powers of two: the only roundings
 left are the chain's explicit ones (bf16 RNE per hidden layer; e4m3 clamp to +-448 then RNE), which the host restates
-(gpu_helpers.chain_bf16_reference / chain_fp8_reference).  So there is no tolerance: one wrong column, k-group or tile shows."""
+(gpu_helpers.chain_bf16_reference / chain_fp8_reference).  So there is no tolerance: one wrong column, k-group or tile shows.
+(A sweep row with a record too short for FC1's sums to pass 256 draws its tables from [-12, 12], so that bf16 still rounds there.)"""
 import re
+import zlib
 
 import numpy as np
 
@@ -47,13 +49,18 @@ def _sparse_layer(rng, K, N, nnz, positive=False):
     return W
 
 
-def make_data(model_spec, seed, n_pool=256):
+def make_data(model_spec, seed, n_pool=256, table_max=3):
     """-> dict: tables (list of float32 [rows][dim]), ws (4 float32 [K][N] arrays, == column-major N x K flattened), fc, and a pool
-    of n_pool items (idx int32 [n][n_tables], dense float32 [n][dense_len] or None)."""
+    of n_pool items (idx int32 [n][n_tables], dense float32 [n][dense_len] or None).  table_max: table and dense values are integers in
+    [-table_max, table_max] (3: the stock distribution; a short record takes a wider range so that its FC1 sums pass 256 and bf16 rounds)."""
     rng = np.random.default_rng(seed)
     fc = [sum(t["dim"] for t in model_spec["tables"]) + model_spec.get("dense_len", 0)] + list(model_spec["fc"]) + [1]
     vals = np.arange(-3, 4, dtype=np.float32)
     pv = np.array([0.02, 0.03, 0.05, 0.1, 0.2, 0.25, 0.35])   # mostly positive: FC1 sums of several hundred (bf16 / e4m3 must round)
+    if table_max != 3:   # the same shape stretched: a ramp that favours the positive end
+        vals = np.arange(-table_max, table_max + 1, dtype=np.float32)
+        pv = np.linspace(1.0, 12.0, vals.size) ** 2
+        pv /= pv.sum()
     tables = [rng.choice(vals, size=(t["rows"], t["dim"]), p=pv).astype(np.float32) for t in model_spec["tables"]]
     ws = [_sparse_layer(rng, fc[0], fc[1], min(fc[0], 320), positive=True), _sparse_layer(rng, fc[1], fc[2], 8),
           _sparse_layer(rng, fc[2], fc[3], 8), _sparse_layer(rng, fc[3], 1, 12)]
@@ -297,6 +304,171 @@ CASES = [
 UNREACHABLE = {}
 
 
+# ---- the shape sweep: every FC-chain kernel at the edges of the ranges its dispatch predicate accepts -------------------------------------
+# A row is a case with its own shape: spec (K, (H1, H2, H3), dense_len), prec, batch, width, group; `edge` says which edge it sits on,
+# `layer` which of FC1 / FC2 / FC3 / stream is swept and `kernel` what fr_worker_last_kernel reports for it (fc_layer_only of that layer, or the
+# streamed launch of `group` pushes).  `family` / `cover` feed the coverage table; the remaining keys say where the edge bites, for the
+# mutants of tests/test_exact_chain_cpu.py: `kstep` = k per K step of the swept layer's loop, `pad` = (k per k-group, K padded) where the
+# kernel zero-pads the swept layer's K, `chunks` = H1 / 256 where the kernel loops over H1 chunks, `split` = the stage pipeline's split-K plan.
+LP, PPN, PP, OUT = "fc_lp_gemm_kernel<%d, %d, %d, %d, 8, 32>", "fc_pp_gemm_n128_kernel<%d, 2>", "fc_pp_gemm_kernel<%d, %d, %d>", "fc_lp_gemm_out_kernel<%d, 2>"
+FUSED, HS = "fr_fused_tile_kernel<%d, 0, 2, %s>", "fr_fused_tile_hs_kernel<1, %s, 0, 0, 0>"
+_PI = {"f32": 0, "bf16": 1, "fp8": 2}
+_KROW = {"f32": 4, "bf16": 8, "fp8": 16}   # k per element row of the GEMM operand images
+C_FC = (2048, 512, 256)
+
+
+def pick_nsplit(K, N, ldm):
+    """The stage pipeline's split-K plan of one fp32 layer (fr_api.cpp pick_nsplit)."""
+    return 2 if ((N // 32) * (ldm // 32) < 256 and (K // 8) % 16 == 0 and (K // 8) // 16 >= 4) else 1
+
+
+def split_plan(row):
+    """(FC1, FC2, FC3) split counts of a row's stage-pipeline run: fp32 only, the low-precision chains never split."""
+    K, fc, _ = row["spec"]
+    ldm = (row["batch"] + 31) // 32 * 32
+    dims = [K] + list(fc)
+    return tuple(pick_nsplit(dims[l], dims[l + 1], ldm) if row["prec"] == "f32" else 1 for l in range(3))
+
+
+def gemm_steps(prec, K):
+    """K steps of 8 element rows the GEMM kernels take for a layer of K inputs (fp8 pads K to a multiple of 64)."""
+    return ((K + 63) // 64 * 4 if prec == "fp8" else K // _KROW[prec]) // 8
+
+
+def fused_db(K, H2):
+    """Which fr_fused_tile_kernel<.., 0, 2, DB> the LDS arithmetic of frk_fused_launch picks (fr_fused.hip: rows of 33 16-byte elements)."""
+    single = max(K // 4 + 64, max(H2 // 4, 68)) * 33 * 16
+    double = max(K // 4 + 128, H2 // 4 + 68) * 33 * 16
+    assert single <= 160 * 1024, (K, H2)
+    return single > 80 * 1024 and double <= 160 * 1024
+
+
+def _hs_kernel(K):
+    return HS % ("22, 4, 16, 3, 4" if K <= 352 else "33, 6, 32, 3, 4" if K <= 528 else "44, 6, 32, 2, 6" if K <= 704 else "55, 7, 32, 2, 6")
+
+
+def _row(family, prec, K, fc, batch, layer, kernel, edge, cover, width=1, group=1, dense_len=0, tag="", **where):
+    rid = "%s-%s-K%d-%s-b%d%s" % (family, prec, K, "x".join(map(str, fc)), batch, tag)
+    return dict(id=rid, family=family, spec=(K, tuple(fc), dense_len), prec=prec, batch=batch, width=width, group=group, layer=layer, kernel=kernel,
+                edge=edge, cover=cover, **where)
+
+
+def _gemm_row(family, prec, K, fc, layer, kernel, edge, batch=4090, **kw):
+    """A GEMM-tile row: the swept layer's K is record K (FC1), H1 (FC2) or H2 (FC3)."""
+    KL = {"FC1": K, "FC2": fc[0], "FC3": fc[1]}[layer]
+    steps = gemm_steps(prec, KL)
+    pad = {"pad": (16, (KL + 63) // 64 * 64)} if prec == "fp8" and KL % 64 else {}
+    cover = "nsub=%d" % (2 * steps) if family == "t256" else "steps=%d" % steps
+    return _row(family, prec, K, fc, batch, layer, kernel, "%s (%d K steps)" % (edge, steps), cover, kstep=8 * _KROW[prec], **pad, **kw)
+
+
+def _sweeps():
+    rows = []
+    # 128 x 256 tiles, FC1 of (2048, 512, 256) on the whole chip: 2 K steps ride the plain loop, 3 (nsub == D + 1), 4, 5 the phased-waves kernel
+    for prec, Ks in (("bf16", (128, 192, 256, 320)), ("fp8", (256, 384, 512, 640, 328)), ("f32", (64, 96, 128, 160))):
+        for K in Ks:
+            st, p = gemm_steps(prec, K), _PI[prec]
+            pp = prec != "f32" and st >= 3
+            rows.append(_gemm_row("n128", prec, K, C_FC, "FC1", PPN % p if pp else LP % (p, 2, 128, 2),
+                                  ("phased waves, nsub == D + 1: one memory phase issues a DMA" if pp and st == 3 else
+                                   "phased waves, nsub == D + %d" % (st - 2) if pp else "plain two-stage loop") +
+                                  (", K zero-padded to 384" if K == 328 else "")))
+    # 256 x 256 tiles (chain width 4): sub-steps of 4 element rows, bf16 D = 3, fp8 D = 2; N = 2048 (XCD tile map) and N = 768 (linear map)
+    for K in (128, 192, 256):
+        for fc, nt in ((C_FC, 8), ((768, 512, 256), 0)):
+            nsub = K // 8 // 4
+            rows.append(_gemm_row("t256", "bf16", K, fc, "FC1", PP % (1, 3, nt), "256 x 256 phased waves, nsub == %d == D + %d" % (nsub, nsub - 3), width=4))
+    for K in (256, 384):   # KE % 8 == 0 makes nsub even: nsub == D + 1 == 3 cannot be reached in fp8
+        nsub = K // 16 // 4
+        rows.append(_gemm_row("t256", "fp8", K, C_FC, "FC1", PP % (2, 2, 8), "256 x 256 phased waves, nsub == %d == D + %d" % (nsub, nsub - 2), width=4))
+    # 64 x 128 tiles, FC2 (K = H1, N = 512): bf16 rides a ring of S = 4 stages -- 2, 3 steps (fewer than the ring), 4, 5 (not a multiple of it)
+    for prec, H1s in (("bf16", (128, 192, 256, 320)), ("fp8", (256, 384)), ("f32", (64, 96))):
+        for H1 in H1s:
+            S = 4 if prec == "bf16" else 2
+            rows.append(_gemm_row("t64", prec, 512, (H1, 512, 256), "FC2", LP % (_PI[prec], 1, 64, S), "64 x 128 tiles, ring of %d" % S))
+    # 128 x 128 tiles: ldm 1664 = 13 * 128, three K steps on the ring of two
+    for prec, K in (("f32", 96), ("bf16", 192), ("fp8", 384)):
+        rows.append(_gemm_row("t128", prec, K, C_FC, "FC1", LP % (_PI[prec], 1, 128, 2), "128 x 128 tiles, ring of 2", batch=1638))
+    # FC3 + the output layer in one launch (K = H2, N = 256): its accepted minimum of two K steps, and three
+    for prec, H2s in (("bf16", (128, 192)), ("fp8", (256, 384))):
+        for H2 in H2s:
+            rows.append(_gemm_row("tail", prec, 512, (512, H2, 256), "FC3", OUT % _PI[prec], "FC3 + output tail, ring of 2"))
+    # fp32 fused kernel, generic-K form: K in blocks of four k-groups of 8; the LDS layout (and DB) follows K and H2
+    for H2, Ks in ((512, (32, 96, 384, 704, 736, 960)), (256, (32, 960))):
+        for K in Ks:
+            db = fused_db(K, H2)
+            single = max(K // 4 + 64, max(H2 // 4, 68)) * 33 * 16 <= 80 * 1024
+            edge = "generic K, %d blocks of 32 k, %s" % (K // 32, "single-buffer layout (two workgroups per CU)" if single else
+                                                         "double-buffered R1" if db else "one workgroup per CU, single R1 buffer (wpe == 2 && !db)")
+            for batch in (33, 200):
+                rows.append(_row("fused32", "f32", K, (512, H2, 256), batch, "stream", FUSED % (2 if H2 == 512 else 1, "true" if db else "false"), edge,
+                                 "K=%d/H2=%d" % (K, H2), group=16, dense_len=16 if K == 960 else 0, kstep=32,
+                                 **({"rows": 400} if K == 32 else {})))   # (a record of one table: enough rows for distinct items)
+    # H1 chunk counts 1 and 3 in every fused kernel with a chunk loop (H1 = 1024, four chunks, is the GPU matrix's)
+    for H1 in (256, 768):
+        edge = "%d H1 chunk%s of 256%s" % (H1 // 256, "" if H1 == 256 else "s", ": the double buffer never alternates" if H1 == 256 else ": an odd count")
+        fc = (H1, 512, 256)
+        for prec, K, batch, group, kern in (("f32", 352, 100, 16, "fr_fused_tile_kernel<2, 44, 4, false>"), ("f32", 512, 100, 16, FUSED % (2, "true")),
+                                            ("f32", 352, 256, 64, "fr_fused_tile_m2_kernel<44>"),
+                                            ("bf16", 352, 100, 16, "fr_fused_tile_h_kernel<2, 2, 22, true, 16, 2>"),
+                                            ("bf16", 880, 100, 16, "fr_fused_tile_h_kernel<2, 2, 55, false, 12, 2>"),
+                                            ("fp8", 352, 100, 16, "fr_fused_tile_f8_kernel<6>"), ("fp8", 880, 100, 16, "fr_fused_tile_f8_kernel<14>")):
+            rows.append(_row("chunks", prec, K, fc, batch, "stream", kern, edge, "chunks=%d" % (H1 // 256), group=group, dense_len=16 if K == 880 else 0,
+                             chunks=H1 // 256))
+    # the persistent bf16 kernel below the top of each instantiation: zero k-groups past the record, partial slices
+    for K in (64, 80, 368, 544, 720, 864):
+        top = 352 if K <= 352 else 528 if K <= 528 else 704 if K <= 704 else 880
+        for batch in (65, 200):
+            rows.append(_row("hs", "bf16", K, (1024, 512, 256), batch, "stream", _hs_kernel(K), "%d k-groups of 16 in an instantiation of %d: %d zero k-groups" % (
+                K // 16, top // 16, (top - K) // 16), "kgroups=%d/%d" % (K // 16, top // 16), group=16, dense_len=16 if K == 720 else 0, kstep=16, pad=(16, top),
+                **({"table_max": 12} if K <= 80 else {})))
+    # the stage pipeline: split-K plans, the fp8 gather of a record with K % 64 != 0, a bf16 record with K % 32 == 16
+    for K, fc, layers in ((640, (384, 512, 256), ("FC2", "FC3")), (576, (640, 384, 256), ("FC2", "FC3")), (384, (512, 256, 256), ("FC1", "FC2")),
+                          (576, (384, 384, 256), ("FC2", "FC3"))):
+        for batch, layer in zip((33, 200), layers):
+            r = _row("stage", "f32", K, fc, batch, layer, None, "", "")
+            ns = split_plan(r)
+            s = int(layer[2])
+            reads, own = (1 if s == 1 else ns[s - 2]), ns[s - 1]
+            r.update(kernel=PIPE % (s, 0), split=ns, cover="split=%d%d%d" % ns,
+                     edge="split-K plan %s: %s reads %d partial%s and writes %d" % (ns, layer, reads, "" if reads == 1 else "s", own))
+            rows.append(r)
+    for K, fc, dl in ((104, (256, 512, 256), 0), (4200, C_FC, 8)):   # (104: a model's record is a multiple of 8 floats, so K = 100 cannot be built)
+        rows.append(_row("stage", "fp8", K, fc, 33, "FC1", PIPE % (1, 2), "the stage pipeline's own q16 gather, K %% 64 == %d (zero-padded to %d)" % (K % 64, (K + 63) // 64 * 64),
+                         "K%%64=%d" % (K % 64), dense_len=dl, kstep=64, pad=(16, (K + 63) // 64 * 64)))
+    for K in (48, 112):
+        rows.append(_row("stage", "bf16", K, (256, 512, 256), 33, "FC1", PIPE % (1, 1), "bf16 record with K % 32 == 16: an odd count of k-groups of 16",
+                         "K%32=16", kstep=16, pad=(16, (K + 31) // 32 * 32), **({"table_max": 12} if K == 48 else {})))
+    return rows
+
+
+SWEEPS = _sweeps()
+
+# Per kernel family: the range its dispatch predicate accepts, and what the sweep leaves out on purpose (the coverage table).
+FAMILIES = {
+    "n128": ("lp_gemm_mu == 2 (N % 128 == 0, ldm % 256 == 0, N / 128 * ldm / 256 >= 192): K steps = KE / 8 >= 2; 2 -> fc_lp_gemm_kernel<P, 2, 128, 2>, "
+             ">= 3 -> fc_pp_gemm_n128_kernel<P, 2> (bf16 / fp8), every count -> fc_lp_gemm_kernel<0, 2, 128, 2> (f32)",
+             "steps above 5 are the steady state the GPU matrix runs (K = 3968, 4200); other N / ldm change the grid only"),
+    "t256": ("lp_gemm_mu == 6 (bf16 / fp8, N % 256 == 0, ldm % 256 == 0, N / 256 * ldm / 256 >= 192 / width): nsub = KE / 4 >= 4, even",
+             "fp8 nsub == D + 1 == 3: KE % 8 == 0 makes nsub even, the predicate cannot produce it; NT = 2 (N = 512) needs FC2's K = H1 = 2048 "
+             "for its tile count, so it stays at the GPU matrix's one shape"),
+    "t64": ("lp_gemm_mu == 3 (N % 64 == 0, ldm % 128 == 0, N / 64 * ldm / 128 >= 128, larger tiles short of the chip): K steps >= 2, ring of 4 (bf16) / 2",
+            "steps above 5: the GPU matrix (K = 2048); fp8 / f32 ring of 2 has no fewer-than-ring case besides 2 and 3 steps, both run"),
+    "t128": ("lp_gemm_mu == 1 (N % 128 == 0, ldm % 128 == 0, N / 128 * ldm / 128 >= 192 or >= 64 where 64 x 128 tiles fall short): K steps >= 2",
+             "2 steps on this tile: the ring logic is the n128 family's fc_lp_gemm_kernel<P, 2, 128, 2> (same body, S = 2), run there at 2 steps"),
+    "tail": ("frk_fc_tail_ok (bf16 / fp8, N == 256, ldm % 128 == 0, K steps >= 2) and lp_gemm_mu != 0",
+             "f32 has no fused tail; steps above 3: the GPU matrix (H2 = 512, 768)"),
+    "fused32": ("frk_fused_ok, generic K: K % 32 == 0 up to the LDS bound K = 960, H1 % 256 == 0, H2 in {256, 512}, H3 == 256",
+                "K = 352 / 880 with H2 = 512 are the straight-line instantiations (GPU matrix, chunks family)"),
+    "chunks": ("every fused kernel with a chunk loop: H1 % 256 == 0 (fr_fused_tile_kernel, _m2_kernel, _h_kernel, _f8_kernel)",
+               "four chunks: the GPU matrix; two chunks: the fused32 family (H1 = 512); fr_fused_tile_hs_kernel takes H1 == 1024 only"),
+    "hs": ("frk_fused_hk_ok: K % 16 == 0, 64 <= K <= 880, hidden (1024, 512, 256); the narrowest of 22 / 33 / 44 / 55 k-groups that holds K",
+           "the top of each instantiation (K = 352 / 528 / 704 / 880): the GPU matrix"),
+    "stage": ("pick_nsplit: 2 where K % 128 == 0, K >= 512 and fewer than 256 tiles of 32 x 32 (fp32 only); any record (K % 8 == 0) in fp8, K % 16 == 0 in bf16",
+              "plans (2, 2, 2) and (1, 2, 2): the GPU matrix (Model C)"),
+}
+
+
 def named_kernels():
     """Every kernel name a GPU-matrix case asserts, or runs where no hook reports it (a case's `runs`: the stage pipeline's gather-only
     first step and its multi-stage steps, which fr_worker_last_kernel does not record)."""
@@ -312,9 +484,14 @@ def named_kernels():
 
 
 def case_data(case, n_items):
-    """(spec, data, idx, dense) of a case: n_items rows drawn (with repetition) from its model's pool."""
-    sp = model_spec(case["model"])
-    data = make_data(sp, model_seed(case["model"]))
+    """(spec, data, idx, dense) of a case or a sweep row: n_items rows drawn (with repetition) from its model's pool."""
+    if "spec" in case:   # a SWEEPS row: its own shape, a seed derived from its id
+        K, fc, dl = case["spec"]
+        sp = spec(K, fc, dense_len=dl, rows=case.get("rows", 29), name="sweep_%08x" % zlib.crc32(case["id"].encode()))
+        data = make_data(sp, 9000 + zlib.crc32(case["id"].encode()) % 100000, table_max=case.get("table_max", 3))
+    else:
+        sp = model_spec(case["model"])
+        data = make_data(sp, model_seed(case["model"]))
     rng = np.random.default_rng(sum(map(ord, case["id"])))
     sel = rng.integers(0, data["idx"].shape[0], size=n_items)
     dense = data["dense"][sel] if data["dense"] is not None else None

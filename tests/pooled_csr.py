@@ -560,7 +560,10 @@ def check_server(fr, device, pool, free_port_block):
     H = 3
     padded = _serve(device, pool, False, free_port_block)
     csr = _serve(device, pool, True, free_port_block)
-    assert [r.split() for r in csr] == [r.split() for r in padded], (csr, padded)
+    # one row per server thread that took a batch -- how many did is a matter of timing (a thread whose connection came up after the last batch
+    # was taken prints none), and every thread's first block holds the same bags: ONE distinct row per run, the same in both
+    rows_c, rows_p = {tuple(r.split()) for r in csr}, {tuple(r.split()) for r in padded}
+    assert rows_c == rows_p and len(rows_p) == 1, (csr, padded)
     m = fr.Model.builtin(fr.MODEL_A)
     idx = P.sender_rows(5, m.n_tables, H, True)
     w = PM.sender_weights(5, m.n_tables, H) if pool == "weighted" else None

@@ -1,7 +1,9 @@
 """The integer-valued exact-chain data (tests/exact_chain.py) on a machine without a GPU: the exactness premise holds for every case of the
 GPU matrix, the CPU back-end matches the exact reference bit for bit, the exact comparison rejects simulated kernel bugs that the old
 max-norm tolerances let through, and every FC-chain kernel compiled into libfleetrec.so is either named by a GPU-matrix case or listed
-as unreachable."""
+as unreachable.  For the shape sweep (exact_chain.SWEEPS: each kernel at the edges of the range its dispatch predicate accepts) the same
+premise and witnesses per row, the CPU back-end on every fp32 row, per edge a simulated bug that must change a score of every row that
+targets the edge, hashes that pin the existing matrix's data, and the printed coverage table."""
 import os
 import shutil
 import sys
@@ -13,6 +15,13 @@ import exact_chain as E
 from gpu_helpers import ROOT, bf16_round, e4m3_decode_table, e4m3_encode
 
 _CACHE = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_cache():
+    """The cached models and data go when the module is done (not at interpreter shutdown, when the library handle is gone)."""
+    yield
+    _CACHE.clear()
 
 
 def _case_rec(fr, case, n=None):
@@ -183,6 +192,197 @@ def test_mutant_restatements_match_the_reference(fr):
         else:
             ae, we = E.act_exponents(rec, ws), E.w_exponents(ws)
             assert np.array_equal(_fp8_chain(rec, ws, ae, we), E.expected("fp8", rec, ws, ae, we))
+
+
+# ---- the shape sweep (exact_chain.SWEEPS) -----------------------------------------------------------------------------------------------
+
+def _exps(row, rec, ws):
+    return (E.act_exponents(rec, ws), E.w_exponents(ws)) if row["prec"] == "fp8" else (None, None)
+
+
+def test_sweep_table_is_well_formed():
+    ids = [r["id"] for r in E.SWEEPS]
+    assert len(set(ids)) == len(ids)
+    assert not set(ids) & {c["id"] for c in E.CASES}
+    for r in E.SWEEPS:
+        assert r["layer"] in ("FC1", "FC2", "FC3", "stream") and r["kernel"] and r["edge"] and r["family"] in E.FAMILIES, r["id"]
+        assert (r["layer"] == "stream") == (r["group"] >= 12), r["id"]     # smaller launch groups ride the stage pipeline
+        assert r["batch"] <= 200 or r["spec"][0] <= 960, r["id"]
+    assert {r["family"] for r in E.SWEEPS} == set(E.FAMILIES)
+
+
+@pytest.mark.parametrize("row", E.SWEEPS, ids=[r["id"] for r in E.SWEEPS])
+def test_premise_holds_for_every_sweep_row(fr, row):
+    """As for the GPU matrix: the exactness premise, rounding witnesses on every hidden layer (the swept one included), deterministic data,
+    finite scores with more than a quarter of them distinct."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 256))
+    ws = data["ws"]
+    K, fc, _ = row["spec"]
+    assert m.record_len == K and list(m.fc) == [K] + list(fc) + [1] == data["fc"]
+    for l in range(4):
+        assert (ws[l] != 0).any(axis=1).all() and (ws[l] != 0).any(axis=0).all()
+    ae, we = _exps(row, rec, ws)
+    if row["prec"] == "fp8":
+        assert we == [7, 7, 7]
+    E.premise(row["prec"], rec, ws, ae, we)
+    if row["prec"] != "f32":
+        for l, (inexact, ties) in enumerate(E.rounding_witnesses(row["prec"], rec, ws, ae, we)):
+            assert inexact > 0 and ties > 0, (row["id"], l, inexact, ties)
+    s1 = E.expected(row["prec"], rec, ws, ae, we)
+    sp, data2, idx2, dense2 = E.case_data(row, idx.shape[0])
+    assert np.array_equal(idx2, idx) and all(np.array_equal(a, b) for a, b in zip(data2["ws"], ws))
+    assert all(np.array_equal(a, b) for a, b in zip(data2["tables"], data["tables"]))
+    assert np.array_equal(E.expected(row["prec"], E.records(m, data2, idx2, dense2), data2["ws"], ae, we), s1)
+    assert np.isfinite(s1).all() and np.unique(s1).size > s1.size // 4
+
+
+F32_SWEEPS = [r for r in E.SWEEPS if r["prec"] == "f32"]
+
+
+@pytest.mark.parametrize("row", F32_SWEEPS, ids=[r["id"] for r in F32_SWEEPS])
+def test_cpu_backend_bit_exact_on_sweep(fr, row):
+    """The library's CPU back-end on every fp32 sweep shape (at most 96 items): bit for bit."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 96))
+    want = E.expected("f32", rec, data["ws"])
+    ctx = fr.Context(m, device=fr.DEVICE_CPU)
+    try:
+        E.load(ctx, data)
+        wk = fr.Worker(ctx, idx.shape[0])
+        assert np.array_equal(wk.infer(idx, dense), want)
+        wk.close()
+    finally:
+        ctx.close()
+
+
+def _chain(prec, rec, ws, ae=None, we=None, prod=None):
+    """The chain of precision `prec` with layer l's matrix product replaced by prod(l, A, W) on the operands the device multiplies
+    (exact_chain.operands); prod None is the reference itself (asserted for every row before its mutants run)."""
+    prod = prod or (lambda l, A, W: A @ W)
+    if prec == "fp8":
+        dec = e4m3_decode_table()
+        x = dec[e4m3_encode(np.asarray(rec, np.float32) * np.float32(2.0 ** ae[0]))]
+        for l in range(3):
+            Wf = dec[e4m3_encode(ws[l] * np.float32(2.0 ** we[l]))]
+            r = (prod(l, x, Wf) * 2.0 ** -(ae[l] + we[l])).astype(np.float32) * np.float32(2.0 ** ae[l + 1])
+            x = dec[e4m3_encode(r)]
+        return ((x * 2.0 ** -ae[3]) @ ws[3].astype(np.float64)).astype(np.float32).ravel()
+    rnd = (lambda v: v) if prec == "f32" else bf16_round
+    x = rnd(np.asarray(rec, np.float32)).astype(np.float64)
+    for l in range(3):
+        r = prod(l, x, rnd(ws[l]).astype(np.float64)).astype(np.float32)
+        x = rnd(r).astype(np.float64)
+    return (x @ rnd(ws[3]).astype(np.float64)).astype(np.float32).ravel()
+
+
+def _at(L, fn):
+    return lambda l, A, W: fn(A, W) if l == L else A @ W
+
+
+def _drop_last_step(ks):
+    def fn(A, W):
+        k0 = (A.shape[1] + ks - 1) // ks * ks - ks
+        return A[:, :k0] @ W[:k0]
+    return fn
+
+
+def _stale_stage(ks):
+    return lambda A, W: A @ W - A[:, ks:2 * ks] @ W[ks:2 * ks] + A[:, :ks] @ W[:ks]
+
+
+def _skip_chunk(c):
+    def fn(A, W):
+        A = A.copy()
+        A[:, 256 * c:256 * (c + 1)] = 0.0
+        return A @ W
+    return fn
+
+
+def _first_partial_only(A, W):
+    h = A.shape[1] // 2
+    return A[:, :h] @ W[:h]
+
+
+def _pad_reads_last_group(g, kpad):
+    def fn(A, W):
+        K = A.shape[1]
+        src = K - g + np.arange(kpad - K) % g
+        return A @ W + A[:, src] @ W[src]
+    return fn
+
+
+def edge_mutants(row):
+    """The simulated bugs at the edge a sweep row sits on: name -> prod hook of _chain."""
+    L = 0 if row["layer"] == "stream" else ("FC1", "FC2", "FC3").index(row["layer"])
+    KL = ([row["spec"][0]] + list(row["spec"][1]))[L]
+    out = {}
+    if row.get("kstep"):
+        out["last K step of the swept layer dropped"] = _at(L, _drop_last_step(row["kstep"]))
+        if KL > row["kstep"]:
+            out["first K step used in place of the second (stale stage)"] = _at(L, _stale_stage(row["kstep"]))
+    if row.get("chunks"):
+        out["one H1 chunk of 256 skipped"] = _at(1, _skip_chunk(row["chunks"] - 1))   # FC2 never sees the last chunk of R1
+    for l, ns in enumerate(row.get("split") or ()):
+        if ns == 2:
+            out["second split-K partial not added (FC%d)" % (l + 1)] = _at(l, _first_partial_only)
+    if row.get("pad") and row["pad"][1] > KL:
+        out["zero-padded k-groups read as the last real k-group"] = _at(L, _pad_reads_last_group(*row["pad"]))
+    return out
+
+
+@pytest.mark.parametrize("row", E.SWEEPS, ids=[r["id"] for r in E.SWEEPS])
+def test_sweep_row_rejects_its_edge_mutants(fr, row):
+    """Every mutant of the edge a row targets changes at least one of the row's scores: the data is not zero exactly where the edge bites."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 256))
+    ws = data["ws"]
+    ae, we = _exps(row, rec, ws)
+    want = E.expected(row["prec"], rec, ws, ae, we)
+    assert np.array_equal(_chain(row["prec"], rec, ws, ae, we), want)
+    mutants = edge_mutants(row)
+    assert mutants or row["family"] == "stage", row["id"]   # (a stage row of the unsplit plan (1, 1, 1) has no edge of its own to mutate)
+    for name, prod in mutants.items():
+        bad = _chain(row["prec"], rec, ws, ae, we, prod)
+        assert not np.array_equal(bad, want), (row["id"], name)
+
+
+def test_every_edge_mutant_is_exercised():
+    names = set()
+    for r in E.SWEEPS:
+        names.update(n.split(" (FC")[0] for n in edge_mutants(r))
+    assert names == {"last K step of the swept layer dropped", "first K step used in place of the second (stale stage)", "one H1 chunk of 256 skipped",
+                     "second split-K partial not added", "zero-padded k-groups read as the last real k-group"}
+
+
+# E.expected(...) of three cases of the GPU matrix (one per precision), sha256 of the float32 bytes, taken before SWEEPS and make_data's
+# optional parameter existed: the sweep must not move the existing matrix's data.
+PINNED = {
+    "f32-A352-g16": "495c68bec55730a95c73061b56c1d8c7f367c2dbc931113d6f6755493173ed84",
+    "bf16-C-b65": "304c361987611f31546af08843e6947b0988d9e29ef237ab90c0fc59e4f7bd1d",
+    "fp8-C-b65": "e742c2656bd0594c736f7e8e359586333ab469e17df373bbc448be56696c41d4",
+}
+
+
+@pytest.mark.parametrize("case_id", list(PINNED))
+def test_existing_matrix_did_not_move(fr, case_id):
+    import hashlib
+    case = next(c for c in E.CASES if c["id"] == case_id)
+    m, data, idx, dense, rec = _case_rec(fr, case)
+    ae, we = _exps(case, rec, data["ws"])
+    s = E.expected(case["prec"], rec, data["ws"], ae, we)
+    assert hashlib.sha256(np.ascontiguousarray(s, np.float32).tobytes()).hexdigest() == PINNED[case_id]
+
+
+def test_sweep_coverage_table():
+    """One line per kernel family: the range its predicate accepts, what the sweep covers, what it leaves out and why (printed; the table of the
+    change's description)."""
+    for fam, (accepted, omitted) in E.FAMILIES.items():
+        rows = [r for r in E.SWEEPS if r["family"] == fam]
+        assert rows, fam
+        cover = sorted({"%s %s" % (r["prec"], r["cover"]) for r in rows})
+        print("sweep %-8s %3d rows | accepts: %s | covers: %s | kernels: %s | left out: %s" % (
+            fam, len(rows), accepted, ", ".join(cover), ", ".join(sorted({r["kernel"] for r in rows})), omitted))
+    # the plans the stage rows and the GPU matrix give between them: every (partials read, own split) pair at FC2 and FC3
+    pairs = {l: {(E.split_plan(r)[l - 1], E.split_plan(r)[l]) for r in E.SWEEPS if r["family"] == "stage" and r["prec"] == "f32"} for l in (1, 2)}
+    assert pairs[1] | {(2, 2)} == pairs[2] | {(2, 2)} == {(1, 1), (1, 2), (2, 1), (2, 2)}, pairs   # (2, 2): Model C in the GPU matrix
 
 
 # ---- kernel completeness -------------------------------------------------------------------------------------------------------------

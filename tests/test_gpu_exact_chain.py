@@ -1,5 +1,6 @@
 """GPU parity on integer-valued data (tests/exact_chain.py): every FC-chain kernel, through every entry point, bit for bit against the host's
-exact restatement of the chain -- no tolerance.  Each case of exact_chain.CASES also pins the kernel the dispatcher picks for it."""
+exact restatement of the chain -- no tolerance.  Each case of exact_chain.CASES also pins the kernel the dispatcher picks for it; each
+row of exact_chain.SWEEPS runs one kernel at an edge of the shapes its dispatch predicate accepts (test_exact_sweep)."""
 import numpy as np
 import pytest
 
@@ -86,6 +87,47 @@ def test_exact_case(fr, gpu, case):
         for l, want_k in enumerate(case.get("layers") or []):
             if want_k:
                 assert names[l] == want_k, (l, names)
+    finally:
+        wk.close()
+        ctx.close()
+
+
+@pytest.mark.parametrize("row", E.SWEEPS, ids=[r["id"] for r in E.SWEEPS])
+def test_exact_sweep(fr, gpu, row):
+    """A shape on an edge of a kernel's accepted range (exact_chain.SWEEPS): one infer, then one push -- or the row's stream group of pushes,
+    where it names a streamed kernel -- into NaN-filled buffers one ldm long: every item bit-exact, nothing written past the batch, and the
+    swept layer (or the streamed launch) ran the kernel the row names."""
+    m, ctx, data, idx, dense, rec = _setup(fr, gpu, row)
+    B, ws = row["batch"], data["ws"]
+    ldm = (B + 31) // 32 * 32
+    wk = fr.Worker(ctx, B)
+    try:
+        want, _, _ = _expect(row, ctx, wk, idx, dense, rec, ws)
+        _same(wk.infer(idx, dense), want, "infer")
+        ctx.set_stream_group(row["group"])
+        d_i = fr.DeviceBuffer.from_numpy(ctx, np.ascontiguousarray(idx))
+        d_d = fr.DeviceBuffer.from_numpy(ctx, np.ascontiguousarray(dense)) if dense is not None else None
+        streamed = row["layer"] == "stream"
+        n_push = row["group"] if streamed else 1
+        outs = []
+        for _ in range(n_push):
+            o = fr.DeviceBuffer(ctx, ldm * 4)
+            o.upload(np.full(ldm, np.nan, np.float32))
+            wk.push_device(B, d_i, d_d, o)
+            outs.append(o)
+        wk.sync()
+        if streamed:
+            assert wk.last_kernel() == row["kernel"], wk.last_kernel()
+        for j, o in enumerate(outs):
+            got = o.download(np.float32, ldm)
+            _same(got[:B], want, "push %d of %d" % (j, n_push))
+            assert np.isnan(got[B:]).all(), "push %d of %d wrote past the batch" % (j, n_push)
+            o.free()
+        if not streamed:
+            wk.fc_layer_only(B, ("FC1", "FC2", "FC3").index(row["layer"]))
+            name = wk.last_kernel()
+            wk.sync()
+            assert name == row["kernel"], name
     finally:
         wk.close()
         ctx.close()
