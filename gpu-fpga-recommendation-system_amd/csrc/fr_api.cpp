@@ -85,36 +85,47 @@ static int lp_ensure_image(fr_ctx *c, int prec);
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 
+// ---- memory (fr_mem.h): the one place that allocates and releases, and the tally of what is live -------------------------------------------
+static std::atomic<uint64_t> g_live_bytes[2];   // [0] device, [1] host
+static inline std::atomic<uint64_t> &live_of(FrMem kind) { return g_live_bytes[kind == FrMem::DEVICE ? 0 : 1]; }
+void fr_mem_live_bytes(uint64_t out[2]) {
+    for (int i = 0; i < 2; i++) out[i] = g_live_bytes[i].load(std::memory_order_relaxed);
+}
+#ifdef FR_EXPERIMENTS
+extern "C" __attribute__((visibility("default"))) void fr_exp_live_bytes(uint64_t out[2]) { fr_mem_live_bytes(out); }   // experiments build only (no header)
+#endif
+
+int fr_mem_alloc(FrMem kind, size_t bytes, const char *what, void **out) {
+    *out = nullptr;
+    if (kind == FrMem::ARENA) {
+        if (!(*out = frc_arena_alloc(bytes))) return FR_ERR_OOM;   // (it has said why)
+    } else if (kind == FrMem::HOST) {
+        if (!(*out = aligned_alloc(64, align_up(bytes ? bytes : 64, 64)))) FR_FAIL(FR_ERR_OOM, "out of host memory (%s, %zu bytes)", what, bytes);
+    } else {
+        const hipError_t e = kind == FrMem::DEVICE ? hipMalloc(out, bytes) : hipHostMalloc(out, bytes, kind == FrMem::PINNED_MAPPED ? hipHostMallocMapped : hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            *out = nullptr;
+            FR_FAIL(e == hipErrorOutOfMemory ? FR_ERR_OOM : FR_ERR_HIP, "%s(%s, %zu bytes) failed: %s", kind == FrMem::DEVICE ? "hipMalloc" : "hipHostMalloc", what, bytes, hipGetErrorString(e));
+        }
+    }
+    if (*out) live_of(kind).fetch_add(bytes, std::memory_order_relaxed);
+    return FR_OK;
+}
+
+void fr_mem_release(FrMem kind, void *p, size_t bytes) {
+    if (!p) return;
+    if (kind == FrMem::ARENA) frc_arena_free(p, bytes);
+    else if (kind == FrMem::HOST) free(p);
+    else if (kind == FrMem::DEVICE) (void)hipFree(p);
+    else (void)hipHostFree(p);
+    live_of(kind).fetch_sub(bytes, std::memory_order_relaxed);
+}
+
 // ---- context --------------------------------------------------------------------------------------
-static void ctx_free(fr_ctx *c) {
+static void ctx_free(fr_ctx *c) {   // every buffer is released by its holder (fr_mem.h)
     if (!c) return;
-    if (c->cpu) {   // the CPU back-end: host memory only
-        frc_arena_free(c->table_arena, c->table_arena_bytes);
-        for (int i = 0; i < 4; i++) free(c->d_w[i]);
-        delete c;
-        return;
-    }
-    if (c->device >= 0) (void)hipSetDevice(c->device);
-    if (c->table_arena) (void)hipFree(c->table_arena);
-    if (c->lp_arena) (void)hipFree(c->lp_arena);
-    if (c->d_words_lp) (void)hipFree(c->d_words_lp);
-    if (c->d_words) (void)hipFree(c->d_words);
-    if (c->d_passes) (void)hipFree(c->d_passes);
-    if (c->d_chunks) (void)hipFree(c->d_chunks);
-    if (c->d_merged) (void)hipFree(c->d_merged);
-    if (c->d_pool) (void)hipFree(c->d_pool);
-    if (c->d_req_desc) (void)hipFree(c->d_req_desc);
-    for (int i = 0; i < 4; i++) {
-        if (c->d_w[i]) (void)hipFree(c->d_w[i]);
-        if (i < 3 && c->d_wq[i]) (void)hipFree(c->d_wq[i]);
-        if (c->d_w_bf16[i]) (void)hipFree(c->d_w_bf16[i]);
-        if (i < 3 && c->d_w_fp8[i]) (void)hipFree(c->d_w_fp8[i]);
-        if (i < 3 && c->d_w_fp8h[i]) (void)hipFree(c->d_w_fp8h[i]);
-    }
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_up_ids) (void)hipFree(c->d_up_ids);
-    if (c->d_up_rows) (void)hipFree(c->d_up_rows);
-    if (c->h_up_err) (void)hipHostFree(c->h_up_err);
+    if (!c->cpu && c->device >= 0) (void)hipSetDevice(c->device);
     if (c->setup_stream) (void)hipStreamDestroy(c->setup_stream);
     delete c;
 }
@@ -301,11 +312,9 @@ static int build_words(fr_ctx *c) {
         off = align_up(off + (size_t)m.tables[t].rows * m.tables[t].dim * 4, 256);
     }
     c->table_arena_bytes = off;
-    if (off && c->cpu) {
-        c->table_arena = (char *)frc_arena_alloc(off);
-        if (!c->table_arena) return FR_ERR_OOM;
-    } else if (off) {
-        FR_HIP(hipMalloc((void **)&c->table_arena, off));
+    if (off) {
+        const int rc = c->table_arena.alloc(c->cpu ? FrMem::ARENA : FrMem::DEVICE, off, "table arena");
+        if (rc) return rc;
     }
 
     // source runs (for the BLOCKED layout)
@@ -357,7 +366,7 @@ static int build_words(fr_ctx *c) {
     c->n_words = (int)c->h_words.size();
     if (c->cpu) return FR_OK;   // the CPU back-end walks h_words
     plan_gather_groups(c);
-    FR_HIP(hipMalloc((void **)&c->d_words, sizeof(FrWordDesc) * c->n_words));
+    FR_TRY(c->d_words.alloc(FrMem::DEVICE, (size_t)c->n_words, "word descriptors"));
     FR_HIP(hipMemcpy(c->d_words, c->h_words.data(), sizeof(FrWordDesc) * c->n_words, hipMemcpyHostToDevice));
     // Item-tile gather plan (gather_tile_kernel): every record segment is cut in power-of-two pieces of <= 16 words, a piece of w words
     // becomes w passes (64 / w items each), consecutive pieces are grouped in chunks of <= FR_TILE_WORDS words.  The destination must
@@ -401,11 +410,11 @@ static int build_words(fr_ctx *c) {
         if (cur.n_words) chunks.push_back(cur);
         c->n_chunks = (int)chunks.size();
         if (c->n_chunks) {
-            FR_HIP(hipMalloc((void **)&c->d_passes, sizeof(FrPassDesc) * passes.size()));
+            FR_TRY(c->d_passes.alloc(FrMem::DEVICE, passes.size(), "gather passes"));
             FR_HIP(hipMemcpy(c->d_passes, passes.data(), sizeof(FrPassDesc) * passes.size(), hipMemcpyHostToDevice));
-            FR_HIP(hipMalloc((void **)&c->d_chunks, sizeof(FrChunkDesc) * chunks.size()));
+            FR_TRY(c->d_chunks.alloc(FrMem::DEVICE, chunks.size(), "gather chunks"));
             FR_HIP(hipMemcpy(c->d_chunks, chunks.data(), sizeof(FrChunkDesc) * chunks.size(), hipMemcpyHostToDevice));
-            FR_HIP(hipMalloc((void **)&c->d_merged, sizeof(unsigned long long)));
+            FR_TRY(c->d_merged.alloc(FrMem::DEVICE, 1, "dedup counter"));
             FR_HIP(hipMemset(c->d_merged, 0, sizeof(unsigned long long)));
         }
     }
@@ -449,33 +458,22 @@ extern "C" int fr_ctx_create_sharded(const fr_model_desc *m, int device, int sha
         ctx_free(c);
         return rc;
     }
-    if (cpu) {   // fp32 master weights in the reference's column-major H x K layout: all the CPU chain reads
-        for (int l = 0; l < 4; l++) {
-            c->d_w[l] = (float *)malloc((size_t)m->fc[l] * m->fc[l + 1] * sizeof(float));
-            if (!c->d_w[l]) {
-                ctx_free(c);
-                FR_FAIL(FR_ERR_OOM, "out of host memory (weights layer %d)", l);
-            }
-        }
-        *out = c;
-        return FR_OK;
-    }
-    {   // immutable after creation (read by every driver thread in fused_flush without synchronisation): the device's compute units and
+    if (!cpu) {   // immutable after creation (read by every driver thread in fused_flush without synchronisation): the device's compute units and
         // whether the persistent K-outer fused kernel applies to this context's descriptors and FC shape
         int n_cu = 0;
         if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) n_cu = 0;
         c->n_cu = n_cu > 0 ? n_cu : 256;
         c->hk_ok = frk_fused_hk_ok(m->fc[0], m->fc[1], m->fc[2], m->fc[3], c->h_words.data(), c->n_words) ? 1 : 0;
     }
-    for (int l = 0; l < 4; l++) {
-        size_t n = (size_t)m->fc[l] * m->fc[l + 1];
-        e = hipMalloc((void **)&c->d_w[l], n * sizeof(float));
-        if (e == hipSuccess && l < 3) e = hipMalloc((void **)&c->d_wq[l], n * sizeof(float));
-        if (e != hipSuccess) {
-            fr_set_error("hipMalloc(weights layer %d) failed: %s", l, hipGetErrorString(e));
-            ctx_free(c);
-            return FR_ERR_OOM;
-        }
+    // fp32 master weights in the reference's column-major H x K layout (all the CPU chain reads), and on a device their q4 re-pack
+    for (int l = 0; l < 4 && !rc; l++) {
+        const size_t n = (size_t)m->fc[l] * m->fc[l + 1];
+        rc = c->d_w[l].alloc(fr_mem_kind(c, FrMem::DEVICE), n, "weights");
+        if (!rc && !cpu && l < 3) rc = c->d_wq[l].alloc(FrMem::DEVICE, n, "re-packed weights");
+    }
+    if (rc) {
+        ctx_free(c);
+        return rc;
     }
     *out = c;
     return FR_OK;
@@ -631,9 +629,10 @@ static int refresh_fp8(fr_ctx *ctx, int layer) {
     if (layer >= 3) return FR_OK;  // the output layer stays in fp32
     const int K = ctx->model.fc[layer], H = ctx->model.fc[layer + 1];
     const int KP = (K + 63) / 64 * 64;
-    if (!ctx->d_w_fp8[layer]) FR_HIP(hipMalloc(&ctx->d_w_fp8[layer], (size_t)KP * H));
-    if (!ctx->d_stats) FR_HIP(hipMalloc((void **)&ctx->d_stats, 64));
-    int rc = frk_stats(ctx->d_w[layer], (size_t)K * H, ctx->d_stats, ctx->setup_stream);
+    int rc = ctx->d_w_fp8[layer].grow(FrMem::DEVICE, (size_t)KP * H, "fp8 weights");
+    if (!rc) rc = ctx->d_stats.grow(FrMem::DEVICE, 16, "reduction scratch");
+    if (rc) return rc;
+    rc = frk_stats(ctx->d_w[layer], (size_t)K * H, ctx->d_stats, ctx->setup_stream);
     if (rc) return rc;
     uint32_t st[2];
     FR_HIP(hipMemcpyAsync(st, ctx->d_stats, 8, hipMemcpyDeviceToHost, ctx->setup_stream));
@@ -649,8 +648,8 @@ static int refresh_fp8(fr_ctx *ctx, int layer) {
 #ifdef FR_EXPERIMENTS
     if (frk_fused_f8_ok(ctx->model.fc[0], ctx->model.fc[1], ctx->model.fc[2], ctx->model.fc[3])) {  // the persistent kernel's fp8 form (experiments build only)
         const int KP32 = (K + 31) / 32 * 32;
-        if (!ctx->d_w_fp8h[layer]) FR_HIP(hipMalloc(&ctx->d_w_fp8h[layer], (size_t)KP32 * H));
-        rc = frk_pack_weights_q16h_fp8(ctx->d_w[layer], ctx->d_w_fp8h[layer], K, H, ctx->f8_e_w[layer], ctx->setup_stream);
+        rc = ctx->d_w_fp8h[layer].grow(FrMem::DEVICE, (size_t)KP32 * H, "fp8 weights (q16h)");
+        if (!rc) rc = frk_pack_weights_q16h_fp8(ctx->d_w[layer], ctx->d_w_fp8h[layer], K, H, ctx->f8_e_w[layer], ctx->setup_stream);
     }
 #endif
     return rc;
@@ -665,7 +664,7 @@ static int refresh_bf16(fr_ctx *ctx, int layer) {
     if (ctx->fc_precision == FR_FC_FP8) return refresh_fp8(ctx, layer);
     if (ctx->fc_precision != FR_FC_BF16) return FR_OK;
     size_t n = (size_t)ctx->model.fc[layer] * ctx->model.fc[layer + 1];
-    if (!ctx->d_w_bf16[layer]) FR_HIP(hipMalloc((void **)&ctx->d_w_bf16[layer], n * sizeof(uint16_t)));
+    FR_TRY(ctx->d_w_bf16[layer].grow(FrMem::DEVICE, n, "bf16 weights"));
     // Wh[k/8][h][k%8]; for the output layer (H == 1) this is simply the bf16 vector w[k]
     return frk_pack_weights_q8_bf16(ctx->d_w[layer], ctx->d_w_bf16[layer], ctx->model.fc[layer], ctx->model.fc[layer + 1], ctx->setup_stream);
 }
@@ -779,62 +778,17 @@ static void ctx_delist(fr_ctx *c, fr_worker *w) {
 extern "C" void fr_worker_destroy(fr_worker *w) {
     if (!w) return;
     if (w->ctx && w->counted) ctx_delist(w->ctx, w);
-    if (w->ctx && w->ctx->cpu) {
-        fr_comm_worker_release(w);   // a sharded step still on the worker's host stream: waited for (bounded), its communicator let go
-        if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
-        void *host[] = {w->h_idx, w->h_pool_w, w->h_pool_off, w->h_req_idx, w->h_req_w, w->h_req_dense, w->h_req_off, w->d_idx, w->d_dense, w->d_pool_w, w->h_dense, w->h_score, w->d_records, w->c_scratch, w->c_x, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all, w->h_sh_status};
-        for (void *p : host) free(p);
-        fr_ctx *held = w->counted ? w->ctx : nullptr;
-        delete w;
-        fr_ctx_unref(held);   // (the last worker of a context that was already destroyed releases it)
-        return;
-    }
-    if (w->ctx) (void)hipSetDevice(w->ctx->device);
-    fr_comm_worker_release(w);   // a sharded step still being issued by the worker's host stream (staged exchange) is waited for (bounded); the communicator is let go
-    if (w->stream) (void)hipStreamSynchronize(w->stream);
+    if (w->ctx && !w->ctx->cpu) (void)hipSetDevice(w->ctx->device);
+    // a sharded step still on the worker's host stream (a CPU worker's step; a GPU worker's staged exchange) is waited for (bounded), its communicator let go
+    fr_comm_worker_release(w);
+    const hipStream_t streams[] = {w->stream, w->hr.copy};
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamSynchronize(s);
     if (w->counted) w->ctx->n_workers.fetch_sub(1, std::memory_order_relaxed);
-    if (w->h_idx) (void)hipHostFree(w->h_idx);
-    if (w->h_pool_w) (void)hipHostFree(w->h_pool_w);
-    if (w->h_pool_off) (void)hipHostFree(w->h_pool_off);
-    for (void *p : {(void *)w->h_req_idx, (void *)w->h_req_w, (void *)w->h_req_dense, (void *)w->h_req_off})
-        if (p) (void)hipHostFree(p);
-    if (w->h_dense) (void)hipHostFree(w->h_dense);
-    if (w->h_score) (void)hipHostFree(w->h_score);
-    if (w->h_err) (void)hipHostFree(w->h_err);
-    if (w->h_sh_status) (void)hipHostFree(w->h_sh_status);
-    if (w->h_stage_send) (void)hipHostFree(w->h_stage_send);
-    if (w->h_stage_recv) (void)hipHostFree(w->h_stage_recv);
-    if (w->h_tk_off) (void)hipHostFree(w->h_tk_off);
-    if (w->h_tk_idx) (void)hipHostFree(w->h_tk_idx);
-    if (w->h_tk_sc) (void)hipHostFree(w->h_tk_sc);
-    if (w->d_rank) (void)hipFree(w->d_rank);
-    void *dev[] = {w->d_idx, w->d_dense, w->d_pool_w, w->d_records, w->d_act[0], w->d_act[1], w->d_score, w->d_slice, w->d_gathered, w->d_score_part, w->d_score_all};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (w->hr.h_idx) (void)hipHostFree(w->hr.h_idx);
-    if (w->hr.h_dense) (void)hipHostFree(w->hr.h_dense);
-    if (w->hr.h_sc) (void)hipHostFree(w->hr.h_sc);
-    void *hdev[] = {w->hr.d_idx, w->hr.d_dense, w->hr.d_sc};
-    for (void *p : hdev)
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : w->hr.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : w->hr.ev_in)
-        if (e) (void)hipEventDestroy(e);
-    if (w->hr.copy) {
-        (void)hipStreamSynchronize(w->hr.copy);
-        (void)hipStreamDestroy(w->hr.copy);
-    }
-    if (w->h_blist) (void)hipHostFree(w->h_blist);
-    if (w->d_blist) (void)hipFree(w->d_blist);
-    for (hipEvent_t e : w->ev_blist)
-        if (e) (void)hipEventDestroy(e);
-    if (w->ev_update) (void)hipEventDestroy(w->ev_update);
-    if (w->ev_start) (void)hipEventDestroy(w->ev_start);
-    if (w->ev_stop) (void)hipEventDestroy(w->ev_stop);
-    if (w->stream) (void)hipStreamDestroy(w->stream);
     fr_ctx *held = w->counted ? w->ctx : nullptr;
-    delete w;
+    delete w;   // every buffer and event is released by its holder (fr_mem.h), behind both streams
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamDestroy(s);
     fr_ctx_unref(held);   // (the last worker of a context that was already destroyed releases it)
 }
 
@@ -851,15 +805,93 @@ static void request_caps(const fr_ctx *c, fr_worker *w) {
     w->req_w_cap = w->pool_w_cap ? (rp > 0 ? rp : 1) : 0;
 }
 
-#define W_HIP(call)                                                                       \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            fr_set_error("%s failed: %s", #call, hipGetErrorString(e_));                  \
-            fr_worker_destroy(w);                                                         \
-            return (e_ == hipErrorOutOfMemory) ? FR_ERR_OOM : FR_ERR_HIP;                 \
-        }                                                                                 \
-    } while (0)
+// the stream, buffers and events of a new worker, one sequence for both back-ends; a failure leaves what was made to fr_worker_destroy
+static int worker_build(fr_worker *w) {
+    fr_ctx *ctx = w->ctx;
+    const int max_batch = w->max_batch;
+    const fr_model_desc &m = ctx->model;
+    const size_t B = (size_t)max_batch;
+    // the index buffers hold one-hot rows and, when pooling is set already, pooled rows (fr_worker_submit_pooled)
+    w->idx_cap = (int)idx_cols(ctx) > ctx->pool_cols ? (int)idx_cols(ctx) : ctx->pool_cols;
+    w->pool_w_cap = ctx->pool_cols;   // per-sample weights of the host form (fr_worker_submit_pooled_weighted): only when pooling is set already
+    if (!ctx->cpu) {
+        // A model that runs the stage pipeline (several launches per step: Model-C, sharded contexts) gives its workers hardware queues of
+        // their own: the HIP runtime keeps one pool of hardware queues per stream priority, four equal-priority streams share two queues
+        // (profiles/archive/r04_C4096_chain_trace_bf16.txt), and there a small launch of one worker waits behind the other's FC1.  The workers
+        // alternate between the HIGHEST and the LOWEST priority, never the default one: those two pools are this library's alone, so the
+        // first four workers get four consecutively created queues = one per compute pipe of the command processor (queue id mod 4;
+        // two workers whose queues share a pipe run 10 % behind the others: profiles/archive/r04_stream_queues_after_other_contexts.txt -- with
+        // the default priority in the rotation, a context served earlier in the process had that effect).  Model-C 4096, four workers:
+        // bf16 41.9 -> 43.1 M inf/s, fp8 65.5 -> 68.9 M = what GPU_MAX_HW_QUEUES=8 buys (profiles/archive/r04_stream_priorities_ab.txt).
+        // Fused-kernel models (one launch per group) gain nothing from it and keep the default streams.
+        // (a model no fused kernel of any precision serves -- the decision must not depend on the precision the context happens to have now)
+        const bool any_fused = frk_fused_ok(m.fc[0], m.fc[1], m.fc[2], m.fc[3]) || frk_fused_h_ok(m.fc[0], m.fc[1], m.fc[2], m.fc[3]) ||
+                               frk_fused_f8_ok(m.fc[0], m.fc[1], m.fc[2], m.fc[3]) || ctx->hk_ok == 1;
+        const bool chain = !(ctx->n_shards == 1 && m.layout == FR_LAYOUT_SEMANTIC && any_fused);
+        const int spread = FR_KNOB_ONCE("STREAM_PRIO", -1);   // experiment knob: 0 = never, 1 = always, 2 = rotate over every level (default included)
+        int lo = 0, hi = 0;   // numerically lower = higher priority
+        if (spread < 0 ? chain : spread != 0) FR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        // k = how many workers the context has EVER created (one fetch_add: two threads creating workers at once cannot draw the same k, and a
+        // destroy + create keeps alternating -- ADVICE r04: the live count did neither)
+        const int k = ctx->worker_seq.fetch_add(1, std::memory_order_relaxed);
+        // (Round 6 tried to CHECK and REPAIR the outcome, and kept none of it -- profiles/r06_experiments.md section 4: after some stream churn in the
+        // process one pair of a context's four workers takes turns (four Model-C chains 48 -> 37-45 M inf/s).  Handshake kernels on the two streams
+        // see each other resident; a BURST of part-chip spin launches on both does expose the pair (0.8-1.2 kernels resident of 2 against 1.95-2.0)
+        // -- but a stream that probes clean at creation pairs up again when the next queue is created, a pool of streams pairs up all the same,
+        // and replacing streams after all workers exist does not converge.  What the library controls is what it does here.)
+        if (lo > hi) FR_HIP(hipStreamCreateWithPriority(&w->stream, hipStreamNonBlocking, spread == 2 ? hi + k % (lo - hi + 1) : (k % 2 ? lo : hi)));
+        else FR_HIP(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    }
+    // Sizes and existence are stated once for both back-ends; on the CPU back-end (fr_mem_kind) every buffer is plain host memory behind the same
+    // accessors (fr_worker_idx_ptr / dense_ptr / score_ptr), and the device-side stand-ins d_idx / d_dense / d_pool_w exist only with a request split.
+    const bool cpu = ctx->cpu, split = !ctx->req_shared.empty();
+    const FrMem pinned = fr_mem_kind(ctx, FrMem::PINNED), device = fr_mem_kind(ctx, FrMem::DEVICE);
+    const size_t n_idx = B * (size_t)w->idx_cap, n_dense = B * m.dense_len, n_pool_w = B * (size_t)w->pool_w_cap;
+    FR_TRY(w->h_idx.alloc(pinned, n_idx, "worker index rows"));
+    if (w->pool_w_cap) FR_TRY(w->h_pool_w.alloc(pinned, n_pool_w, "worker per-sample weights"));   // read in place by the gather, like h_idx
+    if (w->pool_w_cap) FR_TRY(w->h_pool_off.alloc(pinned, B * idx_cols(ctx) + 1, "worker bag offsets"));   // bag offsets of the offsets-form host call
+    if (m.dense_len) FR_TRY(w->h_dense.alloc(pinned, n_dense, "worker dense rows"));
+    FR_TRY(w->h_score.alloc(pinned, B, "worker scores"));
+    if (cpu) {
+        w->h_err = w->d_err = &w->c_err;
+    } else {
+        // index-range flag: pinned, device-visible host word.  Kernels touch it only on the error path
+        // (system-scope atomicOr), so fr_worker_sync() needs no D2H copy -- it just reads the word after the stream drained.
+        FR_TRY(w->err_word.alloc(FrMem::PINNED_MAPPED, 1, "worker status word"));
+        w->h_err = w->err_word;
+        *w->h_err = 0;
+        FR_HIP(hipHostGetDevicePointer((void **)&w->d_err, w->h_err, 0));
+    }
+    if (!cpu || split) {
+        FR_TRY(w->d_idx.alloc(device, n_idx, "worker index rows (device)"));
+        if (m.dense_len) FR_TRY(w->d_dense.alloc(device, n_dense, "worker dense rows (device)"));
+    }
+    FR_TRY(w->d_records.alloc(device, B * (size_t)ctx->slice_padded, "worker records"));
+    if (!cpu && ctx->n_shards == 1 && ctx->slice_padded != m.record_len) FR_FAIL(FR_ERR_STATE, "internal: unsharded ctx with a partial slice");
+    if (cpu) {   // a call computes before it returns: the chain's scratch, and the records of the sharded FC entry points
+        FR_TRY(w->c_scratch.alloc(FrMem::HOST, B * ((size_t)m.fc[1] + m.fc[2] + m.fc[3]), "worker chain scratch"));
+        if (ctx->n_shards > 1) FR_TRY(w->c_x.alloc(FrMem::HOST, B * (size_t)m.fc[0], "worker records (sharded)"));
+    } else {
+        w->ld_max = round_up(max_batch, 64);
+        for (int p = 0; p < 2; p++)
+            FR_TRY(w->d_act[p].alloc(FrMem::DEVICE, (size_t)w->ld_max * ((size_t)m.fc[0] + 2 * ((size_t)m.fc[1] + m.fc[2] + m.fc[3])), "worker activations"));
+        FR_TRY(w->d_score.alloc(FrMem::DEVICE, B, "worker scores (device)"));
+    }
+    if (split) {   // request-form host call: the request side's buffers (pinned: read in place by the expansion) and the expanded weights
+        request_caps(ctx, w);
+        FR_TRY(w->h_req_idx.alloc(pinned, B * (size_t)w->req_idx_cap, "worker request rows"));
+        if (w->req_w_cap) FR_TRY(w->h_req_w.alloc(pinned, B * (size_t)w->req_w_cap, "worker request weights"));
+        if (ctx->req_dense_shared) FR_TRY(w->h_req_dense.alloc(pinned, n_dense, "worker request dense rows"));
+        FR_TRY(w->h_req_off.alloc(pinned, B + 1, "worker request offsets"));
+        if (w->pool_w_cap) FR_TRY(w->d_pool_w.alloc(device, n_pool_w, "worker expanded weights"));
+    }
+    if (!cpu) {
+        FR_HIP(w->ev_start.create(hipEventDefault));
+        FR_HIP(w->ev_stop.create(hipEventDefault));
+        FR_HIP(w->ev_update.create(hipEventDisableTiming));
+    }
+    return FR_OK;
+}
 
 extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     if (!ctx || !out) FR_FAIL(FR_ERR_INVALID, "NULL argument");
@@ -876,106 +908,11 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     if (!w) FR_FAIL(FR_ERR_OOM, "out of host memory");
     w->ctx = ctx;
     w->max_batch = max_batch;
-    const fr_model_desc &m = ctx->model;
-    const size_t B = (size_t)max_batch;
-    // the index buffers hold one-hot rows and, when pooling is set already, pooled rows (fr_worker_submit_pooled)
-    w->idx_cap = (int)idx_cols(ctx) > ctx->pool_cols ? (int)idx_cols(ctx) : ctx->pool_cols;
-    w->pool_w_cap = ctx->pool_cols;   // per-sample weights of the host form (fr_worker_submit_pooled_weighted): only when pooling is set already
-    if (ctx->cpu) {   // the CPU back-end: plain host buffers behind the same accessors (fr_worker_idx_ptr / dense_ptr / score_ptr)
-        auto host = [](size_t bytes) { return aligned_alloc(64, align_up(bytes ? bytes : 64, 64)); };
-        w->h_idx = (int32_t *)host(B * (size_t)w->idx_cap * sizeof(int32_t));
-        if (w->pool_w_cap) w->h_pool_w = (float *)host(B * (size_t)w->pool_w_cap * sizeof(float));
-        if (w->pool_w_cap) w->h_pool_off = (int32_t *)host((B * idx_cols(ctx) + 1) * sizeof(int32_t));
-        if (m.dense_len) w->h_dense = (float *)host(B * m.dense_len * sizeof(float));
-        w->h_score = (float *)host(B * sizeof(float));
-        w->d_records = (float *)host(B * (size_t)ctx->slice_padded * sizeof(float));
-        w->c_scratch = (float *)host(B * ((size_t)m.fc[1] + m.fc[2] + m.fc[3]) * sizeof(float));
-        if (ctx->n_shards > 1) w->c_x = (float *)host(B * (size_t)m.fc[0] * sizeof(float));
-        bool req_ok = true;
-        if (!ctx->req_shared.empty()) {   // request-form host call: the request side's buffers, and host stand-ins for the device buffers the expansion writes
-            request_caps(ctx, w);
-            w->h_req_idx = (int32_t *)host(B * (size_t)w->req_idx_cap * sizeof(int32_t));
-            if (w->req_w_cap) w->h_req_w = (float *)host(B * (size_t)w->req_w_cap * sizeof(float));
-            if (ctx->req_dense_shared) w->h_req_dense = (float *)host(B * m.dense_len * sizeof(float));
-            w->h_req_off = (int32_t *)host((B + 1) * sizeof(int32_t));
-            w->d_idx = (int32_t *)host(B * (size_t)w->idx_cap * sizeof(int32_t));
-            if (m.dense_len) w->d_dense = (float *)host(B * m.dense_len * sizeof(float));
-            if (w->pool_w_cap) w->d_pool_w = (float *)host(B * (size_t)w->pool_w_cap * sizeof(float));
-            req_ok = w->h_req_idx && (!w->req_w_cap || w->h_req_w) && (!ctx->req_dense_shared || w->h_req_dense) && w->h_req_off && w->d_idx && (!m.dense_len || w->d_dense) &&
-                     (!w->pool_w_cap || w->d_pool_w);
-        }
-        if (!req_ok || !w->h_idx || (w->pool_w_cap && (!w->h_pool_w || !w->h_pool_off)) || (m.dense_len && !w->h_dense) || !w->h_score || !w->d_records || !w->c_scratch || (ctx->n_shards > 1 && !w->c_x)) {
-            fr_worker_destroy(w);
-            FR_FAIL(FR_ERR_OOM, "out of host memory (worker buffers for batch %d)", max_batch);
-        }
-        w->h_err = w->d_err = &w->c_err;
-        w->counted = true;
-        fr_ctx_ref(ctx);
-        ctx_enlist(ctx, w);
-        ctx->n_workers.fetch_add(1, std::memory_order_relaxed);
-        *out = w;
-        return FR_OK;
-    }
-    {
-        // A model that runs the stage pipeline (several launches per step: Model-C, sharded contexts) gives its workers hardware queues of
-        // their own: the HIP runtime keeps one pool of hardware queues per stream priority, four equal-priority streams share two queues
-        // (profiles/archive/r04_C4096_chain_trace_bf16.txt), and there a small launch of one worker waits behind the other's FC1.  The workers
-        // alternate between the HIGHEST and the LOWEST priority, never the default one: those two pools are this library's alone, so the
-        // first four workers get four consecutively created queues = one per compute pipe of the command processor (queue id mod 4;
-        // two workers whose queues share a pipe run 10 % behind the others: profiles/archive/r04_stream_queues_after_other_contexts.txt -- with
-        // the default priority in the rotation, a context served earlier in the process had that effect).  Model-C 4096, four workers:
-        // bf16 41.9 -> 43.1 M inf/s, fp8 65.5 -> 68.9 M = what GPU_MAX_HW_QUEUES=8 buys (profiles/archive/r04_stream_priorities_ab.txt).
-        // Fused-kernel models (one launch per group) gain nothing from it and keep the default streams.
-        // (a model no fused kernel of any precision serves -- the decision must not depend on the precision the context happens to have now)
-        const bool any_fused = frk_fused_ok(m.fc[0], m.fc[1], m.fc[2], m.fc[3]) || frk_fused_h_ok(m.fc[0], m.fc[1], m.fc[2], m.fc[3]) ||
-                               frk_fused_f8_ok(m.fc[0], m.fc[1], m.fc[2], m.fc[3]) || ctx->hk_ok == 1;
-        const bool chain = !(ctx->n_shards == 1 && m.layout == FR_LAYOUT_SEMANTIC && any_fused);
-        const int spread = FR_KNOB_ONCE("STREAM_PRIO", -1);   // experiment knob: 0 = never, 1 = always, 2 = rotate over every level (default included)
-        int lo = 0, hi = 0;   // numerically lower = higher priority
-        if (spread < 0 ? chain : spread != 0) W_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        // k = how many workers the context has EVER created (one fetch_add: two threads creating workers at once cannot draw the same k, and a
-        // destroy + create keeps alternating -- ADVICE r04: the live count did neither)
-        const int k = ctx->worker_seq.fetch_add(1, std::memory_order_relaxed);
-        // (Round 6 tried to CHECK and REPAIR the outcome, and kept none of it -- profiles/r06_experiments.md section 4: after some stream churn in the
-        // process one pair of a context's four workers takes turns (four Model-C chains 48 -> 37-45 M inf/s).  Handshake kernels on the two streams
-        // see each other resident; a BURST of part-chip spin launches on both does expose the pair (0.8-1.2 kernels resident of 2 against 1.95-2.0)
-        // -- but a stream that probes clean at creation pairs up again when the next queue is created, a pool of streams pairs up all the same,
-        // and replacing streams after all workers exist does not converge.  What the library controls is what it does here.)
-        if (lo > hi) W_HIP(hipStreamCreateWithPriority(&w->stream, hipStreamNonBlocking, spread == 2 ? hi + k % (lo - hi + 1) : (k % 2 ? lo : hi)));
-        else W_HIP(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    }
-    W_HIP(hipHostMalloc((void **)&w->h_idx, B * (size_t)w->idx_cap * sizeof(int32_t), hipHostMallocDefault));
-    if (w->pool_w_cap) W_HIP(hipHostMalloc((void **)&w->h_pool_w, B * (size_t)w->pool_w_cap * sizeof(float), hipHostMallocDefault));   // read in place by the gather, like h_idx
-    if (w->pool_w_cap) W_HIP(hipHostMalloc((void **)&w->h_pool_off, (B * idx_cols(ctx) + 1) * sizeof(int32_t), hipHostMallocDefault));   // bag offsets of the offsets-form host call
-    if (m.dense_len) W_HIP(hipHostMalloc((void **)&w->h_dense, B * m.dense_len * sizeof(float), hipHostMallocDefault));
-    W_HIP(hipHostMalloc((void **)&w->h_score, B * sizeof(float), hipHostMallocDefault));
-    // index-range flag: pinned, device-visible host word.  Kernels touch it only on the error path
-    // (system-scope atomicOr), so fr_worker_sync() needs no D2H copy -- it just reads the word after the stream drained.
-    W_HIP(hipHostMalloc((void **)&w->h_err, sizeof(int), hipHostMallocMapped));
-    *w->h_err = 0;
-    W_HIP(hipHostGetDevicePointer((void **)&w->d_err, w->h_err, 0));
-    W_HIP(hipMalloc((void **)&w->d_idx, B * (size_t)w->idx_cap * sizeof(int32_t)));
-    if (m.dense_len) W_HIP(hipMalloc((void **)&w->d_dense, B * m.dense_len * sizeof(float)));
-    W_HIP(hipMalloc((void **)&w->d_records, B * (size_t)ctx->slice_padded * sizeof(float) * (ctx->n_shards > 1 ? 1 : 1)));
-    if (ctx->n_shards == 1 && ctx->slice_padded != m.record_len) {
+    const int rc = worker_build(w);
+    if (rc) {
         fr_worker_destroy(w);
-        FR_FAIL(FR_ERR_STATE, "internal: unsharded ctx with a partial slice");
+        return rc;
     }
-    w->ld_max = round_up(max_batch, 64);
-    for (int p = 0; p < 2; p++)
-        W_HIP(hipMalloc((void **)&w->d_act[p], (size_t)w->ld_max * ((size_t)m.fc[0] + 2 * ((size_t)m.fc[1] + m.fc[2] + m.fc[3])) * sizeof(float)));
-    W_HIP(hipMalloc((void **)&w->d_score, B * sizeof(float)));
-    if (!ctx->req_shared.empty()) {   // request-form host call: the request side's pinned buffers (read in place by the expansion) and the expanded weights
-        request_caps(ctx, w);
-        W_HIP(hipHostMalloc((void **)&w->h_req_idx, B * (size_t)w->req_idx_cap * sizeof(int32_t), hipHostMallocDefault));
-        if (w->req_w_cap) W_HIP(hipHostMalloc((void **)&w->h_req_w, B * (size_t)w->req_w_cap * sizeof(float), hipHostMallocDefault));
-        if (ctx->req_dense_shared) W_HIP(hipHostMalloc((void **)&w->h_req_dense, B * m.dense_len * sizeof(float), hipHostMallocDefault));
-        W_HIP(hipHostMalloc((void **)&w->h_req_off, (B + 1) * sizeof(int32_t), hipHostMallocDefault));
-        if (w->pool_w_cap) W_HIP(hipMalloc((void **)&w->d_pool_w, B * (size_t)w->pool_w_cap * sizeof(float)));
-    }
-    W_HIP(hipEventCreate(&w->ev_start));
-    W_HIP(hipEventCreate(&w->ev_stop));
-    W_HIP(hipEventCreateWithFlags(&w->ev_update, hipEventDisableTiming));
     w->counted = true;
     fr_ctx_ref(ctx);
     ctx_enlist(ctx, w);
@@ -990,17 +927,17 @@ extern "C" int fr_worker_create(fr_ctx *ctx, int max_batch, fr_worker **out) {
     return FR_OK;
 }
 
-extern "C" int32_t *fr_worker_idx_ptr(fr_worker *w) { return w ? w->h_idx : nullptr; }
-extern "C" float *fr_worker_pool_weights_ptr(fr_worker *w) { return w ? w->h_pool_w : nullptr; }
-extern "C" int32_t *fr_worker_request_idx_ptr(fr_worker *w) { return w ? w->h_req_idx : nullptr; }
-extern "C" float *fr_worker_request_weights_ptr(fr_worker *w) { return w ? w->h_req_w : nullptr; }
-extern "C" float *fr_worker_request_dense_ptr(fr_worker *w) { return w ? w->h_req_dense : nullptr; }
-extern "C" int32_t *fr_worker_request_offsets_ptr(fr_worker *w) { return w ? w->h_req_off : nullptr; }
-extern "C" int32_t *fr_worker_pool_offsets_ptr(fr_worker *w) { return w ? w->h_pool_off : nullptr; }
-extern "C" float *fr_worker_dense_ptr(fr_worker *w) { return w ? w->h_dense : nullptr; }
-extern "C" float *fr_worker_score_ptr(fr_worker *w) { return w ? w->h_score : nullptr; }
+extern "C" int32_t *fr_worker_idx_ptr(fr_worker *w) { return w ? w->h_idx.p : nullptr; }
+extern "C" float *fr_worker_pool_weights_ptr(fr_worker *w) { return w ? w->h_pool_w.p : nullptr; }
+extern "C" int32_t *fr_worker_request_idx_ptr(fr_worker *w) { return w ? w->h_req_idx.p : nullptr; }
+extern "C" float *fr_worker_request_weights_ptr(fr_worker *w) { return w ? w->h_req_w.p : nullptr; }
+extern "C" float *fr_worker_request_dense_ptr(fr_worker *w) { return w ? w->h_req_dense.p : nullptr; }
+extern "C" int32_t *fr_worker_request_offsets_ptr(fr_worker *w) { return w ? w->h_req_off.p : nullptr; }
+extern "C" int32_t *fr_worker_pool_offsets_ptr(fr_worker *w) { return w ? w->h_pool_off.p : nullptr; }
+extern "C" float *fr_worker_dense_ptr(fr_worker *w) { return w ? w->h_dense.p : nullptr; }
+extern "C" float *fr_worker_score_ptr(fr_worker *w) { return w ? w->h_score.p : nullptr; }
 extern "C" void *fr_worker_stream(fr_worker *w) { return w ? (void *)w->stream : nullptr; }
-extern "C" float *fr_worker_records_dptr(fr_worker *w) { return w ? w->d_records : nullptr; }
+extern "C" float *fr_worker_records_dptr(fr_worker *w) { return w ? w->d_records.p : nullptr; }
 extern "C" float *fr_worker_features_dptr(fr_worker *w, int *ld_max) {
     if (!w) return nullptr;
     if (ld_max) *ld_max = w->ld_max;
@@ -1047,7 +984,7 @@ static int launch_gather(fr_worker *w, int batch, const int32_t *d_idx, const fl
     const bool one_chunk = variant == FR_GATHER_WORD_MAJOR_ONE_CHUNK;
     if (variant != FR_GATHER_WORD_MAJOR && !one_chunk && transport == FR_FC_FP32 && c->n_chunks > 0)
         return frk_gather_tile(c->d_passes, c->d_chunks, c->n_chunks, d_idx, (int)idx_cols(c), d_dense, d_records, c->slice_padded / 4, batch, w->d_err,
-                               variant != FR_GATHER_ITEM_TILE, variant == FR_GATHER_ITEM_TILE_DEDUP_COUNT ? c->d_merged : nullptr, w->stream);
+                               variant != FR_GATHER_ITEM_TILE, variant == FR_GATHER_ITEM_TILE_DEDUP_COUNT ? c->d_merged.p : nullptr, w->stream);
     return frk_gather(c->d_words, c->n_words, c->gather_groups, d_idx, (int)idx_cols(c), d_dense, d_records, batch, w->d_err, transport, c->f8_e_act[0], w->stream,
                       c->slice_padded / 4, one_chunk);  // words per item of the destination: the record (any layout) or the shard's padded slice
 }
@@ -1201,7 +1138,7 @@ extern "C" int fr_ctx_set_lp_bank_image(fr_ctx *ctx, int on) {
     ctx->lp_image_on.store(on ? 1 : 0, std::memory_order_relaxed);
     return FR_OK;
 }
-extern "C" size_t fr_ctx_lp_bank_image_bytes(const fr_ctx *ctx) { return (ctx && ctx->lp_prec) ? ctx->lp_arena_bytes : 0; }
+extern "C" size_t fr_ctx_lp_bank_image_bytes(const fr_ctx *ctx) { return (ctx && ctx->lp_prec) ? ctx->lp_arena.count() : 0; }
 extern "C" long long fr_ctx_lp_bank_image_builds(const fr_ctx *ctx) { return ctx ? ctx->lp_builds.load(std::memory_order_relaxed) : 0; }
 
 // Make the image current for (prec, X exponent, table contents).  Called by the launch path right before a gather that reads it; the
@@ -1255,16 +1192,9 @@ static int lp_ensure_image(fr_ctx *c, int prec) {
         for (fr_worker *w : c->workers)
             if (w->update_recorded) FR_HIP(hipStreamWaitEvent(c->setup_stream, w->ev_update, 0));
     }
-    if (off != c->lp_arena_bytes) {
-        if (c->lp_arena) (void)hipFree(c->lp_arena);
-        c->lp_arena = nullptr;
-        c->lp_arena_bytes = 0;
+    if (off != c->lp_arena.count()) {
         c->lp_prec = 0;
-        if (hipMalloc((void **)&c->lp_arena, off) != hipSuccess) {
-            (void)hipGetLastError();
-            FR_FAIL(FR_ERR_OOM, "operand-type bank image: hipMalloc(%zu bytes) failed", off);
-        }
-        c->lp_arena_bytes = off;
+        FR_TRY(c->lp_arena.alloc(FrMem::DEVICE, off, "operand-type bank image"));
     }
     std::vector<size_t> lp_base(m.n_tables, 0);   // offset of (row 0, column 0) of every resident table inside lp_arena
     c->lp_tables.assign(m.n_tables, fr_ctx::LpTable{});
@@ -1290,7 +1220,7 @@ static int lp_ensure_image(fr_ctx *c, int prec) {
         lw[i].src = (uint64_t)(uintptr_t)(c->lp_arena + lp_base[t]) + (uint64_t)c->h_word_col[i] * esz;
         lw[i].stride = (uint32_t)banks[group_of[t]].lp_stride;
     }
-    if (!c->d_words_lp) FR_HIP(hipMalloc((void **)&c->d_words_lp, sizeof(FrWordDesc) * c->n_words));
+    FR_TRY(c->d_words_lp.grow(FrMem::DEVICE, (size_t)c->n_words, "word descriptors of the bank image"));
     FR_HIP(hipMemcpyAsync(c->d_words_lp, lw.data(), sizeof(FrWordDesc) * c->n_words, hipMemcpyHostToDevice, c->setup_stream));
     FR_HIP(hipStreamSynchronize(c->setup_stream));
     c->lp_prec = prec;
@@ -1332,8 +1262,8 @@ static int pipeline_step(fr_worker *w) {
                   ns3 = one ? 1 : pick_nsplit(fc[2], fc[3], ldm);
         const float *wl[4];
         for (int l = 0; l < 4; l++) {
-            if (bf16) wl[l] = reinterpret_cast<const float *>(c->d_w_bf16[l]);
-            else if (fp8 && l < 3) wl[l] = reinterpret_cast<const float *>(c->d_w_fp8[l]);
+            if (bf16) wl[l] = reinterpret_cast<const float *>(c->d_w_bf16[l].p);
+            else if (fp8 && l < 3) wl[l] = reinterpret_cast<const float *>(c->d_w_fp8[l].p);
             else wl[l] = (l < 3 && !fp8) ? c->d_wq[l] : c->d_w[3];
         }
         if (fp8) {  // power-of-two quantisation exponents of this stage's operands / result
@@ -1535,21 +1465,21 @@ static int fused_flush(fr_worker *w) {
     a.idx_stride = (int)idx_cols(c);
     a.err_flag = w->d_err;
     if (fp8) {  // e4m3 q16 copies of FC1..FC3, fp32 output weights, the quantisation exponents
-        a.w1q = reinterpret_cast<const float4 *>(c->d_w_fp8[0]);
-        a.w2q = reinterpret_cast<const float4 *>(c->d_w_fp8[1]);
-        a.w3q = reinterpret_cast<const float4 *>(c->d_w_fp8[2]);
+        a.w1q = reinterpret_cast<const float4 *>(c->d_w_fp8[0].p);
+        a.w2q = reinterpret_cast<const float4 *>(c->d_w_fp8[1].p);
+        a.w3q = reinterpret_cast<const float4 *>(c->d_w_fp8[2].p);
         a.wout = c->d_w[3];
         for (int l = 0; l < 3; l++) a.e_w[l] = c->f8_e_w[l];
         for (int l = 0; l < 4; l++) a.e_act[l] = c->f8_e_act[l];
     } else if (bf16) {  // the bf16 kernels read the q8-packed bf16 copies through the same argument slots
-        a.w1q = reinterpret_cast<const float4 *>(c->d_w_bf16[0]);
-        a.w2q = reinterpret_cast<const float4 *>(c->d_w_bf16[1]);
-        a.w3q = reinterpret_cast<const float4 *>(c->d_w_bf16[2]);
-        a.wout = reinterpret_cast<const float *>(c->d_w_bf16[3]);
+        a.w1q = reinterpret_cast<const float4 *>(c->d_w_bf16[0].p);
+        a.w2q = reinterpret_cast<const float4 *>(c->d_w_bf16[1].p);
+        a.w3q = reinterpret_cast<const float4 *>(c->d_w_bf16[2].p);
+        a.wout = reinterpret_cast<const float *>(c->d_w_bf16[3].p);
     } else {
-        a.w1q = reinterpret_cast<const float4 *>(c->d_wq[0]);
-        a.w2q = reinterpret_cast<const float4 *>(c->d_wq[1]);
-        a.w3q = reinterpret_cast<const float4 *>(c->d_wq[2]);
+        a.w1q = reinterpret_cast<const float4 *>(c->d_wq[0].p);
+        a.w2q = reinterpret_cast<const float4 *>(c->d_wq[1].p);
+        a.w3q = reinterpret_cast<const float4 *>(c->d_wq[2].p);
         a.wout = c->d_w[3];
     }
     a.K = c->model.fc[0];
@@ -1584,10 +1514,10 @@ static int fused_flush(fr_worker *w) {
         const int hs_from = a.K <= 352 ? c->n_cu : c->n_cu + c->n_cu / 4;
         const bool only_hs = bf16 && !frk_fused_h_ok(a.K, a.H1, a.H2, a.H3);   // a record the chunked kernel has no instantiation for
         if (c->hk_ok == 1 && (only_hs || (hk != 0 && (hk == 1 || tiles >= hs_from)))) {
-            if (!w->h_blist) {
-                FR_HIP(hipHostMalloc((void **)&w->h_blist, sizeof(FrFusedBatch) * FR_FUSED_MAX_QUEUE * FR_BLIST_RING, hipHostMallocDefault));
-                FR_HIP(hipMalloc((void **)&w->d_blist, sizeof(FrFusedBatch) * FR_FUSED_MAX_QUEUE * FR_BLIST_RING));
-                for (int k = 0; k < FR_BLIST_RING; k++) FR_HIP(hipEventCreateWithFlags(&w->ev_blist[k], hipEventDisableTiming));
+            if (!w->ev_blist[FR_BLIST_RING - 1]) {   // first use (a partial failure is made up for: grow and create keep what is there)
+                FR_TRY(w->h_blist.grow(FrMem::PINNED, (size_t)FR_FUSED_MAX_QUEUE * FR_BLIST_RING, "batch lists"));
+                FR_TRY(w->d_blist.grow(FrMem::DEVICE, (size_t)FR_FUSED_MAX_QUEUE * FR_BLIST_RING, "batch lists (device)"));
+                for (FrEvent &e : w->ev_blist) FR_HIP(e.create(hipEventDisableTiming));
             }
             const int k = w->blist_cur;
             w->blist_cur = (k + 1) % FR_BLIST_RING;
@@ -1608,9 +1538,9 @@ static int fused_flush(fr_worker *w) {
             }
             if (bf16 && FR_KNOB_ONCE("FUSED_HS_ABLATE", 0)) a.e_act[3] = -776 - FR_KNOB_ONCE("FUSED_HS_ABLATE", 0);   // experiments build: the kernel's timing ablations (1: no row loads, 2: every row load reads row 0)
             if (fp8) {  // the "q16h" copies of the weights (the non-scaled fp8 MFMA's operand layout)
-                a.w1q = reinterpret_cast<const float4 *>(c->d_w_fp8h[0]);
-                a.w2q = reinterpret_cast<const float4 *>(c->d_w_fp8h[1]);
-                a.w3q = reinterpret_cast<const float4 *>(c->d_w_fp8h[2]);
+                a.w1q = reinterpret_cast<const float4 *>(c->d_w_fp8h[0].p);
+                a.w2q = reinterpret_cast<const float4 *>(c->d_w_fp8h[1].p);
+                a.w3q = reinterpret_cast<const float4 *>(c->d_w_fp8h[2].p);
             }
             return frk_fused_hk_launch(a, c->n_cu, c->fc_precision, w->stream);
         }
@@ -1635,7 +1565,8 @@ static int launch_fc(fr_worker *w, int batch, const float *d_records, float *d_s
     fr_ctx *c = w->ctx;
     if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fc on a sharded ctx needs the all-gathered records (use the sharded driver: fr_worker_submit_sharded, fr_worker_submit_sharded_pooled)");
     if (c->cpu) {
-        frc_fc_chain(c->model.fc, c->d_w, d_records, batch, w->c_scratch, d_scores);
+        const float *const wl[4] = {c->d_w[0], c->d_w[1], c->d_w[2], c->d_w[3]};
+        frc_fc_chain(c->model.fc, wl, d_records, batch, w->c_scratch, d_scores);
         return FR_OK;
     }
     if (w->n_active) FR_FAIL(FR_ERR_STATE, "pipeline busy: call fr_worker_sync first");
@@ -1665,7 +1596,8 @@ static int fc_from_slices_impl(fr_worker *w, int batch_total, int item0, int n_i
     if (c->cpu) {
         if (c->n_shards < 2) FR_FAIL(FR_ERR_STATE, "fc_from_slices needs a sharded context");
         frc_slices_to_records(d_gathered, c->n_shards, batch_total, c->slice_padded, c->shard_offset.data(), c->shard_len.data(), item0, n_items, w->c_x, c->model.fc[0]);
-        frc_fc_chain(c->model.fc, c->d_w, w->c_x, n_items, w->c_scratch, d_scores);
+        const float *const wl[4] = {c->d_w[0], c->d_w[1], c->d_w[2], c->d_w[3]};
+        frc_fc_chain(c->model.fc, wl, w->c_x, n_items, w->c_scratch, d_scores);
         return FR_OK;
     }
     FR_SET_DEVICE(c);
@@ -1747,12 +1679,11 @@ static int pooling_busy(fr_ctx *ctx, const char *who) {
 // uploaded beside the ones in use -- before any pooling state changes, and committed together with it (a commit cannot fail).
 struct RequestTables {
     fr_ctx::ReqForm f[3];
-    int32_t *d = nullptr;   // the new device allocation (GPU contexts with a split)
+    FrBuf<int32_t> d;       // the new device allocation (GPU contexts with a split): the context's own once committed, released with this otherwise
     bool made = false;      // false: the context has no split, nothing to commit
 };
 static int request_prepare(fr_ctx *ctx, const std::vector<int32_t> &shared, bool dense_shared, const int32_t *hots, RequestTables &t);   // hots NULL: no pooling
 static void request_commit(fr_ctx *ctx, RequestTables &t);
-static void request_discard(RequestTables &t);
 
 // the descriptors of hots[] x modes[] (modes == NULL: every column SUM), uploaded; the context's copies are replaced only when all of it worked
 static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *modes) {
@@ -1778,23 +1709,14 @@ static int pooling_install(fr_ctx *ctx, const int32_t *hots, const int32_t *mode
         csr[i] = (col & FR_DESC_DENSE) ? FrPoolDesc{0u, 1u} : FrPoolDesc{col, pool[i].hots};
     }
     if (!ctx->cpu) {
-        FrPoolDesc *d = nullptr;
+        FrBuf<FrPoolDesc> d;   // (released on every way out; the context's own after the swap)
         const size_t n = pool.size();
-        hipError_t e = hipMalloc((void **)&d, sizeof(FrPoolDesc) * (n ? 2 * n : 1));
-        if (e != hipSuccess) {
-            request_discard(rt);
-            FR_FAIL(e == hipErrorOutOfMemory ? FR_ERR_OOM : FR_ERR_HIP, "hipMalloc(pooled descriptors) failed: %s", hipGetErrorString(e));
-        }
-        e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
+        FR_TRY(d.alloc(FrMem::DEVICE, n ? 2 * n : 1, "pooled descriptors"));
+        hipError_t e = hipMemcpy(d, pool.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(d + n, csr.data(), sizeof(FrPoolDesc) * n, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d);
-            request_discard(rt);
-            FR_FAIL(FR_ERR_HIP, "hipMemcpy(pooled descriptors) failed: %s", hipGetErrorString(e));
-        }
-        if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-        ctx->d_pool = d;
-        ctx->d_pool_csr = d + n;
+        if (e != hipSuccess) FR_FAIL(FR_ERR_HIP, "hipMemcpy(pooled descriptors) failed: %s", hipGetErrorString(e));
+        ctx->d_pool.swap(d);
+        ctx->d_pool_csr = ctx->d_pool + n;
     }
     std::vector<int32_t> h(hots, hots + cols), md(cols, FR_POOL_SUM);   // (hots may be ctx->pool_hots itself: copied before it is replaced)
     if (modes) md.assign(modes, modes + cols);
@@ -1860,8 +1782,8 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
         RequestTables rt;   // (a request split keeps its one-hot and dense forms)
         const int rrc = request_prepare(ctx, ctx->req_shared, ctx->req_dense_shared, nullptr, rt);
         if (rrc) return rrc;
-        if (ctx->d_pool) (void)hipFree(ctx->d_pool);
-        ctx->d_pool = ctx->d_pool_csr = nullptr;
+        ctx->d_pool.reset();
+        ctx->d_pool_csr = nullptr;
         ctx->h_pool.clear();
         ctx->h_pool_csr.clear();
         ctx->pool_hots.clear();
@@ -2048,7 +1970,7 @@ static int submit_pooled_host_impl(fr_worker *w, int batch, bool weighted, const
     int rc = pooled_host_ready(w, batch, weighted);
     if (rc) return rc;
     fr_ctx *c = w->ctx;
-    FrPooledBatch b{batch, w->h_idx, weighted ? w->h_pool_w : nullptr, c->model.dense_len ? w->h_dense : nullptr};
+    FrPooledBatch b{batch, w->h_idx, weighted ? w->h_pool_w.p : nullptr, c->model.dense_len ? w->h_dense.p : nullptr};
     b.need_weights = weighted;
     if (csr_who) {
         if (!w->h_pool_off) FR_FAIL(FR_ERR_STATE, "the worker has no offsets buffer: create the worker after fr_ctx_set_pooling");
@@ -2362,7 +2284,7 @@ extern "C" int fr_worker_submit(fr_worker *w, int batch) {
     if (w->in_flight) FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
     fr_ctx *c = w->ctx;
     if (c->cpu) {
-        rc = launch_pipeline(w, batch, w->h_idx, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
+        rc = launch_pipeline(w, batch, w->h_idx, c->model.dense_len ? w->h_dense.p : nullptr, w->h_score);
         if (rc) return rc;
         w->in_flight = true, w->host_batch = batch;
         return FR_OK;
@@ -2375,7 +2297,7 @@ extern "C" int fr_worker_submit(fr_worker *w, int batch) {
     // (profiles/archive/r02_submit_latency.txt): this entry point is the latency path, the streaming entry points are the throughput path.
     const int zero_copy = FR_KNOB_ONCE("SUBMIT_ZEROCOPY", 1);
     if (zero_copy) {
-        rc = launch_pipeline(w, batch, w->h_idx, c->model.dense_len ? w->h_dense : nullptr, w->h_score);
+        rc = launch_pipeline(w, batch, w->h_idx, c->model.dense_len ? w->h_dense.p : nullptr, w->h_score);
         if (rc) return rc;
         w->in_flight = true, w->host_batch = batch;
         return FR_OK;
@@ -2409,16 +2331,17 @@ static int host_ring_init(fr_worker *w) {
     r.dense_slot = (size_t)w->max_batch * c->model.dense_len;
     r.score_slot = (size_t)w->max_batch;
     const size_t slots = (size_t)g * FR_HOST_BLOCKS;
-    FR_HIP(hipHostMalloc((void **)&r.h_idx, slots * r.idx_slot * sizeof(int32_t), hipHostMallocDefault));
-    FR_HIP(hipMalloc((void **)&r.d_idx, slots * r.idx_slot * sizeof(int32_t)));
+    // (r.g is set last: a call that failed half-way is run again, and keeps what the first one made -- alloc releases, create and the stream skip)
+    FR_TRY(r.h_idx.alloc(FrMem::PINNED, slots * r.idx_slot, "host ring index rows"));
+    FR_TRY(r.d_idx.alloc(FrMem::DEVICE, slots * r.idx_slot, "host ring index rows (device)"));
     if (r.dense_slot) {
-        FR_HIP(hipHostMalloc((void **)&r.h_dense, slots * r.dense_slot * sizeof(float), hipHostMallocDefault));
-        FR_HIP(hipMalloc((void **)&r.d_dense, slots * r.dense_slot * sizeof(float)));
+        FR_TRY(r.h_dense.alloc(FrMem::PINNED, slots * r.dense_slot, "host ring dense rows"));
+        FR_TRY(r.d_dense.alloc(FrMem::DEVICE, slots * r.dense_slot, "host ring dense rows (device)"));
     }
-    FR_HIP(hipHostMalloc((void **)&r.h_sc, slots * r.score_slot * sizeof(float), hipHostMallocDefault));
-    FR_HIP(hipMalloc((void **)&r.d_sc, slots * r.score_slot * sizeof(float)));
-    for (int b = 0; b < FR_HOST_BLOCKS; b++) FR_HIP(hipEventCreateWithFlags(&r.ev[b], hipEventDisableTiming));
-    {   // The copy stream lives in the LOWEST stream priority's pool of hardware queues: the HIP runtime pools queues per priority, and in the
+    FR_TRY(r.h_sc.alloc(FrMem::PINNED, slots * r.score_slot, "host ring scores"));
+    FR_TRY(r.d_sc.alloc(FrMem::DEVICE, slots * r.score_slot, "host ring scores (device)"));
+    for (FrEvent &e : r.ev) FR_HIP(e.create(hipEventDisableTiming));
+    if (!r.copy) {   // The copy stream lives in the LOWEST stream priority's pool of hardware queues: the HIP runtime pools queues per priority, and in the
         // default pool the marker packet behind a block's copy (its event) would sit in a hardware queue that some worker's launches share --
         // that worker's next launch then waits out another worker's 65 us copy (seen as a bimodal 97 % / 99 % of the HBM-resident rate,
         // by which queue the runtime happened to hand out: profiles/r05_experiments.md section 1).  Fused-kernel models keep their worker
@@ -2428,7 +2351,7 @@ static int host_ring_init(fr_worker *w) {
         if (lo > hi) FR_HIP(hipStreamCreateWithPriority(&r.copy, hipStreamNonBlocking, lo));
         else FR_HIP(hipStreamCreateWithFlags(&r.copy, hipStreamNonBlocking));
     }
-    for (int b = 0; b < FR_HOST_BLOCKS; b++) FR_HIP(hipEventCreateWithFlags(&r.ev_in[b], hipEventDisableTiming));
+    for (FrEvent &e : r.ev_in) FR_HIP(e.create(hipEventDisableTiming));
     r.g = g;
     return FR_OK;
 }
@@ -2659,7 +2582,7 @@ extern "C" int fr_worker_calibrate_fp8(fr_worker *w, int batch) {
     if (c->n_shards > 1 || c->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "fp8 calibration from index rows: unsharded SEMANTIC contexts only (sharded: fr_worker_calibrate_fp8_slices)");
     if (w->in_flight || w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "worker busy: call fr_worker_sync first");
     FR_SET_DEVICE(c);
-    if (!c->d_stats) FR_HIP(hipMalloc((void **)&c->d_stats, 64));
+    FR_TRY(c->d_stats.grow(FrMem::DEVICE, 16, "reduction scratch"));
     FR_HIP(hipMemcpyAsync(w->d_idx, w->h_idx, (size_t)batch * idx_cols(c) * sizeof(int32_t), hipMemcpyHostToDevice, w->stream));
     if (c->model.dense_len)
         FR_HIP(hipMemcpyAsync(w->d_dense, w->h_dense, (size_t)batch * c->model.dense_len * sizeof(float), hipMemcpyHostToDevice, w->stream));
@@ -2681,7 +2604,7 @@ extern "C" int fr_worker_calibrate_fp8_slices(fr_worker *w, int batch_total, int
     FR_NOT_ON_CPU(c, "fr_worker_calibrate_fp8_slices");
     if (w->in_flight) FR_FAIL(FR_ERR_STATE, "worker busy: call fr_worker_sync first");
     FR_SET_DEVICE(c);
-    if (!c->d_stats) FR_HIP(hipMalloc((void **)&c->d_stats, 64));
+    FR_TRY(c->d_stats.grow(FrMem::DEVICE, 16, "reduction scratch"));
     uint64_t L1 = 0;
     w->calibrating = true;
     int rc = fc_from_slices_impl(w, batch_total, item0, n_items, d_gathered, w->d_score, &L1);
@@ -2756,30 +2679,20 @@ extern "C" int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *
     FR_SET_DEVICE(ctx);
     std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // also serialises the set-up stream and the staging buffers against other updates and an image build
     if (!ctx->h_up_err) {
-        FR_HIP(hipHostMalloc((void **)&ctx->h_up_err, sizeof(int), hipHostMallocMapped));
+        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
         *ctx->h_up_err = 0;
         FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
     }
     const size_t n_floats = (size_t)n * (size_t)dim;
-    if ((size_t)n > ctx->up_ids_cap) {
-        if (ctx->d_up_ids) (void)hipFree(ctx->d_up_ids);
-        ctx->d_up_ids = nullptr, ctx->up_ids_cap = 0;
-        FR_HIP(hipMalloc((void **)&ctx->d_up_ids, (size_t)n * sizeof(int32_t)));
-        ctx->up_ids_cap = (size_t)n;
-    }
-    if (n_floats > ctx->up_rows_cap) {
-        if (ctx->d_up_rows) (void)hipFree(ctx->d_up_rows);
-        ctx->d_up_rows = nullptr, ctx->up_rows_cap = 0;
-        FR_HIP(hipMalloc((void **)&ctx->d_up_rows, n_floats * sizeof(float)));
-        ctx->up_rows_cap = n_floats;
-    }
+    FR_TRY(ctx->d_up_ids.grow(FrMem::DEVICE, (size_t)n, "row-update ids"));
+    FR_TRY(ctx->d_up_rows.grow(FrMem::DEVICE, n_floats, "row-update rows"));
     FR_HIP(hipMemcpyAsync(ctx->d_up_ids, h_row_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->setup_stream));
     FR_HIP(hipMemcpyAsync(ctx->d_up_rows, h_rows, n_floats * sizeof(float), hipMemcpyHostToDevice, ctx->setup_stream));
     rc = update_enqueue(ctx, table, n, ctx->d_up_ids, ctx->d_up_rows, ctx->d_up_err, ctx->setup_stream);
     FR_HIP(hipStreamSynchronize(ctx->setup_stream));
     if (rc) return rc;
-    if (__atomic_load_n(ctx->h_up_err, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(ctx->h_up_err, 0, __ATOMIC_RELEASE);
+    if (__atomic_load_n(ctx->h_up_err.p, __ATOMIC_ACQUIRE)) {
+        __atomic_store_n(ctx->h_up_err.p, 0, __ATOMIC_RELEASE);
         FR_FAIL(FR_ERR_INDEX_RANGE, "a listed row id was outside table %d (that row was not written, the others were)", table);
     }
     return FR_OK;
@@ -2812,16 +2725,11 @@ static int topk_enqueue(fr_worker *w, int n, const float *d_scores, int n_seg, c
     if (a.u_cap) {   // a segment may be longer than one workgroup streams: unit records and candidate lists in the worker's scratch
         const size_t map_bytes = align_up((size_t)a.u_cap * sizeof(int4), 256);
         const size_t need = 256 + map_bytes + (size_t)a.u_cap * FR_TOPK_MAX_K * sizeof(unsigned long long);
-        if (need > w->rank_bytes) {
-            if (w->d_rank) {   // an earlier ranking may still read it
-                FR_HIP(hipStreamSynchronize(w->stream));
-                (void)hipFree(w->d_rank);
-                w->d_rank = nullptr, w->rank_bytes = 0;
-            }
-            FR_HIP(hipMalloc((void **)&w->d_rank, need));
-            w->rank_bytes = need;
+        if (need > w->d_rank.count()) {
+            if (w->d_rank) FR_HIP(hipStreamSynchronize(w->stream));   // an earlier ranking may still read it
+            FR_TRY(w->d_rank.grow(FrMem::DEVICE, need, "ranking scratch"));
         }
-        a.hdr = reinterpret_cast<int *>(w->d_rank);
+        a.hdr = reinterpret_cast<int *>(w->d_rank.p);
         a.unitmap = reinterpret_cast<int4 *>(w->d_rank + 256);
         a.cand = reinterpret_cast<unsigned long long *>(w->d_rank + 256 + map_bytes);
     }
@@ -2847,7 +2755,7 @@ extern "C" int fr_worker_topk_device(fr_worker *w, int n, const float *d_scores,
 }
 
 extern "C" int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t *h_seg_offsets, int k, int32_t *h_top_idx, float *h_top_scores) {
-    int rc = topk_check(w, batch, w ? w->h_score : nullptr, n_seg, k, h_top_idx);
+    int rc = topk_check(w, batch, w ? w->h_score.p : nullptr, n_seg, k, h_top_idx);
     if (rc) return rc;
     if (w->sh_comm || w->ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_worker_topk ranks a host-form batch; a table-sharded step is not one");
     if (!w->host_batch)
@@ -2860,26 +2768,15 @@ extern "C" int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t 
     if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking is already in flight on this worker: call fr_worker_sync first");
     FR_SET_DEVICE(w->ctx);
     const size_t n_off = h_seg_offsets ? (size_t)n_seg + 1 : 0, n_out = (size_t)n_seg * (size_t)k;
-    if (n_off > w->tk_off_cap || n_out > w->tk_out_cap) {   // a grow waits for the stream before pinned memory is released (the header says so)
+    if (n_off > w->h_tk_off.count() || n_out > w->h_tk_idx.count() || n_out > w->h_tk_sc.count()) {   // a grow waits for the stream before pinned memory is released (the header says so)
         FR_HIP(hipStreamSynchronize(w->stream));
-        if (n_off > w->tk_off_cap) {
-            if (w->h_tk_off) (void)hipHostFree(w->h_tk_off);
-            w->h_tk_off = nullptr, w->tk_off_cap = 0;
-            FR_HIP(hipHostMalloc((void **)&w->h_tk_off, n_off * sizeof(int32_t), hipHostMallocDefault));
-            w->tk_off_cap = n_off;
-        }
-        if (n_out > w->tk_out_cap) {
-            if (w->h_tk_idx) (void)hipHostFree(w->h_tk_idx);
-            if (w->h_tk_sc) (void)hipHostFree(w->h_tk_sc);
-            w->h_tk_idx = nullptr, w->h_tk_sc = nullptr, w->tk_out_cap = 0;
-            FR_HIP(hipHostMalloc((void **)&w->h_tk_idx, n_out * sizeof(int32_t), hipHostMallocDefault));
-            FR_HIP(hipHostMalloc((void **)&w->h_tk_sc, n_out * sizeof(float), hipHostMallocDefault));
-            w->tk_out_cap = n_out;
-        }
+        if (n_off) FR_TRY(w->h_tk_off.grow(FrMem::PINNED, n_off, "ranking offsets"));
+        FR_TRY(w->h_tk_idx.grow(FrMem::PINNED, n_out, "ranking results"));
+        FR_TRY(w->h_tk_sc.grow(FrMem::PINNED, n_out, "ranking result scores"));
     }
     if (n_off) memcpy(w->h_tk_off, h_seg_offsets, n_off * sizeof(int32_t));
     // as fr_worker_submit's scores: the kernels read the pinned scores and offsets in place and write the pinned results
-    rc = topk_enqueue(w, batch, w->h_score, n_seg, n_off ? w->h_tk_off : nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc : nullptr);
+    rc = topk_enqueue(w, batch, w->h_score, n_seg, n_off ? w->h_tk_off.p : nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr);
     if (rc) return rc;
     w->tk_dst_idx = h_top_idx, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
     return FR_OK;
@@ -2906,14 +2803,11 @@ static int request_prepare(fr_ctx *ctx, const std::vector<int32_t> &shared, bool
     size_t total = 0;
     for (int form = 0; form < 3; form++) t.f[form].d_first = total, total += t.f[form].desc.size();
     if (!ctx->cpu) {
-        FR_HIP(hipMalloc((void **)&t.d, sizeof(int32_t) * (total ? total : 1)));
+        FR_TRY(t.d.alloc(FrMem::DEVICE, total ? total : 1, "request-form descriptors"));
         for (int form = 0; form < 3; form++) {
             if (t.f[form].desc.empty()) continue;
             const hipError_t e = hipMemcpy(t.d + t.f[form].d_first, t.f[form].desc.data(), sizeof(int32_t) * t.f[form].desc.size(), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                request_discard(t);
-                FR_FAIL(FR_ERR_HIP, "hipMemcpy(request-form descriptors) failed: %s", hipGetErrorString(e));
-            }
+            if (e != hipSuccess) FR_FAIL(FR_ERR_HIP, "hipMemcpy(request-form descriptors) failed: %s", hipGetErrorString(e));
         }
     }
     t.made = true;
@@ -2922,15 +2816,8 @@ static int request_prepare(fr_ctx *ctx, const std::vector<int32_t> &shared, bool
 
 static void request_commit(fr_ctx *ctx, RequestTables &t) {
     if (!t.made) return;
-    if (ctx->d_req_desc) (void)hipFree(ctx->d_req_desc);
-    ctx->d_req_desc = t.d;
-    t.d = nullptr;
+    ctx->d_req_desc.swap(t.d);
     for (int form = 0; form < 3; form++) std::swap(ctx->req_form[form], t.f[form]);
-}
-
-static void request_discard(RequestTables &t) {
-    if (t.d) (void)hipFree(t.d);
-    t.d = nullptr;
 }
 
 extern "C" int fr_ctx_set_request_columns(fr_ctx *ctx, const int32_t *shared, int n_cols, int dense_shared) {
@@ -2954,8 +2841,7 @@ extern "C" int fr_ctx_set_request_columns(fr_ctx *ctx, const int32_t *shared, in
     if (rc) return rc;
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
     if (!shared) {
-        if (ctx->d_req_desc) FR_HIP(hipFree(ctx->d_req_desc));
-        ctx->d_req_desc = nullptr;
+        ctx->d_req_desc.reset();
         ctx->req_shared.clear();
         ctx->req_dense_shared = false;
         for (fr_ctx::ReqForm &f : ctx->req_form) f = fr_ctx::ReqForm{};
@@ -3072,7 +2958,7 @@ extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int
     if (!rc && weighted) rc = request_enqueue(w, *f, batch, n_req, w->h_req_off, w->h_req_w, w->h_pool_w, w->d_pool_w);
     if (!rc && fd) rc = request_enqueue(w, *fd, batch, n_req, w->h_req_off, w->h_req_dense, nullptr, w->d_dense);
     if (rc) return rc;
-    const float *dense = fd ? w->d_dense : (c->model.dense_len ? w->h_dense : nullptr);
+    const float *dense = fd ? w->d_dense.p : (c->model.dense_len ? w->h_dense.p : nullptr);
     if (pooled) rc = submit_pooled_impl(w, weighted ? pooled_batch_weighted(batch, w->d_idx, w->d_pool_w, dense) : FrPooledBatch{batch, w->d_idx, nullptr, dense}, w->h_score);
     else rc = launch_pipeline(w, batch, w->d_idx, dense, w->h_score);
     if (rc) return rc;
@@ -3203,25 +3089,36 @@ extern "C" int fr_worker_timer_stop_ms(fr_worker *w, float *ms) {
 }
 
 // ---- device memory helpers ------------------------------------------------------------------------------
+// fr_device_malloc hands the allocation to the caller; its size is kept for the tally until fr_device_free brings it back
+struct Handed {
+    void *p;
+    size_t bytes;
+};
+static std::mutex g_handed_mutex;
+static std::vector<Handed> g_handed;
 extern "C" int fr_device_malloc(fr_ctx *ctx, size_t bytes, void **dptr) {
     if (!ctx || !dptr) FR_FAIL(FR_ERR_INVALID, "NULL argument");
-    if (ctx->cpu) {   // "device memory" of the CPU back-end is host memory: the same calling code runs against either
-        *dptr = aligned_alloc(64, align_up(bytes ? bytes : 64, 64));
-        if (!*dptr) FR_FAIL(FR_ERR_OOM, "out of host memory (%zu bytes)", bytes);
-        return FR_OK;
-    }
-    FR_SET_DEVICE(ctx);
-    FR_HIP(hipMalloc(dptr, bytes ? bytes : 1));
+    FR_SET_DEVICE(ctx);   // ("device memory" of the CPU back-end is host memory: the same calling code runs against either)
+    FR_TRY(fr_mem_alloc(fr_mem_kind(ctx, FrMem::DEVICE), bytes ? bytes : 1, "fr_device_malloc", dptr));
+    std::lock_guard<std::mutex> g(g_handed_mutex);
+    g_handed.push_back(Handed{*dptr, bytes ? bytes : 1});
     return FR_OK;
 }
 extern "C" int fr_device_free(fr_ctx *ctx, void *dptr) {
     if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    if (ctx->cpu) {
-        free(dptr);
-        return FR_OK;
-    }
     FR_SET_DEVICE(ctx);
-    if (dptr) FR_HIP(hipFree(dptr));
+    size_t bytes = 0;
+    {
+        std::lock_guard<std::mutex> g(g_handed_mutex);
+        if (!dptr) return FR_OK;
+        size_t i = 0;
+        while (i < g_handed.size() && g_handed[i].p != dptr) i++;
+        if (i == g_handed.size()) FR_FAIL(FR_ERR_INVALID, "fr_device_free: %p was not handed out by fr_device_malloc (or was freed already)", dptr);
+        bytes = g_handed[i].bytes;
+        g_handed[i] = g_handed.back();
+        g_handed.pop_back();
+    }
+    fr_mem_release(fr_mem_kind(ctx, FrMem::DEVICE), dptr, bytes);
     return FR_OK;
 }
 extern "C" int fr_memcpy_h2d(fr_ctx *ctx, void *dptr, const void *host, size_t bytes) {

@@ -500,16 +500,6 @@ void fr_comm_worker_release(fr_worker *w) {
 
 // ---- the few device operations of a step, on either back-end: a command on the worker's HIP stream, or the same thing done at once by the
 // thread that runs the step (a CPU worker's step runs on its host stream: "enqueued" there means "done, in order") --------------------------
-static void *step_alloc(fr_worker *w, size_t bytes) {
-    void *p = nullptr;
-    if (w->ctx->cpu) return aligned_alloc(64, (bytes + 63) / 64 * 64);
-    return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
-}
-static void step_free(fr_worker *w, void *p) {
-    if (!p) return;
-    if (w->ctx->cpu) free(p);
-    else (void)hipFree(p);
-}
 static int step_copy(fr_worker *w, void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
     if (w->ctx->cpu) {
         memcpy(dst, src, bytes);
@@ -624,28 +614,17 @@ static int shard_buffers(fr_worker *w, int G, bool staged) {
     const size_t slice = (size_t)w->max_batch * (size_t)c->slice_padded * sizeof(float);
     const size_t chunk = ((size_t)w->max_batch + G - 1) / G + 1;  // + the rank's status word (failure protocol, kind (2))
     if (G > FR_COMM_MAX_RANKS) FR_FAIL(FR_ERR_INVALID, "%d ranks: the status words of a sharded step hold %d", G, FR_COMM_MAX_RANKS);
-    if (!w->h_sh_status) {   // [0] sent, [1 .. G] received
-        if (c->cpu) w->h_sh_status = static_cast<float *>(aligned_alloc(64, (sizeof(float) * (1 + FR_COMM_MAX_RANKS) + 63) / 64 * 64));
-        else FR_HIP(hipHostMalloc((void **)&w->h_sh_status, sizeof(float) * (1 + FR_COMM_MAX_RANKS), hipHostMallocDefault));
-        if (!w->h_sh_status) FR_FAIL(FR_ERR_OOM, "out of host memory (status words)");
-    }
-    void **bufs[] = {&w->d_slice, &w->d_gathered, (void **)&w->d_score_part, (void **)&w->d_score_all};
-    for (void **b : bufs) {
-        step_free(w, *b);
-        *b = nullptr;
-    }
-    w->d_slice = step_alloc(w, slice);
-    w->d_gathered = step_alloc(w, slice * G);
-    w->d_score_part = static_cast<float *>(step_alloc(w, chunk * sizeof(float)));
-    w->d_score_all = static_cast<float *>(step_alloc(w, chunk * G * sizeof(float)));
-    if (!w->d_slice || !w->d_gathered || !w->d_score_part || !w->d_score_all) FR_FAIL(FR_ERR_OOM, "exchange buffers for %d ranks x batch %d: out of memory", G, w->max_batch);
+    // (sh_ranks is set last: a call that failed half-way is run again, and every alloc releases what the first one made)
+    const FrMem pinned = fr_mem_kind(c, FrMem::PINNED), device = fr_mem_kind(c, FrMem::DEVICE);
+    FR_TRY(w->h_sh_status.grow(pinned, 1 + FR_COMM_MAX_RANKS, "status words"));   // [0] sent, [1 .. G] received
+    FR_TRY(w->d_slice.alloc(device, slice, "exchange slice"));
+    FR_TRY(w->d_gathered.alloc(device, slice * G, "exchange slices of all ranks"));
+    FR_TRY(w->d_score_part.alloc(device, chunk, "exchange score chunk"));
+    FR_TRY(w->d_score_all.alloc(device, chunk * G, "exchange score chunks of all ranks"));
     if (staged && !c->cpu) {   // the staged exchange of GPU contexts that share a device: one part out, G parts in, through pinned host memory
-        if (w->h_stage_send) (void)hipHostFree(w->h_stage_send);
-        if (w->h_stage_recv) (void)hipHostFree(w->h_stage_recv);
-        w->h_stage_send = w->h_stage_recv = nullptr;
         const size_t part = slice > chunk * sizeof(float) ? slice : chunk * sizeof(float);
-        FR_HIP(hipHostMalloc(&w->h_stage_send, part, hipHostMallocDefault));
-        FR_HIP(hipHostMalloc(&w->h_stage_recv, part * G, hipHostMallocDefault));
+        FR_TRY(w->h_stage_send.alloc(FrMem::PINNED, part, "exchange staging (send)"));
+        FR_TRY(w->h_stage_recv.alloc(FrMem::PINNED, part * G, "exchange staging (receive)"));
     }
     w->sh_ranks = G;
     return FR_OK;
@@ -680,7 +659,7 @@ static int sharded_prologue(fr_worker *w, fr_comm *comm, ShBatch *what) {
     if (!c->cpu) FR_HIP(hipSetDevice(c->device));
     int rc = shard_buffers(w, comm->n_ranks, comm->grp != nullptr);
     if (rc) return rc;
-    b.weights = b.need_weights ? w->h_pool_w : nullptr;
+    b.weights = b.need_weights ? w->h_pool_w.p : nullptr;
     b.idx = c->cpu ? w->h_idx : w->d_idx;
     b.dense = c->cpu ? w->h_dense : w->d_dense;
     if (c->cpu) return FR_OK;
@@ -914,7 +893,7 @@ static int sharded_calibrate(fr_worker *w, fr_comm *comm, ShBatch what) {
     rc = step_all_gather(w, comm, w->d_slice, w->d_gathered, (size_t)batch * c->slice_padded * sizeof(float));
     if (rc) return comm_fail(comm, rc);
     w->in_flight = false;
-    return fr_worker_calibrate_fp8_slices(w, batch, 0, batch, reinterpret_cast<const float *>(w->d_gathered));
+    return fr_worker_calibrate_fp8_slices(w, batch, 0, batch, reinterpret_cast<const float *>(w->d_gathered.p));
 }
 
 extern "C" int fr_worker_calibrate_fp8_sharded(fr_worker *w, fr_comm *comm, int batch) {

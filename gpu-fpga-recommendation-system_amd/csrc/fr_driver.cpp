@@ -29,11 +29,12 @@
 constexpr int FR_SCORE_RING = 512;  // eight launches of 64 batches (two of 256: the largest group) per worker between two syncs
 
 struct fr_driver {
+    FR_HIDDEN_DTOR(fr_driver);
     fr_ctx *ctx = nullptr;
     int n_threads = 0, depth = 0, max_batch = 0;
     std::vector<fr_worker *> workers;  // [n_threads * depth]
     std::vector<std::vector<float>> host_rings;  // per worker: FR_SCORE_RING x max_batch floats in host memory (run_host_streaming)
-    std::vector<float *> score_rings;  // per worker: FR_SCORE_RING x max_batch floats; the loop syncs a worker every
+    std::vector<FrBuf<float>> score_rings;  // per worker: FR_SCORE_RING x max_batch floats; the loop syncs a worker every
                                        // FR_SCORE_RING pushes, so no two batches in flight ever share a score buffer
 };
 
@@ -41,12 +42,8 @@ extern "C" void fr_driver_destroy(fr_driver *d) {
     if (!d) return;
     for (fr_worker *w : d->workers) fr_worker_destroy(w);
     if (d->ctx && !d->ctx->cpu) (void)hipSetDevice(d->ctx->device);
-    for (float *p : d->score_rings) {
-        if (p && d->ctx->cpu) free(p);
-        else if (p) (void)hipFree(p);
-    }
     fr_ctx *held = d->ctx;
-    delete d;
+    delete d;   // (the score rings are released by their holders)
     fr_ctx_unref(held);   // the driver's own reference (fr_driver_create): a driver destroyed after its context releases it last
 }
 
@@ -69,22 +66,16 @@ extern "C" int fr_driver_create(fr_ctx *ctx, int n_threads, int depth, int max_b
             return rc;
         }
         d->workers.push_back(w);
-        float *ring = nullptr;
-        if (ctx->cpu) {   // the CPU back-end's "device" buffers are host memory
-            ring = (float *)calloc((size_t)FR_SCORE_RING * max_batch, sizeof(float));
-            if (!ring) {
-                fr_driver_destroy(d);
-                FR_FAIL(FR_ERR_OOM, "out of host memory (score ring)");
-            }
-            d->score_rings.push_back(ring);
-            continue;
-        }
-        if (hipMalloc((void **)&ring, (size_t)FR_SCORE_RING * max_batch * sizeof(float)) != hipSuccess) {
+        FrBuf<float> ring;   // zeroed (the CPU back-end's "device" buffers are host memory)
+        const size_t n = (size_t)FR_SCORE_RING * max_batch;
+        rc = ring.alloc(fr_mem_kind(ctx, FrMem::DEVICE), n, "score ring");
+        if (rc) {
             fr_driver_destroy(d);
-            FR_FAIL(FR_ERR_OOM, "hipMalloc(score ring) failed");
+            return rc;
         }
-        (void)hipMemset(ring, 0, (size_t)FR_SCORE_RING * max_batch * sizeof(float));
-        d->score_rings.push_back(ring);
+        if (ctx->cpu) memset(ring, 0, n * sizeof(float));
+        else (void)hipMemset(ring, 0, n * sizeof(float));
+        d->score_rings.push_back(std::move(ring));
     }
     // a driver knows how many chains it will run side by side: an undecided context takes its chain width from it (fr_ctx_set_chain_width)
     {
@@ -138,7 +129,7 @@ extern "C" int fr_driver_run_resident(fr_driver *d, int batch, int64_t total_bat
     for (int t = 0; workers_used > 1 && t < threads_used; t++) {
         threads.emplace_back([&, t]() {
             fr_worker **wk = &d->workers[(size_t)t * d->depth];
-            float **rings = &d->score_rings[(size_t)t * d->depth];
+            const FrBuf<float> *rings = &d->score_rings[(size_t)t * d->depth];
             const int n_wk = workers_used - t * d->depth < d->depth ? workers_used - t * d->depth : d->depth;  // workers this thread uses
             int64_t local = 0;
             int rc = FR_OK;

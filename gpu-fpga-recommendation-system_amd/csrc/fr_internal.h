@@ -13,6 +13,7 @@
 #include "fleetrec.h"
 #include "fleetrec_diag.h"
 #include "fleetrec_serving.h"
+#include "fr_mem.h"
 
 // ---- error plumbing ---------------------------------------------------------------------------
 void fr_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -30,6 +31,12 @@ void fr_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
             fr_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
             return (e_ == hipErrorOutOfMemory) ? FR_ERR_OOM : FR_ERR_HIP;                            \
         }                                                                                            \
+    } while (0)
+
+#define FR_TRY(expr)               \
+    do {                           \
+        const int rc_ = (expr);    \
+        if (rc_) return rc_;       \
     } while (0)
 
 // ---- experiment knobs ---------------------------------------------------------------------------
@@ -285,6 +292,9 @@ struct FrTableMem {
     bool resident = false;     // false when the table belongs to another shard
 };
 
+// (the public headers name the handle types, which gives them default visibility: the destructors that now release things are kept inside the library,
+// so that its export list stays what it was -- fr_ctx's has always been in it)
+#define FR_HIDDEN_DTOR(type) __attribute__((visibility("hidden"))) ~type() = default
 struct fr_ctx {
     int device = -1;
     bool cpu = false;                      // the CPU back-end (fr_ctx_create with device = -1, fr_cpu.cpp): every pointer below is host memory, no HIP call is made
@@ -295,17 +305,17 @@ struct fr_ctx {
     std::vector<int> bank_of_table;        // index column of every table in FR_INDEX_PER_BANK mode (banks numbered by first appearance)
     std::vector<int64_t> bank_rows;        // per bank: min rows over its tables = the valid range of the bank's index
     int n_banks = 0;
-    char *table_arena = nullptr;           // one allocation holding every resident table, 256-B aligned starts
+    FrBuf<char> table_arena;               // one allocation holding every resident table, 256-B aligned starts
     size_t table_arena_bytes = 0;
     bool tables_filled = false;
     // record geometry
     int n_words = 0;                       // words this ctx gathers per item (whole record, or the shard's slice)
-    FrWordDesc *d_words = nullptr;         // [n_words]
+    FrBuf<FrWordDesc> d_words;             // [n_words]
     std::vector<FrWordDesc> h_words;
     FrGatherGroups gather_groups{};        // XCD partition of the record words (gather_pack_xcd_kernel); max_words == 0: none
     // item-tile gather plan (SEMANTIC / sharded layouts): passes grouped in chunks of <= FR_TILE_WORDS record words
-    FrPassDesc *d_passes = nullptr;
-    FrChunkDesc *d_chunks = nullptr;
+    FrBuf<FrPassDesc> d_passes;
+    FrBuf<FrChunkDesc> d_chunks;
     int n_chunks = 0;
     // Operand-type bank image (round 6; FR_INDEX_PER_BANK contexts, bf16 / fp8 chains): the reachable rows [0, bank_rows[b]) of every bank
     // once more, already in the chain's operand type -- bf16, or e4m3 at the X exponent -- so that the in-chain gather of a large batch
@@ -313,9 +323,8 @@ struct fr_ctx {
     // gather applies (RNE at fill = RNE at gather: bit-identical scores); rebuilt lazily (lp_ensure_image) when the precision, the X exponent
     // or the table contents have changed.  The fp32 arena stays the master (gather_only, fp32 chain, calibration, upload / download).
     std::vector<int> h_word_table, h_word_col;   // per h_words entry: source table (-1: dense) and the float column inside its row
-    char *lp_arena = nullptr;
-    size_t lp_arena_bytes = 0;
-    FrWordDesc *d_words_lp = nullptr;      // h_words with src / stride pointing into lp_arena (dense words unchanged)
+    FrBuf<char> lp_arena;
+    FrBuf<FrWordDesc> d_words_lp;          // h_words with src / stride pointing into lp_arena (dense words unchanged)
     int lp_prec = 0, lp_e_x = 0;           // what the image holds (FR_FC_BF16 / FR_FC_FP8 and, for fp8, the X exponent); 0 = nothing
     uint64_t lp_tables_gen = 0;            // tables_gen the image was made from
     uint64_t tables_gen = 1;               // bumped by every fill / upload
@@ -329,14 +338,14 @@ struct fr_ctx {
     std::vector<LpTable> lp_tables;
     std::atomic<long long> lp_builds{0};   // full builds of the image so far (fr_ctx_lp_bank_image_builds); a patch never counts
     // staging of fr_ctx_update_rows (grown on demand, used under lp_mutex on the set-up stream) and its index-range word (pinned, device-visible)
-    int32_t *d_up_ids = nullptr;
-    float *d_up_rows = nullptr;
-    size_t up_ids_cap = 0, up_rows_cap = 0;   // elements
-    int *h_up_err = nullptr, *d_up_err = nullptr;
+    FrBuf<int32_t> d_up_ids;
+    FrBuf<float> d_up_rows;
+    FrBuf<int> h_up_err;
+    int *d_up_err = nullptr;               // h_up_err's device-side alias
     std::atomic<int> lp_image_on{1};       // fr_ctx_set_lp_bank_image (fleetrec_diag.h): 0 = the in-chain gather reads the fp32 rows and converts them itself
     // Pooled (multi-hot) lookups (fr_ctx_set_pooling): the descriptors made of the hots per index column, P = sum of hots (0: no pooling)
     std::vector<FrPoolDesc> h_pool;
-    FrPoolDesc *d_pool = nullptr;          // [2 * n_words]: the padded form's descriptors, then the offsets form's (d_pool_csr)
+    FrBuf<FrPoolDesc> d_pool;              // [2 * n_words]: the padded form's descriptors, then the offsets form's (d_pool_csr)
     // the offsets (CSR) form's descriptors: first = the word's index COLUMN, hots = the column's cap | FR_POOL_DESC_MEAN
     std::vector<FrPoolDesc> h_pool_csr;
     FrPoolDesc *d_pool_csr = nullptr;      // = d_pool + n_words
@@ -355,24 +364,24 @@ struct fr_ctx {
         int req_words = 0, cand_words = 0;
         size_t d_first = 0;                // where the table starts inside d_req_desc
     } req_form[3];
-    int32_t *d_req_desc = nullptr;         // the three tables, one after the other
+    FrBuf<int32_t> d_req_desc;             // the three tables, one after the other
     std::mutex workers_mutex;              // guards `workers`
     std::vector<struct fr_worker *> workers;   // live workers (fr_ctx_set_pooling asks each whether it has work in flight)
-    unsigned long long *d_merged = nullptr;  // lookups merged by the dedup gather (FR_GATHER_ITEM_TILE_DEDUP_COUNT)
+    FrBuf<unsigned long long> d_merged;    // lookups merged by the dedup gather (FR_GATHER_ITEM_TILE_DEDUP_COUNT)
     std::atomic<int> gather_variant{0};    // fr_gather_variant (fr_ctx_set_gather_variant)
     // FC weights: fp32 master copies in the reference's column-major H x K layout
     // (= K-major "Wt[k][h]", cuda_server.c:215) and optional bf16 copies.
-    float *d_w[4] = {nullptr, nullptr, nullptr, nullptr};
-    float *d_wq[3] = {nullptr, nullptr, nullptr};  // FC1..FC3 re-packed as Wq[k/4][h][k%4] for the 16-byte operand loads
-    uint16_t *d_w_bf16[4] = {nullptr, nullptr, nullptr, nullptr};
+    FrBuf<float> d_w[4];
+    FrBuf<float> d_wq[3];  // FC1..FC3 re-packed as Wq[k/4][h][k%4] for the 16-byte operand loads
+    FrBuf<uint16_t> d_w_bf16[4];
     // fp8 chain: e4m3 q16 copies of FC1..FC3 and the power-of-two exponents (weights per layer; activations X, R1, R2, R3)
-    void *d_w_fp8[3] = {nullptr, nullptr, nullptr};
-    void *d_w_fp8h[3] = {nullptr, nullptr, nullptr};  // the same weights in the "q16h" layout of the non-scaled fp8 MFMA (fr_fused_tile_hs_kernel<2, ...>); fused-eligible models only
+    FrBuf<void> d_w_fp8[3];
+    FrBuf<void> d_w_fp8h[3];  // the same weights in the "q16h" layout of the non-scaled fp8 MFMA (fr_fused_tile_hs_kernel<2, ...>); fused-eligible models only
     int f8_e_w[3] = {0, 0, 0};
     int f8_e_act[4] = {0, 0, 0, 0};
     float f8_w_rms_gain[3] = {1.0f, 1.0f, 1.0f};  // ||W_l||_F / sqrt(N_l): rms growth of layer l under uncorrelated inputs
     bool f8_calibrated = false;
-    uint32_t *d_stats = nullptr;  // 16 words of reduction scratch (max |x| bits, sum x^2 per tensor)
+    FrBuf<uint32_t> d_stats;  // 16 words of reduction scratch (max |x| bits, sum x^2 per tensor)
     bool weights_set = false;
     int fc_precision = FR_FC_FP32;
     // sharding
@@ -400,36 +409,37 @@ struct fr_ctx {
 };
 
 struct fr_worker {
+    FR_HIDDEN_DTOR(fr_worker);
     fr_ctx *ctx = nullptr;
     int max_batch = 0;
     int idx_cap = 0;             // int32 columns per item its pinned and device index buffers hold: max(index columns, pooled columns at creation)
-    float *h_pool_w = nullptr;   // pinned [max_batch][pool_w_cap] per-sample weights of the host form (fr_worker_pool_weights_ptr); NULL without pooling at creation
+    FrBuf<float> h_pool_w;       // pinned [max_batch][pool_w_cap] per-sample weights of the host form (fr_worker_pool_weights_ptr); NULL without pooling at creation
     int pool_w_cap = 0;          // pooled columns at creation
-    int32_t *h_pool_off = nullptr;   // pinned [max_batch * index columns + 1] bag offsets of the offsets-form host call (fr_worker_pool_offsets_ptr); NULL without pooling at creation
+    FrBuf<int32_t> h_pool_off;       // pinned [max_batch * index columns + 1] bag offsets of the offsets-form host call (fr_worker_pool_offsets_ptr); NULL without pooling at creation
     // Request-form host call (fr_worker_submit_requests): the request side's pinned buffers, there on a worker created after fr_ctx_set_request_columns
-    int32_t *h_req_idx = nullptr;    // [max_batch][req_idx_cap]
-    float *h_req_w = nullptr;        // [max_batch][req_w_cap]; NULL without pooling at creation
-    float *h_req_dense = nullptr;    // [max_batch][dense_len]; NULL unless dense_shared
-    int32_t *h_req_off = nullptr;    // [max_batch + 1]
+    FrBuf<int32_t> h_req_idx;        // [max_batch][req_idx_cap]
+    FrBuf<float> h_req_w;            // [max_batch][req_w_cap]; NULL without pooling at creation
+    FrBuf<float> h_req_dense;        // [max_batch][dense_len]; NULL unless dense_shared
+    FrBuf<int32_t> h_req_off;        // [max_batch + 1]
     int req_idx_cap = 0, req_w_cap = 0;   // request words per request at creation: max(Rs, Rs') and Rs'
-    float *d_pool_w = nullptr;       // [max_batch][pool_w_cap]: the expanded per-sample weights (host memory on the CPU back-end)
+    FrBuf<float> d_pool_w;           // [max_batch][pool_w_cap]: the expanded per-sample weights (host memory on the CPU back-end)
     // CPU back-end: a call computes before it returns; an index-range error stays in c_err until fr_worker_sync reports it
-    float *c_scratch = nullptr;  // [max_batch][H1 + H2 + H3]
-    float *c_x = nullptr;        // records of the sharded FC entry points, [max_batch][K]
+    FrBuf<float> c_scratch;      // [max_batch][H1 + H2 + H3]
+    FrBuf<float> c_x;            // records of the sharded FC entry points, [max_batch][K]
     int c_err = 0;
     double c_t0 = 0.0;           // fr_worker_timer_start (steady clock, seconds)
     hipStream_t stream = nullptr;
     // pinned host staging (cudaMallocHost in the reference, cuda_server.c:136-160)
-    int32_t *h_idx = nullptr;
-    float *h_dense = nullptr;
-    float *h_score = nullptr;
+    FrBuf<int32_t> h_idx;
+    FrBuf<float> h_dense;
+    FrBuf<float> h_score;
     // device buffers (cudaMalloc in the reference, cuda_server.c:170-183)
-    int32_t *d_idx = nullptr;
-    float *d_dense = nullptr;
-    float *d_records = nullptr; // [max_batch][K]
+    FrBuf<int32_t> d_idx;
+    FrBuf<float> d_dense;
+    FrBuf<float> d_records;     // [max_batch][K]
     // feature-major activations, two sets alternating by launch parity; per set:
     //   Xt[K][ld] | R1t[2][H1][ld] | R2t[2][H2][ld] | R3t[2][H3][ld]   ([2] = K-split partials)
-    float *d_act[2] = {nullptr, nullptr};
+    FrBuf<float> d_act[2];
     int ld_max = 0;             // round_up(max_batch, 64)
     // software pipeline over consecutive batches: slot of the batch whose gather ran in launch L is ring[L % 8]
     struct Slot {
@@ -452,22 +462,23 @@ struct fr_worker {
     int n_pending = 0;
     // batch lists of the persistent kernel's launches: FR_BLIST_RING pinned host blocks + device copies, one H2D copy per launch on the
     // worker's stream; a block is rewritten only after the copy that read it has executed (its event)
-    FrFusedBatch *h_blist = nullptr, *d_blist = nullptr;
-    hipEvent_t ev_blist[FR_BLIST_RING] = {nullptr, nullptr, nullptr, nullptr};
+    FrBuf<FrFusedBatch> h_blist, d_blist;
+    FrEvent ev_blist[FR_BLIST_RING];
     bool blist_busy[FR_BLIST_RING] = {false, false, false, false};
     int blist_cur = 0;
     int64_t pending_items = 0;
-    float *d_score = nullptr;
+    FrBuf<float> d_score;
     // host-fed streaming (fr_worker_push_host): FR_HOST_BLOCKS staging blocks of `g` batches each; a block is filled by CPU copies
     // into pinned memory, then moves as ONE H2D copy + ONE fused launch + ONE D2H copy; its event says when the scores are home
     struct HostRing {
+        FR_HIDDEN_DTOR(HostRing);
         int g = 0;                 // batches per block (fixed when the ring is created)
         size_t idx_slot = 0, dense_slot = 0, score_slot = 0;  // elements per batch slot
-        int32_t *h_idx = nullptr, *d_idx = nullptr;
-        float *h_dense = nullptr, *d_dense = nullptr, *h_sc = nullptr, *d_sc = nullptr;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        FrBuf<int32_t> h_idx, d_idx;
+        FrBuf<float> h_dense, d_dense, h_sc, d_sc;
+        FrEvent ev[4];
         hipStream_t copy = nullptr;   // the blocks' H2D copies run here, ahead of the launches on the worker's stream (ev_in: block b's rows have landed)
-        hipEvent_t ev_in[4] = {nullptr, nullptr, nullptr, nullptr};
+        FrEvent ev_in[4];
         bool inflight[4] = {false, false, false, false};
         int count[4] = {0, 0, 0, 0};          // batches in the block
         float *dst[4][FR_FUSED_MAX_BATCHES];  // where each batch's scores go
@@ -477,35 +488,34 @@ struct fr_worker {
         long long delivered = 0;   // host-fed batches whose scores have been copied to their h_scores so far (fr_worker_host_poll)
     } hr;
     // table-sharded exchange (fr_worker_submit_sharded, fr_comm.cpp): this shard's slice, the all-gathered slices, score chunks
-    void *d_slice = nullptr, *d_gathered = nullptr;
-    float *d_score_part = nullptr, *d_score_all = nullptr;  // [chunk + 1], [G][chunk + 1]: every rank's chunk ends with its status word
-    float *h_sh_status = nullptr;  // pinned: [0] this rank's status word as sent, [1 .. G] the status words of all ranks as received
+    FrBuf<void> d_slice, d_gathered;
+    FrBuf<float> d_score_part, d_score_all;  // [chunk + 1], [G][chunk + 1]: every rank's chunk ends with its status word
+    FrBuf<float> h_sh_status;  // pinned: [0] this rank's status word as sent, [1 .. G] the status words of all ranks as received
     struct fr_comm *sh_comm = nullptr;  // a sharded step is in flight through this communicator (fr_worker_sync -> fr_comm_wait)
     int sh_ranks = 0;
     std::atomic<int> sh_inject_fc_fail{0};   // fr_worker_inject_fc_failure (fleetrec_diag.h): sharded steps left whose FC chain is reported as failed
-    void *h_stage_send = nullptr, *h_stage_recv = nullptr;   // pinned staging of the STAGED host exchange (GPU shard contexts that share a device)
+    FrBuf<void> h_stage_send, h_stage_recv;   // pinned staging of the STAGED host exchange (GPU shard contexts that share a device)
     void *sh_host_stream = nullptr;  // CPU workers: the host stream their sharded steps run on (fr_comm.cpp HostStream), made on first use
-    int *h_err = nullptr;  // sticky index-range flag: pinned host word ...
+    FrBuf<int> err_word;   // sticky index-range flag: the pinned, device-visible host word of a GPU worker (a CPU worker's is c_err) ...
+    int *h_err = nullptr;  // ... as the host reads it ...
     int *d_err = nullptr;  // ... and its device-side alias
     bool in_flight = false;
     // fr_worker_update_rows: recorded on the stream behind the update's launches; a rebuild of the operand-type bank image makes the set-up
     // stream wait for it (lp_ensure_image).  Both touched under fr_ctx::lp_mutex only.
-    hipEvent_t ev_update = nullptr;
+    FrEvent ev_update;
     bool update_recorded = false;
     // Segmented top-K ranking (fr_worker_topk_device / fr_worker_topk).  d_rank: the scratch of segments longer than FR_RANK_PART (head, unit records,
     // candidate lists), allocated by the first call over more than FR_RANK_PART scores, grown (behind a wait for the stream) when a call needs more.
-    char *d_rank = nullptr;
-    size_t rank_bytes = 0;
+    FrBuf<char> d_rank;
     int host_batch = 0;          // items of the host-form batch in flight (fr_worker_submit, the three host-form pooled submits); 0: none
     // host form: pinned staging of the offsets and of the results, which fr_worker_sync copies to where the caller wants them
-    int32_t *h_tk_off = nullptr, *h_tk_idx = nullptr;
-    float *h_tk_sc = nullptr;
-    size_t tk_off_cap = 0, tk_out_cap = 0;   // elements
+    FrBuf<int32_t> h_tk_off, h_tk_idx;
+    FrBuf<float> h_tk_sc;
     int32_t *tk_dst_idx = nullptr;
     float *tk_dst_sc = nullptr;
     size_t tk_count = 0;         // n_seg * k of the host-form ranking in flight; 0: none
     char last_kernel[96] = "";  // fr_worker_last_kernel: the dominant kernel of the most recent launch this worker enqueued
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    FrEvent ev_start, ev_stop;
 };
 
 size_t idx_cols(const fr_ctx *c);   // int32 index columns per item of a one-hot batch (fr_api.cpp)
@@ -517,6 +527,7 @@ int fr_pooled_weights_need_sum(const fr_ctx *c);
 int fr_pooled_host_offsets(const fr_worker *w, int batch, const char *who, int64_t *nnz);
 void fr_ctx_ref(fr_ctx *c);     // + 1 reference (a worker, a communicator handle)
 void fr_ctx_unref(fr_ctx *c);   // - 1; the last one releases the context
+inline FrMem fr_mem_kind(const fr_ctx *c, FrMem k) { return c->cpu ? FrMem::HOST : k; }
 
 // ---- table-sharded exchange (fr_comm.cpp) ------------------------------------------------------------
 int fr_comm_wait(fr_worker *w);  // bounded wait for the sharded step in flight + the ranks' status words; FR_OK when none is in flight
