@@ -141,7 +141,9 @@ void fr_shard_bounds(const fr_model_desc &m, int n_shards, std::vector<int> &seg
         // advance while the end of segment s is closer to (or before) the target than its start
         while (s < m.n_segments && m.segments[s].rec_offset + m.segments[s].len / 2.0 <= target) s++;
         // a COPY segment must stay with the table segment it duplicates only for locality, not correctness
-        if (s < g) s = g;  // at least one segment per shard
+        // at least one segment per shard: past the previous shard's first segment (two targets may fall inside one wide segment), and
+        // leaving one for every shard still to come
+        if (s <= seg_begin[g - 1]) s = seg_begin[g - 1] + 1;
         if (s > m.n_segments - (n_shards - g)) s = m.n_segments - (n_shards - g);
         seg_begin[g] = s;
     }
@@ -259,6 +261,10 @@ static int build_words(fr_ctx *c) {
     for (auto &tm : c->table_mem) tm.resident = false;
     for (int s = s0; s < s1; s++)
         if (m.segments[s].kind != FR_SEG_DENSE) c->table_mem[m.segments[s].src].resident = true;
+    // a shard of DENSE segments only holds no table: there is nothing to fill or upload, so it counts as loaded from the start
+    bool any_resident = false;
+    for (const auto &tm : c->table_mem) any_resident = any_resident || tm.resident;
+    if (!any_resident) c->tables_filled = true;
     // arena layout
     c->n_banks = fr_bank_map(m, c->bank_of_table, c->bank_rows);
     size_t off = 0;

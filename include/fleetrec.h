@@ -388,7 +388,11 @@ int fr_device_synchronize(fr_ctx *ctx);
 int fr_ctx_shard_info(const fr_ctx *ctx, int *shard_rank, int *n_shards, int *slice_offset,
                       int *slice_len, int *slice_padded_len);
 /* Pure host query (no device): the plan fr_ctx_create_sharded uses -- per shard the first record float and the float
- * count of its slice (arrays of n_shards ints), and the common padded slice length F. */
+ * count of its slice (arrays of n_shards ints), and the common padded slice length F.
+ * Guarantee: for 1 <= n_shards <= n_segments every shard holds at least one whole segment (slice_len > 0), the slices tile
+ * the record in shard order, and more shards than segments are refused (FR_ERR_INVALID).
+ * A shard whose segments are all DENSE holds no table: every fr_ctx_upload_table on it is refused (FR_ERR_STATE) and it
+ * counts as loaded from its creation -- it gathers its slice of the request's dense features without any fill or upload. */
 int fr_model_shard_plan(const fr_model_desc *m, int n_shards, int *slice_offset, int *slice_len, int *slice_padded_len);
 /* After the all-gather: d_gathered = [n_shards][batch_total][F] floats (every shard's padded slice, as
  * fr_worker_gather_only wrote it on that shard, concatenated in shard order = what ncclAllGather delivers).

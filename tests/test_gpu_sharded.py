@@ -199,7 +199,8 @@ def test_submit_sharded_through_rccl_one_rank(fr, O, gpu, prec):
     rec = om.gather(idx, dense=dense, content_mode=O.FILL_HASH, seed=SEED_TABLES).view(np.float32)
     ref = om.fc_chain(rec, [ctx.get_weights(l) for l in range(4)], acc64=True)
     assert rel_err(got, ref) <= {"f32": 1e-3, "bf16": 3e-2, "fp8": 0.15}[prec]
-    assert np.array_equal(wk.infer_sharded(comm, idx[:77], dense[:77]), got[:77]) if prec != "f32" else True   # ragged batch, reuse
+    again = wk.infer_sharded(comm, idx[:77], dense[:77])   # ragged batch, reuse: the step's own first result (fp32: another batch may sum in another order)
+    assert np.array_equal(again, got[:77]) if prec != "f32" else rel_err(again, got[:77]) <= 1e-5
     # a communicator belongs to its context
     other = fr.Context(m, device=gpu)
     w2 = fr.Worker(other, 64)
