@@ -6,7 +6,9 @@ reaches 2^24 times the products' common power-of-two quantum (premise(), asserte
 then exact in any order and any split, bf16 / e4m3 products are exact in fp32, the fp8 scales are powers of two: the only roundings
 left are the chain's explicit ones (bf16 RNE per hidden layer; e4m3 clamp to +-448 then RNE), which the host restates
 (gpu_helpers.chain_bf16_reference / chain_fp8_reference).  So there is no tolerance: one wrong column, k-group or tile shows.
-(A sweep row with a record too short for FC1's sums to pass 256 draws its tables from [-12, 12], so that bf16 still rounds there.)"""
+(A sweep row with a record too short for FC1's sums to pass 256 draws its tables from [-12, 12], so that bf16 still rounds there.)
+The integer weights are exact in every operand type, so the master-weight side has data of its own: WIDE (weights the pack kernels must
+round, an fp32 Wout no bf16 image holds), W_EXP_MAXIMA (fp8 weight exponents read back) and REFRESH_OPS (every refresh of a derived image)."""
 import re
 import zlib
 
@@ -49,10 +51,11 @@ def _sparse_layer(rng, K, N, nnz, positive=False):
     return W
 
 
-def make_data(model_spec, seed, n_pool=256, table_max=3):
+def make_data(model_spec, seed, n_pool=256, table_max=3, nnz=(320, 8, 8)):
     """-> dict: tables (list of float32 [rows][dim]), ws (4 float32 [K][N] arrays, == column-major N x K flattened), fc, and a pool
     of n_pool items (idx int32 [n][n_tables], dense float32 [n][dense_len] or None).  table_max: table and dense values are integers in
-    [-table_max, table_max] (3: the stock distribution; a short record takes a wider range so that its FC1 sums pass 256 and bf16 rounds)."""
+    [-table_max, table_max] (3: the stock distribution; a short record takes a wider range so that its FC1 sums pass 256 and bf16 rounds);
+    nnz: nonzeros per column of W1, W2, W3 (320, 8, 8: the stock counts; the fp32-Wout rows of WIDE take fewer, see there)."""
     rng = np.random.default_rng(seed)
     fc = [sum(t["dim"] for t in model_spec["tables"]) + model_spec.get("dense_len", 0)] + list(model_spec["fc"]) + [1]
     vals = np.arange(-3, 4, dtype=np.float32)
@@ -62,8 +65,8 @@ def make_data(model_spec, seed, n_pool=256, table_max=3):
         pv = np.linspace(1.0, 12.0, vals.size) ** 2
         pv /= pv.sum()
     tables = [rng.choice(vals, size=(t["rows"], t["dim"]), p=pv).astype(np.float32) for t in model_spec["tables"]]
-    ws = [_sparse_layer(rng, fc[0], fc[1], min(fc[0], 320), positive=True), _sparse_layer(rng, fc[1], fc[2], 8),
-          _sparse_layer(rng, fc[2], fc[3], 8), _sparse_layer(rng, fc[3], 1, 12)]
+    ws = [_sparse_layer(rng, fc[0], fc[1], min(fc[0], nnz[0]), positive=True), _sparse_layer(rng, fc[1], fc[2], nnz[1]),
+          _sparse_layer(rng, fc[2], fc[3], nnz[2]), _sparse_layer(rng, fc[3], 1, 12)]
     rows = np.array([t["rows"] for t in model_spec["tables"]])
     idx = (rng.random((n_pool, len(rows))) * rows[None, :]).astype(np.int32)
     dl = model_spec.get("dense_len", 0)
@@ -103,9 +106,21 @@ def fp32_acts(rec, ws):
     return acts, (acts[-1] @ ws[3].astype(np.float64)).astype(np.float32).ravel()
 
 
+def w_exponent(W, use_abs=True, skip_nan=True):
+    """One layer's fp8 weight exponent floor_log2(448 / max|W|) in float32, the maximum taken over the values that are not NaN; 0 for an
+    all-zero layer.  (use_abs / skip_nan False: the mutants `max taken without abs`, whose maximum starts at 0 as the device's does, and
+    `NaN drives the max`: a NaN's bit pattern wins the device's integer atomic maximum, and a NaN maximum fails `> 0`, which gives 0.)"""
+    v = np.asarray(W, np.float32).ravel()
+    if not skip_nan and np.isnan(v).any():
+        return 0
+    v = v[~np.isnan(v)]
+    m = np.float32(max(float((np.abs(v) if use_abs else v).max()), 0.0)) if v.size else np.float32(0.0)
+    return floor_log2_f32(np.float32(448.0) / m) if m > 0 else 0
+
+
 def w_exponents(ws):
     """fp8 weight exponents floor_log2(448 / max|W|), in float32."""
-    return [floor_log2_f32(np.float32(448.0) / np.float32(np.abs(ws[l]).max())) for l in range(3)]
+    return [w_exponent(ws[l]) for l in range(3)]
 
 
 def act_exponents(rec, ws):
@@ -160,7 +175,7 @@ def operands(prec, rec, ws, act_exp=None, w_exp=None):
         r = (x @ W).astype(np.float32)
         x = rnd(r).astype(np.float64)
         hidden.append((r.astype(np.float64), x))
-    ops.append((x, ws[3].astype(np.float64)))
+    ops.append((x, rnd(ws[3]).astype(np.float64)))   # (the bf16 chain reads the bf16 vector of Wout, as chain_bf16_reference does)
     return ops, hidden
 
 
@@ -203,6 +218,133 @@ def rounding_witnesses(prec, rec, ws, act_exp=None, w_exp=None):
             tie = np.zeros(r.shape, bool)
         res.append((int(inexact.sum()), int(tie.sum())))
     return res
+
+
+# ---- weights that must round: the master-weight side of the chain (pack kernels, fp8 weight exponents, the form of Wout) ------------------
+# The stock weights {-2 .. 2} are exact in bf16 and in e4m3 at any power-of-two scale, so no pack kernel ever rounds them.  wide_weights()
+# replaces every nonzero weight by a float32 value that the device's conversion must round:
+#   bf16: a value of the closed interval that rounds (RNE) to w * 2^8 -- [255.5, 257] for |w| = 1, [511, 514] for |w| = 2.  Both ends are
+#         exact ties that resolve to the even neighbour, the lower ends carry into the next binade.  The rounded image is the stock
+#         image times 2^8, so every lowbit and every sum of premise() shifts by the same amount: the premise is inherited.
+#   fp8:  a value of FP8_POOL (units in which the layer's maximum is 28, i.e. 448 at scale 2^4): e4m3 keeps four significant bits, so
+#         the images 16 .. 28 are richer than the stock ones and premise() is asserted on them, not inherited.
+# Each value is then scaled by the layer's 2^s (exact in float32).
+def _in(v, toward):
+    return float(np.nextafter(np.float32(v), np.float32(toward)))
+
+
+BF16_PREIMAGES = {   # |stock| -> tie (carries), just inside it, above half, the exact value, below half, just inside the upper tie, upper tie
+    1: (255.5, _in(255.5, 256), 255.75, 256.0, 256.5, _in(257, 256), 257.0),
+    2: (511.0, _in(511, 512), 511.5, 512.0, 513.0, _in(514, 512), 514.0),
+}
+FP8_POOL = (17.0, 19.0, 21.0, 23.0, 25.0, 27.0,     # ties between the e4m3 neighbours 16, 18 .. 28: three resolve downward, three upward
+            15.5,                                    # a tie that carries to 16
+            19.01, 20.99, 23.5, 27.5, 16.99,         # near-ties, above and below half
+            16.0, 24.0, 28.0,                        # exact
+            2.0 ** -14)                              # half the smallest e4m3 subnormal at this scale: a tie that flushes to zero
+FP8_TOPS = {28.0: 1.0, 27.0: 1.0, 3.5: 0.125}        # a layer's maximum at unit scale -> its unit: 28 * 2^4 = 448 exactly (the top of the interval
+#                                                      (224, 448]), 27 * 2^4 = 432 (a tie, rounds to 448), 448 / 3.5 = 2^7 exactly (a power-of-two quotient)
+
+
+def wide_weights(W, prec, s, seed, top=28.0):
+    """The stock matrix W with every nonzero replaced (sign kept) by a value its image must round, times 2^s; every value of the
+    pool is used, the layer's maximum is `top` * 2^s in fp8 (514 * 2^s in bf16)."""
+    rng = np.random.default_rng(seed)
+    W = np.ascontiguousarray(W, np.float32)
+    out = np.zeros(W.size, np.float32)
+    flat = W.ravel()
+    if prec == "bf16":
+        for a, vals in BF16_PREIMAGES.items():
+            sel = np.flatnonzero(np.abs(flat) == a)
+            pool = np.array(vals, np.float32)
+            assert sel.size >= pool.size
+            out[sel] = np.sign(flat[sel]) * pool[rng.permutation(sel.size) % pool.size]
+        assert np.count_nonzero(out) == np.count_nonzero(flat)
+    else:
+        unit = FP8_TOPS[top]
+        pool = np.array([v for v in FP8_POOL if v * unit <= top], np.float32) * np.float32(unit)
+        sel = np.flatnonzero(flat)
+        assert sel.size >= pool.size
+        out[sel] = np.sign(flat[sel]) * pool[rng.permutation(sel.size) % pool.size]
+        assert np.abs(out).max() == np.float32(top)
+    return (out * np.float32(2.0 ** s)).reshape(W.shape)
+
+
+def wide_wout(W, s=0):
+    """The fp8 chain's output layer reads the fp32 master: t * 257 / 256 needs nine significant bits, so a bf16 image of it differs."""
+    return (np.ascontiguousarray(W, np.float32) * np.float32(257.0 / 256.0) * np.float32(2.0 ** s)).astype(np.float32)
+
+
+def bf16_image(W, mode="rne"):
+    """float32 -> bf16 as float32: round to nearest even (the device), or the mutants `trunc` (toward zero) and `away` (half away)."""
+    if mode == "rne":
+        return bf16_round(W)
+    u = np.ascontiguousarray(W, np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + (0x8000 if mode == "away" else 0)) & 0xFFFF0000).astype(np.uint32).view(np.float32).reshape(np.shape(W))
+
+
+def e4m3_image(v, mode="rne"):
+    """The e4m3 value (float64) of float32 v: clamp to +-448, then round to nearest even (== the decode of gpu_helpers.e4m3_encode), or
+    the mutants `trunc` and `away`."""
+    x = np.clip(np.asarray(v, np.float32), -448.0, 448.0).astype(np.float64)
+    a = np.abs(x)
+    _, ex = np.frexp(a)
+    q = np.ldexp(1.0, np.maximum(ex - 1, -6) - 3)
+    t = a / q
+    t = np.rint(t) if mode == "rne" else np.floor(t) if mode == "trunc" else np.floor(t + 0.5)
+    return np.copysign(t * q, x)
+
+
+def weight_image(prec, l, W, w_exp=None, mode="rne"):
+    """What the kernels of precision `prec` multiply by for layer l (float64, in the domain they sum in): the fp32 master (the fp32 chain, and
+    the fp8 chain's output layer), its bf16 image, or the e4m3 image of W * 2^w_exp[l]."""
+    if prec == "f32" or (prec == "fp8" and l == 3):
+        return np.asarray(W, np.float64)
+    if prec == "bf16":
+        return bf16_image(W, mode).astype(np.float64)
+    return e4m3_image(np.asarray(W, np.float32) * np.float32(2.0 ** w_exp[l]), mode)
+
+
+def weight_witnesses(prec, l, W, w_exp=None):
+    """Of one layer's weights: (values the image must round, exact ties resolved toward zero, ties resolved away from zero, roundings that carry
+    into the next binade)."""
+    v = np.asarray(W, np.float32)
+    if prec == "fp8":
+        v = v * np.float32(2.0 ** w_exp[l])
+    img = weight_image(prec, l, W, w_exp)
+    a, b = np.abs(v.astype(np.float64)), np.abs(img)
+    if prec == "bf16":
+        tie = (np.ascontiguousarray(v).view(np.uint32) & 0xFFFF) == 0x8000
+    else:
+        _, ex = np.frexp(a)
+        q = np.ldexp(1.0, np.maximum(ex - 1, -6) - 3)
+        tie = (a <= 448.0) & (np.mod(a, q) == q / 2)
+    carry = (b > a) & (np.frexp(b)[1] > np.frexp(a)[1])
+    return int((a != b).sum()), int((tie & (b < a)).sum()), int((tie & (b > a)).sum()), int(carry.sum())
+
+
+def exponent_margin(quotients):
+    """min over float64 quotients q of |q / 2^round(log2 q) - 1|: how far the nearest one lies from a power of two, where its floor_log2 would
+    flip.  The device finds a maximum or a sum of squares in fp32 and in no fixed order; a margin far above 2^-20 makes its exponent certain."""
+    q = np.asarray(quotients, np.float64)
+    return float(np.abs(q / np.exp2(np.rint(np.log2(q))) - 1.0).min())
+
+
+def act_exponent_quotients(rec, ws):
+    acts, _ = fp32_acts(rec, ws)
+    return [448.0 / (2.0 * float(np.abs(a).max())) for a in acts]
+
+
+def estimated_act_exponents(ws, fc):
+    """The activation exponents of an uncalibrated fp8 context (fr_api.cpp f8_estimate_act_exponents): rms 0.58 at the input, times
+    sqrt(sum W_l^2 / H_l) per layer, 8 rms must fit 448.  -> (exponents, the float64 quotients they are the floor_log2 of)."""
+    rms, out, quot = 0.58, [], []
+    for l in range(4):
+        quot.append(448.0 / (8.0 * rms))
+        out.append(floor_log2_f32(np.float32(448.0) / (np.float32(8.0) * np.float32(rms))))
+        if l < 3:
+            rms *= float(np.sqrt((ws[l].astype(np.float64) ** 2).sum() / fc[l + 1]))
+    return out, quot
 
 
 # ---- the GPU matrix: (model, precision, batch, chain width, stream group) -> the kernels fr_worker_last_kernel must report ----------------
@@ -469,6 +611,70 @@ FAMILIES = {
 }
 
 
+# ---- the weight rows: one per precision for each distinct reader of a weight image, on weights that must round -----------------------------
+# A row runs like a sweep row, on the shape of the smallest CASES / SWEEPS entry that reaches its reader.  `wide`: the layers whose weights
+# wide_weights() replaces (bf16: all four, Wout included; fp8: W1..W3, the images) -- or (3,) for the fp8 chain's fp32-master Wout, rows
+# of their own (`wout`) on smaller-magnitude data: nine significant bits in Wout cost 257 x the headroom of premise()'s output layer.
+# `layer`: FC1 / FC2 / FC3 / OUT = the layer whose fc_layer_only launch must report `kernel`, stream = the streamed launch of `group` pushes,
+# stages = all four layers on the stage pipeline, gather_out = five pushes in flight (fr_gather_out_kernel<P>, which no hook reports).
+BF16_SCALES = (-8, -7, -9, -8)                       # net factor 2^(8 + s) = 1, 2, 1/2, 1: the scores are the stock scores
+FP8_LAYERS = ((28.0, 1), (27.0, -2), (3.5, 0))       # (top, s) per hidden layer -> w_exp 3, 6, 7
+WOUT_SHRINK = dict(table_max=1, nnz=(12, 3, 2))   # tables in {-1, 0, 1}, 12 / 3 / 2 nonzeros per column of W1 / W2 / W3 (where K > N the cover of every row sets the floor)
+R_FC = (2048, 512, 512)
+
+
+def _wide_row(tag, prec, K, fc, batch, layer, kernel, reader, wout=False, width=1, group=1, dense_len=0):
+    return dict(id="wide-%s-%s%s" % (prec, tag, "-wout" if wout else ""), spec=(K, tuple(fc), dense_len), prec=prec, batch=batch, width=width,
+                group=group, layer=layer, kernel=kernel, reader=reader, wout=wout,
+                wide=(3,) if wout else (0, 1, 2, 3) if prec == "bf16" else (0, 1, 2), **(WOUT_SHRINK if wout else {}))
+
+
+def _wide_rows():
+    A, C = (1024, 512, 256), C_FC
+    rows = [
+        _wide_row("fused_h", "bf16", 352, A, 256, "stream", "fr_fused_tile_h_kernel<2, 2, 22, true, 16, 2>", "chunked fused kernel: W1..W3 images, bf16 Wout", group=16),
+        _wide_row("fused_hs", "bf16", 352, A, 256, "stream", _hs_kernel(352), "persistent fused kernel: buffer resources sized from the images", group=64),
+        _wide_row("fused_f8", "fp8", 352, A, 256, "stream", "fr_fused_tile_f8_kernel<6>", "fp8 fused kernel: e4m3 images", group=16),
+        _wide_row("fused_f8", "fp8", 352, A, 256, "stream", "fr_fused_tile_f8_kernel<6>", "fp8 fused kernel: fp32 Wout", group=16, wout=True),
+    ]
+    for prec in ("bf16", "fp8"):
+        p = _PI[prec]
+        k3, k2 = (192, 128) if prec == "bf16" else (384, 256)   # three / two K steps of the GEMM loops
+        rows += [
+            _wide_row("stages", prec, 3968, C, 65, "stages", None, "stage pipeline, stages 1-4", group=4, dense_len=16),
+            _wide_row("n128", prec, k3, C, 4090, "FC1", PPN % p, "128 x 256 tiles, phased waves"),
+            _wide_row("t256", prec, k2, C, 4090, "FC1", PP % (p, 3 if prec == "bf16" else 2, 8), "256 x 256 tiles (chain width 4)", width=4),
+            _wide_row("t64", prec, 512, (k2, 512, 256), 4090, "FC2", LP % (p, 1, 64, 4 if prec == "bf16" else 2), "64 x 128 tiles"),
+            _wide_row("t128", prec, k3, C, 1638, "FC1", LP % (p, 1, 128, 2), "128 x 128 tiles"),
+            _wide_row("tail", prec, 512, (512, k2, 256), 4090, "FC3", OUT % p, "FC3 + output layer in one launch"),
+            _wide_row("gather_out", prec, 3968, R_FC, 4096, "gather_out", "fr_gather_out_kernel<%d>" % p, "gather | output layer in one launch", dense_len=16),
+        ]
+    rows += [
+        _wide_row("kpad", "fp8", 104, (256, 512, 256), 33, "FC1", PIPE % (1, 2), "K % 64 == 40: the zero K padding of the e4m3 image beside weights that round"),
+        _wide_row("stages", "fp8", 3968, C, 65, "OUT", PIPE % (4, 2), "stage 4: fp32 Wout", wout=True, group=4, dense_len=16),
+        _wide_row("tail", "fp8", 512, (512, 256, 256), 4090, "FC3", OUT % 2, "FC3 + output tail: fp32 Wout", wout=True),
+        _wide_row("gather_out", "fp8", 3968, R_FC, 4096, "gather_out", "fr_gather_out_kernel<2>", "gather | output layer: fp32 Wout", wout=True, dense_len=16),
+    ]
+    return rows
+
+
+WIDE = _wide_rows()
+
+
+def widen(row, ws):
+    """The row's weights: the stock ones with the layers of row['wide'] replaced (wide_weights / wide_wout), seeds derived from its id."""
+    seed = zlib.crc32(row["id"].encode())
+    out = list(ws)
+    for l in row["wide"]:
+        if row["prec"] == "bf16":
+            out[l] = wide_weights(ws[l], "bf16", BF16_SCALES[l], seed + l)
+        elif l == 3:
+            out[l] = wide_wout(ws[l])
+        else:
+            out[l] = wide_weights(ws[l], "fp8", FP8_LAYERS[l][1], seed + l, top=FP8_LAYERS[l][0])
+    return out
+
+
 def named_kernels():
     """Every kernel name a GPU-matrix case asserts, or runs where no hook reports it (a case's `runs`: the stage pipeline's gather-only
     first step and its multi-stage steps, which fr_worker_last_kernel does not record)."""
@@ -488,7 +694,9 @@ def case_data(case, n_items):
     if "spec" in case:   # a SWEEPS row: its own shape, a seed derived from its id
         K, fc, dl = case["spec"]
         sp = spec(K, fc, dense_len=dl, rows=case.get("rows", 29), name="sweep_%08x" % zlib.crc32(case["id"].encode()))
-        data = make_data(sp, 9000 + zlib.crc32(case["id"].encode()) % 100000, table_max=case.get("table_max", 3))
+        data = make_data(sp, 9000 + zlib.crc32(case["id"].encode()) % 100000, table_max=case.get("table_max", 3), nnz=case.get("nnz", (320, 8, 8)))
+        if case.get("wide"):   # a WIDE row: `stock` keeps the integer weights its wide ones were drawn from
+            data = dict(data, stock=data["ws"], ws=widen(case, data["ws"]))
     else:
         sp = model_spec(case["model"])
         data = make_data(sp, model_seed(case["model"]))
@@ -511,3 +719,70 @@ def demangle(name):
                 for t, neg, v in re.findall(r"L([ib])(n?)(\d+)E", rest[1:rest.index("EE") + 1])]
         return "%s<%s>" % (base, ", ".join(args))
     return re.sub(r"\(.*\)$", "", re.sub(r"^void ", "", name))
+
+
+# ---- fp8 weight exponents from the weights (stats_kernel + floor_log2(448 / max|W|)) -------------------------------------------------------
+TINY = (64, (64, 64, 64))   # K, hidden widths of the model the exponent tests run on
+
+
+def _f32(v, toward=None):
+    return np.float32(v) if toward is None else np.nextafter(np.float32(v), np.float32(toward))
+
+
+# a layer's maximum |w| -> its exponent, worked out by hand: max * 2^e must land in (224, 448]
+W_EXP_MAXIMA = [
+    ("448", _f32(448), 0), ("448+", _f32(448, np.inf), -1), ("224", _f32(224), 1), ("224-", _f32(224, 0), 1), ("224+", _f32(224, np.inf), 0),
+    ("3.5", _f32(3.5), 7), ("28", _f32(28), 4), ("27", _f32(27), 4), ("1", _f32(1), 8), ("2^-60", _f32(2.0 ** -60), 68), ("2^60", _f32(2.0 ** 60), -52),
+]
+W_EXP_PLACES = ("first", "last", "negative")
+
+
+def layer_with_maximum(stock, m, place):
+    """A layer of the stock weights' pattern scaled to |w| <= m / 2, with the maximum m at the first or the last element, or -m in the middle."""
+    w = (np.asarray(stock, np.float32) * (np.float32(m) / np.float32(4.0))).ravel().copy()
+    pos, val = {"first": (0, m), "last": (w.size - 1, m), "negative": (w.size // 2 + 1, -m)}[place]
+    w[pos] = val
+    assert (np.abs(np.delete(w, pos)) < np.abs(np.float32(m))).all()
+    return w.reshape(np.shape(stock)), pos
+
+
+# ---- the refresh sequence: every call that must rebuild a derived weight image, on one context --------------------------------------------
+# ("prec", p): fr_ctx_set_fc_precision; ("set", l, which): fr_ctx_set_weights of layer l.  A and B are integer weight sets of two seeds
+# (rounding is the WIDE rows' job, this is about staleness); A8 / A4 = A times 8 / 4, so that the fp8 weight exponent of the layer moves.
+REFRESH_OPS = [("prec", "f32"), ("prec", "bf16"), ("set", 0, "B"), ("set", 1, "B"), ("set", 2, "B"), ("set", 3, "B"), ("prec", "fp8"),
+               ("set", 1, "A8"), ("prec", "f32"), ("set", 2, "A4"), ("prec", "bf16"), ("prec", "fp8")]
+REFRESH_SHAPES = {"pipeline": dict(K=112, fc=(256, 512, 256), batch=33, group=1), "fused": dict(K=352, fc=(1024, 512, 256), batch=64, group=16)}
+
+
+def refresh_data(shape):
+    s = REFRESH_SHAPES[shape]
+    sp = spec(s["K"], s["fc"], name="refresh_" + shape)
+    dA, dB = make_data(sp, 4101 + s["K"]), make_data(sp, 5202 + s["K"])
+    sets = {"A": dA["ws"], "B": dB["ws"], "A8": [w * np.float32(8) for w in dA["ws"]], "A4": [w * np.float32(4) for w in dA["ws"]]}
+    return sp, dA, sets
+
+
+def refresh_steps(sets, precs=PRECS):
+    """The sequence as (op, precision in force, the weights in force, stale candidates): a stale candidate is the weight list a context
+    would compute with if it had left one layer's image of that precision as it was when the precision was last in force (or, after a
+    set_weights, as it was before the call).  Ops of a precision outside `precs` are skipped (the CPU back-end: fp32 only)."""
+    cur, prec = list(sets["A"]), "f32"
+    seen = {p: list(cur) for p in PRECS}   # per precision, the weights its images were last built from
+    out = []
+    for op in REFRESH_OPS:
+        if op[0] == "prec":
+            if op[1] not in precs:
+                continue
+            prec = op[1]
+        else:
+            cur = list(cur)
+            cur[op[1]] = sets[op[2]][op[1]]
+        stale = []
+        for l in range(4):
+            if seen[prec][l] is not cur[l]:
+                old = list(cur)
+                old[l] = seen[prec][l]
+                stale.append((l, old))
+        seen[prec] = list(cur)
+        out.append((op, prec, list(cur), stale))
+    return out

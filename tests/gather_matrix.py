@@ -529,13 +529,13 @@ COVERED_ELSEWHERE = {
     "fill_table_kernel": "tests/test_gpu_gather.py::test_fill_kernels_match_oracle_content",
     "fill_weights_kernel": "tests/test_gpu_scores.py::test_scores_within_tolerance",
     "pack_weights_q4_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
-    "pack_weights_q8_bf16_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
-    "pack_weights_q16_fp8_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
+    "pack_weights_q8_bf16_kernel": "tests/test_gpu_exact_chain.py::test_exact_wide_weights",
+    "pack_weights_q16_fp8_kernel": "tests/test_gpu_exact_chain.py::test_exact_wide_weights",
     "pack_weights_q16h_fp8_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
     "transpose_records_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
     "records_to_q8_bf16_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
     "records_to_q16_fp8_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
-    "stats_kernel": "tests/test_gpu_exact_chain.py::test_exact_case",
+    "stats_kernel": "tests/test_gpu_exact_chain.py::test_fp8_weight_exponent_from_the_weights",
     "convert_rows_lp_kernel<1>": "tests/test_gpu_gather_matrix.py::test_operand_image_rounding_exhaustive",
     "convert_rows_lp_kernel<2>": "tests/test_gpu_gather_matrix.py::test_operand_image_rounding_exhaustive",
     "q4_to_lp_kernel<1>": "tests/test_gpu_sharded.py::test_table_sharded_mode_single_device_emulation",

@@ -3,7 +3,9 @@ GPU matrix, the CPU back-end matches the exact reference bit for bit, the exact 
 max-norm tolerances let through, and every FC-chain kernel compiled into libfleetrec.so is either named by a GPU-matrix case or listed
 as unreachable.  For the shape sweep (exact_chain.SWEEPS: each kernel at the edges of the range its dispatch predicate accepts) the same
 premise and witnesses per row, the CPU back-end on every fp32 row, per edge a simulated bug that must change a score of every row that
-targets the edge, hashes that pin the existing matrix's data, and the printed coverage table."""
+targets the edge, hashes that pin the existing matrix's data, and the printed coverage table.  For the master-weight side
+(exact_chain.WIDE, W_EXP_MAXIMA, REFRESH_OPS): premise, hidden-layer and weight witnesses per row, the pack / Wout-form / exponent / stale-image
+mutants, and the fp32 steps of the refresh sequence on the CPU back-end."""
 import os
 import shutil
 import sys
@@ -416,3 +418,188 @@ def test_demangle():
     assert E.demangle("_Z18fr_pipeline_kernelILin1ELi2EEv10FrPipeArgs") == "fr_pipeline_kernel<-1, 2>"
     assert E.demangle("_Z20fr_fused_tile_kernelILi2ELi44ELi2ELb1EEv11FrFusedArgs") == "fr_fused_tile_kernel<2, 44, 2, true>"
     assert E.demangle("void fr_pipeline_kernel<-1, 0>(FrPipeArgs)") == "fr_pipeline_kernel<-1, 0>"
+
+
+# ---- the master-weight side (exact_chain.WIDE, the exponent maxima, the refresh sequence) --------------------------------------------------
+
+def _wide_exps(row, rec, ws):
+    return (E.act_exponents(rec, ws), E.w_exponents(ws)) if row["prec"] == "fp8" else (None, None)
+
+
+def test_wide_table_is_well_formed():
+    ids = [r["id"] for r in E.WIDE]
+    assert len(set(ids)) == len(ids) and not set(ids) & ({c["id"] for c in E.CASES} | {r["id"] for r in E.SWEEPS})
+    shapes = {(c["prec"], E.MODELS[c["model"]][0], E.MODELS[c["model"]][1], c["batch"], c.get("width") or 1, c["group"]) for c in E.CASES}
+    shapes |= {(r["prec"], r["spec"][0], r["spec"][1], r["batch"], r["width"], r["group"]) for r in E.SWEEPS}
+    for r in E.WIDE:   # every row sits on the shape of an existing case or sweep row (a gather | out row: that of test_exact_gather_out_launch)
+        assert (r["prec"], r["spec"][0], r["spec"][1], r["batch"], r["width"], r["group"]) in shapes, r["id"]
+        assert r["prec"] in ("bf16", "fp8") and r["reader"]
+    for prec in ("bf16", "fp8"):   # one row per precision for each distinct reader of a weight image
+        readers = {r["kernel"] or r["layer"] for r in E.WIDE if r["prec"] == prec and not r["wout"]}
+        p = E._PI[prec]
+        assert {E.PPN % p, E.OUT % p, "fr_gather_out_kernel<%d>" % p, "stages", E.LP % (p, 1, 128, 2)} <= readers, readers
+    assert {r["layer"] for r in E.WIDE if r["wout"]} == {"stream", "OUT", "FC3", "gather_out"}   # each output-layer implementation once
+
+
+def test_preimage_pools_round_as_stated():
+    """Every bf16 preimage rounds to its target, the values just outside the intervals do not; the e4m3 pool rounds as its comments say;
+    the restated images agree with the reference's conversions."""
+    for a, vals in E.BF16_PREIMAGES.items():
+        v = np.array(vals, np.float32)
+        assert (bf16_round(v) == 256.0 * a).all() and (bf16_round(-v) == -256.0 * a).all()
+        assert bf16_round(np.nextafter(v[:1], np.float32(0)))[0] < 256.0 * a < bf16_round(np.nextafter(v[-1:], np.float32(1e9)))[0]
+        assert len(vals) == 7 and len(set(vals)) == 7
+    pool = np.array(E.FP8_POOL, np.float32)
+    img = E.e4m3_image(pool * np.float32(16.0)) / 16.0
+    assert img.tolist() == [16, 20, 20, 24, 24, 28, 16, 20, 20, 24, 28, 16, 16, 24, 28, 0]
+    x = np.concatenate([np.random.default_rng(3).normal(0, 60, 4000), pool * 16, -pool, [0.0, 448.0, 449.0, -1e9, 2.0 ** -10, 3 * 2.0 ** -10]]).astype(np.float32)
+    assert np.array_equal(E.e4m3_image(x), e4m3_decode_table()[e4m3_encode(x)])
+    assert np.array_equal(E.bf16_image(x), bf16_round(x))
+    for (top, s), want in zip(E.FP8_LAYERS, (3, 6, 7)):
+        assert E.floor_log2_f32(np.float32(448.0) / np.float32(top * 2.0 ** s)) == want
+
+
+@pytest.mark.parametrize("row", E.WIDE, ids=[r["id"] for r in E.WIDE])
+def test_premise_holds_for_every_wide_row(fr, row):
+    """Premise, hidden-layer witnesses as for the matrix, and per wide layer weights that are inexact, tie downward, tie upward and carry.
+    bf16: the images are the stock images times a power of two, so the scores are the stock scores (the premise is inherited)."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 256))
+    ws, stock, prec = data["ws"], data["stock"], row["prec"]
+    ae, we = _wide_exps(row, rec, ws)
+    for l in range(4):
+        assert ((ws[l] != 0) == (stock[l] != 0)).all()
+    if prec == "fp8" and not row["wout"]:
+        assert we == [3, 6, 7]
+        assert E.exponent_margin(E.act_exponent_quotients(rec, ws)) > 1e-3
+    elif prec == "fp8":
+        assert we == [7, 7, 7]
+    E.premise(prec, rec, ws, ae, we)
+    for l, (inexact, ties) in enumerate(E.rounding_witnesses(prec, rec, ws, ae, we)):
+        assert inexact > 0 and ties > 0, (row["id"], l, inexact, ties)
+    for l in row["wide"]:
+        if prec == "fp8" and l == 3:   # the fp32 master: nine significant bits, so its bf16 image is another vector
+            assert (E.bf16_image(ws[3])[ws[3] != 0] != ws[3][ws[3] != 0]).all()
+        else:
+            assert min(E.weight_witnesses(prec, l, ws[l], we)) > 0, (row["id"], l, E.weight_witnesses(prec, l, ws[l], we))
+    s = E.expected(prec, rec, ws, ae, we)
+    assert np.isfinite(s).all() and np.unique(s).size > s.size // 4
+    if prec == "bf16":
+        for l in range(4):
+            assert np.array_equal(bf16_round(ws[l]), stock[l] * np.float32(2.0 ** (8 + E.BF16_SCALES[l])))
+        assert np.array_equal(s, E.expected("bf16", rec, stock) * np.float32(2.0 ** (32 + sum(E.BF16_SCALES))))
+
+
+def _image_chain(prec, rec, ws, ae, we, image=None, wout=None):
+    """The chain with layer l's weight operand image(l) (None: the device's, exact_chain.weight_image) and the output layer's wout."""
+    image = image or (lambda l: E.weight_image(prec, l, ws[l], we))
+    Ws = [image(l) for l in range(3)] + [wout if wout is not None else image(3)]
+    if prec == "fp8":
+        dec = e4m3_decode_table()
+        x = dec[e4m3_encode(np.asarray(rec, np.float32) * np.float32(2.0 ** ae[0]))]
+        for l in range(3):
+            r = ((x @ Ws[l]) * 2.0 ** -(ae[l] + we[l])).astype(np.float32) * np.float32(2.0 ** ae[l + 1])
+            x = dec[e4m3_encode(r)]
+        return ((x * 2.0 ** -ae[3]) @ Ws[3]).astype(np.float32).ravel()
+    x = bf16_round(np.asarray(rec, np.float32)).astype(np.float64)
+    for l in range(3):
+        x = bf16_round((x @ Ws[l]).astype(np.float32)).astype(np.float64)
+    return (x @ Ws[3]).astype(np.float32).ravel()
+
+
+def weight_mutants(row, ws, we):
+    """The simulated bugs of the master-weight side that a WIDE row targets: name -> (image hook, wout) of _image_chain."""
+    prec, out = row["prec"], {}
+    if row["wout"]:
+        return {"fp8 chain with a bf16 Wout": (None, E.bf16_image(ws[3]).astype(np.float64))}
+    for l in row["wide"]:
+        def one(fn, l=l):
+            return lambda k: fn(k) if k == l else E.weight_image(prec, k, ws[k], we)
+        scaled = (lambda k: ws[k].astype(np.float64) * 2.0 ** we[k]) if prec == "fp8" else (lambda k: ws[k].astype(np.float64))
+        out["%s pack truncates (layer %d)" % (prec, l)] = (one(lambda k: E.weight_image(prec, k, ws[k], we, "trunc")), None)
+        out["%s pack rounds half away (layer %d)" % (prec, l)] = (one(lambda k: E.weight_image(prec, k, ws[k], we, "away")), None)
+        out["layer %d reads the fp32 master instead of its %s image" % (l, prec)] = (one(scaled), None)
+    if prec == "bf16":
+        out["bf16 chain with an fp32 Wout"] = (None, ws[3].astype(np.float64))
+    return out
+
+
+@pytest.mark.parametrize("row", E.WIDE, ids=[r["id"] for r in E.WIDE])
+def test_wide_row_rejects_its_weight_mutants(fr, row):
+    """Truncation, round-half-away and master-instead-of-image in each wide layer, and the other form of Wout, each change a score of
+    the row (the count is printed: the mutant table of the change's description); the unmutated restatement is the reference."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 256))
+    ws, prec = data["ws"], row["prec"]
+    ae, we = _wide_exps(row, rec, ws)
+    want = E.expected(prec, rec, ws, ae, we)
+    assert np.array_equal(_image_chain(prec, rec, ws, ae, we), want)
+    mutants = weight_mutants(row, ws, we)
+    assert len(mutants) == (1 if row["wout"] else 13 if prec == "bf16" else 9)
+    for name, (image, wout) in mutants.items():
+        bad = _image_chain(prec, rec, ws, ae, we, image, wout)
+        err = float(np.nanmax(np.abs(bad.astype(np.float64) - want)) / np.abs(want).max())
+        print("weight mutant %-32s %-58s items changed %4d of %d  max-norm err %.2e  old tolerance %.0e" % (
+            row["id"], name, int((bad != want).sum()), want.size, err, E.OLD_TOL[prec]))
+        assert not np.array_equal(bad, want), (row["id"], name)
+
+
+def test_weight_exponent_restatement_and_its_mutants():
+    """E.w_exponent against the exponents worked out by hand (max * 2^e in (224, 448]) for every maximum and placement of the GPU test;
+    `max without abs` changes the exponent of every negative placement, `NaN drives the max` that of every layer with a NaN
+    whose exponent is not 0, which is what the mutant gives (the GPU test's NaN layers have exponents 6, 7, 8)."""
+    stock = E.make_data(E.spec(*E.TINY), 611, n_pool=8)["ws"]
+    for name, m_val, by_hand in E.W_EXP_MAXIMA:
+        assert 224.0 < float(m_val) * 2.0 ** by_hand <= 448.0, name
+        for l in range(3):
+            for place in E.W_EXP_PLACES:
+                W, pos = E.layer_with_maximum(stock[l], m_val, place)
+                assert E.w_exponent(W) == by_hand, (name, l, place)
+                assert (E.w_exponent(W, use_abs=False) != by_hand) == (place == "negative"), (name, l, place)
+                V = W.ravel().copy()
+                V[pos + 1 if pos + 1 < V.size else pos - 1] = np.nan
+                assert E.w_exponent(V) == by_hand and (E.w_exponent(V, skip_nan=False) != by_hand) == (by_hand != 0), (name, l, place)
+    assert E.w_exponent(np.zeros(64, np.float32)) == 0
+    for seed, scale in ((611, 1.0), (612, 0.37), (613, 5.0)):   # the uncalibrated estimates the GPU test reads back: clear of a binade edge
+        d = E.make_data(E.spec(*E.TINY), seed, n_pool=8)
+        assert E.exponent_margin(E.estimated_act_exponents([w * np.float32(scale) for w in d["ws"]], d["fc"])[1]) >= 0.01
+
+
+@pytest.mark.parametrize("shape", list(E.REFRESH_SHAPES))
+def test_refresh_sequence_on_the_host_and_the_cpu_back_end(fr, shape):
+    """Every step of exact_chain.REFRESH_OPS on the host: the premise holds, the expected scores differ from the previous step's and from
+    those of every stale-image mutant.  The fp32 steps then run on the CPU back-end, on a worker that lives through all of them and on a
+    fresh one per step."""
+    s = E.REFRESH_SHAPES[shape]
+    sp, dA, sets = E.refresh_data(shape)
+    m = fr.Model.from_spec(sp)
+    idx = dA["idx"][:s["batch"]]
+    rec = E.records(m, dA, idx, None)
+    prev, ae, n_stale = None, None, 0
+    for op, prec, ws, stale in E.refresh_steps(sets):
+        we = E.w_exponents(ws) if prec == "fp8" else None
+        if prec == "fp8" and op[0] == "prec":
+            ae = E.act_exponents(rec, ws)
+        E.premise(prec, rec, ws, ae, we)
+        want = E.expected(prec, rec, ws, ae, we)
+        assert prev is None or not np.array_equal(want, prev), op
+        for l, old in stale:
+            assert not np.array_equal(E.expected(prec, rec, old, ae, E.w_exponents(old)), want), (op, l)
+            n_stale += 1
+        prev = want
+    assert n_stale >= 12
+    ctx = fr.Context(m, device=fr.DEVICE_CPU)
+    try:
+        E.load(ctx, dA)
+        live = fr.Worker(ctx, s["batch"])
+        prev = None
+        for op, prec, ws, stale in E.refresh_steps(sets, precs=("f32",)):
+            if op[0] == "set":
+                ctx.set_weights(op[1], ws[op[1]].ravel())
+            want = E.expected("f32", rec, ws)
+            assert op[0] == "prec" or not np.array_equal(want, prev), op   # (back to fp32 from fp32: the one step that changes nothing here)
+            fresh = fr.Worker(ctx, s["batch"])
+            assert np.array_equal(live.infer(idx, None), want) and np.array_equal(fresh.infer(idx, None), want), op
+            fresh.close()
+            prev = want
+        live.close()
+    finally:
+        ctx.close()

@@ -1,6 +1,8 @@
 """GPU parity on integer-valued data (tests/exact_chain.py): every FC-chain kernel, through every entry point, bit for bit against the host's
 exact restatement of the chain -- no tolerance.  Each case of exact_chain.CASES also pins the kernel the dispatcher picks for it; each
-row of exact_chain.SWEEPS runs one kernel at an edge of the shapes its dispatch predicate accepts (test_exact_sweep)."""
+row of exact_chain.SWEEPS runs one kernel at an edge of the shapes its dispatch predicate accepts (test_exact_sweep).  The master-weight side
+(end of the module): each reader of a weight image on weights that must round (exact_chain.WIDE), the fp8 exponents taken from the weights,
+and a sequence of set_weights / set_fc_precision calls that must each leave every derived image fresh."""
 import numpy as np
 import pytest
 
@@ -264,4 +266,245 @@ def test_exact_fp8_extremes(fr, gpu, case, shift):
         assert np.isnan(got[B:]).all(), "the push wrote past the batch"
     finally:
         wk.close()
+        ctx.close()
+
+
+# ---- the master-weight side: weights that must round, exponents taken from the weights, every refresh of a derived image --------------------
+
+def _unique_items(idx, dense):
+    """(first occurrence, inverse) of a batch's distinct items: a batch is drawn from a pool of 256, the host reference runs once per item."""
+    key = idx if dense is None else np.hstack([idx, np.ascontiguousarray(dense, np.float32).view(np.int32)])
+    _, first, inv = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    return first, np.asarray(inv).ravel()
+
+
+def _pushes(fr, ctx, wk, B, idx, dense, want, n_push, what=""):
+    ldm = (B + 31) // 32 * 32
+    d_i = fr.DeviceBuffer.from_numpy(ctx, np.ascontiguousarray(idx))
+    d_d = fr.DeviceBuffer.from_numpy(ctx, np.ascontiguousarray(dense)) if dense is not None else None
+    outs = []
+    for _ in range(n_push):
+        o = fr.DeviceBuffer(ctx, ldm * 4)
+        o.upload(np.full(ldm, np.nan, np.float32))
+        wk.push_device(B, d_i, d_d, o)
+        outs.append(o)
+    wk.sync()
+    name = wk.last_kernel()
+    for j, o in enumerate(outs):
+        got = o.download(np.float32, ldm)
+        _same(got[:B], want, "%spush %d of %d" % (what, j, n_push))
+        assert np.isnan(got[B:]).all(), "%spush %d of %d wrote past the batch" % (what, j, n_push)
+        o.free()
+    d_i.free()
+    if d_d is not None:
+        d_d.free()
+    return name
+
+
+@pytest.mark.parametrize("row", E.WIDE, ids=[r["id"] for r in E.WIDE])
+def test_exact_wide_weights(fr, gpu, row):
+    """A reader of a weight image (exact_chain.WIDE) on weights that the pack kernels must round -- ties to even in both directions, carries,
+    near-ties, a flush to zero; per-layer fp8 exponents 3 / 6 / 7 -- or, in the fp8 chain's output layer, on an fp32 Wout that no bf16
+    image holds.  Run like a sweep row: one infer, then one push, the row's stream group of pushes (a streamed kernel) or five pushes in
+    flight (gather | out) into NaN-filled buffers: every item bit-exact, nothing written past the batch, the named kernel ran."""
+    m, ctx, data, idx, dense, rec = _setup(fr, gpu, row)
+    B, ws, prec = row["batch"], data["ws"], row["prec"]
+    first, inv = _unique_items(idx, dense)
+    wk = fr.Worker(ctx, B)
+    try:
+        if prec == "fp8" and not row["wout"]:   # the calibration's fp32 chain sums these weights inexactly: its maxima must not sit on a binade edge
+            assert E.exponent_margin(E.act_exponent_quotients(rec[first], ws)) > 1e-3
+        want_u, ae, we = _expect(row, ctx, wk, idx, dense, rec[first], ws)
+        for l in row["wide"]:
+            if not (prec == "fp8" and l == 3):
+                assert min(E.weight_witnesses(prec, l, ws[l], we)) > 0, (l, E.weight_witnesses(prec, l, ws[l], we))
+        if prec == "fp8" and not row["wout"]:
+            assert len(set(we)) == 3, we
+        want = want_u[inv]
+        _same(wk.infer(idx, dense), want, "infer")
+        ctx.set_stream_group(row["group"])
+        layer = row["layer"]
+        name = _pushes(fr, ctx, wk, B, idx, dense, want, row["group"] if layer == "stream" else 5 if layer == "gather_out" else 1)
+        if layer == "stream":
+            assert name == row["kernel"], name
+        elif layer == "stages":
+            for l in range(4):
+                wk.fc_layer_only(B, l)
+                name = wk.last_kernel()
+                wk.sync()
+                assert name == E.PIPE % (l + 1, E._PI[prec]), (l, name)
+        elif layer != "gather_out":
+            wk.fc_layer_only(B, ("FC1", "FC2", "FC3", "OUT").index(layer))
+            name = wk.last_kernel()
+            wk.sync()
+            assert name == row["kernel"], name
+    finally:
+        wk.close()
+        ctx.close()
+
+
+def _tiny(fr, gpu, seed=611):
+    K, fc = E.TINY
+    sp = E.spec(K, fc, name="tiny_exponents")
+    data = E.make_data(sp, seed, n_pool=64, table_max=12)
+    m = fr.Model.from_spec(sp)
+    return m, fr.Context(m, device=gpu), data
+
+
+@pytest.mark.parametrize("mx", E.W_EXP_MAXIMA, ids=[t[0] for t in E.W_EXP_MAXIMA])
+def test_fp8_weight_exponent_from_the_weights(fr, gpu, mx):
+    """set_weights in fp8 mode: w_exp[l] = floor_log2(448 / max|W_l|) for a maximum on and beside the edges of (224, 448], at a power-of-two
+    quotient, on a tie, far out in the float range -- at the first element, at the last, and as a negative value, in every layer."""
+    _, m_val, by_hand = mx
+    m, ctx, data = _tiny(fr, gpu)
+    try:
+        ctx.set_fc_precision(fr.FC_FP8)
+        for l in range(3):
+            for place in E.W_EXP_PLACES:
+                W, _ = E.layer_with_maximum(data["ws"][l], m_val, place)
+                assert E.w_exponent(W) == by_hand
+                ctx.set_weights(l, W.ravel())
+                assert ctx.fp8_exponents()[1][l] == by_hand, (l, place, ctx.fp8_exponents()[1], by_hand)
+    finally:
+        ctx.close()
+
+
+def test_fp8_weight_exponent_zero_layer_and_grid_stride_tail(fr, gpu):
+    """An all-zero layer gives w_exp = 0.  One layer of Model-C size (3968 x 2048: stats_kernel's grid-stride loop runs 31 times) with its
+    maximum, a negative one, among the last 256 elements."""
+    m, ctx, data = _tiny(fr, gpu)
+    try:
+        ctx.set_fc_precision(fr.FC_FP8)
+        ctx.set_weights(1, data["ws"][1].ravel())
+        assert ctx.fp8_exponents()[1][1] == 7
+        ctx.set_weights(1, np.zeros(data["ws"][1].size, np.float32))
+        assert ctx.fp8_exponents()[1][1] == 0
+    finally:
+        ctx.close()
+    K, fc, dl = E.MODELS["C"]
+    mC = fr.Model.from_spec(E.spec(K, fc, dense_len=dl, name="exponent_C"))
+    ctx = fr.Context(mC, device=gpu)
+    try:
+        ctx.set_fc_precision(fr.FC_FP8)
+        rng = np.random.default_rng(77)
+        W = rng.integers(-2, 3, size=K * fc[0]).astype(np.float32)
+        for pos in (W.size - 1, W.size - 200):
+            V = W.copy()
+            V[pos] = -27.0
+            assert E.w_exponent(V) == 4 and E.w_exponent(V, use_abs=False) == 7
+            ctx.set_weights(0, V)
+            assert ctx.fp8_exponents()[1][0] == 4, (pos, ctx.fp8_exponents()[1])
+    finally:
+        ctx.close()
+
+
+def test_fp8_nan_weight_never_drives_the_scale(fr, gpu):
+    """A NaN right beside a layer's maximum: the layer's exponent is the one computed without it.  The output column that uses the weight
+    is NaN for every item (NaN x 0 is NaN), and the next layer sums every column, so every score is NaN; with the NaN taken out again
+    every score is back to its exact value."""
+    m, ctx, data = _tiny(fr, gpu)
+    idx, ws = data["idx"][:33], data["ws"]
+    rec = E.records(m, data, idx, None)
+    E.load(ctx, data)
+    ctx.set_fc_precision(fr.FC_FP8)
+    wk = fr.Worker(ctx, 33)
+    try:
+        wk.calibrate_fp8(idx, None)
+        ae, we = ctx.fp8_exponents()
+        assert we == E.w_exponents(ws) and ae == E.act_exponents(rec, ws)
+        E.premise("fp8", rec, ws, ae, we)
+        want = E.expected("fp8", rec, ws, ae, we)
+        _same(wk.infer(idx, None), want, "infer")
+        for l in range(3):
+            W = ws[l] * np.float32(1.0 if l == 1 else 0.5 ** l * 3.0)   # a different maximum, hence exponent, per layer
+            flat = W.ravel().copy()
+            pos = int(np.argmax(np.abs(flat)))
+            nan_at = pos + 1 if pos + 1 < flat.size else pos - 1
+            clean = E.w_exponent(flat)
+            flat[nan_at] = np.nan
+            assert E.w_exponent(flat) == clean and E.w_exponent(flat, skip_nan=False) != clean
+            ctx.set_weights(l, flat)
+            got_we = ctx.fp8_exponents()[1]
+            assert got_we[l] == clean, (l, got_we, clean)
+            assert ctx.fp8_exponents()[0] == ae          # calibrated activation exponents stay
+            assert np.isnan(wk.infer(idx, None)).all(), l
+            ctx.set_weights(l, ws[l].ravel())
+            assert ctx.fp8_exponents()[1] == we
+            _same(wk.infer(idx, None), want, "infer after the NaN left layer %d" % l)
+    finally:
+        wk.close()
+        ctx.close()
+
+
+def test_fp8_uncalibrated_activation_exponents(fr, gpu):
+    """Before any calibration the activation exponents are the host restatement of the rms estimate (0.58 at the input, times
+    sqrt(sum W^2 / H) per layer, 8 rms must fit 448) -- on weight sets whose quotients lie at least 1 % from a power of two, since the
+    device adds its block sums of squares with a float atomic, in no fixed order."""
+    for seed, scale in ((611, 1.0), (612, 0.37), (613, 5.0)):
+        m, ctx, data = _tiny(fr, gpu, seed)
+        try:
+            ws = [w * np.float32(scale) for w in data["ws"]]
+            want, quot = E.estimated_act_exponents(ws, data["fc"])
+            assert E.exponent_margin(quot) >= 0.01, (seed, scale, quot)
+            ctx.set_fc_precision(fr.FC_FP8)
+            for l in range(4):
+                ctx.set_weights(l, ws[l].ravel())
+            ae, we = ctx.fp8_exponents()
+            assert ae == want and we == E.w_exponents(ws), (seed, scale, ae, want, we)
+        finally:
+            ctx.close()
+
+
+@pytest.mark.parametrize("shape", list(E.REFRESH_SHAPES))
+def test_exact_refresh_sequence(fr, gpu, shape):
+    """exact_chain.REFRESH_OPS on one context: set_weights per layer after the precision was chosen, a precision switch after weights were
+    set in another precision, fp8 exponents that follow the weights while the calibrated activation exponents stay.  After every step a
+    worker that lives through the whole sequence and a fresh one both give the exact scores of the weights now in force (infer, and the
+    shape's stream group of pushes), and those differ from the previous step's, so that no stale image can pass."""
+    s = E.REFRESH_SHAPES[shape]
+    sp, dA, sets = E.refresh_data(shape)
+    B = s["batch"]
+    m = fr.Model.from_spec(sp)
+    ctx = fr.Context(m, device=gpu)
+    idx = dA["idx"][:B]
+    rec = E.records(m, dA, idx, None)
+    E.load(ctx, dA)
+    ctx.set_stream_group(s["group"])
+    live = fr.Worker(ctx, B)
+    prev, ae, calibrated = None, None, False
+    try:
+        for n, (op, prec, ws, stale) in enumerate(E.refresh_steps(sets)):
+            what = "step %d %s: " % (n, op)
+            before = ctx.fp8_exponents()
+            if op[0] == "prec":
+                ctx.set_fc_precision(_prec(fr, prec))
+            else:
+                ctx.set_weights(op[1], ws[op[1]].ravel())
+            we = None
+            if prec == "fp8":
+                we = E.w_exponents(ws)
+                assert ctx.fp8_exponents()[1] == we, (what, ctx.fp8_exponents(), we)
+                if op[0] == "prec":   # calibrate on entering fp8: the exponents of the weights now in force
+                    live.calibrate_fp8(idx, None)
+                    ae = E.act_exponents(rec, ws)
+                else:                  # set_weights(1, A * 8): w_exp[1] drops by 3, everything else stays
+                    assert we == [before[1][0], before[1][1] - 3, before[1][2]], (what, before, we)
+                assert ctx.fp8_exponents()[0] == ae, (what, ctx.fp8_exponents(), ae)
+            E.premise(prec, rec, ws, ae, we)
+            want = E.expected(prec, rec, ws, ae, we)
+            assert prev is None or not np.array_equal(want, prev), what
+            for l, old in stale:   # the scores a stale image of layer l would give are other scores
+                assert not np.array_equal(E.expected(prec, rec, old, ae, E.w_exponents(old)), want), (what, l)
+            fresh = fr.Worker(ctx, B)
+            try:
+                for who, wk in (("live worker ", live), ("fresh worker ", fresh)):
+                    _same(wk.infer(idx, None), want, what + who + "infer")
+                    name = _pushes(fr, ctx, wk, B, idx, None, want, s["group"], what + who)
+                    if shape == "fused":
+                        assert name.startswith("fr_fused_tile"), (what, name)
+            finally:
+                fresh.close()
+            prev = want
+    finally:
+        live.close()
         ctx.close()
