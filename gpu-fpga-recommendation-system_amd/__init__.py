@@ -31,6 +31,9 @@ EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step
 POOL_MAX_HOTS = 64   # FR_POOL_MAX_HOTS (fleetrec_serving.h): slots per bag of a pooled lookup
 TOPK_MAX_K = 256   # FR_TOPK_MAX_K (fleetrec_serving.h): the largest k of a top-K ranking
 REQ_ONE_HOT, REQ_POOLED, REQ_DENSE = 0, 1, 2   # FR_REQ_* (fleetrec_serving.h): the forms of a request-form expansion
+KEYS_ROWS, KEYS_HASHED, KEYS_MAPPED = 0, 1, 2   # FR_KEYS_*: the key space of an index column (Context.set_key_space)
+KEY_EMPTY, KEY_NO_ROW = -1, 0x7fffffff   # FR_KEY_EMPTY: the empty slot of a bag; FR_KEY_NO_ROW: the row of a key without one (out of range for every gather)
+KEY_ROWS_FULL, KEY_ROWS_REQUEST, KEY_ROWS_CANDIDATE = 0, 1, 2   # FR_KEY_ROWS_*: which rows Worker.resolve_keys_device resolves
 POOL_SUM, POOL_MEAN = 0, 1   # FR_POOL_SUM / FR_POOL_MEAN: the pooling mode of an index column (Context.set_pooling(hots, modes))
 ABI_VERSION = 6   # include/fleetrec.h FR_ABI_VERSION this binding was written against
 MEM_CLASS_NAMES = {0: "HBM", 1: "DDR", 2: "PLRAM"}
@@ -88,6 +91,8 @@ ABI_SYMBOLS = [
     "fr_worker_topk_device", "fr_worker_topk",
     "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
+    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
+    "fr_worker_submit_keyed", "fr_worker_key_misses",
 ]
 
 
@@ -101,7 +106,9 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
                    "fr_worker_topk_device", "fr_worker_topk",
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
-                   "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests")
+                   "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
+                   "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
+                   "fr_worker_submit_keyed", "fr_worker_key_misses")
 
 
 def lib():
@@ -189,6 +196,11 @@ def lib():
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
         "fr_worker_request_idx_ptr": (pi, [vp]), "fr_worker_request_weights_ptr": (pf, [vp]), "fr_worker_request_dense_ptr": (pf, [vp]),
         "fr_worker_request_offsets_ptr": (pi, [vp]), "fr_worker_submit_requests": (i32, [vp, i32, i32, i32]),
+        "fr_ctx_set_key_space": (i32, [vp, i32, i32, ctypes.c_uint64, i64, ctypes.c_int32]),
+        "fr_ctx_key_space": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32)]),
+        "fr_ctx_put_keys": (i32, [vp, i32, i32, vp, vp]), "fr_worker_put_keys": (i32, [vp, i32, i32, vp, vp]),
+        "fr_worker_resolve_keys_device": (i32, [vp, i32, i32, i32, vp, vp]), "fr_worker_key_ptr": (ctypes.POINTER(ctypes.c_int64), [vp]),
+        "fr_worker_submit_keyed": (i32, [vp, i32, i32]), "fr_worker_key_misses": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -679,6 +691,28 @@ class Context:
         r, c, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _check(lib().fr_ctx_request_words(self._h, int(form), ctypes.byref(r), ctypes.byref(c), ctypes.byref(w)))
         return r.value, c.value, w.value
+
+    def set_key_space(self, col, mode, seed=0, max_keys=0, miss_row=KEY_NO_ROW):
+        """fr_ctx_set_key_space: what a key of index column `col` means -- KEYS_ROWS (a key is a row), KEYS_HASHED (the hashing trick under `seed`) or
+        KEYS_MAPPED (an exact map in device memory, created EMPTY for up to max_keys keys; an absent key resolves to miss_row: a row of the column,
+        -1 = an empty bag slot, or KEY_NO_ROW = an index-range error at sync)."""
+        _check(lib().fr_ctx_set_key_space(self._h, int(col), int(mode), int(seed) & (2 ** 64 - 1), int(max_keys), int(miss_row)))
+
+    def key_space(self, col):
+        """-> (mode, seed, max_keys, n_keys, miss_row) of index column col (fr_ctx_key_space; synchronises the device)."""
+        mode, seed, mk, nk, miss = ctypes.c_int(), ctypes.c_uint64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        _check(lib().fr_ctx_key_space(self._h, int(col), ctypes.byref(mode), ctypes.byref(seed), ctypes.byref(mk), ctypes.byref(nk), ctypes.byref(miss)))
+        return mode.value, seed.value, mk.value, nk.value, miss.value
+
+    def put_keys(self, col, keys, rows):
+        """fr_ctx_put_keys: upsert the pairs (keys[i] int64, rows[i] int32) into the map of MAPPED column col; synchronous, legal beside workers in
+        flight.  A pair that cannot be applied (a key of -1, an illegal row, a new key for a full map) raises FleetRecError(FR_ERR_INDEX_RANGE); every
+        other pair is applied."""
+        k = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        if k.size != r.size:
+            raise FleetRecError(FR_ERR_INVALID, "%d keys, %d rows" % (k.size, r.size))
+        _check(lib().fr_ctx_put_keys(self._h, int(col), int(k.size), k.ctypes.data, r.ctypes.data))
 
     def synchronize(self):
         _check(lib().fr_device_synchronize(self._h))
@@ -1249,6 +1283,73 @@ class Worker:
         B, n_req, pooled, off = self._load_requests(req_idx, cand_idx, seg_offsets, req_dense, dense, req_weights, weights, pooled)
         self.submit_requests(B, n_req, pooled)
         return self._topk_host(B, k, off)
+
+    # keyed lookups (Context.set_key_space): int64 feature ids resolved to the int32 rows every lookup path takes, on the device ---------------------
+    def put_keys(self, col, n, d_keys, d_rows):
+        """fr_worker_put_keys: n pairs from device memory (d_keys int64, d_rows int32) into the map of MAPPED column col, asynchronous on the worker's
+        stream; both stay valid until sync(), which reports a pair that could not be applied as FR_ERR_INDEX_RANGE."""
+        _check(lib().fr_worker_put_keys(self._h, int(col), int(n), self._ptr(d_keys), self._ptr(d_rows)))
+
+    def resolve_keys_device(self, n_rows, d_keys, d_idx_out, rows_kind=KEY_ROWS_FULL, pooled=False):
+        """fr_worker_resolve_keys_device: d_keys int64 [n_rows][W] -> d_idx_out int32 [n_rows][W]; W follows rows_kind (KEY_ROWS_FULL: the index or
+        pooled row; KEY_ROWS_REQUEST / KEY_ROWS_CANDIDATE: the two sides of the request split) and pooled.  One launch on the worker's stream; a
+        following gather / submit / push / expand_requests_device on this worker reads the rows."""
+        _check(lib().fr_worker_resolve_keys_device(self._h, int(n_rows), int(rows_kind), int(bool(pooled)), self._ptr(d_keys), self._ptr(d_idx_out)))
+
+    def key_rows(self):
+        """-> flat int64 numpy view of the pinned key rows of the keyed host form (fr_worker_key_ptr): max_batch x max(index cols, pooled cols at
+        creation); None on a worker created before the context's first non-default key space."""
+        p = lib().fr_worker_key_ptr(self._h)
+        return np.ctypeslib.as_array(p, shape=(self.max_batch * self._pool_cap,)) if p else None
+
+    def submit_keyed(self, batch, pooled=0):
+        """fr_worker_submit_keyed on what key_rows() (and the dense / pool-weight buffers) hold; pooled: 0 one-hot, 1 pooled, 2 pooled weighted.
+        Asynchronous; follow with sync()."""
+        _check(lib().fr_worker_submit_keyed(self._h, int(batch), int(pooled)))
+
+    def key_misses(self, reset=True):
+        """MAPPED lookups of this worker that found no key since the last reset (fr_worker_key_misses; synchronises the worker's stream)."""
+        v = ctypes.c_uint64()
+        _check(lib().fr_worker_key_misses(self._h, ctypes.byref(v), int(bool(reset))))
+        return v.value
+
+    def _load_keys(self, keys, width, dense):
+        buf = self.key_rows()
+        if buf is None:
+            raise FleetRecError(FR_ERR_STATE, "the worker has no key buffer: create the worker after Context.set_key_space")
+        if width > self._pool_cap:
+            raise FleetRecError(FR_ERR_STATE, "the worker's key buffer holds %d columns per item, the key rows have %d: create the worker after Context.set_pooling" % (self._pool_cap, width))
+        k = np.ascontiguousarray(keys, dtype=np.int64)
+        B = len(k)
+        if B < 1 or B > self.max_batch or k.size != B * width:
+            raise FleetRecError(FR_ERR_INVALID, "key rows of shape %s: this call takes [1 .. %d][%d]" % (k.shape, self.max_batch, width))
+        buf[:k.size] = k.reshape(-1)
+        if dense is not None:
+            self.dense[:B] = dense
+        return B
+
+    def infer_keyed(self, keys, dense=None):
+        """Host-buffer path of a keyed one-hot batch: keys int64 [B][index cols] -> fp32 scores [B]."""
+        B = self._load_keys(keys, self.ctx.model.idx_cols, dense)
+        self.submit_keyed(B, 0)
+        self.sync()
+        return self.score[:B].copy()
+
+    def infer_pooled_keyed(self, keys, dense=None, weights=None):
+        """Host-buffer path of a keyed pooled batch: keys int64 [B][P] (-1 = empty slot), weights float32 [B][P] or None -> fp32 scores [B]."""
+        P = self.ctx.pooled_index_cols
+        B = self._load_keys(keys, P, dense)
+        if weights is not None:
+            pw = self.pool_weights
+            if pw is None:
+                raise FleetRecError(FR_ERR_STATE, "the worker has no weight buffer: create the worker after Context.set_pooling")
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.size != B * P:
+                raise FleetRecError(FR_ERR_INVALID, "per-sample weights are %s, the key rows [%d][%d]" % (w.shape, B, P))
+            pw.reshape(-1)[:B * P] = w.reshape(-1)
+        self.submit_keyed(B, 2 if weights is not None else 1)
+        self.sync()
+        return self.score[:B].copy()
 
     # convenience used by the parity tests --------------------------------------------------------
     def gather_records(self, idx, dense=None):

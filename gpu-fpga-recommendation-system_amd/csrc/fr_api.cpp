@@ -868,7 +868,7 @@ static int worker_build(fr_worker *w) {
         *w->h_err = 0;
         FR_HIP(hipHostGetDevicePointer((void **)&w->d_err, w->h_err, 0));
     }
-    if (!cpu || split) {
+    if (!cpu || split || ctx->keyed) {
         FR_TRY(w->d_idx.alloc(device, n_idx, "worker index rows (device)"));
         if (m.dense_len) FR_TRY(w->d_dense.alloc(device, n_dense, "worker dense rows (device)"));
     }
@@ -891,6 +891,7 @@ static int worker_build(fr_worker *w) {
         FR_TRY(w->h_req_off.alloc(pinned, B + 1, "worker request offsets"));
         if (w->pool_w_cap) FR_TRY(w->d_pool_w.alloc(device, n_pool_w, "worker expanded weights"));
     }
+    if (ctx->keyed) FR_TRY(w->h_keys.alloc(pinned, n_idx, "worker key rows"));   // keyed host form: read in place by the resolve
     if (!cpu) {
         FR_HIP(w->ev_start.create(hipEventDefault));
         FR_HIP(w->ev_stop.create(hipEventDefault));
@@ -2972,6 +2973,316 @@ extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int
     return FR_OK;
 }
 
+// ---- keyed lookups (fleetrec_serving.h) --------------------------------------------------------------------------------------------------------
+// The kernels are the third companion code object's (fr_keys.hip -> libfleetrec_keys.so, linked with an $ORIGIN rpath); slot layout, mix64 and the probe
+// rule are fr_keys.h's; key spaces, tables, order and the host form are here, the CPU twins in fr_cpu.cpp.
+static uint32_t key_col_range(const fr_ctx *c, int col) {   // R_c: the row count the one-hot gather checks for index column col (build_words)
+    const fr_model_desc &m = c->model;
+    if (m.index_mode == FR_INDEX_PER_TABLE) return (uint32_t)c->tables[(size_t)col].rows;
+    if (m.index_mode == FR_INDEX_PER_BANK) return (uint32_t)c->bank_rows[(size_t)col];
+    int64_t r = c->tables[0].rows;
+    for (const fr_table_desc &t : c->tables) r = t.rows < r ? t.rows : r;
+    return (uint32_t)r;
+}
+
+static int key_col_check(const fr_ctx *c, int col, const char *who) {
+    if (col < 0 || col >= (int)idx_cols(c)) FR_FAIL(FR_ERR_INVALID, "%s: column %d, the context has %zu index columns", who, col, idx_cols(c));
+    return FR_OK;
+}
+
+// the records of every column as a resolve reads them, from key_spaces: on the device (synchronous copy) or, on the CPU back-end, in place
+static int key_cols_upload(fr_ctx *c) {
+    const size_t C = idx_cols(c);
+    c->h_key_cols.resize(C);
+    for (size_t i = 0; i < C; i++) {
+        const fr_ctx::KeySpace &k = c->key_spaces[i];
+        FrKeyCol &r = c->h_key_cols[i];
+        r.seed = k.seed, r.slots = k.slots.p, r.mask = k.slots.p ? (uint32_t)(k.slots.count() - 1) : 0u;
+        r.range = key_col_range(c, (int)i), r.miss_row = k.miss_row, r.mode = k.mode;
+    }
+    if (c->cpu) return FR_OK;
+    FR_TRY(c->d_key_cols.grow(FrMem::DEVICE, C, "key-space records"));
+    FR_HIP(hipMemcpy(c->d_key_cols, c->h_key_cols.data(), C * sizeof(FrKeyCol), hipMemcpyHostToDevice));
+    return FR_OK;
+}
+
+// key spaces exist from the first call on: every column FR_KEYS_ROWS, the counts zero
+static int key_spaces_init(fr_ctx *c) {
+    if (!c->key_spaces.empty()) return FR_OK;
+    const size_t C = idx_cols(c);
+    FrBuf<uint32_t> counts;
+    FR_TRY(counts.alloc(fr_mem_kind(c, FrMem::DEVICE), C, "key counts"));
+    if (c->cpu) memset(counts.p, 0, C * sizeof(uint32_t));
+    else FR_HIP(hipMemset(counts.p, 0, C * sizeof(uint32_t)));
+    c->d_key_counts.swap(counts);
+    c->key_spaces.resize(C);
+    return key_cols_upload(c);
+}
+
+extern "C" int fr_ctx_set_key_space(fr_ctx *ctx, int col, int mode, uint64_t seed, int64_t max_keys, int32_t miss_row) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_col_check(ctx, col, "fr_ctx_set_key_space"));
+    if (mode < FR_KEYS_ROWS || mode > FR_KEYS_MAPPED) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_key_space: mode %d is none of FR_KEYS_ROWS, FR_KEYS_HASHED, FR_KEYS_MAPPED", mode);
+    const uint32_t range = key_col_range(ctx, col);
+    if (mode == FR_KEYS_MAPPED) {
+        if (max_keys < 1 || max_keys > (1ll << 30)) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_key_space: max_keys %lld outside [1, 2^30]", (long long)max_keys);
+        if (miss_row != -1 && miss_row != FR_KEY_NO_ROW && !(miss_row >= 0 && (uint32_t)miss_row < range))
+            FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_key_space: miss_row %d is neither a row of column %d (%u rows), nor -1, nor FR_KEY_NO_ROW", miss_row, col, range);
+    }
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_key_space: keyed lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    FR_TRY(pooling_busy(ctx, "fr_ctx_set_key_space"));
+    if (!ctx->cpu) FR_SET_DEVICE(ctx);
+    std::lock_guard<std::mutex> lk(ctx->key_mutex);   // (a first resolve on another thread makes the key spaces under the same lock)
+    FR_TRY(key_spaces_init(ctx));
+    fr_ctx::KeySpace next;
+    next.mode = mode, next.seed = mode == FR_KEYS_ROWS ? 0 : seed;
+    if (mode == FR_KEYS_MAPPED) {
+        next.max_keys = max_keys, next.miss_row = miss_row;
+        const uint64_t slots = fr_key_slots((uint64_t)max_keys);
+        FR_TRY(next.slots.alloc(fr_mem_kind(ctx, FrMem::DEVICE), (size_t)slots, "key map"));
+        FrKeyFillArgs f{next.slots.p, slots, miss_row};
+        if (ctx->cpu) {
+            frc_fill_keys(f);
+        } else {
+            const int e = fr_key_fill_launch(&f, (void *)ctx->setup_stream);
+            if (e) FR_FAIL(FR_ERR_HIP, "the key map's fill launch failed: %s", hipGetErrorString((hipError_t)e));
+            FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+        }
+    }
+    const uint32_t zero = 0;
+    if (ctx->cpu) ctx->d_key_counts[col] = 0;
+    else FR_HIP(hipMemcpy(ctx->d_key_counts + col, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    std::swap(ctx->key_spaces[(size_t)col], next);   // (no worker has work in flight: whatever map the column had is released with `next`)
+    if (mode != FR_KEYS_ROWS) ctx->keyed = true;
+    return key_cols_upload(ctx);
+}
+
+extern "C" int fr_ctx_key_space(fr_ctx *ctx, int col, int *mode, uint64_t *seed, int64_t *max_keys, int64_t *n_keys, int32_t *miss_row) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_col_check(ctx, col, "fr_ctx_key_space"));
+    const fr_ctx::KeySpace none{};
+    const fr_ctx::KeySpace &k = ctx->key_spaces.empty() ? none : ctx->key_spaces[(size_t)col];
+    uint32_t n = 0;
+    if (k.mode == FR_KEYS_MAPPED) {
+        if (ctx->cpu) {
+            n = __atomic_load_n(ctx->d_key_counts + col, __ATOMIC_ACQUIRE);
+        } else {
+            FR_SET_DEVICE(ctx);
+            FR_HIP(hipDeviceSynchronize());
+            FR_HIP(hipMemcpy(&n, ctx->d_key_counts + col, sizeof(n), hipMemcpyDeviceToHost));
+        }
+    }
+    if (mode) *mode = k.mode;
+    if (seed) *seed = k.seed;
+    if (max_keys) *max_keys = k.max_keys;
+    if (n_keys) *n_keys = (int64_t)n;
+    if (miss_row) *miss_row = k.miss_row;
+    return FR_OK;
+}
+
+static int key_put_check(fr_ctx *c, int col, int n, const void *keys, const void *rows, const char *who) {
+    FR_TRY(key_col_check(c, col, who));
+    if (n < 0) FR_FAIL(FR_ERR_INVALID, "%s: n = %d pairs", who, n);
+    if (n > 0 && (!keys || !rows)) FR_FAIL(FR_ERR_INVALID, "%s: keys / rows is NULL", who);
+    if (c->key_spaces.empty() || c->key_spaces[(size_t)col].mode != FR_KEYS_MAPPED)
+        FR_FAIL(FR_ERR_STATE, "%s: column %d has no map: call fr_ctx_set_key_space(ctx, %d, FR_KEYS_MAPPED, ...) first", who, col, col);
+    return FR_OK;
+}
+
+static FrKeyPutArgs key_put_args(fr_ctx *c, int col, int n, const int64_t *keys, const int32_t *rows, int *err) {
+    FrKeyPutArgs a{};
+    a.col = c->h_key_cols[(size_t)col], a.n_keys = c->d_key_counts + col, a.max_keys = (uint32_t)c->key_spaces[(size_t)col].max_keys;
+    a.n = n, a.keys = keys, a.rows = rows, a.err_flag = err;
+    return a;
+}
+
+// what fr_worker_sync (or fr_ctx_put_keys itself) says about the bits of a status word; bit 0 is the lookups'
+static int index_range_fail(int bits) {
+    const char *lookup = (bits & 1) ? "a lookup index was outside its table (row 0 was read instead)" : "";
+    if (!(bits & (FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_ROW | FR_KEYS_ERR_FULL))) FR_FAIL(FR_ERR_INDEX_RANGE, "%s", lookup);
+    FR_FAIL(FR_ERR_INDEX_RANGE, "%s%sa key put was not applied (every other pair was):%s%s%s", lookup, (bits & 1) ? "; " : "", (bits & FR_KEYS_ERR_EMPTY_KEY) ? " a key of -1 (FR_KEY_EMPTY);" : "",
+            (bits & FR_KEYS_ERR_ROW) ? " a row that is neither one of the column's rows nor its miss_row;" : "", (bits & FR_KEYS_ERR_FULL) ? " a new key for a map that holds max_keys keys;" : "");
+}
+
+extern "C" int fr_worker_put_keys(fr_worker *w, int col, int n, const int64_t *d_keys, const int32_t *d_rows) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    fr_ctx *c = w->ctx;
+    FR_TRY(key_put_check(c, col, n, d_keys, d_rows, "fr_worker_put_keys"));
+    if (n == 0) return FR_OK;
+    if ((uintptr_t)d_keys % 8 || (uintptr_t)d_rows % 4) FR_FAIL(FR_ERR_INVALID, "fr_worker_put_keys: d_keys must be 8-byte aligned, d_rows 4-byte aligned");
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then put");
+    if (c->cpu) {   // computed before the call returns, one writer at a time; what was not applied waits in c_err for fr_worker_sync
+        std::lock_guard<std::mutex> lk(c->lp_mutex);
+        const int bad = frc_put_keys(key_put_args(c, col, n, d_keys, d_rows, nullptr));
+        if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
+        return FR_OK;
+    }
+    FR_SET_DEVICE(c);
+    FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the put: whatever they read was resolved against the old map
+    const FrKeyPutArgs a = key_put_args(c, col, n, d_keys, d_rows, w->d_err);
+    const int e = fr_key_put_launch(&a, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the key put launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_put_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys, const int32_t *h_rows) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_put_check(ctx, col, n, h_keys, h_rows, "fr_ctx_put_keys"));
+    if (n == 0) return FR_OK;
+    if ((uintptr_t)h_keys % 8 || (uintptr_t)h_rows % 4) FR_FAIL(FR_ERR_INVALID, "fr_ctx_put_keys: h_keys must be 8-byte aligned, h_rows 4-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_update_rows's too
+    if (ctx->cpu) {
+        const int bad = frc_put_keys(key_put_args(ctx, col, n, h_keys, h_rows, nullptr));
+        return bad ? index_range_fail(bad) : FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    if (!ctx->h_up_err) {
+        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
+        *ctx->h_up_err = 0;
+        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
+    }
+    FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
+    FR_TRY(ctx->d_kp_rows.grow(FrMem::DEVICE, (size_t)n, "key-put rows"));
+    FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
+    FR_HIP(hipMemcpyAsync(ctx->d_kp_rows, h_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->setup_stream));
+    const FrKeyPutArgs a = key_put_args(ctx, col, n, ctx->d_kp_keys, ctx->d_kp_rows, ctx->d_up_err);
+    const int e = fr_key_put_launch(&a, (void *)ctx->setup_stream);
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    if (e) FR_FAIL(FR_ERR_HIP, "the key put launch failed: %s", hipGetErrorString((hipError_t)e));
+    const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
+    return bad ? index_range_fail(bad) : FR_OK;
+}
+
+// The word -> column tables of the six forms ([rows_kind][pooled]) for the pooling and the split as they stand, made again when either has changed
+// since they were made (both change only while no worker has work in flight, so no launch reads the tables being replaced).  Under key_mutex.
+static int key_tables_ensure(fr_ctx *c) {
+    if (c->key_tab_made && c->key_tab_hots == c->pool_hots && c->key_tab_shared == c->req_shared) return FR_OK;
+    const size_t C = idx_cols(c);
+    const bool pool = c->pool_cols > 0, split = !c->req_shared.empty();
+    std::vector<uint16_t> all;
+    fr_ctx::KeyTable tab[3][2];
+    for (int kind = FR_KEY_ROWS_FULL; kind <= FR_KEY_ROWS_CANDIDATE; kind++)
+        for (int pooled = 0; pooled < 2; pooled++) {
+            if ((pooled && !pool) || (kind != FR_KEY_ROWS_FULL && !split)) continue;
+            tab[kind][pooled].first = all.size();
+            for (size_t col = 0; col < C; col++) {
+                if (kind != FR_KEY_ROWS_FULL && (c->req_shared[col] != 0) != (kind == FR_KEY_ROWS_REQUEST)) continue;
+                all.insert(all.end(), pooled ? (size_t)c->pool_hots[col] : 1, (uint16_t)col);
+            }
+            tab[kind][pooled].words = (int)(all.size() - tab[kind][pooled].first);
+        }
+    FrBuf<uint16_t> d;
+    FR_TRY(d.alloc(fr_mem_kind(c, FrMem::DEVICE), all.size() ? all.size() : 1, "key word tables"));
+    if (c->cpu) memcpy(d.p, all.data(), all.size() * sizeof(uint16_t));
+    else if (!all.empty()) FR_HIP(hipMemcpy(d.p, all.data(), all.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    c->d_key_wcol.swap(d);
+    memcpy(c->key_tab, tab, sizeof(tab));
+    c->key_tab_hots = c->pool_hots, c->key_tab_shared = c->req_shared, c->key_tab_made = true;
+    return FR_OK;
+}
+
+// the one launch (the CPU back-end: the twin, computed here)
+static int key_resolve_enqueue(fr_worker *w, int n_rows, int rows_kind, int pooled, const int64_t *keys, int32_t *out, const char *who) {
+    fr_ctx *c = w->ctx;
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "%s: keyed lookups are not available on a sharded context (%d shards)", who, c->n_shards);
+    if (rows_kind != FR_KEY_ROWS_FULL && c->req_shared.empty()) FR_FAIL(FR_ERR_STATE, "%s: request and candidate rows need a split: call fr_ctx_set_request_columns first", who);
+    if (pooled && c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "%s: the pooled forms need pooling: call fr_ctx_set_pooling first", who);
+    if (!c->cpu) FR_SET_DEVICE(c);
+    FrKeyResolveArgs a{};
+    {
+        std::lock_guard<std::mutex> lk(c->key_mutex);
+        FR_TRY(key_spaces_init(c));
+        FR_TRY(key_tables_ensure(c));
+        const fr_ctx::KeyTable &t = c->key_tab[rows_kind][pooled];
+        a.W = t.words, a.wcol = c->d_key_wcol + t.first;
+    }
+    if (a.W <= 0) FR_FAIL(FR_ERR_STATE, "%s: the split leaves no word to this side of the form", who);
+    const uint64_t bound = (uint64_t)4000 << 20;
+    a.total = (uint64_t)n_rows * (uint64_t)a.W;
+    if (a.total * sizeof(int64_t) >= bound) FR_FAIL(FR_ERR_INVALID, "%s: %d rows of %d keys reach 4000 MiB", who, n_rows, a.W);
+    if (!w->d_key_miss) {   // the worker's first resolve
+        FR_TRY(w->d_key_miss.alloc(fr_mem_kind(c, FrMem::DEVICE), 1, "worker key misses"));
+        if (c->cpu) *w->d_key_miss = 0;
+        else FR_HIP(hipMemsetAsync(w->d_key_miss, 0, sizeof(unsigned long long), w->stream));   // in front of the launch, in stream order
+    }
+    a.keys = keys, a.out = out, a.misses = w->d_key_miss, a.n_cols = (int)idx_cols(c);
+    if (c->cpu) {
+        a.cols = c->h_key_cols.data();
+        frc_resolve_keys(a);
+        return FR_OK;
+    }
+    a.cols = c->d_key_cols, a.max_blocks = 8 * (c->n_cu > 0 ? c->n_cu : 256);
+    const int e = fr_key_resolve_launch(&a, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the key resolve launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_worker_resolve_keys_device(fr_worker *w, int n_rows, int rows_kind, int pooled, const int64_t *d_keys, int32_t *d_idx_out) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    if (rows_kind < FR_KEY_ROWS_FULL || rows_kind > FR_KEY_ROWS_CANDIDATE) FR_FAIL(FR_ERR_INVALID, "rows_kind %d is none of FR_KEY_ROWS_FULL, _REQUEST, _CANDIDATE", rows_kind);
+    if (pooled != 0 && pooled != 1) FR_FAIL(FR_ERR_INVALID, "pooled = %d is neither 0 nor 1", pooled);
+    const int most = rows_kind == FR_KEY_ROWS_REQUEST ? (1 << 24) : w->max_batch;
+    if (n_rows < 1 || n_rows > most) FR_FAIL(FR_ERR_INVALID, "n_rows = %d outside [1, %d]", n_rows, most);
+    if (!d_keys || !d_idx_out) FR_FAIL(FR_ERR_INVALID, "d_keys / d_idx_out is NULL");
+    if ((uintptr_t)d_keys % 8 || (uintptr_t)d_idx_out % 4) FR_FAIL(FR_ERR_INVALID, "d_keys must be 8-byte aligned, d_idx_out 4-byte aligned");
+    return key_resolve_enqueue(w, n_rows, rows_kind, pooled, d_keys, d_idx_out, "fr_worker_resolve_keys_device");
+}
+
+extern "C" int64_t *fr_worker_key_ptr(fr_worker *w) { return w ? w->h_keys.p : nullptr; }
+
+extern "C" int fr_worker_submit_keyed(fr_worker *w, int batch, int pooled) {
+    int rc = check_ready(w, batch, true, true);
+    if (rc) return rc;
+    if (pooled < 0 || pooled > 2) FR_FAIL(FR_ERR_INVALID, "pooled = %d: 0 one-hot, 1 pooled, 2 pooled weighted", pooled);
+    fr_ctx *c = w->ctx;
+    const bool weighted = pooled == 2;
+    if (!w->h_keys || !w->d_idx) FR_FAIL(FR_ERR_STATE, "the worker has no key buffer: create the worker after the context's first fr_ctx_set_key_space");
+    if (pooled) {
+        rc = pooled_host_ready(w, batch, weighted);
+        if (!rc && weighted) rc = fr_pooled_weights_need_sum(c);
+        if (rc) return rc;
+    } else if (w->in_flight) {
+        FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
+    }
+    if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_worker_submit_keyed: keyed lookups are not available on a sharded context (%d shards)", c->n_shards);
+    if (!c->cpu) FR_SET_DEVICE(c);
+    // the resolve reads the pinned keys in place and writes the worker's device index buffer; the unchanged submit runs behind it
+    rc = key_resolve_enqueue(w, batch, FR_KEY_ROWS_FULL, pooled ? 1 : 0, w->h_keys, w->d_idx, "fr_worker_submit_keyed");
+    if (rc) return rc;
+    const float *dense = c->model.dense_len ? w->h_dense.p : nullptr;
+    if (pooled) rc = submit_pooled_impl(w, weighted ? pooled_batch_weighted(batch, w->d_idx, w->h_pool_w, dense) : FrPooledBatch{batch, w->d_idx, nullptr, dense}, w->h_score);
+    else rc = launch_pipeline(w, batch, w->d_idx, dense, w->h_score);
+    if (rc) return rc;
+    w->in_flight = true, w->host_batch = batch;   // (fr_worker_topk ranks it)
+    return FR_OK;
+}
+
+extern "C" int fr_worker_key_misses(fr_worker *w, uint64_t *misses, int reset) {
+    if (!w || !misses) FR_FAIL(FR_ERR_INVALID, "NULL argument");
+    *misses = 0;
+    if (!w->d_key_miss) return FR_OK;   // the worker has resolved nothing yet
+    if (w->ctx->cpu) {
+        *misses = reset ? __atomic_exchange_n(w->d_key_miss.p, 0ull, __ATOMIC_ACQ_REL) : __atomic_load_n(w->d_key_miss.p, __ATOMIC_ACQUIRE);
+        return FR_OK;
+    }
+    FR_SET_DEVICE(w->ctx);
+    FR_HIP(hipStreamSynchronize(w->stream));
+    unsigned long long v = 0;
+    FR_HIP(hipMemcpy(&v, w->d_key_miss, sizeof(v), hipMemcpyDeviceToHost));
+    if (reset) {
+        FR_HIP(hipMemsetAsync(w->d_key_miss, 0, sizeof(v), w->stream));
+        FR_HIP(hipStreamSynchronize(w->stream));
+    }
+    *misses = (uint64_t)v;
+    return FR_OK;
+}
+
 // Launch what is queued -- the partially filled host block, the batches queued by fr_worker_push_device -- without waiting for it.
 extern "C" int fr_worker_flush(fr_worker *w) {
     if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
@@ -3032,8 +3343,8 @@ extern "C" int fr_worker_sync(fr_worker *w) {
         const int crc = fr_comm_wait(w);   // (bounded wait + the ranks' status words, fr_comm.cpp; FR_OK at once when no such step is in flight)
         w->in_flight = false;
         if (crc) return crc;
-        if (__atomic_exchange_n(&w->c_err, 0, __ATOMIC_ACQ_REL)) FR_FAIL(FR_ERR_INDEX_RANGE, "a lookup index was outside its table (row 0 was read instead)");
-        return FR_OK;
+        const int bits = __atomic_exchange_n(&w->c_err, 0, __ATOMIC_ACQ_REL);
+        return bits ? index_range_fail(bits) : FR_OK;
     }
     FR_SET_DEVICE(w->ctx);
     if (w->sh_comm && w->sh_host_stream) {
@@ -3063,11 +3374,8 @@ extern "C" int fr_worker_sync(fr_worker *w) {
         memcpy(w->tk_dst_idx, w->h_tk_idx, w->tk_count * sizeof(int32_t));
         if (w->tk_dst_sc) memcpy(w->tk_dst_sc, w->h_tk_sc, w->tk_count * sizeof(float));
     }
-    if (__atomic_load_n(w->h_err, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(w->h_err, 0, __ATOMIC_RELEASE);
-        FR_FAIL(FR_ERR_INDEX_RANGE, "a lookup index was outside its table (row 0 was read instead)");
-    }
-    return FR_OK;
+    const int bits = __atomic_exchange_n(w->h_err, 0, __ATOMIC_ACQ_REL);   // (bit 0: the lookups'; the others: a key put's, FR_KEYS_ERR_*)
+    return bits ? index_range_fail(bits) : FR_OK;
 }
 
 extern "C" int fr_worker_timer_start(fr_worker *w) {

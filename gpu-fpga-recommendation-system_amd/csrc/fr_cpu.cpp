@@ -559,3 +559,61 @@ int frc_expand_requests(const FrRequestArgs &a) {
     });
     return bad;
 }
+
+// ---- keyed lookups: the CPU twins of key_resolve_kernel, key_put_kernel and key_fill_kernel (fr_keys.hip) ---------------------------------------
+// The rows are fr_keys.h's own functions of the key, the column record and the map, so they are the device's bit for bit.
+void frc_resolve_keys(const FrKeyResolveArgs &a) {
+    const uint64_t unit = 4096;   // words per unit of work
+    std::atomic<unsigned long long> misses{0};
+    Pool::get().run((int)((a.total + unit - 1) / unit), [&](int u) {
+        const uint64_t e0 = (uint64_t)u * unit, e1 = e0 + unit < a.total ? e0 + unit : a.total;
+        unsigned long long mine = 0;
+        unsigned word = (unsigned)(e0 % (uint64_t)a.W);
+        for (uint64_t e = e0; e < e1; e++) {
+            bool miss = false;
+            a.out[e] = fr_key_resolve(a.cols[a.wcol[word]], a.keys[e], &miss);
+            mine += miss;
+            if (++word == (unsigned)a.W) word = 0;
+        }
+        if (mine) misses.fetch_add(mine, std::memory_order_relaxed);
+    });
+    if (a.misses) __atomic_fetch_add(a.misses, misses.load(), __ATOMIC_RELAXED);
+}
+
+int frc_put_keys(const FrKeyPutArgs &a) {
+    int bad = 0;
+    for (int i = 0; i < a.n; i++) {
+        const int64_t k = a.keys[i];
+        if (k == FR_KEYS_EMPTY_KEY) {
+            bad |= FR_KEYS_ERR_EMPTY_KEY;
+            continue;
+        }
+        if (!fr_key_row_legal(a.col.range, a.col.miss_row, a.rows[i])) {
+            bad |= FR_KEYS_ERR_ROW;
+            continue;
+        }
+        uint64_t h = fr_key_home(a.col, k);
+        bool found = false;
+        for (uint64_t left = (uint64_t)a.col.mask + 1; left && !found; left--) {
+            FrKeySlot *s = a.col.slots + h;
+            const int64_t cur = __atomic_load_n(&s->key, __ATOMIC_RELAXED);
+            if (cur == FR_KEYS_EMPTY_KEY) {
+                if (*a.n_keys >= a.max_keys) break;   // the map is full: nothing is claimed
+                ++*a.n_keys;
+                __atomic_store_n(&s->key, k, __ATOMIC_RELEASE);   // the key first (the slot still holds miss_row) ...
+                found = true;
+            } else if (cur == k) {
+                found = true;
+            } else {
+                h = (h + 1) & (uint64_t)a.col.mask;
+            }
+        }
+        if (found) __atomic_store_n(&a.col.slots[h].row, a.rows[i], __ATOMIC_RELEASE);   // ... the row second
+        else bad |= FR_KEYS_ERR_FULL;
+    }
+    return bad;
+}
+
+void frc_fill_keys(const FrKeyFillArgs &a) {
+    for (uint64_t i = 0; i < a.n; i++) a.slots[i] = FrKeySlot{FR_KEYS_EMPTY_KEY, a.miss_row, 0};
+}

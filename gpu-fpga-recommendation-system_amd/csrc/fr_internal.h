@@ -13,6 +13,7 @@
 #include "fleetrec.h"
 #include "fleetrec_diag.h"
 #include "fleetrec_serving.h"
+#include "fr_keys.h"
 #include "fr_mem.h"
 
 // ---- error plumbing ---------------------------------------------------------------------------
@@ -278,6 +279,37 @@ static inline int fr_request_tile(int W) {
 // Enqueues the one expansion launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
 extern "C" int fr_request_launch(const FrRequestArgs *args, void *stream);
 
+// ---- keyed lookups (fr_keys.hip -> libfleetrec_keys.so, the third companion code object; fr_cpu.cpp has the twins; fr_keys.h: slot, mix64, probe) ----
+constexpr int FR_KEY_PER_THREAD = 4;     // keys a thread of key_resolve_kernel resolves per chunk: their first probes are in flight together
+struct FrKeyResolveArgs {
+    const int64_t *keys;         // [total], 8-byte aligned
+    int32_t *out;                // [total]
+    const FrKeyCol *cols;        // [n_cols]
+    const uint16_t *wcol;        // [W]: the index column of every word of a row
+    unsigned long long *misses;  // the worker's counter of MAPPED lookups that found no key
+    uint64_t total;              // n_rows * W
+    int W, n_cols;
+    int max_blocks;              // workgroups the launch takes at most (they stride over the chunks of 256 x FR_KEY_PER_THREAD words)
+};
+struct FrKeyPutArgs {
+    FrKeyCol col;                // a MAPPED column
+    uint32_t *n_keys;            // the column's key count
+    uint32_t max_keys;
+    int n;
+    const int64_t *keys;         // [n]
+    const int32_t *rows;         // [n]
+    int *err_flag;               // FR_KEYS_ERR_* bits
+};
+struct FrKeyFillArgs {
+    FrKeySlot *slots;
+    uint64_t n;
+    int32_t miss_row;
+};
+// Each enqueues its one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_key_resolve_launch(const FrKeyResolveArgs *args, void *stream);
+extern "C" int fr_key_put_launch(const FrKeyPutArgs *args, void *stream);
+extern "C" int fr_key_fill_launch(const FrKeyFillArgs *args, void *stream);
+
 // ---- host objects -------------------------------------------------------------------------------
 // Where a table's rows live inside ctx->table_arena.  A table stored on its own: row r at byte_offset + r * dim * 4 (il_rows == 0).
 // FR_INDEX_PER_BANK contexts interleave the tables of one memory bank: rows [0, il_rows) of every table of the bank share one
@@ -365,6 +397,32 @@ struct fr_ctx {
         size_t d_first = 0;                // where the table starts inside d_req_desc
     } req_form[3];
     FrBuf<int32_t> d_req_desc;             // the three tables, one after the other
+    // Keyed lookups (fr_ctx_set_key_space): one key space per index column.  `keyed` turns true with the first non-default key space and stays: workers
+    // created from then on carry the pinned key rows of the host form.  The records and the word -> column tables a resolve reads live in device memory
+    // (plain host memory on the CPU back-end); the tables follow the pooling and the request split, so they are made again, under key_mutex, by the first
+    // resolve after either has changed (both change only while no worker has work in flight).
+    struct KeySpace {
+        int mode = 0;                      // FR_KEYS_ROWS
+        uint64_t seed = 0;
+        int64_t max_keys = 0;
+        int32_t miss_row = 0x7fffffff;
+        FrBuf<FrKeySlot> slots;            // MAPPED: the map
+    };
+    std::vector<KeySpace> key_spaces;      // [index columns]; empty until the first fr_ctx_set_key_space
+    bool keyed = false;
+    std::vector<FrKeyCol> h_key_cols;      // [index columns]: what d_key_cols holds
+    FrBuf<FrKeyCol> d_key_cols;
+    FrBuf<uint32_t> d_key_counts;          // [index columns]: keys in every map
+    std::mutex key_mutex;                  // guards the creation of the key spaces (key_spaces_init) and the tables below; the CPU back-end's puts take lp_mutex
+    struct KeyTable {
+        size_t first = 0;                  // inside d_key_wcol
+        int words = 0;                     // W; 0: the form is not available (no split, no pooling)
+    } key_tab[3][2];                       // [rows_kind][pooled]
+    FrBuf<uint16_t> d_key_wcol;
+    std::vector<int32_t> key_tab_hots, key_tab_shared;   // the pooling and the split the tables were made for
+    bool key_tab_made = false;
+    FrBuf<int64_t> d_kp_keys;              // staging of fr_ctx_put_keys (grown on demand, used under lp_mutex on the set-up stream)
+    FrBuf<int32_t> d_kp_rows;
     std::mutex workers_mutex;              // guards `workers`
     std::vector<struct fr_worker *> workers;   // live workers (fr_ctx_set_pooling asks each whether it has work in flight)
     FrBuf<unsigned long long> d_merged;    // lookups merged by the dedup gather (FR_GATHER_ITEM_TILE_DEDUP_COUNT)
@@ -423,6 +481,10 @@ struct fr_worker {
     FrBuf<int32_t> h_req_off;        // [max_batch + 1]
     int req_idx_cap = 0, req_w_cap = 0;   // request words per request at creation: max(Rs, Rs') and Rs'
     FrBuf<float> d_pool_w;           // [max_batch][pool_w_cap]: the expanded per-sample weights (host memory on the CPU back-end)
+    // Keyed lookups: the pinned key rows of the host form (fr_worker_key_ptr), there on a worker created after the context's first non-default key space;
+    // the counter of MAPPED lookups that found no key (device memory; made by the worker's first resolve)
+    FrBuf<int64_t> h_keys;           // [max_batch][idx_cap]
+    FrBuf<unsigned long long> d_key_miss;
     // CPU back-end: a call computes before it returns; an index-range error stays in c_err until fr_worker_sync reports it
     FrBuf<float> c_scratch;      // [max_batch][H1 + H2 + H3]
     FrBuf<float> c_x;            // records of the sharded FC entry points, [max_batch][K]
@@ -551,6 +613,12 @@ int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, in
 int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int k, int32_t *top_idx, float *top_scores);
 // the CPU twin of fr_request_launch: the same words, items over the pool's threads; -> 1 when the offsets were malformed, else 0
 int frc_expand_requests(const FrRequestArgs &a);
+// the CPU twins of fr_key_resolve_launch (words over the pool's threads), fr_key_put_launch (pair after pair, ONE writer at a time -- the callers hold
+// fr_ctx::lp_mutex; readers need no lock: the key is published before the row --: of a key listed twice the last row stays;
+// -> the FR_KEYS_ERR_* bits of the pairs that were not applied) and fr_key_fill_launch
+void frc_resolve_keys(const FrKeyResolveArgs &a);
+int frc_put_keys(const FrKeyPutArgs &a);
+void frc_fill_keys(const FrKeyFillArgs &a);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \

@@ -1,0 +1,107 @@
+// Keyed lookups (fleetrec_serving.h, "Keyed lookups"): ONE definition of the slot layout, of mix64 and of the probe rule, included by the kernels
+// (fr_keys.hip -> libfleetrec_keys.so, the third companion code object), by the CPU back-end (fr_cpu.cpp) and, through fr_internal.h, by the host
+// side.  Everything here is plain data or an inline function; nothing is a symbol of any library.
+#pragma once
+
+#include <cstdint>
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define FR_KEYS_HD static inline __host__ __device__
+#else
+#define FR_KEYS_HD static inline
+#endif
+
+constexpr int64_t FR_KEYS_EMPTY_KEY = -1;           // FR_KEY_EMPTY: the empty slot of a bag, and the key of an empty map slot; never a map key
+constexpr int32_t FR_KEYS_NO_ROW = 0x7fffffff;      // FR_KEY_NO_ROW: out of range for every gather
+constexpr int FR_KEYS_MODE_ROWS = 0, FR_KEYS_MODE_HASHED = 1, FR_KEYS_MODE_MAPPED = 2;   // FR_KEYS_ROWS / _HASHED / _MAPPED
+constexpr int FR_KEYS_LDS_WORDS = 2048;             // words of the word -> column table a workgroup stages in LDS (4 KiB); a longer row: read in place
+constexpr int FR_KEYS_LDS_COLS = 384;               // column records a workgroup of key_resolve_kernel stages in LDS (12 KiB); more: read in place
+// what a put raises in the status word it is given (bit 0 stays the lookups' own "index outside its table")
+constexpr int FR_KEYS_ERR_EMPTY_KEY = 2, FR_KEYS_ERR_ROW = 4, FR_KEYS_ERR_FULL = 8;
+
+struct FrKeySlot {   // 16 bytes, 16-byte aligned: one probe is one load
+    int64_t key;     // FR_KEYS_EMPTY_KEY: nobody has claimed the slot
+    int32_t row;     // an empty slot holds the column's miss_row, so a reader that sees a key claimed and its row not yet stored reads "unknown"
+    int32_t pad;
+};
+
+struct FrKeyCol {    // 32 bytes: what a resolve needs of one index column
+    uint64_t seed;
+    FrKeySlot *slots;    // MAPPED: the map (device memory; host memory on the CPU back-end); NULL otherwise
+    uint32_t mask;       // slots - 1, slots a power of two <= 2^31
+    uint32_t range;      // R_c: the row count the one-hot gather checks for the column
+    int32_t miss_row;
+    int32_t mode;
+};
+
+// the splitmix64 finaliser: mix64(5) = 13168350753275463132, mix64(4) = 13232826040865663252
+FR_KEYS_HD uint64_t fr_mix64(uint64_t z) {
+    z ^= z >> 30;
+    z *= 0xbf58476d1ce4e5b9ull;
+    z ^= z >> 27;
+    z *= 0x94d049bb133111ebull;
+    z ^= z >> 31;
+    return z;
+}
+
+// the smallest power of two >= 2 * max_keys (max_keys in 1 .. 2^30): the load of a map never exceeds 0.5, so a probe chain always ends
+FR_KEYS_HD uint64_t fr_key_slots(uint64_t max_keys) {
+    uint64_t s = 2;
+    while (s < 2 * max_keys) s <<= 1;
+    return s;
+}
+
+FR_KEYS_HD uint64_t fr_key_home(const FrKeyCol &c, int64_t k) { return fr_mix64((uint64_t)k ^ c.seed) & (uint64_t)c.mask; }
+
+// The modes without a table, and the empty key of every mode.  -> true: *row is the answer; false: the key has to be looked up in the column's map.
+FR_KEYS_HD bool fr_key_direct(const FrKeyCol &c, int64_t k, int32_t *row) {
+    if (k == FR_KEYS_EMPTY_KEY) {
+        *row = -1;
+        return true;
+    }
+    if (c.mode == FR_KEYS_MODE_MAPPED) return false;
+    if (c.mode == FR_KEYS_MODE_HASHED) *row = (int32_t)(uint32_t)(((fr_mix64((uint64_t)k ^ c.seed) >> 32) * (uint64_t)c.range) >> 32);   // < range <= 2^31 - 1
+    else *row = (uint64_t)k < 0x7fffffffull ? (int32_t)k : FR_KEYS_NO_ROW;
+    return true;
+}
+
+// One probe: the slot as ONE 16-byte load on the device (a reader sees a claimed key with either its old or its new row, never half a slot); the
+// CPU back-end reads the key, then the row.
+FR_KEYS_HD FrKeySlot fr_key_load_slot(const FrKeySlot *p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int4 v = *reinterpret_cast<const int4 *>(p);
+    FrKeySlot s;
+    s.key = (int64_t)(((uint64_t)(uint32_t)v.y << 32) | (uint64_t)(uint32_t)v.x), s.row = v.z, s.pad = 0;
+    return s;
+#else
+    FrKeySlot s;
+    s.key = __atomic_load_n(&p->key, __ATOMIC_ACQUIRE), s.row = __atomic_load_n(&p->row, __ATOMIC_RELAXED), s.pad = 0;
+    return s;
+#endif
+}
+
+// The probe rule: from the home slot h (whose content `s` the caller has loaded already) linearly, wrapping, until the key or an empty slot is
+// found.  At most `slots` probes WHATEVER the memory holds: a corrupt map may give a wrong row, it cannot spin.  *miss: no slot holds the key.
+FR_KEYS_HD int32_t fr_key_probe(const FrKeyCol &c, int64_t k, uint64_t h, FrKeySlot s, bool *miss) {
+    *miss = false;
+    for (uint64_t left = (uint64_t)c.mask;; left--) {   // the slot in hand + mask more = slots probes
+        if (s.key == k) return s.row;
+        if (s.key == FR_KEYS_EMPTY_KEY || left == 0) break;
+        h = (h + 1) & (uint64_t)c.mask;
+        s = fr_key_load_slot(c.slots + h);
+    }
+    *miss = true;
+    return c.miss_row;
+}
+
+// a whole lookup (the CPU back-end; the kernel issues its first probes early and finishes with fr_key_probe)
+FR_KEYS_HD int32_t fr_key_resolve(const FrKeyCol &c, int64_t k, bool *miss) {
+    int32_t row;
+    *miss = false;
+    if (fr_key_direct(c, k, &row)) return row;
+    const uint64_t h = fr_key_home(c, k);
+    return fr_key_probe(c, k, h, fr_key_load_slot(c.slots + h), miss);
+}
+
+// a row a put may store: one of the column's rows, or the column's own miss_row (which "forgets" the key)
+FR_KEYS_HD bool fr_key_row_legal(uint32_t range, int32_t miss_row, int32_t row) { return row == miss_row || (row >= 0 && (uint32_t)row < range); }

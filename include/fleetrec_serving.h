@@ -345,6 +345,82 @@ float *fr_worker_request_dense_ptr(fr_worker *w);      /* pinned float [max_batc
 int32_t *fr_worker_request_offsets_ptr(fr_worker *w);  /* pinned int32 [max_batch + 1] */
 int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int pooled /* 0 one-hot, 1 pooled, 2 pooled weighted */);
 
+/* Keyed lookups (additive in ABI 6): the id -> row step in front of every lookup path.  Every entry point above takes int32 ROW NUMBERS; a serving host
+ * holds 64-bit feature ids (hashed strings, item ids, user ids).  With a KEY SPACE set on an index column, one small launch turns int64 keys into the
+ * int32 rows every existing path takes; nothing downstream changes.
+ * Key spaces: every index column c < fr_model_index_cols(model) -- a table, a bank or the single per-item column -- has one.  R_c is the row count the
+ *   one-hot gather checks for the column.
+ *     FR_KEYS_ROWS (the default)  a key IS a row number: 0 <= k < 2^31 - 1 -> (int32) k; any other key -> FR_KEY_NO_ROW.
+ *     FR_KEYS_HASHED              the hashing trick, no table and no state: row = (uint32) ((((mix64((uint64) k ^ seed)) >> 32) * (uint64) R_c) >> 32).
+ *     FR_KEYS_MAPPED              an exact map in device memory: a present key -> its row, an absent key -> the column's miss_row.
+ *   mix64 is the splitmix64 finaliser: z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31
+ *   (mix64(5) = 13168350753275463132, mix64(4) = 13232826040865663252).
+ *   FR_KEY_EMPTY (-1) is the empty slot of a pooled bag: it resolves to -1 in every mode and is never a map key.  FR_KEY_NO_ROW (0x7fffffff) is the row a
+ *   key without a row becomes; every gather reports it as out of range, as it always has.  miss_row is a row in [0, R_c) (a shared "unknown" row), -1
+ *   (an unknown id in a bag is an empty slot) or FR_KEY_NO_ROW (an unknown id is an index-range error at fr_worker_sync).
+ * fr_ctx_set_key_space: MAPPED creates an EMPTY map for up to max_keys keys: slots = the smallest power of two >= 2 * max_keys (the load never exceeds
+ *   0.5) of 16 bytes each, {int64 key; int32 row; int32 pad}; an empty slot holds key -1 and row miss_row; the home slot of a key is
+ *   mix64(k ^ seed) & (slots - 1), probing is linear.  seed is the HASHED hash's and the MAPPED home slot's; max_keys and miss_row are read for MAPPED
+ *   only.  Setting a column again replaces its key space (a MAPPED one starts empty again); ROWS drops it.
+ *   FR_ERR_OOM: the map does not fit.  FR_ERR_INVALID: a column or mode out of range; for MAPPED a miss_row that is none of the three kinds, max_keys
+ *   outside 1 .. 2^30.  FR_ERR_STATE: a worker of the context has work in flight (the rule of fr_ctx_set_pooling), a context with n_shards > 1.
+ *   Key spaces belong to index columns: they survive fr_ctx_set_pooling / fr_ctx_set_pooling_modes / fr_ctx_set_request_columns.
+ * fr_ctx_key_space reads one back (any output pointer may be NULL; n_keys: the keys in the map, 0 unless MAPPED); it synchronises the device, as
+ *   fr_ctx_gather_merged_lookups does.
+ * Writing a map: n pairs (keys[i], rows[i]) of ONE MAPPED column.  A put is an UPSERT: a present key gets the new row, an absent key is inserted.
+ *   Legal rows are [0, R_c) and the column's own miss_row; putting miss_row "forgets" a key (it keeps its slot and resolves like an unknown one; it still
+ *   counts in n_keys and is no miss for fr_worker_key_misses).  Not applied, and reported: a pair whose key is -1, a pair whose row is not legal, a NEW
+ *   key when n_keys == max_keys -- every other pair of the call is still applied.  A key listed twice in one call ends up with one of its listed rows,
+ *   which one is unspecified (the CPU back-end: the last); when such a key is new and takes the map's LAST place, its other occurrences may be reported
+ *   as finding the map full.
+ *   fr_worker_put_keys: device pointers (host pointers on the CPU back-end, which computes before it returns), asynchronous on the worker's stream;
+ *   d_keys (8-byte aligned) and d_rows (4-byte aligned; FR_ERR_INVALID otherwise, in the host form too) stay valid until fr_worker_sync(w) has returned.  A pair that is not applied raises the worker's sticky word:
+ *   FR_ERR_INDEX_RANGE at fr_worker_sync, fr_last_error() saying which of the three it was; the worker is usable afterwards.
+ *   fr_ctx_put_keys: the host form -- host arrays, synchronous on the context's set-up stream, legal beside workers in flight; returns FR_ERR_INDEX_RANGE itself.
+ *   Arguments (the rules of fr_worker_update_rows): n == 0 is FR_OK and does nothing; n < 0, a NULL pointer with n > 0, a column out of range:
+ *   FR_ERR_INVALID; a column that is not MAPPED: FR_ERR_STATE.
+ *   Order (the rules of fr_worker_update_rows): on one worker, keys resolved BEFORE the call see the old map, keys resolved AFTER it the new one; batches
+ *   fr_worker_push_device has queued for a fused launch are launched first (not waited for); host-fed batches still queued in a block make the call
+ *   FR_ERR_STATE (flush first).  Across workers there is no order until fr_worker_sync(w) has returned; a resolve in flight on another worker meanwhile
+ *   yields, per key, the old row (miss_row if the key was absent) or the new row, never anything else: the key is claimed first (one 64-bit
+ *   compare-and-swap), the row stored second, and an empty slot is pre-filled with miss_row.
+ * fr_worker_resolve_keys_device: d_keys int64 [n_rows][W] (8-byte aligned, nothing more) -> d_idx_out int32 [n_rows][W].  W and the word -> column map:
+ *     FR_KEY_ROWS_FULL        the rows fr_worker_submit_device (pooled = 0: W = C) / fr_worker_submit_pooled_device (pooled = 1: W = P) take; n_rows <= max_batch
+ *     FR_KEY_ROWS_REQUEST     the request rows of fr_worker_expand_requests_device (FR_REQ_ONE_HOT: W = Rs / FR_REQ_POOLED: W = Rs'); n_rows <= 2^24
+ *     FR_KEY_ROWS_CANDIDATE   its candidate rows (W = Rc / Rc'); n_rows <= max_batch
+ *   (the widths of fr_ctx_request_words).  It enqueues ONE launch and nothing else -- the rule of fr_worker_expand_requests_device: queued fused batches are not
+ *   flushed, the stage pipeline is not drained.  (The first resolve after the pooling or the split has changed uploads the word -> column tables first.)  A following
+ *   fr_worker_gather_only, submit*_device, push*_device or fr_worker_expand_requests_device ON THE SAME WORKER with d_idx_out among its inputs reads the resolved
+ *   rows: no new push entry point is needed; the buffer-lifetime rule of fr_worker_push_device applies.  No byte outside d_keys[0 .. n_rows x W), the maps and
+ *   d_idx_out[0 .. n_rows x W) is read or written.  The CPU back-end computes before it returns, the same rows bit for bit.
+ *   FR_ERR_INVALID: a NULL worker or pointer, an unknown rows_kind, pooled other than 0 / 1, n_rows outside its range, a key or row array reaching 4000 MiB.
+ *   FR_ERR_STATE: REQUEST / CANDIDATE rows without a split, the pooled forms without pooling, a form of zero words, a context with n_shards > 1.
+ * Host form: fr_worker_key_ptr is pinned int64 [max_batch][max(C, P)] (host memory on the CPU back-end), there on a worker created AFTER the context's first
+ *   non-default key space, NULL before; fr_worker_submit_keyed runs the resolve over the pinned keys ([batch][C] or [batch][P]) in place into the worker's
+ *   device index buffer and then the unchanged chain of fr_worker_submit_device / fr_worker_submit_pooled[_weighted]_device with the pinned score buffer as
+ *   destination (dense rows in fr_worker_dense_ptr, weights in fr_worker_pool_weights_ptr, as for the plain host forms).  It counts as the host-form batch in
+ *   flight: fr_worker_topk ranks it.  FR_ERR_STATE: a worker without the key buffer, and every state the plain host forms refuse.
+ * fr_worker_key_misses: the MAPPED lookups of this worker that found no slot holding their key, since the worker was created or the counter was last reset;
+ *   it synchronises the worker's stream (nothing is flushed).  The counter lives in device memory; a wave adds to it once, not a lane.
+ * Out of scope: flat key arrays for the offsets (CSR) form; keyed forms of fr_worker_push_host and fr_worker_submit_requests; the TCP wire format of
+ *   fleetrec_server; sharded contexts; erasing slots and growing a map. */
+#define FR_KEYS_ROWS   0
+#define FR_KEYS_HASHED 1
+#define FR_KEYS_MAPPED 2
+#define FR_KEY_EMPTY  (-1)
+#define FR_KEY_NO_ROW 0x7fffffff
+#define FR_KEY_ROWS_FULL      0
+#define FR_KEY_ROWS_REQUEST   1
+#define FR_KEY_ROWS_CANDIDATE 2
+int fr_ctx_set_key_space(fr_ctx *ctx, int col, int mode, uint64_t seed, int64_t max_keys, int32_t miss_row);
+int fr_ctx_key_space(fr_ctx *ctx, int col, int *mode, uint64_t *seed, int64_t *max_keys, int64_t *n_keys, int32_t *miss_row);
+int fr_ctx_put_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys, const int32_t *h_rows);
+int fr_worker_put_keys(fr_worker *w, int col, int n, const int64_t *d_keys, const int32_t *d_rows);
+int fr_worker_resolve_keys_device(fr_worker *w, int n_rows, int rows_kind, int pooled, const int64_t *d_keys, int32_t *d_idx_out);
+int64_t *fr_worker_key_ptr(fr_worker *w);
+int fr_worker_submit_keyed(fr_worker *w, int batch, int pooled /* 0 one-hot, 1 pooled, 2 pooled weighted */);
+int fr_worker_key_misses(fr_worker *w, uint64_t *misses, int reset);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
