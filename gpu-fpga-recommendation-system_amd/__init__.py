@@ -23,6 +23,8 @@ MODEL_A, MODEL_B, MODEL_C = 0, 1, 2
 FILL_EVEN_ODD, FILL_HASH, FILL_TAGGED = 0, 1, 2
 WEIGHTS_ONES, WEIGHTS_UNIFORM = 0, 1
 FC_FP32, FC_BF16, FC_FP8 = 0, 1, 2
+ACT_NONE, ACT_RELU = 0, 1   # fr_ctx_set_epilogue (fleetrec_serving.h)
+_ACTS = {"none": ACT_NONE, "relu": ACT_RELU}
 LAYOUT_SEMANTIC, LAYOUT_BLOCKED = 0, 1
 INDEX_PER_TABLE, INDEX_PER_ITEM, INDEX_PER_BANK = 0, 1, 2
 SEG_TABLE, SEG_COPY, SEG_DENSE = 0, 1, 2
@@ -93,6 +95,7 @@ ABI_SYMBOLS = [
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
     "fr_worker_submit_keyed", "fr_worker_key_misses",
+    "fr_ctx_set_epilogue", "fr_ctx_epilogue",
 ]
 
 
@@ -108,7 +111,8 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
-                   "fr_worker_submit_keyed", "fr_worker_key_misses")
+                   "fr_worker_submit_keyed", "fr_worker_key_misses",
+                   "fr_ctx_set_epilogue", "fr_ctx_epilogue")
 
 
 def lib():
@@ -201,6 +205,7 @@ def lib():
         "fr_ctx_put_keys": (i32, [vp, i32, i32, vp, vp]), "fr_worker_put_keys": (i32, [vp, i32, i32, vp, vp]),
         "fr_worker_resolve_keys_device": (i32, [vp, i32, i32, i32, vp, vp]), "fr_worker_key_ptr": (ctypes.POINTER(ctypes.c_int64), [vp]),
         "fr_worker_submit_keyed": (i32, [vp, i32, i32]), "fr_worker_key_misses": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), i32]),
+        "fr_ctx_set_epilogue": (i32, [vp, i32, vp, sz, i32]), "fr_ctx_epilogue": (i32, [vp, i32, vp, sz, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -588,6 +593,28 @@ class Context:
         w = np.empty(fc[layer] * fc[layer + 1], dtype=np.float32)
         _check(lib().fr_ctx_get_weights(self._h, layer, w.ctypes.data_as(ctypes.c_void_p), w.size))
         return w
+
+    def set_epilogue(self, layer, bias=None, act="none"):
+        """fleetrec_serving.h fr_ctx_set_epilogue: layer 0..3 computes act(W x + bias).  bias: fc[layer + 1] float32 values or None; act: "none" / "relu"
+        (or ACT_NONE / ACT_RELU); the output layer (3) takes "none" only.  (None, "none") restores the layer as it was."""
+        a = _ACTS.get(act, act) if isinstance(act, str) else act
+        if isinstance(a, str):
+            raise FleetRecError(FR_ERR_INVALID, "unknown activation %r (\"none\", \"relu\")" % (act,))
+        if bias is None:
+            _check(lib().fr_ctx_set_epilogue(self._h, layer, None, 0, int(a)))
+            return
+        b = np.ascontiguousarray(bias, dtype=np.float32).ravel()
+        _check(lib().fr_ctx_set_epilogue(self._h, layer, b.ctypes.data_as(ctypes.c_void_p), b.size, int(a)))
+
+    def epilogue(self, layer):
+        """-> (bias float32 [fc[layer + 1]] or None, "none" / "relu") as set by set_epilogue."""
+        hb, act = ctypes.c_int(0), ctypes.c_int(0)
+        _check(lib().fr_ctx_epilogue(self._h, layer, None, 0, ctypes.byref(hb), ctypes.byref(act)))
+        b = None
+        if hb.value:
+            b = np.empty(self.model.fc[layer + 1], dtype=np.float32)
+            _check(lib().fr_ctx_epilogue(self._h, layer, b.ctypes.data_as(ctypes.c_void_p), b.size, None, None))
+        return b, {v: k for k, v in _ACTS.items()}[act.value]
 
     def set_fc_precision(self, precision):
         _check(lib().fr_ctx_set_fc_precision(self._h, precision))

@@ -694,6 +694,58 @@ extern "C" int fr_ctx_set_weights(fr_ctx *ctx, int layer, const float *w, size_t
     return FR_OK;
 }
 
+// ---- per-layer epilogue (fleetrec_serving.h) ------------------------------------------------------------------------------------------
+// The bias stays fp32 in every chain (never rounded to bf16 / e4m3) and is read by the kernels that finish the layer; nothing derived is kept, so the
+// fp8 exponents, the weight images, the chain width and the stream group are as they were.  Same rules as fr_ctx_set_weights: no launch in flight.
+extern "C" int fr_ctx_set_epilogue(fr_ctx *ctx, int layer, const float *bias, size_t count, int act) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (layer < 0 || layer > 3) FR_FAIL(FR_ERR_INVALID, "layer %d out of range", layer);
+    if (act != FR_ACT_NONE && act != FR_ACT_RELU) FR_FAIL(FR_ERR_INVALID, "unknown activation %d (FR_ACT_NONE, FR_ACT_RELU)", act);
+    if (layer == 3 && act != FR_ACT_NONE) FR_FAIL(FR_ERR_INVALID, "the output layer takes FR_ACT_NONE only (a monotone transform does not change a ranking)");
+    const size_t n = (size_t)ctx->model.fc[layer + 1];
+    if (bias ? count != n : count != 0) FR_FAIL(FR_ERR_INVALID, "layer %d expects %zu bias values (or NULL and 0), got %zu", layer, n, count);
+    if (!ctx->cpu && !ctx->d_negzero) {
+        FR_SET_DEVICE(ctx);
+        size_t widest = 4;
+        for (int l = 1; l <= 4; l++) widest = std::max(widest, (size_t)ctx->model.fc[l]);
+        const std::vector<float> nz(widest, -0.0f);
+        FrBuf<float> fresh;   // taken by the context only once it is filled: a failed copy leaves no buffer of undefined contents behind
+        FR_TRY(fresh.alloc(FrMem::DEVICE, widest, "epilogue zeros"));
+        FR_HIP(hipMemcpy(fresh, nz.data(), widest * sizeof(float), hipMemcpyHostToDevice));
+        ctx->d_negzero = std::move(fresh);
+    }
+    if (bias) {
+        FR_TRY(ctx->d_bias[layer].grow(fr_mem_kind(ctx, FrMem::DEVICE), n, "layer bias"));
+        if (ctx->cpu) {
+            memcpy(ctx->d_bias[layer], bias, n * sizeof(float));
+        } else {
+            FR_SET_DEVICE(ctx);
+            FR_HIP(hipMemcpy(ctx->d_bias[layer], bias, n * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    ctx->has_bias[layer] = bias != nullptr;
+    ctx->act[layer] = act;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_epilogue(fr_ctx *ctx, int layer, float *bias_out, size_t count, int *has_bias, int *act) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (layer < 0 || layer > 3) FR_FAIL(FR_ERR_INVALID, "layer %d out of range", layer);
+    const size_t n = (size_t)ctx->model.fc[layer + 1];
+    if (bias_out && count != n) FR_FAIL(FR_ERR_INVALID, "layer %d holds %zu bias values, got %zu", layer, n, count);
+    if (has_bias) *has_bias = ctx->has_bias[layer] ? 1 : 0;
+    if (act) *act = ctx->act[layer];
+    if (bias_out && ctx->has_bias[layer]) {
+        if (ctx->cpu) {
+            memcpy(bias_out, ctx->d_bias[layer], n * sizeof(float));
+        } else {
+            FR_SET_DEVICE(ctx);
+            FR_HIP(hipMemcpy(bias_out, ctx->d_bias[layer], n * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }
+    return FR_OK;
+}
+
 extern "C" int fr_ctx_fill_weights(fr_ctx *ctx, int mode, uint32_t seed) {
     if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
     if (mode != FR_WEIGHTS_ONES && mode != FR_WEIGHTS_UNIFORM) FR_FAIL(FR_ERR_INVALID, "bad weight mode %d", mode);
@@ -1331,9 +1383,16 @@ static int pipeline_step(fr_worker *w) {
                 st.in = rd.r3; st.in_part_stride = (int)rd.p3; st.out = sl.d_scores; st.w = wl[3];
                 break;
         }
+        // the context's epilogues (fr_ctx_set_epilogue): a stage that stores whole sums applies its own layer's; a split stage stores raw partials and
+        // the stage that combines them (nparts_in == 2) applies the producing layer's to their sum -- one fp32 add after the WHOLE K sum either way
+        if (s >= 1) {
+            if (st.nsplit == 1) a.epi[s] = c->epi(s - 1);
+            if (s >= 2 && st.nparts_in == 2) a.epi_in[s] = c->epi(s - 2);
+            a.has_epi = c->any_epi() ? 1 : 0;
+        }
         if (s == 3 && st.nparts_in == 1 && st.nsplit == 1 && !w->calibrating && frk_fc_lp_gemm_ok(prec, st.K, st.N, ldm) && frk_fc_tail_ok(prec, st.K, st.N, ldm)) {
             // large batch, bf16 / fp8: FC3 and the output layer of this batch in ONE launch (fc_tail_kernel); the batch leaves the pipeline here
-            int rc = frk_fc_tail(prec, st.w, st.in, wl[3], sl.d_scores, st.K, st.N, ldm, sl.batch, st.e_w, st.e_in, st.e_out, w->stream);
+            int rc = frk_fc_tail(prec, st.w, st.in, wl[3], sl.d_scores, st.K, st.N, ldm, sl.batch, st.e_w, st.e_in, st.e_out, a.epi[s], c->epi(3), w->stream);
             if (rc) return rc;
             st.batch = 0;
             sl.active = false;
@@ -1346,7 +1405,7 @@ static int pipeline_step(fr_worker *w) {
             long heaviest = 0;
             for (int l = 0; l < 3; l++) heaviest = std::max(heaviest, (long)fc[l] * fc[l + 1]);
             const bool minor = 2 * (long)st.K * st.N <= heaviest;
-            int rc = frk_fc_lp_gemm(prec, st.w, st.in, st.out, st.K, st.N, ldm, st.e_w, st.e_in, st.e_out, prec == FR_FC_FP32 ? 1 : chain_width(c, !w->diag_launch), minor, w->stream);
+            int rc = frk_fc_lp_gemm(prec, st.w, st.in, st.out, st.K, st.N, ldm, st.e_w, st.e_in, st.e_out, prec == FR_FC_FP32 ? 1 : chain_width(c, !w->diag_launch), minor, a.epi[s], w->stream);
             if (rc) return rc;
             st.batch = 0;  // inactive in the combined launch
             continue;
@@ -1412,7 +1471,8 @@ static bool fused_eligible(const fr_ctx *c) {
     if (c->fc_precision == FR_FC_FP8) return frk_fused_f8_ok(fc[0], fc[1], fc[2], fc[3]);
     // bf16: the chunked kernel exists for the two reference records (352 / 880 floats); any other record the K-outer persistent kernel
     // accepts (64 .. 880 floats in whole k-groups, frk_fused_hk_ok) streams through that kernel at every launch size
-    if (c->fc_precision == FR_FC_BF16) return frk_fused_h_ok(fc[0], fc[1], fc[2], fc[3]) || c->hk_ok == 1;
+    // (... unless the context has an epilogue, which that kernel does not carry: see fused_flush)
+    if (c->fc_precision == FR_FC_BF16) return frk_fused_h_ok(fc[0], fc[1], fc[2], fc[3]) || (c->hk_ok == 1 && !c->any_epi());
     return frk_fused_ok(fc[0], fc[1], fc[2], fc[3]);
 }
 
@@ -1489,6 +1549,8 @@ static int fused_flush(fr_worker *w) {
         a.w3q = reinterpret_cast<const float4 *>(c->d_wq[2].p);
         a.wout = c->d_w[3];
     }
+    if (c->any_epi())   // the epilogue forms of the fused kernels are branch-free: a layer without a bias adds -0.0f
+        for (int l = 0; l < 4; l++) a.epi[l] = FrEpi{c->has_bias[l] ? c->d_bias[l].p : c->d_negzero.p, c->act[l] == FR_ACT_RELU ? 1 : 0, 0};
     a.K = c->model.fc[0];
     a.H1 = c->model.fc[1];
     a.H2 = c->model.fc[2];
@@ -1520,7 +1582,10 @@ static int fused_flush(fr_worker *w) {
         // and 10-30 % ahead from 1.25 on; K = 880 (Model-B) 5 % behind at one tile (305 vs 320 M), 5 % ahead at 1.25, level at 1.5, 6 % ahead at 2.
         const int hs_from = a.K <= 352 ? c->n_cu : c->n_cu + c->n_cu / 4;
         const bool only_hs = bf16 && !frk_fused_h_ok(a.K, a.H1, a.H2, a.H3);   // a record the chunked kernel has no instantiation for
-        if (c->hk_ok == 1 && (only_hs || (hk != 0 && (hk == 1 || tiles >= hs_from)))) {
+        // A context WITH an epilogue never takes the persistent kernel: its consumers hold 128 accumulators in a budget of 168 registers and FC1's tile
+        // stores run beside the first half of FC2's weight ring -- nothing is left for the bias fragments without scratch.  Its launches stay on the
+        // chunked fr_fused_tile_h_kernel (fused_eligible() has already sent a record that kernel has no instantiation for to the stage pipeline).
+        if (c->hk_ok == 1 && !c->any_epi() && (only_hs || (hk != 0 && (hk == 1 || tiles >= hs_from)))) {
             if (!w->ev_blist[FR_BLIST_RING - 1]) {   // first use (a partial failure is made up for: grow and create keep what is there)
                 FR_TRY(w->h_blist.grow(FrMem::PINNED, (size_t)FR_FUSED_MAX_QUEUE * FR_BLIST_RING, "batch lists"));
                 FR_TRY(w->d_blist.grow(FrMem::DEVICE, (size_t)FR_FUSED_MAX_QUEUE * FR_BLIST_RING, "batch lists (device)"));
@@ -1573,7 +1638,8 @@ static int launch_fc(fr_worker *w, int batch, const float *d_records, float *d_s
     if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fc on a sharded ctx needs the all-gathered records (use the sharded driver: fr_worker_submit_sharded, fr_worker_submit_sharded_pooled)");
     if (c->cpu) {
         const float *const wl[4] = {c->d_w[0], c->d_w[1], c->d_w[2], c->d_w[3]};
-        frc_fc_chain(c->model.fc, wl, d_records, batch, w->c_scratch, d_scores);
+        const FrEpi ep[4] = {c->epi(0), c->epi(1), c->epi(2), c->epi(3)};
+        frc_fc_chain(c->model.fc, wl, ep, d_records, batch, w->c_scratch, d_scores);
         return FR_OK;
     }
     if (w->n_active) FR_FAIL(FR_ERR_STATE, "pipeline busy: call fr_worker_sync first");
@@ -1604,7 +1670,8 @@ static int fc_from_slices_impl(fr_worker *w, int batch_total, int item0, int n_i
         if (c->n_shards < 2) FR_FAIL(FR_ERR_STATE, "fc_from_slices needs a sharded context");
         frc_slices_to_records(d_gathered, c->n_shards, batch_total, c->slice_padded, c->shard_offset.data(), c->shard_len.data(), item0, n_items, w->c_x, c->model.fc[0]);
         const float *const wl[4] = {c->d_w[0], c->d_w[1], c->d_w[2], c->d_w[3]};
-        frc_fc_chain(c->model.fc, wl, w->c_x, n_items, w->c_scratch, d_scores);
+        const FrEpi ep[4] = {c->epi(0), c->epi(1), c->epi(2), c->epi(3)};
+        frc_fc_chain(c->model.fc, wl, ep, w->c_x, n_items, w->c_scratch, d_scores);
         return FR_OK;
     }
     FR_SET_DEVICE(c);
@@ -2562,7 +2629,9 @@ static int f8_calibrate_finish(fr_worker *w, uint64_t L0, int batch) {
     const float *reg[4] = {act_set(w, (int)(L0 & 1)).x, act_set(w, (int)((L0 + 1) & 1)).r1, act_set(w, (int)((L0 + 2) & 1)).r2,
                            act_set(w, (int)((L0 + 3) & 1)).r3};
     for (int l = 0; l < 4; l++) {
-        int rc = frk_stats(reg[l], (size_t)fc[l] * ldm, c->d_stats + 2 * l, w->stream);
+        // with an epilogue the buffers hold the POST-activation R1..R3 (the calibration batch runs unsplit: every stage applies its own layer's), and the
+        // pad items hold relu(b) instead of zeros: they are left out
+        int rc = frk_stats(reg[l], (size_t)fc[l] * ldm, c->d_stats + 2 * l, w->stream, c->any_epi() ? (int)ldm : 0, batch);
         if (rc) return rc;
     }
     uint32_t st[8];

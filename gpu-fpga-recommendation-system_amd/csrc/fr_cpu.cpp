@@ -409,7 +409,7 @@ int frc_gather_pooled(const FrPooledPlan &p, const FrPooledBatch &pb, const FrPo
 }
 #pragma GCC pop_options
 
-// ---- the FC chain: 4 x cublasLtMatmul, alpha = 1, beta = 0, no bias, no activation (cuda_server.c:211-217,468-491) ---------------------
+// ---- the FC chain: 4 x cublasLtMatmul, alpha = 1, beta = 0 (cuda_server.c:211-217,468-491); bias and activation only where fr_ctx_set_epilogue set them ----
 // Y[b][h] = sum over k, IN k ORDER, of W[h + k * H] * X[b][k], each step one fused multiply-add in fp32.  A tile of MB items x HT outputs
 // keeps its sums in registers while k runs; W is read in its own (column-major: h contiguous) order.
 namespace {
@@ -428,6 +428,21 @@ static inline __attribute__((always_inline)) void fc_tile(const float *W, int H,
     for (int b = 0; b < MB; b++)
         if (y[b])
             for (int j = 0; j < HT; j++) y[b][h0 + j] = acc[b][j];
+}
+
+// The layer's epilogue (fr_ctx_set_epilogue) on finished sums, in place: v = sum + b[h] (one fp32 add), then ReLU -- v > 0 ? v : +0, a NaN stays a NaN
+// (it fails the compare).  {NULL, 0}: nothing is touched.  A pass of its own behind the layer: the k-ordered chains above stay what they were.
+void fc_epilogue(float *Y, int ldy, int H, int batch, const FrEpi &e) {
+    if (!e.bias && !e.relu) return;
+    Pool::get().run((batch + 63) / 64, [&](int u) {
+        for (int b = u * 64; b < batch && b < (u + 1) * 64; b++) {
+            float *y = Y + (size_t)b * ldy;
+            if (e.bias)
+                for (int h = 0; h < H; h++) y[h] = y[h] + e.bias[h];
+            if (e.relu)
+                for (int h = 0; h < H; h++) y[h] = y[h] <= 0.0f ? 0.0f : y[h];
+        }
+    });
 }
 
 // one unit of a layer: items [b0, b0 + MB) x outputs [h0, h0 + HT) (ragged item blocks compute item b0 again and do not store it)
@@ -477,7 +492,7 @@ FcUnitFn pick_fc_unit() {
     return fc_unit_base;   // any other host: the compiler's baseline (fmaf() keeps one rounding per step everywhere)
 }
 
-void fc_layer(const float *W, int H, int K, const float *X, int ldx, float *Y, int ldy, int batch) {
+void fc_layer_sums(const float *W, int H, int K, const float *X, int ldx, float *Y, int ldy, int batch) {
     static const FcUnitFn unit = pick_fc_unit();
     if (H % FC_HT) {   // the output layer (H = 1) and any narrow layer: one k-ordered chain per (item, output)
         Pool::get().run(batch, [&](int b) {
@@ -504,16 +519,21 @@ void fc_layer(const float *W, int H, int K, const float *X, int ldx, float *Y, i
         for (int ib = ib0; ib < ib1; ib++) unit(W, H, K, X, ldx, Y, ldy, batch, ib * FC_MB, h0);
     });
 }
+
+void fc_layer(const float *W, int H, int K, const float *X, int ldx, float *Y, int ldy, int batch, const FrEpi &e) {
+    fc_layer_sums(W, H, K, X, ldx, Y, ldy, batch);
+    fc_epilogue(Y, ldy, H, batch, e);
+}
 }  // namespace
 
 // X: item-major records [batch][K] (for the BLOCKED layout: the 3-node buffer read "as if it were B x K item-major", 3-node
 // cuda_server.c:216-217).  scratch: batch * (H1 + H2 + H3) floats.  w[l]: column-major H x K (fr_ctx_set_weights).
-void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores) {
+void frc_fc_chain(const int32_t fc[5], const float *const w[4], const FrEpi epi[4], const float *X, int batch, float *scratch, float *scores) {
     float *r1 = scratch, *r2 = r1 + (size_t)batch * fc[1], *r3 = r2 + (size_t)batch * fc[2];
-    fc_layer(w[0], fc[1], fc[0], X, fc[0], r1, fc[1], batch);   // R1 = W1 * X        cuda_server.c:468-472
-    fc_layer(w[1], fc[2], fc[1], r1, fc[1], r2, fc[2], batch);  // R2 = W2 * R1       :474-478
-    fc_layer(w[2], fc[3], fc[2], r2, fc[2], r3, fc[3], batch);  // R3 = W3 * R2       :480-484
-    fc_layer(w[3], fc[4], fc[3], r3, fc[3], scores, fc[4], batch);  // out = Wout * R3 :486-491
+    fc_layer(w[0], fc[1], fc[0], X, fc[0], r1, fc[1], batch, epi[0]);   // R1 = W1 * X        cuda_server.c:468-472
+    fc_layer(w[1], fc[2], fc[1], r1, fc[1], r2, fc[2], batch, epi[1]);  // R2 = W2 * R1       :474-478
+    fc_layer(w[2], fc[3], fc[2], r2, fc[2], r3, fc[3], batch, epi[2]);  // R3 = W3 * R2       :480-484
+    fc_layer(w[3], fc[4], fc[3], r3, fc[3], scores, fc[4], batch, epi[3]);  // out = Wout * R3 :486-491
 }
 
 // Table-sharded mode after the exchange: gathered = [n_shards][batch_total][slice_padded] floats -> item-major records [n_items][K] of

@@ -10,10 +10,29 @@
 
 #include "fr_internal.h"
 
+// Two builds of the FC-chain kernel files (fr_fused.hip, fr_pipeline.hip, fr_gemm.hip).  libfleetrec.so: the kernels as they always were, without a line
+// of epilogue code (FR_HAS_EPI 0: every epilogue argument folds to {NULL, 0} at compile time); a launch of a context WITH an epilogue is forwarded to
+// the companion.  -DFR_EPI_FORMS -> libfleetrec_epi.so: the same bodies under names of their own (fr_epi_* / fc_epi_*), which apply the epilogues.
+#ifdef FR_EPI_FORMS
+#define FR_HAS_EPI 1
+extern thread_local char fr_epi_noted[96];   // the companion's fr_note_kernel writes here (fr_fused.hip)
+extern thread_local int fr_epi_hip_error;    // ... and its KCHECK keeps the launch error it consumed here, for the export to return
+// what an export of the companion returns for a launcher's status: 0, the kept hipError_t, or hipErrorInvalidValue (a shape without an instantiation)
+static inline int fr_epi_status(int rc) { return rc == 0 ? 0 : (fr_epi_hip_error ? fr_epi_hip_error : (int)hipErrorInvalidValue); }
+#else
+#define FR_HAS_EPI 0
+#endif
+
+#ifdef FR_EPI_FORMS
+#define FR_KEEP_HIP_ERROR(e) (fr_epi_hip_error = (int)(e))
+#else
+#define FR_KEEP_HIP_ERROR(e) ((void)0)
+#endif
 #define KCHECK()                                                                          \
     do {                                                                                  \
         hipError_t e_ = hipGetLastError();                                                \
         if (e_ != hipSuccess) {                                                           \
+            FR_KEEP_HIP_ERROR(e_);                                                        \
             fr_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, __LINE__); \
             return FR_ERR_HIP;                                                            \
         }                                                                                 \
@@ -66,6 +85,70 @@ __device__ __forceinline__ uint32_t pack_fp8x4(float a, float b, float c, float 
 }
 __device__ __forceinline__ uint32_t pack_fp8_word(const uint4 &v, float scale) {
     return pack_fp8x4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w), scale);
+}
+
+// ---- per-layer epilogue (FrEpi, fr_internal.h) ------------------------------------------------------------------------------------------
+// ReLU as the contract states it: v > 0 ? v : +0.0f.  The compare is written so that a NaN fails it and is kept (v_max_f32 alone would drop
+// it); -0 and negatives become +0.
+__device__ __forceinline__ float fr_relu(float v) { return v <= 0.0f ? 0.0f : v; }
+// Four consecutive outputs n .. n + 3 of a layer, as every MFMA accumulator layout here holds them (registers 4i .. 4i + 3 of a 32 x 32 tile:
+// n = n_tile + 8i + 4 (lane / 32) + c; of a 16 x 16 tile: n = n_tile + 4 (lane / 16) + c): the lane's n = n_uni + STRIDE * sel with n_uni
+// wave-uniform (n_uni % 4 == 0) and sel = 0 .. NSEL - 1 the lane's half / quarter of the wave.  The NSEL aligned 16-byte bias fragments are read
+// through the SCALAR cache (constant address space: nothing writes a bias while a kernel runs) and the lane picks its own with v_cndmask: no vector
+// register is held across the read, which is what the fused kernels, full of accumulators, cannot spare.  Both branches are wave-uniform;
+// without an epilogue nothing is added at all (-0 stays -0).
+template <int NSEL = 2, int STRIDE = 4>
+__device__ __forceinline__ void fr_epi4(float &a, float &b, float &c, float &d, const FrEpi &e, int n_uni, int sel) {
+    typedef float cf4 __attribute__((ext_vector_type(4)));
+    typedef const cf4 __attribute__((address_space(4))) *cf4_ptr;
+    if (e.bias) {
+        const cf4_ptr bp = (cf4_ptr)(uintptr_t)(e.bias + __builtin_amdgcn_readfirstlane(n_uni));
+        cf4 b4 = bp[0];
+#pragma unroll
+        for (int s = 1; s < NSEL; s++) {
+            const cf4 o = bp[s * STRIDE / 4];
+            b4.x = sel == s ? o.x : b4.x;
+            b4.y = sel == s ? o.y : b4.y;
+            b4.z = sel == s ? o.z : b4.z;
+            b4.w = sel == s ? o.w : b4.w;
+        }
+        a += b4.x;
+        b += b4.y;
+        c += b4.z;
+        d += b4.w;
+    }
+    if (e.relu) {
+        a = fr_relu(a);
+        b = fr_relu(b);
+        c = fr_relu(c);
+        d = fr_relu(d);
+    }
+}
+
+// The branch-free form of the fused kernels' epilogue forms (fr_fused.hip): the bias pointer is always there (a vector of -0.0f stands for "no
+// bias": v + (-0.0f) == v for every v, -0 and NaN included) and ReLU is `v <= lo ? +0 : v` with lo = +0 (on) or NaN (off: nothing compares <= NaN).
+template <int NSEL = 2, int STRIDE = 4>
+__device__ __forceinline__ void fr_epi4_always(float &a, float &b, float &c, float &d, const float *bias, float lo, int n_uni, int sel) {
+    typedef float cf4 __attribute__((ext_vector_type(4)));
+    typedef const cf4 __attribute__((address_space(4))) *cf4_ptr;
+    const cf4_ptr bp = (cf4_ptr)(uintptr_t)(bias + __builtin_amdgcn_readfirstlane(n_uni));
+    cf4 b4 = bp[0];
+#pragma unroll
+    for (int s = 1; s < NSEL; s++) {
+        const cf4 o = bp[s * STRIDE / 4];
+        b4.x = sel == s ? o.x : b4.x;
+        b4.y = sel == s ? o.y : b4.y;
+        b4.z = sel == s ? o.z : b4.z;
+        b4.w = sel == s ? o.w : b4.w;
+    }
+    a += b4.x;
+    b += b4.y;
+    c += b4.z;
+    d += b4.w;
+    a = a <= lo ? 0.0f : a;
+    b = b <= lo ? 0.0f : b;
+    c = c <= lo ? 0.0f : c;
+    d = d <= lo ? 0.0f : d;
 }
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));

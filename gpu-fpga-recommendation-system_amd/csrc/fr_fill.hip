@@ -407,10 +407,13 @@ int frk_records_to_q16_fp8(const float *X, void *Xf, int batch, int K, int ldm, 
 }
 
 // max |x| and sum x^2 of a float array (fp8 scale selection): out[0] = bits of max |x| (atomicMax on the uint pattern), out[1] = sum
-__global__ void __launch_bounds__(256) stats_kernel(const float *__restrict__ p, size_t n, unsigned *out_max, float *out_sumsq) {
+// ldm > 0: the array is a feature-major q4 image [..][ldm][4] and the items m >= batch are left out (the calibration of a chain with biases:
+// its pad items hold relu(b), not zeros)
+__global__ void __launch_bounds__(256) stats_kernel(const float *__restrict__ p, size_t n, unsigned *out_max, float *out_sumsq, int ldm, int batch) {
     float mx = 0.0f, ss = 0.0f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float v = p[i];
+        if (ldm > 0 && (int)((i >> 2) % (size_t)ldm) >= batch) continue;
         if (v == v) {  // NaN never drives a scale
             mx = fmaxf(mx, fabsf(v));
             ss = fmaf(v, v, ss);
@@ -434,10 +437,10 @@ __global__ void __launch_bounds__(256) stats_kernel(const float *__restrict__ p,
 }
 
 // d_out: 2 words (zeroed here); returns after the launch is enqueued
-int frk_stats(const float *p, size_t n, void *d_out, hipStream_t s) {
+int frk_stats(const float *p, size_t n, void *d_out, hipStream_t s, int ldm, int batch) {
     if (hipMemsetAsync(d_out, 0, 8, s) != hipSuccess) FR_FAIL(FR_ERR_HIP, "hipMemsetAsync failed");
     unsigned blocks = (unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
-    stats_kernel<<<dim3(blocks ? blocks : 1), dim3(256), 0, s>>>(p, n, reinterpret_cast<unsigned *>(d_out), reinterpret_cast<float *>(d_out) + 1);
+    stats_kernel<<<dim3(blocks ? blocks : 1), dim3(256), 0, s>>>(p, n, reinterpret_cast<unsigned *>(d_out), reinterpret_cast<float *>(d_out) + 1, ldm, batch);
     KCHECK();
     return FR_OK;
 }

@@ -1,5 +1,34 @@
 #include "fr_device.h"
 
+// This file is compiled twice (fr_device.h; so are fr_pipeline.hip and fr_gemm.hip).  Into libfleetrec.so: the fused kernels as they always were
+// (fr_fused_tile_*_kernel) and their launchers; a launch of a context WITH an epilogue is forwarded to fr_epi_fused_launch.  With -DFR_EPI_FORMS into the
+// companion code object libfleetrec_epi.so (the kernel list of libfleetrec.so is pinned name for name, tests/golden/libfleetrec_kernel_names.txt): the
+// same bodies as fr_epi_tile_*_kernel, which apply the per-layer epilogues of FrFusedArgs::epi, behind this file's exported launcher.  The companion
+// calls nothing of libfleetrec.so; its stand-ins for fr_set_error / fr_note_kernel (shared with the other two files) are below.
+#ifdef FR_EPI_FORMS
+#include <cstdarg>
+#include <cstdio>
+thread_local char fr_epi_noted[96];
+thread_local int fr_epi_hip_error = 0;
+void fr_set_error(const char *, ...) {}   // (the companion reports a launch failure as the hipError_t it returns)
+void fr_note_kernel(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(fr_epi_noted, sizeof(fr_epi_noted), fmt, ap);
+    va_end(ap);
+}
+#define FR_NO_DEFAULT_FORM() return FR_ERR_INVALID   /* this build holds the epilogue forms only */
+#else
+// kind: which launcher (FR_EPI_KIND_*); -> FR_OK with the kernel's name noted, or FR_ERR_HIP
+static int fused_epi_forward(const FrFusedArgs &a, int kind, hipStream_t s) {
+    char name[96] = "";
+    const int e = fr_epi_fused_launch(&a, kind, s, name, sizeof(name));
+    if (e) FR_FAIL(FR_ERR_HIP, "launch of the epilogue form of the fused kernel failed: %s", hipGetErrorString((hipError_t)e));
+    fr_note_kernel("%s", name);
+    return FR_OK;
+}
+#endif
+
 // ===================================================================================================
 // fr_fused_tile_kernel: the whole hot path of 32 items in ONE workgroup, activations never leave LDS.
 //
@@ -172,14 +201,33 @@ __device__ __forceinline__ void ft_gemm(f32x16 (&acc)[NT], const float4 *__restr
 }
 
 // store a 32(n) x 32(m) accumulator tile as q4 elements into an LDS operand image: n_local = tile's first n inside the image
-__device__ __forceinline__ void ft_store_tile(uint4 *img, const f32x16 &acc, int n_local, int hk, int lm) {
+// The fused kernels come in two forms under two names.  fr_fused_tile_*_kernel<...> is the chain without an epilogue, compiled as it always was
+// (EPI = false: no epilogue code exists in it).  fr_epi_tile_*_kernel<...> is the same body with the per-layer epilogues of FrFusedArgs::epi applied
+// in every tile store, BRANCH-FREE: these kernels are full of accumulators, and a run-time branch around the stores of a phase's tiles cost 30
+// registers (the fp8 K = 880 form spilled 111).  So the launcher hands every layer a bias pointer -- a vector of -0.0f where the layer has none:
+// v + (-0.0f) == v bit for bit, for every v -- and ReLU is a compare against a threshold that is +0 where it is on and NaN where it is off (no v
+// compares <= NaN).  A context that never calls fr_ctx_set_epilogue never launches the second form.
+template <bool EPI>
+__device__ __forceinline__ void ft_epi4(float &c0, float &c1, float &c2, float &c3, const FrEpi &e, int n_uni, int hk) {
+    if constexpr (EPI) fr_epi4_always(c0, c1, c2, c3, e.bias, e.relu ? 0.0f : __builtin_nanf(""), n_uni, hk);
+}
+template <bool EPI>
+__device__ __forceinline__ float ft_out_bias(const FrFusedArgs &a, float t) {
+    if constexpr (EPI) return t + a.epi[3].bias[0];
+    else return t;
+}
+// e, n_glob: the layer's epilogue and the tile's first n inside the layer (the bias index)
+template <bool EPI>
+__device__ __forceinline__ void ft_store_tile(uint4 *img, const f32x16 &acc, int n_local, int hk, int lm, const FrEpi &e, int n_glob) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
+        float c0 = acc[4 * i + 0], c1 = acc[4 * i + 1], c2 = acc[4 * i + 2], c3 = acc[4 * i + 3];
+        ft_epi4<EPI>(c0, c1, c2, c3, e, n_glob + 8 * i, hk);
         uint4 v;
-        v.x = __float_as_uint(acc[4 * i + 0]);
-        v.y = __float_as_uint(acc[4 * i + 1]);
-        v.z = __float_as_uint(acc[4 * i + 2]);
-        v.w = __float_as_uint(acc[4 * i + 3]);
+        v.x = __float_as_uint(c0);
+        v.y = __float_as_uint(c1);
+        v.z = __float_as_uint(c2);
+        v.w = __float_as_uint(c3);
         img[(size_t)((n_local >> 2) + 2 * i + hk) * FR_FT_LD + lm] = v;  // n = n_local + 8i + 4hk + c
     }
 }
@@ -244,8 +292,8 @@ __device__ __forceinline__ bool ft_gather_tile(const FrFusedArgs &a, const FrFus
     return bad;
 }
 
-template <int T2W, int KG, int WPE, bool DB>
-__global__ void __launch_bounds__(512, WPE) fr_fused_tile_kernel(const FrFusedArgs a) {
+template <int T2W, int KG, int WPE, bool DB, bool EPI>
+__device__ __forceinline__ void fused_tile_body(const FrFusedArgs &a) {
     extern __shared__ uint4 lds[];
     constexpr int RD = (WPE == 2) ? 1 : 2;  // ring depth divisor: half-depth rings when two workgroups share a CU's registers
     const int KQ = a.K / 4;
@@ -343,7 +391,7 @@ __global__ void __launch_bounds__(512, WPE) fr_fused_tile_kernel(const FrFusedAr
         ft_ring_fill<T2W, RB, 32>(ring2, W2, 32 * T2W * wave, 32 * c);
         uint4 *R1 = R1b[c & 1];  // double-buffered: ONE barrier per chunk (the buffer written now was last read two chunks ago)
         if (!DB && c > 0) __syncthreads();  // single buffer: every wave must be done with the previous chunk's FC2
-        ft_store_tile(R1, acc1[0], 32 * wave, hk, lm);
+        ft_store_tile<EPI>(R1, acc1[0], 32 * wave, hk, lm, a.epi[0], c * 256 + 32 * wave);
         __syncthreads();
         stamp();
         // FC2: K range [256 c, 256 c + 256) = groups [32 c, 32 c + 32); this wave's n tiles start at 32 * T2W * wave
@@ -359,7 +407,7 @@ __global__ void __launch_bounds__(512, WPE) fr_fused_tile_kernel(const FrFusedAr
     ft_ring_fill<1, RA, 32 * T2W>(ring3, W3, 32 * wave, 0);
     __syncthreads();  // every wave is done with Xq and both R1 buffers: R2 may overlay them
 #pragma unroll
-    for (int t = 0; t < T2W; t++) ft_store_tile(R2, acc2[t], 32 * (T2W * wave + t), hk, lm);
+    for (int t = 0; t < T2W; t++) ft_store_tile<EPI>(R2, acc2[t], 32 * (T2W * wave + t), hk, lm, a.epi[1], 32 * (T2W * wave + t));
     __syncthreads();  // R2 complete
     stamp();
 
@@ -369,7 +417,7 @@ __global__ void __launch_bounds__(512, WPE) fr_fused_tile_kernel(const FrFusedAr
     for (int i = 0; i < 16; i++) acc3[0][i] = 0.0f;
     ft_gemm_ct<1, RA, 32 * T2W>(acc3, ring3, W3, 32 * wave, R2, 0, 0, hk, lm);  // H2 / 8 = 32 * T2W groups
     if (!DB) __syncthreads();                       // R3 overlays R2: every wave must have finished reading R2
-    ft_store_tile(R3, acc3[0], 32 * wave, hk, lm);  // R3 image [H3/4][33]
+    ft_store_tile<EPI>(R3, acc3[0], 32 * wave, hk, lm, a.epi[2], 32 * wave);  // R3 image [H3/4][33]
     __syncthreads();
     stamp();
     {   // score[m] = sum_n wout[n] * R3[n][m]: 32 items x 16 slices of 4 q4 rows, fixed-order reduction through LDS (reuses Xq)
@@ -391,11 +439,24 @@ __global__ void __launch_bounds__(512, WPE) fr_fused_tile_kernel(const FrFusedAr
             float t = part[tid];
 #pragma unroll
             for (int i = 1; i < 16; i++) t += part[i * 32 + tid];
+            t = ft_out_bias<EPI>(a, t);
             bt.scores[m0 + tid] = t;
         }
     }
     stamp();
 }
+
+#ifndef FR_EPI_FORMS
+template <int T2W, int KG, int WPE, bool DB>
+__global__ void __launch_bounds__(512, WPE) fr_fused_tile_kernel(const FrFusedArgs a) {
+    fused_tile_body<T2W, KG, WPE, DB, false>(a);
+}
+#else
+template <int T2W, int KG, int WPE, bool DB>
+__global__ void __launch_bounds__(512, WPE) fr_epi_tile_kernel(const FrFusedArgs a) {
+    fused_tile_body<T2W, KG, WPE, DB, true>(a);
+}
+#endif
 
 size_t frk_fused_lds_bytes(int K, int H2, int wpe) {  // wpe 4 stands for the single-buffer layout here
     if (wpe == 4) {  // Xq + one R1 buffer | R2, then R3 + scratch over R2
@@ -422,6 +483,7 @@ static int fused_wpe(int K, int H2) {
     return frk_fused_lds_bytes(K, H2, 4) <= 80 * 1024 ? 4 : 2;
 }
 
+#ifndef FR_EPI_FORMS
 template <int T2W, int KG, int WPE, bool DB>
 static int fused_launch_inst(const FrFusedArgs &a, dim3 grid, size_t lds, hipStream_t s) {
     static FrLdsAttrOnce lds_once;  // per instantiation, per device
@@ -432,11 +494,47 @@ static int fused_launch_inst(const FrFusedArgs &a, dim3 grid, size_t lds, hipStr
     return FR_OK;
 }
 
+#else
+template <int T2W, int KG, int WPE, bool DB>
+static int fused_launch_epi_inst(const FrFusedArgs &a, dim3 grid, size_t lds, hipStream_t s) {
+    static FrLdsAttrOnce lds_once;  // per instantiation, per device
+    if (int rc_ = fr_allow_full_lds(&fr_epi_tile_kernel<T2W, KG, WPE, DB>, lds_once)) return rc_;
+    fr_epi_tile_kernel<T2W, KG, WPE, DB><<<grid, dim3(512), lds, s>>>(a);
+    fr_note_kernel("fr_epi_tile_kernel<%d, %d, %d, %s>", T2W, KG, WPE, DB ? "true" : "false");
+    KCHECK();
+    return FR_OK;
+}
+
+#endif
+// fused_flush (fr_api.cpp) fills FrFusedArgs::epi of a context with an epilogue so that EVERY layer has a bias pointer (-0.0f where it has none)
+static bool fused_has_epi(const FrFusedArgs &a) { return a.epi[3].bias != nullptr; }
+
 int frk_fused_launch(const FrFusedArgs &a, hipStream_t s) {
-    int wpe = fused_wpe(a.K, a.H2);
+    const int wpe = fused_wpe(a.K, a.H2);
+    (void)wpe;
+    dim3 grid(a.n_batches * a.tiles_per_batch);
+    if (fused_has_epi(a)) {
+#ifndef FR_EPI_FORMS
+        return fused_epi_forward(a, FR_EPI_KIND_F32, s);
+#else
+        // The epilogue forms, instantiation for instantiation -- but for Model-A's: in the 128 registers of the two-workgroups-per-CU build (WPE 4) the
+        // epilogue form spills two, so a K = 352 context WITH an epilogue takes the one-workgroup-per-CU, double-buffered sibling <2, 44, 2, true>
+        // (114 KiB of LDS), which has the registers; its cost: profiles/fc_epilogue.json, shape A256_fp32_g16.  Same sums in the same order: bit-identical scores.
+        if (a.H2 == 512 && a.K == 352) return fused_launch_epi_inst<2, 44, 2, true>(a, grid, frk_fused_lds_bytes(a.K, a.H2, 2), s);
+        const bool db = frk_fused_lds_bytes(a.K, a.H2, 4) > 80 * 1024 && frk_fused_lds_bytes(a.K, a.H2, 2) <= 160 * 1024;
+        const size_t lds = frk_fused_lds_bytes(a.K, a.H2, db ? 2 : 4);
+        if (a.H2 == 512) {
+            if (a.K == 880) return fused_launch_epi_inst<2, 110, 2, false>(a, grid, lds, s);
+            return db ? fused_launch_epi_inst<2, 0, 2, true>(a, grid, lds, s) : fused_launch_epi_inst<2, 0, 2, false>(a, grid, lds, s);
+        }
+        return db ? fused_launch_epi_inst<1, 0, 2, true>(a, grid, lds, s) : fused_launch_epi_inst<1, 0, 2, false>(a, grid, lds, s);
+#endif
+    }
+#ifdef FR_EPI_FORMS
+    FR_NO_DEFAULT_FORM();
+#else
     const bool db = wpe == 2 && frk_fused_lds_bytes(a.K, a.H2, 2) <= 160 * 1024;
     const size_t lds = frk_fused_lds_bytes(a.K, a.H2, db ? 2 : 4);
-    dim3 grid(a.n_batches * a.tiles_per_batch);
     if (a.H2 == 512) {
         if (a.K == 352) {  // Model-A: straight-line FC1; 78 KiB in the single-buffer layout, so WPE 4 unless FR_FUSED_WPE forces the other build
 #ifdef FR_EXPERIMENTS
@@ -450,6 +548,7 @@ int frk_fused_launch(const FrFusedArgs &a, hipStream_t s) {
     }
     if (db) return fused_launch_inst<1, 0, 2, true>(a, grid, lds, s);
     return fused_launch_inst<1, 0, 2, false>(a, grid, lds, s);
+#endif
 }
 
 // ===================================================================================================
@@ -512,20 +611,23 @@ __device__ __forceinline__ void ftm_gemm_ct(f32x16 (&acc)[NT][MT], float4 (&ring
     }
 }
 
-__device__ __forceinline__ void ftm_store_tile(uint4 *img, const f32x16 &acc, int n_local, int m_local, int hk, int lm) {
+template <bool EPI>
+__device__ __forceinline__ void ftm_store_tile(uint4 *img, const f32x16 &acc, int n_local, int m_local, int hk, int lm, const FrEpi &e, int n_glob) {
 #pragma unroll
     for (int i = 0; i < 4; i++) {
+        float c0 = acc[4 * i + 0], c1 = acc[4 * i + 1], c2 = acc[4 * i + 2], c3 = acc[4 * i + 3];
+        ft_epi4<EPI>(c0, c1, c2, c3, e, n_glob + 8 * i, hk);
         uint4 v;
-        v.x = __float_as_uint(acc[4 * i + 0]);
-        v.y = __float_as_uint(acc[4 * i + 1]);
-        v.z = __float_as_uint(acc[4 * i + 2]);
-        v.w = __float_as_uint(acc[4 * i + 3]);
+        v.x = __float_as_uint(c0);
+        v.y = __float_as_uint(c1);
+        v.z = __float_as_uint(c2);
+        v.w = __float_as_uint(c3);
         img[(size_t)((n_local >> 2) + 2 * i + hk) * FR_M2_LD + m_local + lm] = v;  // n = n_local + 8i + 4hk + c
     }
 }
 
-template <int KG>
-__global__ void __launch_bounds__(512) fr_fused_tile_m2_kernel(const FrFusedArgs a) {
+template <int KG, bool EPI>
+__device__ __forceinline__ void fused_tile_m2_body(const FrFusedArgs &a) {
     extern __shared__ uint4 lds[];
     constexpr int LD = FR_M2_LD, MT = 2, T2W = 2, TI = 64;
     constexpr int RA = 12, RB = 8;
@@ -572,7 +674,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_m2_kernel(const FrFusedArgs
         ft_ring_fill<T2W, RB, 32>(ring2, W2, 32 * T2W * wave, 32 * c);
         if (c > 0) __syncthreads();  // single R1 buffer: every wave must be done with the previous chunk's FC2
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) ftm_store_tile(R1, acc1[0][mt], 32 * wave, 32 * mt, hk, lm);
+        for (int mt = 0; mt < MT; mt++) ftm_store_tile<EPI>(R1, acc1[0][mt], 32 * wave, 32 * mt, hk, lm, a.epi[0], c * 256 + 32 * wave);
         __syncthreads();
         ftm_gemm_ct<T2W, MT, RB, 32>(acc2, ring2, W2, 32 * T2W * wave, R1, 0, 32 * c, hk, lm);
         const int cn = (c + 1 < n_chunks) ? c + 1 : c;  // the last chunk re-requests its own: branch-free, harmless
@@ -584,7 +686,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_m2_kernel(const FrFusedArgs
 #pragma unroll
     for (int t = 0; t < T2W; t++)
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) ftm_store_tile(R2, acc2[t][mt], 32 * (T2W * wave + t), 32 * mt, hk, lm);
+        for (int mt = 0; mt < MT; mt++) ftm_store_tile<EPI>(R2, acc2[t][mt], 32 * (T2W * wave + t), 32 * mt, hk, lm, a.epi[1], 32 * (T2W * wave + t));
     __syncthreads();
 
     f32x16 acc3[1][MT];
@@ -595,7 +697,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_m2_kernel(const FrFusedArgs
     ftm_gemm_ct<1, MT, RA, 32 * T2W>(acc3, ring3, W3, 32 * wave, R2, 0, 0, hk, lm);
     __syncthreads();  // R3 overlays R2: every wave must have finished reading R2
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++) ftm_store_tile(R3, acc3[0][mt], 32 * wave, 32 * mt, hk, lm);
+    for (int mt = 0; mt < MT; mt++) ftm_store_tile<EPI>(R3, acc3[0][mt], 32 * wave, 32 * mt, hk, lm, a.epi[2], 32 * wave);
     __syncthreads();
     {   // score[m] = sum_n wout[n] * R3[n][m]: 64 items x 16 slices of 4 q4 rows (two slices per thread), fixed-order reduction
         // through LDS -- the same partial sums in the same order as fr_fused_tile_kernel
@@ -621,21 +723,42 @@ __global__ void __launch_bounds__(512) fr_fused_tile_m2_kernel(const FrFusedArgs
             float t = part[tid];
 #pragma unroll
             for (int i = 1; i < 16; i++) t += part[i * 64 + tid];
+            t = ft_out_bias<EPI>(a, t);
             bt.scores[m0 + tid] = t;
         }
     }
 }
+
+#ifndef FR_EPI_FORMS
+template <int KG>
+__global__ void __launch_bounds__(512) fr_fused_tile_m2_kernel(const FrFusedArgs a) {
+    fused_tile_m2_body<KG, false>(a);
+}
+#else
+template <int KG>
+__global__ void __launch_bounds__(512) fr_epi_tile_m2_kernel(const FrFusedArgs a) {
+    fused_tile_m2_body<KG, true>(a);
+}
+#endif
 
 bool frk_fused_m2_ok(int K, int H1, int H2, int H3) { return K == 352 && H1 % 256 == 0 && H2 == 512 && H3 == 256; }
 
 // a.tiles_per_batch counts 64-item tiles
 int frk_fused_m2_launch(const FrFusedArgs &a, hipStream_t s) {
     static FrLdsAttrOnce lds_once;  // per instantiation, per device
-    if (int rc_ = fr_allow_full_lds(&fr_fused_tile_m2_kernel<44>, lds_once)) return rc_;
     const size_t rows1 = (size_t)(a.K / 4) + 64, rows2 = (size_t)(a.H2 / 4), rows3 = 64 + 4;  // R3 + 4 KiB of reduction scratch
     const size_t rows = rows1 > rows2 ? (rows1 > rows3 ? rows1 : rows3) : (rows2 > rows3 ? rows2 : rows3);
+#ifdef FR_EPI_FORMS
+    if (!fused_has_epi(a)) FR_NO_DEFAULT_FORM();
+    if (int rc_ = fr_allow_full_lds(&fr_epi_tile_m2_kernel<44>, lds_once)) return rc_;
+    fr_epi_tile_m2_kernel<44><<<dim3(a.n_batches * a.tiles_per_batch), dim3(512), rows * FR_M2_LD * 16, s>>>(a);
+    fr_note_kernel("fr_epi_tile_m2_kernel<44>");
+#else
+    if (fused_has_epi(a)) return fused_epi_forward(a, FR_EPI_KIND_F32_M2, s);
+    if (int rc_ = fr_allow_full_lds(&fr_fused_tile_m2_kernel<44>, lds_once)) return rc_;
     fr_fused_tile_m2_kernel<44><<<dim3(a.n_batches * a.tiles_per_batch), dim3(512), rows * FR_M2_LD * 16, s>>>(a);
     fr_note_kernel("fr_fused_tile_m2_kernel<44>");
+#endif
     KCHECK();
     return FR_OK;
 }
@@ -676,19 +799,23 @@ __device__ __forceinline__ void fth_gemm_ct(f32x16 (&acc)[NT][MT], const FtW &w,
 }
 
 // 32(n) x 32(m) fp32 accumulator tile -> bf16, stored as 8-byte halves of q8 elements of an LDS operand image (row stride ld)
-__device__ __forceinline__ void fth_store_tile(uint4 *img, int ld, const f32x16 &acc, int n_local, int m_local, int hk, int lm) {
+// (the epilogue works on the fp32 sums: bias and ReLU first, then the ONE rounding to bf16)
+template <bool EPI>
+__device__ __forceinline__ void fth_store_tile(uint4 *img, int ld, const f32x16 &acc, int n_local, int m_local, int hk, int lm, const FrEpi &e, int n_glob) {
     uint2 *h = reinterpret_cast<uint2 *>(img);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
+        float c0 = acc[4 * i + 0], c1 = acc[4 * i + 1], c2 = acc[4 * i + 2], c3 = acc[4 * i + 3];
+        ft_epi4<EPI>(c0, c1, c2, c3, e, n_glob + 8 * i, hk);
         uint2 v;
-        v.x = pack_bf16x2(acc[4 * i + 0], acc[4 * i + 1]);
-        v.y = pack_bf16x2(acc[4 * i + 2], acc[4 * i + 3]);
+        v.x = pack_bf16x2(c0, c1);
+        v.y = pack_bf16x2(c2, c3);
         h[((size_t)((n_local >> 3) + i) * ld + m_local + lm) * 2 + hk] = v;  // n = n_local + 8i + 4hk + c
     }
 }
 
-template <int MT, int T2W, int KG, bool DB, int RD, int PD>
-__global__ void __launch_bounds__(512) fr_fused_tile_h_kernel(const FrFusedArgs a) {
+template <int MT, int T2W, int KG, bool DB, int RD, int PD, bool EPI>
+__device__ __forceinline__ void fused_tile_h_body(const FrFusedArgs &a) {
     extern __shared__ uint4 lds[];
     constexpr int LD = 32 * MT + 1, TI = 32 * MT;
     const int KO = a.K / 8;
@@ -791,7 +918,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_h_kernel(const FrFusedArgs 
         uint4 *R1 = R1b[DB ? (c & 1) : 0];
         if (!DB && c > 0) __syncthreads();  // single R1 buffer: every wave must be done reading the previous chunk
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) fth_store_tile(R1, LD, acc1[0][mt], 32 * wave, 32 * mt, hk, lm);
+        for (int mt = 0; mt < MT; mt++) fth_store_tile<EPI>(R1, LD, acc1[0][mt], 32 * wave, 32 * mt, hk, lm, a.epi[0], c * 256 + 32 * wave);
         __syncthreads();
         // FC2: K range [256 c, 256 c + 256) = 16 groups of 16 k; its tail requests the next stream: W1 chunk c + 1, or W3 after the last chunk
         const bool last = c + 1 == n_chunks;
@@ -828,7 +955,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_h_kernel(const FrFusedArgs 
 #pragma unroll
     for (int t = 0; t < T2W; t++)
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) fth_store_tile(R2, LD, acc2[t][mt], 32 * (T2W * wave + t), 32 * mt, hk, lm);
+        for (int mt = 0; mt < MT; mt++) fth_store_tile<EPI>(R2, LD, acc2[t][mt], 32 * (T2W * wave + t), 32 * mt, hk, lm, a.epi[1], 32 * (T2W * wave + t));
     __syncthreads();
 
     f32x16 acc3[1][MT];
@@ -856,7 +983,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_h_kernel(const FrFusedArgs 
         }
     }
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++) fth_store_tile(R3, LD, acc3[0][mt], 32 * wave, 32 * mt, hk, lm);
+    for (int mt = 0; mt < MT; mt++) fth_store_tile<EPI>(R3, LD, acc3[0][mt], 32 * wave, 32 * mt, hk, lm, a.epi[2], 32 * wave);
     __syncthreads();
     stamp();
     {   // score[m] = sum_n wout[n] * R3[n][m] (bf16 x bf16, fp32 sum): TI items x (512 / TI) slices of q8 rows, fixed-order reduction
@@ -882,10 +1009,23 @@ __global__ void __launch_bounds__(512) fr_fused_tile_h_kernel(const FrFusedArgs 
             float t = part[tid];
 #pragma unroll
             for (int i = 1; i < NSL; i++) t += part[i * TI + tid];
+            t = ft_out_bias<EPI>(a, t);
             bt.scores[m0 + tid] = t;
         }
     }
 }
+
+#ifndef FR_EPI_FORMS
+template <int MT, int T2W, int KG, bool DB, int RD, int PD>
+__global__ void __launch_bounds__(512) fr_fused_tile_h_kernel(const FrFusedArgs a) {
+    fused_tile_h_body<MT, T2W, KG, DB, RD, PD, false>(a);
+}
+#else
+template <int MT, int T2W, int KG, bool DB, int RD, int PD>
+__global__ void __launch_bounds__(512) fr_epi_tile_h_kernel(const FrFusedArgs a) {
+    fused_tile_h_body<MT, T2W, KG, DB, RD, PD, true>(a);
+}
+#endif
 
 static size_t fused_h_lds_bytes(int K, int H2, int H3, int MT, bool db) {
     const size_t LD = 32 * MT + 1;
@@ -905,9 +1045,17 @@ int frk_fused_h_items_per_wg() { return 64; }
 template <int MT, int T2W, int KG, bool DB, int RD, int PD>
 static int fused_h_launch_inst(const FrFusedArgs &a, dim3 grid, size_t lds, hipStream_t s) {
     static FrLdsAttrOnce lds_once;  // per instantiation, per device
+#ifdef FR_EPI_FORMS
+    if (!fused_has_epi(a)) FR_NO_DEFAULT_FORM();
+    if (int rc_ = fr_allow_full_lds(&fr_epi_tile_h_kernel<MT, T2W, KG, DB, RD, PD>, lds_once)) return rc_;
+    fr_epi_tile_h_kernel<MT, T2W, KG, DB, RD, PD><<<grid, dim3(512), lds, s>>>(a);
+    fr_note_kernel("fr_epi_tile_h_kernel<%d, %d, %d, %s, %d, %d>", MT, T2W, KG, DB ? "true" : "false", RD, PD);
+#else
+    if (fused_has_epi(a)) return fused_epi_forward(a, FR_EPI_KIND_BF16, s);
     if (int rc_ = fr_allow_full_lds(&fr_fused_tile_h_kernel<MT, T2W, KG, DB, RD, PD>, lds_once)) return rc_;
     fr_fused_tile_h_kernel<MT, T2W, KG, DB, RD, PD><<<grid, dim3(512), lds, s>>>(a);
     fr_note_kernel("fr_fused_tile_h_kernel<%d, %d, %d, %s, %d, %d>", MT, T2W, KG, DB ? "true" : "false", RD, PD);
+#endif
     KCHECK();
     return FR_OK;
 }
@@ -982,17 +1130,21 @@ __device__ __forceinline__ void ft8_gemm_ct(f32x16 (&acc)[NT][MT], const FtW8 &w
 }
 
 // 32(n) x 32(m) fp32 accumulator tile -> e4m3 (x oscale, saturated), stored as 4-byte quarters of q16 elements of an LDS image
-__device__ __forceinline__ void ft8_store_tile(uint4 *img, int ld, const f32x16 &acc, int n_local, int m_local, int hk, int lm, float oscale) {
+// (the scaled MFMA's block scales leave the accumulators in real units: the bias is added as it is, then ReLU, then x oscale and the quantisation)
+template <bool EPI>
+__device__ __forceinline__ void ft8_store_tile(uint4 *img, int ld, const f32x16 &acc, int n_local, int m_local, int hk, int lm, float oscale, const FrEpi &e, int n_glob) {
     uint32_t *q = reinterpret_cast<uint32_t *>(img);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
         const int n = n_local + 8 * i + 4 * hk;  // + c
-        q[((size_t)(n >> 4) * ld + m_local + lm) * 4 + ((n & 15) >> 2)] = pack_fp8x4(acc[4 * i + 0], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3], oscale);
+        float c0 = acc[4 * i + 0], c1 = acc[4 * i + 1], c2 = acc[4 * i + 2], c3 = acc[4 * i + 3];
+        ft_epi4<EPI>(c0, c1, c2, c3, e, n_glob + 8 * i, hk);
+        q[((size_t)(n >> 4) * ld + m_local + lm) * 4 + ((n & 15) >> 2)] = pack_fp8x4(c0, c1, c2, c3, oscale);
     }
 }
 
-template <int G1 /* FC1 groups of 64 k */>
-__global__ void __launch_bounds__(512) fr_fused_tile_f8_kernel(const FrFusedArgs a) {
+template <int G1 /* FC1 groups of 64 k */, bool EPI>
+__device__ __forceinline__ void fused_tile_f8_body(const FrFusedArgs &a) {
     extern __shared__ uint4 lds[];
     constexpr int MT = 2, T2W = 2, LD = 32 * MT + 1, TI = 32 * MT;
     constexpr int KE1 = 4 * G1;                       // q16 rows of the (padded) record
@@ -1042,7 +1194,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_f8_kernel(const FrFusedArgs
         ft8_gemm_ct<1, MT, (G1 < 8 ? G1 : 8), G1>(acc1, W1, c * 256 + 32 * wave, Xf, LD, 0, 0, hk, lm, 127 - a.e_w[0], 127 - a.e_act[0]);
         uint4 *R1 = R1b[c & 1];  // double-buffered: one barrier per chunk
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) ft8_store_tile(R1, LD, acc1[0][mt], 32 * wave, 32 * mt, hk, lm, os1);
+        for (int mt = 0; mt < MT; mt++) ft8_store_tile<EPI>(R1, LD, acc1[0][mt], 32 * wave, 32 * mt, hk, lm, os1, a.epi[0], c * 256 + 32 * wave);
         __syncthreads();
         // FC2: K range [256 c, 256 c + 256) = 4 groups of 64 k
         ft8_gemm_ct<T2W, MT, 4, 4>(acc2, W2, 32 * T2W * wave, R1, LD, 0, 4 * c, hk, lm, 127 - a.e_w[1], 127 - a.e_act[1]);
@@ -1051,7 +1203,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_f8_kernel(const FrFusedArgs
 #pragma unroll
     for (int t = 0; t < T2W; t++)
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) ft8_store_tile(R2, LD, acc2[t][mt], 32 * (T2W * wave + t), 32 * mt, hk, lm, os2);
+        for (int mt = 0; mt < MT; mt++) ft8_store_tile<EPI>(R2, LD, acc2[t][mt], 32 * (T2W * wave + t), 32 * mt, hk, lm, os2, a.epi[1], 32 * (T2W * wave + t));
     __syncthreads();
 
     f32x16 acc3[1][MT];
@@ -1061,7 +1213,7 @@ __global__ void __launch_bounds__(512) fr_fused_tile_f8_kernel(const FrFusedArgs
         for (int i = 0; i < 16; i++) acc3[0][mt][i] = 0.0f;
     ft8_gemm_ct<1, MT, 8, 8>(acc3, W3, 32 * wave, R2, LD, 0, 0, hk, lm, 127 - a.e_w[2], 127 - a.e_act[2]);  // H2 / 64 = 8 groups
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++) ft8_store_tile(R3, LD, acc3[0][mt], 32 * wave, 32 * mt, hk, lm, os3);
+    for (int mt = 0; mt < MT; mt++) ft8_store_tile<EPI>(R3, LD, acc3[0][mt], 32 * wave, 32 * mt, hk, lm, os3, a.epi[2], 32 * wave);
     __syncthreads();
     {   // score[m] = 2^-e3 * sum_n wout[n] * e4m3(R3)[n][m]: 64 items x 8 slices of 2 q16 rows, fp32 master weights, fixed order
         const int il = tid & 63, sl = tid >> 6;
@@ -1086,20 +1238,42 @@ __global__ void __launch_bounds__(512) fr_fused_tile_f8_kernel(const FrFusedArgs
             float t = part[tid];
 #pragma unroll
             for (int i = 1; i < 8; i++) t += part[i * 64 + tid];
-            bt.scores[m0 + tid] = t * __builtin_ldexpf(1.0f, -a.e_act[3]);
+            t *= __builtin_ldexpf(1.0f, -a.e_act[3]);
+            t = ft_out_bias<EPI>(a, t);
+            bt.scores[m0 + tid] = t;
         }
     }
 }
+
+#ifndef FR_EPI_FORMS
+template <int G1>
+__global__ void __launch_bounds__(512) fr_fused_tile_f8_kernel(const FrFusedArgs a) {
+    fused_tile_f8_body<G1, false>(a);
+}
+#else
+template <int G1>
+__global__ void __launch_bounds__(512) fr_epi_tile_f8_kernel(const FrFusedArgs a) {
+    fused_tile_f8_body<G1, true>(a);
+}
+#endif
 
 bool frk_fused_f8_ok(int K, int H1, int H2, int H3) { return (K == 352 || K == 880) && H1 % 256 == 0 && H2 == 512 && H3 == 256; }
 
 template <int G1>
 static int fused_f8_launch_inst(const FrFusedArgs &a, hipStream_t s) {
     static FrLdsAttrOnce lds_once;  // per instantiation, per device
-    if (int rc_ = fr_allow_full_lds(&fr_fused_tile_f8_kernel<G1>, lds_once)) return rc_;
     const size_t rows1 = 4 * G1 + 32, rows2 = (size_t)(a.H2 / 16) + (size_t)(a.H3 / 16) + 2;  // + 2 rows: 512 floats of reduction scratch
+#ifdef FR_EPI_FORMS
+    if (!fused_has_epi(a)) FR_NO_DEFAULT_FORM();
+    if (int rc_ = fr_allow_full_lds(&fr_epi_tile_f8_kernel<G1>, lds_once)) return rc_;
+    fr_epi_tile_f8_kernel<G1><<<dim3(a.n_batches * a.tiles_per_batch), dim3(512), (rows1 > rows2 ? rows1 : rows2) * 65 * 16, s>>>(a);
+    fr_note_kernel("fr_epi_tile_f8_kernel<%d>", G1);
+#else
+    if (fused_has_epi(a)) return fused_epi_forward(a, FR_EPI_KIND_FP8, s);
+    if (int rc_ = fr_allow_full_lds(&fr_fused_tile_f8_kernel<G1>, lds_once)) return rc_;
     fr_fused_tile_f8_kernel<G1><<<dim3(a.n_batches * a.tiles_per_batch), dim3(512), (rows1 > rows2 ? rows1 : rows2) * 65 * 16, s>>>(a);
     fr_note_kernel("fr_fused_tile_f8_kernel<%d>", G1);
+#endif
     KCHECK();
     return FR_OK;
 }
@@ -1110,3 +1284,16 @@ int frk_fused_f8_launch(const FrFusedArgs &a, hipStream_t s) {
     if (a.K == 880) return fused_f8_launch_inst<14>(a, s);
     FR_FAIL(FR_ERR_INVALID, "no fp8 fused instantiation for K=%d", a.K);
 }
+
+#ifdef FR_EPI_FORMS
+// The companion's one export: the epilogue form of launcher `kind` on `stream` (a hipStream_t); the kernel's name (as fr_worker_last_kernel reports it)
+// goes to name[0 .. name_len).  -> 0, or the hipError_t value (hipErrorInvalidValue: a shape without an instantiation).
+extern "C" __attribute__((visibility("default"))) int fr_epi_fused_launch(const FrFusedArgs *a, int kind, void *stream, char *name, size_t name_len) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    fr_epi_noted[0] = 0, fr_epi_hip_error = 0;
+    const int rc = kind == FR_EPI_KIND_F32 ? frk_fused_launch(*a, s) : kind == FR_EPI_KIND_F32_M2 ? frk_fused_m2_launch(*a, s) :
+                   kind == FR_EPI_KIND_BF16 ? frk_fused_h_launch(*a, s) : kind == FR_EPI_KIND_FP8 ? frk_fused_f8_launch(*a, s) : (int)FR_ERR_INVALID;
+    if (name && name_len) snprintf(name, name_len, "%s", fr_epi_noted);
+    return fr_epi_status(rc);
+}
+#endif

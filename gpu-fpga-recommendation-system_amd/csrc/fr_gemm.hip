@@ -1,5 +1,27 @@
 #include "fr_device.h"
 
+// (two builds: see fr_device.h)
+#ifdef FR_EPI_FORMS
+#include <cstdio>
+#define fc_lp_gemm_kernel fc_epi_lp_gemm_kernel
+#define fc_lp_gemm_out_kernel fc_epi_lp_gemm_out_kernel
+#define fc_pp_gemm_kernel fc_epi_pp_gemm_kernel
+#define fc_pp_gemm_n128_kernel fc_epi_pp_gemm_n128_kernel
+#define FR_GN(x) "fc_epi_" x
+#define FR_EPI_KPARAM , const FrEpi epi
+#define FR_EPI_KARG(e) , e
+#define FR_EPI_KVAL epi
+#define FR_EPI_KPARAM2 , const FrEpi epi, const FrEpi epi_out
+#define FR_EPI_KVAL2 , epi_out
+#else
+#define FR_GN(x) "fc_" x
+#define FR_EPI_KPARAM
+#define FR_EPI_KARG(e)
+#define FR_EPI_KVAL FrEpi{nullptr, 0, 0}
+#define FR_EPI_KPARAM2
+#define FR_EPI_KVAL2
+#endif
+
 // ===================================================================================================
 // fc_lp_gemm_kernel<PREC>: LDS-tiled GEMM for low-precision layers that fill the chip on their own (Model-C FC1 at batch 4096).
 // PREC 0 = fp32 (q4 elements, v_mfma_f32_32x32x2_f32: the same k-ordered exact-f32 sums as the other fp32 kernels, full K per
@@ -32,7 +54,8 @@ struct FrTailArgs {
 
 template <int PREC, int MU, int GN, int S, int GR, int MF = 32, int EPI = 0>
 __device__ __forceinline__ void lp_gemm_body(uint4 *glds, const uint4 *__restrict__ W, const uint4 *__restrict__ X, void *__restrict__ Y, int KE /* element rows */,
-                                             int N, int ldm, int sc_a, int sc_b, float oscale, const FrTailArgs tail = FrTailArgs{}) {
+                                             int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi epi, const FrTailArgs tail = FrTailArgs{},
+                                             const FrEpi epi_out = FrEpi{nullptr, 0, 0} /* EPI == 1: b_3 in bias[0], added to the finished score (after out_scale) */) {
     typedef __attribute__((address_space(3))) void *lds_ptr;
     constexpr int GM = 128 * MU, ROW = GN + GM, TN = GN / 64;  // elements per staged row: GN of W, GM of X; TN n tiles of 32 per wave
     const int tid = threadIdx.x, lane = tid & 63;
@@ -232,6 +255,11 @@ __device__ __forceinline__ void lp_gemm_body(uint4 *glds, const uint4 *__restric
                 b_[j] = __uint_as_float(sw[1]);
             }
             const int slice = 4 * wn + 2 * p + h;       // = (n / 32) of the lane's tile: n0 == 0, the wave's tiles start at 128 wn
+#pragma unroll
+            for (int i = 0; i < 4; i++) {               // FC3's epilogue on the fp32 sums, before R3 is rounded: a_ holds n = 32 slice + 8 i + c, b_ n = 32 slice + 8 i + 4 + c
+                fr_epi4<2, 32>(a_[4 * i + 0], a_[4 * i + 1], a_[4 * i + 2], a_[4 * i + 3], epi, 32 * (4 * wn + 2 * p) + 8 * i, h);
+                fr_epi4<2, 32>(b_[4 * i + 0], b_[4 * i + 1], b_[4 * i + 2], b_[4 * i + 3], epi, 32 * (4 * wn + 2 * p) + 8 * i + 4, h);
+            }
             float sacc = 0.0f;
             if constexpr (PREC == 1) {
                 const uint4 *wv = reinterpret_cast<const uint4 *>(tail.wout) + 4 * slice;   // 8 bf16 per element
@@ -270,7 +298,9 @@ __device__ __forceinline__ void lp_gemm_body(uint4 *glds, const uint4 *__restric
             float t = red[tid];
 #pragma unroll
             for (int q = 1; q < 8; q++) t += red[q * 128 + tid];
-            tail.scores[m0 + tid] = PREC == 2 ? t * tail.out_scale : t;
+            if (PREC == 2) t *= tail.out_scale;
+            if (FR_HAS_EPI && epi_out.bias) t += epi_out.bias[0];
+            tail.scores[m0 + tid] = t;
         }
         return;
     }
@@ -280,12 +310,14 @@ __device__ __forceinline__ void lp_gemm_body(uint4 *glds, const uint4 *__restric
         for (int t = 0; t < 2 * TN; t++)
 #pragma unroll
             for (int u = 0; u < 2 * MU; u++) {
-                const f32x4_t &c = acc16[t][u];
+                f32x4_t c = acc16[t][u];
                 const int m = m0 + wm * 32 * MU + 16 * u + (lane & 15);
                 const int n = n0 + wn * 32 * TN + 16 * t + 4 * (lane >> 4);
+                float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+                fr_epi4<4>(c0, c1, c2, c3, epi, n0 + wn * 32 * TN + 16 * t, lane >> 4);   // the layer's epilogue on the fp32 sums, before the one rounding
                 uint2 hv;
-                hv.x = pack_bf16x2(c[0], c[1]);
-                hv.y = pack_bf16x2(c[2], c[3]);
+                hv.x = pack_bf16x2(c0, c1);
+                hv.y = pack_bf16x2(c2, c3);
                 reinterpret_cast<uint2 *>(Y)[((size_t)(n >> 3) * ldm + m) * 2 + ((n & 7) >> 2)] = hv;
             }
         return;
@@ -299,16 +331,17 @@ __device__ __forceinline__ void lp_gemm_body(uint4 *glds, const uint4 *__restric
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 const int n = n0 + wn * 32 * TN + 32 * t + 8 * i + 4 * h;  // + c
+                float c0 = c[4 * i + 0], c1 = c[4 * i + 1], c2 = c[4 * i + 2], c3 = c[4 * i + 3];
+                fr_epi4(c0, c1, c2, c3, epi, n0 + wn * 32 * TN + 32 * t + 8 * i, h);   // the layer's epilogue on the fp32 sums (fp8: real units), before the one rounding
                 if constexpr (PREC == 0) {  // q4 element (n / 4) of the next layer's operand
-                    reinterpret_cast<float4 *>(Y)[(size_t)(n >> 2) * ldm + m] = make_float4(c[4 * i + 0], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+                    reinterpret_cast<float4 *>(Y)[(size_t)(n >> 2) * ldm + m] = make_float4(c0, c1, c2, c3);
                 } else if constexpr (PREC == 1) {
                     uint2 hv;
-                    hv.x = pack_bf16x2(c[4 * i + 0], c[4 * i + 1]);
-                    hv.y = pack_bf16x2(c[4 * i + 2], c[4 * i + 3]);
+                    hv.x = pack_bf16x2(c0, c1);
+                    hv.y = pack_bf16x2(c2, c3);
                     reinterpret_cast<uint2 *>(Y)[((size_t)(n >> 3) * ldm + m) * 2 + ((n & 7) >> 2)] = hv;
                 } else {
-                    reinterpret_cast<uint32_t *>(Y)[((size_t)(n >> 4) * ldm + m) * 4 + ((n & 15) >> 2)] =
-                        pack_fp8x4(c[4 * i + 0], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3], oscale);
+                    reinterpret_cast<uint32_t *>(Y)[((size_t)(n >> 4) * ldm + m) * 4 + ((n & 15) >> 2)] = pack_fp8x4(c0, c1, c2, c3, oscale);
                 }
             }
         }
@@ -316,17 +349,17 @@ __device__ __forceinline__ void lp_gemm_body(uint4 *glds, const uint4 *__restric
 
 template <int PREC, int MU, int GN, int S, int GR = FR_GR, int MF = 32>
 __global__ void __launch_bounds__(512) fc_lp_gemm_kernel(const uint4 *__restrict__ W, const uint4 *__restrict__ X, void *__restrict__ Y, int KE /* element rows */,
-                                                         int N, int ldm, int sc_a, int sc_b, float oscale) {
+                                                         int N, int ldm, int sc_a, int sc_b, float oscale FR_EPI_KPARAM) {
     extern __shared__ uint4 glds[];
-    lp_gemm_body<PREC, MU, GN, S, GR, MF>(glds, W, X, Y, KE, N, ldm, sc_a, sc_b, oscale);
+    lp_gemm_body<PREC, MU, GN, S, GR, MF>(glds, W, X, Y, KE, N, ldm, sc_a, sc_b, oscale, FR_EPI_KVAL);
 }
 
 // FC3 + the output layer: 256 (n) x 128 (m) tiles, EPI = 1 (see FrTailArgs)
 template <int PREC, int S>
 __global__ void __launch_bounds__(512) fc_lp_gemm_out_kernel(const uint4 *__restrict__ W, const uint4 *__restrict__ X, int KE, int N, int ldm, int sc_a, int sc_b, float oscale,
-                                                             const FrTailArgs tail) {
+                                                             const FrTailArgs tail FR_EPI_KPARAM2) {
     extern __shared__ uint4 glds[];
-    lp_gemm_body<PREC, 1, 256, S, FR_GR, 32, 1>(glds, W, X, nullptr, KE, N, ldm, sc_a, sc_b, oscale, tail);
+    lp_gemm_body<PREC, 1, 256, S, FR_GR, 32, 1>(glds, W, X, nullptr, KE, N, ldm, sc_a, sc_b, oscale, FR_EPI_KVAL, tail FR_EPI_KVAL2);
 }
 
 // ===================================================================================================
@@ -345,7 +378,7 @@ __global__ void __launch_bounds__(512) fc_lp_gemm_out_kernel(const uint4 *__rest
 // ===================================================================================================
 template <int PREC, int D, int NT, int GN, int PR>
 __device__ __forceinline__ void pp_gemm_body(uint4 *glds, const uint4 *__restrict__ W, const uint4 *__restrict__ X, void *__restrict__ Y, int KE /* element rows */,
-                                             int N, int ldm, int sc_a, int sc_b, float oscale, int ablate) {
+                                             int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi epi, int ablate) {
     static_assert(PREC == 1 || PREC == 2, "bf16 / fp8");
     static_assert((GN == 256 && PR == 4) || (GN == 128 && PR == 8), "256 x 256 tiles in sub-steps of 4 element rows, 128 x 256 tiles in sub-steps of 8");
 #ifndef FR_EXPERIMENTS
@@ -538,12 +571,14 @@ __device__ __forceinline__ void pp_gemm_body(uint4 *glds, const uint4 *__restric
         for (int t = 0; t < NT16; t++)
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const f32x4_t &c = acc16[4 * t + u];
+                f32x4_t c = acc16[4 * t + u];
                 const int m = m0 + wm * 64 + 16 * u + (lane & 15);
                 const int n = n0 + wn * WN + 16 * t + 4 * (lane >> 4);
+                float c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+                fr_epi4<4>(c0, c1, c2, c3, epi, n0 + wn * WN + 16 * t, lane >> 4);   // the layer's epilogue on the fp32 sums, before the one rounding
                 uint2 hv;
-                hv.x = pack_bf16x2(c[0], c[1]);
-                hv.y = pack_bf16x2(c[2], c[3]);
+                hv.x = pack_bf16x2(c0, c1);
+                hv.y = pack_bf16x2(c2, c3);
                 reinterpret_cast<uint2 *>(Y)[((size_t)(n >> 3) * ldm + m) * 2 + ((n & 7) >> 2)] = hv;
             }
     } else {
@@ -557,8 +592,9 @@ __device__ __forceinline__ void pp_gemm_body(uint4 *glds, const uint4 *__restric
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const int n = n0 + wn * WN + 32 * t + 8 * i + 4 * h;
-                    reinterpret_cast<uint32_t *>(Y)[((size_t)(n >> 4) * ldm + m) * 4 + ((n & 15) >> 2)] =
-                        pack_fp8x4(c[4 * i + 0], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3], oscale);
+                    float c0 = c[4 * i + 0], c1 = c[4 * i + 1], c2 = c[4 * i + 2], c3 = c[4 * i + 3];
+                    fr_epi4(c0, c1, c2, c3, epi, n0 + wn * WN + 32 * t + 8 * i, h);
+                    reinterpret_cast<uint32_t *>(Y)[((size_t)(n >> 4) * ldm + m) * 4 + ((n & 15) >> 2)] = pack_fp8x4(c0, c1, c2, c3, oscale);
                 }
             }
     }
@@ -566,18 +602,18 @@ __device__ __forceinline__ void pp_gemm_body(uint4 *glds, const uint4 *__restric
 
 template <int PREC, int D, int NT>
 __global__ void __launch_bounds__(512) fc_pp_gemm_kernel(const uint4 *__restrict__ W, const uint4 *__restrict__ X, void *__restrict__ Y, int KE /* element rows */,
-                                                         int N, int ldm, int sc_a, int sc_b, float oscale, int ablate) {
+                                                         int N, int ldm, int sc_a, int sc_b, float oscale, int ablate FR_EPI_KPARAM) {
     extern __shared__ uint4 glds[];
-    pp_gemm_body<PREC, D, NT, 256, 4>(glds, W, X, Y, KE, N, ldm, sc_a, sc_b, oscale, ablate);
+    pp_gemm_body<PREC, D, NT, 256, 4>(glds, W, X, Y, KE, N, ldm, sc_a, sc_b, oscale, FR_EPI_KVAL, ablate);
 }
 
 // the same on 128 (n) x 256 (m) tiles (64 x 64 wave tiles) in sub-steps of 8 element rows (two k groups per phase: 32 / 8 MFMAs per wave again;
 // D = 2: 144 KiB): layers whose 256 x 256 tiles would not cover their share of the chip -- Model-C FC1 for a lone worker
 template <int PREC, int D>
 __global__ void __launch_bounds__(512) fc_pp_gemm_n128_kernel(const uint4 *__restrict__ W, const uint4 *__restrict__ X, void *__restrict__ Y, int KE /* element rows */,
-                                                              int N, int ldm, int sc_a, int sc_b, float oscale, int ablate) {
+                                                              int N, int ldm, int sc_a, int sc_b, float oscale, int ablate FR_EPI_KPARAM) {
     extern __shared__ uint4 glds[];
-    pp_gemm_body<PREC, D, 0, 128, 8>(glds, W, X, Y, KE, N, ldm, sc_a, sc_b, oscale, ablate);
+    pp_gemm_body<PREC, D, 0, 128, 8>(glds, W, X, Y, KE, N, ldm, sc_a, sc_b, oscale, FR_EPI_KVAL, ablate);
 }
 
 // FC3 + the output layer as ONE launch (fc_lp_gemm_out_kernel): wherever FC3 would run as a GEMM launch of its own (large batches) in the
@@ -595,8 +631,19 @@ bool frk_fc_tail_ok(int precision, int K, int N, int ldm) {
     return true;
 }
 
-int frk_fc_tail(int precision, const void *W3, const void *R2, const void *wout, float *scores, int K, int N, int ldm, int batch, int e_w, int e_in, int e_r3, hipStream_t s) {
+int frk_fc_tail(int precision, const void *W3, const void *R2, const void *wout, float *scores, int K, int N, int ldm, int batch, int e_w, int e_in, int e_r3, const FrEpi &epi3, const FrEpi &epi_out,
+                hipStream_t s) {
     if (!frk_fc_tail_ok(precision, K, N, ldm)) FR_FAIL(FR_ERR_INVALID, "internal: %d x %d x %d is not a fused-tail layer", K, N, ldm);
+#ifndef FR_EPI_FORMS
+    if (epi3.bias || epi3.relu || epi_out.bias) {   // a context with an epilogue: the epilogue form, in the companion code object
+        const FrEpiGemmCall c{1, precision, W3, R2, const_cast<void *>(wout), scores, K, N, ldm, batch, e_w, e_in, e_r3, 1, 0, epi3, epi_out};
+        char name[96] = "";
+        const int e = fr_epi_gemm_launch(&c, s, name, sizeof(name));
+        if (e) FR_FAIL(FR_ERR_HIP, "launch of the epilogue form of the FC3 + output kernel failed: %s", hipGetErrorString((hipError_t)e));
+        fr_note_kernel("%s", name);
+        return FR_OK;
+    }
+#endif
     const int KE = precision == FR_FC_FP8 ? (K + 63) / 64 * 4 : K / 8;
     const size_t lds = (size_t)FR_GSTAGES * FR_GR * (256 + 128) * 16;
     dim3 grid(ldm / 128);
@@ -604,16 +651,16 @@ int frk_fc_tail(int precision, const void *W3, const void *R2, const void *wout,
     if (precision == FR_FC_BF16) {
         static FrLdsAttrOnce once1;
         if (int rc_ = fr_allow_full_lds(&fc_lp_gemm_out_kernel<1, FR_GSTAGES>, once1)) return rc_;
-        fc_lp_gemm_out_kernel<1, FR_GSTAGES><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(W3), reinterpret_cast<const uint4 *>(R2), KE, N, ldm, 0, 0, 1.0f, t);
+        fc_lp_gemm_out_kernel<1, FR_GSTAGES><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(W3), reinterpret_cast<const uint4 *>(R2), KE, N, ldm, 0, 0, 1.0f, t FR_EPI_KARG(epi3) FR_EPI_KARG(epi_out));
         KCHECK();
-        fr_note_kernel("fc_lp_gemm_out_kernel<1, %d>", FR_GSTAGES);
+        fr_note_kernel(FR_GN("lp_gemm_out_kernel<1, %d>"), FR_GSTAGES);
     } else {
         static FrLdsAttrOnce once2;
         if (int rc_ = fr_allow_full_lds(&fc_lp_gemm_out_kernel<2, FR_GSTAGES>, once2)) return rc_;
         fc_lp_gemm_out_kernel<2, FR_GSTAGES><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(W3), reinterpret_cast<const uint4 *>(R2), KE, N, ldm, 127 - e_w, 127 - e_in,
-                                                                         ldexpf(1.0f, e_r3), t);
+                                                                         ldexpf(1.0f, e_r3), t FR_EPI_KARG(epi3) FR_EPI_KARG(epi_out));
         KCHECK();
-        fr_note_kernel("fc_lp_gemm_out_kernel<2, %d>", FR_GSTAGES);
+        fr_note_kernel(FR_GN("lp_gemm_out_kernel<2, %d>"), FR_GSTAGES);
     }
     return FR_OK;
 }
@@ -660,65 +707,65 @@ static int lp_gemm_mu(int precision, int K, int N, int ldm, int width = 1, bool 
 bool frk_fc_lp_gemm_ok(int precision, int K, int N, int ldm) { return lp_gemm_mu(precision, K, N, ldm) != 0; }
 
 template <int PREC, int MU, int GN, int S, int GR = FR_GR, int MF = 32>
-static int lp_gemm_launch(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, hipStream_t s) {
+static int lp_gemm_launch(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi &epi, hipStream_t s) {
     static FrLdsAttrOnce lds_once;  // per instantiation, per device
     const size_t lds = (size_t)S * GR * (GN + 128 * MU) * 16;
     if (int rc_ = fr_allow_full_lds(&fc_lp_gemm_kernel<PREC, MU, GN, S, GR, MF>, lds_once)) return rc_;
     dim3 grid((N / GN) * (ldm / (128 * MU)));
-    fc_lp_gemm_kernel<PREC, MU, GN, S, GR, MF><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(Wp), reinterpret_cast<const uint4 *>(Xp), Yp, KE, N, ldm, sc_a, sc_b, oscale);
+    fc_lp_gemm_kernel<PREC, MU, GN, S, GR, MF><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(Wp), reinterpret_cast<const uint4 *>(Xp), Yp, KE, N, ldm, sc_a, sc_b, oscale FR_EPI_KARG(epi));
     KCHECK();
-    fr_note_kernel("fc_lp_gemm_kernel<%d, %d, %d, %d, %d, %d>", PREC, MU, GN, S, GR, MF);   // as rocprofv3 prints it
+    fr_note_kernel(FR_GN("lp_gemm_kernel<%d, %d, %d, %d, %d, %d>"), PREC, MU, GN, S, GR, MF);   // as rocprofv3 prints it
     return FR_OK;
 }
 
 template <int PREC, int D, int NT>
-static int pp_gemm_launch_nt(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, hipStream_t s) {
+static int pp_gemm_launch_nt(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi &epi, hipStream_t s) {
     static FrLdsAttrOnce lds_once;
     const size_t lds = (size_t)(D + 1) * 4 * 512 * 16;
     if (int rc_ = fr_allow_full_lds(&fc_pp_gemm_kernel<PREC, D, NT>, lds_once)) return rc_;
     dim3 grid((N / 256) * (ldm / 256));
     fc_pp_gemm_kernel<PREC, D, NT><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(Wp), reinterpret_cast<const uint4 *>(Xp), Yp, KE, N, ldm, sc_a, sc_b, oscale,
-                                                                FR_KNOB_ONCE("PP_ABLATE", 0));
+                                                                FR_KNOB_ONCE("PP_ABLATE", 0) FR_EPI_KARG(epi));
     KCHECK();
-    fr_note_kernel("fc_pp_gemm_kernel<%d, %d, %d>", PREC, D, NT);
+    fr_note_kernel(FR_GN("pp_gemm_kernel<%d, %d, %d>"), PREC, D, NT);
     return FR_OK;
 }
 
 template <int PREC, int D>
-static int pp_gemm_n128_launch(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, hipStream_t s) {
+static int pp_gemm_n128_launch(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi &epi, hipStream_t s) {
     static FrLdsAttrOnce lds_once;
     const size_t lds = (size_t)(D + 1) * 8 * (128 + 256) * 16;
     if (int rc_ = fr_allow_full_lds(&fc_pp_gemm_n128_kernel<PREC, D>, lds_once)) return rc_;
     dim3 grid((N / 128) * (ldm / 256));
     fc_pp_gemm_n128_kernel<PREC, D><<<grid, dim3(512), lds, s>>>(reinterpret_cast<const uint4 *>(Wp), reinterpret_cast<const uint4 *>(Xp), Yp, KE, N, ldm, sc_a, sc_b, oscale,
-                                                                 FR_KNOB_ONCE("PP_ABLATE", 0));
+                                                                 FR_KNOB_ONCE("PP_ABLATE", 0) FR_EPI_KARG(epi));
     KCHECK();
-    fr_note_kernel("fc_pp_gemm_n128_kernel<%d, %d>", PREC, D);
+    fr_note_kernel(FR_GN("pp_gemm_n128_kernel<%d, %d>"), PREC, D);
     return FR_OK;
 }
 
 template <int PREC, int D>
-static int pp_gemm_launch(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, hipStream_t s) {
-    if (N == 2048) return pp_gemm_launch_nt<PREC, D, 8>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-    if (N == 512) return pp_gemm_launch_nt<PREC, D, 2>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-    return pp_gemm_launch_nt<PREC, D, 0>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+static int pp_gemm_launch(const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi &epi, hipStream_t s) {
+    if (N == 2048) return pp_gemm_launch_nt<PREC, D, 8>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+    if (N == 512) return pp_gemm_launch_nt<PREC, D, 2>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+    return pp_gemm_launch_nt<PREC, D, 0>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
 }
 
 template <int PREC>
-static int lp_gemm_tile(int mu, const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, hipStream_t s) {
+static int lp_gemm_tile(int mu, const void *Wp, const void *Xp, void *Yp, int KE, int N, int ldm, int sc_a, int sc_b, float oscale, const FrEpi &epi, hipStream_t s) {
     if constexpr (PREC != 0) {
         if (mu == 6) {   // the 256 x 256 tile: fc_pp_gemm_kernel, the SIMD's two waves in opposite phases; 3 sub-steps ahead in bf16, 2 in fp8
                          // (profiles/r05_experiments.md section 13).  lp_gemm_mu guarantees KE % 8 == 0 and KE >= 16: whole sub-steps, a full pipeline.
 #ifdef FR_EXPERIMENTS
             const int pp = FR_KNOB_ONCE("LP_GEMM_PP", (PREC == 1 ? 3 : 2));   // 0 = fc_lp_gemm_kernel's plain loop on the same tile (the A/B partner: same bits)
-            if (pp == 3) return pp_gemm_launch<PREC, 3>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-            if (pp == 2) return pp_gemm_launch<PREC, 2>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+            if (pp == 3) return pp_gemm_launch<PREC, 3>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+            if (pp == 2) return pp_gemm_launch<PREC, 2>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
             if constexpr (PREC == 1) {
-                if (FR_KNOB_ONCE("LP_GEMM_MF16", 1)) return lp_gemm_launch<1, 2, 256, FR_GSTAGES, FR_GR, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+                if (FR_KNOB_ONCE("LP_GEMM_MF16", 1)) return lp_gemm_launch<1, 2, 256, FR_GSTAGES, FR_GR, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
             }
-            return lp_gemm_launch<PREC, 2, 256, FR_GSTAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+            return lp_gemm_launch<PREC, 2, 256, FR_GSTAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
 #else
-            return pp_gemm_launch<PREC, (PREC == 1 ? 3 : 2)>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+            return pp_gemm_launch<PREC, (PREC == 1 ? 3 : 2)>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
 #endif
         }
     }
@@ -726,10 +773,10 @@ static int lp_gemm_tile(int mu, const void *Wp, const void *Xp, void *Yp, int KE
 #ifdef FR_EXPERIMENTS
         // FR_LP_GEMM_PP128=0 in bf16: the plain loop on the 16x16x32 MFMAs of the phased-waves body -- its A/B partner, same bits
         if constexpr (PREC == 1) {
-            if (FR_KNOB_ONCE("LP_GEMM_PP128", 1) == 0) return lp_gemm_launch<1, 2, 128, FR_GSTAGES, FR_GR, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+            if (FR_KNOB_ONCE("LP_GEMM_PP128", 1) == 0) return lp_gemm_launch<1, 2, 128, FR_GSTAGES, FR_GR, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
         }
 #endif
-        return lp_gemm_launch<PREC, 2, 128, FR_GSTAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+        return lp_gemm_launch<PREC, 2, 128, FR_GSTAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
     }
     if (mu == 3) {
         // 4 stages pay in bf16 only (Model-C FC2 19.8 -> 14.7 us, end to end +2.5 %); in fp8 / f32 the larger LDS footprint costs more
@@ -740,35 +787,57 @@ static int lp_gemm_tile(int mu, const void *Wp, const void *Xp, void *Yp, int KE
         const int deep = FR_KNOB_ONCE("LP_GEMM_STAGES", STAGES);
         const int rows = FR_KNOB_ONCE("LP_GEMM_ROWS", 8);   // element rows per K step of the narrow tile
         if (rows == 16 && KE % 16 == 0 && KE / 16 >= 2) {
-            if (deep == 2) return lp_gemm_launch<PREC, 1, 64, 2, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-            return lp_gemm_launch<PREC, 1, 64, 3, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+            if (deep == 2) return lp_gemm_launch<PREC, 1, 64, 2, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+            return lp_gemm_launch<PREC, 1, 64, 3, 16>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
         }
-        if (rows == 32 && KE % 32 == 0 && KE / 32 >= 2) return lp_gemm_launch<PREC, 1, 64, 2, 32>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-        if (deep == 3) return lp_gemm_launch<PREC, 1, 64, 3>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-        if (deep == 5) return lp_gemm_launch<PREC, 1, 64, 5>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-        if (deep == 6) return lp_gemm_launch<PREC, 1, 64, 6>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
-        return deep == 2 ? lp_gemm_launch<PREC, 1, 64, 2>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s)
-                         : lp_gemm_launch<PREC, 1, 64, 4>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+        if (rows == 32 && KE % 32 == 0 && KE / 32 >= 2) return lp_gemm_launch<PREC, 1, 64, 2, 32>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+        if (deep == 3) return lp_gemm_launch<PREC, 1, 64, 3>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+        if (deep == 5) return lp_gemm_launch<PREC, 1, 64, 5>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+        if (deep == 6) return lp_gemm_launch<PREC, 1, 64, 6>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
+        return deep == 2 ? lp_gemm_launch<PREC, 1, 64, 2>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s)
+                         : lp_gemm_launch<PREC, 1, 64, 4>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
 #else
-        return lp_gemm_launch<PREC, 1, 64, STAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+        return lp_gemm_launch<PREC, 1, 64, STAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
 #endif
     }
-    return lp_gemm_launch<PREC, 1, 128, FR_GSTAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, s);
+    return lp_gemm_launch<PREC, 1, 128, FR_GSTAGES>(Wp, Xp, Yp, KE, N, ldm, sc_a, sc_b, oscale, epi, s);
 }
 
-int frk_fc_lp_gemm(int precision, const void *Wp, const void *Xp, void *Yp, int K, int N, int ldm, int e_w, int e_in, int e_out, int width, bool minor, hipStream_t s) {
+int frk_fc_lp_gemm(int precision, const void *Wp, const void *Xp, void *Yp, int K, int N, int ldm, int e_w, int e_in, int e_out, int width, bool minor, const FrEpi &epi, hipStream_t s) {
     const int mu = lp_gemm_mu(precision, K, N, ldm, width, minor);
     if (mu == 0) FR_FAIL(FR_ERR_INVALID, "internal: layer %d x %d x %d is not a GEMM-kernel layer", K, N, ldm);
+#ifndef FR_EPI_FORMS
+    if (epi.bias || epi.relu) {   // a context with an epilogue: the epilogue form of the same tile, in the companion code object
+        const FrEpiGemmCall c{0, precision, Wp, Xp, Yp, nullptr, K, N, ldm, 0, e_w, e_in, e_out, width, minor ? 1 : 0, epi, FrEpi{nullptr, 0, 0}};
+        char name[96] = "";
+        const int e = fr_epi_gemm_launch(&c, s, name, sizeof(name));
+        if (e) FR_FAIL(FR_ERR_HIP, "launch of the epilogue form of a GEMM layer failed: %s", hipGetErrorString((hipError_t)e));
+        fr_note_kernel("%s", name);
+        return FR_OK;
+    }
+#endif
     const int KE = precision == FR_FC_FP8 ? (K + 63) / 64 * 4 : (precision == FR_FC_BF16 ? K / 8 : K / 4);
-    if (precision == FR_FC_FP32) return lp_gemm_tile<0>(mu, Wp, Xp, Yp, KE, N, ldm, 0, 0, 1.0f, s);
+    if (precision == FR_FC_FP32) return lp_gemm_tile<0>(mu, Wp, Xp, Yp, KE, N, ldm, 0, 0, 1.0f, epi, s);
     // 128 x 256 layers (a lone worker's Model-C FC1: chain width 1) run the phased-waves body in 8-row sub-steps (lp_gemm_mu guarantees
     // KE % 8 == 0; KE >= 24: a full pipeline): bit-identical to fc_lp_gemm_kernel's plain loop on the same MFMAs, FC1 bf16 65.5 -> 59.6 us, fp8 32.5 -> 31.4 us
     // (profiles/r05_experiments.md section 13).  A layer of two K steps (KE == 16) and every other tile go to lp_gemm_tile; so does the
     // experiments build under FR_LP_GEMM_PP128=0 (the A/B partner).
     if (mu == 2 && FR_KNOB_ONCE("LP_GEMM_PP128", 1) && KE / 8 >= 3) {
-        if (precision == FR_FC_FP8) return pp_gemm_n128_launch<2, 2>(Wp, Xp, Yp, KE, N, ldm, 127 - e_w, 127 - e_in, ldexpf(1.0f, e_out), s);
-        return pp_gemm_n128_launch<1, 2>(Wp, Xp, Yp, KE, N, ldm, 0, 0, 1.0f, s);
+        if (precision == FR_FC_FP8) return pp_gemm_n128_launch<2, 2>(Wp, Xp, Yp, KE, N, ldm, 127 - e_w, 127 - e_in, ldexpf(1.0f, e_out), epi, s);
+        return pp_gemm_n128_launch<1, 2>(Wp, Xp, Yp, KE, N, ldm, 0, 0, 1.0f, epi, s);
     }
-    if (precision == FR_FC_FP8) return lp_gemm_tile<2>(mu, Wp, Xp, Yp, KE, N, ldm, 127 - e_w, 127 - e_in, ldexpf(1.0f, e_out), s);
-    return lp_gemm_tile<1>(mu, Wp, Xp, Yp, KE, N, ldm, 0, 0, 1.0f, s);
+    if (precision == FR_FC_FP8) return lp_gemm_tile<2>(mu, Wp, Xp, Yp, KE, N, ldm, 127 - e_w, 127 - e_in, ldexpf(1.0f, e_out), epi, s);
+    return lp_gemm_tile<1>(mu, Wp, Xp, Yp, KE, N, ldm, 0, 0, 1.0f, epi, s);
 }
+
+#ifdef FR_EPI_FORMS
+// the companion's export for the GEMM layers: -> 0 or the hipError_t value; the kernel's name goes to name[0 .. name_len)
+extern "C" __attribute__((visibility("default"))) int fr_epi_gemm_launch(const FrEpiGemmCall *c, void *stream, char *name, size_t name_len) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    fr_epi_noted[0] = 0, fr_epi_hip_error = 0;
+    const int rc = c->tail ? frk_fc_tail(c->precision, c->Wp, c->Xp, c->Yp, c->scores, c->K, c->N, c->ldm, c->batch, c->e_w, c->e_in, c->e_out, c->epi, c->epi_out, s)
+                           : frk_fc_lp_gemm(c->precision, c->Wp, c->Xp, c->Yp, c->K, c->N, c->ldm, c->e_w, c->e_in, c->e_out, c->width, c->minor != 0, c->epi, s);
+    if (name && name_len) snprintf(name, name_len, "%s", fr_epi_noted);
+    return fr_epi_status(rc);
+}
+#endif

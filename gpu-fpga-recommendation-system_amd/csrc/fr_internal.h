@@ -165,6 +165,16 @@ struct FrChunkDesc {
     int word0, n_words;        // the chunk's word range inside the item's destination row
 };
 
+// ---- per-layer epilogue (fr_ctx_set_epilogue, fleetrec_serving.h) --------------------------------------
+// What a kernel that finishes a layer applies to the layer's fp32 sums before it stores them: v = sum + bias[n] (ONE fp32 add after the whole
+// K sum), then ReLU, then the chain's own rounding.  Both members are wave-uniform kernel arguments; {NULL, 0} is the chain as it always was,
+// bit for bit (no add at all: -0 stays -0).  The output layer's entry carries b_3 in bias[0] and never an activation.
+struct FrEpi {
+    const float *bias;   // [N] fp32 (device memory; host memory on the CPU back-end) or NULL
+    int relu;            // 1: FR_ACT_RELU
+    int pad_;
+};
+
 // ---- pipelined FC chain: launch arguments (see fr_pipeline.hip) ------------------------------------
 constexpr int FR_N_STAGES = 5;  // gather | FC1 | FC2 | FC3 | out
 
@@ -185,7 +195,7 @@ struct FrStageArgs {
     const float *w;   // weights Wt[K][N] (FC) or w[H] (out)
 };
 
-struct FrPipeArgs {
+struct FrPipeCore {   // what the kernels of libfleetrec.so take: the parent's kernel arguments, byte for byte
     FrStageArgs st[FR_N_STAGES];
     int n_blocks;
     // gather stage
@@ -198,6 +208,14 @@ struct FrPipeArgs {
     int *err_flag;
     // diagnostic build aid (NULL in normal operation): per workgroup {s_memrealtime at entry, at exit, stage, hw id}
     unsigned long long *stamps;
+};
+struct FrPipeArgs : FrPipeCore {
+    // Epilogues per stage (pipeline_step, fr_api.cpp).  Only the epilogue forms of the kernels (libfleetrec_epi.so) take this part as kernel arguments;
+    // has_epi == 0 sends the launch to the kernels of libfleetrec.so, which take the FrPipeCore slice.  epi[s]: stage s's own layer, applied where the stage
+    // stores WHOLE sums (nsplit == 1; the out stage: bias[0] added to the score) -- left {NULL, 0} on a split stage, whose partials are stored raw.
+    // epi_in[s]: the PRODUCING layer's, set only where stage s reads two partials (nparts_in == 2): it applies it to their sum while loading.
+    FrEpi epi[FR_N_STAGES], epi_in[FR_N_STAGES];
+    int has_epi;
 };
 
 // ---- fused item-tile kernel: launch arguments (see fr_fused.hip) -------------------------------------
@@ -229,7 +247,31 @@ struct FrFusedArgs {
     int K, H1, H2, H3;
     int e_w[3], e_act[4];        // fp8 kernel only: quantisation exponents (weights W1..W3; activations X, R1, R2, R3)
     unsigned long long *stamps;  // diagnostics only (NULL normally): 16 s_memrealtime stamps per workgroup
+    // per-layer epilogues (FC1, FC2, FC3, output).  All {NULL, 0} without fr_ctx_set_epilogue: the launchers run fr_fused_tile_*_kernel.  With one, EVERY
+    // bias pointer is set (a layer without a bias points at -0.0f values) and the launchers run the branch-free fr_epi_tile_*_kernel forms.
+    // fr_fused_tile_hs_kernel does not read them: a context with an epilogue never launches it (fused_flush, fr_api.cpp)
+    FrEpi epi[4];
 };
+
+// ---- epilogue forms of the FC-chain kernels (libfleetrec_epi.so, the fourth companion code object) ------------------------------------------------
+// fr_fused.hip, fr_pipeline.hip and fr_gemm.hip built a second time with -DFR_EPI_FORMS: the same bodies under names of their own (fr_epi_tile_*_kernel,
+// fr_epi_pipeline_kernel, fr_epi_gather_out_kernel, fc_epi_*gemm*_kernel), which apply the per-layer epilogues; the kernels of libfleetrec.so carry no
+// epilogue code.  Three exported launchers, one per file; each enqueues on `stream` (a hipStream_t), names the kernel in name[0 .. name_len) and
+// -> 0 or the hipError_t value.  (The FR_* experiment knobs do not reach them: the companion is a product build, also beside libfleetrec_exp.so.)
+// fr_epi_fused_launch: the epilogue form of the fused launcher `kind`.
+constexpr int FR_EPI_KIND_F32 = 0, FR_EPI_KIND_F32_M2 = 1, FR_EPI_KIND_BF16 = 2, FR_EPI_KIND_FP8 = 3;
+extern "C" int fr_epi_fused_launch(const FrFusedArgs *args, int kind, void *stream, char *name, size_t name_len);
+// fr_epi_pipeline_launch: frk_pipeline_launch's arguments.  fr_epi_gemm_launch:
+struct FrEpiGemmCall {   // the arguments of frk_fc_lp_gemm (tail == 0) or frk_fc_tail (tail == 1: Yp = wout, scores / batch set, epi = FC3's)
+    int tail, precision;
+    const void *Wp, *Xp;
+    void *Yp;
+    float *scores;
+    int K, N, ldm, batch, e_w, e_in, e_out, width, minor;
+    FrEpi epi, epi_out;
+};
+extern "C" int fr_epi_pipeline_launch(const FrPipeArgs *args, int single_stage, int precision, void *stream, char *name, size_t name_len);
+extern "C" int fr_epi_gemm_launch(const FrEpiGemmCall *call, void *stream, char *name, size_t name_len);
 
 // ---- segmented top-K ranking (fr_rank.hip -> libfleetrec_rank.so, the companion code object; fr_cpu.cpp has the twin) ------------------------
 // The rank order of fleetrec_serving.h on a score's 32 bits: a larger key ranks first; every NaN has key 0, behind -inf (0x007fffff).
@@ -441,6 +483,14 @@ struct fr_ctx {
     bool f8_calibrated = false;
     FrBuf<uint32_t> d_stats;  // 16 words of reduction scratch (max |x| bits, sum x^2 per tensor)
     bool weights_set = false;
+    // Per-layer epilogues (fr_ctx_set_epilogue): fp32 biases of fc[l + 1] values (device memory; host memory on the CPU back-end; empty: no bias)
+    // and the hidden layers' activation.  Never rounded to the chain's operand type; set under the rules of fr_ctx_set_weights.
+    FrBuf<float> d_bias[4];
+    FrBuf<float> d_negzero;                // GPU contexts: max(fc[1..3]) values of -0.0f, the "no bias" operand of the fused kernels' branch-free epilogue forms (v + -0.0f == v)
+    bool has_bias[4] = {false, false, false, false};
+    int act[4] = {0, 0, 0, 0};             // FR_ACT_*; act[3] stays FR_ACT_NONE
+    FrEpi epi(int l) const { return FrEpi{has_bias[l] ? d_bias[l].p : nullptr, act[l] == FR_ACT_RELU ? 1 : 0, 0}; }
+    bool any_epi() const { return has_bias[0] || has_bias[1] || has_bias[2] || has_bias[3] || act[0] || act[1] || act[2]; }
     int fc_precision = FR_FC_FP32;
     // sharding
     int shard_rank = 0, n_shards = 1;
@@ -619,7 +669,7 @@ int frc_expand_requests(const FrRequestArgs &a);
 void frc_resolve_keys(const FrKeyResolveArgs &a);
 int frc_put_keys(const FrKeyPutArgs &a);
 void frc_fill_keys(const FrKeyFillArgs &a);
-void frc_fc_chain(const int32_t fc[5], const float *const w[4], const float *X, int batch, float *scratch, float *scores);
+void frc_fc_chain(const int32_t fc[5], const float *const w[4], const FrEpi epi[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \
     do {                                                                                                                           \
@@ -660,15 +710,17 @@ int frk_pipeline_launch(const FrPipeArgs &a, int single_stage, int precision, hi
 int frk_pack_weights_q8_bf16(const float *W, uint16_t *Wh, int K, int H, hipStream_t s);
 bool frk_fc_lp_gemm_ok(int precision, int K, int N, int ldm);
 // width: the context's chain width (fr_ctx::chain_width) -> the larger tile already when it covers 1 / width of the chip (lp_gemm_mu)
-int frk_fc_lp_gemm(int precision, const void *Wp, const void *Xp, void *Yp, int K, int N, int ldm, int e_w, int e_in, int e_out, int width, bool minor, hipStream_t s);
+int frk_fc_lp_gemm(int precision, const void *Wp, const void *Xp, void *Yp, int K, int N, int ldm, int e_w, int e_in, int e_out, int width, bool minor, const FrEpi &epi, hipStream_t s);   // epi: the layer's epilogue
 bool frk_fused_hk_takes_lp_rows(int K);   // the persistent bf16 fused kernel has an instantiation that reads operand-type (bf16) rows for this record length
 bool frk_fc_tail_ok(int precision, int K, int N, int ldm);   // FC3 + output layer as one launch (fc_tail_kernel, fr_gemm.hip)
-int frk_fc_tail(int precision, const void *W3, const void *R2, const void *wout, float *scores, int K, int N, int ldm, int batch, int e_w, int e_in, int e_r3, hipStream_t s);
+int frk_fc_tail(int precision, const void *W3, const void *R2, const void *wout, float *scores, int K, int N, int ldm, int batch, int e_w, int e_in, int e_r3, const FrEpi &epi3, const FrEpi &epi_out,
+                hipStream_t s);   // epi3: FC3's epilogue, applied before R3 is rounded in registers; epi_out: b_3
 int frk_records_to_q8_bf16(const float *X, void *Xh, int batch, int K, int ldm, hipStream_t s);
 int frk_pack_weights_q16_fp8(const float *W, void *Wf, int K, int H, int e_w, hipStream_t s);
 int frk_pack_weights_q16h_fp8(const float *W, void *Wg, int K, int H, int e_w, hipStream_t s);  // the persistent fp8 kernel's operand layout
 int frk_records_to_q16_fp8(const float *X, void *Xf, int batch, int K, int ldm, int e_x, hipStream_t s);
-int frk_stats(const float *p, size_t n, void *d_out, hipStream_t s);
+// ldm > 0: p is a feature-major q4 image [n / 4 / ldm][ldm][4] and only the items m < batch count (the pad items of a chain with biases are not zeros)
+int frk_stats(const float *p, size_t n, void *d_out, hipStream_t s, int ldm = 0, int batch = 0);
 int frk_q4_to_lp(int precision, const float *Xq, void *Xo, int K, int ldm, int e_x, hipStream_t s);
 int frk_stage_blocks_f8_gather(int K, int ldm);
 int frk_pack_weights_q4(const float *W, float *Wq, int K, int H, hipStream_t s);

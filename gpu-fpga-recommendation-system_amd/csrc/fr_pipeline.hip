@@ -3,6 +3,22 @@
 // (fr_fused.hip) and the LDS-tiled GEMM (fr_gemm.hip) do not cover.  Wavefront = 64 lanes everywhere; gfx950 only.
 #include "fr_device.h"
 
+// (two builds: see fr_device.h)
+#ifdef FR_EPI_FORMS
+#include <cstdio>
+#define fr_pipeline_kernel fr_epi_pipeline_kernel
+#define fr_gather_out_kernel fr_epi_gather_out_kernel
+#define FR_PIPE_NAME "fr_epi_pipeline_kernel"
+#define FR_GO_NAME "fr_epi_gather_out_kernel"
+#define FR_PE(a, s) (a).epi[s], (a).epi_in[s]
+#define FR_PIPE_KARGS FrPipeArgs
+#else
+#define FR_PIPE_KARGS FrPipeCore   /* the launch slices the caller's FrPipeArgs: no epilogue argument reaches these kernels */
+#define FR_PIPE_NAME "fr_pipeline_kernel"
+#define FR_GO_NAME "fr_gather_out_kernel"
+#define FR_PE(a, s) FrEpi{nullptr, 0, 0}, FrEpi{nullptr, 0, 0}
+#endif
+
 
 // ===================================================================================================
 // FC chain on k-quad-packed feature-major activations, split-K inside the workgroup, stages
@@ -43,7 +59,7 @@ constexpr int FR_PIPE_WAVES = 8;
 // ---- stage 0: gather_q.  Lanes = 64 consecutive items; each wave walks WPW record words (wave-uniform descriptor ->
 // scalar loads); each lane reads its item's 16-byte row word and stores it as ONE q4 element Xq[word][m]
 // (1 KiB coalesced per wave-store).
-__device__ __forceinline__ void gather_q_body(const FrPipeArgs &a, const FrStageArgs &st, int local) {
+__device__ __forceinline__ void gather_q_body(const FrPipeCore &a, const FrStageArgs &st, int local) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m_blocks = (st.ldm + 63) / 64;
@@ -91,7 +107,7 @@ __device__ __forceinline__ int gt_at(int item, int word) { return item * FR_GT_W
 __device__ __forceinline__ uint32_t pack_fp8_word(const uint4 &v, float scale);
 
 template <int PREC>
-__device__ __forceinline__ void gather_tr_body(const FrPipeArgs &a, const FrStageArgs &st, int local, uint4 *tile /* [32][64], swizzled */) {
+__device__ __forceinline__ void gather_tr_body(const FrPipeCore &a, const FrStageArgs &st, int local, uint4 *tile /* [32][64], swizzled */) {
     const int m_blocks = st.ldm / FR_GT_ITEMS;
     const int mb = local % m_blocks, wb = local / m_blocks;
     const int m0 = mb * FR_GT_ITEMS, w0 = wb * FR_GT_WORDS;
@@ -180,7 +196,7 @@ __device__ __forceinline__ void gather_tr_body(const FrPipeArgs &a, const FrStag
 // over the workgroup's word block with the cache policy AUX (16 = write-through: the image is not left dirty in L2 for the
 // end-of-kernel write-back).  Needs batch * idx_stride * 4 < 4000 MiB (variant chosen by the host).
 template <int PREC, int NT, int AUX>
-__device__ __forceinline__ void gather_tr_stream_body(const FrPipeArgs &a, const FrStageArgs &st, int local, uint4 *tile /* [32][64], swizzled */) {
+__device__ __forceinline__ void gather_tr_stream_body(const FrPipeCore &a, const FrStageArgs &st, int local, uint4 *tile /* [32][64], swizzled */) {
     const int m_tiles = st.ldm / FR_GT_ITEMS, m_groups = (m_tiles + NT - 1) / NT;
     const int mg = local % m_groups, wb = local / m_groups;
     const int w0 = wb * FR_GT_WORDS;
@@ -287,7 +303,7 @@ __device__ __forceinline__ void gather_tr_stream_body(const FrPipeArgs &a, const
 // stay adjacent (phase 2 reads them in one piece), 16 consecutive words of an item (phase 1) and one element of 32 consecutive items
 // (phase 2) spread over all banks.
 template <int PREC, int NT, int AUX>
-__device__ __forceinline__ void gather_tr_stream_lp_body(const FrPipeArgs &a, const FrStageArgs &st, int local, uint4 *tile_raw) {
+__device__ __forceinline__ void gather_tr_stream_lp_body(const FrPipeCore &a, const FrStageArgs &st, int local, uint4 *tile_raw) {
     static_assert(PREC == 1 || PREC == 2, "operand-type rows exist for the bf16 and fp8 chains");
     constexpr int EW = PREC == 1 ? 2 : 4;          // record words per 16-byte image element
     constexpr int SW = 64 / EW - 1;                // swizzle mask over the element index
@@ -416,7 +432,7 @@ __device__ __forceinline__ void mfma4(f32x16 &acc, const float4 &a, const float4
 }
 
 template <bool TWO_IN>
-__device__ __forceinline__ void fc_q_body(const FrStageArgs &st, int local, float *red /* [8][16][64] */) {
+__device__ __forceinline__ void fc_q_body(const FrStageArgs &st, int local, float *red /* [8][16][64] */, const FrEpi &ep, const FrEpi &ep_in) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int N = st.N, ldm = st.ldm;
@@ -474,6 +490,9 @@ __device__ __forceinline__ void fc_q_body(const FrStageArgs &st, int local, floa
             b.y += c.y;
             b.z += c.z;
             b.w += c.w;
+            // ... whose epilogue belongs HERE, after the partials are combined (never per partial): the element holds k = 4 (2 g + hk) + c of this
+            // layer = outputs n of the producing one
+            fr_epi4(b.x, b.y, b.z, b.w, ep_in, 8 * g, hk);
         }
         return b;
     };
@@ -530,6 +549,7 @@ __device__ __forceinline__ void fc_q_body(const FrStageArgs &st, int local, floa
             for (int w = 1; w < FR_PIPE_WAVES; w++) s += red[(w * 16 + 4 * i + c) * 64 + l];
             v[c] = s;
         }
+        fr_epi4(v[0], v[1], v[2], v[3], ep, n0 + 8 * i, l >> 5);   // ({NULL, 0} on a split stage: partials go out raw, the consumer finishes them)
         const int nq = (n0 >> 2) + 2 * i + (l >> 5);  // n = n0 + 8i + 4(l>>5) + c
         Yq[(size_t)nq * ldm + m0 + (l & 31)] = make_float4(v[0], v[1], v[2], v[3]);
     }
@@ -540,7 +560,7 @@ static int pad8(int v) { return (v + 7) / 8 * 8; }
 
 // ---- stage 4: score[m] = sum_n w[n] * (R3q[n/4][m][n%4] (+ second partial)); 64 items x 8 slices of n, one 16-byte
 // load per 4 n, LDS reduce in fixed order.
-__device__ __forceinline__ void fc_out_q_body(const FrStageArgs &st, int local, float *red) {
+__device__ __forceinline__ void fc_out_q_body(const FrStageArgs &st, int local, float *red, const FrEpi &ep, const FrEpi &ep_in) {
     const int lane = threadIdx.x & 63;
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = local * 64 + lane;  // padding workgroups have m >= ldm
@@ -565,6 +585,7 @@ __device__ __forceinline__ void fc_out_q_body(const FrStageArgs &st, int local, 
                     v[i].y += c.y;
                     v[i].z += c.z;
                     v[i].w += c.w;
+                    fr_epi4<1>(v[i].x, v[i].y, v[i].z, v[i].w, ep_in, 4 * hh, 0);   // FC3's epilogue, on the combined partials
                 }
             }
 #pragma unroll
@@ -585,6 +606,7 @@ __device__ __forceinline__ void fc_out_q_body(const FrStageArgs &st, int local, 
         float t = red[lane];
 #pragma unroll
         for (int i = 1; i < FR_PIPE_WAVES; i++) t += red[i * 64 + lane];
+        if (ep.bias) t += ep.bias[0];
         st.out[m] = t;
     }
 }
@@ -599,7 +621,7 @@ __device__ __forceinline__ void fc_out_q_body(const FrStageArgs &st, int local, 
 // rounded twice.
 // ===================================================================================================
 
-__device__ __forceinline__ void gather_h_body(const FrPipeArgs &a, const FrStageArgs &st, int local) {
+__device__ __forceinline__ void gather_h_body(const FrPipeCore &a, const FrStageArgs &st, int local) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m_blocks = (st.ldm + 63) / 64;
@@ -637,7 +659,7 @@ __device__ __forceinline__ void gather_h_body(const FrPipeArgs &a, const FrStage
     if (bad) atomicOr_system(a.err_flag, 1);
 }
 
-__device__ __forceinline__ void fc_h_body(const FrStageArgs &st, int local, float *red) {
+__device__ __forceinline__ void fc_h_body(const FrStageArgs &st, int local, float *red, const FrEpi &ep, const FrEpi &ep_in) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int N = st.N, ldm = st.ldm;
@@ -722,6 +744,7 @@ __device__ __forceinline__ void fc_h_body(const FrStageArgs &st, int local, floa
             for (int w = 1; w < FR_PIPE_WAVES; w++) s += red[(w * 16 + 4 * i + c) * 64 + l];
             v[c] = s;
         }
+        fr_epi4(v[0], v[1], v[2], v[3], ep, n0 + 8 * i, l >> 5);   // on the fp32 sums, before the ONE rounding
         uint2 h;
         h.x = pack_bf16x2(v[0], v[1]);
         h.y = pack_bf16x2(v[2], v[3]);
@@ -731,7 +754,7 @@ __device__ __forceinline__ void fc_h_body(const FrStageArgs &st, int local, floa
 }
 
 // score[m] = sum_n w[n] * R3h[n/8][m][n%8]; weights for this layer stay fp32 values rounded to bf16 (st.w = bf16 array)
-__device__ __forceinline__ void fc_out_h_body(const FrStageArgs &st, int local, float *red) {
+__device__ __forceinline__ void fc_out_h_body(const FrStageArgs &st, int local, float *red, const FrEpi &ep, const FrEpi &ep_in) {
     const int lane = threadIdx.x & 63;
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = local * 64 + lane;
@@ -760,6 +783,7 @@ __device__ __forceinline__ void fc_out_h_body(const FrStageArgs &st, int local, 
         float t = red[lane];
 #pragma unroll
         for (int i = 1; i < FR_PIPE_WAVES; i++) t += red[i * 64 + lane];
+        if (ep.bias) t += ep.bias[0];
         st.out[m] = t;
     }
 }
@@ -778,7 +802,7 @@ __device__ __forceinline__ void fc_out_h_body(const FrStageArgs &st, int local, 
 // ===================================================================================================
 
 // stage 0, small batches: lanes = 64 consecutive items, each wave builds ONE q16 element (4 record words) per item
-__device__ __forceinline__ void gather_f_body(const FrPipeArgs &a, const FrStageArgs &st, int local) {
+__device__ __forceinline__ void gather_f_body(const FrPipeCore &a, const FrStageArgs &st, int local) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m_blocks = (st.ldm + 63) / 64;
@@ -812,7 +836,7 @@ __device__ __forceinline__ void gather_f_body(const FrPipeArgs &a, const FrStage
 }
 static int gather_f_blocks(int K, int ldm) { return ((ldm + 63) / 64) * (((K + 63) / 64 * 4 + FR_PIPE_WAVES - 1) / FR_PIPE_WAVES); }
 
-__device__ __forceinline__ void fc_f_body(const FrStageArgs &st, int local, float *red) {
+__device__ __forceinline__ void fc_f_body(const FrStageArgs &st, int local, float *red, const FrEpi &ep, const FrEpi &ep_in) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int N = st.N, ldm = st.ldm;
@@ -904,12 +928,13 @@ __device__ __forceinline__ void fc_f_body(const FrStageArgs &st, int local, floa
             v[c] = s;
         }
         const int n = n0 + 8 * i + 4 * (l >> 5);  // + c
+        fr_epi4(v[0], v[1], v[2], v[3], ep, n0 + 8 * i, l >> 5);   // (real units: the block scales undid both exponents) before x 2^e_out and the quantisation
         Yf[((size_t)(n >> 4) * ldm + m0 + (l & 31)) * 4 + ((n & 15) >> 2)] = pack_fp8x4(v[0], v[1], v[2], v[3], oscale);
     }
 }
 
 // stage 4: score[m] = 2^-e_in * sum_k w[k] * e4m3(R3)[k][m]; fp32 master weights, 64 items x 8 slices of q16 rows
-__device__ __forceinline__ void fc_out_f_body(const FrStageArgs &st, int local, float *red) {
+__device__ __forceinline__ void fc_out_f_body(const FrStageArgs &st, int local, float *red, const FrEpi &ep, const FrEpi &ep_in) {
     const int lane = threadIdx.x & 63;
     const int q = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int m = local * 64 + lane;
@@ -939,7 +964,9 @@ __device__ __forceinline__ void fc_out_f_body(const FrStageArgs &st, int local, 
         float t = red[lane];
 #pragma unroll
         for (int i = 1; i < FR_PIPE_WAVES; i++) t += red[i * 64 + lane];
-        st.out[m] = t * __builtin_ldexpf(1.0f, -st.e_in);
+        t *= __builtin_ldexpf(1.0f, -st.e_in);
+        if (ep.bias) t += ep.bias[0];
+        st.out[m] = t;
     }
 }
 
@@ -948,7 +975,7 @@ __device__ __forceinline__ void fc_out_f_body(const FrStageArgs &st, int local, 
 // PREC: 0 = fp32 chain (q4 operands, exact-f32 MFMA), 1 = bf16 chain (q8 operands, bf16 MFMA, fp32 accumulate),
 // 2 = fp8 chain (q16 e4m3 operands, scaled f8f6f4 MFMA, fp32 accumulate).
 template <int STAGE, int PREC>
-__global__ void __launch_bounds__(FR_PIPE_THREADS) fr_pipeline_kernel(const FrPipeArgs a) {
+__global__ void __launch_bounds__(FR_PIPE_THREADS) fr_pipeline_kernel(const FR_PIPE_KARGS a) {
     __shared__ uint4 smem[FR_GT_ITEMS * FR_GT_WORDS];  // 32 KiB: the gather tile, or float red[8][16][64] of the FC stages
     float *red = reinterpret_cast<float *>(smem);
     const int b = blockIdx.x;
@@ -974,21 +1001,21 @@ __global__ void __launch_bounds__(FR_PIPE_THREADS) fr_pipeline_kernel(const FrPi
         }
     } else if constexpr (PREC == 1) {
         if (s == 0) gather_h_body(a, st, local);
-        else if (s == 4) fc_out_h_body(st, local, red);
-        else fc_h_body(st, local, red);
+        else if (s == 4) fc_out_h_body(st, local, red, FR_PE(a, s));
+        else fc_h_body(st, local, red, FR_PE(a, s));
     } else if constexpr (PREC == 2) {
         if (s == 0) gather_f_body(a, st, local);
-        else if (s == 4) fc_out_f_body(st, local, red);
-        else fc_f_body(st, local, red);
+        else if (s == 4) fc_out_f_body(st, local, red, FR_PE(a, s));
+        else fc_f_body(st, local, red, FR_PE(a, s));
     } else {
         if (s == 0) {
             gather_q_body(a, st, local);
         } else if (s == 4) {
-            fc_out_q_body(st, local, red);
+            fc_out_q_body(st, local, red, FR_PE(a, s));
         } else if (st.nparts_in == 2) {
-            fc_q_body<true>(st, local, red);
+            fc_q_body<true>(st, local, red, FR_PE(a, s));
         } else {
-            fc_q_body<false>(st, local, red);
+            fc_q_body<false>(st, local, red, FR_PE(a, s));
         }
     }
     if (a.stamps) {
@@ -1013,7 +1040,7 @@ __global__ void __launch_bounds__(FR_PIPE_THREADS) fr_pipeline_kernel(const FrPi
 #define FR_GO_VGPRS 56
 #endif
 template <int PREC>
-__global__ void __launch_bounds__(FR_PIPE_THREADS) __attribute__((amdgpu_num_vgpr(FR_GO_VGPRS))) fr_gather_out_kernel(const FrPipeArgs a) {
+__global__ void __launch_bounds__(FR_PIPE_THREADS) __attribute__((amdgpu_num_vgpr(FR_GO_VGPRS))) fr_gather_out_kernel(const FR_PIPE_KARGS a) {
     __shared__ uint4 smem[FR_GT_ITEMS * FR_GT_WORDS];
     float *red = reinterpret_cast<float *>(smem);
     const int b = blockIdx.x;
@@ -1027,9 +1054,9 @@ __global__ void __launch_bounds__(FR_PIPE_THREADS) __attribute__((amdgpu_num_vgp
     } else {
         const FrStageArgs &st = a.st[4];
         const int local = b - st.block_begin;
-        if constexpr (PREC == 1) fc_out_h_body(st, local, red);
-        else if constexpr (PREC == 2) fc_out_f_body(st, local, red);
-        else fc_out_q_body(st, local, red);
+        if constexpr (PREC == 1) fc_out_h_body(st, local, red, FR_PE(a, 4));
+        else if constexpr (PREC == 2) fc_out_f_body(st, local, red, FR_PE(a, 4));
+        else fc_out_q_body(st, local, red, FR_PE(a, 4));
     }
 }
 
@@ -1042,7 +1069,7 @@ static int pipeline_launch_prec(const FrPipeArgs &a, int single_stage, hipStream
         a.st[2].block_begin == a.st[3].block_begin && a.st[3].block_begin == a.st[4].block_begin) {
         fr_gather_out_kernel<PREC><<<grid, block, 0, s>>>(a);
         KCHECK();
-        fr_note_kernel("fr_gather_out_kernel<%d>", PREC);
+        fr_note_kernel(FR_GO_NAME "<%d>", PREC);
         return FR_OK;
     }
     switch (single_stage) {
@@ -1055,12 +1082,21 @@ static int pipeline_launch_prec(const FrPipeArgs &a, int single_stage, hipStream
         default: FR_FAIL(FR_ERR_INVALID, "bad stage %d", single_stage);
     }
     KCHECK();
-    fr_note_kernel("fr_pipeline_kernel<%d, %d>", single_stage, PREC);
+    fr_note_kernel(FR_PIPE_NAME "<%d, %d>", single_stage, PREC);
     return FR_OK;
 }
 
 int frk_pipeline_launch(const FrPipeArgs &a, int single_stage, int precision, hipStream_t s) {
     if (a.n_blocks <= 0) return FR_OK;
+#ifndef FR_EPI_FORMS
+    if (a.has_epi) {   // a context with an epilogue: the epilogue forms of these kernels, in the companion code object
+        char name[96] = "";
+        const int e = fr_epi_pipeline_launch(&a, single_stage, precision, s, name, sizeof(name));
+        if (e) FR_FAIL(FR_ERR_HIP, "launch of the epilogue form of the stage pipeline failed: %s", hipGetErrorString((hipError_t)e));
+        fr_note_kernel("%s", name);
+        return FR_OK;
+    }
+#endif
     if (precision == FR_FC_FP8) return pipeline_launch_prec<2>(a, single_stage, s);
     return precision == FR_FC_BF16 ? pipeline_launch_prec<1>(a, single_stage, s) : pipeline_launch_prec<0>(a, single_stage, s);
 }
@@ -1123,3 +1159,13 @@ int frk_convert_rows_lp(int precision, const void *src, size_t src_stride, void 
     KCHECK();
     return FR_OK;
 }
+
+#ifdef FR_EPI_FORMS
+// the companion's export for the stage pipeline: -> 0 or the hipError_t value; the kernel's name goes to name[0 .. name_len)
+extern "C" __attribute__((visibility("default"))) int fr_epi_pipeline_launch(const FrPipeArgs *a, int single_stage, int precision, void *stream, char *name, size_t name_len) {
+    fr_epi_noted[0] = 0, fr_epi_hip_error = 0;
+    const int rc = frk_pipeline_launch(*a, single_stage, precision, static_cast<hipStream_t>(stream));
+    if (name && name_len) snprintf(name, name_len, "%s", fr_epi_noted);
+    return fr_epi_status(rc);
+}
+#endif

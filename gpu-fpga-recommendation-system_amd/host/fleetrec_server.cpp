@@ -45,6 +45,12 @@
 //                        scores, and with --topk K the S x K pairs of the reply (--segments, if given, must equal S; omitted it is S), are those of the
 //                        expanded block.  Not with --stream, --shards, --csr or --pool weighted; N = 1 .. index columns - 1 unless --shared-dense
 //                        (fleetrec_sender takes the same three options).
+//        [--relu] [--bias-seed S]: the per-layer epilogue of the FC chain (fr_ctx_set_epilogue), a context setting: legal with every mode above, set on
+//                        every shard context with --shards.  --relu puts FR_ACT_RELU on the three hidden layers.  --bias-seed S gives every layer l = 0..3
+//                        a bias made here on the host, scaled like --weights uniform: with fmix32 the 32-bit murmur3 finaliser
+//                        (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16),
+//                          g = fmix32(fmix32(S ^ ((l + 1) * 0x9E3779B1)) ^ h),   b_l[h] = ((float)(g >> 8) / 8388608 - 1) / sqrtf(fc[l])
+//                        for h = 0 .. fc[l + 1] - 1, all in float32 (fc[l] = the layer's input width).  fleetrec_sender is unchanged.
 // --shards G: BASELINE configs[3]/[4] -- the tables are sharded by table-ID over GPUs device .. device + G - 1 of this node, or with
 // --device -1 over G CPU shard contexts of this process exchanging through the library's in-process host exchange (one
 // context and one worker per shard, fr_comm_init_all); every batch goes through fr_worker_submit_sharded on all shards (slices
@@ -60,6 +66,7 @@
 
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -78,6 +85,8 @@ struct Options {
     int model = FR_MODEL_A, batch = 256, threads = 4, port = 8080, device = 0;
     long total = 1024;
     int tables = FR_FILL_EVEN_ODD, weights = FR_WEIGHTS_ONES;
+    bool relu = false, bias_seed_given = false;   // the FC chain's per-layer epilogue (fr_ctx_set_epilogue)
+    uint32_t bias_seed = 0;
     bool per_item = false, per_bank = false, reply = false;
     int shards = 0;            // > 0: table-sharded over `shards` GPUs
     bool one_device = false;   // --shards G --one-device: all G shard contexts on GPU `device` (the library's staged host exchange: a G-rank job rehearsed on one GPU)
@@ -558,6 +567,29 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
     fr_worker_destroy(wk);
 }
 
+// --relu / --bias-seed: the context's epilogues (the formula is in the usage comment)
+static uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+static bool set_epilogues(fr_ctx *ctx, const fr_model_desc *model, const Options &o) {
+    if (!o.relu && !o.bias_seed_given) return true;
+    for (int l = 0; l < 4; l++) {
+        std::vector<float> b;
+        if (o.bias_seed_given) {
+            const uint32_t hl = fmix32(o.bias_seed ^ ((uint32_t)(l + 1) * 0x9E3779B1u));
+            const float scale = 1.0f / sqrtf((float)model->fc[l]);
+            for (int h = 0; h < model->fc[l + 1]; h++) b.push_back(((float)(fmix32(hl ^ (uint32_t)h) >> 8) * (1.0f / 8388608.0f) - 1.0f) * scale);
+        }
+        if (fr_ctx_set_epilogue(ctx, l, b.empty() ? nullptr : b.data(), b.size(), o.relu && l < 3 ? FR_ACT_RELU : FR_ACT_NONE) != FR_OK) return false;
+    }
+    return true;
+}
+
 int main(int argc, char **argv) {
     Options o;
     for (int i = 1; i < argc; i++) {
@@ -583,6 +615,8 @@ int main(int argc, char **argv) {
         else if (a == "--flush-min") o.flush_min = atoi(next());
         else if (a == "--small-block") o.small_block = atoi(next());
         else if (a == "--row-cap") o.row_cap = atol(next());
+        else if (a == "--relu") o.relu = true;
+        else if (a == "--bias-seed") { o.bias_seed = (uint32_t)strtoul(next(), nullptr, 0); o.bias_seed_given = true; }
         else if (a == "--hots") o.hots = atoi(next());
         else if (a == "--csr") o.csr = true;
         else if (a == "--update-port") o.update_port = atoi(next());
@@ -658,7 +692,7 @@ int main(int argc, char **argv) {
             // GPUs device .. device + G - 1, or (--device -1) G CPU shard contexts exchanging in process (fr_comm_init_all picks the transport)
             if (fr_ctx_create_sharded(model, o.device < 0 ? -1 : (o.one_device ? o.device : o.device + r), r, o.shards, &engine.ctxs[r]) != FR_OK || fr_ctx_fill_tables(engine.ctxs[r], o.tables, 0xF1EE7) != FR_OK ||
                 fr_ctx_fill_weights(engine.ctxs[r], o.weights, 99) != FR_OK || fr_ctx_set_fc_precision(engine.ctxs[r], o.precision) != FR_OK ||
-                fr_worker_create(engine.ctxs[r], o.batch, &engine.workers[r]) != FR_OK) {
+                !set_epilogues(engine.ctxs[r], model, o) || fr_worker_create(engine.ctxs[r], o.batch, &engine.workers[r]) != FR_OK) {
                 fprintf(stderr, "shard %d set-up failed: %s\n", r, fr_last_error());
                 return 1;
             }
@@ -682,10 +716,11 @@ int main(int argc, char **argv) {
         else if (o.one_device) printf("table-sharded over %d shard contexts on GPU %d (staged host %s of the looked-up slices)\n", o.shards, o.device, a2a ? "all-to-all" : "exchange");
         else printf("table-sharded over %d GPUs (RCCL %s of the looked-up slices)\n", o.shards, a2a ? "all-to-all" : "all-gather");
     } else if (fr_ctx_create(model, o.device, &ctx) != FR_OK || fr_ctx_fill_tables(ctx, o.tables, 0xF1EE7) != FR_OK ||
-               fr_ctx_fill_weights(ctx, o.weights, 99) != FR_OK || fr_ctx_set_fc_precision(ctx, o.precision) != FR_OK) {
+               fr_ctx_fill_weights(ctx, o.weights, 99) != FR_OK || fr_ctx_set_fc_precision(ctx, o.precision) != FR_OK || !set_epilogues(ctx, model, o)) {
         fprintf(stderr, "set-up failed: %s\n", fr_last_error());
         return 1;
     }
+    if (o.relu || o.bias_seed_given) printf("FC epilogue:%s%s\n", o.relu ? " ReLU on the hidden layers" : "", o.bias_seed_given ? " hashed biases on every layer" : "");
     if (o.hots > 0) {   // before the threads create their workers: a worker sizes its index buffers for the pooled rows at creation
         std::vector<int32_t> hots((size_t)fr_model_index_cols(model), o.hots);
         if (fr_ctx_set_pooling(ctx, hots.data(), (int)hots.size()) != FR_OK) {

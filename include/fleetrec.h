@@ -50,6 +50,8 @@ extern "C" {
  * Still 6, additive: request-form batches, request rows + candidate rows + segment offsets expanded on the device (fleetrec_serving.h:
  * fr_ctx_set_request_columns, fr_ctx_request_words, fr_worker_expand_requests_device, fr_worker_request_*_ptr, fr_worker_submit_requests) -- every
  * existing entry point is as before, with or without a split.
+ * Still 6, additive: an opt-in per-layer bias and ReLU of the FC chain (fleetrec_serving.h: fr_ctx_set_epilogue, fr_ctx_epilogue), honoured by every
+ * kernel that finishes a layer and by the CPU back-end -- a context that never sets one computes, names its kernels and performs as before.
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile
  * shape of a chain model no longer follows the number of live workers).
  * 4 (round 4): the surface is three headers -- this one (the three spans of thread_consume() that SURVEY section 8(b) cuts, the request
@@ -243,7 +245,8 @@ int fr_ctx_download_table(fr_ctx *ctx, int table, int64_t row0, int64_t nrows, f
 
 /* FC weights.  layer 0..3 = W1, W2, W3, Wout; `w` is column-major H x K with ld = H
  * (element (h,k) at w[h + k*H]) exactly as cuda_server.c:215 hands it to cuBLASLt.  No bias and no
- * activation exist on the reference path (cuda_server.c:403,468-491: alpha=1, beta=0). */
+ * activation exist on the reference path (cuda_server.c:403,468-491: alpha=1, beta=0); a context opts into a per-layer bias
+ * and ReLU with fr_ctx_set_epilogue (fleetrec_serving.h). */
 int fr_ctx_set_weights(fr_ctx *ctx, int layer, const float *w_colmajor, size_t count);
 int fr_ctx_fill_weights(fr_ctx *ctx, int mode /* fr_weight_mode */, uint32_t seed);
 int fr_ctx_get_weights(fr_ctx *ctx, int layer, float *w_colmajor, size_t count);

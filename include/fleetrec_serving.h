@@ -421,6 +421,39 @@ int64_t *fr_worker_key_ptr(fr_worker *w);
 int fr_worker_submit_keyed(fr_worker *w, int batch, int pooled /* 0 one-hot, 1 pooled, 2 pooled weighted */);
 int fr_worker_key_misses(fr_worker *w, uint64_t *misses, int reset);
 
+/* ---- per-layer epilogue: bias and ReLU between the FC layers ----
+ * The reference's chain is four matrix products with nothing between them (alpha = 1, beta = 0, cuda_server.c:211-217), which no trained model
+ * looks like.  A context holds, per layer l = 0..3 (W1, W2, W3, Wout), an optional bias vector b_l of fc[l + 1] fp32 values and, for the hidden
+ * layers 0..2, an activation: FR_ACT_NONE (the default) or FR_ACT_RELU.  The chain then computes R_l = act(W_l R_(l-1) + b_l), in every kernel
+ * that finishes a layer, on both back-ends.  A context that never sets one behaves, names its kernels and performs exactly as before.
+ *   fp32:  the layer's sum over k is taken exactly as without an epilogue; v = sum + b[h] is ONE fp32 add after the WHOLE K sum (where the stage
+ *          pipeline splits K in two, after the partials are combined, never per partial); then the activation.
+ *   ReLU:  v > 0 ? v : +0.0f; a NaN stays a NaN (a corrupt feature still reaches the score); -0 and negatives become +0.
+ *   bf16:  the same fp32 v; activation first, then the chain's ONE round-to-nearest-even to bf16 per hidden activation.  The bias is never rounded.
+ *   fp8:   the sum in real units (the accumulator times 2^-(e_act[l] + e_w[l])), v = real + b[h] in fp32, the activation, then x 2^e_act[l + 1],
+ *          the clamp to +-448 and round-to-nearest-even to e4m3 as before.
+ *   output layer: score = sum + b_3[0], one fp32 add after the sum -- also where the output layer is folded into FC3's launch.  No activation
+ *          there: a monotone transform does not change a ranking (sigmoid is out of scope).
+ *   fp8 calibration (fr_worker_calibrate_fp8, _slices, _sharded, _sharded_pooled) runs the fp32 chain WITH the epilogues and takes max |.| of X
+ *          and of the post-activation R1..R3.  The uncalibrated rms estimate does not know about biases: a context with biases should calibrate.
+ * The epilogue belongs to the context: submit, submit_device, push_device, push_host / staged, the pooled, CSR, request-form and keyed forms,
+ * fr_worker_fc_only, fr_worker_fc_layer_only / _repeat, fr_worker_fc_from_slices[_lp], fr_worker_submit_sharded[_pooled] and the drivers all honour
+ * it without a new entry point.  FC weights are replicated on shards, and so are the epilogues: each shard context is set by its owner.
+ * Two dispatch changes for a context WITH an epilogue, both for want of registers, both with bit-identical sums (DESIGN section 3.6 has the measured
+ * cost).  (1) bf16: the persistent fused kernel is not run; streamed launches take the chunked bf16 fused kernel (records of 352 / 880 floats), other
+ * records the stage pipeline (fr_ctx_stream_group reports 1 then, and fr_worker_push_host refuses as for any model that does not stream through a
+ * fused kernel).  (2) fp32, records of 352 floats (Model-A), launches of the 32-item fused kernel (stream groups below 64, partial launches): the
+ * one-workgroup-per-CU instantiation runs instead of the two-workgroups-per-CU one.
+ * fr_ctx_set_epilogue: bias = fc[layer + 1] floats, or NULL with count 0 (no bias); act = FR_ACT_*.  The threading and in-flight rules of
+ *   fr_ctx_set_weights (a blocking copy; no worker of the context may have work in flight).  (NULL, 0, FR_ACT_NONE) restores the layer as it was
+ *   before, bit for bit.  It does not touch the fp8 exponents, the weight images, the chain width or the stream group setting.
+ *   FR_ERR_INVALID: a bad layer, a count that is not the layer's width, an unknown activation, an activation on layer 3.
+ * fr_ctx_epilogue reads back: bias_out may be NULL (else count = the layer's width; written only when a bias is set), *has_bias 0 / 1, *act. */
+#define FR_ACT_NONE 0
+#define FR_ACT_RELU 1
+int fr_ctx_set_epilogue(fr_ctx *ctx, int layer, const float *bias, size_t count, int act);
+int fr_ctx_epilogue(fr_ctx *ctx, int layer, float *bias_out, size_t count, int *has_bias, int *act);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
