@@ -8,7 +8,9 @@ left are the chain's explicit ones (bf16 RNE per hidden layer; e4m3 clamp to +-4
 (gpu_helpers.chain_bf16_reference / chain_fp8_reference).  So there is no tolerance: one wrong column, k-group or tile shows.
 (A sweep row with a record too short for FC1's sums to pass 256 draws its tables from [-12, 12], so that bf16 still rounds there.)
 The integer weights are exact in every operand type, so the master-weight side has data of its own: WIDE (weights the pack kernels must
-round, an fp32 Wout no bf16 image holds), W_EXP_MAXIMA (fp8 weight exponents read back) and REFRESH_OPS (every refresh of a derived image)."""
+round, an fp32 Wout no bf16 image holds), W_EXP_MAXIMA (fp8 weight exponents read back) and REFRESH_OPS (every refresh of a derived image).
+So has the record side: RECORDS (tables and dense features drawn from the preimages of the stock operand images, so that every converter of
+a record must round) and F32_WIDTH (fp32 rows whose operands need the whole 24-bit significand), both at the end of the module."""
 import re
 import zlib
 
@@ -697,12 +699,20 @@ def case_data(case, n_items):
         data = make_data(sp, 9000 + zlib.crc32(case["id"].encode()) % 100000, table_max=case.get("table_max", 3), nnz=case.get("nnz", (320, 8, 8)))
         if case.get("wide"):   # a WIDE row: `stock` keeps the integer weights its wide ones were drawn from
             data = dict(data, stock=data["ws"], ws=widen(case, data["ws"]))
+        if case.get("records"):   # a RECORDS row: `stock_tables` / `stock_dense` keep the integers its preimages were drawn from
+            data = wide_records(case, data)
+        if case.get("f32w"):   # an F32_WIDTH row: carriers of a full fp32 significand in the record, the weights or both
+            data = f32_width_data(case, data)
     else:
         sp = model_spec(case["model"])
         data = make_data(sp, model_seed(case["model"]))
     rng = np.random.default_rng(sum(map(ord, case["id"])))
     sel = rng.integers(0, data["idx"].shape[0], size=n_items)
+    if case.get("f32w") in ("rec", "w1"):   # every position of P within the first |P| items
+        sel = np.arange(n_items) % data["idx"].shape[0]
     dense = data["dense"][sel] if data["dense"] is not None else None
+    if "stock_tables" in data:
+        data = dict(data, sel=sel)
     return sp, data, data["idx"][sel], dense
 
 
@@ -786,3 +796,402 @@ def refresh_steps(sets, precs=PRECS):
         seen[prec] = list(cur)
         out.append((op, prec, list(cur), stale))
     return out
+
+
+# ---- the record side: records that must round, one row per reader of a record ---------------------------------------------------------------
+# The stock tables and dense features are integers, exact in bf16 and in e4m3 at any power-of-two scale, so no conversion of a RECORD to the
+# operand type ever rounds.  wide_records() replaces every table and dense value v by a float32 preimage of the operand-type image of
+# v * 2^s under the chain's record conversion (bf16: RNE; e4m3: x 2^act_exp[0], clamp to +-448, RNE), drawn in turn from the witness classes
+# of the image's preimage interval: both ties (where the interval holds them: an even significand), the float32 neighbours just inside each
+# end, the value itself, values further inside; where the image is a power of two the lower ties and near-ties carry into its binade.  Zeros
+# stay zeros and every other one is -0.0 (fp8: some are the tie 2^-10 that flushes to zero, or lie just inside it).  The rounded record is
+# the stock record times 2^s, so premise() and the expectation are inherited: the scores are the stock scores times 2^s.  In fp8 the
+# activation exponents are set explicitly, every one to the stock one minus s: the e4m3 image of the record (and of every hidden activation,
+# which is 2^s larger in real units too) is the stock image bit for bit.  A `clamp` row sets the stock layer-0 exponent two above the calibrated one, so that the stock image holds the top
+# code 448 (|v| >= 2 of the stock range 3): there, and only there, the preimages include values above 448, which the clamp brings back.
+REC_S = {"bf16": 8, "fp8": 3}
+BF16_CLASSES = ("tie toward zero", "just inside it", "three quarters toward it", "the value", "a quarter past it", "just inside the outer tie", "tie away from zero")
+FP8_CLASSES = BF16_CLASSES + ("above 448 (clamped)",)
+FP8_ABOVE = (449.0, 460.0, 464.0, 500.0, 2.0 ** 20)   # 464 is the tie between 448 and the code a conversion without the clamp would take
+FP8_ZEROS = (0.0, -0.0, 2.0 ** -10, -2.0 ** -10, _in(2.0 ** -10, 0), 2.0 ** -20)   # +-2^-10: half the smallest subnormal, a tie that flushes to zero
+
+
+def bf16_preimage(t):
+    """The float32 interval that RNE takes to the bf16 value t (nonzero, finite, exact in bf16): (end nearer zero, outer end, closed).  Both ends
+    are ties; they belong to the interval where t's significand is even (closed), and neither does where it is odd."""
+    u = np.ascontiguousarray(t, np.float32).view(np.uint32).astype(np.int64)
+    sign, mag = u & 0x80000000, u & 0x7FFFFFFF
+    assert ((u & 0xFFFF) == 0).all() and (mag > 0x8000).all() and (mag < 0x7F800000).all()
+    f = lambda b: (sign | b).astype(np.uint32).view(np.float32)
+    return f(mag - 0x8000), f(mag + 0x8000), ((mag >> 16) & 1) == 0
+
+
+def bf16_record_preimages(t, cls):
+    """Per element of t (bf16 values as float32, zeros allowed: they stay) the witness of class cls[i] (an index into BF16_CLASSES); a tie
+    class of an open interval takes the neighbour just inside instead."""
+    t = np.ascontiguousarray(t, np.float32)
+    out = t.copy()
+    nz = t != 0
+    u = t[nz].view(np.uint32).astype(np.int64)
+    sign, mag = u & 0x80000000, u & 0x7FFFFFFF
+    closed = ((mag >> 16) & 1) == 0
+    c = np.asarray(cls)[nz]
+    off = np.select([c == 0, c == 1, c == 2, c == 3, c == 4, c == 5, c == 6],
+                    [np.where(closed, -0x8000, -0x7FFF), -0x7FFF, -0x6000, 0, 0x2000, 0x7FFF, np.where(closed, 0x8000, 0x7FFF)])
+    out[nz] = (sign | (mag + off)).astype(np.uint32).view(np.float32)
+    return out
+
+
+def _e4m3_quantum(a):
+    _, ex = np.frexp(a)
+    return np.ldexp(1.0, np.maximum(ex - 1, -6) - 3)
+
+
+def e4m3_preimage(a):
+    """The interval of magnitudes that clamp-then-RNE takes to the e4m3 magnitude a (0 < a <= 448, float64): (lower end, upper end, closed).
+    The spacing below a power of two above 2^-6 is half the spacing above it; the top code 448 takes everything above it too (inf)."""
+    a = np.asarray(a, np.float64)
+    q = _e4m3_quantum(a)
+    assert (a > 0).all() and (a <= 448).all() and (np.mod(a, q) == 0).all()
+    m, _ = np.frexp(a)
+    q_lo = np.where((m == 0.5) & (a > 2.0 ** -6), q / 2, q)
+    return a - q_lo / 2, np.where(a == 448.0, np.inf, a + q / 2), np.mod(a / q, 2) == 0
+
+
+def fp8_record_preimages(img, cls, rng):
+    """Per element of img (e4m3 values, the stock record image in the scaled domain) a float32 witness of class cls[i] (FP8_CLASSES) in the
+    same domain; class 7 applies where |img| == 448 only (elsewhere: the value).  Zeros draw from FP8_ZEROS."""
+    img = np.asarray(img, np.float64)
+    out = np.zeros(img.shape, np.float32)
+    z = img == 0
+    out[z] = np.array(FP8_ZEROS, np.float32)[rng.permutation(int(z.sum())) % len(FP8_ZEROS)]
+    a = np.abs(img[~z])
+    c = np.asarray(cls)[~z]
+    lo, hi, closed = e4m3_preimage(a)
+    hi_f = np.where(np.isinf(hi), a + _e4m3_quantum(a) / 2, hi)   # 448: 464 is no tie under the clamp, yet every value up to it (and past it) is a preimage
+    lo32, hi32 = lo.astype(np.float32), hi_f.astype(np.float32)
+    assert (lo32 == lo).all() and (hi32 == hi_f).all()
+    lo_in, hi_in = np.nextafter(lo32, np.float32(np.inf)), np.nextafter(hi32, np.float32(0))
+    top = a == 448.0
+    above = np.array(FP8_ABOVE, np.float32)[rng.permutation(a.size) % len(FP8_ABOVE)]
+    w = np.select([c == 0, c == 1, c == 2, c == 3, c == 4, c == 5, c == 6, (c == 7) & top],
+                  [np.where(closed, lo32, lo_in), lo_in, (a - 0.75 * (a - lo)).astype(np.float32), a.astype(np.float32),
+                   (a + 0.25 * (hi_f - a)).astype(np.float32), hi_in, np.where(closed | top, hi32, hi_in), above], default=a.astype(np.float32))
+    out[~z] = np.copysign(w, img[~z]).astype(np.float32)
+    return out
+
+
+def record_exponent(row):
+    """The layer-0 activation exponent of a row's STOCK fp8 data: the calibrated floor_log2(448 / (2 max|v|)), plus 2 on a `clamp` row."""
+    return floor_log2_f32(np.float32(448.0) / (np.float32(2.0) * np.float32(row.get("table_max", 3)))) + (2 if row.get("clamp") else 0)
+
+
+def _wide_values(v, prec, s, e0, rng):
+    """Stock integers v -> their float32 preimages (see the head of this part)."""
+    v = np.ascontiguousarray(v, np.float32)
+    flat = v.ravel()
+    ncls = len(BF16_CLASSES if prec == "bf16" else FP8_CLASSES)
+    cls = rng.permutation(flat.size) % ncls
+    if prec == "bf16":
+        out = bf16_record_preimages(flat * np.float32(2.0 ** s), cls)
+        z = np.flatnonzero(flat == 0)
+        out[z[1::2]] = np.float32(-0.0)
+    else:
+        img = e4m3_image(flat * np.float32(2.0 ** e0))
+        out = fp8_record_preimages(img, cls, rng) * np.float32(2.0 ** (s - e0))
+    return out.reshape(v.shape)
+
+
+def wide_records(row, data):
+    """The row's data with every table and dense value replaced by a preimage; stock_tables / stock_dense keep the integers."""
+    rng = np.random.default_rng(zlib.crc32(row["id"].encode()) + 77)
+    prec, s, e0 = row["prec"], REC_S[row["prec"]], record_exponent(row)
+    tables = [_wide_values(t, prec, s, e0, rng) for t in data["tables"]]
+    dense = _wide_values(data["dense"], prec, s, e0, rng) if data["dense"] is not None else None
+    return dict(data, stock_tables=data["tables"], stock_dense=data["dense"], tables=tables, dense=dense)
+
+
+def record_image(prec, rec, e_x=0, mode="rne"):
+    """The operand-type image (float64, the domain FC1 sums in) of float32 records: bf16, or e4m3 of rec * 2^e_x; mode as bf16_image / e4m3_image."""
+    if prec == "bf16":
+        return bf16_image(rec, mode).astype(np.float64)
+    return e4m3_image(np.asarray(rec, np.float32) * np.float32(2.0 ** e_x), mode)
+
+
+def record_witnesses(prec, rec, e_x=0):
+    """Of float32 records: dict of counts -- values the conversion must round, ties resolved toward zero / away from it, near-ties (one float32
+    step inside a tie), roundings that carry into the next binade, negative zeros; fp8 also ties that flush to zero and values above 448."""
+    v = np.asarray(rec, np.float32) * np.float32(2.0 ** (e_x if prec == "fp8" else 0))
+    a, b = np.abs(v.astype(np.float64)), np.abs(record_image(prec, rec, e_x))
+    if prec == "bf16":
+        lowbits = np.ascontiguousarray(v).view(np.uint32) & 0xFFFF
+        tie, near = lowbits == 0x8000, (lowbits == 0x7FFF) | (lowbits == 0x8001)
+    else:
+        q = _e4m3_quantum(a)
+        tie = (a <= 448.0) & (np.mod(a, q) == q / 2)
+        stepped = [np.abs(np.nextafter(np.abs(v), np.float32(d)).astype(np.float64)) for d in (0, np.inf)]
+        near = (a <= 448.0) & ~tie & ((np.mod(stepped[0], _e4m3_quantum(stepped[0])) == _e4m3_quantum(stepped[0]) / 2) |
+                                      (np.mod(stepped[1], _e4m3_quantum(stepped[1])) == _e4m3_quantum(stepped[1]) / 2))
+    out = {"inexact": int((a != b).sum()), "tie toward zero": int((tie & (b < a)).sum()), "tie away": int((tie & (b > a)).sum()), "near-tie": int(near.sum()),
+           "carry": int(((b > a) & (np.frexp(b)[1] > np.frexp(a)[1]) & (a > 0) & (b > 2.0 ** -6 if prec == "fp8" else True)).sum()),
+           "-0.0": int(((v == 0) & np.signbit(v)).sum())}
+    if prec == "fp8":
+        out["flush tie"] = int((a == 2.0 ** -10).sum())
+        out["above 448"] = int((a > 448.0).sum())
+    return out
+
+
+def _rec_row(tag, prec, K, fc, batch, layer, kernel, reader, width=1, group=1, dense_len=0, **kw):
+    return dict(id="rec-%s-%s" % (prec, tag), spec=(K, tuple(fc), dense_len), prec=prec, batch=batch, width=width, group=group, layer=layer,
+                kernel=kernel, reader=reader, records=True, **kw)
+
+
+def _record_rows():
+    """One row per precision for each distinct reader of a record (fr_api.cpp: fused_launch's kernels, pipeline_step's stage 0 / stage 1 forms and
+    its GEMM launches, launch_fc's and fc_from_slices_impl's converters, the gather | out launch, the operand-type bank image), on the shape of
+    the smallest CASES / SWEEPS / WIDE entry that reaches it.  `layer` as for WIDE; `fc_only`: fr_worker_fc_only also runs (records_to_*_kernel);
+    `sharded`: the row is fr_worker_fc_from_slices on a two-shard context (frk_transpose_slices + q4_to_lp_kernel); `bank`: a per-bank context,
+    run with the operand-type bank image on and off (the large-batch gather reads the image: convert_rows_lp_kernel made it)."""
+    A, C = (1024, 512, 256), C_FC
+    H, F8 = "fr_fused_tile_h_kernel<2, 2, %s>", "fr_fused_tile_f8_kernel<%d>"
+    rows = [
+        _rec_row("fused_h22", "bf16", 352, A, 256, "stream", H % "22, true, 16, 2", "chunked fused kernel, straight-line K = 352", group=16),
+        _rec_row("fused_h55", "bf16", 880, A, 256, "stream", H % "55, false, 12, 2", "chunked fused kernel, K = 880, dense block mid-record", group=16, dense_len=16),
+        _rec_row("hs22", "bf16", 352, A, 256, "stream", _hs_kernel(352), "persistent fused kernel, 22 k-groups", group=64),
+        _rec_row("hs33", "bf16", 528, A, 200, "stream", _hs_kernel(528), "persistent fused kernel, 33 k-groups", group=16),
+        _rec_row("hs33-below", "bf16", 368, A, 65, "stream", _hs_kernel(368), "persistent fused kernel, 23 of 33 k-groups: zero k-groups beside values that round", group=16),
+        _rec_row("hs44", "bf16", 704, A, 200, "stream", _hs_kernel(704), "persistent fused kernel, 44 k-groups, dense block mid-record", group=16, dense_len=16),
+        _rec_row("hs55", "bf16", 880, A, 256, "stream", _hs_kernel(880), "persistent fused kernel, 55 k-groups, dense block mid-record", group=128, dense_len=16),
+        _rec_row("k16", "bf16", 112, (256, 512, 256), 33, "FC1", PIPE % (1, 1), "stage 1's q8 gather, K % 32 == 16"),
+        _rec_row("fused_f6", "fp8", 352, A, 256, "stream", F8 % 6, "fp8 fused kernel, K = 352", group=16),
+        _rec_row("fused_f14", "fp8", 880, A, 100, "stream", F8 % 14, "fp8 fused kernel, K = 880, dense block mid-record", group=16, dense_len=16),
+        _rec_row("fused_f6-clamp", "fp8", 352, A, 256, "stream", F8 % 6, "fp8 fused kernel: records above 448 at the layer-0 scale", group=16, clamp=True),
+        _rec_row("kpad", "fp8", 104, (256, 512, 256), 33, "FC1", PIPE % (1, 2), "stage 1's q16 gather, K % 64 == 40: zero K padding beside values that round"),
+        _rec_row("kpad-dense", "fp8", 4200, C, 33, "FC1", PIPE % (1, 2), "stage 1's q16 gather, K % 64 == 40, dense block mid-record", dense_len=8),
+    ]
+    for prec in ("bf16", "fp8"):
+        p = _PI[prec]
+        k3 = 192 if prec == "bf16" else 384
+        rows += [
+            _rec_row("stages", prec, 3968, C, 65, "stages", None, "stage pipeline: gather-only step, stage 1, the multi-stage launch; dense block mid-record", group=4, dense_len=16),
+            _rec_row("n128", prec, k3, C, 4090, "FC1", PPN % p, "large-batch transposing gather + records_to_%s_kernel in front of the 128 x 256 tiles" % ("q8_bf16" if p == 1 else "q16_fp8"), fc_only=True),
+            _rec_row("slices", prec, 352, A, 256, "slices", None, "q4_to_lp_kernel<%d> behind frk_transpose_slices (fc_from_slices)" % p, sharded=True),
+            _rec_row("gather_out", prec, 3968, R_FC, 4096, "gather_out", "fr_gather_out_kernel<%d>" % p, "gather | output layer in one launch", dense_len=16),
+            _rec_row("image", prec, 3968, C, 4096, "FC1", PPN % p, "large-batch gather of a per-bank context: operand-type bank image on and off", dense_len=16, bank=True),
+        ]
+    rows.append(_rec_row("stages-clamp", "fp8", 3968, C, 65, "stages", None, "stage pipeline: records above 448 at the layer-0 scale", group=4, dense_len=16, clamp=True))
+    return rows
+
+
+RECORDS = _record_rows()
+# Readers of a record that no RECORDS row reaches, with the reason (the coverage table of tests/test_exact_chain_cpu.py prints them).
+RECORDS_LEFT_OUT = {
+    "fr_fused_tile_hs_kernel reading operand-type rows (SRC = 1)": "frk_fused_hk_takes_lp_rows() is false in the product build: no fused kernel reads the bank image; "
+                                                                   "the fused rows still run with fr_ctx_set_lp_bank_image on and off and must not change",
+    "gather_pooled_kernel's operand-store arms, transpose_slices_lp_kernel": "pooled and table-sharded low-precision transports: tests/gather_matrix.py and tests/exact_sharded.py own them",
+}
+
+
+def record_row_exponents(row, stock_rec, ws):
+    """(stock activation exponents, those the row sets): calibrated on the stock integers (+2 at layer 0 on a clamp row); each minus s.  (The
+    record is the stock record times 2^s in real units, and so is every hidden activation: with all four exponents s lower every e4m3 image
+    of the chain is the stock image bit for bit.  Layer 0's alone would leave R1 2^s too large for its stock exponent.)"""
+    ae = act_exponents(stock_rec, ws)
+    assert ae[0] + (2 if row.get("clamp") else 0) == record_exponent(row), (ae, row["id"])
+    ae[0] = record_exponent(row)
+    return ae, [e - REC_S["fp8"] for e in ae]
+
+
+def stock_records(model, data, idx):
+    """The stock integer records of a RECORDS row's items (data as case_data returned it)."""
+    dense = data["stock_dense"][data["sel"]] if data["stock_dense"] is not None else None
+    return records(model, dict(data, tables=data["stock_tables"]), idx, dense)
+
+
+# ---- fp32 operand width: rows whose operands need the whole fp32 significand ------------------------------------------------------------------
+# Every fp32 operand of the stock data is an integer of at most 11 significant bits: an fp32 kernel that read a bf16 / e4m3 row image, kept
+# R1 in a narrower type or fed the MFMA a truncated operand would still be bit-exact.  Integer data cannot be stretched to 24 bits and still
+# sum exactly in any order unless the wide term is alone in its sum, so the rows are built from CARRIERS: odd integers m, 2^22 <= |m| < 3 * 2^22 (from 2^23 on they need all 24 bits of the significand).
+#   `rec`  record carriers (operand A of FC1, then R1 -> R2 -> R3 as operand A of the later layers).  A set P of record positions -- every
+#          residue of k modulo the row's `kstep`, the first and the last K step, every table, the dense block -- may hold a carrier.  Each item of
+#          the pool holds exactly ONE, at the position P[item % |P|] (its table row there is a carrier row; every other table row it reads, and
+#          its dense block elsewhere, is in {-1, 0, 1}).  Position p has a chain of columns n_p of W1, j_p of W2, i_p of W3 with weight +-1
+#          down to Wout[i_p] = +-1; the carrier rows of W1 (and the rows n_p of W2, j_p of W3, i_p of Wout) are zero elsewhere, so every
+#          column of every layer takes at most one wide input, plus narrow ones.  Every partial sum is an integer below 2^24 (premise(),
+#          unchanged), and every item's score is +-m plus a narrow sum: a 24-bit integer that has been operand A of all four layers.
+#   `w1`   weight carriers (operand B of FC1), the mirror image: W1[p, n_p] = m_p, the item's record is +-1 at its own position of P and 0 at
+#          the others; the chain below is the same.
+#   `ulp`  operand B of FC2, FC3 and the output layer: a 24-bit weight there would need activations in {0, +-1}, which the chain cannot
+#          promise, so (as wide_wout) the layer's weights are w * (1 + 2^-j) on shrunk data (WOUT_SHRINK), j as large as premise() still
+#          passes and never below 12 -- no operand of 8 (bf16) or 11 (fp16, tf32) significant bits holds it.  One layer at a time (the quanta
+#          of two such layers would multiply): the row runs three weight sets, ulp_weights(data, l) for l = 1, 2, 3.
+F32_KINDS = ("rec", "w1", "ulp")
+ULP_J_MIN = 12
+ULP_NNZ = (2, 2, 2)   # nonzeros per column of W1, W2, W3 on an `ulp` row (where K > N the cover of every row sets the floor)
+
+
+def _layout(sp):
+    """Record position -> (table, column), table -1 = the dense block (Model.from_spec's segment order)."""
+    out, dl, at = [], sp.get("dense_len", 0), sp.get("dense_at", 0)
+    for t in range(len(sp["tables"]) + 1):
+        if dl and t == at:
+            out += [(-1, j) for j in range(dl)]
+        if t < len(sp["tables"]):
+            out += [(t, c) for c in range(sp["tables"][t]["dim"])]
+    return out
+
+
+def carrier_positions(sp, kstep):
+    """P: one record position per residue modulo kstep, spread over the K steps (residue 0 in the first, kstep - 1 in the last), then one per
+    table not yet hit (its middle column) and one in the dense block."""
+    lay = _layout(sp)
+    K = len(lay)
+    steps = (K + kstep - 1) // kstep
+    P = []
+    for r in range(min(kstep, K)):
+        g = 0 if r == 0 else steps - 1 if r == kstep - 1 else (r * 7) % steps
+        k = g * kstep + r
+        P.append(k if k < K else (g - 1) * kstep + r)
+    if max(P) < (steps - 1) * kstep:   # K is no multiple of the step: the last, partial step takes a position of its own
+        P.append(K - 1)
+    hit = {lay[k][0] for k in P}
+    for t in [-1] * bool(sp.get("dense_len", 0)) + list(range(len(sp["tables"]))):
+        if t not in hit:
+            ks = [k for k in range(K) if lay[k][0] == t]
+            P.append(ks[len(ks) // 2])
+    assert len(set(P)) == len(P)
+    return P
+
+
+def f32_width_data(row, data):
+    """The data of an F32_WIDTH row (see the head of this part), from the stock data of its shape drawn with tables in {-1, 0, 1}.  Adds `active`
+    (per pool item, its position of P), `P`, `chain` (per p: n_p, j_p, i_p) and, on an `ulp` row, `ulp_j` (the j reached per layer 1..3)."""
+    kind = row["f32w"]
+    if kind == "ulp":   # weights in {-1, 0, 1}: with the dense output layer (256 nonzeros) every magnitude counts against j
+        data = dict(data, ws=[np.sign(w) for w in data["ws"]])
+        js = {l: ulp_j(data, l) for l in (1, 2, 3)}
+        return dict(data, stock=data["ws"], ulp_j=js)
+    sp, fc = data["spec"], data["fc"]
+    rng = np.random.default_rng(zlib.crc32(row["id"].encode()) + 5)
+    lay = _layout(sp)
+    P = carrier_positions(sp, row["kstep"])
+    n_pool = data["idx"].shape[0]
+    assert len(P) <= n_pool
+    # |m| odd in [2^22, 3 * 2^22): 23 significant bits below 2^23, the full 24 from there on (a sum may add 2^22 of narrow terms and stay below 2^24)
+    odd = lambda n: ((rng.integers(2 ** 21, 3 * 2 ** 21, size=n) * 2 + 1) * rng.choice([-1, 1], size=n)).astype(np.float32)
+    tables = [t.copy() for t in data["tables"]]
+    dense = data["dense"].copy() if data["dense"] is not None else None
+    idx = data["idx"].copy()
+    by_table = {}
+    for p in P:
+        by_table.setdefault(lay[p][0], []).append(p)
+    # table t: its first 2 * |P_t| rows are carrier rows (row r carries at P_t[r % |P_t|]); the rest hold no carrier.  `fill`: what a row holds at
+    # a position of P that is not its own -- anything narrow on a `rec` row, 0 on a `w1` row (the wide weight must meet one +-1 per item)
+    n_carrier = {}
+    for t, Pt in by_table.items():
+        cols = [lay[p][1] for p in Pt]
+        if t < 0:
+            if kind == "w1":
+                dense[:, cols] = 0.0
+            continue
+        n_carrier[t] = 2 * len(Pt)
+        assert n_carrier[t] + 8 <= tables[t].shape[0], (t, n_carrier[t], tables[t].shape)
+        if kind == "w1":
+            tables[t][:, cols] = 0.0
+        for r in range(n_carrier[t]):
+            tables[t][r, cols[r % len(Pt)]] = odd(1)[0] if kind == "rec" else rng.choice([-1.0, 1.0])
+    active = np.empty(n_pool, np.int64)
+    for i in range(n_pool):
+        p = P[i % len(P)]
+        active[i] = p
+        for t, nc in n_carrier.items():   # rows without a carrier for every table ...
+            idx[i, t] = nc + idx[i, t] % (tables[t].shape[0] - nc)
+        t, c = lay[p]
+        if t < 0:
+            dense[i, c] = odd(1)[0] if kind == "rec" else rng.choice([-1.0, 1.0])
+        else:                              # ... but the item's own
+            Pt = by_table[t]
+            idx[i, t] = Pt.index(p) + len(Pt) * ((i // len(P)) % 2)
+    ws = [w.copy() for w in data["ws"]]
+    cols = [rng.permutation(fc[l + 1])[:len(P)] for l in range(3)]
+    assert all(len(c) == len(P) for c in cols), (len(P), fc)
+    sgn = lambda: float(rng.choice([-1.0, 1.0]))
+    ws[0][P, :] = 0.0
+    for l in (1, 2):
+        ws[l][cols[l - 1], :] = 0.0
+    ws[3][cols[2], :] = 0.0
+    wide_w = odd(len(P))
+    for q, p in enumerate(P):
+        ws[0][p, cols[0][q]] = sgn() if kind == "rec" else wide_w[q]
+        ws[1][cols[0][q], cols[1][q]] = sgn()
+        ws[2][cols[1][q], cols[2][q]] = sgn()
+        ws[3][cols[2][q], 0] = sgn()
+    return dict(data, tables=tables, dense=dense, idx=idx, ws=ws, active=active, P=P, chain=[c.tolist() for c in cols])
+
+
+def ulp_weights(data, l):
+    """The weight set of an `ulp` row's run for layer l (1 = FC2, 2 = FC3, 3 = the output layer): layer l times (1 + 2^-j)."""
+    ws = list(data["stock"])
+    ws[l] = (ws[l] * np.float32(1.0 + 2.0 ** -data["ulp_j"][l])).astype(np.float32)
+    return ws
+
+
+def f32_runs(row, data):
+    """(what, the layer widened or None, weights) of an F32_WIDTH row's runs: one, or the three layers of an `ulp` row in turn."""
+    if row["f32w"] == "ulp":
+        return [("layer %d x (1 + 2^-%d): " % (l, data["ulp_j"][l]), l, ulp_weights(data, l)) for l in (1, 2, 3)]
+    return [("", None, data["ws"])]
+
+
+def ulp_j(data, l):
+    """The largest j <= 22 for which the chain with layer l's weights times (1 + 2^-j) keeps premise() on the whole pool: every product a multiple
+    of the layer's quantum, every sum of |products| below 2^24 quanta, in layer l and in every layer behind it."""
+    sp = data["spec"]
+    lay = _layout(sp)
+    rec = np.empty((data["idx"].shape[0], len(lay)), np.float32)
+    for k, (t, c) in enumerate(lay):
+        rec[:, k] = data["dense"][:, c] if t < 0 else data["tables"][t][data["idx"][:, t], c]
+    acts, _ = fp32_acts(rec, data["ws"])
+    for j in range(22, ULP_J_MIN - 1, -1):
+        W = (data["ws"][l] * np.float32(1.0 + 2.0 ** -j)).astype(np.float64)
+        x, ok = acts[l], True
+        for L in range(l, 4):
+            WL = W if L == l else data["ws"][L].astype(np.float64)
+            la, lw = _lowbit(x), _lowbit(WL)
+            ok = ok and la is not None and float((np.abs(x) @ np.abs(WL)).max()) < 2.0 ** (24 + la + lw)
+            x = x @ WL
+        if ok:
+            return j
+    raise AssertionError("no j >= %d keeps the premise for layer %d" % (ULP_J_MIN, l))
+
+
+def _f32_row(tag, kind, K, fc, batch, layer, kernel, reader, kstep=32, group=1, dense_len=0):
+    return dict(id="f32w-%s-%s" % (tag, kind), spec=(K, tuple(fc), dense_len), prec="f32", batch=batch, width=1, group=group, layer=layer, kernel=kernel,
+                reader=reader, f32w=kind, kstep=kstep, table_max=1, rows=80, **({"nnz": ULP_NNZ} if kind == "ulp" else {}))
+
+
+def _f32_rows():
+    """Per fp32 reader (fr_api.cpp: fused_launch's fp32 kernels, pipeline_step's stages and GEMM launches, the gather | out launch) one row of
+    each kind, on the shape of the CASES / SWEEPS entry that reaches it.  `layer` as for WIDE."""
+    A = (1024, 512, 256)
+    readers = [
+        ("fused44", 352, A, 256, "stream", "fr_fused_tile_kernel<2, 44, 4, false>", "straight-line fused kernel, K = 352", dict(group=16)),
+        ("fused110", 880, A, 200, "stream", "fr_fused_tile_kernel<2, 110, 2, false>", "straight-line fused kernel, K = 880, dense block mid-record", dict(group=16, dense_len=16)),
+        ("fused_db", 512, A, 128, "stream", FUSED % (2, "true"), "generic-K fused kernel, double-buffered R1", dict(group=16)),
+        ("fused_sb", 256, A, 128, "stream", FUSED % (2, "false"), "generic-K fused kernel, single R1 buffer", dict(group=16)),
+        ("m2", 352, A, 256, "stream", "fr_fused_tile_m2_kernel<44>", "two-tile fused kernel", dict(group=64)),
+        ("stages-split", 640, (384, 512, 256), 200, "stages", None, "stage pipeline, stages 1-4, a split-K plan with a split layer", dict(kstep=64)),
+        ("stages-whole", 576, (384, 384, 256), 200, "stages", None, "stage pipeline, stages 1-4, no layer split", dict(kstep=64)),
+        ("n128", 64, C_FC, 4090, "FC1", LP % (0, 2, 128, 2), "128 x 256 GEMM tiles (FC1)", {}),
+        ("t64", 512, (192, 256, 256), 5500, "FC1", LP % (0, 1, 64, 2), "64 x 128 GEMM tiles (FC1, N = 192)", {}),
+        ("t128", 96, C_FC, 1638, "FC1", LP % (0, 1, 128, 2), "128 x 128 GEMM tiles (FC1)", {}),
+        ("gather_out", 3968, C_FC, 4096, "gather_out", "fr_gather_out_kernel<0>", "gather | output layer in one launch, dense block mid-record", dict(dense_len=16)),
+    ]
+    return [_f32_row(tag, kind, K, fc, batch, layer, kernel, reader, **kw) for tag, K, fc, batch, layer, kernel, reader, kw in readers for kind in F32_KINDS]
+
+
+F32_WIDTH = _f32_rows()
+F32_LEFT_OUT = {
+    "transpose_slices_lp_kernel (the table-sharded re-pack)": "a low-precision transport in front of the fp32 chain: tests/exact_sharded.py owns the sharded path",
+    "the pooled forms (gather_pooled_kernel's operand stores)": "sums of rows, not a reader of one record: tests/gather_matrix.py owns them",
+}

@@ -5,7 +5,9 @@ as unreachable.  For the shape sweep (exact_chain.SWEEPS: each kernel at the edg
 premise and witnesses per row, the CPU back-end on every fp32 row, per edge a simulated bug that must change a score of every row that
 targets the edge, hashes that pin the existing matrix's data, and the printed coverage table.  For the master-weight side
 (exact_chain.WIDE, W_EXP_MAXIMA, REFRESH_OPS): premise, hidden-layer and weight witnesses per row, the pack / Wout-form / exponent / stale-image
-mutants, and the fp32 steps of the refresh sequence on the CPU back-end."""
+mutants, and the fp32 steps of the refresh sequence on the CPU back-end.  For the record side (exact_chain.RECORDS, F32_WIDTH): the preimage
+helpers against brute force, premise, operand equality with the stock data and witness classes per row, the conversion / layout / width
+mutants with their summaries, the CPU back-end on every fp32 width row, and the coverage table of readers."""
 import os
 import shutil
 import sys
@@ -603,3 +605,384 @@ def test_refresh_sequence_on_the_host_and_the_cpu_back_end(fr, shape):
         live.close()
     finally:
         ctx.close()
+
+
+# ---- the record side (exact_chain.RECORDS) and fp32 operand width (exact_chain.F32_WIDTH) ---------------------------------------------------
+
+def _shapes():
+    shapes = {(c["prec"], E.MODELS[c["model"]][0], E.MODELS[c["model"]][1], c["batch"], c.get("width") or 1, c["group"]) for c in E.CASES}
+    return shapes | {(r["prec"], r["spec"][0], r["spec"][1], r["batch"], r["width"], r["group"]) for r in E.SWEEPS + E.WIDE}
+
+
+def test_record_and_width_tables_are_well_formed():
+    ids = [r["id"] for r in E.RECORDS + E.F32_WIDTH]
+    assert len(set(ids)) == len(ids) and not set(ids) & ({c["id"] for c in E.CASES} | {r["id"] for r in E.SWEEPS + E.WIDE})
+    shapes = _shapes()
+    for r in E.RECORDS + E.F32_WIDTH:   # every row sits on the shape of an existing case or row (a `sharded` row: fc_from_slices on Model-A's shape)
+        assert (r["prec"], r["spec"][0], r["spec"][1], r["batch"], r["width"], r["group"]) in shapes or r.get("sharded"), r["id"]
+        assert r["reader"] and 33 <= r["batch"] <= (5500 if r["prec"] == "f32" else 4096), r["id"]   # (5500: the one shape with 64 x 128 fp32 tiles at FC1)
+    for prec in ("bf16", "fp8"):   # one row per precision for each distinct reader of a record
+        p = E._PI[prec]
+        readers = {r["kernel"] or r["layer"] for r in E.RECORDS if r["prec"] == prec}
+        assert {"stages", "slices", E.PPN % p, E.PIPE % (1, p), "fr_gather_out_kernel<%d>" % p} <= readers, readers
+        assert any(r.get("bank") for r in E.RECORDS if r["prec"] == prec) and any(r.get("fc_only") for r in E.RECORDS if r["prec"] == prec)
+        dense = {r["kernel"] or r["layer"] for r in E.RECORDS if r["prec"] == prec and r["spec"][2]}
+        assert all(r["group"] == 4 for r in E.RECORDS if r["layer"] == "stages")   # several batches in flight: the multi-stage launch
+        assert "stages" in dense and any(k.startswith("fr_fused_tile") for k in dense), dense   # a dense block mid-record for a fused and a pipeline reader
+    bf = {r["kernel"] for r in E.RECORDS if r["prec"] == "bf16"}
+    assert {E._hs_kernel(K) for K in (352, 528, 704, 880)} <= bf and "fr_fused_tile_h_kernel<2, 2, 22, true, 16, 2>" in bf
+    assert {"fr_fused_tile_f8_kernel<6>", "fr_fused_tile_f8_kernel<14>"} <= {r["kernel"] for r in E.RECORDS if r["prec"] == "fp8"}
+    assert any(r["spec"][0] % 64 == 40 for r in E.RECORDS if r["prec"] == "fp8") and any(r["spec"][0] % 32 == 16 for r in E.RECORDS if r["prec"] == "bf16")
+    assert any(r.get("clamp") for r in E.RECORDS)
+    tags = {r["id"].rsplit("-", 1)[0] for r in E.F32_WIDTH}   # each fp32 reader: one row of each kind
+    for tag in tags:
+        assert {r["f32w"] for r in E.F32_WIDTH if r["id"].rsplit("-", 1)[0] == tag} == set(E.F32_KINDS), tag
+    named = {r["kernel"] or r["layer"] for r in E.F32_WIDTH}
+    assert {"fr_fused_tile_kernel<2, 44, 4, false>", "fr_fused_tile_kernel<2, 110, 2, false>", E.FUSED % (2, "true"), E.FUSED % (2, "false"), "fr_fused_tile_m2_kernel<44>",
+            "stages", E.LP % (0, 2, 128, 2), E.LP % (0, 1, 64, 2), E.LP % (0, 1, 128, 2), "fr_gather_out_kernel<0>"} == named, named
+    plans = {r["id"]: E.split_plan(r) for r in E.F32_WIDTH if r["layer"] == "stages"}
+    assert all(2 in plans["f32w-stages-split-" + k] and plans["f32w-stages-whole-" + k] == (1, 1, 1) for k in E.F32_KINDS), plans
+
+
+def test_record_preimage_helpers_round_as_stated():
+    """bf16_preimage against brute force: both ends are ties, they round to t exactly where t's significand is even, their float32 neighbours
+    inside do always and those outside never; every class of bf16_record_preimages rounds to t.  The same for e4m3_preimage on all 126
+    positive codes (the top one: no upper end) and for every class of fp8_record_preimages; FP8_ZEROS all flush to zero, FP8_ABOVE all clamp."""
+    t = np.array([v * 2.0 ** s for v in range(1, 13) for s in (-3, 0, 8)] + [258.0, 262.0, 1.0078125, 129.0 * 2.0 ** -20, 255.0], np.float32)
+    t = np.concatenate([t, -t])
+    lo, hi, closed = E.bf16_preimage(t)
+    assert closed[:36].all() and not closed[36:41].any()   # v < 16 times a power of two: an even significand; 258 = 129 * 2, ...: odd
+    up = lambda v, d: np.nextafter(v, np.float32(d) * np.sign(v))
+    assert ((bf16_round(lo) == t) == closed).all() and ((bf16_round(hi) == t) == closed).all()
+    assert (bf16_round(up(lo, np.inf)) == t).all() and (bf16_round(up(hi, 0)) == t).all()
+    assert (bf16_round(up(lo, 0)) != t).all() and (bf16_round(up(hi, np.inf)) != t).all()
+    assert (np.abs(lo) < np.abs(t)).all() and (np.abs(t) < np.abs(hi)).all()
+    for c in range(len(E.BF16_CLASSES)):
+        w = E.bf16_record_preimages(t, np.full(t.size, c))
+        assert (bf16_round(w) == t).all() and ((w == t) == (c == 3)).all(), c
+    dec = e4m3_decode_table()
+    a = dec[1:127]
+    lo, hi, closed = E.e4m3_preimage(a)
+    img = lambda v: E.e4m3_image(np.asarray(v, np.float32))
+    assert np.isinf(hi[-1]) and a[-1] == 448.0
+    lo32, hi32 = lo.astype(np.float32), hi[:-1].astype(np.float32)
+    assert ((img(lo32) == a) == closed).all() and ((img(hi32) == a[:-1]) == closed[:-1]).all()
+    assert (img(np.nextafter(lo32, np.float32(np.inf))) == a).all() and (img(np.nextafter(hi32, np.float32(0))) == a[:-1]).all()
+    assert (img(np.nextafter(lo32, np.float32(0))) != a).all() and (img(np.nextafter(hi32, np.float32(np.inf))) != a[:-1]).all()
+    rng = np.random.default_rng(5)
+    both = np.concatenate([a, -a])
+    for c in range(len(E.FP8_CLASSES)):
+        w = E.fp8_record_preimages(both, np.full(both.size, c), rng)
+        assert np.array_equal(E.e4m3_image(w), both), c
+        assert np.array_equal(dec[e4m3_encode(w)], both), c
+    assert (np.abs(E.fp8_record_preimages(np.array([448.0] * 20), np.full(20, 7), rng)) > 448).all()
+    assert (E.e4m3_image(np.array(E.FP8_ZEROS, np.float32)) == 0).all() and (E.e4m3_image(np.array(E.FP8_ABOVE, np.float32)) == 448).all()
+    assert E.e4m3_image(np.array([2.0 ** -10], np.float32), "away")[0] == 2.0 ** -9
+
+
+def _record_row(fr, row, n=256):
+    """(model, data, idx, dense, wide records, stock records, stock exponents, the row's exponents, w_exp)."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], n))
+    stock = E.stock_records(m, data, idx)
+    if row["prec"] == "fp8":
+        ae_s, ae = E.record_row_exponents(row, stock, data["ws"])
+        return m, data, idx, dense, rec, stock, ae_s, ae, E.w_exponents(data["ws"])
+    return m, data, idx, dense, rec, stock, None, None, None
+
+
+@pytest.mark.parametrize("row", E.RECORDS, ids=[r["id"] for r in E.RECORDS])
+def test_premise_holds_for_every_record_row(fr, row):
+    """premise() on the rounded operands; operands() of the wide data are those of the stock data times 2^s (bf16) or the same e4m3 images
+    (fp8), layer for layer, so the scores are the stock scores times 2^s; every witness class is present in the batch's records (values above
+    448 on a clamp row and nowhere else); no hidden activation comes near bf16's overflow or underflow."""
+    m, data, idx, dense, rec, stock, ae_s, ae, we = _record_row(fr, row)
+    ws, prec, s = data["ws"], row["prec"], E.REC_S[row["prec"]]
+    assert np.isfinite(rec).all() and not np.array_equal(rec, stock)
+    assert np.array_equal(rec == 0, stock == 0) or prec == "fp8"        # (fp8: some zeros are ties that flush)
+    E.premise(prec, rec, ws, ae, we)
+    ops, hidden = E.operands(prec, rec, ws, ae, we)
+    ops_s, hidden_s = E.operands(prec, stock, ws, ae_s, we)
+    f = 2.0 ** s if prec == "bf16" else 1.0
+    for l in range(4):
+        assert np.array_equal(ops[l][0], ops_s[l][0] * (f if prec == "bf16" or l < 3 else 2.0 ** s)), (row["id"], l)
+        assert np.array_equal(ops[l][1], ops_s[l][1]), (row["id"], l)
+    for r, x in hidden:
+        nz = np.abs(r[r != 0])
+        assert nz.max() < 2.0 ** 100 and nz.min() > 2.0 ** -100
+    for l, (inexact, ties) in enumerate(E.rounding_witnesses(prec, rec, ws, ae, we)):
+        assert inexact > 0 and ties > 0, (row["id"], l, inexact, ties)
+    wit = E.record_witnesses(prec, rec, ae[0] if ae else 0)
+    for k, n in wit.items():
+        assert (n > 0) == (k != "above 448" or bool(row.get("clamp"))), (row["id"], wit)
+    want = E.expected(prec, rec, ws, ae, we)
+    assert np.array_equal(want, E.expected(prec, stock, ws, ae_s, we) * np.float32(2.0 ** s))
+    assert np.isfinite(want).all() and np.unique(want).size > want.size // 4
+    if row.get("clamp"):
+        assert (np.abs(E.record_image("fp8", stock, ae_s[0])) == 448).any() and ae_s[0] == E.act_exponents(stock, ws)[0] + 2
+
+
+def _from_image(prec, x0, ws, ae, we):
+    """The chain of precision bf16 / fp8 from a given operand image of the records (float64, the domain FC1 sums in)."""
+    if prec == "fp8":
+        dec = e4m3_decode_table()
+        x = x0
+        for l in range(3):
+            Wf = dec[e4m3_encode(ws[l] * np.float32(2.0 ** we[l]))]
+            r = ((x @ Wf) * 2.0 ** -(ae[l] + we[l])).astype(np.float32) * np.float32(2.0 ** ae[l + 1])
+            x = dec[e4m3_encode(np.nan_to_num(r))]
+            x[np.isnan(r)] = np.nan   # (a mutant's NaN stays one)
+        return ((x * 2.0 ** -ae[3]) @ ws[3].astype(np.float64)).astype(np.float32).ravel()
+    x = x0
+    for l in range(3):
+        x = bf16_round((x @ bf16_round(ws[l]).astype(np.float64)).astype(np.float32)).astype(np.float64)
+    return (x @ bf16_round(ws[3]).astype(np.float64)).astype(np.float32).ravel()
+
+
+def _lane_perm(K, n, rot):
+    k = np.arange(K)
+    return (k // n) * n + (k % n + rot) % n
+
+
+def record_mutants(row, rec, e_x):
+    """The simulated bugs of a record's conversion and layout: name -> operand image of the records."""
+    prec = row["prec"]
+    n = 2 if prec == "bf16" else 4
+    rne, trunc = E.record_image(prec, rec, e_x), E.record_image(prec, rec, e_x, "trunc")
+    perm = _lane_perm(rec.shape[1], n, 1)
+    step = np.where(rne != trunc, rne - trunc, 0.0)   # the rounding's own step up in magnitude, where it took one
+    scaled = np.abs(np.asarray(rec, np.float32) * np.float32(2.0 ** e_x)).astype(np.float64)
+    quantum = np.ldexp(1.0, np.frexp(np.maximum(np.abs(trunc), 2.0 ** -126))[1] - 8) if prec == "bf16" else E._e4m3_quantum(np.minimum(np.maximum(scaled, 2.0 ** -9), 448.0))
+    took = (step != 0)[:, perm]
+    out = {
+        "record conversion truncates": trunc,
+        "record conversion rounds half away from zero": E.record_image(prec, rec, e_x, "away"),
+        "%s exchanged" % ("the two halves of a packed bf16 pair" if n == 2 else "e4m3 quad lanes rotated: positions"): rne[:, perm],
+        "the rounding decision taken from the %s" % ("other half of the pair" if n == 2 else "next lane of the quad"): trunc + np.copysign(quantum, np.where(trunc == 0, rec, trunc)) * took,
+    }
+    if row.get("clamp"):   # a conversion that rounds first: past the tie 464 there is no finite code, the top one is taken only by what the clamp would have brought back
+        bad = rne.copy()
+        bad[scaled >= 464.0] = np.nan
+        out["e4m3 rounding before the clamp"] = bad
+    return out
+
+
+RECORD_MUTANT_SHARES = {}
+
+
+def _run_record_mutants(fr, row):
+    if row["id"] not in RECORD_MUTANT_SHARES:
+        RECORD_MUTANT_SHARES[row["id"]] = _record_mutants_of(fr, row)
+    return RECORD_MUTANT_SHARES[row["id"]]
+
+
+@pytest.mark.parametrize("row", E.RECORDS, ids=[r["id"] for r in E.RECORDS])
+def test_record_row_rejects_its_record_mutants(fr, row):
+    """Truncation, round-half-away, an exchanged pair / rotated quad (positions, and the rounding decision alone), and on a clamp row rounding
+    before the clamp each change a score of the row; the unmutated restatement is the reference.  A -0.0 that becomes +0.0 changes no
+    score and cannot: a sum with one nonzero term has no signed zero left, and no item's FC1 column is all zeros."""
+    for name, (share, inside) in _run_record_mutants(fr, row).items():
+        assert share > 0, (row["id"], name)
+
+
+def _record_mutants_of(fr, row):
+    m, data, idx, dense, rec, stock, ae_s, ae, we = _record_row(fr, row)
+    out = {}
+    ws, prec = data["ws"], row["prec"]
+    e_x = ae[0] if ae else 0
+    want = E.expected(prec, rec, ws, ae, we)
+    assert np.array_equal(_from_image(prec, E.record_image(prec, rec, e_x), ws, ae, we), want)
+    for name, img in record_mutants(row, rec, e_x).items():
+        bad = _from_image(prec, img, ws, ae, we)
+        changed = int((~(bad == want)).sum())
+        err = float(np.nanmax(np.abs(bad.astype(np.float64) - want)) / np.abs(want).max()) if np.isfinite(bad).any() else np.inf
+        inside = np.isfinite(bad).all() and err <= E.OLD_TOL[prec]
+        out[name] = (changed / want.size, bool(inside))
+        print("record mutant %-24s %-60s items changed %4d of %d  max-norm err %.2e  old tolerance %.0e%s" % (
+            row["id"], name, changed, want.size, err, E.OLD_TOL[prec], "  INSIDE the old tolerance" if inside else ""))
+    plus = E.record_image(prec, rec, e_x) + 0.0   # -0.0 + 0.0 = +0.0
+    assert np.signbit(E.record_image(prec, rec, e_x)[rec == 0]).any() and not np.signbit(plus[plus == 0]).any()
+    assert np.array_equal(_from_image(prec, plus, ws, ae, we), want)
+    A, W = E.operands(prec, rec, ws, ae, we)[0][0]
+    assert (np.abs(A) @ np.abs(W) > 0).all()
+    return out
+
+
+def test_record_mutant_summary(fr):
+    """Per record mutant the least share of scores it changes over the rows that target it, and how many (mutant, row) pairs the old max-norm
+    tolerances would have let through (printed: the table of the change's description)."""
+    by_name = {}
+    for row in E.RECORDS:
+        for name, got in _run_record_mutants(fr, row).items():
+            by_name.setdefault(name.replace("the two halves of a packed bf16 pair", "pair halves / quad lanes").replace("e4m3 quad lanes rotated: positions", "pair halves / quad lanes")
+                               .replace("other half of the pair", "neighbouring lane").replace("next lane of the quad", "neighbouring lane"), []).append(got)
+    for name, got in by_name.items():
+        print("record mutant summary %-62s rows %2d  least share of scores changed %.3f  inside the old tolerance on %d rows" % (
+            name, len(got), min(s for s, _ in got), sum(i for _, i in got)))
+        assert min(s for s, _ in got) > 0
+
+
+@pytest.mark.parametrize("row_id", ["rec-fp8-fused_f6", "rec-fp8-stages"])
+def test_calibration_on_wide_records_is_certain(fr, row_id):
+    """The rows the GPU calibration test runs: the fp32 chain's maxima on the WIDE records lie far from a power-of-two edge (the device sums
+    these floats inexactly and in no fixed order), and the exponents calibrate must return are the stock ones minus s."""
+    row = next(r for r in E.RECORDS if r["id"] == row_id)
+    m, data, idx, dense, rec, stock, ae_s, ae, we = _record_row(fr, row, row["batch"])
+    assert E.exponent_margin(E.act_exponent_quotients(rec, data["ws"])) > 1e-2
+    assert E.act_exponents(rec, data["ws"]) == ae
+
+
+def _round_bits(x, n):
+    """x (float64) rounded to n significant bits, to nearest even."""
+    m, e = np.frexp(x)
+    return np.ldexp(np.rint(np.ldexp(m, n)), e - n)
+
+
+def _f32_chain(rec, ws, a_hook=None, w_hook=None):
+    x = np.asarray(rec, np.float64)
+    for l in range(4):
+        W = ws[l].astype(np.float64)
+        x = ((a_hook(l, x) if a_hook else x) @ (w_hook(l, W) if w_hook else W)).astype(np.float32).astype(np.float64)
+    return x.astype(np.float32).ravel()
+
+
+def _f32_runs(data, row):
+    return E.f32_runs(row, data)
+
+
+@pytest.mark.parametrize("row", E.F32_WIDTH, ids=[r["id"] for r in E.F32_WIDTH])
+def test_premise_holds_for_every_f32_width_row(fr, row):
+    """premise() unchanged.  Carrier rows: the positions P hit every residue of k modulo the row's K step, the first and the last step, every
+    table and the dense block, and the batch's items use all of them; each item holds one carrier (rec) or one +-1 among zeros on P (w1); every
+    column of every layer takes at most one wide input; the scores need more than 11 bits, and some all 24.  ulp rows: j >= 12 per layer."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 256))
+    kind, K = row["f32w"], row["spec"][0]
+    for what, l, ws in _f32_runs(data, row):
+        E.premise("f32", rec, ws)
+        s = E.expected("f32", rec, ws)
+        assert np.isfinite(s).all() and np.unique(s).size > s.size // 4
+        s64 = s.astype(np.float64)
+        assert (_round_bits(s64, 11) != s64).mean() > 0.9, (row["id"], what)
+        if l is not None:
+            assert data["ulp_j"][l] >= E.ULP_J_MIN
+            nz = ws[l][ws[l] != 0].astype(np.float64)
+            assert (_round_bits(nz, 11) != nz).all() and (bf16_round(ws[l])[ws[l] != 0] != ws[l][ws[l] != 0]).all()
+    if kind == "ulp":
+        return
+    P, ks, ws = data["P"], row["kstep"], data["ws"]
+    lay = E._layout(data["spec"])
+    assert {p % ks for p in P} == set(range(min(ks, K))) and min(P) < ks and max(P) >= (K - 1) // ks * ks
+    assert {lay[p][0] for p in P} == set(range(m.n_tables)) | ({-1} if row["spec"][2] else set())
+    active = data["active"][np.arange(idx.shape[0]) % data["active"].size]
+    assert set(active.tolist()) == set(P)
+    wide = np.abs(rec) >= 2.0 ** 22
+    on_p = rec[:, P]
+    if kind == "rec":
+        assert (wide.sum(axis=1) == 1).all() and (np.argmax(wide, axis=1) == active).all() and (np.abs(rec[~wide]) <= 1).all()
+        assert (rec[wide] % 2 == 1).all() and (np.abs(rec[wide]) >= 2.0 ** 23).any() and (np.abs(rec[wide]) < 2.0 ** 23).any()
+        assert all(np.abs(w).max() <= 2 for w in ws)
+    else:
+        assert not wide.any() and (np.abs(rec) <= 1).all() and ((on_p != 0).sum(axis=1) == 1).all() and (np.abs(rec[np.arange(rec.shape[0]), active]) == 1).all()
+        big = np.abs(ws[0]) >= 2.0 ** 22
+        assert (big.sum(axis=0) <= 1).all() and (big.sum(axis=1)[P] == 1).all() and big.sum() == len(P) and (ws[0][big] % 2 == 1).all()
+    acts, _ = E.fp32_acts(rec, ws)
+    for l in range(4):   # at most one wide input per output column and item
+        assert ((np.abs(acts[l] if l else (rec if kind == "rec" else np.zeros_like(rec))) >= 2.0 ** 21).astype(np.float64) @ (ws[l] != 0) <= 1).all(), (row["id"], l)
+    s = E.expected("f32", rec, ws).astype(np.float64)
+    assert (np.abs(s) >= 2.0 ** 21).all() and (_round_bits(s, 23) != s).any()
+
+
+def f32_mutants(row, data, l_run):
+    """The simulated narrow operands a row targets: name -> (a_hook, w_hook) of _f32_chain.  Operand A of layer l is the record (l = 0) or
+    R_l, so `R_l stored at 11 bits` is the same arithmetic as `operand A of layer l at 11 bits` and is listed under both names."""
+    kind, out = row["f32w"], {}
+    rnd = {"bf16": lambda v: bf16_round(v.astype(np.float32)).astype(np.float64), "11 bits": lambda v: _round_bits(v, 11), "23 bits": lambda v: _round_bits(v, 23)}
+    at = lambda L, fn: (lambda l, v: fn(v) if l == L else v)
+    if kind == "rec":
+        for L in range(4):
+            for name, fn in rnd.items():
+                out["operand A of layer %d rounded to %s" % (L, name)] = (at(L, fn), None)
+            if L:
+                out["R%d stored at 11 bits" % L] = (at(L, rnd["11 bits"]), None)
+    elif kind == "w1":
+        for name, fn in rnd.items():
+            out["operand B of layer 0 rounded to %s" % name] = (None, at(0, fn))
+    else:
+        for name in ("bf16", "11 bits"):
+            out["operand B of layer %d rounded to %s" % (l_run, name)] = (None, at(l_run, rnd[name]))
+    return out
+
+
+F32_MUTANT_SHARES = {}
+
+
+@pytest.mark.parametrize("row", E.F32_WIDTH, ids=[r["id"] for r in E.F32_WIDTH])
+def test_f32_width_row_rejects_its_width_mutants(fr, row):
+    """Every narrow-operand mutant a row targets changes at least one of its scores (on a carrier row: rounding to 23 bits too)."""
+    for name, (share, inside) in _run_f32_mutants(fr, row).items():
+        assert share > 0, (row["id"], name)
+
+
+def _run_f32_mutants(fr, row):
+    if row["id"] in F32_MUTANT_SHARES:
+        return F32_MUTANT_SHARES[row["id"]]
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 256))
+    out = F32_MUTANT_SHARES.setdefault(row["id"], {})
+    for what, l, ws in _f32_runs(data, row):
+        want = E.expected("f32", rec, ws)
+        assert np.array_equal(_f32_chain(rec, ws), want)
+        for name, (a_hook, w_hook) in f32_mutants(row, data, l).items():
+            bad = _f32_chain(rec, ws, a_hook, w_hook)
+            changed = int((bad != want).sum())
+            err = float(np.abs(bad.astype(np.float64) - want).max() / np.abs(want).max())
+            out[name] = (changed / want.size, err <= E.OLD_TOL["f32"])
+            print("width mutant %-26s %-44s items changed %4d of %d  max-norm err %.2e  old tolerance %.0e%s" % (
+                row["id"], name, changed, want.size, err, E.OLD_TOL["f32"], "  INSIDE the old tolerance" if err <= E.OLD_TOL["f32"] else ""))
+    return out
+
+
+def test_f32_width_mutant_summary(fr):
+    """Per width mutant the least share of scores it changes over the rows that target it, and on how many rows the old 1e-3 bar would have
+    let it through (printed: the table of the change's description)."""
+    by_name = {}
+    for row in E.F32_WIDTH:
+        for name, got in _run_f32_mutants(fr, row).items():
+            by_name.setdefault(name, []).append(got)
+    assert len(by_name) == 12 + 3 + 3 + 6
+    for name, got in by_name.items():
+        print("width mutant summary %-44s rows %2d  least share of scores changed %.3f  inside the old tolerance on %d rows" % (
+            name, len(got), min(s for s, _ in got), sum(i for _, i in got)))
+        assert min(s for s, _ in got) > 0
+
+
+@pytest.mark.parametrize("row", E.F32_WIDTH, ids=[r["id"] for r in E.F32_WIDTH])
+def test_cpu_backend_bit_exact_on_f32_width(fr, row):
+    """The library's CPU back-end (fp32 too) on every F32_WIDTH row, at most 128 items: the same bits."""
+    m, data, idx, dense, rec = _case_rec(fr, row, min(row["batch"], 128))
+    ctx = fr.Context(m, device=fr.DEVICE_CPU)
+    try:
+        E.load(ctx, data)
+        wk = fr.Worker(ctx, idx.shape[0])
+        for what, l, ws in _f32_runs(data, row):
+            for k in range(4):
+                ctx.set_weights(k, ws[k].ravel())
+            want = E.expected("f32", rec, ws)
+            assert np.array_equal(wk.infer(idx, dense), want), (row["id"], what)
+            assert np.array_equal(wk.fc_scores(rec), want), (row["id"], what)
+        wk.close()
+    finally:
+        ctx.close()
+
+
+def test_record_and_width_coverage_table():
+    """For every reader of a record and every fp32 MFMA operand the row that pins it; what no row reaches, with the reason (printed)."""
+    for r in E.RECORDS:
+        print("record reader %-5s %-58s | %s | row %s%s" % (r["prec"], r["kernel"] or r["layer"], r["reader"], r["id"],
+                                                           " (+ fr_worker_fc_only)" if r.get("fc_only") else " (bank image on and off)" if r.get("bank") else ""))
+    for name, why in E.RECORDS_LEFT_OUT.items():
+        print("record reader left out: %s -- %s" % (name, why))
+    operands = {"rec": "operand A of FC1, FC2, FC3, output layer", "w1": "operand B of FC1", "ulp": "operand B of FC2, FC3, output layer (one run each)"}
+    for r in E.F32_WIDTH:
+        print("fp32 operand  %-42s | %s | %s | row %s" % (r["kernel"] or r["layer"], r["reader"], operands[r["f32w"]], r["id"]))
+    for name, why in E.F32_LEFT_OUT.items():
+        print("fp32 reader left out: %s -- %s" % (name, why))
+    assert all(E.RECORDS_LEFT_OUT.values()) and all(E.F32_LEFT_OUT.values())

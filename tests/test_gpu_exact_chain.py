@@ -2,7 +2,9 @@
 exact restatement of the chain -- no tolerance.  Each case of exact_chain.CASES also pins the kernel the dispatcher picks for it; each
 row of exact_chain.SWEEPS runs one kernel at an edge of the shapes its dispatch predicate accepts (test_exact_sweep).  The master-weight side
 (end of the module): each reader of a weight image on weights that must round (exact_chain.WIDE), the fp8 exponents taken from the weights,
-and a sequence of set_weights / set_fc_precision calls that must each leave every derived image fresh."""
+and a sequence of set_weights / set_fc_precision calls that must each leave every derived image fresh.  The record side after it: each
+reader of a record on tables that its conversion must round (exact_chain.RECORDS), preimage rows written by update_rows, calibration on them,
+and each fp32 reader on operands that need the whole significand (exact_chain.F32_WIDTH)."""
 import numpy as np
 import pytest
 
@@ -507,4 +509,185 @@ def test_exact_refresh_sequence(fr, gpu, shape):
             prev = want
     finally:
         live.close()
+        ctx.close()
+
+
+# ---- the record side: records that every converter must round (exact_chain.RECORDS) ----------------------------------------------------------
+
+def _record_ctx(fr, gpu, row, tables="wide"):
+    """Context, worker and expectation of a RECORDS row: (m, ctx, wk, data, idx, dense, rec, want, ae).  tables: "wide" = the row's preimages,
+    None = none uploaded (a sharded row: fc_from_slices never reads them; the update_rows case uploads its own)."""
+    B, prec = row["batch"], row["prec"]
+    sp, data, idx, dense = E.case_data(row, B)
+    m = fr.Model.from_spec(sp)
+    if row.get("bank"):
+        m = m.clone(index_mode=fr.INDEX_PER_BANK)
+    ctx = fr.Context(m, device=gpu, shard_rank=0, n_shards=2) if row.get("sharded") else fr.Context(m, device=gpu)
+    try:
+        ws = data["ws"]
+        if tables == "wide" and not row.get("sharded"):
+            for t, a in enumerate(data["tables"]):
+                ctx.upload_table(t, a)
+        for l in range(4):
+            ctx.set_weights(l, ws[l].ravel())
+        ctx.set_fc_precision(_prec(fr, prec))
+        ctx.set_chain_width(row["width"])
+        rec = E.records(m, data, idx, dense)
+        first, inv = _unique_items(idx, dense)
+        stock = E.stock_records(m, data, idx)[first]
+        ae = ae_s = we = None
+        if prec == "fp8":
+            ae_s, ae = E.record_row_exponents(row, stock, ws)
+            ctx.set_fp8_act_exponents(ae)
+            got_ae, we = ctx.fp8_exponents()
+            assert got_ae == ae and we == E.w_exponents(ws), (got_ae, ae, we)
+        E.premise(prec, rec[first], ws, ae, we)
+        wit = E.record_witnesses(prec, rec[first], ae[0] if ae else 0)
+        assert all((n > 0) == (k != "above 448" or bool(row.get("clamp"))) for k, n in wit.items()), wit
+        want_u = E.expected(prec, rec[first], ws, ae, we)
+        assert np.array_equal(want_u, E.expected(prec, stock, ws, ae_s, we) * np.float32(2.0 ** E.REC_S[prec]))   # the stock scores times 2^s
+        return m, ctx, fr.Worker(ctx, B), data, idx, dense, rec, want_u[inv], ae
+    except BaseException:
+        ctx.close()
+        raise
+
+
+@pytest.mark.parametrize("row", E.RECORDS, ids=[r["id"] for r in E.RECORDS])
+def test_exact_wide_records(fr, gpu, row):
+    """A reader of a record (exact_chain.RECORDS) on tables and dense features that its conversion to bf16 / e4m3 must round -- ties to even in
+    both directions, near-ties, carries, signed zeros, in fp8 flushes to zero and (clamp rows) values above 448.  The rounded record is the
+    stock integer record times 2^s, so the scores are the stock scores times 2^s, bit for bit.  Run like a weight row: one infer, then one
+    push, the row's stream group of pushes or five pushes in flight into NaN-filled buffers; fr_worker_fc_only on the host's records where the
+    batch is small or the row asks for it; fc_from_slices on a sharded row.  A streamed or per-bank row runs with the operand-type bank image
+    on and off: the image's rows and the in-kernel conversion give the same bits."""
+    m, ctx, wk, data, idx, dense, rec, want, ae = _record_ctx(fr, gpu, row)
+    B, prec, layer = row["batch"], row["prec"], row["layer"]
+    try:
+        if row.get("sharded"):
+            offs, lens, F = m.shard_plan(2)
+            gathered = np.zeros((2, B, F), np.float32)
+            for g in range(2):
+                gathered[g, :, :lens[g]] = rec[:, offs[g]:offs[g] + lens[g]]
+            ldm = (B + 31) // 32 * 32
+            d_g = fr.DeviceBuffer.from_numpy(ctx, gathered)
+            for item0, n in ((0, B), (64, B - 64 - 3)):
+                d_s = fr.DeviceBuffer(ctx, ldm * 4)
+                d_s.upload(np.full(ldm, np.nan, np.float32))
+                wk.fc_from_slices(B, item0, n, d_g, d_s)
+                wk.sync()
+                got = d_s.download(np.float32, ldm)
+                _same(got[:n], want[item0:item0 + n], "fc_from_slices of items [%d, +%d)" % (item0, n))
+                assert np.isnan(got[n:]).all(), "fc_from_slices wrote past its items"
+                d_s.free()
+            d_g.free()
+            return
+        ctx.set_stream_group(row["group"])
+        for on in ((1, 0) if row.get("bank") or layer == "stream" else (1,)):
+            what = "bank image %s: " % ("on" if on else "off")
+            ctx.set_lp_bank_image(on)
+            _same(wk.infer(idx, dense), want, what + "infer")
+            if row.get("bank") and on:
+                assert ctx.lp_bank_image_bytes() > 0, "the large-batch gather of a per-bank context did not build the image"
+            # (a `stages` row: four pushes before the sync keep several batches in flight, so their steps are the multi-stage launch)
+            name = _pushes(fr, ctx, wk, B, idx, dense, want, row["group"] if layer in ("stream", "stages") else 5 if layer == "gather_out" else 1, what)
+            if layer == "stream":
+                assert name == row["kernel"], name
+        if row.get("bank"):
+            assert ctx.lp_bank_image_builds() == 1
+        if row.get("fc_only") or B <= 256:
+            _same(wk.fc_scores(rec), want, "fc_only")
+        if layer == "stages":
+            for l in range(4):
+                wk.fc_layer_only(B, l)
+                name = wk.last_kernel()
+                wk.sync()
+                assert name == E.PIPE % (l + 1, E._PI[prec]), (l, name)
+        elif layer not in ("stream", "gather_out"):
+            wk.fc_layer_only(B, ("FC1", "FC2", "FC3", "OUT").index(layer))
+            name = wk.last_kernel()
+            wk.sync()
+            assert name == row["kernel"], name
+    finally:
+        wk.close()
+        ctx.close()
+
+
+@pytest.mark.parametrize("prec", ["bf16", "fp8"])
+def test_exact_records_written_by_update_rows(fr, gpu, prec):
+    """Preimage rows written into a live operand-type bank image: the context starts on the NEGATED stock rows (times 2^s, exact in the operand
+    type), whose scores are the negated expectation (RNE and the clamp are symmetric); fr_ctx_update_rows then writes every row's preimage,
+    the image is patched in place (no rebuild) and the next batch is exact."""
+    row = next(r for r in E.RECORDS if r["id"] == "rec-%s-image" % prec)
+    m, ctx, wk, data, idx, dense, rec, want, ae = _record_ctx(fr, gpu, row, tables=None)
+    try:
+        neg = np.float32(-(2.0 ** E.REC_S[prec]))
+        for t, a in enumerate(data["stock_tables"]):
+            ctx.upload_table(t, a * neg)
+        neg_dense = data["stock_dense"][data["sel"]] * neg
+        _same(wk.infer(idx, neg_dense), -want, "the negated stock rows")
+        assert ctx.lp_bank_image_bytes() > 0
+        builds = ctx.lp_bank_image_builds()
+        for t, a in enumerate(data["tables"]):
+            ctx.update_rows(t, np.arange(a.shape[0]), a)
+        _same(wk.infer(idx, dense), want, "after update_rows")
+        assert ctx.lp_bank_image_builds() == builds, "the update made the next launch rebuild the image"
+        _pushes(fr, ctx, wk, row["batch"], idx, dense, want, 1, "after update_rows: ")
+    finally:
+        wk.close()
+        ctx.close()
+
+
+@pytest.mark.parametrize("row_id", ["rec-fp8-fused_f6", "rec-fp8-stages"])
+def test_fp8_calibration_on_wide_records(fr, gpu, row_id):
+    """calibrate on records that are not integers: the fp32 chain sums them inexactly, yet its maxima lie far from a power-of-two edge
+    (tests/test_exact_chain_cpu.py checks the margin), so the exponents are certain -- the stock ones minus s, those the row sets by hand."""
+    row = next(r for r in E.RECORDS if r["id"] == row_id)
+    m, ctx, wk, data, idx, dense, rec, want, ae = _record_ctx(fr, gpu, row)
+    try:
+        assert E.exponent_margin(E.act_exponent_quotients(rec, data["ws"])) > 1e-2
+        ctx.set_fp8_act_exponents([0, 0, 0, 0])
+        wk.calibrate_fp8(idx, dense)
+        assert ctx.fp8_exponents()[0] == ae == E.act_exponents(rec, data["ws"]), (ctx.fp8_exponents(), ae)
+        _same(wk.infer(idx, dense), want, "infer after calibration")
+    finally:
+        wk.close()
+        ctx.close()
+
+
+# ---- fp32 operand width (exact_chain.F32_WIDTH) ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("row", E.F32_WIDTH, ids=[r["id"] for r in E.F32_WIDTH])
+def test_exact_f32_width(fr, gpu, row):
+    """An fp32 reader on operands that need the whole significand: one carrier of 23 or 24 bits per item in the record (operand A of every
+    layer in turn) or in W1 (operand B of FC1), or one of W2, W3, Wout times (1 + 2^-j), j >= 12, three runs (operand B of the later
+    layers).  Every score is exact and needs more bits than bf16, fp16 or tf32 hold.  Run like a sweep row."""
+    m, ctx, data, idx, dense, rec = _setup(fr, gpu, row)
+    B, layer = row["batch"], row["layer"]
+    first, inv = _unique_items(idx, dense)
+    wk = fr.Worker(ctx, B)
+    try:
+        ctx.set_stream_group(row["group"])
+        for what, l, ws in E.f32_runs(row, data):
+            if l is not None:
+                for k in range(4):
+                    ctx.set_weights(k, ws[k].ravel())
+            E.premise("f32", rec[first], ws)
+            want = E.expected("f32", rec[first], ws)[inv]
+            _same(wk.infer(idx, dense), want, what + "infer")
+            name = _pushes(fr, ctx, wk, B, idx, dense, want, row["group"] if layer == "stream" else 5 if layer == "gather_out" else 4 if layer == "stages" else 1, what)
+            if layer == "stream":
+                assert name == row["kernel"], name
+            elif layer == "stages":
+                for k in range(4):
+                    wk.fc_layer_only(B, k)
+                    name = wk.last_kernel()
+                    wk.sync()
+                    assert name == E.PIPE % (k + 1, 0), (k, name)
+            elif layer != "gather_out":
+                wk.fc_layer_only(B, ("FC1", "FC2", "FC3").index(layer))
+                name = wk.last_kernel()
+                wk.sync()
+                assert name == row["kernel"], name
+    finally:
+        wk.close()
         ctx.close()
