@@ -95,6 +95,7 @@ ABI_SYMBOLS = [
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
     "fr_worker_submit_keyed", "fr_worker_key_misses",
+    "fr_worker_erase_keys", "fr_ctx_erase_keys", "fr_ctx_key_space_stats", "fr_ctx_export_keys", "fr_ctx_rebuild_key_space",
     "fr_ctx_set_epilogue", "fr_ctx_epilogue",
 ]
 
@@ -112,6 +113,7 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
                    "fr_worker_submit_keyed", "fr_worker_key_misses",
+                   "fr_worker_erase_keys", "fr_ctx_erase_keys", "fr_ctx_key_space_stats", "fr_ctx_export_keys", "fr_ctx_rebuild_key_space",
                    "fr_ctx_set_epilogue", "fr_ctx_epilogue")
 
 
@@ -205,6 +207,10 @@ def lib():
         "fr_ctx_put_keys": (i32, [vp, i32, i32, vp, vp]), "fr_worker_put_keys": (i32, [vp, i32, i32, vp, vp]),
         "fr_worker_resolve_keys_device": (i32, [vp, i32, i32, i32, vp, vp]), "fr_worker_key_ptr": (ctypes.POINTER(ctypes.c_int64), [vp]),
         "fr_worker_submit_keyed": (i32, [vp, i32, i32]), "fr_worker_key_misses": (i32, [vp, ctypes.POINTER(ctypes.c_uint64), i32]),
+        "fr_worker_erase_keys": (i32, [vp, i32, i32, vp]), "fr_ctx_erase_keys": (i32, [vp, i32, i32, vp]),
+        "fr_ctx_key_space_stats": (i32, [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+        "fr_ctx_export_keys": (i32, [vp, i32, i64, vp, vp, ctypes.POINTER(i64)]),
+        "fr_ctx_rebuild_key_space": (i32, [vp, i32, ctypes.c_uint64, i64]),
         "fr_ctx_set_epilogue": (i32, [vp, i32, vp, sz, i32]), "fr_ctx_epilogue": (i32, [vp, i32, vp, sz, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
@@ -740,6 +746,36 @@ class Context:
         if k.size != r.size:
             raise FleetRecError(FR_ERR_INVALID, "%d keys, %d rows" % (k.size, r.size))
         _check(lib().fr_ctx_put_keys(self._h, int(col), int(k.size), k.ctypes.data, r.ctypes.data))
+
+    def erase_keys(self, col, keys):
+        """fr_ctx_erase_keys: the row of every PRESENT key (int64) of MAPPED column col becomes the column's miss_row; an absent key writes nothing.
+        Synchronous, legal beside workers in flight.  A key of -1 raises FleetRecError(FR_ERR_INDEX_RANGE); every other key is applied."""
+        k = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        _check(lib().fr_ctx_erase_keys(self._h, int(col), int(k.size), k.ctypes.data))
+
+    def key_space_stats(self, col):
+        """-> (slots, occupied, live, probe_sum) of the map of MAPPED column col (fr_ctx_key_space_stats; synchronises the device):
+        1 + probe_sum / occupied is the mean number of probes of a present key."""
+        s, o, l, p = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _check(lib().fr_ctx_key_space_stats(self._h, int(col), ctypes.byref(s), ctypes.byref(o), ctypes.byref(l), ctypes.byref(p)))
+        return s.value, o.value, l.value, p.value
+
+    def export_keys(self, col):
+        """-> (keys int64 [live], rows int32 [live]): the live pairs of the map of MAPPED column col, in unspecified order (fr_ctx_export_keys: the
+        size query, then the export; synchronises the device)."""
+        n = ctypes.c_int64()
+        rc = lib().fr_ctx_export_keys(self._h, int(col), 0, None, None, ctypes.byref(n))
+        if rc != FR_OK and not (rc == FR_ERR_INVALID and n.value > 0):
+            _check(rc)
+        k, r = np.empty(n.value, np.int64), np.empty(n.value, np.int32)
+        if n.value:
+            _check(lib().fr_ctx_export_keys(self._h, int(col), int(n.value), k.ctypes.data, r.ctypes.data, ctypes.byref(n)))
+        return k, r
+
+    def rebuild_key_space(self, col, seed, max_keys):
+        """fr_ctx_rebuild_key_space: replace the map of MAPPED column col by one for max_keys keys under `seed` that holds exactly its live pairs
+        (dead slots are dropped); on the device, synchronous; no worker of the context may have work in flight."""
+        _check(lib().fr_ctx_rebuild_key_space(self._h, int(col), int(seed) & (2 ** 64 - 1), int(max_keys)))
 
     def synchronize(self):
         _check(lib().fr_device_synchronize(self._h))
@@ -1316,6 +1352,11 @@ class Worker:
         """fr_worker_put_keys: n pairs from device memory (d_keys int64, d_rows int32) into the map of MAPPED column col, asynchronous on the worker's
         stream; both stay valid until sync(), which reports a pair that could not be applied as FR_ERR_INDEX_RANGE."""
         _check(lib().fr_worker_put_keys(self._h, int(col), int(n), self._ptr(d_keys), self._ptr(d_rows)))
+
+    def erase_keys(self, col, n, d_keys):
+        """fr_worker_erase_keys: n keys from device memory (d_keys int64); the row of every present one becomes the column's miss_row, asynchronous on
+        the worker's stream; a key of -1 is reported by sync()."""
+        _check(lib().fr_worker_erase_keys(self._h, int(col), int(n), self._ptr(d_keys)))
 
     def resolve_keys_device(self, n_rows, d_keys, d_idx_out, rows_kind=KEY_ROWS_FULL, pooled=False):
         """fr_worker_resolve_keys_device: d_keys int64 [n_rows][W] -> d_idx_out int32 [n_rows][W]; W follows rows_kind (KEY_ROWS_FULL: the index or

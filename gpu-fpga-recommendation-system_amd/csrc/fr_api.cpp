@@ -3083,6 +3083,7 @@ static int key_spaces_init(fr_ctx *c) {
     FR_TRY(counts.alloc(fr_mem_kind(c, FrMem::DEVICE), C, "key counts"));
     if (c->cpu) memset(counts.p, 0, C * sizeof(uint32_t));
     else FR_HIP(hipMemset(counts.p, 0, C * sizeof(uint32_t)));
+    if (!c->cpu) FR_TRY(c->d_key_walk.alloc(FrMem::DEVICE, 3, "key-map walk counters"));
     c->d_key_counts.swap(counts);
     c->key_spaces.resize(C);
     return key_cols_upload(c);
@@ -3168,9 +3169,12 @@ static FrKeyPutArgs key_put_args(fr_ctx *c, int col, int n, const int64_t *keys,
 // what fr_worker_sync (or fr_ctx_put_keys itself) says about the bits of a status word; bit 0 is the lookups'
 static int index_range_fail(int bits) {
     const char *lookup = (bits & 1) ? "a lookup index was outside its table (row 0 was read instead)" : "";
-    if (!(bits & (FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_ROW | FR_KEYS_ERR_FULL))) FR_FAIL(FR_ERR_INDEX_RANGE, "%s", lookup);
-    FR_FAIL(FR_ERR_INDEX_RANGE, "%s%sa key put was not applied (every other pair was):%s%s%s", lookup, (bits & 1) ? "; " : "", (bits & FR_KEYS_ERR_EMPTY_KEY) ? " a key of -1 (FR_KEY_EMPTY);" : "",
-            (bits & FR_KEYS_ERR_ROW) ? " a row that is neither one of the column's rows nor its miss_row;" : "", (bits & FR_KEYS_ERR_FULL) ? " a new key for a map that holds max_keys keys;" : "");
+    const int put = bits & (FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_ROW | FR_KEYS_ERR_FULL);
+    const char *erase = (bits & FR_KEYS_ERR_ERASE_EMPTY) ? "a key erase was not applied (every other key was): a key of -1 (FR_KEY_EMPTY);" : "";
+    if (!put) FR_FAIL(FR_ERR_INDEX_RANGE, "%s%s%s", lookup, (bits & 1) && *erase ? "; " : "", erase);
+    FR_FAIL(FR_ERR_INDEX_RANGE, "%s%sa key put was not applied (every other pair was):%s%s%s%s%s", lookup, (bits & 1) ? "; " : "", (bits & FR_KEYS_ERR_EMPTY_KEY) ? " a key of -1 (FR_KEY_EMPTY);" : "",
+            (bits & FR_KEYS_ERR_ROW) ? " a row that is neither one of the column's rows nor its miss_row;" : "", (bits & FR_KEYS_ERR_FULL) ? " a new key for a map that holds max_keys keys;" : "",
+            *erase ? " " : "", erase);
 }
 
 extern "C" int fr_worker_put_keys(fr_worker *w, int col, int n, const int64_t *d_keys, const int32_t *d_rows) {
@@ -3224,6 +3228,195 @@ extern "C" int fr_ctx_put_keys(fr_ctx *ctx, int col, int n, const int64_t *h_key
     if (e) FR_FAIL(FR_ERR_HIP, "the key put launch failed: %s", hipGetErrorString((hipError_t)e));
     const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
     return bad ? index_range_fail(bad) : FR_OK;
+}
+
+// ---- the life cycle of a key map: erase, stats, export, rebuild (fleetrec_serving.h) --------------------------------------------------------------
+// The kernels are the fifth companion code object's (fr_keymaint.hip -> libfleetrec_keymaint.so); the CPU twins are frc_erase_keys / frc_walk_keys.
+static int key_erase_check(fr_ctx *c, int col, int n, const void *keys, const char *who) {
+    FR_TRY(key_col_check(c, col, who));
+    if (n < 0) FR_FAIL(FR_ERR_INVALID, "%s: n = %d keys", who, n);
+    if (n > 0 && !keys) FR_FAIL(FR_ERR_INVALID, "%s: keys is NULL", who);
+    if (c->key_spaces.empty() || c->key_spaces[(size_t)col].mode != FR_KEYS_MAPPED)
+        FR_FAIL(FR_ERR_STATE, "%s: column %d has no map: call fr_ctx_set_key_space(ctx, %d, FR_KEYS_MAPPED, ...) first", who, col, col);
+    return FR_OK;
+}
+
+static FrKeyEraseArgs key_erase_args(fr_ctx *c, int col, int n, const int64_t *keys, int *err) {
+    FrKeyEraseArgs a{};
+    a.col = c->h_key_cols[(size_t)col], a.n = n, a.keys = keys, a.err_flag = err;
+    return a;
+}
+
+extern "C" int fr_worker_erase_keys(fr_worker *w, int col, int n, const int64_t *d_keys) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    fr_ctx *c = w->ctx;
+    FR_TRY(key_erase_check(c, col, n, d_keys, "fr_worker_erase_keys"));
+    if (n == 0) return FR_OK;
+    if ((uintptr_t)d_keys % 8) FR_FAIL(FR_ERR_INVALID, "fr_worker_erase_keys: d_keys must be 8-byte aligned");
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then erase");
+    if (c->cpu) {   // computed before the call returns, one writer at a time; a -1 key waits in c_err for fr_worker_sync
+        std::lock_guard<std::mutex> lk(c->lp_mutex);
+        const int bad = frc_erase_keys(key_erase_args(c, col, n, d_keys, nullptr));
+        if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
+        return FR_OK;
+    }
+    FR_SET_DEVICE(c);
+    FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the erase: whatever they read was resolved against the old map
+    const FrKeyEraseArgs a = key_erase_args(c, col, n, d_keys, w->d_err);
+    const int e = fr_keymap_erase_launch(&a, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the key erase launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_erase_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_erase_check(ctx, col, n, h_keys, "fr_ctx_erase_keys"));
+    if (n == 0) return FR_OK;
+    if ((uintptr_t)h_keys % 8) FR_FAIL(FR_ERR_INVALID, "fr_ctx_erase_keys: h_keys must be 8-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_put_keys's
+    if (ctx->cpu) {
+        const int bad = frc_erase_keys(key_erase_args(ctx, col, n, h_keys, nullptr));
+        return bad ? index_range_fail(bad) : FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    if (!ctx->h_up_err) {
+        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
+        *ctx->h_up_err = 0;
+        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
+    }
+    FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
+    FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
+    const FrKeyEraseArgs a = key_erase_args(ctx, col, n, ctx->d_kp_keys, ctx->d_up_err);
+    const int e = fr_keymap_erase_launch(&a, (void *)ctx->setup_stream);
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    if (e) FR_FAIL(FR_ERR_HIP, "the key erase launch failed: %s", hipGetErrorString((hipError_t)e));
+    const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
+    return bad ? index_range_fail(bad) : FR_OK;
+}
+
+// One walk of column col's map (under key_mutex) on the set-up stream, waited for: counts[3] are zeroed first and read back.  The CPU back-end: the twin.
+static int key_walk(fr_ctx *c, FrKeyWalkArgs a, unsigned long long counts[3]) {
+    counts[0] = counts[1] = counts[2] = 0;
+    if (c->cpu) {
+        a.counts = counts;
+        frc_walk_keys(a);
+        return FR_OK;
+    }
+    unsigned long long *d = c->d_key_walk.p;   // (made with the key spaces: no call of the life cycle changes what the context holds besides its maps)
+    FR_HIP(hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), c->setup_stream));
+    a.counts = d, a.max_blocks = 4 * (c->n_cu > 0 ? c->n_cu : 256);
+    const int e = fr_keymap_walk_launch(&a, (void *)c->setup_stream);
+    if (e) {
+        (void)hipStreamSynchronize(c->setup_stream);
+        FR_FAIL(FR_ERR_HIP, "the key-map walk launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    FR_HIP(hipMemcpyAsync(counts, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->setup_stream));
+    FR_HIP(hipStreamSynchronize(c->setup_stream));
+    return FR_OK;
+}
+
+// what the three read-side calls share: the column is MAPPED, the device is idle
+static int key_map_ready(fr_ctx *c, int col, const char *who) {
+    FR_TRY(key_col_check(c, col, who));
+    if (c->key_spaces.empty() || c->key_spaces[(size_t)col].mode != FR_KEYS_MAPPED)
+        FR_FAIL(FR_ERR_STATE, "%s: column %d has no map: call fr_ctx_set_key_space(ctx, %d, FR_KEYS_MAPPED, ...) first", who, col, col);
+    if (!c->cpu) {
+        FR_SET_DEVICE(c);
+        FR_HIP(hipDeviceSynchronize());
+    }
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_key_space_stats(fr_ctx *ctx, int col, int64_t *slots, int64_t *occupied, int64_t *live, int64_t *probe_sum) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    std::lock_guard<std::mutex> lk(ctx->key_mutex);
+    FR_TRY(key_map_ready(ctx, col, "fr_ctx_key_space_stats"));
+    FrKeyWalkArgs a{};
+    a.col = ctx->h_key_cols[(size_t)col], a.sink = FR_KEYWALK_COUNT;
+    unsigned long long n[3];
+    FR_TRY(key_walk(ctx, a, n));
+    if (slots) *slots = (int64_t)a.col.mask + 1;
+    if (occupied) *occupied = (int64_t)n[0];
+    if (live) *live = (int64_t)n[1];
+    if (probe_sum) *probe_sum = (int64_t)n[2];
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_export_keys(fr_ctx *ctx, int col, int64_t cap, int64_t *h_keys, int32_t *h_rows, int64_t *n_out) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (n_out) *n_out = 0;
+    if (cap < 0) FR_FAIL(FR_ERR_INVALID, "fr_ctx_export_keys: cap = %lld", (long long)cap);
+    if (cap > 0 && (!h_keys || !h_rows)) FR_FAIL(FR_ERR_INVALID, "fr_ctx_export_keys: h_keys / h_rows is NULL with cap = %lld", (long long)cap);
+    std::lock_guard<std::mutex> lk(ctx->key_mutex);
+    FR_TRY(key_map_ready(ctx, col, "fr_ctx_export_keys"));
+    FrKeyWalkArgs a{};
+    a.col = ctx->h_key_cols[(size_t)col];
+    unsigned long long n[3];
+    a.sink = FR_KEYWALK_COUNT;   // the size first: nothing is written unless everything fits
+    FR_TRY(key_walk(ctx, a, n));
+    const uint64_t live = n[1];
+    if (n_out) *n_out = (int64_t)live;
+    if ((uint64_t)cap < live) FR_FAIL(FR_ERR_INVALID, "fr_ctx_export_keys: the map of column %d holds %llu live pairs, cap is %lld (nothing was written)", col, (unsigned long long)live, (long long)cap);
+    if (live == 0) return FR_OK;
+    a.sink = FR_KEYWALK_EXPORT, a.cap = live;   // (no put is in flight: the device was synchronised and the caller holds the map still)
+    if (ctx->cpu) {
+        a.out_keys = h_keys, a.out_rows = h_rows;
+        return key_walk(ctx, a, n);
+    }
+    FrBuf<int64_t> d_keys;
+    FrBuf<int32_t> d_rows;
+    FR_TRY(d_keys.alloc(FrMem::DEVICE, (size_t)live, "key export keys"));
+    FR_TRY(d_rows.alloc(FrMem::DEVICE, (size_t)live, "key export rows"));
+    a.out_keys = d_keys.p, a.out_rows = d_rows.p;
+    FR_TRY(key_walk(ctx, a, n));
+    if (n[0] != live) FR_FAIL(FR_ERR_STATE, "fr_ctx_export_keys: the map of column %d changed during the call (%llu live pairs, then %llu): a put or erase is in flight", col, (unsigned long long)live, n[0]);
+    FR_HIP(hipMemcpy(h_keys, d_keys.p, (size_t)live * sizeof(int64_t), hipMemcpyDeviceToHost));
+    FR_HIP(hipMemcpy(h_rows, d_rows.p, (size_t)live * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_rebuild_key_space(fr_ctx *ctx, int col, uint64_t seed, int64_t max_keys) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_col_check(ctx, col, "fr_ctx_rebuild_key_space"));
+    if (max_keys < 1 || max_keys > (1ll << 30)) FR_FAIL(FR_ERR_INVALID, "fr_ctx_rebuild_key_space: max_keys %lld outside [1, 2^30]", (long long)max_keys);
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_rebuild_key_space: keyed lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    FR_TRY(pooling_busy(ctx, "fr_ctx_rebuild_key_space"));
+    std::lock_guard<std::mutex> lk(ctx->key_mutex);
+    FR_TRY(key_map_ready(ctx, col, "fr_ctx_rebuild_key_space"));
+    fr_ctx::KeySpace &old = ctx->key_spaces[(size_t)col];
+    FrKeyWalkArgs a{};
+    a.col = ctx->h_key_cols[(size_t)col], a.sink = FR_KEYWALK_COUNT;
+    unsigned long long n[3];
+    FR_TRY(key_walk(ctx, a, n));
+    const uint64_t live = n[1];
+    if ((uint64_t)max_keys < live) FR_FAIL(FR_ERR_INVALID, "fr_ctx_rebuild_key_space: max_keys %lld is below the %llu live keys of column %d", (long long)max_keys, (unsigned long long)live, col);
+    fr_ctx::KeySpace next;   // (whatever fails from here on: `next` releases the new map, the old one stays as it was)
+    next.mode = FR_KEYS_MAPPED, next.seed = seed, next.max_keys = max_keys, next.miss_row = old.miss_row;
+    const uint64_t slots = fr_key_slots((uint64_t)max_keys);
+    FR_TRY(next.slots.alloc(fr_mem_kind(ctx, FrMem::DEVICE), (size_t)slots, "key map"));
+    FrKeyFillArgs f{next.slots.p, slots, old.miss_row};
+    if (ctx->cpu) {
+        frc_fill_keys(f);
+    } else {
+        const int e = fr_key_fill_launch(&f, (void *)ctx->setup_stream);   // (the walk below follows it on the same stream)
+        if (e) {
+            (void)hipStreamSynchronize(ctx->setup_stream);
+            FR_FAIL(FR_ERR_HIP, "the key map's fill launch failed: %s", hipGetErrorString((hipError_t)e));
+        }
+    }
+    a.sink = FR_KEYWALK_REHASH, a.dst = a.col;
+    a.dst.seed = seed, a.dst.slots = next.slots.p, a.dst.mask = (uint32_t)(slots - 1);
+    FR_TRY(key_walk(ctx, a, n));
+    if (n[0] != live) FR_FAIL(FR_ERR_HIP, "fr_ctx_rebuild_key_space: %llu of the %llu live pairs of column %d reached the new map (the old map stays)", n[0], (unsigned long long)live, col);
+    const uint32_t count = (uint32_t)live;
+    if (ctx->cpu) ctx->d_key_counts[col] = count;
+    else FR_HIP(hipMemcpy(ctx->d_key_counts + col, &count, sizeof(count), hipMemcpyHostToDevice));
+    std::swap(old, next);   // (no worker has work in flight: the old map is released with `next`)
+    return key_cols_upload(ctx);
 }
 
 // The word -> column tables of the six forms ([rows_kind][pooled]) for the pooling and the split as they stand, made again when either has changed

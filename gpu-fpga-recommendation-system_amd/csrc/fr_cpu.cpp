@@ -637,3 +637,47 @@ int frc_put_keys(const FrKeyPutArgs &a) {
 void frc_fill_keys(const FrKeyFillArgs &a) {
     for (uint64_t i = 0; i < a.n; i++) a.slots[i] = FrKeySlot{FR_KEYS_EMPTY_KEY, a.miss_row, 0};
 }
+
+// ---- the life cycle of a key map: the CPU twins of keymap_erase_kernel and keymap_walk_kernel (fr_keymaint.hip), on the same fr_keys.h functions ----
+int frc_erase_keys(const FrKeyEraseArgs &a) {
+    int bad = 0;
+    for (int i = 0; i < a.n; i++) {
+        const int64_t k = a.keys[i];
+        if (k == FR_KEYS_EMPTY_KEY) {
+            bad |= FR_KEYS_ERR_ERASE_EMPTY;
+            continue;
+        }
+        const int64_t at = fr_key_find(a.col, k);
+        if (at >= 0) __atomic_store_n(&a.col.slots[at].row, a.col.miss_row, __ATOMIC_RELEASE);
+    }
+    return bad;
+}
+
+void frc_walk_keys(const FrKeyWalkArgs &a) {
+    const uint64_t n = (uint64_t)a.col.mask + 1;
+    unsigned long long occupied = 0, live = 0, psum = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const FrKeySlot s = fr_key_load_slot(a.col.slots + i);
+        if (!fr_key_slot_occupied(s)) continue;
+        const bool l = fr_key_slot_live(s, a.col.miss_row);
+        if (a.sink == FR_KEYWALK_COUNT) {
+            occupied++, live += l, psum += fr_key_displacement(a.col, s.key, i);
+        } else if (a.sink == FR_KEYWALK_EXPORT) {
+            if (l && live < a.cap) a.out_keys[live] = s.key, a.out_rows[live] = s.row;
+            live += l;
+        } else if (l) {
+            uint64_t h = fr_key_home(a.dst, s.key);
+            for (uint64_t left = (uint64_t)a.dst.mask + 1; left; left--) {   // at most the new map's slots
+                FrKeySlot *d = a.dst.slots + h;
+                if (d->key == FR_KEYS_EMPTY_KEY) {
+                    d->key = s.key, d->row = s.row;
+                    live++;
+                    break;
+                }
+                h = (h + 1) & (uint64_t)a.dst.mask;
+            }
+        }
+    }
+    if (a.sink == FR_KEYWALK_COUNT) a.counts[0] += occupied, a.counts[1] += live, a.counts[2] += psum;
+    else a.counts[0] += live;
+}

@@ -352,6 +352,29 @@ extern "C" int fr_key_resolve_launch(const FrKeyResolveArgs *args, void *stream)
 extern "C" int fr_key_put_launch(const FrKeyPutArgs *args, void *stream);
 extern "C" int fr_key_fill_launch(const FrKeyFillArgs *args, void *stream);
 
+// ---- the life cycle of a key map (fr_keymaint.hip -> libfleetrec_keymaint.so, the fifth companion code object; fr_cpu.cpp has the twins) ----
+constexpr int FR_KEYMAINT_PER_THREAD = 4;   // slots a thread of keymap_walk_kernel loads per trip before its first compare
+enum { FR_KEYWALK_COUNT = 0, FR_KEYWALK_EXPORT = 1, FR_KEYWALK_REHASH = 2 };
+struct FrKeyEraseArgs {
+    FrKeyCol col;                // a MAPPED column
+    int n;
+    const int64_t *keys;         // [n]
+    int *err_flag;               // FR_KEYS_ERR_ERASE_EMPTY
+};
+struct FrKeyWalkArgs {
+    FrKeyCol col;                // the map that is walked
+    int sink;                    // FR_KEYWALK_*
+    int max_blocks;              // workgroups the launch takes at most (they stride over chunks of 256 x FR_KEYMAINT_PER_THREAD slots)
+    unsigned long long *counts;  // COUNT: [0] occupied, [1] live, [2] probe_sum; EXPORT: [0] the pairs reserved; REHASH: [0] the pairs inserted
+    int64_t *out_keys;           // EXPORT: [cap]
+    int32_t *out_rows;           // EXPORT: [cap]
+    uint64_t cap;
+    FrKeyCol dst;                // REHASH: the new map (its seed, mask and slots; pre-filled)
+};
+// Each enqueues its one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_keymap_erase_launch(const FrKeyEraseArgs *args, void *stream);
+extern "C" int fr_keymap_walk_launch(const FrKeyWalkArgs *args, void *stream);
+
 // ---- host objects -------------------------------------------------------------------------------
 // Where a table's rows live inside ctx->table_arena.  A table stored on its own: row r at byte_offset + r * dim * 4 (il_rows == 0).
 // FR_INDEX_PER_BANK contexts interleave the tables of one memory bank: rows [0, il_rows) of every table of the bank share one
@@ -455,6 +478,7 @@ struct fr_ctx {
     std::vector<FrKeyCol> h_key_cols;      // [index columns]: what d_key_cols holds
     FrBuf<FrKeyCol> d_key_cols;
     FrBuf<uint32_t> d_key_counts;          // [index columns]: keys in every map
+    FrBuf<unsigned long long> d_key_walk;  // [3]: the counters of one walk of a map (fr_keymaint.hip); device contexts only, used under key_mutex on the set-up stream
     std::mutex key_mutex;                  // guards the creation of the key spaces (key_spaces_init) and the tables below; the CPU back-end's puts take lp_mutex
     struct KeyTable {
         size_t first = 0;                  // inside d_key_wcol
@@ -669,6 +693,10 @@ int frc_expand_requests(const FrRequestArgs &a);
 void frc_resolve_keys(const FrKeyResolveArgs &a);
 int frc_put_keys(const FrKeyPutArgs &a);
 void frc_fill_keys(const FrKeyFillArgs &a);
+// the CPU twins of fr_keymap_erase_launch (-> FR_KEYS_ERR_ERASE_EMPTY or 0; the callers hold fr_ctx::lp_mutex) and fr_keymap_walk_launch (one pass,
+// slot after slot, the same fr_keys.h predicates; export order: by slot)
+int frc_erase_keys(const FrKeyEraseArgs &a);
+void frc_walk_keys(const FrKeyWalkArgs &a);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const FrEpi epi[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \

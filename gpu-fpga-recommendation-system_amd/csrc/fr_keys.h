@@ -1,5 +1,5 @@
 // Keyed lookups (fleetrec_serving.h, "Keyed lookups"): ONE definition of the slot layout, of mix64 and of the probe rule, included by the kernels
-// (fr_keys.hip -> libfleetrec_keys.so, the third companion code object), by the CPU back-end (fr_cpu.cpp) and, through fr_internal.h, by the host
+// (fr_keys.hip -> libfleetrec_keys.so, the third companion code object; fr_keymaint.hip -> libfleetrec_keymaint.so, the fifth), by the CPU back-end (fr_cpu.cpp) and, through fr_internal.h, by the host
 // side.  Everything here is plain data or an inline function; nothing is a symbol of any library.
 #pragma once
 
@@ -18,6 +18,7 @@ constexpr int FR_KEYS_LDS_WORDS = 2048;             // words of the word -> colu
 constexpr int FR_KEYS_LDS_COLS = 384;               // column records a workgroup of key_resolve_kernel stages in LDS (12 KiB); more: read in place
 // what a put raises in the status word it is given (bit 0 stays the lookups' own "index outside its table")
 constexpr int FR_KEYS_ERR_EMPTY_KEY = 2, FR_KEYS_ERR_ROW = 4, FR_KEYS_ERR_FULL = 8;
+constexpr int FR_KEYS_ERR_ERASE_EMPTY = 16;         // what an erase raises there: a key of -1 in its list
 
 struct FrKeySlot {   // 16 bytes, 16-byte aligned: one probe is one load
     int64_t key;     // FR_KEYS_EMPTY_KEY: nobody has claimed the slot
@@ -105,3 +106,25 @@ FR_KEYS_HD int32_t fr_key_resolve(const FrKeyCol &c, int64_t k, bool *miss) {
 
 // a row a put may store: one of the column's rows, or the column's own miss_row (which "forgets" the key)
 FR_KEYS_HD bool fr_key_row_legal(uint32_t range, int32_t miss_row, int32_t row) { return row == miss_row || (row >= 0 && (uint32_t)row < range); }
+
+// ---- the life cycle of a map (fr_*_erase_keys, fr_ctx_key_space_stats, fr_ctx_export_keys, fr_ctx_rebuild_key_space; fr_keymaint.hip and the CPU twins) ----
+// A slot is OCCUPIED when it holds a key, DEAD when it is occupied and its row is the column's miss_row (an erased or "forgotten" key -- or a key put
+// on purpose with a row equal to a miss_row that is a real row), LIVE when it is occupied and not dead.
+FR_KEYS_HD bool fr_key_slot_occupied(const FrKeySlot &s) { return s.key != FR_KEYS_EMPTY_KEY; }
+FR_KEYS_HD bool fr_key_slot_dead(const FrKeySlot &s, int32_t miss_row) { return s.key != FR_KEYS_EMPTY_KEY && s.row == miss_row; }
+FR_KEYS_HD bool fr_key_slot_live(const FrKeySlot &s, int32_t miss_row) { return s.key != FR_KEYS_EMPTY_KEY && s.row != miss_row; }
+
+// how far from its home slot the key of slot `at` sits (wrapping): 1 + the sum over the occupied slots / their number = the mean probes of a present key
+FR_KEYS_HD uint64_t fr_key_displacement(const FrKeyCol &c, int64_t k, uint64_t at) { return (at - fr_key_home(c, k)) & (uint64_t)c.mask; }
+
+// fr_key_probe's walk, returning WHERE the key sits: -> the slot index, or -1 when no slot holds the key.  At most `slots` probes whatever the memory holds.
+FR_KEYS_HD int64_t fr_key_find(const FrKeyCol &c, int64_t k) {
+    uint64_t h = fr_key_home(c, k);
+    for (uint64_t left = (uint64_t)c.mask;; left--) {   // the home slot + mask more = slots probes
+        const FrKeySlot s = fr_key_load_slot(c.slots + h);
+        if (s.key == k) return (int64_t)h;
+        if (s.key == FR_KEYS_EMPTY_KEY || left == 0) break;
+        h = (h + 1) & (uint64_t)c.mask;
+    }
+    return -1;
+}

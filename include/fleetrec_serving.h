@@ -403,7 +403,7 @@ int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int pooled /* 
  * fr_worker_key_misses: the MAPPED lookups of this worker that found no slot holding their key, since the worker was created or the counter was last reset;
  *   it synchronises the worker's stream (nothing is flushed).  The counter lives in device memory; a wave adds to it once, not a lane.
  * Out of scope: flat key arrays for the offsets (CSR) form; keyed forms of fr_worker_push_host and fr_worker_submit_requests; the TCP wire format of
- *   fleetrec_server; sharded contexts; erasing slots and growing a map. */
+ *   fleetrec_server; sharded contexts.  (Retiring keys and growing a map: "The life cycle of a key map" below.) */
 #define FR_KEYS_ROWS   0
 #define FR_KEYS_HASHED 1
 #define FR_KEYS_MAPPED 2
@@ -420,6 +420,45 @@ int fr_worker_resolve_keys_device(fr_worker *w, int n_rows, int rows_kind, int p
 int64_t *fr_worker_key_ptr(fr_worker *w);
 int fr_worker_submit_keyed(fr_worker *w, int batch, int pooled /* 0 one-hot, 1 pooled, 2 pooled weighted */);
 int fr_worker_key_misses(fr_worker *w, uint64_t *misses, int reset);
+
+/* The life cycle of a key map (additive in ABI 6): retire ids, look at a map, and compact / grow / shrink / reseed it on the device.
+ * For a MAPPED column a slot is OCCUPIED when its key is not -1, DEAD when it is occupied and its row equals the column's miss_row, LIVE when it is
+ *   occupied and not dead.  Dead is exactly what putting miss_row ("forgetting") has always produced; a key put on purpose with a row equal to a
+ *   miss_row that is a real row of the column is dead by the same definition: export does not list it and a rebuild drops it (it resolves to the same
+ *   row before and after, as a miss afterwards).
+ * Erase: n keys of ONE MAPPED column.  A present key's row becomes miss_row; the slot keeps its key (probe chains stay whole) and the key still counts in
+ *   n_keys.  An ABSENT key writes nothing, claims nothing and is no error -- the difference from put(k, miss_row), which inserts.  A key of -1 is not
+ *   applied and is reported: FR_ERR_INDEX_RANGE at fr_worker_sync (fr_ctx_erase_keys returns it itself), fr_last_error() naming the key erase and
+ *   FR_KEY_EMPTY; every other key of the call is applied and the worker stays usable.  A later put of an erased key gives it a row again in the same
+ *   slot, n_keys unchanged.  An erased key is no miss for fr_worker_key_misses, an absent one is.
+ *   fr_worker_erase_keys: device pointer (host pointer on the CPU back-end, which computes before it returns), asynchronous on the worker's stream;
+ *   d_keys (8-byte aligned, FR_ERR_INVALID otherwise, in the host form too) stays valid until fr_worker_sync(w) has returned.  fr_ctx_erase_keys: the host
+ *   form, synchronous on the context's set-up stream, legal beside workers in flight.  Arguments and order are fr_worker_put_keys's: n == 0 is FR_OK;
+ *   n < 0, a NULL pointer with n > 0, a column out of range: FR_ERR_INVALID; a column that is not MAPPED: FR_ERR_STATE; on one worker keys resolved BEFORE
+ *   the call see the old rows, keys resolved AFTER it the erased ones; batches queued for a fused launch are launched first; host-fed batches still
+ *   queued in a block make the call FR_ERR_STATE (flush first).  Across workers a resolve in flight sees, per key, the old row or miss_row, never anything
+ *   else (one 4-byte store).  Erase and put of the same key on different unsynchronised workers: one of the two results, unspecified which.
+ * fr_ctx_key_space_stats: slots = the slot count; occupied (= n_keys of fr_ctx_key_space when no put is in flight); live; probe_sum = the sum over the
+ *   occupied slots of (slot - home(key)) & (slots - 1), so 1 + probe_sum / occupied is the mean number of probes of a present key.  probe_sum, unlike
+ *   the longest displacement, does not depend on the order in which the keys were put.  Any output pointer may be NULL; it synchronises the device as
+ *   fr_ctx_key_space does.  A column that is not MAPPED: FR_ERR_STATE.
+ * fr_ctx_export_keys: the LIVE pairs into host arrays of cap elements each, in unspecified order; *n_out = their number.  cap < live: FR_ERR_INVALID with
+ *   *n_out = live and nothing written (cap == 0 with NULL arrays is the size query).  Never a byte past cap elements of either array.  It synchronises
+ *   the device first; a put or erase racing it from another thread makes the result unspecified.  A column that is not MAPPED: FR_ERR_STATE.
+ * fr_ctx_rebuild_key_space replaces the column's map by a new one of fr_key_slots(max_keys) slots (the smallest power of two >= 2 * max_keys) with home
+ *   slot mix64(k ^ seed) & (slots - 1), pre-filled with the UNCHANGED miss_row, holding exactly the live pairs of the old one: dead slots are dropped,
+ *   n_keys becomes live, max_keys and seed become the arguments.  Afterwards every key resolves to the row it resolved to before; the one visible
+ *   difference is that a dropped key is now a miss for fr_worker_key_misses.  It runs on the context's set-up stream, is synchronous, and the pairs
+ *   never leave the device.  State: the rule of fr_ctx_set_key_space -- a worker of the context with work in flight, or a context with n_shards > 1:
+ *   FR_ERR_STATE (a live, undrained rebuild is out of scope).  FR_ERR_INVALID: max_keys outside 1 .. 2^30 or below live; FR_ERR_STATE: a column that is
+ *   not MAPPED; FR_ERR_OOM: old and new map coexist during the call.  In every error case the old map stays exactly as it was.  On success the old map
+ *   is released before the call returns; workers created earlier keep working; other columns are untouched.
+ * Out of scope: reusing dead slots in place; a rebuild beside workers in flight; sharded contexts; keyed CSR arrays; fleetrec_server's wire format. */
+int fr_worker_erase_keys(fr_worker *w, int col, int n, const int64_t *d_keys);
+int fr_ctx_erase_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys);
+int fr_ctx_key_space_stats(fr_ctx *ctx, int col, int64_t *slots, int64_t *occupied, int64_t *live, int64_t *probe_sum);
+int fr_ctx_export_keys(fr_ctx *ctx, int col, int64_t cap, int64_t *h_keys, int32_t *h_rows, int64_t *n_out);
+int fr_ctx_rebuild_key_space(fr_ctx *ctx, int col, uint64_t seed, int64_t max_keys);
 
 /* ---- per-layer epilogue: bias and ReLU between the FC layers ----
  * The reference's chain is four matrix products with nothing between them (alpha = 1, beta = 0, cuda_server.c:211-217), which no trained model

@@ -1,0 +1,611 @@
+"""The life cycle of a key map (fr_*_erase_keys / fr_ctx_key_space_stats / fr_ctx_export_keys / fr_ctx_rebuild_key_space): the checks, stated once and
+parameterised by device; the tests are tests/test_cpu_key_lifecycle.py (device = -1) and tests/test_gpu_key_lifecycle.py.  The reference is the
+contract in plain Python: keyed.Spaces' dict per MAPPED column -- an erase sets a present key's row to the column's miss_row, a rebuild keeps the
+items whose row is not miss_row -- and, for probe_sum, a replay of linear probing over the occupied key set (probe_sum has one right answer per key
+set whatever the insertion order, so the replay inserts in dict order).  Every comparison is exact."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+import keyed as K
+import rank_topk as R
+import request_form as Q
+
+CPU = K.CPU
+ROOT = K.ROOT
+KEYMAINT_LIB = os.path.join(ROOT, "gpu-fpga-recommendation-system_amd", "libfleetrec_keymaint.so")
+NO_ROW = K.NO_ROW
+GUARD = 64
+CANARY64, CANARY32 = 0x5a5a5a5a5a5a5a5a, 0x5a5a5a5a
+ERASE_SIZES = (1, 63, 64, 65, 255, 256, 257, 301)     # around a wave and around a workgroup of keymap_erase_kernel
+# What one trip of keymap_walk_kernel covers: the grid cap (4 workgroups per CU x 256 CUs) x 256 threads x 4 slots per thread (FR_KEYMAINT_PER_THREAD)
+WALK_SPAN = 4 * 256 * 256 * 4                         # = 2^20 slots; BIG_MAX_KEYS gives 2^21 slots: two trips of every workgroup
+BIG_MAX_KEYS = 1 << 20
+BIG_KEYS = 300000
+
+
+# ---- the reference -------------------------------------------------------------------------------------------------------------------------------
+
+def homes(keys, seed, slots):
+    """mix64(k ^ seed) & (slots - 1) of an int64 array, in numpy (equal to keyed.home key by key)"""
+    z = np.asarray(keys, np.int64).view(np.uint64) ^ np.uint64(seed)
+    z ^= z >> np.uint64(30)
+    z *= np.uint64(0xbf58476d1ce4e5b9)
+    z ^= z >> np.uint64(27)
+    z *= np.uint64(0x94d049bb133111eb)
+    z ^= z >> np.uint64(31)
+    return (z & np.uint64(slots - 1)).astype(np.int64)
+
+
+def probe_sum(keys, seed, slots):
+    """the sum of the displacements after inserting `keys` (distinct) by linear probing, in the order given"""
+    taken, total = set(), 0
+    for h in homes(np.array(list(keys), np.int64), seed, slots).tolist() if len(keys) else []:
+        d = 0
+        while ((h + d) & (slots - 1)) in taken:
+            d += 1
+        taken.add((h + d) & (slots - 1))
+        total += d
+    return total
+
+
+def erase_ref(sp, col, keys):
+    for k in keys:
+        if int(k) != -1 and int(k) in sp.map[col]:
+            sp.map[col][int(k)] = sp.miss[col]
+
+
+def live_items(sp, col):
+    return sorted((k, r) for k, r in sp.map[col].items() if r != sp.miss[col])
+
+
+def want_stats(sp, col):
+    slots = K.slots_of(sp.max_keys[col])
+    return slots, len(sp.map[col]), len(live_items(sp, col)), probe_sum(sp.map[col].keys(), sp.seed[col], slots)
+
+
+def exported(ctx, col):
+    k, r = ctx.export_keys(col)
+    assert k.dtype == np.int64 and r.dtype == np.int32 and k.shape == r.shape
+    return sorted(zip(k.tolist(), r.tolist()))
+
+
+def rebuild(sp, ctx, col, seed, max_keys):
+    """the library's call and the reference's: dead keys are dropped"""
+    ctx.rebuild_key_space(col, seed, max_keys)
+    sp.map[col] = dict(live_items(sp, col))
+    sp.seed[col], sp.max_keys[col] = seed, max_keys
+
+
+def assert_map(fr, sp, ctx, col, what):
+    """stats, key_space() and the export against the reference"""
+    assert ctx.key_space_stats(col) == want_stats(sp, col), (what, ctx.key_space_stats(col), want_stats(sp, col))
+    assert ctx.key_space(col) == (fr.KEYS_MAPPED, sp.seed[col], sp.max_keys[col], len(sp.map[col]), sp.miss[col]), (what, ctx.key_space(col))
+    assert exported(ctx, col) == live_items(sp, col), what
+
+
+class Asker:
+    """resolves keys of ONE column of the narrow model on a worker and compares with the reference"""
+
+    def __init__(self, fr, ctx, wk, sp, col):
+        self.fr, self.ctx, self.wk, self.sp, self.col = fr, ctx, wk, sp, col
+
+    def rows(self, ask):
+        keys = np.full((len(ask), 3), -1, np.int64)
+        keys[:, self.col] = ask
+        return K.run_resolve(self.fr, self.ctx, self.wk, keys)[:, self.col]
+
+    def check(self, ask, what):
+        """-> the misses the reference expects of these lookups"""
+        ref = [self.sp.row(self.col, k) for k in ask]
+        got = self.rows(ask)
+        assert np.array_equal(got, np.array([r for r, _ in ref], np.int64).astype(np.int32)), (what, got)
+        return sum(m for _, m in ref)
+
+
+def random_keys(rng, n, avoid=()):
+    out, seen = [], set(avoid) | {-1}
+    while len(out) < n:
+        x = int(rng.integers(K.I64_MIN, K.I64_MAX, dtype=np.int64))
+        if x not in seen:
+            out.append(x)
+            seen.add(x)
+    return out
+
+
+def rows_not(rng, n, R_c, miss):
+    """n rows of the column, none of them its miss_row (such a pair would be dead)"""
+    return [int(x) for x in (rng.integers(0, R_c - 1, size=n) + 1 + (miss if 0 <= miss < R_c else -1)) % R_c]
+
+
+class Bufs:
+    def __init__(self, fr, ctx):
+        self.fr, self.ctx, self.all = fr, ctx, []
+
+    def __call__(self, a):
+        self.all.append(self.fr.DeviceBuffer.from_numpy(self.ctx, np.ascontiguousarray(a)))
+        return self.all[-1]
+
+    def free(self):
+        for b in self.all:
+            b.free()
+
+
+def chain_map(fr, sp, rng, col, max_keys, seed, miss):
+    """keyed.check_probe_chains' map: filled to the last place, up to five keys whose home is the LAST slot so that the chain wraps.
+    -> (the chain's keys in the map, absent keys on the chain, the other keys)"""
+    slots, R_c = K.slots_of(max_keys), sp.ranges[col]
+    sp.set(col, fr.KEYS_MAPPED, seed, max_keys, miss)
+    on_chain, k = [], 1
+    while len(on_chain) < 9:
+        if K.home(k, seed, slots) == slots - 1:
+            on_chain.append(k)
+        k += 1
+    n_chain = min(max_keys, 5)
+    others = random_keys(rng, max_keys - n_chain, avoid=on_chain)
+    have = on_chain[:n_chain] + others
+    sp.put(col, have, rows_not(rng, len(have), R_c, miss))
+    return on_chain[:n_chain], on_chain[n_chain:], others
+
+
+# ---- 1. erase (and 4. export of the state it leaves) ---------------------------------------------------------------------------------------------
+
+def check_erase(fr, device):
+    """-> [(what, stats, sorted export, resolved rows)] for the comparison across back-ends"""
+    out = []
+    L = fr.lib()
+    for n_case, miss_kind in enumerate(("minus one", "row", "no row")):
+        rng = np.random.default_rng(8100 + n_case)
+        m, ctx = Q.context(fr, device, "narrow")
+        bufs = Bufs(fr, ctx)
+        try:
+            sp = K.Spaces(fr, ctx, m)
+            col, R_c, MAXK = 1, sp.ranges[1], 16
+            miss = {"minus one": -1, "row": 7, "no row": NO_ROW}[miss_kind]
+            sp.set(col, fr.KEYS_MAPPED, 0x51 + n_case, MAXK, miss)
+            wk = fr.Worker(ctx, 512)
+            ask = Asker(fr, ctx, wk, sp, col)
+            have = random_keys(rng, MAXK - 2) + [0, K.I64_MIN]
+            sp.put(col, have, rows_not(rng, MAXK, R_c, miss))
+            absent = random_keys(rng, 400, avoid=have)
+            erased = []
+            for i, n in enumerate(ERASE_SIZES):
+                victim = have[i]
+                lst = ([victim, victim] + erased[-3:] + absent)[:n]                          # present and listed twice, already erased, absent
+                lst = [lst[j] for j in rng.permutation(n)]
+                if i % 2:
+                    ctx.erase_keys(col, lst)
+                else:
+                    wk.erase_keys(col, n, bufs(np.array(lst, np.int64)))
+                    wk.sync()
+                erase_ref(sp, col, lst)
+                erased.append(victim)
+                what = "%s, erase list of %d" % (miss_kind, n)
+                assert ctx.key_space(col)[3] == MAXK, what + ": absent keys changed n_keys"
+                wk.key_misses()
+                misses = ask.check(have + absent[:40] + [-1], what)
+                assert misses == 40 and wk.key_misses() == 40, what                     # an erased key is no miss, an absent one is
+                assert all(sp.row(col, k) == (miss, False) for k in erased)
+            assert_map(fr, sp, ctx, col, miss_kind)
+            assert len(live_items(sp, col)) == MAXK - len(ERASE_SIZES)
+            # a -1 among good keys: reported, the other keys applied, the next sync clean
+            for via in ("ctx", "worker"):
+                lst = [have[8 if via == "ctx" else 9], -1, absent[0]]
+                if via == "ctx":
+                    assert R.status_of(fr, lambda: ctx.erase_keys(col, lst)) == fr.FR_ERR_INDEX_RANGE
+                else:
+                    wk.erase_keys(col, 3, bufs(np.array(lst, np.int64)))
+                    assert R.status_of(fr, wk.sync) == fr.FR_ERR_INDEX_RANGE
+                msg = L.fr_last_error().decode()
+                assert "key erase" in msg and "FR_KEY_EMPTY" in msg and "key put" not in msg, msg
+                erase_ref(sp, col, lst)
+                ask.check(have + absent[:3], "good keys beside a -1, " + via)
+                wk.sync()
+            assert ctx.key_space(col)[3] == MAXK
+            # a put gives an erased key a row again, in the same slot
+            before = ctx.key_space_stats(col)
+            sp.put(col, [have[0], have[9]], rows_not(rng, 2, R_c, miss))
+            wk.put_keys(col, 1, bufs(np.array([have[1]], np.int64)), bufs(np.array([(miss + 2) % R_c if 0 <= miss < R_c else 2], np.int32)))
+            wk.sync()
+            sp.map[col][have[1]] = (miss + 2) % R_c if 0 <= miss < R_c else 2
+            after = ctx.key_space_stats(col)
+            assert after == (before[0], before[1], before[2] + 3, before[3]) and ctx.key_space(col)[3] == MAXK
+            ask.check(have + absent[:5], "put after erase")
+            assert_map(fr, sp, ctx, col, miss_kind + ", after the re-put")
+            check_export_edges(fr, ctx, sp, col)
+            out.append((miss_kind, ctx.key_space_stats(col), exported(ctx, col), ask.rows(have + absent[:40]).tolist()))
+            # arguments and state, as fr_*_put_keys
+            k8 = np.arange(4, dtype=np.int64)
+            d_k = bufs(k8)
+            INV, ST, OK = fr.FR_ERR_INVALID, fr.FR_ERR_STATE, fr.FR_OK
+            for er, a in ((lambda *x: L.fr_ctx_erase_keys(ctx._h, *x), k8.ctypes.data), (lambda *x: L.fr_worker_erase_keys(wk._h, *x), d_k.ptr)):
+                assert er(col, 0, None) == OK and er(col, -1, a) == INV and er(col, 4, None) == INV and er(3, 4, a) == INV and er(-1, 4, a) == INV
+                assert er(0, 4, a) == ST and "FR_KEYS_MAPPED" in L.fr_last_error().decode()
+                assert er(col, 2, ctypes.c_void_p((a if isinstance(a, int) else a.value) + 4)) == INV and "aligned" in L.fr_last_error().decode()
+            assert L.fr_ctx_erase_keys(None, col, 4, k8.ctypes.data) == INV and L.fr_worker_erase_keys(None, col, 4, d_k.ptr) == INV
+            wk.sync()
+            assert exported(ctx, col) == live_items(sp, col), "a refused erase changed the map"
+            wk.close()
+        finally:
+            bufs.free()
+            ctx.close()
+    return out
+
+
+def check_export_edges(fr, ctx, sp, col):
+    """cap == live with canaries behind both arrays; cap == live - 1: FR_ERR_INVALID, *n_out == live, nothing written; cap 0 / NULL: the size"""
+    L, h = fr.lib(), ctx._h
+    live = len(live_items(sp, col))
+    n = ctypes.c_int64(-5)
+    assert L.fr_ctx_export_keys(h, col, 0, None, None, ctypes.byref(n)) == (fr.FR_ERR_INVALID if live else fr.FR_OK) and n.value == live
+    for cap in (live, live - 1):
+        k, r = np.full(live + GUARD, CANARY64, np.uint64), np.full(live + GUARD, CANARY32, np.uint32)
+        n = ctypes.c_int64(-5)
+        rc = L.fr_ctx_export_keys(h, col, cap, k.ctypes.data, r.ctypes.data, ctypes.byref(n))
+        assert n.value == live
+        if cap == live:
+            assert rc == fr.FR_OK and (k[live:] == CANARY64).all() and (r[live:] == CANARY32).all(), "a canary behind the export was written"
+            assert sorted(zip(k[:live].view(np.int64).tolist(), r[:live].view(np.int32).tolist())) == live_items(sp, col)
+        elif cap >= 0:
+            assert rc == fr.FR_ERR_INVALID and (k == CANARY64).all() and (r == CANARY32).all(), "a refused export wrote"
+    assert L.fr_ctx_export_keys(h, col, live, None, None, None) == (fr.FR_ERR_INVALID if live else fr.FR_OK)
+    assert L.fr_ctx_export_keys(None, col, 0, None, None, None) == fr.FR_ERR_INVALID and L.fr_ctx_export_keys(h, 3, 0, None, None, None) == fr.FR_ERR_INVALID
+    assert L.fr_ctx_export_keys(h, 0, 0, None, None, None) == fr.FR_ERR_STATE and L.fr_ctx_key_space_stats(h, 0, None, None, None, None) == fr.FR_ERR_STATE
+    assert L.fr_ctx_key_space_stats(h, col, None, None, None, None) == fr.FR_OK and L.fr_ctx_key_space_stats(None, col, None, None, None, None) == fr.FR_ERR_INVALID
+
+
+def check_export_empty_and_device_built(fr, device):
+    """an empty map exports nothing; a map built only through fr_worker_put_keys exports what was put"""
+    rng = np.random.default_rng(8400)
+    m, ctx = Q.context(fr, device, "narrow")
+    bufs = Bufs(fr, ctx)
+    try:
+        sp = K.Spaces(fr, ctx, m)
+        col = 2
+        sp.set(col, fr.KEYS_MAPPED, 9, 600, -1)
+        assert exported(ctx, col) == [] and ctx.key_space_stats(col) == (2048, 0, 0, 0)
+        check_export_edges(fr, ctx, sp, col)
+        wk = fr.Worker(ctx, 64)
+        have = random_keys(rng, 600)
+
+        def by_worker(c, keys, rows):
+            wk.put_keys(c, len(keys), bufs(np.asarray(keys, np.int64)), bufs(np.asarray(rows, np.int32)))
+            wk.sync()
+
+        sp.put(col, have[:300], rows_not(rng, 300, sp.ranges[col], -1), via=by_worker)
+        sp.put(col, have[300:], rows_not(rng, 300, sp.ranges[col], -1), via=by_worker)
+        assert_map(fr, sp, ctx, col, "built by fr_worker_put_keys")
+        wk.close()
+    finally:
+        bufs.free()
+        ctx.close()
+
+
+# ---- 2. chains ---------------------------------------------------------------------------------------------------------------------------------------
+
+def check_chains(fr, device):
+    out = []
+    rng = np.random.default_rng(8200)
+    m, ctx = Q.context(fr, device, "narrow")
+    try:
+        sp = K.Spaces(fr, ctx, m)
+        wk = fr.Worker(ctx, 2048)
+        col = 2
+        ask = Asker(fr, ctx, wk, sp, col)
+        for max_keys in (1, 2, 8, 1000):
+            chain, chain_absent, others = chain_map(fr, sp, rng, col, max_keys, 0x1234 + max_keys, 3)
+            what = "max_keys %d" % max_keys
+            assert_map(fr, sp, ctx, col, what + ", full")
+            victims = [chain[0]] + ([chain[len(chain) // 2]] if len(chain) > 2 else [])     # the first and a middle key of the wrapped chain
+            ctx.erase_keys(col, victims + chain_absent[:2])
+            erase_ref(sp, col, victims)
+            absent = chain_absent + random_keys(rng, 40, avoid=chain + others)
+            wk.key_misses()
+            assert ask.check(chain + others + absent + [-1], what) == len(absent) == wk.key_misses()
+            assert_map(fr, sp, ctx, col, what + ", after the erase")
+            out.append((what, ctx.key_space_stats(col), exported(ctx, col), ask.rows(chain + others + absent).tolist()))
+        wk.close()
+    finally:
+        ctx.close()
+    return out
+
+
+# ---- 3. stream order ---------------------------------------------------------------------------------------------------------------------------------
+
+def check_stream_order(fr, device, two_workers):
+    m, ctx = Q.context(fr, device, "narrow")
+    bufs = Bufs(fr, ctx)
+    try:
+        sp = K.Spaces(fr, ctx, m)
+        col = 1
+        sp.set(col, fr.KEYS_MAPPED, 78, 16, 5)
+        sp.put(col, [1, 2, 3, 4], [10, 20, 30, 40])
+        wk = fr.Worker(ctx, 64)
+        ask = np.array([1, 2, 3, 4, 6], np.int64)
+        keys = np.full((5, 3), -1, np.int64)
+        keys[:, col] = ask
+        d_keys, d_a, d_b, d_c = bufs(keys), bufs(np.zeros(15, np.int32)), bufs(np.zeros(15, np.int32)), bufs(np.zeros(15, np.int32))
+        got = lambda d: list(d.download(np.int32, 15).reshape(5, 3)[:, col])
+        # one worker: resolve, erase, resolve, put (one key re-admitted), resolve, ONE sync
+        wk.resolve_keys_device(5, d_keys, d_a)
+        wk.erase_keys(col, 3, bufs(np.array([2, 4, 99], np.int64)))
+        wk.resolve_keys_device(5, d_keys, d_b)
+        wk.put_keys(col, 1, bufs(np.array([4], np.int64)), bufs(np.array([41], np.int32)))
+        wk.resolve_keys_device(5, d_keys, d_c)
+        wk.sync()
+        assert got(d_a) == [10, 20, 30, 40, 5] and got(d_b) == [10, 5, 30, 5, 5] and got(d_c) == [10, 5, 30, 41, 5]
+        assert ctx.key_space(col)[3] == 4                                                   # 99 was absent: nothing was claimed
+        # fr_ctx_erase_keys beside a worker in flight: per key the old row or miss_row
+        wk.resolve_keys_device(5, d_keys, d_a)
+        ctx.erase_keys(col, [1, 3])
+        wk.sync()
+        a = got(d_a)
+        assert a[0] in (10, 5) and a[2] in (30, 5) and [a[1], a[3], a[4]] == [5, 41, 5], a
+        wk.resolve_keys_device(5, d_keys, d_a)
+        wk.sync()
+        assert got(d_a) == [5, 5, 5, 41, 5]
+        if two_workers:                                                                     # an erase on A with a resolve in flight on B
+            other = fr.Worker(ctx, 64)
+            ctx.put_keys(col, [1, 2, 3], [10, 20, 30])
+            other.resolve_keys_device(5, d_keys, d_b)
+            wk.erase_keys(col, 2, bufs(np.array([2, 3], np.int64)))
+            other.sync()
+            wk.sync()
+            b = got(d_b)
+            assert b[1] in (20, 5) and b[2] in (30, 5) and [b[0], b[3], b[4]] == [10, 41, 5], b
+            other.resolve_keys_device(5, d_keys, d_b)
+            other.sync()
+            assert got(d_b) == [10, 5, 5, 41, 5]
+            other.close()
+        wk.close()
+    finally:
+        bufs.free()
+        ctx.close()
+
+
+# ---- 5. rebuild ----------------------------------------------------------------------------------------------------------------------------------------
+
+def check_rebuild(fr, device):
+    out = []
+    rng = np.random.default_rng(8500)
+    L = fr.lib()
+    INV, ST, OK = fr.FR_ERR_INVALID, fr.FR_ERR_STATE, fr.FR_OK
+    m, ctx = Q.context(fr, device, "narrow")
+    bufs = Bufs(fr, ctx)
+    try:
+        sp = K.Spaces(fr, ctx, m)
+        col, other_col, MAXK, miss = 1, 2, 16, 5
+        R_c = sp.ranges[col]
+        sp.set(other_col, fr.KEYS_MAPPED, 4, 32, -1)                                       # another MAPPED column: untouched by everything below
+        sp.put(other_col, random_keys(rng, 20), rows_not(rng, 20, sp.ranges[other_col], -1))
+        ctx.erase_keys(other_col, list(sp.map[other_col])[:3])
+        erase_ref(sp, other_col, list(sp.map[other_col])[:3])
+        other_before = (ctx.key_space_stats(other_col), exported(ctx, other_col), ctx.key_space(other_col))
+        sp.set(col, fr.KEYS_MAPPED, 0x77, MAXK, miss)
+        wk = fr.Worker(ctx, 2048)                                                           # created BEFORE every rebuild
+        ask = Asker(fr, ctx, wk, sp, col)
+        have = random_keys(rng, MAXK)
+        sp.put(col, have, rows_not(rng, MAXK, R_c, miss))
+        dropped, new_key = have[::2], random_keys(rng, 1, avoid=have)[0]
+        ctx.erase_keys(col, dropped)
+        erase_ref(sp, col, dropped)
+        assert R.status_of(fr, lambda: ctx.put_keys(col, [new_key], [1])) == fr.FR_ERR_INDEX_RANGE and "max_keys" in L.fr_last_error().decode()
+        wk.key_misses()
+        assert ask.check(have + [new_key], "before the rebuild") == 1 and wk.key_misses() == 1      # the erased keys are no misses yet
+        before = exported(ctx, col)
+        rebuild(sp, ctx, col, 0x99, MAXK)                                                   # same max_keys: compaction
+        assert ctx.key_space(col) == (fr.KEYS_MAPPED, 0x99, MAXK, MAXK // 2, miss)
+        assert exported(ctx, col) == before
+        assert_map(fr, sp, ctx, col, "compacted")                                           # (probe_sum: the replay of the live keys alone under the new seed)
+        assert ask.check(have + [new_key], "after the rebuild") == MAXK // 2 + 1 == wk.key_misses()   # a dropped key is now a miss
+        sp.put(col, [new_key], [1])                                                         # the refused key is accepted
+        ask.check(have + [new_key], "the refused key after the rebuild")
+        out.append(("compacted", ctx.key_space_stats(col), exported(ctx, col), ask.rows(have + [new_key]).tolist()))
+        # shrink to exactly live; to live - 1: refused, nothing changes
+        live = len(live_items(sp, col))
+        rebuild(sp, ctx, col, 0x99, live)
+        assert_map(fr, sp, ctx, col, "shrunk to live")
+        state = (ctx.key_space_stats(col), exported(ctx, col), ctx.key_space(col))
+        assert L.fr_ctx_rebuild_key_space(ctx._h, col, 5, live - 1) == INV and "live" in L.fr_last_error().decode()
+        assert L.fr_ctx_rebuild_key_space(ctx._h, col, 5, 0) == INV and L.fr_ctx_rebuild_key_space(ctx._h, col, 5, 2 ** 30 + 1) == INV
+        assert L.fr_ctx_rebuild_key_space(None, col, 5, 64) == INV and L.fr_ctx_rebuild_key_space(ctx._h, 3, 5, 64) == INV and L.fr_ctx_rebuild_key_space(ctx._h, -1, 5, 64) == INV
+        assert L.fr_ctx_rebuild_key_space(ctx._h, 0, 5, 64) == ST and "FR_KEYS_MAPPED" in L.fr_last_error().decode()      # a ROWS column
+        ctx.set_key_space(0, fr.KEYS_HASHED, 3)
+        assert L.fr_ctx_rebuild_key_space(ctx._h, 0, 5, 64) == ST                           # a HASHED column
+        ctx.set_key_space(0, fr.KEYS_ROWS)
+        idx = Q.valid_rows(rng, m, 64).view(np.int32)
+        d_idx, d_rec = bufs(idx), fr.DeviceBuffer(ctx, 64 * m.record_len * 4)
+        bufs.all.append(d_rec)
+        wk.gather_only(64, d_idx, None, d_rec)
+        assert L.fr_ctx_rebuild_key_space(ctx._h, col, 5, 64) == ST and "in flight" in L.fr_last_error().decode()
+        wk.sync()
+        assert (ctx.key_space_stats(col), exported(ctx, col), ctx.key_space(col)) == state, "a refused rebuild changed the map"
+        ask.check(have + [new_key], "after the refused rebuilds")
+        # the same max_keys under a new seed
+        rebuild(sp, ctx, col, 0xabcdef0123456789, live)
+        assert_map(fr, sp, ctx, col, "reseeded")
+        ask.check(have + [new_key], "reseeded")
+        assert (ctx.key_space_stats(other_col), exported(ctx, other_col), ctx.key_space(other_col)) == other_before, "another column changed"
+        # grow a full map of 8 to 1000 and on to 3000: the wrapped chain survives; then erase on the chain and compact
+        chain, chain_absent, others = chain_map(fr, sp, rng, col, 8, 0x1234 + 8, miss)
+        for bigger in (1000, 3000):
+            rebuild(sp, ctx, col, 0x1234 + 8, bigger)
+            assert_map(fr, sp, ctx, col, "grown to %d" % bigger)
+            wk.key_misses()
+            assert ask.check(chain + others + chain_absent, "grown to %d" % bigger) == len(chain_absent) == wk.key_misses()
+            fill = random_keys(rng, bigger - len(sp.map[col]), avoid=list(sp.map[col]) + chain_absent)
+            sp.put(col, fill, rows_not(rng, len(fill), R_c, miss))                          # filled to the last place again
+            assert_map(fr, sp, ctx, col, "filled to %d" % bigger)
+        ctx.erase_keys(col, [chain[0], chain[2]] + fill[::3])
+        erase_ref(sp, col, [chain[0], chain[2]] + fill[::3])
+        rebuild(sp, ctx, col, 3, 2500)
+        assert_map(fr, sp, ctx, col, "compacted from 3000 to 2500")
+        ask.check(chain + others + chain_absent + fill[:600], "compacted from 3000 to 2500")
+        out.append(("grown and compacted", ctx.key_space_stats(col), exported(ctx, col), ask.rows(chain + others + chain_absent + fill[:600]).tolist()))
+        assert (ctx.key_space_stats(other_col), exported(ctx, other_col), ctx.key_space(other_col)) == other_before, "another column changed"
+        wk.close()
+    finally:
+        bufs.free()
+        ctx.close()
+    c0 = fr.Context(Q.model(fr, "narrow"), device=device, shard_rank=0, n_shards=2)        # a sharded context
+    try:
+        assert L.fr_ctx_rebuild_key_space(c0._h, 0, 1, 8) == ST and "sharded" in L.fr_last_error().decode()
+    finally:
+        c0.close()
+    return out
+
+
+# ---- 6. more than one trip of the walk -----------------------------------------------------------------------------------------------------------------
+
+def check_big_walk(fr, device):
+    """A map of 2^21 slots (32 MiB): twice WALK_SPAN, so every workgroup of keymap_walk_kernel makes two trips.  Set comparisons in numpy."""
+    rng = np.random.default_rng(8600)
+    m, ctx = Q.context(fr, device, "narrow")
+    try:
+        col, seed, miss = 0, 0xb16, -1
+        slots = K.slots_of(BIG_MAX_KEYS)
+        assert slots == 2 * WALK_SPAN
+        ctx.set_key_space(col, fr.KEYS_MAPPED, seed, BIG_MAX_KEYS, miss)
+        keys = np.unique(rng.integers(K.I64_MIN, K.I64_MAX, size=BIG_KEYS, dtype=np.int64))
+        keys = keys[keys != -1]
+        rng.shuffle(keys)
+        rows = rng.integers(0, 50, size=keys.size).astype(np.int32)
+        for part in np.array_split(np.arange(keys.size), 3):
+            ctx.put_keys(col, keys[part], rows[part])
+        dead = keys[::5]
+        ctx.erase_keys(col, np.concatenate([dead, rng.integers(1, 2 ** 40, size=1000)]))
+        alive = np.ones(keys.size, bool)
+        alive[::5] = False
+        order = np.argsort(keys[alive])
+        want_k, want_r = keys[alive][order], rows[alive][order]
+        assert ctx.key_space_stats(col) == (slots, keys.size, int(alive.sum()), probe_sum(keys, seed, slots))
+        k, r = ctx.export_keys(col)
+        o = np.argsort(k)
+        assert np.array_equal(k[o], want_k) and np.array_equal(r[o], want_r)
+        ctx.rebuild_key_space(col, 0xb17, 2 * BIG_MAX_KEYS)
+        assert ctx.key_space_stats(col) == (2 * slots, want_k.size, want_k.size, probe_sum(want_k, 0xb17, 2 * slots))
+        assert ctx.key_space(col) == (fr.KEYS_MAPPED, 0xb17, 2 * BIG_MAX_KEYS, want_k.size, miss)
+        k, r = ctx.export_keys(col)
+        o = np.argsort(k)
+        assert np.array_equal(k[o], want_k) and np.array_equal(r[o], want_r)
+        wk = fr.Worker(ctx, 4096)
+        probe = np.full((4096, 3), -1, np.int64)
+        probe[:, col] = keys[:4096]
+        want = np.where(alive[:4096], rows[:4096], miss).astype(np.int32)
+        assert np.array_equal(K.run_resolve(fr, ctx, wk, probe)[:, col], want)
+        assert wk.key_misses() == int((~alive[:4096]).sum())
+        wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- 7. through the paths --------------------------------------------------------------------------------------------------------------------------------
+
+def check_paths(fr, device, kind, pooled):
+    """submit_keyed before a rebuild of every map and after it: the same score bits; after erasing keys of maps whose miss_row is a row (or, in a bag,
+    -1), the scores of submit on the dict's rows."""
+    rng = np.random.default_rng(8700 + pooled)
+    m, ctx = Q.context(fr, device, kind)
+    try:
+        C, B = m.idx_cols, 301
+        sp = K.Spaces(fr, ctx, m)
+        sp.cycle(rng, miss_kinds=("row", -1) if pooled else ("row",))
+        hots = np.array([1, 2, 4, 3], np.int32)[np.arange(C) % 4] if pooled else None
+        if pooled:
+            ctx.set_pooling(hots)
+        pools = K.Pools(rng, sp, valid_only=True)
+        wk = fr.Worker(ctx, 512)
+        wcol = K.word_cols(C, 0, hots=hots)
+        keys, rows, _ = pools.draw(rng, B, wcol)
+        dense = rng.standard_normal((B, m.dense_len)).astype(np.float32) if m.dense_len else None
+        wts = rng.standard_normal(keys.shape).astype(np.float32) if pooled else None
+        keyed = lambda: (wk.infer_pooled_keyed(keys, dense, wts) if pooled else wk.infer_keyed(keys, dense)).view(np.uint32).copy()
+        plain = lambda r: (wk.infer_pooled(r, dense, weights=wts) if pooled else wk.infer(r, dense)).view(np.uint32).copy()
+        first = keyed()
+        assert np.array_equal(first, plain(rows)) and len(set(first.tolist())) > B // 4
+        mapped = [c for c in range(C) if sp.mode[c] == fr.KEYS_MAPPED]
+        assert mapped
+        for c in mapped:
+            rebuild(sp, ctx, c, 0x5eed + c, 100)
+        assert np.array_equal(keyed(), first), "the scores changed with a rebuild"
+        for c in mapped:                                                                     # erase every other key of every map
+            gone = list(sp.map[c])[::2]
+            ctx.erase_keys(c, gone + [12345678901])
+            erase_ref(sp, c, gone)
+        after_rows = np.array([[sp.row(c, k)[0] for k in keys[:, w]] for w, c in enumerate(wcol)], np.int64).T.astype(np.int32)
+        assert (after_rows != rows).any()
+        erased = keyed()
+        assert np.array_equal(erased, plain(np.ascontiguousarray(after_rows))), "scores after the erase differ from submit on the dict's rows"
+        for c in mapped:
+            rebuild(sp, ctx, c, 0xfeed + c, 48)
+        assert np.array_equal(keyed(), erased), "the scores changed with a compaction"
+        wk.close()
+    finally:
+        ctx.close()
+
+
+# ---- 9. lifetime -------------------------------------------------------------------------------------------------------------------------------------------
+
+def lifetime_cycle(fr, m, device, rng, live_bytes=None):
+    """Rebuilds to larger / smaller / equal, exports and ctx-form erases; live_bytes (a function -> the library's tally): a same-size rebuild leaves
+    the tally where it was.  Everything is released with close()."""
+    import lifetime
+    ctx = lifetime.make_ctx(fr, m, device)
+    wk = fr.Worker(ctx, lifetime.B)
+    ctx.set_key_space(0, fr.KEYS_MAPPED, 9, 300, 0)
+    keys = rng.integers(1, 2 ** 50, size=200)
+    ctx.put_keys(0, keys, 1 + rng.integers(0, 5, size=200).astype(np.int32))
+    ctx.erase_keys(0, keys[:50])
+    for max_keys in (4000, 150, 150, 300):
+        tally = live_bytes() if live_bytes else None
+        n_before = len(ctx.export_keys(0)[0])
+        same = max_keys == ctx.key_space(0)[2]
+        ctx.rebuild_key_space(0, int(rng.integers(0, 2 ** 63)), max_keys)
+        if same and live_bytes:
+            assert live_bytes() == tally, ("a same-size rebuild changed the tally of live bytes", live_bytes(), tally)
+        assert len(ctx.export_keys(0)[0]) == n_before == ctx.key_space(0)[3]
+        ctx.erase_keys(0, keys[50 + max_keys % 7::40])
+    assert ctx.key_space_stats(0)[2] == len(ctx.export_keys(0)[0]) > 0
+    d, o = fr.DeviceBuffer.from_numpy(ctx, np.zeros(lifetime.B * m.idx_cols, np.int64)), fr.DeviceBuffer(ctx, lifetime.B * m.idx_cols * 4)
+    wk.resolve_keys_device(lifetime.B, d, o)
+    wk.sync()
+    d.free()
+    o.free()
+    wk.close()
+    ctx.close()
+
+
+# ---- 10. the companion code object ----------------------------------------------------------------------------------------------------------------------
+
+def check_companion(fr):
+    """libfleetrec_keymaint.so: exports only its fr_* launchers, does not import getenv, is named by libfleetrec.so with $ORIGIN; its kernels are the
+    keymap_ ones, spill no register and have no private segment (that part only when llvm-readelf is there).  libfleetrec_keys.so is what it was."""
+    import importlib.util
+    assert os.path.exists(KEYMAINT_LIB), "the key-map maintenance companion code object has not been built"
+    und = subprocess.check_output(["nm", "-D", "--undefined-only", KEYMAINT_LIB]).decode()
+    assert "getenv" not in und, "libfleetrec_keymaint.so imports getenv"
+    assert not [l for l in und.splitlines() if l.split()[-1].startswith(("fr_", "frc_"))], "libfleetrec_keymaint.so calls into the library"
+    out = subprocess.check_output(["nm", "-D", "--defined-only", KEYMAINT_LIB]).decode()
+    exported_syms = [l.split()[-1] for l in out.splitlines() if " T " in l]
+    assert sorted(exported_syms) == ["fr_keymap_erase_launch", "fr_keymap_walk_launch"], exported_syms
+    need = subprocess.check_output(["readelf", "-d", fr.LIB_PATH]).decode()
+    assert "libfleetrec_keymaint.so" in need and "$ORIGIN" in need, "libfleetrec.so does not link the companion through $ORIGIN"
+    out = subprocess.check_output(["nm", "-D", "--defined-only", K.KEYS_LIB]).decode()
+    assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == ["fr_key_fill_launch", "fr_key_put_launch", "fr_key_resolve_launch"]
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
+        import pytest
+        pytest.skip("llvm-readelf not available: the kernel list and the register / scratch checks of libfleetrec_keymaint.so did not run")
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    recs = kr.kernel_records(KEYMAINT_LIB)
+    names = [r["name"] for r in recs]
+    count = {k: sum(k in n for n in names) for k in ("keymap_erase_kernel", "keymap_walk_kernel")}
+    assert count == {"keymap_erase_kernel": 1, "keymap_walk_kernel": 3} and len(names) == 4, names
+    for r in recs:
+        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
+        assert r["vgpr_count"] <= 64, r                      # eight waves per SIMD, as the sibling kernels
+    assert not [r["name"] for r in kr.kernel_records(fr.LIB_PATH) if "keymap_" in r["name"]], "a keymap_ kernel inside libfleetrec.so"
+    assert not [r["name"] for r in kr.kernel_records(K.KEYS_LIB) if "keymap_" in r["name"]], "a keymap_ kernel inside libfleetrec_keys.so"
