@@ -96,6 +96,7 @@ ABI_SYMBOLS = [
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
     "fr_worker_submit_keyed", "fr_worker_key_misses",
     "fr_worker_erase_keys", "fr_ctx_erase_keys", "fr_ctx_key_space_stats", "fr_ctx_export_keys", "fr_ctx_rebuild_key_space",
+    "fr_ctx_set_row_pool", "fr_ctx_row_pool", "fr_worker_admit_keys", "fr_ctx_admit_keys",
     "fr_ctx_set_epilogue", "fr_ctx_epilogue",
 ]
 
@@ -114,6 +115,7 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
                    "fr_worker_submit_keyed", "fr_worker_key_misses",
                    "fr_worker_erase_keys", "fr_ctx_erase_keys", "fr_ctx_key_space_stats", "fr_ctx_export_keys", "fr_ctx_rebuild_key_space",
+                   "fr_ctx_set_row_pool", "fr_ctx_row_pool", "fr_worker_admit_keys", "fr_ctx_admit_keys",
                    "fr_ctx_set_epilogue", "fr_ctx_epilogue")
 
 
@@ -211,6 +213,9 @@ def lib():
         "fr_ctx_key_space_stats": (i32, [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "fr_ctx_export_keys": (i32, [vp, i32, i64, vp, vp, ctypes.POINTER(i64)]),
         "fr_ctx_rebuild_key_space": (i32, [vp, i32, ctypes.c_uint64, i64]),
+        "fr_ctx_set_row_pool": (i32, [vp, i32, ctypes.c_int32, ctypes.c_int32]),
+        "fr_ctx_row_pool": (i32, [vp, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)]),
+        "fr_worker_admit_keys": (i32, [vp, i32, i32, vp, vp]), "fr_ctx_admit_keys": (i32, [vp, i32, i32, vp, vp]),
         "fr_ctx_set_epilogue": (i32, [vp, i32, vp, sz, i32]), "fr_ctx_epilogue": (i32, [vp, i32, vp, sz, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
@@ -776,6 +781,30 @@ class Context:
         """fr_ctx_rebuild_key_space: replace the map of MAPPED column col by one for max_keys keys under `seed` that holds exactly its live pairs
         (dead slots are dropped); on the device, synchronous; no worker of the context may have work in flight."""
         _check(lib().fr_ctx_rebuild_key_space(self._h, int(col), int(seed) & (2 ** 64 - 1), int(max_keys)))
+
+    def set_row_pool(self, col, first_row, n_rows):
+        """fr_ctx_set_row_pool: the rows [first_row, first_row + n_rows) of MAPPED column col become its row pool, which admit_keys hands out and
+        erase_keys takes back; the free set is derived from the map as it stands (a pool row held by a live key is taken).  n_rows = 0 drops the pool."""
+        _check(lib().fr_ctx_set_row_pool(self._h, int(col), int(first_row), int(n_rows)))
+
+    def row_pool(self, col):
+        """-> (first_row, n_rows, free_rows) of the row pool of index column col; n_rows = 0: no pool (fr_ctx_row_pool; synchronises the device)."""
+        first, n, free = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        _check(lib().fr_ctx_row_pool(self._h, int(col), ctypes.byref(first), ctypes.byref(n), ctypes.byref(free)))
+        return first.value, n.value, free.value
+
+    def admit_keys(self, col, keys):
+        """fr_ctx_admit_keys: -> int32 rows, one per key (int64) of MAPPED column col: a live key's own row, for an absent or dead key a free row of
+        the column's pool, now its row.  Synchronous, legal beside workers in flight.  A key that cannot be applied (-1, no free row, a new key for a
+        full map) raises FleetRecError(FR_ERR_INDEX_RANGE) after every other key was applied; the rows are then in the exception's `rows`."""
+        k = np.ascontiguousarray(keys, dtype=np.int64).reshape(-1)
+        rows = np.empty(k.size, np.int32)
+        try:
+            _check(lib().fr_ctx_admit_keys(self._h, int(col), int(k.size), k.ctypes.data, rows.ctypes.data))
+        except FleetRecError as e:
+            e.rows = rows
+            raise
+        return rows
 
     def synchronize(self):
         _check(lib().fr_device_synchronize(self._h))
@@ -1357,6 +1386,12 @@ class Worker:
         """fr_worker_erase_keys: n keys from device memory (d_keys int64); the row of every present one becomes the column's miss_row, asynchronous on
         the worker's stream; a key of -1 is reported by sync()."""
         _check(lib().fr_worker_erase_keys(self._h, int(col), int(n), self._ptr(d_keys)))
+
+    def admit_keys(self, col, n, d_keys, d_rows_out):
+        """fr_worker_admit_keys: n keys from device memory (d_keys int64) -> d_rows_out int32: a live key's own row, for an absent or dead key a free
+        row of the column's pool, now its row; asynchronous on the worker's stream.  A key that cannot be applied (-1, no free row, a new key for a
+        full map) is reported by sync(); d_rows_out is what a following update_rows takes as its row ids."""
+        _check(lib().fr_worker_admit_keys(self._h, int(col), int(n), self._ptr(d_keys), self._ptr(d_rows_out)))
 
     def resolve_keys_device(self, n_rows, d_keys, d_idx_out, rows_kind=KEY_ROWS_FULL, pooled=False):
         """fr_worker_resolve_keys_device: d_keys int64 [n_rows][W] -> d_idx_out int32 [n_rows][W]; W follows rows_kind (KEY_ROWS_FULL: the index or

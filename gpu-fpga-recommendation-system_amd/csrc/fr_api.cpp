@@ -3169,6 +3169,17 @@ static FrKeyPutArgs key_put_args(fr_ctx *c, int col, int n, const int64_t *keys,
 // what fr_worker_sync (or fr_ctx_put_keys itself) says about the bits of a status word; bit 0 is the lookups'
 static int index_range_fail(int bits) {
     const char *lookup = (bits & 1) ? "a lookup index was outside its table (row 0 was read instead)" : "";
+    if (bits & FR_KEYS_ERR_ADMIT) {   // an admit marks its bits; whatever else the word holds is named by the rest of the word, without the admit's
+        char rest[640] = "";
+        const int other = bits & ~(FR_KEYS_ERR_ADMIT | FR_KEYS_ERR_NO_FREE_ROW | FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_FULL);
+        if (other) {
+            (void)index_range_fail(other);
+            snprintf(rest, sizeof rest, " %s", fr_last_error());
+        }
+        FR_FAIL(FR_ERR_INDEX_RANGE, "a key admit was not applied (every other key was):%s%s%s%s", (bits & FR_KEYS_ERR_EMPTY_KEY) ? " a key of -1 (FR_KEY_EMPTY);" : "",
+                (bits & FR_KEYS_ERR_NO_FREE_ROW) ? " no free row: the column's row pool is exhausted (FR_KEYS_ERR_NO_FREE_ROW);" : "",
+                (bits & FR_KEYS_ERR_FULL) ? " a new key for a map that holds max_keys keys (the row went back to the pool);" : "", rest);
+    }
     const int put = bits & (FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_ROW | FR_KEYS_ERR_FULL);
     const char *erase = (bits & FR_KEYS_ERR_ERASE_EMPTY) ? "a key erase was not applied (every other key was): a key of -1 (FR_KEY_EMPTY);" : "";
     if (!put) FR_FAIL(FR_ERR_INDEX_RANGE, "%s%s%s", lookup, (bits & 1) && *erase ? "; " : "", erase);
@@ -3247,6 +3258,24 @@ static FrKeyEraseArgs key_erase_args(fr_ctx *c, int col, int n, const int64_t *k
     return a;
 }
 
+// the pool of column col as the kernels and the twins take it (n_rows == 0: the column has none)
+static FrKeyPool key_pool_of(const fr_ctx *c, int col) {
+    const fr_ctx::KeySpace &k = c->key_spaces[(size_t)col];
+    return FrKeyPool{k.pool_bits.p, k.pool_free.p, k.pool_first, k.pool_rows};
+}
+
+// An erase on a column with a pool gives the rows back (keyadmit_release_kernel of libfleetrec_admit.so; frc_release_keys); without one it is
+// keymap_erase_kernel (frc_erase_keys), as ever.  -> the twin's bits on the CPU back-end, the launch's hipError_t value on the device.
+static int key_erase_run(fr_ctx *c, int col, int n, const int64_t *keys, int *err, hipStream_t s) {
+    const FrKeyPool pool = key_pool_of(c, col);
+    if (pool.n_rows > 0) {
+        const FrKeyReleaseArgs r{c->h_key_cols[(size_t)col], pool, n, keys, err};
+        return c->cpu ? frc_release_keys(r) : fr_keyadmit_release_launch(&r, (void *)s);
+    }
+    const FrKeyEraseArgs a = key_erase_args(c, col, n, keys, err);
+    return c->cpu ? frc_erase_keys(a) : fr_keymap_erase_launch(&a, (void *)s);
+}
+
 extern "C" int fr_worker_erase_keys(fr_worker *w, int col, int n, const int64_t *d_keys) {
     if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
     fr_ctx *c = w->ctx;
@@ -3259,14 +3288,13 @@ extern "C" int fr_worker_erase_keys(fr_worker *w, int col, int n, const int64_t 
         FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then erase");
     if (c->cpu) {   // computed before the call returns, one writer at a time; a -1 key waits in c_err for fr_worker_sync
         std::lock_guard<std::mutex> lk(c->lp_mutex);
-        const int bad = frc_erase_keys(key_erase_args(c, col, n, d_keys, nullptr));
+        const int bad = key_erase_run(c, col, n, d_keys, nullptr, nullptr);
         if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
         return FR_OK;
     }
     FR_SET_DEVICE(c);
     FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the erase: whatever they read was resolved against the old map
-    const FrKeyEraseArgs a = key_erase_args(c, col, n, d_keys, w->d_err);
-    const int e = fr_keymap_erase_launch(&a, (void *)w->stream);
+    const int e = key_erase_run(c, col, n, d_keys, w->d_err, w->stream);
     if (e) FR_FAIL(FR_ERR_HIP, "the key erase launch failed: %s", hipGetErrorString((hipError_t)e));
     w->in_flight = true;
     return FR_OK;
@@ -3279,7 +3307,7 @@ extern "C" int fr_ctx_erase_keys(fr_ctx *ctx, int col, int n, const int64_t *h_k
     if ((uintptr_t)h_keys % 8) FR_FAIL(FR_ERR_INVALID, "fr_ctx_erase_keys: h_keys must be 8-byte aligned");
     std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_put_keys's
     if (ctx->cpu) {
-        const int bad = frc_erase_keys(key_erase_args(ctx, col, n, h_keys, nullptr));
+        const int bad = key_erase_run(ctx, col, n, h_keys, nullptr, nullptr);
         return bad ? index_range_fail(bad) : FR_OK;
     }
     FR_SET_DEVICE(ctx);
@@ -3290,8 +3318,7 @@ extern "C" int fr_ctx_erase_keys(fr_ctx *ctx, int col, int n, const int64_t *h_k
     }
     FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
     FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
-    const FrKeyEraseArgs a = key_erase_args(ctx, col, n, ctx->d_kp_keys, ctx->d_up_err);
-    const int e = fr_keymap_erase_launch(&a, (void *)ctx->setup_stream);
+    const int e = key_erase_run(ctx, col, n, ctx->d_kp_keys, ctx->d_up_err, ctx->setup_stream);
     FR_HIP(hipStreamSynchronize(ctx->setup_stream));
     if (e) FR_FAIL(FR_ERR_HIP, "the key erase launch failed: %s", hipGetErrorString((hipError_t)e));
     const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
@@ -3415,8 +3442,162 @@ extern "C" int fr_ctx_rebuild_key_space(fr_ctx *ctx, int col, uint64_t seed, int
     const uint32_t count = (uint32_t)live;
     if (ctx->cpu) ctx->d_key_counts[col] = count;
     else FR_HIP(hipMemcpy(ctx->d_key_counts + col, &count, sizeof(count), hipMemcpyHostToDevice));
+    next.pool_first = old.pool_first, next.pool_rows = old.pool_rows;   // the row pool goes with the live keys: they keep their rows
+    next.pool_bits.swap(old.pool_bits), next.pool_free.swap(old.pool_free);
     std::swap(old, next);   // (no worker has work in flight: the old map is released with `next`)
     return key_cols_upload(ctx);
+}
+
+// ---- row pools: admitting ids (fleetrec_serving.h) --------------------------------------------------------------------------------------------------
+// The kernels are the sixth companion code object's (fr_keyadmit.hip -> libfleetrec_admit.so); the CPU twins are frc_admit_keys / frc_release_keys /
+// frc_mark_pool.  The pool's bitmap and counter belong to the column's KeySpace: a rebuild hands them on, fr_ctx_set_key_space drops them.
+extern "C" int fr_ctx_set_row_pool(fr_ctx *ctx, int col, int32_t first_row, int32_t n_rows) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_col_check(ctx, col, "fr_ctx_set_row_pool"));
+    if (n_rows < 0) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_row_pool: n_rows = %d", n_rows);
+    const uint32_t range = key_col_range(ctx, col);
+    if (n_rows > 0 && (first_row < 0 || (int64_t)first_row + n_rows > (int64_t)range))
+        FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_row_pool: rows [%d, %lld) are not inside the %u rows of column %d", first_row, (long long)first_row + n_rows, range, col);
+    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_row_pool: keyed lookups are not available on a sharded context (%d shards)", ctx->n_shards);
+    FR_TRY(pooling_busy(ctx, "fr_ctx_set_row_pool"));
+    std::lock_guard<std::mutex> lk(ctx->key_mutex);
+    FR_TRY(key_map_ready(ctx, col, "fr_ctx_set_row_pool"));
+    fr_ctx::KeySpace &k = ctx->key_spaces[(size_t)col];
+    if (n_rows == 0) {   // drop the pool
+        k.pool_first = k.pool_rows = 0;
+        k.pool_bits.reset(), k.pool_free.reset();
+        return FR_OK;
+    }
+    if (k.miss_row >= first_row && k.miss_row - first_row < n_rows)
+        FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_row_pool: rows [%d, %d) contain the column's miss_row %d", first_row, first_row + n_rows, k.miss_row);
+    // the free set is derived from the map as it stands: whatever fails from here on, the column keeps the pool it had
+    FrBuf<uint32_t> bits;
+    FrBuf<int32_t> free_rows;
+    const uint32_t words = fr_key_pool_words(n_rows), pad = fr_key_pool_pad(n_rows);
+    FR_TRY(bits.alloc(fr_mem_kind(ctx, FrMem::DEVICE), words, "row-pool bitmap"));
+    FR_TRY(free_rows.alloc(fr_mem_kind(ctx, FrMem::DEVICE), 1, "row-pool counter"));
+    FrKeyMarkArgs m{ctx->h_key_cols[(size_t)col], FrKeyPool{bits.p, free_rows.p, first_row, n_rows}, 0};
+    if (ctx->cpu) {
+        memset(bits.p, 0, words * sizeof(uint32_t));
+        bits[words - 1] = pad, *free_rows = n_rows;
+        frc_mark_pool(m);
+    } else {
+        hipStream_t s = ctx->setup_stream;
+        hipError_t he = hipMemsetAsync(bits.p, 0, words * sizeof(uint32_t), s);
+        if (he == hipSuccess && pad) he = hipMemcpyAsync(bits.p + words - 1, &pad, sizeof(pad), hipMemcpyHostToDevice, s);
+        if (he == hipSuccess) he = hipMemcpyAsync(free_rows.p, &n_rows, sizeof(n_rows), hipMemcpyHostToDevice, s);
+        m.max_blocks = 4 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
+        const int e = he == hipSuccess ? fr_keyadmit_mark_launch(&m, (void *)s) : (int)he;
+        const hipError_t se = hipStreamSynchronize(s);   // (before `bits`, `pad` and `n_rows` leave)
+        if (e) FR_FAIL(FR_ERR_HIP, "the row pool's mark launch failed: %s", hipGetErrorString((hipError_t)e));
+        FR_HIP(se);
+    }
+    k.pool_first = first_row, k.pool_rows = n_rows;
+    k.pool_bits.swap(bits), k.pool_free.swap(free_rows);   // (no worker has work in flight: the old bitmap is released with `bits`)
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_row_pool(fr_ctx *ctx, int col, int32_t *first_row, int32_t *n_rows, int64_t *free_rows) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_col_check(ctx, col, "fr_ctx_row_pool"));
+    const fr_ctx::KeySpace none{};
+    const fr_ctx::KeySpace &k = ctx->key_spaces.empty() ? none : ctx->key_spaces[(size_t)col];
+    int32_t n = 0;
+    if (k.pool_rows > 0) {
+        if (ctx->cpu) {
+            n = __atomic_load_n(k.pool_free.p, __ATOMIC_ACQUIRE);
+        } else {
+            FR_SET_DEVICE(ctx);
+            FR_HIP(hipDeviceSynchronize());
+            FR_HIP(hipMemcpy(&n, k.pool_free.p, sizeof(n), hipMemcpyDeviceToHost));
+        }
+    }
+    if (first_row) *first_row = k.pool_first;
+    if (n_rows) *n_rows = k.pool_rows;
+    if (free_rows) *free_rows = (int64_t)n;
+    return FR_OK;
+}
+
+static int key_admit_check(fr_ctx *c, int col, int n, const void *keys, const void *rows, const char *who) {
+    FR_TRY(key_put_check(c, col, n, keys, rows, who));
+    if (c->key_spaces[(size_t)col].pool_rows <= 0) FR_FAIL(FR_ERR_STATE, "%s: column %d has no row pool: call fr_ctx_set_row_pool(ctx, %d, first_row, n_rows) first", who, col, col);
+    return FR_OK;
+}
+
+static FrKeyAdmitArgs key_admit_args(fr_ctx *c, int col, int n, const int64_t *keys, int32_t *rows, int *err) {
+    FrKeyAdmitArgs a{};
+    a.col = c->h_key_cols[(size_t)col], a.pool = key_pool_of(c, col), a.n_keys = c->d_key_counts + col, a.max_keys = (uint32_t)c->key_spaces[(size_t)col].max_keys;
+    a.n = n, a.keys = keys, a.rows_out = rows, a.err_flag = err;
+    return a;
+}
+
+// The launches of one admit on stream s: per piece of at most 2^20 keys the piece's own table is filled (key_fill_kernel), keyadmit_admit_kernel elects
+// one occurrence of every key and admits it, keyadmit_settle_kernel hands its row to the others.  A key listed in two pieces is live by the second.
+static int key_admit_enqueue(fr_ctx *c, int col, int n, const int64_t *keys, int32_t *rows, int *err, FrBuf<FrKeySlot> &tab, hipStream_t s) {
+    constexpr int PIECE = 1 << 20;
+    FR_TRY(tab.grow(FrMem::DEVICE, (size_t)fr_key_slots((uint64_t)(n < PIECE ? n : PIECE)), "key-admit table"));
+    for (int at = 0; at < n; at += PIECE) {
+        const int m = n - at < PIECE ? n - at : PIECE;
+        const uint64_t slots = fr_key_slots((uint64_t)m);
+        const FrKeyFillArgs f{tab.p, slots, FR_KEYS_NO_ROW};
+        int e = fr_key_fill_launch(&f, (void *)s);
+        FrKeyAdmitArgs a = key_admit_args(c, col, m, keys + at, rows + at, err);
+        a.tab = tab.p, a.tab_mask = (uint32_t)(slots - 1);
+        if (!e) e = fr_keyadmit_admit_launch(&a, (void *)s);
+        if (!e) e = fr_keyadmit_settle_launch(&a, (void *)s);
+        if (e) FR_FAIL(FR_ERR_HIP, "the key admit launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
+    return FR_OK;
+}
+
+extern "C" int fr_worker_admit_keys(fr_worker *w, int col, int n, const int64_t *d_keys, int32_t *d_rows_out) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    fr_ctx *c = w->ctx;
+    FR_TRY(key_admit_check(c, col, n, d_keys, d_rows_out, "fr_worker_admit_keys"));
+    if (n == 0) return FR_OK;
+    if ((uintptr_t)d_keys % 8 || (uintptr_t)d_rows_out % 4) FR_FAIL(FR_ERR_INVALID, "fr_worker_admit_keys: d_keys must be 8-byte aligned, d_rows_out 4-byte aligned");
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then admit");
+    if (c->cpu) {   // computed before the call returns, one writer at a time; what was not applied waits in c_err for fr_worker_sync
+        std::lock_guard<std::mutex> lk(c->lp_mutex);
+        const int bad = frc_admit_keys(key_admit_args(c, col, n, d_keys, d_rows_out, nullptr));
+        if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
+        return FR_OK;
+    }
+    FR_SET_DEVICE(c);
+    FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the admit: whatever they read was resolved against the old map
+    FR_TRY(key_admit_enqueue(c, col, n, d_keys, d_rows_out, w->d_err, w->d_admit_tab, w->stream));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_admit_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys, int32_t *h_rows_out) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(key_admit_check(ctx, col, n, h_keys, h_rows_out, "fr_ctx_admit_keys"));
+    if (n == 0) return FR_OK;
+    if ((uintptr_t)h_keys % 8 || (uintptr_t)h_rows_out % 4) FR_FAIL(FR_ERR_INVALID, "fr_ctx_admit_keys: h_keys must be 8-byte aligned, h_rows_out 4-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_put_keys's
+    if (ctx->cpu) {
+        const int bad = frc_admit_keys(key_admit_args(ctx, col, n, h_keys, h_rows_out, nullptr));
+        return bad ? index_range_fail(bad) : FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    if (!ctx->h_up_err) {
+        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
+        *ctx->h_up_err = 0;
+        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
+    }
+    FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
+    FR_TRY(ctx->d_kp_rows.grow(FrMem::DEVICE, (size_t)n, "key-put rows"));
+    FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
+    const int rc = key_admit_enqueue(ctx, col, n, ctx->d_kp_keys, ctx->d_kp_rows, ctx->d_up_err, ctx->d_ka_tab, ctx->setup_stream);
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    if (rc) return rc;
+    FR_HIP(hipMemcpy(h_rows_out, ctx->d_kp_rows, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
+    return bad ? index_range_fail(bad) : FR_OK;
 }
 
 // The word -> column tables of the six forms ([rows_kind][pooled]) for the pooling and the split as they stand, made again when either has changed

@@ -681,3 +681,93 @@ void frc_walk_keys(const FrKeyWalkArgs &a) {
     if (a.sink == FR_KEYWALK_COUNT) a.counts[0] += occupied, a.counts[1] += live, a.counts[2] += psum;
     else a.counts[0] += live;
 }
+
+// ---- row pools: the CPU twins of keyadmit_admit_kernel + keyadmit_settle_kernel, keyadmit_release_kernel and keyadmit_mark_kernel (fr_keyadmit.hip) ----
+// Sequential, ONE writer at a time (the callers hold fr_ctx::lp_mutex): a key listed twice finds itself live the second time, so there is nothing to
+// elect and nothing to give back but the row of a key the full map refused.  The LOWEST free row is taken first.
+static int32_t frc_pool_take(const FrKeyPool &p) {
+    if (*p.free_rows <= 0) return -1;
+    const uint32_t words = fr_key_pool_words(p.n_rows);
+    for (uint32_t w = 0; w < words; w++) {
+        if (p.bits[w] == ~0u) continue;
+        const uint32_t b = (uint32_t)__builtin_ctz(~p.bits[w]);
+        p.bits[w] |= 1u << b;
+        --*p.free_rows;
+        return p.first_row + (int32_t)(w * 32u + b);
+    }
+    return -1;   // (a counter that disagrees with its bitmap)
+}
+
+static void frc_pool_give(const FrKeyPool &p, int32_t row) {
+    const uint32_t o = (uint32_t)(row - p.first_row), bit = 1u << (o & 31u);
+    if (p.bits[o >> 5] & bit) p.bits[o >> 5] &= ~bit, ++*p.free_rows;
+}
+
+int frc_admit_keys(const FrKeyAdmitArgs &a) {
+    int bad = 0;
+    for (int i = 0; i < a.n; i++) {
+        const int64_t k = a.keys[i];
+        if (k == FR_KEYS_EMPTY_KEY) {
+            bad |= FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_ADMIT;
+            a.rows_out[i] = -1;
+            continue;
+        }
+        uint64_t h = fr_key_home(a.col, k);
+        bool found = false, empty = false;
+        for (uint64_t left = (uint64_t)a.col.mask + 1; left; left--) {
+            const int64_t cur = __atomic_load_n(&a.col.slots[h].key, __ATOMIC_RELAXED);
+            found = cur == k, empty = cur == FR_KEYS_EMPTY_KEY;
+            if (found || empty) break;
+            h = (h + 1) & (uint64_t)a.col.mask;
+        }
+        FrKeySlot *s = a.col.slots + h;
+        if (found && s->row != a.col.miss_row) {   // live: nothing is written
+            a.rows_out[i] = s->row;
+            continue;
+        }
+        a.rows_out[i] = FR_KEYS_NO_ROW;
+        const int32_t r = frc_pool_take(a.pool);
+        if (r < 0) {
+            bad |= FR_KEYS_ERR_NO_FREE_ROW | FR_KEYS_ERR_ADMIT;
+            continue;
+        }
+        if (!found) {
+            if (!empty || *a.n_keys >= a.max_keys) {   // the map is full: nothing is claimed, the row goes back
+                frc_pool_give(a.pool, r);
+                bad |= FR_KEYS_ERR_FULL | FR_KEYS_ERR_ADMIT;
+                continue;
+            }
+            ++*a.n_keys;
+            __atomic_store_n(&s->key, k, __ATOMIC_RELEASE);   // the key first (the slot still holds miss_row) ...
+        }
+        __atomic_store_n(&s->row, r, __ATOMIC_RELEASE);       // ... the row second
+        a.rows_out[i] = r;
+    }
+    return bad;
+}
+
+int frc_release_keys(const FrKeyReleaseArgs &a) {
+    int bad = 0;
+    for (int i = 0; i < a.n; i++) {
+        const int64_t k = a.keys[i];
+        if (k == FR_KEYS_EMPTY_KEY) {
+            bad |= FR_KEYS_ERR_ERASE_EMPTY;
+            continue;
+        }
+        const int64_t at = fr_key_find(a.col, k);
+        if (at < 0) continue;
+        const int32_t was = __atomic_exchange_n(&a.col.slots[at].row, a.col.miss_row, __ATOMIC_ACQ_REL);
+        if (was != a.col.miss_row && fr_key_pool_holds(a.pool, was)) frc_pool_give(a.pool, was);
+    }
+    return bad;
+}
+
+void frc_mark_pool(const FrKeyMarkArgs &a) {
+    const uint64_t n = (uint64_t)a.col.mask + 1;
+    for (uint64_t i = 0; i < n; i++) {
+        const FrKeySlot s = fr_key_load_slot(a.col.slots + i);
+        if (!fr_key_slot_live(s, a.col.miss_row) || !fr_key_pool_holds(a.pool, s.row)) continue;
+        const uint32_t o = (uint32_t)(s.row - a.pool.first_row), bit = 1u << (o & 31u);
+        if (!(a.pool.bits[o >> 5] & bit)) a.pool.bits[o >> 5] |= bit, --*a.pool.free_rows;
+    }
+}

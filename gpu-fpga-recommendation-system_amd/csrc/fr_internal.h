@@ -375,6 +375,38 @@ struct FrKeyWalkArgs {
 extern "C" int fr_keymap_erase_launch(const FrKeyEraseArgs *args, void *stream);
 extern "C" int fr_keymap_walk_launch(const FrKeyWalkArgs *args, void *stream);
 
+// ---- row pools: admitting ids (fr_keyadmit.hip -> libfleetrec_admit.so, the sixth companion code object; fr_cpu.cpp has the twins; fr_keys.h: FrKeyPool) ----
+constexpr int FR_KEYADMIT_PER_THREAD = 4;   // slots a thread of keyadmit_mark_kernel loads per trip before its first compare
+struct FrKeyAdmitArgs {
+    FrKeyCol col;                // a MAPPED column with a pool
+    FrKeyPool pool;
+    uint32_t *n_keys;            // the column's key count
+    uint32_t max_keys;
+    int n;
+    const int64_t *keys;         // [n]
+    int32_t *rows_out;           // [n]
+    FrKeySlot *tab;              // the call's own table of tab_mask + 1 >= 2 n slots, pre-filled {-1, FR_KEYS_NO_ROW}: ONE occurrence of every key of the
+    uint32_t tab_mask;           //   call admits it, the others take its row from here (keyadmit_settle_kernel); the CPU twin needs none (NULL)
+    int *err_flag;               // FR_KEYS_ERR_* bits
+};
+struct FrKeyReleaseArgs {
+    FrKeyCol col;
+    FrKeyPool pool;
+    int n;
+    const int64_t *keys;         // [n]
+    int *err_flag;               // FR_KEYS_ERR_ERASE_EMPTY
+};
+struct FrKeyMarkArgs {
+    FrKeyCol col;                // the map that is walked
+    FrKeyPool pool;              // bits: clear but for the pad bits; *free_rows: n_rows
+    int max_blocks;              // workgroups the launch takes at most (they stride over chunks of 256 x FR_KEYADMIT_PER_THREAD slots)
+};
+// Each enqueues its one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.  An admit is admit, then settle, on one stream.
+extern "C" int fr_keyadmit_admit_launch(const FrKeyAdmitArgs *args, void *stream);
+extern "C" int fr_keyadmit_settle_launch(const FrKeyAdmitArgs *args, void *stream);
+extern "C" int fr_keyadmit_release_launch(const FrKeyReleaseArgs *args, void *stream);
+extern "C" int fr_keyadmit_mark_launch(const FrKeyMarkArgs *args, void *stream);
+
 // ---- host objects -------------------------------------------------------------------------------
 // Where a table's rows live inside ctx->table_arena.  A table stored on its own: row r at byte_offset + r * dim * 4 (il_rows == 0).
 // FR_INDEX_PER_BANK contexts interleave the tables of one memory bank: rows [0, il_rows) of every table of the bank share one
@@ -472,6 +504,10 @@ struct fr_ctx {
         int64_t max_keys = 0;
         int32_t miss_row = 0x7fffffff;
         FrBuf<FrKeySlot> slots;            // MAPPED: the map
+        // the row pool (fr_ctx_set_row_pool; pool_rows == 0: none): a rebuild hands it to the new map, fr_ctx_set_key_space drops it with the old one
+        int32_t pool_first = 0, pool_rows = 0;
+        FrBuf<uint32_t> pool_bits;         // one bit per pool row, set = taken
+        FrBuf<int32_t> pool_free;          // [1]: the free rows
     };
     std::vector<KeySpace> key_spaces;      // [index columns]; empty until the first fr_ctx_set_key_space
     bool keyed = false;
@@ -489,6 +525,7 @@ struct fr_ctx {
     bool key_tab_made = false;
     FrBuf<int64_t> d_kp_keys;              // staging of fr_ctx_put_keys (grown on demand, used under lp_mutex on the set-up stream)
     FrBuf<int32_t> d_kp_rows;
+    FrBuf<FrKeySlot> d_ka_tab;             // the call's own table of fr_ctx_admit_keys (grown on demand, used under lp_mutex on the set-up stream)
     std::mutex workers_mutex;              // guards `workers`
     std::vector<struct fr_worker *> workers;   // live workers (fr_ctx_set_pooling asks each whether it has work in flight)
     FrBuf<unsigned long long> d_merged;    // lookups merged by the dedup gather (FR_GATHER_ITEM_TILE_DEDUP_COUNT)
@@ -559,6 +596,7 @@ struct fr_worker {
     // the counter of MAPPED lookups that found no key (device memory; made by the worker's first resolve)
     FrBuf<int64_t> h_keys;           // [max_batch][idx_cap]
     FrBuf<unsigned long long> d_key_miss;
+    FrBuf<FrKeySlot> d_admit_tab;    // the call's own table of fr_worker_admit_keys (device workers; grown on demand by the largest admit so far)
     // CPU back-end: a call computes before it returns; an index-range error stays in c_err until fr_worker_sync reports it
     FrBuf<float> c_scratch;      // [max_batch][H1 + H2 + H3]
     FrBuf<float> c_x;            // records of the sharded FC entry points, [max_batch][K]
@@ -697,6 +735,11 @@ void frc_fill_keys(const FrKeyFillArgs &a);
 // slot after slot, the same fr_keys.h predicates; export order: by slot)
 int frc_erase_keys(const FrKeyEraseArgs &a);
 void frc_walk_keys(const FrKeyWalkArgs &a);
+// the CPU twins of fr_keyadmit_admit_launch + _settle_launch (key after key, the LOWEST free row first; -> the FR_KEYS_ERR_* bits of the keys that were
+// not applied), fr_keyadmit_release_launch (-> FR_KEYS_ERR_ERASE_EMPTY or 0) and fr_keyadmit_mark_launch; the callers hold fr_ctx::lp_mutex
+int frc_admit_keys(const FrKeyAdmitArgs &a);
+int frc_release_keys(const FrKeyReleaseArgs &a);
+void frc_mark_pool(const FrKeyMarkArgs &a);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const FrEpi epi[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \

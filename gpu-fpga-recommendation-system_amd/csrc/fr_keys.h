@@ -1,5 +1,6 @@
 // Keyed lookups (fleetrec_serving.h, "Keyed lookups"): ONE definition of the slot layout, of mix64 and of the probe rule, included by the kernels
-// (fr_keys.hip -> libfleetrec_keys.so, the third companion code object; fr_keymaint.hip -> libfleetrec_keymaint.so, the fifth), by the CPU back-end (fr_cpu.cpp) and, through fr_internal.h, by the host
+// (fr_keys.hip -> libfleetrec_keys.so, the third companion code object; fr_keymaint.hip -> libfleetrec_keymaint.so, the fifth; fr_keyadmit.hip ->
+// libfleetrec_admit.so, the sixth), by the CPU back-end (fr_cpu.cpp) and, through fr_internal.h, by the host
 // side.  Everything here is plain data or an inline function; nothing is a symbol of any library.
 #pragma once
 
@@ -19,6 +20,9 @@ constexpr int FR_KEYS_LDS_COLS = 384;               // column records a workgrou
 // what a put raises in the status word it is given (bit 0 stays the lookups' own "index outside its table")
 constexpr int FR_KEYS_ERR_EMPTY_KEY = 2, FR_KEYS_ERR_ROW = 4, FR_KEYS_ERR_FULL = 8;
 constexpr int FR_KEYS_ERR_ERASE_EMPTY = 16;         // what an erase raises there: a key of -1 in its list
+// what an admit raises there: its own case (the pool has no free row), and, beside that bit or FR_KEYS_ERR_EMPTY_KEY / _FULL, the mark that the
+// call was an admit and not a put (fr_worker_sync words its message by it)
+constexpr int FR_KEYS_ERR_NO_FREE_ROW = 32, FR_KEYS_ERR_ADMIT = 64;
 
 struct FrKeySlot {   // 16 bytes, 16-byte aligned: one probe is one load
     int64_t key;     // FR_KEYS_EMPTY_KEY: nobody has claimed the slot
@@ -128,3 +132,19 @@ FR_KEYS_HD int64_t fr_key_find(const FrKeyCol &c, int64_t k) {
     }
     return -1;
 }
+
+// ---- row pools (fr_ctx_set_row_pool / fr_*_admit_keys; fr_keyadmit.hip and the CPU twins) ----
+// The pool of a MAPPED column: the rows [first_row, first_row + n_rows), one bit per row (set = taken) in 32-bit words, and ONE counter of free rows.
+// The pad bits past n_rows in the last word are set for good, so no scan hands them out.  The counter is signed: a taker subtracts first and gives
+// back what went below zero.
+struct FrKeyPool {
+    uint32_t *bits;        // [fr_key_pool_words(n_rows)]
+    int32_t *free_rows;    // = the clear bits, whenever no admit or erase is in flight
+    int32_t first_row;
+    int32_t n_rows;        // 0: the column has no pool
+};
+
+FR_KEYS_HD uint32_t fr_key_pool_words(int32_t n_rows) { return ((uint32_t)n_rows + 31u) >> 5; }
+FR_KEYS_HD bool fr_key_pool_holds(const FrKeyPool &p, int32_t row) { return row >= p.first_row && row - p.first_row < p.n_rows; }   // (first_row + n_rows <= 2^31 - 1)
+// the pad bits of the last word (0 when n_rows is a multiple of 32)
+FR_KEYS_HD uint32_t fr_key_pool_pad(int32_t n_rows) { return ((uint32_t)n_rows & 31u) ? ~0u << ((uint32_t)n_rows & 31u) : 0u; }

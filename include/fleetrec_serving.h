@@ -460,6 +460,48 @@ int fr_ctx_key_space_stats(fr_ctx *ctx, int col, int64_t *slots, int64_t *occupi
 int fr_ctx_export_keys(fr_ctx *ctx, int col, int64_t cap, int64_t *h_keys, int32_t *h_rows, int64_t *n_out);
 int fr_ctx_rebuild_key_space(fr_ctx *ctx, int col, uint64_t seed, int64_t max_keys);
 
+/* Row pools: admitting ids (additive in ABI 6).  Which row a new id gets is decided on the device: a MAPPED column is given a ROW POOL, a range of
+ * its rows that the library hands out and takes back, and the whole life of an id runs in one stream on one worker, without a host copy of the map:
+ *   fr_worker_admit_keys -> fr_worker_update_rows (ids = the rows just assigned) -> fr_worker_resolve_keys_device -> gather / submit -> fr_worker_erase_keys
+ * Pool: the rows [first_row, first_row + n_rows) of the column, inside [0, R_c), not containing the column's miss_row; n_rows == 0 drops the pool.
+ *   The FREE SET IS DERIVED FROM THE MAP AS IT STANDS: a pool row held by a live key is taken, every other pool row is free.  So the call works on a map
+ *   restored from an export (set_key_space + put_keys + set_row_pool), on an empty map, and AGAIN on the same column, where it re-derives the free set:
+ *   the way back after rows inside the range were put by hand, which fr_*_put_keys still allows and the pool does not learn of.  FR_ERR_INVALID: a
+ *   range outside [0, R_c), one that contains miss_row, n_rows < 0, a column out of range; FR_ERR_STATE (the rules of fr_ctx_set_key_space): a column
+ *   that is not MAPPED, a worker of the context with work in flight, n_shards > 1; FR_ERR_OOM: the bookkeeping (one bit per pool row) does not fit.  In
+ *   every error case the column keeps the pool it had.  fr_ctx_rebuild_key_space keeps the pool (live keys keep their rows); fr_ctx_set_key_space on
+ *   the column drops it (the map starts empty).  fr_ctx_row_pool: n_rows = 0 for a column without a pool; free_rows = the free rows; any output pointer
+ *   may be NULL; it synchronises the device as fr_ctx_key_space does.
+ * Admit, per key k of the call (a column without a pool: FR_ERR_STATE):
+ *   k live (present, row != miss_row): rows_out[i] = its row; nothing is written, free_rows is unchanged.
+ *   k absent or dead: one free pool row r is taken; an absent key claims a slot under the put's rules (n_keys against max_keys, bounded probe), a dead
+ *     key keeps its slot and n_keys; the row is stored and rows_out[i] = r.  Which free row is taken is unspecified on the device; the CPU back-end
+ *     takes the lowest-numbered one.
+ *   Not applied, reported as FR_ERR_INDEX_RANGE at fr_worker_sync (fr_ctx_admit_keys returns it itself), fr_last_error() naming the key admit and the
+ *     case, every other key applied, the worker usable afterwards: k == -1 (rows_out[i] = -1); no free row (status bit FR_KEYS_ERR_NO_FREE_ROW = 32;
+ *     rows_out[i] = FR_KEY_NO_ROW; an absent key stays absent: nothing is claimed, n_keys is unchanged); a new key when n_keys == max_keys
+ *     (rows_out[i] = FR_KEY_NO_ROW; the row goes back to the pool).
+ *   A key listed several times in one call: every occurrence reports the SAME row and free_rows drops by one per distinct new key -- one occurrence is
+ *     elected on the device and the others take its answer, so neither rows nor places in the map are taken for a moment by the duplicates.  The put's
+ *     caveat remains between CALLS: when admits of one key race from unsynchronised workers while the pool is at its last row or the map at its last
+ *     place, one of them may be reported as finding none.
+ *   Arguments, order and the flush rule are fr_worker_put_keys's: n == 0 is FR_OK; d_keys 8-byte, d_rows_out 4-byte aligned; queued fused batches are
+ *     launched first; host-fed blocks still queued: FR_ERR_STATE; both arrays stay valid until the sync.  While the call is in flight rows_out may hold
+ *     values that are no answer.  fr_ctx_admit_keys: the host form, synchronous on the context's set-up stream, legal beside workers in flight.
+ *   Composition: a following fr_worker_update_rows(w, table, n, d_rows_out, d_vectors) on the same worker writes the embeddings of exactly the admitted
+ *     ids (FR_KEY_NO_ROW and -1 entries write nothing and are reported, by the range rule of the updates); a following resolve sees the new rows; a
+ *     resolve in flight on another worker sees, per key, the old row (or miss_row) or the new row, never anything else.
+ *   Racing admits of one column from unsynchronised workers are legal: distinct keys get distinct rows, the same key gets one row, free_rows ends exact.
+ *   Admit racing erase of one column across unsynchronised workers: which rows are handed out is unspecified; no row outside the pool is ever handed
+ *     out, no live row is handed out twice, and no byte outside the map, the pool's bookkeeping and the call's arrays is touched.
+ * Erase on a column with a pool: fr_*_erase_keys keeps its contract word for word; in addition the row of each erased key goes back to the pool if it
+ *   lies in the pool range -- once, however often the key is listed.  Absent keys and -1 behave as ever.
+ * Out of scope: a combined admit-and-write call; eviction policy; pools on sharded contexts; reuse of dead SLOTS (fr_ctx_rebuild_key_space). */
+int fr_ctx_set_row_pool(fr_ctx *ctx, int col, int32_t first_row, int32_t n_rows);   /* n_rows == 0 drops the pool */
+int fr_ctx_row_pool(fr_ctx *ctx, int col, int32_t *first_row, int32_t *n_rows, int64_t *free_rows);
+int fr_worker_admit_keys(fr_worker *w, int col, int n, const int64_t *d_keys, int32_t *d_rows_out);
+int fr_ctx_admit_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys, int32_t *h_rows_out);
+
 /* ---- per-layer epilogue: bias and ReLU between the FC layers ----
  * The reference's chain is four matrix products with nothing between them (alpha = 1, beta = 0, cuda_server.c:211-217), which no trained model
  * looks like.  A context holds, per layer l = 0..3 (W1, W2, W3, Wout), an optional bias vector b_l of fc[l + 1] fp32 values and, for the hidden
