@@ -69,12 +69,6 @@ static int select_device(int device) {
     return FR_OK;
 }
 
-// every entry point selects its context's device first; a CPU context (device = -1, fr_cpu.cpp) has none
-#define FR_SET_DEVICE(ctx_)                                    \
-    do {                                                       \
-        if (!(ctx_)->cpu) FR_HIP(hipSetDevice((ctx_)->device)); \
-    } while (0)
-
 static unsigned long long *g_stamp_buffer = nullptr;  // diagnostics (tools/experiments): see fr_debug_set_stamp_buffer
 extern "C" __attribute__((visibility("default"))) void fr_debug_set_stamp_buffer(void *dptr) { g_stamp_buffer = (unsigned long long *)dptr; }
 
@@ -464,7 +458,7 @@ extern "C" int fr_ctx_create_sharded(const fr_model_desc *m, int device, int sha
         ctx_free(c);
         return rc;
     }
-    if (!cpu) {   // immutable after creation (read by every driver thread in fused_flush without synchronisation): the device's compute units and
+    if (!cpu) {   // immutable after creation (read by every driver thread in fr_fused_flush without synchronisation): the device's compute units and
         // whether the persistent K-outer fused kernel applies to this context's descriptors and FC shape
         int n_cu = 0;
         if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) n_cu = 0;
@@ -1471,7 +1465,7 @@ static bool fused_eligible(const fr_ctx *c) {
     if (c->fc_precision == FR_FC_FP8) return frk_fused_f8_ok(fc[0], fc[1], fc[2], fc[3]);
     // bf16: the chunked kernel exists for the two reference records (352 / 880 floats); any other record the K-outer persistent kernel
     // accepts (64 .. 880 floats in whole k-groups, frk_fused_hk_ok) streams through that kernel at every launch size
-    // (... unless the context has an epilogue, which that kernel does not carry: see fused_flush)
+    // (... unless the context has an epilogue, which that kernel does not carry: see fr_fused_flush)
     if (c->fc_precision == FR_FC_BF16) return frk_fused_h_ok(fc[0], fc[1], fc[2], fc[3]) || (c->hk_ok == 1 && !c->any_epi());
     return frk_fused_ok(fc[0], fc[1], fc[2], fc[3]);
 }
@@ -1522,7 +1516,7 @@ static int fused_launch_slice(fr_worker *w, FrFusedArgs &a, int first, int n) {
     return frk_fused_launch(a, w->stream);
 }
 
-static int fused_flush(fr_worker *w) {
+int fr_fused_flush(fr_worker *w) {
     if (w->n_pending == 0) return FR_OK;
     fr_ctx *c = w->ctx;
     FrFusedArgs a{};
@@ -1741,7 +1735,16 @@ extern "C" int fr_worker_gather_only(fr_worker *w, int batch, const int32_t *d_i
 // ---- multi-hot pooled lookups (fleetrec_serving.h) -------------------------------------------------------
 // Pooling is stated per index column; the pooled descriptors (one FrPoolDesc per FrWordDesc) follow from h_words: a TABLE / COPY word's bag
 // is its index column's, a DENSE word is a bag of one.  The column's mode (fr_ctx_set_pooling_modes) rides in the descriptor's hots word.
-static int pooling_busy(fr_ctx *ctx, const char *who) {
+// what every stream-ordered worker call but a host-fed push itself says while host-fed batches wait in a block that has not been launched
+int fr_host_fed_queued(fr_worker *w, const char *verb) {
+    int queued = 0;
+    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
+    if (queued > 0 || w->hr.staged)
+        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then %s", verb);
+    return FR_OK;
+}
+
+int fr_pooling_busy(fr_ctx *ctx, const char *who) {
     std::lock_guard<std::mutex> g(ctx->workers_mutex);
     for (const fr_worker *w : ctx->workers)
         if (w->in_flight || w->n_active || w->n_pending || w->sh_comm)
@@ -1849,7 +1852,7 @@ extern "C" int fr_ctx_set_pooling(fr_ctx *ctx, const int32_t *hots, int n_cols) 
         for (int c = 0; c < cols; c++)
             if (hots[c] < 1 || hots[c] > FR_POOL_MAX_HOTS) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling: hots[%d] = %d outside [1, %d]", c, hots[c], FR_POOL_MAX_HOTS);
     }
-    const int rc = pooling_busy(ctx, "fr_ctx_set_pooling");
+    const int rc = fr_pooling_busy(ctx, "fr_ctx_set_pooling");
     if (rc) return rc;
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
     if (!hots) {
@@ -1881,7 +1884,7 @@ extern "C" int fr_ctx_set_pooling_modes(fr_ctx *ctx, const int32_t *modes, int n
         for (int c = 0; c < cols; c++)
             if (modes[c] != FR_POOL_SUM && modes[c] != FR_POOL_MEAN) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_pooling_modes: modes[%d] = %d is no pooling mode", c, modes[c]);
     }
-    const int rc = pooling_busy(ctx, "fr_ctx_set_pooling_modes");
+    const int rc = fr_pooling_busy(ctx, "fr_ctx_set_pooling_modes");
     if (rc) return rc;
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
     return pooling_install(ctx, ctx->pool_hots.data(), modes);   // the descriptors are rebuilt and uploaded again
@@ -2218,7 +2221,7 @@ extern "C" int fr_worker_push_device(fr_worker *w, int batch, const int32_t *d_i
         if (rc) return rc;
     }
     if (!fused && w->n_pending > 0) {        // ... or lowered with batches queued for a fused launch
-        rc = fused_flush(w);
+        rc = fr_fused_flush(w);
         if (rc) return rc;
     }
     if (fused) {
@@ -2238,7 +2241,7 @@ extern "C" int fr_worker_push_device(fr_worker *w, int batch, const int32_t *d_i
         // 1024: 330 M inf/s at 4 tiles per workgroup (group 64), 340 M at 8 (group 128), 342 M at 16 (profiles/archive/r03_fused_hs_items_ab.txt)
         const bool big = c->fc_precision == FR_FC_BF16 || (c->fc_precision == FR_FC_FP8 && FR_KNOB_ONCE("FUSED_HK", -1) == 1);
         const int64_t max_items = FR_KNOB_ONCE("FUSED_ITEMS", 0) ? FR_KNOB_ONCE("FUSED_ITEMS", 0) : (big ? 4096 * 64 : 256 * 64);
-        return (w->n_pending >= fused_group(c) || w->pending_items >= max_items || w->n_pending >= FR_FUSED_MAX_QUEUE) ? fused_flush(w) : FR_OK;
+        return (w->n_pending >= fused_group(c) || w->pending_items >= max_items || w->n_pending >= FR_FUSED_MAX_QUEUE) ? fr_fused_flush(w) : FR_OK;
     }
     rc = pipeline_push(w, batch, 0, d_idx, d_dense, d_scores);
     if (rc) return rc;
@@ -2274,13 +2277,10 @@ static int push_pooled_impl(fr_worker *w, const FrPooledBatch &b, float *d_score
         w->in_flight = true;
         return FR_OK;
     }
-    int queued = 0;
-    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
-    if (queued > 0 || w->hr.staged)
-        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then push");
+    FR_TRY(fr_host_fed_queued(w, "push"));
     if (c->slice_padded != c->model.fc[0]) FR_FAIL(FR_ERR_STATE, "internal: a record of %d floats on a chain of K = %d", c->slice_padded, c->model.fc[0]);
     FR_SET_DEVICE(c);
-    rc = fused_flush(w);   // batches fr_worker_push_device queued for a fused launch were pushed before this one: launched first, not waited for
+    rc = fr_fused_flush(w);   // batches fr_worker_push_device queued for a fused launch were pushed before this one: launched first, not waited for
     if (rc) return rc;
     if (w->launch_no == 0) w->launch_no = 1;   // stage 1 of the next launch reads the set the (virtual) previous launch wrote
     // a one-hot batch gathered by the previous launch holds the slot (and the X operand) this batch would take: one launch without a new batch
@@ -2448,7 +2448,7 @@ static int host_block_launch(fr_worker *w) {
     fr_worker::HostRing &r = w->hr;
     const int b = r.cur, n = r.count[b];
     if (n == 0) return FR_OK;
-    int rc = fused_flush(w);  // batches queued by fr_worker_push_device go first
+    int rc = fr_fused_flush(w);  // batches queued by fr_worker_push_device go first
     if (rc) return rc;
     const size_t s0 = (size_t)b * r.g;
     if (n <= w->ctx->small_block.load(std::memory_order_relaxed) && w->n_active == 0) {
@@ -2500,7 +2500,7 @@ static int host_block_launch(fr_worker *w) {
             fb.scores = (zc ? r.h_sc : r.d_sc) + (s0 + i) * r.score_slot;
             fb.batch = r.bsz[b][i];
         }
-        int rc2 = fused_flush(w);
+        int rc2 = fr_fused_flush(w);
         if (rc2) return rc2;
         if (!zc) FR_HIP(hipMemcpyAsync(r.h_sc + s0 * r.score_slot, r.d_sc + s0 * r.score_slot, (size_t)n * r.score_slot * sizeof(float), hipMemcpyDeviceToHost, w->stream));
         FR_HIP(hipEventRecord(r.ev[b], w->stream));
@@ -2690,6 +2690,17 @@ extern "C" int fr_worker_calibrate_fp8_slices(fr_worker *w, int batch_total, int
 }
 
 // ---- sparse row updates (fleetrec_serving.h) ---------------------------------------------------------------------------------------
+// The status word of the set-up stream's list-form calls (fr_ctx_update_rows, fr_ctx_put_keys / _erase_keys / _admit_keys), under lp_mutex: made by
+// the first of them, taken -- read and cleared -- by each behind its own launches.
+int fr_up_err_ensure(fr_ctx *ctx) {
+    if (ctx->h_up_err) return FR_OK;
+    FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
+    *ctx->h_up_err = 0;
+    FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
+    return FR_OK;
+}
+int fr_up_err_take(fr_ctx *ctx) { return __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL); }
+
 static int update_check(fr_ctx *ctx, int table, int n, const void *ids, const void *rows) {
     if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
     if (n < 0) FR_FAIL(FR_ERR_INVALID, "n = %d rows", n);
@@ -2727,12 +2738,9 @@ extern "C" int fr_worker_update_rows(fr_worker *w, int table, int n, const int32
         return FR_OK;
     }
     if ((uintptr_t)d_rows % 16) FR_FAIL(FR_ERR_INVALID, "d_rows must be 16-byte aligned");
-    int queued = 0;
-    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
-    if (queued > 0 || w->hr.staged)
-        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then update");
+    FR_TRY(fr_host_fed_queued(w, "update"));
     FR_SET_DEVICE(c);
-    rc = fused_flush(w);   // batches fr_worker_push_device queued for a fused launch were pushed BEFORE the update: they gather the old rows
+    rc = fr_fused_flush(w);   // batches fr_worker_push_device queued for a fused launch were pushed BEFORE the update: they gather the old rows
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->lp_mutex);
     rc = update_enqueue(c, table, n, d_row_ids, d_rows, w->d_err, w->stream);
@@ -2754,11 +2762,7 @@ extern "C" int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *
     }
     FR_SET_DEVICE(ctx);
     std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // also serialises the set-up stream and the staging buffers against other updates and an image build
-    if (!ctx->h_up_err) {
-        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
-        *ctx->h_up_err = 0;
-        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
-    }
+    FR_TRY(fr_up_err_ensure(ctx));
     const size_t n_floats = (size_t)n * (size_t)dim;
     FR_TRY(ctx->d_up_ids.grow(FrMem::DEVICE, (size_t)n, "row-update ids"));
     FR_TRY(ctx->d_up_rows.grow(FrMem::DEVICE, n_floats, "row-update rows"));
@@ -2767,10 +2771,7 @@ extern "C" int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *
     rc = update_enqueue(ctx, table, n, ctx->d_up_ids, ctx->d_up_rows, ctx->d_up_err, ctx->setup_stream);
     FR_HIP(hipStreamSynchronize(ctx->setup_stream));
     if (rc) return rc;
-    if (__atomic_load_n(ctx->h_up_err.p, __ATOMIC_ACQUIRE)) {
-        __atomic_store_n(ctx->h_up_err.p, 0, __ATOMIC_RELEASE);
-        FR_FAIL(FR_ERR_INDEX_RANGE, "a listed row id was outside table %d (that row was not written, the others were)", table);
-    }
+    if (fr_up_err_take(ctx)) FR_FAIL(FR_ERR_INDEX_RANGE, "a listed row id was outside table %d (that row was not written, the others were)", table);
     return FR_OK;
 }
 
@@ -2788,10 +2789,7 @@ static int topk_check(fr_worker *w, int n, const void *scores, int n_seg, int k,
 // behind everything submitted or pushed on w: queued fused batches are launched, the stage pipeline is drained by launches; nothing is waited for
 static int topk_enqueue(fr_worker *w, int n, const float *d_scores, int n_seg, const int32_t *d_off, int k, int32_t *d_top_idx, float *d_top_scores) {
     fr_ctx *c = w->ctx;
-    int queued = 0;
-    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
-    if (queued > 0 || w->hr.staged)
-        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then rank");
+    FR_TRY(fr_host_fed_queued(w, "rank"));
     if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then rank");
     FR_SET_DEVICE(c);
     FrRankArgs a{};
@@ -2809,7 +2807,7 @@ static int topk_enqueue(fr_worker *w, int n, const float *d_scores, int n_seg, c
         a.unitmap = reinterpret_cast<int4 *>(w->d_rank + 256);
         a.cand = reinterpret_cast<unsigned long long *>(w->d_rank + 256 + map_bytes);
     }
-    int rc = fused_flush(w);
+    int rc = fr_fused_flush(w);
     if (!rc) rc = pipeline_flush(w);
     if (rc) return rc;
     // a wave per segment when the segments are short on average (the host does not know the offsets: any length is ranked correctly by either form)
@@ -2913,7 +2911,7 @@ extern "C" int fr_ctx_set_request_columns(fr_ctx *ctx, const int32_t *shared, in
         if (n_shared == cols && (!ctx->model.dense_len || dense_shared))
             FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_request_columns: nothing is left per item (every column is shared and there are no per-item dense features)");
     }
-    const int rc = pooling_busy(ctx, "fr_ctx_set_request_columns");
+    const int rc = fr_pooling_busy(ctx, "fr_ctx_set_request_columns");
     if (rc) return rc;
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
     if (!shared) {
@@ -3042,642 +3040,7 @@ extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int
     return FR_OK;
 }
 
-// ---- keyed lookups (fleetrec_serving.h) --------------------------------------------------------------------------------------------------------
-// The kernels are the third companion code object's (fr_keys.hip -> libfleetrec_keys.so, linked with an $ORIGIN rpath); slot layout, mix64 and the probe
-// rule are fr_keys.h's; key spaces, tables, order and the host form are here, the CPU twins in fr_cpu.cpp.
-static uint32_t key_col_range(const fr_ctx *c, int col) {   // R_c: the row count the one-hot gather checks for index column col (build_words)
-    const fr_model_desc &m = c->model;
-    if (m.index_mode == FR_INDEX_PER_TABLE) return (uint32_t)c->tables[(size_t)col].rows;
-    if (m.index_mode == FR_INDEX_PER_BANK) return (uint32_t)c->bank_rows[(size_t)col];
-    int64_t r = c->tables[0].rows;
-    for (const fr_table_desc &t : c->tables) r = t.rows < r ? t.rows : r;
-    return (uint32_t)r;
-}
-
-static int key_col_check(const fr_ctx *c, int col, const char *who) {
-    if (col < 0 || col >= (int)idx_cols(c)) FR_FAIL(FR_ERR_INVALID, "%s: column %d, the context has %zu index columns", who, col, idx_cols(c));
-    return FR_OK;
-}
-
-// the records of every column as a resolve reads them, from key_spaces: on the device (synchronous copy) or, on the CPU back-end, in place
-static int key_cols_upload(fr_ctx *c) {
-    const size_t C = idx_cols(c);
-    c->h_key_cols.resize(C);
-    for (size_t i = 0; i < C; i++) {
-        const fr_ctx::KeySpace &k = c->key_spaces[i];
-        FrKeyCol &r = c->h_key_cols[i];
-        r.seed = k.seed, r.slots = k.slots.p, r.mask = k.slots.p ? (uint32_t)(k.slots.count() - 1) : 0u;
-        r.range = key_col_range(c, (int)i), r.miss_row = k.miss_row, r.mode = k.mode;
-    }
-    if (c->cpu) return FR_OK;
-    FR_TRY(c->d_key_cols.grow(FrMem::DEVICE, C, "key-space records"));
-    FR_HIP(hipMemcpy(c->d_key_cols, c->h_key_cols.data(), C * sizeof(FrKeyCol), hipMemcpyHostToDevice));
-    return FR_OK;
-}
-
-// key spaces exist from the first call on: every column FR_KEYS_ROWS, the counts zero
-static int key_spaces_init(fr_ctx *c) {
-    if (!c->key_spaces.empty()) return FR_OK;
-    const size_t C = idx_cols(c);
-    FrBuf<uint32_t> counts;
-    FR_TRY(counts.alloc(fr_mem_kind(c, FrMem::DEVICE), C, "key counts"));
-    if (c->cpu) memset(counts.p, 0, C * sizeof(uint32_t));
-    else FR_HIP(hipMemset(counts.p, 0, C * sizeof(uint32_t)));
-    if (!c->cpu) FR_TRY(c->d_key_walk.alloc(FrMem::DEVICE, 3, "key-map walk counters"));
-    c->d_key_counts.swap(counts);
-    c->key_spaces.resize(C);
-    return key_cols_upload(c);
-}
-
-extern "C" int fr_ctx_set_key_space(fr_ctx *ctx, int col, int mode, uint64_t seed, int64_t max_keys, int32_t miss_row) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_col_check(ctx, col, "fr_ctx_set_key_space"));
-    if (mode < FR_KEYS_ROWS || mode > FR_KEYS_MAPPED) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_key_space: mode %d is none of FR_KEYS_ROWS, FR_KEYS_HASHED, FR_KEYS_MAPPED", mode);
-    const uint32_t range = key_col_range(ctx, col);
-    if (mode == FR_KEYS_MAPPED) {
-        if (max_keys < 1 || max_keys > (1ll << 30)) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_key_space: max_keys %lld outside [1, 2^30]", (long long)max_keys);
-        if (miss_row != -1 && miss_row != FR_KEY_NO_ROW && !(miss_row >= 0 && (uint32_t)miss_row < range))
-            FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_key_space: miss_row %d is neither a row of column %d (%u rows), nor -1, nor FR_KEY_NO_ROW", miss_row, col, range);
-    }
-    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_key_space: keyed lookups are not available on a sharded context (%d shards)", ctx->n_shards);
-    FR_TRY(pooling_busy(ctx, "fr_ctx_set_key_space"));
-    if (!ctx->cpu) FR_SET_DEVICE(ctx);
-    std::lock_guard<std::mutex> lk(ctx->key_mutex);   // (a first resolve on another thread makes the key spaces under the same lock)
-    FR_TRY(key_spaces_init(ctx));
-    fr_ctx::KeySpace next;
-    next.mode = mode, next.seed = mode == FR_KEYS_ROWS ? 0 : seed;
-    if (mode == FR_KEYS_MAPPED) {
-        next.max_keys = max_keys, next.miss_row = miss_row;
-        const uint64_t slots = fr_key_slots((uint64_t)max_keys);
-        FR_TRY(next.slots.alloc(fr_mem_kind(ctx, FrMem::DEVICE), (size_t)slots, "key map"));
-        FrKeyFillArgs f{next.slots.p, slots, miss_row};
-        if (ctx->cpu) {
-            frc_fill_keys(f);
-        } else {
-            const int e = fr_key_fill_launch(&f, (void *)ctx->setup_stream);
-            if (e) FR_FAIL(FR_ERR_HIP, "the key map's fill launch failed: %s", hipGetErrorString((hipError_t)e));
-            FR_HIP(hipStreamSynchronize(ctx->setup_stream));
-        }
-    }
-    const uint32_t zero = 0;
-    if (ctx->cpu) ctx->d_key_counts[col] = 0;
-    else FR_HIP(hipMemcpy(ctx->d_key_counts + col, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    std::swap(ctx->key_spaces[(size_t)col], next);   // (no worker has work in flight: whatever map the column had is released with `next`)
-    if (mode != FR_KEYS_ROWS) ctx->keyed = true;
-    return key_cols_upload(ctx);
-}
-
-extern "C" int fr_ctx_key_space(fr_ctx *ctx, int col, int *mode, uint64_t *seed, int64_t *max_keys, int64_t *n_keys, int32_t *miss_row) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_col_check(ctx, col, "fr_ctx_key_space"));
-    const fr_ctx::KeySpace none{};
-    const fr_ctx::KeySpace &k = ctx->key_spaces.empty() ? none : ctx->key_spaces[(size_t)col];
-    uint32_t n = 0;
-    if (k.mode == FR_KEYS_MAPPED) {
-        if (ctx->cpu) {
-            n = __atomic_load_n(ctx->d_key_counts + col, __ATOMIC_ACQUIRE);
-        } else {
-            FR_SET_DEVICE(ctx);
-            FR_HIP(hipDeviceSynchronize());
-            FR_HIP(hipMemcpy(&n, ctx->d_key_counts + col, sizeof(n), hipMemcpyDeviceToHost));
-        }
-    }
-    if (mode) *mode = k.mode;
-    if (seed) *seed = k.seed;
-    if (max_keys) *max_keys = k.max_keys;
-    if (n_keys) *n_keys = (int64_t)n;
-    if (miss_row) *miss_row = k.miss_row;
-    return FR_OK;
-}
-
-static int key_put_check(fr_ctx *c, int col, int n, const void *keys, const void *rows, const char *who) {
-    FR_TRY(key_col_check(c, col, who));
-    if (n < 0) FR_FAIL(FR_ERR_INVALID, "%s: n = %d pairs", who, n);
-    if (n > 0 && (!keys || !rows)) FR_FAIL(FR_ERR_INVALID, "%s: keys / rows is NULL", who);
-    if (c->key_spaces.empty() || c->key_spaces[(size_t)col].mode != FR_KEYS_MAPPED)
-        FR_FAIL(FR_ERR_STATE, "%s: column %d has no map: call fr_ctx_set_key_space(ctx, %d, FR_KEYS_MAPPED, ...) first", who, col, col);
-    return FR_OK;
-}
-
-static FrKeyPutArgs key_put_args(fr_ctx *c, int col, int n, const int64_t *keys, const int32_t *rows, int *err) {
-    FrKeyPutArgs a{};
-    a.col = c->h_key_cols[(size_t)col], a.n_keys = c->d_key_counts + col, a.max_keys = (uint32_t)c->key_spaces[(size_t)col].max_keys;
-    a.n = n, a.keys = keys, a.rows = rows, a.err_flag = err;
-    return a;
-}
-
-// what fr_worker_sync (or fr_ctx_put_keys itself) says about the bits of a status word; bit 0 is the lookups'
-static int index_range_fail(int bits) {
-    const char *lookup = (bits & 1) ? "a lookup index was outside its table (row 0 was read instead)" : "";
-    if (bits & FR_KEYS_ERR_ADMIT) {   // an admit marks its bits; whatever else the word holds is named by the rest of the word, without the admit's
-        char rest[640] = "";
-        const int other = bits & ~(FR_KEYS_ERR_ADMIT | FR_KEYS_ERR_NO_FREE_ROW | FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_FULL);
-        if (other) {
-            (void)index_range_fail(other);
-            snprintf(rest, sizeof rest, " %s", fr_last_error());
-        }
-        FR_FAIL(FR_ERR_INDEX_RANGE, "a key admit was not applied (every other key was):%s%s%s%s", (bits & FR_KEYS_ERR_EMPTY_KEY) ? " a key of -1 (FR_KEY_EMPTY);" : "",
-                (bits & FR_KEYS_ERR_NO_FREE_ROW) ? " no free row: the column's row pool is exhausted (FR_KEYS_ERR_NO_FREE_ROW);" : "",
-                (bits & FR_KEYS_ERR_FULL) ? " a new key for a map that holds max_keys keys (the row went back to the pool);" : "", rest);
-    }
-    const int put = bits & (FR_KEYS_ERR_EMPTY_KEY | FR_KEYS_ERR_ROW | FR_KEYS_ERR_FULL);
-    const char *erase = (bits & FR_KEYS_ERR_ERASE_EMPTY) ? "a key erase was not applied (every other key was): a key of -1 (FR_KEY_EMPTY);" : "";
-    if (!put) FR_FAIL(FR_ERR_INDEX_RANGE, "%s%s%s", lookup, (bits & 1) && *erase ? "; " : "", erase);
-    FR_FAIL(FR_ERR_INDEX_RANGE, "%s%sa key put was not applied (every other pair was):%s%s%s%s%s", lookup, (bits & 1) ? "; " : "", (bits & FR_KEYS_ERR_EMPTY_KEY) ? " a key of -1 (FR_KEY_EMPTY);" : "",
-            (bits & FR_KEYS_ERR_ROW) ? " a row that is neither one of the column's rows nor its miss_row;" : "", (bits & FR_KEYS_ERR_FULL) ? " a new key for a map that holds max_keys keys;" : "",
-            *erase ? " " : "", erase);
-}
-
-extern "C" int fr_worker_put_keys(fr_worker *w, int col, int n, const int64_t *d_keys, const int32_t *d_rows) {
-    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
-    fr_ctx *c = w->ctx;
-    FR_TRY(key_put_check(c, col, n, d_keys, d_rows, "fr_worker_put_keys"));
-    if (n == 0) return FR_OK;
-    if ((uintptr_t)d_keys % 8 || (uintptr_t)d_rows % 4) FR_FAIL(FR_ERR_INVALID, "fr_worker_put_keys: d_keys must be 8-byte aligned, d_rows 4-byte aligned");
-    int queued = 0;
-    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
-    if (queued > 0 || w->hr.staged)
-        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then put");
-    if (c->cpu) {   // computed before the call returns, one writer at a time; what was not applied waits in c_err for fr_worker_sync
-        std::lock_guard<std::mutex> lk(c->lp_mutex);
-        const int bad = frc_put_keys(key_put_args(c, col, n, d_keys, d_rows, nullptr));
-        if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
-        return FR_OK;
-    }
-    FR_SET_DEVICE(c);
-    FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the put: whatever they read was resolved against the old map
-    const FrKeyPutArgs a = key_put_args(c, col, n, d_keys, d_rows, w->d_err);
-    const int e = fr_key_put_launch(&a, (void *)w->stream);
-    if (e) FR_FAIL(FR_ERR_HIP, "the key put launch failed: %s", hipGetErrorString((hipError_t)e));
-    w->in_flight = true;
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_put_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys, const int32_t *h_rows) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_put_check(ctx, col, n, h_keys, h_rows, "fr_ctx_put_keys"));
-    if (n == 0) return FR_OK;
-    if ((uintptr_t)h_keys % 8 || (uintptr_t)h_rows % 4) FR_FAIL(FR_ERR_INVALID, "fr_ctx_put_keys: h_keys must be 8-byte aligned, h_rows 4-byte aligned");
-    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_update_rows's too
-    if (ctx->cpu) {
-        const int bad = frc_put_keys(key_put_args(ctx, col, n, h_keys, h_rows, nullptr));
-        return bad ? index_range_fail(bad) : FR_OK;
-    }
-    FR_SET_DEVICE(ctx);
-    if (!ctx->h_up_err) {
-        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
-        *ctx->h_up_err = 0;
-        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
-    }
-    FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
-    FR_TRY(ctx->d_kp_rows.grow(FrMem::DEVICE, (size_t)n, "key-put rows"));
-    FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
-    FR_HIP(hipMemcpyAsync(ctx->d_kp_rows, h_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->setup_stream));
-    const FrKeyPutArgs a = key_put_args(ctx, col, n, ctx->d_kp_keys, ctx->d_kp_rows, ctx->d_up_err);
-    const int e = fr_key_put_launch(&a, (void *)ctx->setup_stream);
-    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
-    if (e) FR_FAIL(FR_ERR_HIP, "the key put launch failed: %s", hipGetErrorString((hipError_t)e));
-    const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
-    return bad ? index_range_fail(bad) : FR_OK;
-}
-
-// ---- the life cycle of a key map: erase, stats, export, rebuild (fleetrec_serving.h) --------------------------------------------------------------
-// The kernels are the fifth companion code object's (fr_keymaint.hip -> libfleetrec_keymaint.so); the CPU twins are frc_erase_keys / frc_walk_keys.
-static int key_erase_check(fr_ctx *c, int col, int n, const void *keys, const char *who) {
-    FR_TRY(key_col_check(c, col, who));
-    if (n < 0) FR_FAIL(FR_ERR_INVALID, "%s: n = %d keys", who, n);
-    if (n > 0 && !keys) FR_FAIL(FR_ERR_INVALID, "%s: keys is NULL", who);
-    if (c->key_spaces.empty() || c->key_spaces[(size_t)col].mode != FR_KEYS_MAPPED)
-        FR_FAIL(FR_ERR_STATE, "%s: column %d has no map: call fr_ctx_set_key_space(ctx, %d, FR_KEYS_MAPPED, ...) first", who, col, col);
-    return FR_OK;
-}
-
-static FrKeyEraseArgs key_erase_args(fr_ctx *c, int col, int n, const int64_t *keys, int *err) {
-    FrKeyEraseArgs a{};
-    a.col = c->h_key_cols[(size_t)col], a.n = n, a.keys = keys, a.err_flag = err;
-    return a;
-}
-
-// the pool of column col as the kernels and the twins take it (n_rows == 0: the column has none)
-static FrKeyPool key_pool_of(const fr_ctx *c, int col) {
-    const fr_ctx::KeySpace &k = c->key_spaces[(size_t)col];
-    return FrKeyPool{k.pool_bits.p, k.pool_free.p, k.pool_first, k.pool_rows};
-}
-
-// An erase on a column with a pool gives the rows back (keyadmit_release_kernel of libfleetrec_admit.so; frc_release_keys); without one it is
-// keymap_erase_kernel (frc_erase_keys), as ever.  -> the twin's bits on the CPU back-end, the launch's hipError_t value on the device.
-static int key_erase_run(fr_ctx *c, int col, int n, const int64_t *keys, int *err, hipStream_t s) {
-    const FrKeyPool pool = key_pool_of(c, col);
-    if (pool.n_rows > 0) {
-        const FrKeyReleaseArgs r{c->h_key_cols[(size_t)col], pool, n, keys, err};
-        return c->cpu ? frc_release_keys(r) : fr_keyadmit_release_launch(&r, (void *)s);
-    }
-    const FrKeyEraseArgs a = key_erase_args(c, col, n, keys, err);
-    return c->cpu ? frc_erase_keys(a) : fr_keymap_erase_launch(&a, (void *)s);
-}
-
-extern "C" int fr_worker_erase_keys(fr_worker *w, int col, int n, const int64_t *d_keys) {
-    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
-    fr_ctx *c = w->ctx;
-    FR_TRY(key_erase_check(c, col, n, d_keys, "fr_worker_erase_keys"));
-    if (n == 0) return FR_OK;
-    if ((uintptr_t)d_keys % 8) FR_FAIL(FR_ERR_INVALID, "fr_worker_erase_keys: d_keys must be 8-byte aligned");
-    int queued = 0;
-    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
-    if (queued > 0 || w->hr.staged)
-        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then erase");
-    if (c->cpu) {   // computed before the call returns, one writer at a time; a -1 key waits in c_err for fr_worker_sync
-        std::lock_guard<std::mutex> lk(c->lp_mutex);
-        const int bad = key_erase_run(c, col, n, d_keys, nullptr, nullptr);
-        if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
-        return FR_OK;
-    }
-    FR_SET_DEVICE(c);
-    FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the erase: whatever they read was resolved against the old map
-    const int e = key_erase_run(c, col, n, d_keys, w->d_err, w->stream);
-    if (e) FR_FAIL(FR_ERR_HIP, "the key erase launch failed: %s", hipGetErrorString((hipError_t)e));
-    w->in_flight = true;
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_erase_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_erase_check(ctx, col, n, h_keys, "fr_ctx_erase_keys"));
-    if (n == 0) return FR_OK;
-    if ((uintptr_t)h_keys % 8) FR_FAIL(FR_ERR_INVALID, "fr_ctx_erase_keys: h_keys must be 8-byte aligned");
-    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_put_keys's
-    if (ctx->cpu) {
-        const int bad = key_erase_run(ctx, col, n, h_keys, nullptr, nullptr);
-        return bad ? index_range_fail(bad) : FR_OK;
-    }
-    FR_SET_DEVICE(ctx);
-    if (!ctx->h_up_err) {
-        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
-        *ctx->h_up_err = 0;
-        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
-    }
-    FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
-    FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
-    const int e = key_erase_run(ctx, col, n, ctx->d_kp_keys, ctx->d_up_err, ctx->setup_stream);
-    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
-    if (e) FR_FAIL(FR_ERR_HIP, "the key erase launch failed: %s", hipGetErrorString((hipError_t)e));
-    const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
-    return bad ? index_range_fail(bad) : FR_OK;
-}
-
-// One walk of column col's map (under key_mutex) on the set-up stream, waited for: counts[3] are zeroed first and read back.  The CPU back-end: the twin.
-static int key_walk(fr_ctx *c, FrKeyWalkArgs a, unsigned long long counts[3]) {
-    counts[0] = counts[1] = counts[2] = 0;
-    if (c->cpu) {
-        a.counts = counts;
-        frc_walk_keys(a);
-        return FR_OK;
-    }
-    unsigned long long *d = c->d_key_walk.p;   // (made with the key spaces: no call of the life cycle changes what the context holds besides its maps)
-    FR_HIP(hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), c->setup_stream));
-    a.counts = d, a.max_blocks = 4 * (c->n_cu > 0 ? c->n_cu : 256);
-    const int e = fr_keymap_walk_launch(&a, (void *)c->setup_stream);
-    if (e) {
-        (void)hipStreamSynchronize(c->setup_stream);
-        FR_FAIL(FR_ERR_HIP, "the key-map walk launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    FR_HIP(hipMemcpyAsync(counts, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->setup_stream));
-    FR_HIP(hipStreamSynchronize(c->setup_stream));
-    return FR_OK;
-}
-
-// what the three read-side calls share: the column is MAPPED, the device is idle
-static int key_map_ready(fr_ctx *c, int col, const char *who) {
-    FR_TRY(key_col_check(c, col, who));
-    if (c->key_spaces.empty() || c->key_spaces[(size_t)col].mode != FR_KEYS_MAPPED)
-        FR_FAIL(FR_ERR_STATE, "%s: column %d has no map: call fr_ctx_set_key_space(ctx, %d, FR_KEYS_MAPPED, ...) first", who, col, col);
-    if (!c->cpu) {
-        FR_SET_DEVICE(c);
-        FR_HIP(hipDeviceSynchronize());
-    }
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_key_space_stats(fr_ctx *ctx, int col, int64_t *slots, int64_t *occupied, int64_t *live, int64_t *probe_sum) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    std::lock_guard<std::mutex> lk(ctx->key_mutex);
-    FR_TRY(key_map_ready(ctx, col, "fr_ctx_key_space_stats"));
-    FrKeyWalkArgs a{};
-    a.col = ctx->h_key_cols[(size_t)col], a.sink = FR_KEYWALK_COUNT;
-    unsigned long long n[3];
-    FR_TRY(key_walk(ctx, a, n));
-    if (slots) *slots = (int64_t)a.col.mask + 1;
-    if (occupied) *occupied = (int64_t)n[0];
-    if (live) *live = (int64_t)n[1];
-    if (probe_sum) *probe_sum = (int64_t)n[2];
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_export_keys(fr_ctx *ctx, int col, int64_t cap, int64_t *h_keys, int32_t *h_rows, int64_t *n_out) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    if (n_out) *n_out = 0;
-    if (cap < 0) FR_FAIL(FR_ERR_INVALID, "fr_ctx_export_keys: cap = %lld", (long long)cap);
-    if (cap > 0 && (!h_keys || !h_rows)) FR_FAIL(FR_ERR_INVALID, "fr_ctx_export_keys: h_keys / h_rows is NULL with cap = %lld", (long long)cap);
-    std::lock_guard<std::mutex> lk(ctx->key_mutex);
-    FR_TRY(key_map_ready(ctx, col, "fr_ctx_export_keys"));
-    FrKeyWalkArgs a{};
-    a.col = ctx->h_key_cols[(size_t)col];
-    unsigned long long n[3];
-    a.sink = FR_KEYWALK_COUNT;   // the size first: nothing is written unless everything fits
-    FR_TRY(key_walk(ctx, a, n));
-    const uint64_t live = n[1];
-    if (n_out) *n_out = (int64_t)live;
-    if ((uint64_t)cap < live) FR_FAIL(FR_ERR_INVALID, "fr_ctx_export_keys: the map of column %d holds %llu live pairs, cap is %lld (nothing was written)", col, (unsigned long long)live, (long long)cap);
-    if (live == 0) return FR_OK;
-    a.sink = FR_KEYWALK_EXPORT, a.cap = live;   // (no put is in flight: the device was synchronised and the caller holds the map still)
-    if (ctx->cpu) {
-        a.out_keys = h_keys, a.out_rows = h_rows;
-        return key_walk(ctx, a, n);
-    }
-    FrBuf<int64_t> d_keys;
-    FrBuf<int32_t> d_rows;
-    FR_TRY(d_keys.alloc(FrMem::DEVICE, (size_t)live, "key export keys"));
-    FR_TRY(d_rows.alloc(FrMem::DEVICE, (size_t)live, "key export rows"));
-    a.out_keys = d_keys.p, a.out_rows = d_rows.p;
-    FR_TRY(key_walk(ctx, a, n));
-    if (n[0] != live) FR_FAIL(FR_ERR_STATE, "fr_ctx_export_keys: the map of column %d changed during the call (%llu live pairs, then %llu): a put or erase is in flight", col, (unsigned long long)live, n[0]);
-    FR_HIP(hipMemcpy(h_keys, d_keys.p, (size_t)live * sizeof(int64_t), hipMemcpyDeviceToHost));
-    FR_HIP(hipMemcpy(h_rows, d_rows.p, (size_t)live * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_rebuild_key_space(fr_ctx *ctx, int col, uint64_t seed, int64_t max_keys) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_col_check(ctx, col, "fr_ctx_rebuild_key_space"));
-    if (max_keys < 1 || max_keys > (1ll << 30)) FR_FAIL(FR_ERR_INVALID, "fr_ctx_rebuild_key_space: max_keys %lld outside [1, 2^30]", (long long)max_keys);
-    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_rebuild_key_space: keyed lookups are not available on a sharded context (%d shards)", ctx->n_shards);
-    FR_TRY(pooling_busy(ctx, "fr_ctx_rebuild_key_space"));
-    std::lock_guard<std::mutex> lk(ctx->key_mutex);
-    FR_TRY(key_map_ready(ctx, col, "fr_ctx_rebuild_key_space"));
-    fr_ctx::KeySpace &old = ctx->key_spaces[(size_t)col];
-    FrKeyWalkArgs a{};
-    a.col = ctx->h_key_cols[(size_t)col], a.sink = FR_KEYWALK_COUNT;
-    unsigned long long n[3];
-    FR_TRY(key_walk(ctx, a, n));
-    const uint64_t live = n[1];
-    if ((uint64_t)max_keys < live) FR_FAIL(FR_ERR_INVALID, "fr_ctx_rebuild_key_space: max_keys %lld is below the %llu live keys of column %d", (long long)max_keys, (unsigned long long)live, col);
-    fr_ctx::KeySpace next;   // (whatever fails from here on: `next` releases the new map, the old one stays as it was)
-    next.mode = FR_KEYS_MAPPED, next.seed = seed, next.max_keys = max_keys, next.miss_row = old.miss_row;
-    const uint64_t slots = fr_key_slots((uint64_t)max_keys);
-    FR_TRY(next.slots.alloc(fr_mem_kind(ctx, FrMem::DEVICE), (size_t)slots, "key map"));
-    FrKeyFillArgs f{next.slots.p, slots, old.miss_row};
-    if (ctx->cpu) {
-        frc_fill_keys(f);
-    } else {
-        const int e = fr_key_fill_launch(&f, (void *)ctx->setup_stream);   // (the walk below follows it on the same stream)
-        if (e) {
-            (void)hipStreamSynchronize(ctx->setup_stream);
-            FR_FAIL(FR_ERR_HIP, "the key map's fill launch failed: %s", hipGetErrorString((hipError_t)e));
-        }
-    }
-    a.sink = FR_KEYWALK_REHASH, a.dst = a.col;
-    a.dst.seed = seed, a.dst.slots = next.slots.p, a.dst.mask = (uint32_t)(slots - 1);
-    FR_TRY(key_walk(ctx, a, n));
-    if (n[0] != live) FR_FAIL(FR_ERR_HIP, "fr_ctx_rebuild_key_space: %llu of the %llu live pairs of column %d reached the new map (the old map stays)", n[0], (unsigned long long)live, col);
-    const uint32_t count = (uint32_t)live;
-    if (ctx->cpu) ctx->d_key_counts[col] = count;
-    else FR_HIP(hipMemcpy(ctx->d_key_counts + col, &count, sizeof(count), hipMemcpyHostToDevice));
-    next.pool_first = old.pool_first, next.pool_rows = old.pool_rows;   // the row pool goes with the live keys: they keep their rows
-    next.pool_bits.swap(old.pool_bits), next.pool_free.swap(old.pool_free);
-    std::swap(old, next);   // (no worker has work in flight: the old map is released with `next`)
-    return key_cols_upload(ctx);
-}
-
-// ---- row pools: admitting ids (fleetrec_serving.h) --------------------------------------------------------------------------------------------------
-// The kernels are the sixth companion code object's (fr_keyadmit.hip -> libfleetrec_admit.so); the CPU twins are frc_admit_keys / frc_release_keys /
-// frc_mark_pool.  The pool's bitmap and counter belong to the column's KeySpace: a rebuild hands them on, fr_ctx_set_key_space drops them.
-extern "C" int fr_ctx_set_row_pool(fr_ctx *ctx, int col, int32_t first_row, int32_t n_rows) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_col_check(ctx, col, "fr_ctx_set_row_pool"));
-    if (n_rows < 0) FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_row_pool: n_rows = %d", n_rows);
-    const uint32_t range = key_col_range(ctx, col);
-    if (n_rows > 0 && (first_row < 0 || (int64_t)first_row + n_rows > (int64_t)range))
-        FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_row_pool: rows [%d, %lld) are not inside the %u rows of column %d", first_row, (long long)first_row + n_rows, range, col);
-    if (ctx->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_row_pool: keyed lookups are not available on a sharded context (%d shards)", ctx->n_shards);
-    FR_TRY(pooling_busy(ctx, "fr_ctx_set_row_pool"));
-    std::lock_guard<std::mutex> lk(ctx->key_mutex);
-    FR_TRY(key_map_ready(ctx, col, "fr_ctx_set_row_pool"));
-    fr_ctx::KeySpace &k = ctx->key_spaces[(size_t)col];
-    if (n_rows == 0) {   // drop the pool
-        k.pool_first = k.pool_rows = 0;
-        k.pool_bits.reset(), k.pool_free.reset();
-        return FR_OK;
-    }
-    if (k.miss_row >= first_row && k.miss_row - first_row < n_rows)
-        FR_FAIL(FR_ERR_INVALID, "fr_ctx_set_row_pool: rows [%d, %d) contain the column's miss_row %d", first_row, first_row + n_rows, k.miss_row);
-    // the free set is derived from the map as it stands: whatever fails from here on, the column keeps the pool it had
-    FrBuf<uint32_t> bits;
-    FrBuf<int32_t> free_rows;
-    const uint32_t words = fr_key_pool_words(n_rows), pad = fr_key_pool_pad(n_rows);
-    FR_TRY(bits.alloc(fr_mem_kind(ctx, FrMem::DEVICE), words, "row-pool bitmap"));
-    FR_TRY(free_rows.alloc(fr_mem_kind(ctx, FrMem::DEVICE), 1, "row-pool counter"));
-    FrKeyMarkArgs m{ctx->h_key_cols[(size_t)col], FrKeyPool{bits.p, free_rows.p, first_row, n_rows}, 0};
-    if (ctx->cpu) {
-        memset(bits.p, 0, words * sizeof(uint32_t));
-        bits[words - 1] = pad, *free_rows = n_rows;
-        frc_mark_pool(m);
-    } else {
-        hipStream_t s = ctx->setup_stream;
-        hipError_t he = hipMemsetAsync(bits.p, 0, words * sizeof(uint32_t), s);
-        if (he == hipSuccess && pad) he = hipMemcpyAsync(bits.p + words - 1, &pad, sizeof(pad), hipMemcpyHostToDevice, s);
-        if (he == hipSuccess) he = hipMemcpyAsync(free_rows.p, &n_rows, sizeof(n_rows), hipMemcpyHostToDevice, s);
-        m.max_blocks = 4 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-        const int e = he == hipSuccess ? fr_keyadmit_mark_launch(&m, (void *)s) : (int)he;
-        const hipError_t se = hipStreamSynchronize(s);   // (before `bits`, `pad` and `n_rows` leave)
-        if (e) FR_FAIL(FR_ERR_HIP, "the row pool's mark launch failed: %s", hipGetErrorString((hipError_t)e));
-        FR_HIP(se);
-    }
-    k.pool_first = first_row, k.pool_rows = n_rows;
-    k.pool_bits.swap(bits), k.pool_free.swap(free_rows);   // (no worker has work in flight: the old bitmap is released with `bits`)
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_row_pool(fr_ctx *ctx, int col, int32_t *first_row, int32_t *n_rows, int64_t *free_rows) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_col_check(ctx, col, "fr_ctx_row_pool"));
-    const fr_ctx::KeySpace none{};
-    const fr_ctx::KeySpace &k = ctx->key_spaces.empty() ? none : ctx->key_spaces[(size_t)col];
-    int32_t n = 0;
-    if (k.pool_rows > 0) {
-        if (ctx->cpu) {
-            n = __atomic_load_n(k.pool_free.p, __ATOMIC_ACQUIRE);
-        } else {
-            FR_SET_DEVICE(ctx);
-            FR_HIP(hipDeviceSynchronize());
-            FR_HIP(hipMemcpy(&n, k.pool_free.p, sizeof(n), hipMemcpyDeviceToHost));
-        }
-    }
-    if (first_row) *first_row = k.pool_first;
-    if (n_rows) *n_rows = k.pool_rows;
-    if (free_rows) *free_rows = (int64_t)n;
-    return FR_OK;
-}
-
-static int key_admit_check(fr_ctx *c, int col, int n, const void *keys, const void *rows, const char *who) {
-    FR_TRY(key_put_check(c, col, n, keys, rows, who));
-    if (c->key_spaces[(size_t)col].pool_rows <= 0) FR_FAIL(FR_ERR_STATE, "%s: column %d has no row pool: call fr_ctx_set_row_pool(ctx, %d, first_row, n_rows) first", who, col, col);
-    return FR_OK;
-}
-
-static FrKeyAdmitArgs key_admit_args(fr_ctx *c, int col, int n, const int64_t *keys, int32_t *rows, int *err) {
-    FrKeyAdmitArgs a{};
-    a.col = c->h_key_cols[(size_t)col], a.pool = key_pool_of(c, col), a.n_keys = c->d_key_counts + col, a.max_keys = (uint32_t)c->key_spaces[(size_t)col].max_keys;
-    a.n = n, a.keys = keys, a.rows_out = rows, a.err_flag = err;
-    return a;
-}
-
-// The launches of one admit on stream s: per piece of at most 2^20 keys the piece's own table is filled (key_fill_kernel), keyadmit_admit_kernel elects
-// one occurrence of every key and admits it, keyadmit_settle_kernel hands its row to the others.  A key listed in two pieces is live by the second.
-static int key_admit_enqueue(fr_ctx *c, int col, int n, const int64_t *keys, int32_t *rows, int *err, FrBuf<FrKeySlot> &tab, hipStream_t s) {
-    constexpr int PIECE = 1 << 20;
-    FR_TRY(tab.grow(FrMem::DEVICE, (size_t)fr_key_slots((uint64_t)(n < PIECE ? n : PIECE)), "key-admit table"));
-    for (int at = 0; at < n; at += PIECE) {
-        const int m = n - at < PIECE ? n - at : PIECE;
-        const uint64_t slots = fr_key_slots((uint64_t)m);
-        const FrKeyFillArgs f{tab.p, slots, FR_KEYS_NO_ROW};
-        int e = fr_key_fill_launch(&f, (void *)s);
-        FrKeyAdmitArgs a = key_admit_args(c, col, m, keys + at, rows + at, err);
-        a.tab = tab.p, a.tab_mask = (uint32_t)(slots - 1);
-        if (!e) e = fr_keyadmit_admit_launch(&a, (void *)s);
-        if (!e) e = fr_keyadmit_settle_launch(&a, (void *)s);
-        if (e) FR_FAIL(FR_ERR_HIP, "the key admit launch failed: %s", hipGetErrorString((hipError_t)e));
-    }
-    return FR_OK;
-}
-
-extern "C" int fr_worker_admit_keys(fr_worker *w, int col, int n, const int64_t *d_keys, int32_t *d_rows_out) {
-    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
-    fr_ctx *c = w->ctx;
-    FR_TRY(key_admit_check(c, col, n, d_keys, d_rows_out, "fr_worker_admit_keys"));
-    if (n == 0) return FR_OK;
-    if ((uintptr_t)d_keys % 8 || (uintptr_t)d_rows_out % 4) FR_FAIL(FR_ERR_INVALID, "fr_worker_admit_keys: d_keys must be 8-byte aligned, d_rows_out 4-byte aligned");
-    int queued = 0;
-    (void)fr_worker_host_pending(w, &queued, nullptr, nullptr);
-    if (queued > 0 || w->hr.staged)
-        FR_FAIL(FR_ERR_STATE, "host-fed batches are queued on this worker (fr_worker_push_host / push_staged): flush first (fr_worker_flush), then admit");
-    if (c->cpu) {   // computed before the call returns, one writer at a time; what was not applied waits in c_err for fr_worker_sync
-        std::lock_guard<std::mutex> lk(c->lp_mutex);
-        const int bad = frc_admit_keys(key_admit_args(c, col, n, d_keys, d_rows_out, nullptr));
-        if (bad) __atomic_fetch_or(&w->c_err, bad, __ATOMIC_ACQ_REL);
-        return FR_OK;
-    }
-    FR_SET_DEVICE(c);
-    FR_TRY(fused_flush(w));   // batches queued for a fused launch were pushed BEFORE the admit: whatever they read was resolved against the old map
-    FR_TRY(key_admit_enqueue(c, col, n, d_keys, d_rows_out, w->d_err, w->d_admit_tab, w->stream));
-    w->in_flight = true;
-    return FR_OK;
-}
-
-extern "C" int fr_ctx_admit_keys(fr_ctx *ctx, int col, int n, const int64_t *h_keys, int32_t *h_rows_out) {
-    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
-    FR_TRY(key_admit_check(ctx, col, n, h_keys, h_rows_out, "fr_ctx_admit_keys"));
-    if (n == 0) return FR_OK;
-    if ((uintptr_t)h_keys % 8 || (uintptr_t)h_rows_out % 4) FR_FAIL(FR_ERR_INVALID, "fr_ctx_admit_keys: h_keys must be 8-byte aligned, h_rows_out 4-byte aligned");
-    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // one writer at a time; the set-up stream, the staging and the status word are fr_ctx_put_keys's
-    if (ctx->cpu) {
-        const int bad = frc_admit_keys(key_admit_args(ctx, col, n, h_keys, h_rows_out, nullptr));
-        return bad ? index_range_fail(bad) : FR_OK;
-    }
-    FR_SET_DEVICE(ctx);
-    if (!ctx->h_up_err) {
-        FR_TRY(ctx->h_up_err.alloc(FrMem::PINNED_MAPPED, 1, "row-update status word"));
-        *ctx->h_up_err = 0;
-        FR_HIP(hipHostGetDevicePointer((void **)&ctx->d_up_err, ctx->h_up_err, 0));
-    }
-    FR_TRY(ctx->d_kp_keys.grow(FrMem::DEVICE, (size_t)n, "key-put keys"));
-    FR_TRY(ctx->d_kp_rows.grow(FrMem::DEVICE, (size_t)n, "key-put rows"));
-    FR_HIP(hipMemcpyAsync(ctx->d_kp_keys, h_keys, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
-    const int rc = key_admit_enqueue(ctx, col, n, ctx->d_kp_keys, ctx->d_kp_rows, ctx->d_up_err, ctx->d_ka_tab, ctx->setup_stream);
-    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
-    if (rc) return rc;
-    FR_HIP(hipMemcpy(h_rows_out, ctx->d_kp_rows, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    const int bad = __atomic_exchange_n(ctx->h_up_err.p, 0, __ATOMIC_ACQ_REL);
-    return bad ? index_range_fail(bad) : FR_OK;
-}
-
-// The word -> column tables of the six forms ([rows_kind][pooled]) for the pooling and the split as they stand, made again when either has changed
-// since they were made (both change only while no worker has work in flight, so no launch reads the tables being replaced).  Under key_mutex.
-static int key_tables_ensure(fr_ctx *c) {
-    if (c->key_tab_made && c->key_tab_hots == c->pool_hots && c->key_tab_shared == c->req_shared) return FR_OK;
-    const size_t C = idx_cols(c);
-    const bool pool = c->pool_cols > 0, split = !c->req_shared.empty();
-    std::vector<uint16_t> all;
-    fr_ctx::KeyTable tab[3][2];
-    for (int kind = FR_KEY_ROWS_FULL; kind <= FR_KEY_ROWS_CANDIDATE; kind++)
-        for (int pooled = 0; pooled < 2; pooled++) {
-            if ((pooled && !pool) || (kind != FR_KEY_ROWS_FULL && !split)) continue;
-            tab[kind][pooled].first = all.size();
-            for (size_t col = 0; col < C; col++) {
-                if (kind != FR_KEY_ROWS_FULL && (c->req_shared[col] != 0) != (kind == FR_KEY_ROWS_REQUEST)) continue;
-                all.insert(all.end(), pooled ? (size_t)c->pool_hots[col] : 1, (uint16_t)col);
-            }
-            tab[kind][pooled].words = (int)(all.size() - tab[kind][pooled].first);
-        }
-    FrBuf<uint16_t> d;
-    FR_TRY(d.alloc(fr_mem_kind(c, FrMem::DEVICE), all.size() ? all.size() : 1, "key word tables"));
-    if (c->cpu) memcpy(d.p, all.data(), all.size() * sizeof(uint16_t));
-    else if (!all.empty()) FR_HIP(hipMemcpy(d.p, all.data(), all.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    c->d_key_wcol.swap(d);
-    memcpy(c->key_tab, tab, sizeof(tab));
-    c->key_tab_hots = c->pool_hots, c->key_tab_shared = c->req_shared, c->key_tab_made = true;
-    return FR_OK;
-}
-
-// the one launch (the CPU back-end: the twin, computed here)
-static int key_resolve_enqueue(fr_worker *w, int n_rows, int rows_kind, int pooled, const int64_t *keys, int32_t *out, const char *who) {
-    fr_ctx *c = w->ctx;
-    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "%s: keyed lookups are not available on a sharded context (%d shards)", who, c->n_shards);
-    if (rows_kind != FR_KEY_ROWS_FULL && c->req_shared.empty()) FR_FAIL(FR_ERR_STATE, "%s: request and candidate rows need a split: call fr_ctx_set_request_columns first", who);
-    if (pooled && c->pool_cols <= 0) FR_FAIL(FR_ERR_STATE, "%s: the pooled forms need pooling: call fr_ctx_set_pooling first", who);
-    if (!c->cpu) FR_SET_DEVICE(c);
-    FrKeyResolveArgs a{};
-    {
-        std::lock_guard<std::mutex> lk(c->key_mutex);
-        FR_TRY(key_spaces_init(c));
-        FR_TRY(key_tables_ensure(c));
-        const fr_ctx::KeyTable &t = c->key_tab[rows_kind][pooled];
-        a.W = t.words, a.wcol = c->d_key_wcol + t.first;
-    }
-    if (a.W <= 0) FR_FAIL(FR_ERR_STATE, "%s: the split leaves no word to this side of the form", who);
-    const uint64_t bound = (uint64_t)4000 << 20;
-    a.total = (uint64_t)n_rows * (uint64_t)a.W;
-    if (a.total * sizeof(int64_t) >= bound) FR_FAIL(FR_ERR_INVALID, "%s: %d rows of %d keys reach 4000 MiB", who, n_rows, a.W);
-    if (!w->d_key_miss) {   // the worker's first resolve
-        FR_TRY(w->d_key_miss.alloc(fr_mem_kind(c, FrMem::DEVICE), 1, "worker key misses"));
-        if (c->cpu) *w->d_key_miss = 0;
-        else FR_HIP(hipMemsetAsync(w->d_key_miss, 0, sizeof(unsigned long long), w->stream));   // in front of the launch, in stream order
-    }
-    a.keys = keys, a.out = out, a.misses = w->d_key_miss, a.n_cols = (int)idx_cols(c);
-    if (c->cpu) {
-        a.cols = c->h_key_cols.data();
-        frc_resolve_keys(a);
-        return FR_OK;
-    }
-    a.cols = c->d_key_cols, a.max_blocks = 8 * (c->n_cu > 0 ? c->n_cu : 256);
-    const int e = fr_key_resolve_launch(&a, (void *)w->stream);
-    if (e) FR_FAIL(FR_ERR_HIP, "the key resolve launch failed: %s", hipGetErrorString((hipError_t)e));
-    w->in_flight = true;
-    return FR_OK;
-}
-
-extern "C" int fr_worker_resolve_keys_device(fr_worker *w, int n_rows, int rows_kind, int pooled, const int64_t *d_keys, int32_t *d_idx_out) {
-    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
-    if (rows_kind < FR_KEY_ROWS_FULL || rows_kind > FR_KEY_ROWS_CANDIDATE) FR_FAIL(FR_ERR_INVALID, "rows_kind %d is none of FR_KEY_ROWS_FULL, _REQUEST, _CANDIDATE", rows_kind);
-    if (pooled != 0 && pooled != 1) FR_FAIL(FR_ERR_INVALID, "pooled = %d is neither 0 nor 1", pooled);
-    const int most = rows_kind == FR_KEY_ROWS_REQUEST ? (1 << 24) : w->max_batch;
-    if (n_rows < 1 || n_rows > most) FR_FAIL(FR_ERR_INVALID, "n_rows = %d outside [1, %d]", n_rows, most);
-    if (!d_keys || !d_idx_out) FR_FAIL(FR_ERR_INVALID, "d_keys / d_idx_out is NULL");
-    if ((uintptr_t)d_keys % 8 || (uintptr_t)d_idx_out % 4) FR_FAIL(FR_ERR_INVALID, "d_keys must be 8-byte aligned, d_idx_out 4-byte aligned");
-    return key_resolve_enqueue(w, n_rows, rows_kind, pooled, d_keys, d_idx_out, "fr_worker_resolve_keys_device");
-}
-
-extern "C" int64_t *fr_worker_key_ptr(fr_worker *w) { return w ? w->h_keys.p : nullptr; }
-
+// ---- keyed lookups (fleetrec_serving.h): fr_keyspace.cpp; the host form's submit is here, beside the submit paths it calls ---------------------------
 extern "C" int fr_worker_submit_keyed(fr_worker *w, int batch, int pooled) {
     int rc = check_ready(w, batch, true, true);
     if (rc) return rc;
@@ -3693,36 +3056,16 @@ extern "C" int fr_worker_submit_keyed(fr_worker *w, int batch, int pooled) {
         FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
     }
     if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
-    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "fr_worker_submit_keyed: keyed lookups are not available on a sharded context (%d shards)", c->n_shards);
+    FR_TRY(fr_key_unsharded(c, "fr_worker_submit_keyed"));
     if (!c->cpu) FR_SET_DEVICE(c);
     // the resolve reads the pinned keys in place and writes the worker's device index buffer; the unchanged submit runs behind it
-    rc = key_resolve_enqueue(w, batch, FR_KEY_ROWS_FULL, pooled ? 1 : 0, w->h_keys, w->d_idx, "fr_worker_submit_keyed");
+    rc = fr_key_resolve_enqueue(w, batch, FR_KEY_ROWS_FULL, pooled ? 1 : 0, w->h_keys, w->d_idx, "fr_worker_submit_keyed");
     if (rc) return rc;
     const float *dense = c->model.dense_len ? w->h_dense.p : nullptr;
     if (pooled) rc = submit_pooled_impl(w, weighted ? pooled_batch_weighted(batch, w->d_idx, w->h_pool_w, dense) : FrPooledBatch{batch, w->d_idx, nullptr, dense}, w->h_score);
     else rc = launch_pipeline(w, batch, w->d_idx, dense, w->h_score);
     if (rc) return rc;
     w->in_flight = true, w->host_batch = batch;   // (fr_worker_topk ranks it)
-    return FR_OK;
-}
-
-extern "C" int fr_worker_key_misses(fr_worker *w, uint64_t *misses, int reset) {
-    if (!w || !misses) FR_FAIL(FR_ERR_INVALID, "NULL argument");
-    *misses = 0;
-    if (!w->d_key_miss) return FR_OK;   // the worker has resolved nothing yet
-    if (w->ctx->cpu) {
-        *misses = reset ? __atomic_exchange_n(w->d_key_miss.p, 0ull, __ATOMIC_ACQ_REL) : __atomic_load_n(w->d_key_miss.p, __ATOMIC_ACQUIRE);
-        return FR_OK;
-    }
-    FR_SET_DEVICE(w->ctx);
-    FR_HIP(hipStreamSynchronize(w->stream));
-    unsigned long long v = 0;
-    FR_HIP(hipMemcpy(&v, w->d_key_miss, sizeof(v), hipMemcpyDeviceToHost));
-    if (reset) {
-        FR_HIP(hipMemsetAsync(w->d_key_miss, 0, sizeof(v), w->stream));
-        FR_HIP(hipStreamSynchronize(w->stream));
-    }
-    *misses = (uint64_t)v;
     return FR_OK;
 }
 
@@ -3735,7 +3078,7 @@ extern "C" int fr_worker_flush(fr_worker *w) {
         int rc = host_block_launch(w);
         if (rc) return rc;
     }
-    return fused_flush(w);
+    return fr_fused_flush(w);
 }
 
 // Hand out the scores of the host-fed blocks that have finished, oldest first, WITHOUT waiting for the others; *delivered = host-fed
@@ -3787,7 +3130,7 @@ extern "C" int fr_worker_sync(fr_worker *w) {
         w->in_flight = false;
         if (crc) return crc;
         const int bits = __atomic_exchange_n(&w->c_err, 0, __ATOMIC_ACQ_REL);
-        return bits ? index_range_fail(bits) : FR_OK;
+        return bits ? fr_index_range_fail(bits) : FR_OK;
     }
     FR_SET_DEVICE(w->ctx);
     if (w->sh_comm && w->sh_host_stream) {
@@ -3800,7 +3143,7 @@ extern "C" int fr_worker_sync(fr_worker *w) {
         }
     }
     int frc = host_ring_drain(w);  // host-fed blocks: launch the partial one, deliver every block's scores
-    if (!frc) frc = fused_flush(w);  // launch batches still queued by fr_worker_push_device
+    if (!frc) frc = fr_fused_flush(w);  // launch batches still queued by fr_worker_push_device
     if (!frc) frc = pipeline_flush(w);  // drain the stage pipeline
     if (frc) {
         fr_comm_forget(w);   // a sharded step in flight keeps no hold on its communicator past a failed sync
@@ -3818,7 +3161,7 @@ extern "C" int fr_worker_sync(fr_worker *w) {
         if (w->tk_dst_sc) memcpy(w->tk_dst_sc, w->h_tk_sc, w->tk_count * sizeof(float));
     }
     const int bits = __atomic_exchange_n(w->h_err, 0, __ATOMIC_ACQ_REL);   // (bit 0: the lookups'; the others: a key put's, FR_KEYS_ERR_*)
-    return bits ? index_range_fail(bits) : FR_OK;
+    return bits ? fr_index_range_fail(bits) : FR_OK;
 }
 
 extern "C" int fr_worker_timer_start(fr_worker *w) {

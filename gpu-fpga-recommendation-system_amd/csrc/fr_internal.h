@@ -249,7 +249,7 @@ struct FrFusedArgs {
     unsigned long long *stamps;  // diagnostics only (NULL normally): 16 s_memrealtime stamps per workgroup
     // per-layer epilogues (FC1, FC2, FC3, output).  All {NULL, 0} without fr_ctx_set_epilogue: the launchers run fr_fused_tile_*_kernel.  With one, EVERY
     // bias pointer is set (a layer without a bias points at -0.0f values) and the launchers run the branch-free fr_epi_tile_*_kernel forms.
-    // fr_fused_tile_hs_kernel does not read them: a context with an epilogue never launches it (fused_flush, fr_api.cpp)
+    // fr_fused_tile_hs_kernel does not read them: a context with an epilogue never launches it (fr_fused_flush, fr_api.cpp)
     FrEpi epi[4];
 };
 
@@ -508,6 +508,10 @@ struct fr_ctx {
         int32_t pool_first = 0, pool_rows = 0;
         FrBuf<uint32_t> pool_bits;         // one bit per pool row, set = taken
         FrBuf<int32_t> pool_free;          // [1]: the free rows
+        // (moved by std::swap in more than one file: kept inside the library, like the destructors, so that its export list stays what it was)
+        KeySpace() = default;
+        __attribute__((visibility("hidden"))) KeySpace(KeySpace &&) = default;
+        __attribute__((visibility("hidden"))) KeySpace &operator=(KeySpace &&) = default;
     };
     std::vector<KeySpace> key_spaces;      // [index columns]; empty until the first fr_ctx_set_key_space
     bool keyed = false;
@@ -742,6 +746,24 @@ int frc_release_keys(const FrKeyReleaseArgs &a);
 void frc_mark_pool(const FrKeyMarkArgs &a);
 void frc_fc_chain(const int32_t fc[5], const float *const w[4], const FrEpi epi[4], const float *X, int batch, float *scratch, float *scores);
 void frc_slices_to_records(const float *gathered, int n_shards, int batch_total, int slice_padded, const int *offs, const int *lens, int item0, int n_items, float *X, int K);
+// every entry point selects its context's device first; a CPU context (device = -1, fr_cpu.cpp) has none
+#define FR_SET_DEVICE(ctx_)                                    \
+    do {                                                       \
+        if (!(ctx_)->cpu) FR_HIP(hipSetDevice((ctx_)->device)); \
+    } while (0)
+
+// ---- the seams between fr_api.cpp and fr_keyspace.cpp -------------------------------------------------------------------------------
+// fr_api.cpp's, called by the keyed code:
+int fr_pooling_busy(fr_ctx *ctx, const char *who);           // refuses while a worker of the context has work in flight
+int fr_fused_flush(fr_worker *w);                            // launches the batches queued for a fused launch, without waiting
+int fr_host_fed_queued(fr_worker *w, const char *verb);      // refuses while host-fed batches wait in a block not launched yet: "... flush first ..., then <verb>"
+int fr_up_err_ensure(fr_ctx *ctx);                           // the set-up stream's status word (h_up_err / d_up_err), made on first use; under lp_mutex
+int fr_up_err_take(fr_ctx *ctx);                             // ... read and cleared
+// fr_keyspace.cpp's, called by fr_worker_sync and fr_worker_submit_keyed:
+int fr_index_range_fail(int bits);                           // FR_ERR_INDEX_RANGE with the text of a status word's bits (bit 0: a lookup; FR_KEYS_ERR_*)
+int fr_key_unsharded(const fr_ctx *c, const char *who);      // refuses a sharded context
+int fr_key_resolve_enqueue(fr_worker *w, int n_rows, int rows_kind, int pooled, const int64_t *keys, int32_t *out, const char *who);   // the one resolve launch
+
 #define FR_NOT_ON_CPU(ctx_, what)                                                                                                  \
     do {                                                                                                                           \
         if ((ctx_)->cpu) FR_FAIL(FR_ERR_STATE, "%s is not available on the CPU back-end (device = -1): fp32 submit / sync / gather_only / fc_only only", what); \

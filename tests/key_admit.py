@@ -6,7 +6,6 @@ the counter equals the size of the set -- and each invariant is exact; on the CP
 first).  The model is keyed.py's narrow one with a longer middle table: a call of 301 new keys needs 301 rows."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -625,31 +624,9 @@ KERNELS = ("keyadmit_admit_kernel", "keyadmit_mark_kernel", "keyadmit_release_ke
 
 
 def check_companion(fr):
-    """libfleetrec_admit.so: exports only its launchers, imports neither getenv nor any fr_* symbol, is named by libfleetrec.so with $ORIGIN; with
-    llvm-readelf there, its kernels are exactly the keyadmit_ ones, spill no register, have no private segment and need at most 64 VGPRs, and no
-    keyadmit_ kernel sits in any other library."""
-    import importlib.util
-    assert os.path.exists(ADMIT_LIB), "the row-pool companion code object has not been built"
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", ADMIT_LIB]).decode()
-    assert "getenv" not in und, "libfleetrec_admit.so imports getenv"
-    assert not [l for l in und.splitlines() if l.split()[-1].startswith(("fr_", "frc_"))], "libfleetrec_admit.so calls into the library"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", ADMIT_LIB]).decode()
-    assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == LAUNCHERS, out
-    need = subprocess.check_output(["readelf", "-d", fr.LIB_PATH]).decode()
-    assert "libfleetrec_admit.so" in need and "$ORIGIN" in need, "libfleetrec.so does not link the companion through $ORIGIN"
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        return                                                                                   # (the kernel list and the register checks need it)
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    recs = kr.kernel_records(ADMIT_LIB)
-    names = [r["name"] for r in recs]
-    assert len(names) == len(KERNELS) and all(sum(k in n for n in names) == 1 for k in KERNELS), names
-    for r in recs:
-        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
-        assert r["vgpr_count"] <= 64, r                                                          # eight waves per SIMD, as the sibling kernels
-    for other in (fr.LIB_PATH, K.KEYS_LIB, KL.KEYMAINT_LIB):
-        assert not [r["name"] for r in kr.kernel_records(other) if "keyadmit_" in r["name"]], "a keyadmit_ kernel inside %s" % other
+    """libfleetrec_admit.so (companion.check_companion)"""
+    import companion
+    companion.check_companion(fr, ADMIT_LIB, LAUNCHERS, dict.fromkeys(KERNELS, 1), "keyadmit_", (fr.LIB_PATH, K.KEYS_LIB, KL.KEYMAINT_LIB))
 
 
 # ---- 12. lifetime ----------------------------------------------------------------------------------------------------------------------------------------------------------

@@ -5,7 +5,6 @@ items whose row is not miss_row -- and, for probe_sum, a replay of linear probin
 set whatever the insertion order, so the replay inserts in dict order).  Every comparison is exact."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -580,32 +579,7 @@ def lifetime_cycle(fr, m, device, rng, live_bytes=None):
 # ---- 10. the companion code object ----------------------------------------------------------------------------------------------------------------------
 
 def check_companion(fr):
-    """libfleetrec_keymaint.so: exports only its fr_* launchers, does not import getenv, is named by libfleetrec.so with $ORIGIN; its kernels are the
-    keymap_ ones, spill no register and have no private segment (that part only when llvm-readelf is there).  libfleetrec_keys.so is what it was."""
-    import importlib.util
-    assert os.path.exists(KEYMAINT_LIB), "the key-map maintenance companion code object has not been built"
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", KEYMAINT_LIB]).decode()
-    assert "getenv" not in und, "libfleetrec_keymaint.so imports getenv"
-    assert not [l for l in und.splitlines() if l.split()[-1].startswith(("fr_", "frc_"))], "libfleetrec_keymaint.so calls into the library"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", KEYMAINT_LIB]).decode()
-    exported_syms = [l.split()[-1] for l in out.splitlines() if " T " in l]
-    assert sorted(exported_syms) == ["fr_keymap_erase_launch", "fr_keymap_walk_launch"], exported_syms
-    need = subprocess.check_output(["readelf", "-d", fr.LIB_PATH]).decode()
-    assert "libfleetrec_keymaint.so" in need and "$ORIGIN" in need, "libfleetrec.so does not link the companion through $ORIGIN"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", K.KEYS_LIB]).decode()
-    assert sorted(l.split()[-1] for l in out.splitlines() if " T " in l) == ["fr_key_fill_launch", "fr_key_put_launch", "fr_key_resolve_launch"]
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        import pytest
-        pytest.skip("llvm-readelf not available: the kernel list and the register / scratch checks of libfleetrec_keymaint.so did not run")
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    recs = kr.kernel_records(KEYMAINT_LIB)
-    names = [r["name"] for r in recs]
-    count = {k: sum(k in n for n in names) for k in ("keymap_erase_kernel", "keymap_walk_kernel")}
-    assert count == {"keymap_erase_kernel": 1, "keymap_walk_kernel": 3} and len(names) == 4, names
-    for r in recs:
-        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
-        assert r["vgpr_count"] <= 64, r                      # eight waves per SIMD, as the sibling kernels
-    assert not [r["name"] for r in kr.kernel_records(fr.LIB_PATH) if "keymap_" in r["name"]], "a keymap_ kernel inside libfleetrec.so"
-    assert not [r["name"] for r in kr.kernel_records(K.KEYS_LIB) if "keymap_" in r["name"]], "a keymap_ kernel inside libfleetrec_keys.so"
+    """libfleetrec_keymaint.so (companion.check_companion); libfleetrec_keys.so exports what it did"""
+    import companion
+    assert companion.exported(K.KEYS_LIB) == K.KEYS_LAUNCHERS
+    companion.check_companion(fr, KEYMAINT_LIB, ["fr_keymap_erase_launch", "fr_keymap_walk_launch"], {"keymap_erase_kernel": 1, "keymap_walk_kernel": 3}, "keymap_", (fr.LIB_PATH, K.KEYS_LIB))

@@ -5,7 +5,6 @@ every special value among them -- so the reference is computed once per (column,
 np.array_equal; nothing here has a tolerance: the resolve produces integers, and everything behind it is the code that runs on pre-resolved rows."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 
@@ -629,32 +628,13 @@ def check_errors(fr, device):
 
 # ---- 9. the companion code object --------------------------------------------------------------------------------------------------------------------
 
+KEYS_LAUNCHERS = ["fr_key_fill_launch", "fr_key_put_launch", "fr_key_resolve_launch"]
+
+
 def check_companion(fr):
-    """libfleetrec_keys.so: exports only fr_*, does not import getenv, is named by libfleetrec.so with $ORIGIN; its kernels are the key_ ones, spill
-    no register and have no private segment (that part only when llvm-readelf is there)."""
-    import importlib.util
-    assert os.path.exists(KEYS_LIB), "the keys companion code object has not been built"
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", KEYS_LIB]).decode()
-    assert "getenv" not in und, "libfleetrec_keys.so imports getenv"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", KEYS_LIB]).decode()
-    exported = [l.split()[-1] for l in out.splitlines() if " T " in l]
-    assert sorted(exported) == ["fr_key_fill_launch", "fr_key_put_launch", "fr_key_resolve_launch"], exported
-    need = subprocess.check_output(["readelf", "-d", fr.LIB_PATH]).decode()
-    assert "libfleetrec_keys.so" in need and "$ORIGIN" in need, "libfleetrec.so does not link the keys companion through $ORIGIN"
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        import pytest
-        pytest.skip("llvm-readelf not available: the kernel list and the register / scratch checks of libfleetrec_keys.so did not run")
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    recs = kr.kernel_records(KEYS_LIB)
-    names = [r["name"] for r in recs]   # (mangled where llvm-cxxfilt is missing)
-    count = {k: sum(k in n for n in names) for k in ("key_fill_kernel", "key_put_kernel", "key_resolve_kernel")}
-    assert count == {"key_fill_kernel": 1, "key_put_kernel": 1, "key_resolve_kernel": 2} and len(names) == 4, names
-    for r in recs:
-        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
-        assert r["vgpr_count"] <= 64, r                      # eight waves per SIMD
-    assert not [r["name"] for r in kr.kernel_records(fr.LIB_PATH) if "key_" in r["name"]], "a key_ kernel inside libfleetrec.so"
+    """libfleetrec_keys.so (companion.check_companion)"""
+    import companion
+    companion.check_companion(fr, KEYS_LIB, KEYS_LAUNCHERS, {"key_fill_kernel": 1, "key_put_kernel": 1, "key_resolve_kernel": 2}, "key_", (fr.LIB_PATH,))
 
 
 # ---- 10. lifetime --------------------------------------------------------------------------------------------------------------------------------------

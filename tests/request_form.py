@@ -683,23 +683,6 @@ def check_server(fr, device, free_port_block):
 # ---- 9. the companion code object -------------------------------------------------------------------------------------------------------------------
 
 def check_companion(fr):
-    """libfleetrec_request.so: exports only fr_*, does not import getenv, is named by libfleetrec.so with $ORIGIN; its kernels spill no register and
-    have no private segment (that part only when llvm-readelf is there)."""
-    import importlib.util
-    assert os.path.exists(REQUEST_LIB), "the request companion code object has not been built"
-    und = subprocess.check_output(["nm", "-D", "--undefined-only", REQUEST_LIB]).decode()
-    assert "getenv" not in und, "libfleetrec_request.so imports getenv"
-    out = subprocess.check_output(["nm", "-D", "--defined-only", REQUEST_LIB]).decode()
-    exported = [l.split()[-1] for l in out.splitlines() if " T " in l]
-    assert exported and all(e.startswith("fr_") for e in exported), exported
-    need = subprocess.check_output(["readelf", "-d", fr.LIB_PATH]).decode()
-    assert "libfleetrec_request.so" in need and "$ORIGIN" in need, "libfleetrec.so does not link the request companion through $ORIGIN"
-    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
-        return
-    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
-    kr = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(kr)
-    recs = kr.kernel_records(REQUEST_LIB)
-    assert 1 <= len(recs) <= 2 and all("request_expand_kernel" in r["name"] for r in recs), [r["name"] for r in recs]
-    for r in recs:
-        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0 and r["private_segment_fixed_size"] == 0, r
+    """libfleetrec_request.so (companion.check_companion)"""
+    import companion
+    companion.check_companion(fr, REQUEST_LIB, ["fr_request_launch"], {"request_expand_kernel": 1}, "request_", (fr.LIB_PATH,))
