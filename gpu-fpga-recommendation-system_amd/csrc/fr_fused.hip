@@ -558,29 +558,26 @@ int frk_fused_launch(const FrFusedArgs &a, hipStream_t s) {
 // (158 KiB of LDS: Xq[K/4][65] + ONE R1 buffer; R3 overlays R2) and 64 queued batches of 256 to put one workgroup on every CU,
 // so it is used only when the launch group is 64 (fr_ctx_set_stream_group) -- twice the queueing latency of the 32-item kernel.
 // Same arithmetic as fr_fused_tile_kernel: full-K k-ordered f32 sums, bit-identical scores.
+// Its gather is sliced along K (FtmSlot below): FC1's first chunk runs in three segments, each started as soon as its record words are in LDS,
+// so that only the first quarter of the row loads has no MFMA over it (profiles/m2_sliced_gather.json).
 // ===================================================================================================
 constexpr int FR_M2_LD = 65;
 
-template <int NT, int MT, int R, int CNT>
-__device__ __forceinline__ void ftm_gemm_ct(f32x16 (&acc)[NT][MT], float4 (&ring)[R][NT], const FtW &w, int n0, const uint4 *Bq, int gb0, int g0, int hk,
-                                            int lm) {
+// Groups [GA, GB) of a CNT-group GEMM whose ring already holds groups GA .. GA + R - 1: the MFMAs and refills of exactly these groups, in the
+// order the whole GEMM issues them.  The caller owns both partial accumulators (NT == 1) and may put LDS stores and a barrier between two
+// segments: a segment reads no B fragment of a group past GB - 1.
+template <int NT, int MT, int R, int CNT, int GA, int GB>
+__device__ __forceinline__ void ftm_gemm_seg(f32x16 (&acc)[NT][MT], f32x16 (&alt)[MT], float4 (&ring)[R][NT], const FtW &w, int n0, const uint4 *Bq, int gb0,
+                                             int g0, int hk, int lm) {
     const unsigned s0 = (unsigned)g0 * w.row2 + (unsigned)n0 * 16u;
     const uint4 *bl = Bq + (size_t)(2 * gb0 + hk) * FR_M2_LD + lm;
     uint4 bcur[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++) bcur[mt] = bl[32 * mt];
-    // NT == 1: even / odd k partial accumulators exactly as in fr_fused_tile_kernel, so that both kernels return the same bits
-    f32x16 alt[MT];
-    if constexpr (NT == 1) {
+    for (int mt = 0; mt < MT; mt++) bcur[mt] = bl[(size_t)(2 * GA) * FR_M2_LD + 32 * mt];
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-            for (int i = 0; i < 16; i++) alt[mt][i] = 0.0f;
-    }
-#pragma unroll
-    for (int g = 0; g < CNT; g++) {
+    for (int g = GA; g < GB; g++) {
         uint4 bnext[MT];
-        const int gn = (g + 1 < CNT) ? g + 1 : g;
+        const int gn = (g + 1 < GB) ? g + 1 : g;
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) bnext[mt] = bl[(size_t)(2 * gn) * FR_M2_LD + 32 * mt];  // next group's B fragments from LDS
         const float4(&a4)[NT] = ring[g % R];
@@ -603,12 +600,35 @@ __device__ __forceinline__ void ftm_gemm_ct(f32x16 (&acc)[NT][MT], float4 (&ring
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) bcur[mt] = bnext[mt];
     }
+}
+
+template <int NT, int MT>
+__device__ __forceinline__ void ftm_alt_zero(f32x16 (&alt)[MT]) {
+    if constexpr (NT == 1) {
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) alt[mt][i] = 0.0f;
+    }
+}
+template <int NT, int MT>
+__device__ __forceinline__ void ftm_alt_add(f32x16 (&acc)[NT][MT], const f32x16 (&alt)[MT]) {
     if constexpr (NT == 1) {
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int i = 0; i < 16; i++) acc[0][mt][i] += alt[mt][i];
     }
+}
+
+template <int NT, int MT, int R, int CNT>
+__device__ __forceinline__ void ftm_gemm_ct(f32x16 (&acc)[NT][MT], float4 (&ring)[R][NT], const FtW &w, int n0, const uint4 *Bq, int gb0, int g0, int hk,
+                                            int lm) {
+    // NT == 1: even / odd k partial accumulators exactly as in fr_fused_tile_kernel, so that both kernels return the same bits
+    f32x16 alt[MT];
+    ftm_alt_zero<NT, MT>(alt);
+    ftm_gemm_seg<NT, MT, R, CNT, 0, CNT>(acc, alt, ring, w, n0, Bq, gb0, g0, hk, lm);
+    ftm_alt_add<NT, MT>(acc, alt);
 }
 
 template <bool EPI>
@@ -626,11 +646,98 @@ __device__ __forceinline__ void ftm_store_tile(uint4 *img, const f32x16 &acc, in
     }
 }
 
+// The gather of this kernel, SLICED along K so that FC1's first chunk starts under it (ft_gather_tile hands the whole record over at once).
+// A slot is W consecutive record words W0 .. W0 + W - 1 across W lanes (W in {8, 16, 32, 64}) and the tile's 64 items across the remaining
+// 64 / W lane rows, the 8 waves and IPT = W / 8 loads per thread.  Lanes run along words as in ft_gather_tile (neighbouring lanes read
+// neighbouring 16 bytes of one table row), and 8 contiguous lanes always hold 8 consecutive words of ONE item: at row stride 65 these are the
+// eight 16-byte slots of the 32 LDS banks a ds_write_b128 serves per pass, so the Xq stores stay conflict-free in every slot width.
+// The four steps are those of ft_gather_tile and are issued in its order over all slots (every descriptor, every index, every row); a
+// slice is the set of slots handed to LDS together.
+template <int W0, int W>
+struct FtmSlot {
+    static constexpr int IPT = W / 8;
+    uint64_t base;
+    uint32_t stride, rows, icol;
+    bool dense;
+    uint32_t id[IPT];
+    uint4 v[IPT];
+    static __device__ __forceinline__ int word(int lane) { return W0 + (lane & (W - 1)); }
+    static __device__ __forceinline__ int item(int lane, int wave, int i) { return lane / W + (64 / W) * (wave + 8 * i); }
+    __device__ __forceinline__ void desc(const FrFusedArgs &a, const FrFusedBatch &bt, int lane) {
+        const int w = word(lane) < a.n_words ? word(lane) : a.n_words - 1;   // a lane past the record repeats the last word (never stored)
+        const uint4 d0 = reinterpret_cast<const uint4 *>(a.words)[2 * w];
+        const uint4 d1 = reinterpret_cast<const uint4 *>(a.words)[2 * w + 1];
+        dense = (d0.w & FR_DESC_DENSE) != 0;
+        base = (dense ? (uint64_t)reinterpret_cast<uintptr_t>(bt.dense) : 0ull) + (((uint64_t)d0.y << 32) | d0.x);
+        stride = d0.z, rows = d1.x, icol = dense ? 0u : d0.w * 4u;
+    }
+    __device__ __forceinline__ void index(const FrFusedArgs &a, const __amdgpu_buffer_rsrc_t &rs_idx, int m0, int lane, int wave) {
+#pragma unroll
+        for (int i = 0; i < IPT; i++)
+            id[i] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_idx, (unsigned)(m0 + item(lane, wave, i)) * (unsigned)a.idx_stride * 4u + icol, 0, 0);
+    }
+    // the indices -> the rows to read (id[] in place); -> the out-of-range flag, known before any row load is issued
+    __device__ __forceinline__ bool check(const FrFusedBatch &bt, int m0, int lane, int wave) {
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < IPT; i++) {
+            const unsigned m = (unsigned)(m0 + item(lane, wave, i));
+            uint32_t r = id[i];
+            const bool oob = !dense & (r >= rows);  // reference: silent out-of-bounds read (embedding_47_krnl.cpp:927-933)
+            bad |= oob;
+            r = oob ? 0u : r;
+            id[i] = dense ? (m < (unsigned)bt.batch ? m : 0u) : r;
+        }
+        return bad;
+    }
+    // issues the row loads
+    __device__ __forceinline__ void load() {
+#pragma unroll
+        for (int i = 0; i < IPT; i++) {
+            typedef const u32x4_t __attribute__((address_space(1))) * gptr_t;
+            const u32x4_t q = *(gptr_t)(base + (uint64_t)id[i] * stride);
+            v[i] = make_uint4(q.x, q.y, q.z, q.w);
+        }
+    }
+    // the slot's rows into Xq, zeroed past the batch.  No barrier in here: the store is masked per lane.
+    __device__ __forceinline__ void put(const FrFusedArgs &a, const FrFusedBatch &bt, uint4 *Xq, int m0, int lane, int wave) const {
+        if (word(lane) < a.n_words) {
+#pragma unroll
+            for (int i = 0; i < IPT; i++) {
+                const int it = item(lane, wave, i);
+                Xq[(size_t)word(lane) * FR_M2_LD + it] = (m0 + it < bt.batch) ? v[i] : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+    }
+};
+template <class... S>
+struct FtmSlice : S... {
+    __device__ __forceinline__ void desc(const FrFusedArgs &a, const FrFusedBatch &bt, int lane) { (S::desc(a, bt, lane), ...); }
+    __device__ __forceinline__ void index(const FrFusedArgs &a, const __amdgpu_buffer_rsrc_t &rs, int m0, int lane, int wave) { (S::index(a, rs, m0, lane, wave), ...); }
+    __device__ __forceinline__ bool check(const FrFusedBatch &bt, int m0, int lane, int wave) { return (false | ... | S::check(bt, m0, lane, wave)); }
+    __device__ __forceinline__ void load() { (S::load(), ...); }
+    __device__ __forceinline__ void put(const FrFusedArgs &a, const FrFusedBatch &bt, uint4 *Xq, int m0, int lane, int wave) const { (S::put(a, bt, Xq, m0, lane, wave), ...); }
+};
+// K = 352: 88 record words, 44 groups of 8 k; group g reads words 2g and 2g + 1.  Three slices:
+//   words  0 .. 23 (groups  0 .. 11)  a quarter of the tile's rows, 3 loads per thread: the only part of the gather no MFMA covers
+//   words 24 .. 55 (groups 12 .. 27)  issued with the first, in flight in 4 x 4 registers under groups 0 .. 11
+//   words 56 .. 87 (groups 28 .. 43)  indices held, rows issued at the first cut, in flight under groups 12 .. 27
+// The cuts sit where a wave waits anyway.  Vector-memory loads return in order and ring1 (depth 12) is filled BEFORE the gather, so the wait
+// for group 12's weights -- the first refill, issued behind every row load of the first two slices -- is also the wait for the second slice;
+// rows issued up front for the third slice would have to land under the same twelve groups (5 us of MFMA for 7 us of rows: measured,
+// profiles/m2_sliced_gather.json form B).  Issued at the first cut they queue behind the refills of groups 12 .. 23 and are waited for with
+// group 24's weights, four groups before their cut.
+constexpr int FR_M2_CUT1 = 12, FR_M2_CUT2 = 28;
+using FtmS0 = FtmSlice<FtmSlot<0, 16>, FtmSlot<16, 8>>;
+using FtmS1 = FtmSlice<FtmSlot<24, 32>>;
+using FtmS2 = FtmSlice<FtmSlot<56, 32>>;
+
 template <int KG, bool EPI>
 __device__ __forceinline__ void fused_tile_m2_body(const FrFusedArgs &a) {
     extern __shared__ uint4 lds[];
     constexpr int LD = FR_M2_LD, MT = 2, T2W = 2, TI = 64;
-    constexpr int RA = 12, RB = 8;
+    constexpr int RA = 12, RB = 8, GC1 = FR_M2_CUT1, GC2 = FR_M2_CUT2;
+    static_assert(KG == 44 && GC1 < GC2 && GC2 < KG, "the slices above are cut for 88 record words");
     const int KQ = a.K / 4;
     uint4 *Xq = lds;                     // [KQ][65]
     uint4 *R1 = Xq + (size_t)KQ * LD;    // [64][65]: 256 outputs of FC1
@@ -647,41 +754,74 @@ __device__ __forceinline__ void fused_tile_m2_body(const FrFusedArgs &a) {
     float4 ring1[RA][1];
     ft_ring_fill<1, RA, KG>(ring1, W1, 32 * wave, 0);  // FC1 chunk 0's first weight groups: requested before the gather
 
-    {   // ---- gather: lanes along record words, 8 items per thread ----
-        const int wl = tid & 63, ig = tid >> 6;
-        constexpr int NB = (2 * KG + 63) / 64;   // K = 8 KG floats = 2 KG record words
-        const bool bad = ft_gather_tile<NB, 8>(a, bt, m0, wl, ig, [&](int w, int i, const uint4 &x) { Xq[(size_t)w * LD + 8 * ig + i] = x; });
-        if (bad) atomicOr_system(a.err_flag, 1);
-    }
+    // ---- gather, sliced (FtmSlot): every slice's descriptor and index loads and the first two slices' row loads are issued here; only the
+    // first slice is waited for ----
+    FtmS0 s0;
+    FtmS1 s1;
+    FtmS2 s2;
+    s0.desc(a, bt, lane), s1.desc(a, bt, lane), s2.desc(a, bt, lane);
+    const __amdgpu_buffer_rsrc_t rs_idx = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(bt.idx), 0, (unsigned)bt.batch * (unsigned)a.idx_stride * 4u, 0x00020000);
+    s0.index(a, rs_idx, m0, lane, wave), s1.index(a, rs_idx, m0, lane, wave), s2.index(a, rs_idx, m0, lane, wave);
+    const bool bad0 = s0.check(bt, m0, lane, wave), bad1 = s1.check(bt, m0, lane, wave), bad2 = s2.check(bt, m0, lane, wave);
+    s0.load(), s1.load();
+    if (bad0 | bad1 | bad2) atomicOr_system(a.err_flag, 1);  // before the first wait: nothing between the segments below but LDS stores, a barrier and row loads
+    s0.put(a, bt, Xq, m0, lane, wave);
     __syncthreads();
 
+    const int n_chunks = a.H1 / 256;
     f32x16 acc2[T2W][MT];
+    // the rest of a chunk once acc1 holds FC1's 256 outputs: R1 store, FC2 on it, and the next ring1
+    auto fc2_chunk = [&](int c, f32x16(&acc1)[1][MT]) {
+        float4 ring2[RB][T2W];  // FC2's first weight groups are requested before the R1 store and the barriers
+        ft_ring_fill<T2W, RB, 32>(ring2, W2, 32 * T2W * wave, 32 * c);
+        if (c > 0) __syncthreads();  // single R1 buffer: every wave must be done with the previous chunk's FC2 (chunk 0: nobody has read R1)
 #pragma unroll
-    for (int t = 0; t < T2W; t++)
+        for (int mt = 0; mt < MT; mt++) ftm_store_tile<EPI>(R1, acc1[0][mt], 32 * wave, 32 * mt, hk, lm, a.epi[0], c * 256 + 32 * wave);
+        __syncthreads();
+        ftm_gemm_ct<T2W, MT, RB, 32>(acc2, ring2, W2, 32 * T2W * wave, R1, 0, 32 * c, hk, lm);
+        if constexpr (EPI) {  // (the branch below costs this form 9 more scalar registers spilled to lanes: it keeps the branch-free request)
+            const int cn = (c + 1 < n_chunks) ? c + 1 : c;  // the last chunk re-requests its own: harmless
+            ft_ring_fill<1, RA, KG>(ring1, W1, cn * 256 + 32 * wave, 0);
+        } else {  // a uniform branch between two GEMMs, twelve loads on either side: the counted waits of the GEMM that follows are the same
+            if (c + 1 < n_chunks) ft_ring_fill<1, RA, KG>(ring1, W1, (c + 1) * 256 + 32 * wave, 0);
+            else ft_ring_fill<1, RA, 32 * T2W>(ring1, W3, 32 * wave, 0);  // after the last chunk the ring serves FC3: no 96 KB of FC1 weights nobody reads
+        }
+    };
+    {   // ---- chunk 0, peeled: FC1 in three straight-line segments around the later slices' hand-over, both partial accumulators carried ----
+        f32x16 acc1[1][MT], alt1[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-            for (int i = 0; i < 16; i++) acc2[t][mt][i] = 0.0f;
-    const int n_chunks = a.H1 / 256;
-    for (int c = 0; c < n_chunks; c++) {
+            for (int i = 0; i < 16; i++) acc1[0][mt][i] = 0.0f;
+        ftm_alt_zero<1, MT>(alt1);
+        ftm_gemm_seg<1, MT, RA, KG, 0, GC1>(acc1, alt1, ring1, W1, 32 * wave, Xq, 0, 0, hk, lm);
+        s1.put(a, bt, Xq, m0, lane, wave);  // rows of Xq that held the LDS's previous contents until now: no group >= GC1 has run
+        __syncthreads();
+        s2.load();  // behind the refills of groups GC1 .. GC1 + RA - 1: the wait for group GC1 + RA's weights is the wait for these rows
+        ftm_gemm_seg<1, MT, RA, KG, GC1, GC2>(acc1, alt1, ring1, W1, 32 * wave, Xq, 0, 0, hk, lm);
+        s2.put(a, bt, Xq, m0, lane, wave);
+        __syncthreads();
+        ftm_gemm_seg<1, MT, RA, KG, GC2, KG>(acc1, alt1, ring1, W1, 32 * wave, Xq, 0, 0, hk, lm);
+        ftm_alt_add<1, MT>(acc1, alt1);
+#pragma unroll
+        for (int t = 0; t < T2W; t++)
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+                for (int i = 0; i < 16; i++) acc2[t][mt][i] = 0.0f;
+        fc2_chunk(0, acc1);
+    }
+    for (int c = 1; c < n_chunks; c++) {
         f32x16 acc1[1][MT];
 #pragma unroll
         for (int mt = 0; mt < MT; mt++)
 #pragma unroll
             for (int i = 0; i < 16; i++) acc1[0][mt][i] = 0.0f;
         ftm_gemm_ct<1, MT, RA, KG>(acc1, ring1, W1, c * 256 + 32 * wave, Xq, 0, 0, hk, lm);
-        float4 ring2[RB][T2W];  // FC2's first weight groups are requested before the R1 store and the barriers
-        ft_ring_fill<T2W, RB, 32>(ring2, W2, 32 * T2W * wave, 32 * c);
-        if (c > 0) __syncthreads();  // single R1 buffer: every wave must be done with the previous chunk's FC2
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) ftm_store_tile<EPI>(R1, acc1[0][mt], 32 * wave, 32 * mt, hk, lm, a.epi[0], c * 256 + 32 * wave);
-        __syncthreads();
-        ftm_gemm_ct<T2W, MT, RB, 32>(acc2, ring2, W2, 32 * T2W * wave, R1, 0, 32 * c, hk, lm);
-        const int cn = (c + 1 < n_chunks) ? c + 1 : c;  // the last chunk re-requests its own: branch-free, harmless
-        ft_ring_fill<1, RA, KG>(ring1, W1, cn * 256 + 32 * wave, 0);
+        fc2_chunk(c, acc1);
     }
-    float4 ring3[RA][1];
-    ft_ring_fill<1, RA, 32 * T2W>(ring3, W3, 32 * wave, 0);
+    float4(&ring3)[RA][1] = ring1;  // !EPI: filled with FC3's first weight groups behind the last chunk's FC2
+    if constexpr (EPI) ft_ring_fill<1, RA, 32 * T2W>(ring3, W3, 32 * wave, 0);
     __syncthreads();  // Xq and R1 dead: R2 may overlay them
 #pragma unroll
     for (int t = 0; t < T2W; t++)
