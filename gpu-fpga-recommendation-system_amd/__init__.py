@@ -98,6 +98,7 @@ ABI_SYMBOLS = [
     "fr_worker_erase_keys", "fr_ctx_erase_keys", "fr_ctx_key_space_stats", "fr_ctx_export_keys", "fr_ctx_rebuild_key_space",
     "fr_ctx_set_row_pool", "fr_ctx_row_pool", "fr_worker_admit_keys", "fr_ctx_admit_keys",
     "fr_ctx_set_epilogue", "fr_ctx_epilogue",
+    "fr_worker_push_requests_factored_device", "fr_worker_submit_requests_factored",
 ]
 
 
@@ -116,7 +117,8 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_submit_keyed", "fr_worker_key_misses",
                    "fr_worker_erase_keys", "fr_ctx_erase_keys", "fr_ctx_key_space_stats", "fr_ctx_export_keys", "fr_ctx_rebuild_key_space",
                    "fr_ctx_set_row_pool", "fr_ctx_row_pool", "fr_worker_admit_keys", "fr_ctx_admit_keys",
-                   "fr_ctx_set_epilogue", "fr_ctx_epilogue")
+                   "fr_ctx_set_epilogue", "fr_ctx_epilogue",
+                   "fr_worker_push_requests_factored_device", "fr_worker_submit_requests_factored")
 
 
 def lib():
@@ -204,6 +206,7 @@ def lib():
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
         "fr_worker_request_idx_ptr": (pi, [vp]), "fr_worker_request_weights_ptr": (pf, [vp]), "fr_worker_request_dense_ptr": (pf, [vp]),
         "fr_worker_request_offsets_ptr": (pi, [vp]), "fr_worker_submit_requests": (i32, [vp, i32, i32, i32]),
+        "fr_worker_push_requests_factored_device": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp]), "fr_worker_submit_requests_factored": (i32, [vp, i32, i32]),
         "fr_ctx_set_key_space": (i32, [vp, i32, i32, ctypes.c_uint64, i64, ctypes.c_int32]),
         "fr_ctx_key_space": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32)]),
         "fr_ctx_put_keys": (i32, [vp, i32, i32, vp, vp]), "fr_worker_put_keys": (i32, [vp, i32, i32, vp, vp]),
@@ -1374,6 +1377,30 @@ class Worker:
         ranked (fr_worker_topk over the same offsets)."""
         B, n_req, pooled, off = self._load_requests(req_idx, cand_idx, seg_offsets, req_dense, dense, req_weights, weights, pooled)
         self.submit_requests(B, n_req, pooled)
+        return self._topk_host(B, k, off)
+
+    # factored request-form batches: FC1 split into the request's and the candidate's part, no expansion (one-hot rows, fp32 / bf16 chain) ---------
+    def push_requests_factored_device(self, batch, n_req, d_req, d_cand, d_scores, d_seg_offsets=None, d_req_dense=None, d_cand_dense=None):
+        """fr_worker_push_requests_factored_device: d_req int32 [n_req][request words] + d_cand int32 [batch][candidate words] (+ the dense features
+        on the side the split names) -> d_scores [batch]; stream-ordered and un-flushed like push_pooled_device, sync() drains."""
+        _check(lib().fr_worker_push_requests_factored_device(self._h, int(batch), int(n_req), self._ptr(d_seg_offsets), self._ptr(d_req), self._ptr(d_cand),
+                                                             self._ptr(d_req_dense), self._ptr(d_cand_dense), self._ptr(d_scores)))
+
+    def submit_requests_factored(self, batch, n_req):
+        """fr_worker_submit_requests_factored on what the pinned buffers hold (as submit_requests(batch, n_req, 0)).  Asynchronous; follow with sync()."""
+        _check(lib().fr_worker_submit_requests_factored(self._h, int(batch), int(n_req)))
+
+    def infer_requests_factored(self, req_idx, cand_idx, seg_offsets, req_dense=None, dense=None):
+        """infer_requests() of a one-hot request-form batch through the factored FC1 -> scores float32 [B]."""
+        B, n_req, _, _ = self._load_requests(req_idx, cand_idx, seg_offsets, req_dense, dense, None, None, 0)
+        self.submit_requests_factored(B, n_req)
+        self.sync()
+        return self.score[:B].copy()
+
+    def infer_requests_factored_topk(self, req_idx, cand_idx, seg_offsets, k, req_dense=None, dense=None):
+        """infer_requests_factored() with the ranking on the device (fr_worker_topk over the same offsets)."""
+        B, n_req, _, off = self._load_requests(req_idx, cand_idx, seg_offsets, req_dense, dense, None, None, 0)
+        self.submit_requests_factored(B, n_req)
         return self._topk_host(B, k, off)
 
     # keyed lookups (Context.set_key_space): int64 feature ids resolved to the int32 rows every lookup path takes, on the device ---------------------

@@ -2,6 +2,7 @@
 // worker = stream + staging buffers, submit/sync = the hot-loop body of the reference's
 // thread_consume() (GPU/final_network_cublasLt_1_node_no_FIFO_scatter/cuda_server.c:101-503) with
 // the FPGA embedding stage (FPGA/kernel/user_krnl/embedding_*_krnl) pulled in front of the FC chain.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -657,6 +658,7 @@ static int refresh_fp8(fr_ctx *ctx, int layer) {
 
 // derived copies of one layer's weights: the q4 re-pack for the fp32 chain, the bf16 / fp8 casts for the low-precision chains
 static int refresh_bf16(fr_ctx *ctx, int layer) {
+    ctx->weights_gen++;   // (the split images of the factored FC1 follow W1: reqfc_ensure)
     if (layer < 3) {
         int rc = frk_pack_weights_q4(ctx->d_w[layer], ctx->d_wq[layer], ctx->model.fc[layer], ctx->model.fc[layer + 1], ctx->setup_stream);
         if (rc) return rc;
@@ -676,7 +678,7 @@ extern "C" int fr_ctx_set_weights(fr_ctx *ctx, int layer, const float *w, size_t
     if (count != n) FR_FAIL(FR_ERR_INVALID, "layer %d expects %zu weights (H=%d x K=%d), got %zu", layer, n, ctx->model.fc[layer + 1], ctx->model.fc[layer], count);
     if (ctx->cpu) {
         memcpy(ctx->d_w[layer], w, n * sizeof(float));
-        ctx->weights_set = true;
+        ctx->weights_set = true, ctx->weights_gen++;
         return FR_OK;
     }
     FR_SET_DEVICE(ctx);
@@ -746,7 +748,7 @@ extern "C" int fr_ctx_fill_weights(fr_ctx *ctx, int mode, uint32_t seed) {
     if (ctx->cpu) {
         for (int l = 0; l < 4; l++)
             frc_fill_weights(ctx->d_w[l], (size_t)ctx->model.fc[l] * ctx->model.fc[l + 1], mode, seed, (uint32_t)l, 1.0f / std::sqrt((float)ctx->model.fc[l]));
-        ctx->weights_set = true;
+        ctx->weights_set = true, ctx->weights_gen++;
         return FR_OK;
     }
     FR_SET_DEVICE(ctx);
@@ -857,6 +859,32 @@ static void request_caps(const fr_ctx *c, fr_worker *w) {
     w->req_w_cap = w->pool_w_cap ? (rp > 0 ? rp : 1) : 0;
 }
 
+// which side of the request split a record word belongs to (0: the request's, 1: the candidate's): its index column's, dense words as dense_shared says
+static int reqfc_side(const fr_ctx *c, const FrWordDesc &wd) {
+    if (wd.idx_col & FR_DESC_DENSE) return c->req_dense_shared ? 0 : 1;
+    return c->req_shared[wd.idx_col] ? 0 : 1;
+}
+
+// the factored FC1's worker-owned operands, sized for the split as it stands (every side's word count rounded up to even: the bf16 pad word)
+static int reqfc_worker_buffers(const fr_ctx *c, fr_worker *w) {
+    // (contexts the factored entry points refuse get none: sharded, not SEMANTIC, pooled or fp8 as things stand at the worker's creation)
+    if (c->n_shards > 1 || c->model.layout != FR_LAYOUT_SEMANTIC || c->pool_cols > 0 || (!c->cpu && c->fc_precision == FR_FC_FP8)) return FR_OK;
+    int n[2] = {0, 0};
+    for (const FrWordDesc &wd : c->h_words) n[reqfc_side(c, wd)]++;
+    w->reqfc_ws_cap = n[0] + (n[0] & 1), w->reqfc_wc_cap = n[1] + (n[1] & 1);
+    const FrMem device = fr_mem_kind(c, FrMem::DEVICE);
+    const size_t B = (size_t)w->max_batch, H1 = (size_t)c->model.fc[1];
+    if (c->cpu) {   // item-major records and products
+        FR_TRY(w->d_reqfc_xs.alloc(device, B * 4 * (size_t)w->reqfc_ws_cap + 4, "worker request-side operand"));
+        FR_TRY(w->d_reqfc_xc.alloc(device, B * 4 * (size_t)w->reqfc_wc_cap + 4, "worker candidate-side operand"));
+        return w->d_reqfc_u.alloc(device, B * H1, "worker request-side products");
+    }
+    const size_t ldr = (size_t)round_up(w->max_batch, 32), part_ldr = ldr < (size_t)FR_REQFC_PART_LDR ? ldr : (size_t)FR_REQFC_PART_LDR;
+    FR_TRY(w->d_reqfc_xs.alloc(device, ldr * 4 * (size_t)w->reqfc_ws_cap + 4, "worker request-side operand"));
+    FR_TRY(w->d_reqfc_xc.alloc(device, (size_t)w->ld_max * 4 * (size_t)w->reqfc_wc_cap + 4, "worker candidate-side operand"));
+    return w->d_reqfc_u.alloc(device, std::max(ldr, (size_t)FR_REQFC_MAX_PARTS * part_ldr) * H1, "worker request-side products");
+}
+
 // the stream, buffers and events of a new worker, one sequence for both back-ends; a failure leaves what was made to fr_worker_destroy
 static int worker_build(fr_worker *w) {
     fr_ctx *ctx = w->ctx;
@@ -936,6 +964,7 @@ static int worker_build(fr_worker *w) {
         if (ctx->req_dense_shared) FR_TRY(w->h_req_dense.alloc(pinned, n_dense, "worker request dense rows"));
         FR_TRY(w->h_req_off.alloc(pinned, B + 1, "worker request offsets"));
         if (w->pool_w_cap) FR_TRY(w->d_pool_w.alloc(device, n_pool_w, "worker expanded weights"));
+        FR_TRY(reqfc_worker_buffers(ctx, w));
     }
     if (ctx->keyed) FR_TRY(w->h_keys.alloc(pinned, n_idx, "worker key rows"));   // keyed host form: read in place by the resolve
     if (!cpu) {
@@ -1365,7 +1394,8 @@ static int pipeline_step(fr_worker *w) {
                 st.in = rd.x; st.in_part_stride = 0; st.out = wr.r1; st.part_stride = (int)wr.p1; st.w = wl[0];
                 break;
             case 2:
-                st.K = fc[1]; st.N = fc[2]; st.nsplit = ns2; st.nparts_in = ns1;
+                st.K = fc[1]; st.N = fc[2]; st.nsplit = ns2;
+                st.nparts_in = sl.whole_in ? 1 : ns1;   // (whole_in: the factored FC1 brought a finished R1 -- no partials, no epi_in)
                 st.in = rd.r1; st.in_part_stride = (int)rd.p1; st.out = wr.r2; st.part_stride = (int)wr.p2; st.w = wl[1];
                 break;
             case 3:
@@ -1424,13 +1454,14 @@ static int pipeline_step(fr_worker *w) {
     return frk_pipeline_launch(a, -1, prec, w->stream);
 }
 
-static int pipeline_push(fr_worker *w, int batch, int first_stage, const int32_t *d_idx, const float *d_dense, float *d_scores) {
+static int pipeline_push(fr_worker *w, int batch, int first_stage, const int32_t *d_idx, const float *d_dense, float *d_scores, bool whole_in = false) {
     const uint64_t L0 = w->launch_no - (uint64_t)first_stage;  // launch number its (virtual) stage 0 had
     fr_worker::Slot &sl = w->ring[L0 % 8];
     if (sl.active) FR_FAIL(FR_ERR_STATE, "internal: pipeline ring slot still busy");
     sl.active = true;
     sl.launch0 = L0;
     sl.first_stage = first_stage;
+    sl.whole_in = whole_in;
     sl.batch = batch;
     sl.ldm = round_up(batch, 32);
     sl.d_idx = d_idx;
@@ -2160,6 +2191,7 @@ extern "C" int fr_worker_fc_layer_only(fr_worker *w, int batch, int layer) {
     sl.active = true;
     sl.launch0 = L0;
     sl.first_stage = stage;
+    sl.whole_in = false;
     sl.batch = batch;
     sl.ldm = round_up(batch, 32);
     sl.d_idx = nullptr;
@@ -2914,6 +2946,7 @@ extern "C" int fr_ctx_set_request_columns(fr_ctx *ctx, const int32_t *shared, in
     const int rc = fr_pooling_busy(ctx, "fr_ctx_set_request_columns");
     if (rc) return rc;
     if (!ctx->cpu) FR_SET_DEVICE(ctx);
+    ctx->req_split_gen++;   // (the split images of the factored FC1 follow the split: reqfc_ensure)
     if (!shared) {
         ctx->d_req_desc.reset();
         ctx->req_shared.clear();
@@ -3036,6 +3069,190 @@ extern "C" int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int
     if (pooled) rc = submit_pooled_impl(w, weighted ? pooled_batch_weighted(batch, w->d_idx, w->d_pool_w, dense) : FrPooledBatch{batch, w->d_idx, nullptr, dense}, w->h_score);
     else rc = launch_pipeline(w, batch, w->d_idx, dense, w->h_score);
     if (rc) return rc;
+    w->in_flight = true, w->host_batch = batch;   // (fr_worker_topk ranks it)
+    return FR_OK;
+}
+
+// ---- factored FC1 of request-form batches (fleetrec_serving.h; fr_reqfc.hip -> libfleetrec_reqfc.so, the CPU twin in fr_cpu.cpp) --------------------
+// The split images of the context: per side the subset of h_words -- destination words renumbered compactly in ascending record order, index
+// columns renumbered to their place in the request / candidate row (request_prepare's two running counters) -- and W1's columns of that side,
+// packed by the chain's own packers.  A record word is 4 consecutive k, so a side's columns of the K-major master are whole runs of 4 x H1 floats.
+static int reqfc_ensure(fr_ctx *c) {
+    std::lock_guard<std::mutex> lk(c->lp_mutex);
+    const int prec = c->cpu ? (int)FR_FC_FP32 : c->fc_precision;
+    if (c->reqfc_gen && c->reqfc_split_gen == c->req_split_gen && c->reqfc_weights_gen == c->weights_gen && c->reqfc_prec == prec && c->reqfc_arena == (const void *)c->table_arena.p)
+        return FR_OK;
+    const size_t H1 = (size_t)c->model.fc[1];
+    const int cols = (int)idx_cols(c);
+    std::vector<uint32_t> pos((size_t)cols, 0u);
+    for (int col = 0, nr = 0, nc = 0; col < cols; col++) pos[(size_t)col] = (uint32_t)(c->req_shared[(size_t)col] ? nr++ : nc++);
+    std::vector<FrWordDesc> list[2];
+    for (const FrWordDesc &wd : c->h_words) list[reqfc_side(c, wd)].push_back(wd);
+    const FrMem device = fr_mem_kind(c, FrMem::DEVICE);
+    if (!c->cpu && !c->reqfc_zero) {
+        FrBuf<float> fresh;   // taken by the context only once it is cleared
+        FR_TRY(fresh.alloc(FrMem::DEVICE, 16, "factored FC1 zero row"));
+        FR_HIP(hipMemset(fresh, 0, 16 * sizeof(float)));
+        c->reqfc_zero = std::move(fresh);
+    }
+    for (int s = 0; s < 2; s++) {
+        fr_ctx::ReqfcSide &sd = c->reqfc[s];
+        std::vector<FrWordDesc> &l = list[s];
+        if (l.empty()) FR_FAIL(FR_ERR_STATE, "the request split leaves no record word on the %s side: FC1 cannot be factored", s ? "candidate" : "request");
+        std::stable_sort(l.begin(), l.end(), [](const FrWordDesc &a, const FrWordDesc &b) { return a.dst_off < b.dst_off; });
+        const int n = (int)l.size(), pad = (prec == FR_FC_BF16) ? (n & 1) : 0;
+        const size_t K = 4 * (size_t)(n + pad);
+        FR_TRY(sd.w1.alloc(device, K * H1, "split FC1 weights"));
+        if (!c->cpu) FR_TRY(sd.img.alloc(device, K * H1, "split FC1 weight image"));
+        for (int j = 0; j < n; j++) {   // (SEMANTIC layout: dst_off is the record word, 4 dst_off its first k)
+            const float *src = c->d_w[0] + 4 * (size_t)l[(size_t)j].dst_off * H1;
+            if (c->cpu) memcpy(sd.w1 + 4 * (size_t)j * H1, src, 4 * H1 * sizeof(float));
+            else FR_HIP(hipMemcpyAsync(sd.w1 + 4 * (size_t)j * H1, src, 4 * H1 * sizeof(float), hipMemcpyDeviceToDevice, c->setup_stream));
+            FrWordDesc &wd = l[(size_t)j];
+            if (!(wd.idx_col & FR_DESC_DENSE)) wd.idx_col = pos[wd.idx_col];
+            wd.dst_off = (uint32_t)j, wd.dst_stride = (uint32_t)n, wd.dst_blk = 0;
+        }
+        if (pad) {   // the pad word: zero k-rows in the image, and a descriptor that makes the gather write zeros (every index reads the one zero row)
+            FR_HIP(hipMemsetAsync(sd.w1 + 4 * (size_t)n * H1, 0, 4 * H1 * sizeof(float), c->setup_stream));
+            FrWordDesc z{};
+            z.src = (uint64_t)(uintptr_t)c->reqfc_zero.p, z.stride = 0, z.idx_col = 0, z.rows = 0xffffffffu, z.dst_off = (uint32_t)n;
+            l.push_back(z);
+        }
+        if (!c->cpu) {
+            FR_TRY(prec == FR_FC_BF16 ? frk_pack_weights_q8_bf16(sd.w1, reinterpret_cast<uint16_t *>(sd.img.p), (int)K, (int)H1, c->setup_stream)
+                                      : frk_pack_weights_q4(sd.w1, sd.img, (int)K, (int)H1, c->setup_stream));
+            FR_TRY(sd.d_words.alloc(FrMem::DEVICE, l.size(), "split word descriptors"));
+            FR_HIP(hipMemcpyAsync(sd.d_words, l.data(), sizeof(FrWordDesc) * l.size(), hipMemcpyHostToDevice, c->setup_stream));
+            FR_HIP(hipStreamSynchronize(c->setup_stream));   // (l is read by the copy)
+        }
+        sd.h_words.swap(l);
+        sd.n_words = n + pad, sd.rows = prec == FR_FC_BF16 ? (n + pad) / 2 : n;
+    }
+    c->reqfc_split_gen = c->req_split_gen, c->reqfc_weights_gen = c->weights_gen, c->reqfc_prec = prec, c->reqfc_arena = (const void *)c->table_arena.p;
+    c->reqfc_gen++;
+    return FR_OK;
+}
+
+// one side's gather: the stage pipeline's stage 0 alone, with the side's descriptors, over `items` rows of `stride` index words into x [rows][ld]
+static int reqfc_gather(fr_worker *w, const fr_ctx::ReqfcSide &sd, int items, int ld, const int32_t *rows, int stride, const float *dense, float *x, int prec) {
+    FrPipeArgs a{};
+    a.words = sd.d_words, a.n_words = sd.n_words, a.idx_stride = stride, a.idx = rows, a.dense = dense, a.err_flag = w->d_err;
+    FrStageArgs &st = a.st[0];
+    st.batch = items, st.ldm = ld, st.K = 4 * sd.n_words, st.out = x;
+    const int trv = frk_gather_tr_variant(items, stride), trb = frk_gather_tr_blocks(sd.n_words, ld, trv);
+    int blocks = frk_stage_blocks(0, sd.n_words, st.K, 0, ld, 1);
+    if (trb > 0) st.variant = trv, blocks = (trb + 7) / 8 * 8;   // a large side: the LDS-transposing forms, as pipeline_step picks them
+    for (int s = 1; s < FR_N_STAGES; s++) a.st[s].block_begin = blocks;
+    a.n_blocks = blocks;
+    return frk_pipeline_launch(a, 0, prec, w->stream);
+}
+
+// the contexts the factored entry points refuse, before anything else is looked at
+static int reqfc_refuse(const fr_worker *w, const char *who) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    const fr_ctx *c = w->ctx;
+    if (c->n_shards > 1) FR_FAIL(FR_ERR_STATE, "%s: a factored request-form batch is not available on a sharded context (%d shards)", who, c->n_shards);
+    const fr_ctx::ReqForm *f = nullptr;
+    FR_TRY(request_form(c, FR_REQ_ONE_HOT, &f));
+    if (c->pool_cols > 0) FR_FAIL(FR_ERR_STATE, "%s: a factored request-form batch is not available on a pooled context", who);
+    if (!c->cpu && c->fc_precision == FR_FC_FP8) FR_FAIL(FR_ERR_STATE, "%s: a factored request-form batch is not available on an fp8 chain (fp32 and bf16 only)", who);
+    if (c->model.layout != FR_LAYOUT_SEMANTIC) FR_FAIL(FR_ERR_STATE, "%s needs a SEMANTIC-layout context", who);
+    if (c->model.fc[1] % 32) FR_FAIL(FR_ERR_STATE, "%s: FC1 has %d outputs, the factored FC1 takes multiples of 32", who, c->model.fc[1]);
+    return FR_OK;
+}
+
+struct ReqfcBatch {   // a factored batch as the two entry points hand it in
+    int batch, n_req;
+    const int32_t *off, *req, *cand;
+    const float *req_dense, *cand_dense;
+    float *scores;
+};
+
+// What both entry points share: the refusals, then user gather | reqfc_user | candidate gather | reqfc_cand on the worker's stream, then the batch
+// enters the stage pipeline at stage 2 with R1 in the activation set stage 2 of the next launch reads.  Un-flushed; the host form drains behind it.
+static int reqfc_enqueue(fr_worker *w, const ReqfcBatch &b, const char *who) {
+    fr_ctx *c = w->ctx;
+    const int32_t *fc = c->model.fc;
+    const fr_ctx::ReqForm *f = &c->req_form[FR_REQ_ONE_HOT];
+    if ((f->req_words && !b.req) || (f->cand_words && !b.cand) || !b.scores) FR_FAIL(FR_ERR_INVALID, "%s: request rows, candidate rows or scores is NULL", who);
+    if (c->model.dense_len && !(c->req_dense_shared ? b.req_dense : b.cand_dense))
+        FR_FAIL(FR_ERR_INVALID, "%s: the model has dense features (%s) but their pointer is NULL", who, c->req_dense_shared ? "shared: the request side's" : "per item: the candidate side's");
+    if (!b.off && b.batch % b.n_req) FR_FAIL(FR_ERR_INVALID, "%s: NULL offsets ask for %d equal requests, batch %d is no multiple", who, b.n_req, b.batch);
+    if (!c->cpu) FR_SET_DEVICE(c);
+    FR_TRY(reqfc_ensure(c));
+    const fr_ctx::ReqfcSide &S = c->reqfc[0], &C = c->reqfc[1];
+    if (!w->d_reqfc_xs || !w->d_reqfc_xc || !w->d_reqfc_u || w->reqfc_ws_cap < S.n_words || w->reqfc_wc_cap < C.n_words)
+        FR_FAIL(FR_ERR_STATE, "%s: the worker's factored operands hold %d + %d record words, the split needs %d + %d: create the worker after fr_ctx_set_request_columns", who,
+                w->reqfc_ws_cap, w->reqfc_wc_cap, S.n_words, C.n_words);
+    if (c->cpu) {
+        const float *const wl[4] = {c->d_w[0], c->d_w[1], c->d_w[2], c->d_w[3]};
+        const FrEpi ep[4] = {c->epi(0), c->epi(1), c->epi(2), c->epi(3)};
+        FrReqfcCpuArgs a{};
+        a.ws = S.h_words.data(), a.wc = C.h_words.data(), a.n_ws = S.n_words, a.n_wc = C.n_words, a.w1s = S.w1, a.w1c = C.w1, a.w = wl, a.epi = ep, a.fc = fc;
+        a.off = b.off, a.req = b.req, a.cand = b.cand, a.req_dense = b.req_dense, a.cand_dense = b.cand_dense;
+        a.batch = b.batch, a.n_req = b.n_req, a.Rs = f->req_words, a.Rc = f->cand_words;
+        a.xs = w->d_reqfc_xs, a.xc = w->d_reqfc_xc, a.u = w->d_reqfc_u, a.scratch = w->c_scratch, a.scores = b.scores;
+        if (frc_reqfc(a, &w->c_err)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+        w->in_flight = true;
+        return FR_OK;
+    }
+    FR_TRY(fr_host_fed_queued(w, "push"));
+    FR_TRY(fr_fused_flush(w));   // batches fr_worker_push_device queued for a fused launch were pushed before this one: launched first, not waited for
+    if (w->launch_no < 2) w->launch_no = 2;   // stage 2 of the next launch reads the set the (virtual) previous launch wrote
+    // a batch whose FC1 ran in the previous launch holds the slot (and the R1) this batch would take: launches without a new batch move it on -- at
+    // most twice (the second for a batch gathered by the previous launch), nothing enters a launch made here
+    while (w->ring[(w->launch_no - 2) % 8].active) FR_TRY(pipeline_step(w));
+    const int prec = c->fc_precision, H1 = fc[1];
+    const int ldm = round_up(b.batch, 32), ldr = round_up(b.n_req, 32);
+    float *r1 = act_set(w, (int)((w->launch_no - 1) & 1)).r1;
+    // (a side without index columns -- only the dense features are shared -- still hands its pad word an index row to read: the zero row)
+    const int32_t *zero_idx = reinterpret_cast<const int32_t *>(c->reqfc_zero.p);
+    FR_TRY(reqfc_gather(w, S, b.n_req, ldr, f->req_words ? b.req : zero_idx, f->req_words, b.req_dense, w->d_reqfc_xs, prec));
+    w->in_flight = true;
+    FrReqfcUserArgs ua{};
+    ua.w = S.img, ua.x = w->d_reqfc_xs, ua.u = w->d_reqfc_u, ua.rows = S.rows, ua.H1 = H1, ua.ldr = ldr, ua.precision = prec;
+    ua.nparts = fr_reqfc_parts(H1, ldr, (S.rows + 1) / 2);
+    int e = fr_reqfc_user_launch(&ua, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the reqfc_user_kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    FR_TRY(reqfc_gather(w, C, b.batch, ldm, f->cand_words ? b.cand : zero_idx, f->cand_words, b.cand_dense, w->d_reqfc_xc, prec));
+    FrReqfcCandArgs ca{};
+    ca.w = C.img, ca.x = w->d_reqfc_xc, ca.r1 = r1, ca.u = w->d_reqfc_u, ca.off = b.off, ca.err_flag = w->d_err;
+    ca.rows = C.rows, ca.H1 = H1, ca.ldm = ldm, ca.batch = b.batch, ca.n_req = b.n_req, ca.ldr = ldr, ca.nparts = ua.nparts, ca.precision = prec, ca.epi = c->epi(0);
+    e = fr_reqfc_cand_launch(&ca, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the reqfc_cand_kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    FR_TRY(pipeline_push(w, b.batch, 2, nullptr, nullptr, b.scores, true));   // whole R1; no flush: fr_worker_sync drains
+    snprintf(w->last_kernel, sizeof(w->last_kernel), "reqfc_cand_kernel<%d>", prec == FR_FC_BF16 ? 1 : 0);
+    return FR_OK;
+}
+
+extern "C" int fr_worker_push_requests_factored_device(fr_worker *w, int batch, int n_req, const int32_t *d_seg_offsets, const int32_t *d_req_rows, const int32_t *d_cand_rows,
+                                                       const float *d_req_dense, const float *d_cand_dense, float *d_scores) {
+    FR_TRY(reqfc_refuse(w, "fr_worker_push_requests_factored_device"));
+    FR_TRY(check_ready(w, batch, true, true));
+    if (n_req < 1 || n_req > w->max_batch) FR_FAIL(FR_ERR_INVALID, "n_req = %d outside [1, max_batch=%d]", n_req, w->max_batch);
+    return reqfc_enqueue(w, ReqfcBatch{batch, n_req, d_seg_offsets, d_req_rows, d_cand_rows, d_req_dense, d_cand_dense, d_scores}, "fr_worker_push_requests_factored_device");
+}
+
+extern "C" int fr_worker_submit_requests_factored(fr_worker *w, int batch, int n_req) {
+    const char *who = "fr_worker_submit_requests_factored";
+    FR_TRY(reqfc_refuse(w, who));
+    FR_TRY(check_ready(w, batch, true, true));
+    if (n_req < 1 || n_req > w->max_batch) FR_FAIL(FR_ERR_INVALID, "n_req = %d outside [1, max_batch=%d]", n_req, w->max_batch);
+    fr_ctx *c = w->ctx;
+    const fr_ctx::ReqForm *f = &c->req_form[FR_REQ_ONE_HOT];
+    if (!w->h_req_idx || !w->h_req_off || (c->req_dense_shared && !w->h_req_dense)) FR_FAIL(FR_ERR_STATE, "the worker has no request buffers: create the worker after fr_ctx_set_request_columns");
+    if (w->in_flight) FR_FAIL(FR_ERR_STATE, "a batch is already in flight on this worker: call fr_worker_sync first");
+    if (w->req_idx_cap < f->req_words)
+        FR_FAIL(FR_ERR_STATE, "the worker's request index buffer holds %d words per request, the split needs %d: create the worker after the split and the pooling are set", w->req_idx_cap,
+                f->req_words);
+    if (w->n_active || w->n_pending) FR_FAIL(FR_ERR_STATE, "pipeline busy (push_device in flight): call fr_worker_sync first");
+    // the host knows the offsets: the two ends are checked here, before anything is enqueued (the pair checks are reqfc_cand_kernel's)
+    if (w->h_req_off[0] != 0) FR_FAIL(FR_ERR_INVALID, "%s: offsets[0] is %d, not 0", who, w->h_req_off[0]);
+    if (w->h_req_off[n_req] != batch) FR_FAIL(FR_ERR_INVALID, "%s: offsets[n_req] is %d, the batch has %d items", who, w->h_req_off[n_req], batch);
+    // the pinned arrays are read in place, the scores land in the pinned score buffer
+    const float *dense = c->model.dense_len ? w->h_dense.p : nullptr;
+    FR_TRY(reqfc_enqueue(w, ReqfcBatch{batch, n_req, w->h_req_off, w->h_req_idx, w->h_idx, c->req_dense_shared ? w->h_req_dense.p : nullptr, dense, w->h_score}, who));
+    if (!c->cpu) FR_TRY(pipeline_flush(w));
     w->in_flight = true, w->host_batch = batch;   // (fr_worker_topk ranks it)
     return FR_OK;
 }

@@ -580,6 +580,47 @@ int frc_expand_requests(const FrRequestArgs &a) {
     return bad;
 }
 
+// ---- factored FC1 of request-form batches: the CPU twin of reqfc_user_kernel + reqfc_cand_kernel (fr_reqfc.hip), and the rest of the chain ---------
+// U[r] = W1[:, S] x_S(r) once per request, V[b] = W1[:, C] x_C(b) per item (both fp32 sums in this back-end's k order), R1[b] = fl(V[b] + U[owner(b)]),
+// FC1's epilogue, then FC2 / FC3 / the output layer as frc_fc_chain runs them.  The owner rule is frc_expand_requests's: clamped, so nothing outside
+// off[0 .. n_req], req[0 .. n_req * Rs), cand[0 .. batch * Rc) and the rows the descriptors name is read, whatever off holds.  -> 1: off was malformed.
+int frc_reqfc(const FrReqfcCpuArgs &a, int *err_flag) {
+    int bad = 0;
+    if (a.off) {
+        bad = a.off[0] != 0 || a.off[a.n_req] != a.batch;
+        for (int j = 0; j < a.n_req && !bad; j++) bad = a.off[j] > a.off[j + 1];
+    }
+    const int H1 = a.fc[1], KS = 4 * a.n_ws, KC = 4 * a.n_wc;
+    frc_gather(a.ws, a.n_ws, a.req, a.Rs, a.req_dense, a.xs, a.n_req, err_flag);
+    frc_gather(a.wc, a.n_wc, a.cand, a.Rc, a.cand_dense, a.xc, a.batch, err_flag);
+    float *r1 = a.scratch, *r2 = r1 + (size_t)a.batch * a.fc[1], *r3 = r2 + (size_t)a.batch * a.fc[2];
+    fc_layer_sums(a.w1s, H1, KS, a.xs, KS, a.u, H1, a.n_req);
+    fc_layer_sums(a.w1c, H1, KC, a.xc, KC, r1, H1, a.batch);
+    Pool::get().run((a.batch + 63) / 64, [&](int unit) {
+        for (int i = unit * 64; i < a.batch && i < (unit + 1) * 64; i++) {
+            int r = a.off ? 0 : i / (a.batch / a.n_req);
+            if (a.off) {
+                int lo = 0, hi = a.n_req;
+                while (lo < hi) {
+                    const int mid = lo + ((hi - lo) >> 1);
+                    if (a.off[mid] <= i) lo = mid + 1;
+                    else hi = mid;
+                }
+                r = lo - 1;
+            }
+            r = r < 0 ? 0 : (r >= a.n_req ? a.n_req - 1 : r);
+            const float *u = a.u + (size_t)r * H1;
+            float *v = r1 + (size_t)i * H1;
+            for (int n = 0; n < H1; n++) v[n] = v[n] + u[n];
+        }
+    });
+    fc_epilogue(r1, H1, H1, a.batch, a.epi[0]);
+    fc_layer(a.w[1], a.fc[2], a.fc[1], r1, a.fc[1], r2, a.fc[2], a.batch, a.epi[1]);
+    fc_layer(a.w[2], a.fc[3], a.fc[2], r2, a.fc[2], r3, a.fc[3], a.batch, a.epi[2]);
+    fc_layer(a.w[3], a.fc[4], a.fc[3], r3, a.fc[3], a.scores, a.fc[4], a.batch, a.epi[3]);
+    return bad;
+}
+
 // ---- keyed lookups: the CPU twins of key_resolve_kernel, key_put_kernel and key_fill_kernel (fr_keys.hip) ---------------------------------------
 // The rows are fr_keys.h's own functions of the key, the column record and the map, so they are the device's bit for bit.
 void frc_resolve_keys(const FrKeyResolveArgs &a) {

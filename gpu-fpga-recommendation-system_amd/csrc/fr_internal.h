@@ -321,6 +321,55 @@ static inline int fr_request_tile(int W) {
 // Enqueues the one expansion launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
 extern "C" int fr_request_launch(const FrRequestArgs *args, void *stream);
 
+// ---- factored FC1 of request-form batches (fr_reqfc.hip -> libfleetrec_reqfc.so, the seventh companion code object; fr_cpu.cpp has the twin) ----
+// Operands are the stage pipeline's feature-major 16-byte elements: `rows` element rows of 4 k (fp32, q4) or 8 k (bf16, q8) -- ANY count: a k-group
+// whose second row lies past the operand reads zeros.  U: `nparts` partial buffers [ldr][H1] fp32, request-major, ldr = round_up(n_req, 32).
+constexpr int FR_REQFC_MAX_PARTS = 4;    // partial U buffers the K_S sum is cut into at most
+constexpr int FR_REQFC_PART_LDR = 64;    // ... and only while ldr is at most this (more requests fill the chip with their own tiles)
+struct FrReqfcUserArgs {
+    const void *w;           // W1_S image [rows][H1]
+    const void *x;           // X_S [rows][ldr]: pad requests [n_req, ldr) are zeros
+    float *u;                // [nparts][ldr][H1]
+    int rows, H1, ldr, nparts;
+    int precision;           // FR_FC_FP32 / FR_FC_BF16
+};
+struct FrReqfcCandArgs {
+    const void *w;           // W1_C image [rows][H1]
+    const void *x;           // X_C [rows][ldm]: pad items [batch, ldm) are zeros
+    void *r1;                // R1 as stage 2 reads it: [H1 / E][ldm] 16-byte elements of E = 4 fp32 / 8 bf16 outputs
+    const float *u;          // reqfc_user_kernel's partials
+    const int32_t *off;      // [n_req + 1] or NULL: n_req equal requests
+    int *err_flag;           // raised when off is malformed (off[0] != 0, a decreasing pair, off[n_req] != batch)
+    int rows, H1, ldm, batch, n_req, ldr, nparts;
+    int precision;
+    FrEpi epi;               // FC1's epilogue; {NULL, 0}: none
+};
+// partial buffers of a launch over `groups` k-groups: enough workgroups for the chip's 256 CUs, at least 4 k-groups per part
+static inline int fr_reqfc_parts(int H1, int ldr, int groups) {
+    if (ldr > FR_REQFC_PART_LDR) return 1;
+    const int tiles = (H1 / 32) * (ldr / 32);
+    int p = tiles > 0 ? 256 / tiles : 1;
+    p = p > groups / 4 ? groups / 4 : p;
+    return p < 1 ? 1 : (p > FR_REQFC_MAX_PARTS ? FR_REQFC_MAX_PARTS : p);
+}
+// Each enqueues its one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_reqfc_user_launch(const FrReqfcUserArgs *args, void *stream);
+extern "C" int fr_reqfc_cand_launch(const FrReqfcCandArgs *args, void *stream);
+// The CPU twin's arguments (frc_reqfc, fr_cpu.cpp): plain host memory, fp32, item-major.  ws / wc: the two descriptor lists (dst_stride = the side's
+// words, so frc_gather writes item-major [n][4 x words] records); w1s / w1c: W1's columns of each side, K-major [4 x words][H1] like the master.
+struct FrReqfcCpuArgs {
+    const FrWordDesc *ws, *wc;
+    int n_ws, n_wc;
+    const float *w1s, *w1c;
+    const float *const *w;       // [4]: the master weights (FC2, FC3 and the output layer are read)
+    const FrEpi *epi;            // [4]
+    const int32_t *fc;           // [5]
+    const int32_t *off, *req, *cand;
+    const float *req_dense, *cand_dense;
+    int batch, n_req, Rs, Rc;
+    float *xs, *xc, *u, *scratch, *scores;   // [n_req][K_S], [batch][K_C], [n_req][H1], [batch][H1 + H2 + H3], [batch]
+};
+
 // ---- keyed lookups (fr_keys.hip -> libfleetrec_keys.so, the third companion code object; fr_cpu.cpp has the twins; fr_keys.h: slot, mix64, probe) ----
 constexpr int FR_KEY_PER_THREAD = 4;     // keys a thread of key_resolve_kernel resolves per chunk: their first probes are in flight together
 struct FrKeyResolveArgs {
@@ -494,6 +543,23 @@ struct fr_ctx {
         size_t d_first = 0;                // where the table starts inside d_req_desc
     } req_form[3];
     FrBuf<int32_t> d_req_desc;             // the three tables, one after the other
+    // Factored FC1 of request-form batches (fr_reqfc.hip): the split images -- per side (0 request, 1 candidate) the subset of h_words with compact
+    // destination words and the side's own index columns, and W1's columns of that side as the chain's weight image.  Built lazily by the first
+    // factored call (reqfc_ensure, fr_api.cpp) and again when the split, W1, the precision or the tables' place has changed; reqfc_gen counts the builds.
+    struct ReqfcSide {
+        std::vector<FrWordDesc> h_words;
+        FrBuf<FrWordDesc> d_words;         // GPU contexts
+        FrBuf<float> w1;                   // W1's columns of the side, K-major [4 x (n_words + pad)][H1] (the bf16 pad word's rows are zeros)
+        FrBuf<float> img;                  // GPU contexts: q4 / q8 image of w1
+        int n_words = 0, rows = 0;         // words the side's gather writes (bf16: the pad word included); 16-byte element rows of its operands (fp32: n_words, bf16: n_words / 2)
+    } reqfc[2];
+    FrBuf<float> reqfc_zero;               // GPU contexts: 64 zero bytes, the source row of a side's bf16 pad word (and the index row of a side without index columns)
+    uint64_t reqfc_gen = 0;
+    uint64_t reqfc_split_gen = 0, reqfc_weights_gen = 0;   // what the images were made from: req_split_gen, weights_gen, ...
+    int reqfc_prec = -1;                                   // ... the precision ...
+    const void *reqfc_arena = nullptr;                     // ... and the table arena the descriptors point into
+    uint64_t req_split_gen = 1;            // bumped by every fr_ctx_set_request_columns
+    uint64_t weights_gen = 1;              // bumped by every change of a layer's weights
     // Keyed lookups (fr_ctx_set_key_space): one key space per index column.  `keyed` turns true with the first non-default key space and stays: workers
     // created from then on carry the pinned key rows of the host form.  The records and the word -> column tables a resolve reads live in device memory
     // (plain host memory on the CPU back-end); the tables follow the pooling and the request split, so they are made again, under key_mutex, by the first
@@ -595,6 +661,10 @@ struct fr_worker {
     FrBuf<float> h_req_dense;        // [max_batch][dense_len]; NULL unless dense_shared
     FrBuf<int32_t> h_req_off;        // [max_batch + 1]
     int req_idx_cap = 0, req_w_cap = 0;   // request words per request at creation: max(Rs, Rs') and Rs'
+    // Factored FC1: the two gathered operands and the request-side products, there on a worker created after fr_ctx_set_request_columns and sized for
+    // the split as it stood then (device memory; item-major host memory on the CPU back-end)
+    FrBuf<float> d_reqfc_xs, d_reqfc_xc, d_reqfc_u;
+    int reqfc_ws_cap = 0, reqfc_wc_cap = 0;   // record words per side the operands hold (the bf16 pad word included)
     FrBuf<float> d_pool_w;           // [max_batch][pool_w_cap]: the expanded per-sample weights (host memory on the CPU back-end)
     // Keyed lookups: the pinned key rows of the host form (fr_worker_key_ptr), there on a worker created after the context's first non-default key space;
     // the counter of MAPPED lookups that found no key (device memory; made by the worker's first resolve)
@@ -624,6 +694,7 @@ struct fr_worker {
         bool active = false;
         uint64_t launch0 = 0;   // launch number of its stage 0
         int first_stage = 0;    // 0 normally; 1 for fc_only (activations supplied by a transpose)
+        bool whole_in = false;  // the batch entered at stage 2 with a WHOLE, finished R1 (the factored FC1, reqfc_enqueue alone sets it): no partials, no epi_in
         int batch = 0, ldm = 0;
         const int32_t *d_idx = nullptr;
         const float *d_dense = nullptr;
@@ -729,6 +800,9 @@ int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, in
 int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int k, int32_t *top_idx, float *top_scores);
 // the CPU twin of fr_request_launch: the same words, items over the pool's threads; -> 1 when the offsets were malformed, else 0
 int frc_expand_requests(const FrRequestArgs &a);
+// the CPU twin of the factored chain (fleetrec_serving.h states the arithmetic): both gathers, U, V + U[owner], FC1's epilogue, then the chain's own
+// FC2 / FC3 / output layer; -> 1 when the offsets were malformed (owners are clamped all the same), else 0; a row out of range raises *err_flag
+int frc_reqfc(const FrReqfcCpuArgs &a, int *err_flag);
 // the CPU twins of fr_key_resolve_launch (words over the pool's threads), fr_key_put_launch (pair after pair, ONE writer at a time -- the callers hold
 // fr_ctx::lp_mutex; readers need no lock: the key is published before the row --: of a key listed twice the last row stays;
 // -> the FR_KEYS_ERR_* bits of the pairs that were not applied) and fr_key_fill_launch

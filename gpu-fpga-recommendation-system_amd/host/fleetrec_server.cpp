@@ -41,7 +41,8 @@
 //                        columns are the request's, with --shared-dense the dense features too; a block is S equal requests of batch / S candidates
 //                        (batch % S == 0).  On the wire: int32 [S][Rs] request rows, then float32 [S][dense_len] with --shared-dense, then int32 [B][Rc]
 //                        candidate rows, then the per-item dense rows where they are not shared (Rs = N, Rc = index columns - N; with --hots H both x H,
-//                        and the call is fr_worker_submit_requests(..., pooled = 1) in the sum or mean fold).  The rows are expanded on the device; the
+//                        and the call is fr_worker_submit_requests(..., pooled = 1) in the sum or mean fold; with --factored, one-hot blocks only -- not with
+//                        --hots --, the call is fr_worker_submit_requests_factored: the same wire format and replies, no expansion on the device).  The rows are expanded on the device; the
 //                        scores, and with --topk K the S x K pairs of the reply (--segments, if given, must equal S; omitted it is S), are those of the
 //                        expanded block.  Not with --stream, --shards, --csr or --pool weighted; N = 1 .. index columns - 1 unless --shared-dense
 //                        (fleetrec_sender takes the same three options).
@@ -110,6 +111,7 @@ struct Options {
     int requests = 0;      // --requests S: request-form blocks of S equal requests (0: full rows)
     int shared_cols = 0;   // --shared-cols N: the first N index columns are the request's
     bool shared_cols_given = false, shared_dense = false;   // --shared-dense: the dense features are the request's too
+    bool factored = false; // --factored (with --requests): fr_worker_submit_requests_factored, FC1 once per request + once per candidate, no expansion
 };
 
 static bool read_exact(int fd, void *buf, size_t n) {  // the recv loop of cuda_server.c:425-450
@@ -527,7 +529,7 @@ static void thread_consume(ThreadInfo *t, const Options &o) {
                 break;
             }
             const auto t_recv = std::chrono::steady_clock::now();  // network_time / cuda_time pair of cuda_server.c:429,462
-            if ((o.requests > 0 ? fr_worker_submit_requests(wk, o.batch, o.requests, o.hots > 0 ? 1 : 0) : o.csr ? fr_worker_submit_pooled_csr(wk, o.batch, o.pool == 2) : weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
+            if ((o.factored ? fr_worker_submit_requests_factored(wk, o.batch, o.requests) : o.requests > 0 ? fr_worker_submit_requests(wk, o.batch, o.requests, o.hots > 0 ? 1 : 0) : o.csr ? fr_worker_submit_pooled_csr(wk, o.batch, o.pool == 2) : weight_bytes ? fr_worker_submit_pooled_weighted(wk, o.batch) : o.hots > 0 ? fr_worker_submit_pooled(wk, o.batch) : fr_worker_submit(wk, o.batch)) != FR_OK) {
                 t->status = -5;
                 t->error = fr_last_error();
                 break;
@@ -623,6 +625,7 @@ int main(int argc, char **argv) {
         else if (a == "--topk") { o.topk = atoi(next()); o.topk_given = true; }
         else if (a == "--segments") { o.segments = atoi(next()); o.segments_given = true; }
         else if (a == "--requests") o.requests = atoi(next());
+        else if (a == "--factored") o.factored = true;
         else if (a == "--shared-cols") { o.shared_cols = atoi(next()); o.shared_cols_given = true; }
         else if (a == "--shared-dense") o.shared_dense = true;
         else if (a == "--pool") {
@@ -645,6 +648,8 @@ int main(int argc, char **argv) {
         return 2;
     }
     if (o.requests == 0 && (o.shared_cols_given || o.shared_dense)) { fprintf(stderr, "--shared-cols / --shared-dense need --requests S\n"); return 2; }
+    if (o.factored && o.requests == 0) { fprintf(stderr, "--factored needs --requests S --shared-cols N\n"); return 2; }
+    if (o.factored && o.hots > 0) { fprintf(stderr, "--factored is not served with --hots: the factored FC1 takes one-hot request-form blocks only\n"); return 2; }
     if (o.requests != 0) {   // request-form blocks: the submit-and-sync path, full or padded pooled rows, unweighted
         const char *with = o.stream ? "--stream (its blocks are host-fed full rows)" : o.shards > 0 ? "--shards (a sharded context takes no request split)" :
                            o.csr ? "--csr (the request form cuts padded rows)" : o.pool == 2 ? "--pool weighted" : nullptr;

@@ -50,6 +50,8 @@ extern "C" {
  * Still 6, additive: request-form batches, request rows + candidate rows + segment offsets expanded on the device (fleetrec_serving.h:
  * fr_ctx_set_request_columns, fr_ctx_request_words, fr_worker_expand_requests_device, fr_worker_request_*_ptr, fr_worker_submit_requests) -- every
  * existing entry point is as before, with or without a split.
+ * Still 6, additive: factored request-form batches, FC1 computed once per request for the shared columns and once per item for the others
+ * (fleetrec_serving.h: fr_worker_push_requests_factored_device, fr_worker_submit_requests_factored) -- every existing entry point is as before.
  * Still 6, additive: an opt-in per-layer bias and ReLU of the FC chain (fleetrec_serving.h: fr_ctx_set_epilogue, fr_ctx_epilogue), honoured by every
  * kernel that finishes a layer and by the CPU back-end -- a context that never sets one computes, names its kernels and performs as before.
  * 5 (round 5): fr_ctx_create(device = -1) = the CPU back-end, fr_cpu_set_threads; fr_ctx_set_chain_width / fr_ctx_chain_width (the GEMM tile

@@ -345,6 +345,35 @@ float *fr_worker_request_dense_ptr(fr_worker *w);      /* pinned float [max_batc
 int32_t *fr_worker_request_offsets_ptr(fr_worker *w);  /* pinned int32 [max_batch + 1] */
 int fr_worker_submit_requests(fr_worker *w, int batch, int n_req, int pooled /* 0 one-hot, 1 pooled, 2 pooled weighted */);
 
+/* Factored request-form batches (additive in ABI 6): FC1 is linear in its input, and the request's part of the feature vector is the same for all of
+ * a request's candidates, so  W1 x = W1[:, S] x_S(request) + W1[:, C] x_C(candidate)  with S the k of the shared columns (and of the dense features
+ * when dense_shared) and C the others.  With a split set, the two entry points below score a request-form batch WITHOUT expanding it: the request
+ * rows are gathered n_req times instead of batch times, the first term is computed once per request, and no expansion launch is made.
+ * Arithmetic:  U[r][n] = sum_{k in S} W1[n][k] x[r][k],  V[b][n] = sum_{k in C} W1[n][k] x[b][k],  both accumulated in fp32 in the kernel's own k
+ *   order (in the bf16 chain on bf16 operands, as FC1 always is).  s = fl(V[b][n] + U[owner(b)][n]); then, with an epilogue set on FC1
+ *   (fr_ctx_set_epilogue), s = fl(s + b1[n]) and ReLU that keeps a NaN; then the chain's own rounding of R1: none in fp32, RNE in bf16.  owner(b) is
+ *   the last r with off[r] <= b, clamped into [0, n_req) -- the rule of the expansion above.  FC2, FC3 and the output layer are the chain's own,
+ *   unchanged.  Scores are NOT promised bit-identical to the full-row path (the K sum is cut in two): they are identical wherever the fp32 sums are
+ *   exact and within the project's score bars otherwise.
+ * fr_worker_push_requests_factored_device: stream-ordered and un-flushed, under the rules of fr_worker_push_pooled_device (batches queued for a fused
+ *   launch are launched first; fr_worker_sync drains); buffer lifetime as for fr_worker_push_device.  d_req_rows int32 [n_req][Rs], d_cand_rows int32
+ *   [batch][Rc], the widths of fr_ctx_request_words(FR_REQ_ONE_HOT); dense features float [n_req][dense_len] in d_req_dense when dense_shared,
+ *   float [batch][dense_len] in d_cand_dense otherwise (the other pointer is not read).
+ * fr_worker_submit_requests_factored: the host form, on the pinned buffers and with the host-side checks of fr_worker_submit_requests(w, batch,
+ *   n_req, 0).  One batch in flight, completed by fr_worker_sync; it counts as the host-form batch in flight, so fr_worker_topk with the same offsets
+ *   ranks it.
+ * Errors: malformed offsets raise the worker's sticky index-range word (FR_ERR_INDEX_RANGE at fr_worker_sync) and never cause a read outside the
+ *   arrays; a row out of range is reported by the gather as today; empty requests are legal.
+ * Refusals: no split set: FR_ERR_STATE.  A pooled context: FR_ERR_STATE.  An fp8 chain: FR_ERR_STATE.  A sharded context: FR_ERR_STATE.  A context
+ *   that is not SEMANTIC-layout, an FC1 whose width is no multiple of 32, a worker created before the split: FR_ERR_STATE.  n_req outside
+ *   1 .. max_batch, a NULL pointer that the split needs, NULL offsets with batch % n_req != 0: FR_ERR_INVALID.  Every model whose chain the stage
+ *   pipeline runs is taken at every batch: R1 enters the pipeline whole, whatever K split FC1 would have had.
+ * fr_worker_last_kernel names reqfc_cand_kernel<...>.  The CPU back-end computes the same contract in plain fp32 loops before the call returns. */
+int fr_worker_push_requests_factored_device(fr_worker *w, int batch, int n_req, const int32_t *d_seg_offsets /* NULL: equal */, const int32_t *d_req_rows,
+                                            const int32_t *d_cand_rows, const float *d_req_dense /* or NULL */, const float *d_cand_dense /* or NULL */,
+                                            float *d_scores);
+int fr_worker_submit_requests_factored(fr_worker *w, int batch, int n_req);
+
 /* Keyed lookups (additive in ABI 6): the id -> row step in front of every lookup path.  Every entry point above takes int32 ROW NUMBERS; a serving host
  * holds 64-bit feature ids (hashed strings, item ids, user ids).  With a KEY SPACE set on an index column, one small launch turns int64 keys into the
  * int32 rows every existing path takes; nothing downstream changes.
