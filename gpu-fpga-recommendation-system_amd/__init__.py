@@ -90,7 +90,7 @@ ABI_SYMBOLS = [
     "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
     "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
     "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
-    "fr_worker_topk_device", "fr_worker_topk",
+    "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
     "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -110,7 +110,7 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_push_pooled_device", "fr_worker_push_pooled_csr_device", "fr_worker_push_pooled_device_list",
                    "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
                    "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
-                   "fr_worker_topk_device", "fr_worker_topk",
+                   "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -202,6 +202,7 @@ def lib():
         "fr_worker_submit_sharded_pooled": (i32, [vp, vp, i32, i32]), "fr_worker_submit_sharded_pooled_csr": (i32, [vp, vp, i32, i32]),
         "fr_worker_calibrate_fp8_sharded_pooled": (i32, [vp, vp, i32, i32]),
         "fr_worker_topk_device": (i32, [vp, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_topk": (i32, [vp, i32, i32, vp, i32, vp, vp]),
+        "fr_worker_retrieve_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
         "fr_ctx_set_request_columns": (i32, [vp, pi, i32, i32]), "fr_ctx_request_words": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
         "fr_worker_request_idx_ptr": (pi, [vp]), "fr_worker_request_weights_ptr": (pf, [vp]), "fr_worker_request_dense_ptr": (pf, [vp]),
@@ -1275,6 +1276,25 @@ class Worker:
             raise
         self.sync()
         return out_i, out_s
+
+    # top-K inner-product retrieval over a table window (fr_worker_retrieve_device / fr_worker_retrieve) ------------------------------
+    def retrieve_device(self, table, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores=None):
+        """fr_worker_retrieve_device: for the n_q device queries float32 [n_q][dim] the k rows of table[row0 .. row0 + n_rows) with the largest inner
+        product, on the worker's stream behind everything submitted or pushed before; d_top_rows int32 [n_q][k] (absolute rows, -1 past the window's
+        rows), d_top_scores float32 [n_q][k] or None.  Asynchronous: sync() is the completion point, the buffers stay valid until then."""
+        _check(lib().fr_worker_retrieve_device(self._h, int(table), int(row0), int(n_rows), int(n_q), self._ptr(d_queries), int(k), self._ptr(d_top_rows), self._ptr(d_top_scores)))
+
+    def retrieve(self, table, queries, k, row0=0, n_rows=None):
+        """fr_worker_retrieve, then sync(): queries float32 [n_q][dim] (or uint32 bit patterns) -> (rows int32 [n_q][k], scores float32 [n_q][k])."""
+        q = np.ascontiguousarray(queries)
+        q = q.view(np.float32) if q.dtype == np.uint32 else np.ascontiguousarray(q, dtype=np.float32)
+        if n_rows is None:
+            n_rows = int(self.ctx.model.desc.tables[table].rows) - int(row0)
+        out_r, out_s = np.empty((q.shape[0], int(k)), np.int32), np.empty((q.shape[0], int(k)), np.float32)
+        _check(lib().fr_worker_retrieve(self._h, int(table), int(row0), int(n_rows), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), int(k),
+                                        out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
+        self.sync()
+        return out_r, out_s
 
     def infer_topk(self, idx, k, seg_offsets=None, dense=None):
         """infer() with the ranking on the device: idx int32 [B][idx_cols] (+ dense) -> (positions int32 [n_seg][k], scores float32 [n_seg][k]) of the

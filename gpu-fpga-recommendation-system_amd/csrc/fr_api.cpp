@@ -2888,6 +2888,111 @@ extern "C" int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t 
     return FR_OK;
 }
 
+// ---- top-K inner-product retrieval (fleetrec_serving.h) ----------------------------------------------------------------------------------------
+// The kernels are the eighth companion code object's (fr_retrieve.hip -> libfleetrec_retrieve.so); the chunking rule is fr_retrieve_chunk
+// (fr_internal.h), the merge is the ranking companion's, the CPU twin is frc_retrieve.
+static int retrieve_check(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const void *queries, int k, const void *top_rows) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    const fr_ctx *c = w->ctx;
+    if (!queries || !top_rows) FR_FAIL(FR_ERR_INVALID, "queries / top_rows is NULL");
+    if (table < 0 || table >= c->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (k < 1 || k > FR_RETRIEVE_MAX_K) FR_FAIL(FR_ERR_INVALID, "k = %d outside [1, %d]", k, FR_RETRIEVE_MAX_K);
+    if (n_q < 1 || n_q > 65536) FR_FAIL(FR_ERR_INVALID, "n_q = %d queries outside [1, 65536]", n_q);
+    const int64_t rows = c->tables[table].rows;
+    if (n_rows < 1 || row0 < 0 || row0 > rows - n_rows)
+        FR_FAIL(FR_ERR_INVALID, "the window [%lld, %lld + %lld) is empty or leaves table %d (%lld rows)", (long long)row0, (long long)row0, (long long)n_rows, table, (long long)rows);
+    if (row0 + n_rows > (1ll << 31)) FR_FAIL(FR_ERR_INVALID, "the window ends past row 2^31, which an int32 row number cannot name");
+    if (c->model.index_mode == FR_INDEX_PER_BANK || c->table_mem[table].il_rows)
+        FR_FAIL(FR_ERR_STATE, "retrieval reads dense tables; the tables of an FR_INDEX_PER_BANK context are interleaved in bank rows");
+    if (c->n_shards > 1 || !c->table_mem[table].resident) FR_FAIL(FR_ERR_STATE, "retrieval is not available on a table-sharded context (shard %d of %d)", c->shard_rank, c->n_shards);
+    if (c->tables[table].dim > FR_RETRIEVE_MAX_DIM) FR_FAIL(FR_ERR_STATE, "table %d has dim %d; retrieval holds a query in registers up to dim %d", table, c->tables[table].dim, FR_RETRIEVE_MAX_DIM);
+    return FR_OK;
+}
+
+// The launches of one retrieval on the worker's stream, behind everything submitted or pushed before (the rule of topk_enqueue).  h_queries != NULL:
+// the host form -- they are the pinned staging, copied into the scratch first.
+static int retrieve_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, const float *h_queries, int k, int32_t *d_top_rows, float *d_top_scores) {
+    fr_ctx *c = w->ctx;
+    FR_TRY(fr_host_fed_queued(w, "retrieve"));
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
+    FR_SET_DEVICE(c);
+    const int dim = c->tables[table].dim;
+    FrRetrieveArgs a{};
+    a.table = reinterpret_cast<const float *>(c->table_arena + c->table_mem[table].byte_offset);
+    a.dim = dim, a.n_q = n_q, a.k = k, a.row0 = row0, a.n_rows = n_rows;
+    a.chunk = fr_retrieve_chunk(n_rows, n_q, k, c->n_cu);
+    a.n_chunks = (int)((n_rows + a.chunk - 1) / a.chunk);
+    const size_t n_part = (size_t)n_q * (size_t)a.n_chunks * (size_t)k;   // <= 2^24
+    const size_t plane = align_up(n_part * 4, 256), off_bytes = align_up(((size_t)n_q + 1) * 4, 256), pos_bytes = align_up((size_t)n_q * k * 4, 256);
+    const size_t q_bytes = h_queries ? align_up((size_t)n_q * dim * 4, 256) : 0;
+    const size_t need = 2 * plane + off_bytes + pos_bytes + q_bytes;
+    if (need > w->d_retrieve.count()) {
+        if (w->d_retrieve) FR_HIP(hipStreamSynchronize(w->stream));   // an earlier retrieval may still use it
+        FR_TRY(w->d_retrieve.grow(FrMem::DEVICE, need, "retrieval scratch"));
+    }
+    char *base = w->d_retrieve.p;
+    a.part_scores = reinterpret_cast<float *>(base);
+    a.part_rows = reinterpret_cast<int32_t *>(base + plane);
+    a.seg_off = reinterpret_cast<int32_t *>(base + 2 * plane);
+    int32_t *top_pos = reinterpret_cast<int32_t *>(base + 2 * plane + off_bytes);
+    a.top_pos = top_pos, a.top_rows = d_top_rows, a.top_scores = d_top_scores;
+    a.queries = d_queries;
+    int rc = fr_fused_flush(w);
+    if (!rc) rc = pipeline_flush(w);
+    if (rc) return rc;
+    if (h_queries) {
+        float *dq = reinterpret_cast<float *>(base + 2 * plane + off_bytes + pos_bytes);
+        FR_HIP(hipMemcpyAsync(dq, h_queries, (size_t)n_q * dim * 4, hipMemcpyHostToDevice, w->stream));
+        a.queries = dq;
+    }
+    int e = fr_retrieve_launch(&a, 0, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the retrieval scan launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true;
+    // the n_chunks * k partial scores of every query are one segment of the ranking; its positions index the planes
+    FR_TRY(topk_enqueue(w, (int)n_part, a.part_scores, n_q, a.seg_off, k, top_pos, nullptr));
+    e = fr_retrieve_launch(&a, 1, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the retrieval row-mapping launch failed: %s", hipGetErrorString((hipError_t)e));
+    return FR_OK;
+}
+
+static const float *retrieve_cpu_table(const fr_ctx *c, int table) { return reinterpret_cast<const float *>(c->table_arena + c->table_mem[table].byte_offset); }
+
+extern "C" int fr_worker_retrieve_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, int k, int32_t *d_top_rows, float *d_top_scores) {
+    int rc = retrieve_check(w, table, row0, n_rows, n_q, d_queries, k, d_top_rows);
+    if (rc) return rc;
+    if (w->ctx->cpu) {   // computed before the call returns
+        frc_retrieve(retrieve_cpu_table(w->ctx, table), w->ctx->tables[table].dim, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores);
+        return FR_OK;
+    }
+    return retrieve_enqueue(w, table, row0, n_rows, n_q, d_queries, nullptr, k, d_top_rows, d_top_scores);
+}
+
+extern "C" int fr_worker_retrieve(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows, float *h_top_scores) {
+    int rc = retrieve_check(w, table, row0, n_rows, n_q, h_queries, k, h_top_rows);
+    if (rc) return rc;
+    if (w->ctx->cpu) {
+        frc_retrieve(retrieve_cpu_table(w->ctx, table), w->ctx->tables[table].dim, row0, n_rows, n_q, h_queries, k, h_top_rows, h_top_scores);
+        return FR_OK;
+    }
+    if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking or retrieval is already in flight on this worker: call fr_worker_sync first");
+    FR_TRY(fr_host_fed_queued(w, "retrieve"));   // (before the staging is touched: nothing happens on a refusal)
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
+    FR_SET_DEVICE(w->ctx);
+    const size_t n_query = (size_t)n_q * (size_t)w->ctx->tables[table].dim, n_out = (size_t)n_q * (size_t)k;
+    if (n_query > w->h_rt_q.count() || n_out > w->h_tk_idx.count() || n_out > w->h_tk_sc.count()) {   // a grow waits for the stream before pinned memory is released
+        FR_HIP(hipStreamSynchronize(w->stream));
+        FR_TRY(w->h_rt_q.grow(FrMem::PINNED, n_query, "retrieval queries"));
+        FR_TRY(w->h_tk_idx.grow(FrMem::PINNED, n_out, "ranking results"));
+        FR_TRY(w->h_tk_sc.grow(FrMem::PINNED, n_out, "ranking result scores"));
+    }
+    memcpy(w->h_rt_q, h_queries, n_query * sizeof(float));
+    // the results come back through the host-form ranking's staging and are delivered by fr_worker_sync as its results are
+    rc = retrieve_enqueue(w, table, row0, n_rows, n_q, nullptr, w->h_rt_q, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr);
+    if (rc) return rc;
+    w->tk_dst_idx = h_top_rows, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
+    return FR_OK;
+}
+
 // ---- request-form batches (fleetrec_serving.h) -------------------------------------------------------------------------------------------------
 // The kernel is the second companion code object's (fr_request.hip -> libfleetrec_request.so, linked with an $ORIGIN rpath); the descriptor tables,
 // state and the host form are here, the CPU twin in fr_cpu.cpp.

@@ -270,6 +270,36 @@ int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int
     return bad.load(std::memory_order_relaxed);
 }
 
+// Top-K retrieval: per query the composites of fr_retrieve.hip -- (key << 32) | (0xffffffff - (row - row0)) -- over the window and a partial sort.  The
+// sum starts at -0, the identity of the addition, and runs in ascending c; no read outside table[row0 .. row0 + n_rows) and queries[n_q][dim].
+void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores) {
+    const int units = n_q < Pool::get().size() ? n_q : Pool::get().size();
+    Pool::get().run(units, [&](int u) {
+        std::vector<uint64_t> comp((size_t)n_rows);
+        const int qa = (int)((int64_t)n_q * u / units), qb = (int)((int64_t)n_q * (u + 1) / units);
+        for (int q = qa; q < qb; q++) {
+            const float *qv = queries + (size_t)q * (size_t)dim;
+            for (int64_t i = 0; i < n_rows; i++) {
+                const float *t = table + (size_t)(row0 + i) * (size_t)dim;
+                float acc = -0.0f;
+                for (int c = 0; c < dim; c++) acc += qv[c] * t[c];
+                uint32_t bits;
+                memcpy(&bits, &acc, 4);
+                comp[(size_t)i] = ((uint64_t)fr_rank_key(bits) << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
+            }
+            const size_t top = (size_t)n_rows < (size_t)k ? (size_t)n_rows : (size_t)k;
+            std::partial_sort(comp.begin(), comp.begin() + (ptrdiff_t)top, comp.end(), std::greater<uint64_t>());
+            for (size_t j = 0; j < (size_t)k; j++) {
+                const size_t o = (size_t)q * (size_t)k + j;
+                const uint32_t key = j < top ? (uint32_t)(comp[j] >> 32) : 0u;
+                const uint32_t bits = j >= top ? 0xff800000u : (key == 0u ? 0x7fc00000u : ((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key));
+                top_rows[o] = j < top ? (int32_t)(row0 + (int64_t)(0xffffffffu - (uint32_t)comp[j])) : -1;
+                if (top_scores) memcpy(top_scores + o, &bits, 4);
+            }
+        }
+    });
+}
+
 int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale) {
     const uint32_t h0 = fr_weight_hash_seed(seed, layer);
     const size_t chunk = 1 << 16;

@@ -297,6 +297,40 @@ static inline int fr_rank_units(int n) { return n > FR_RANK_PART ? 2 * ((n + FR_
 // Enqueues the ranking on `stream` (a hipStream_t); wave_form: one wave per segment instead of a 256-thread workgroup.  -> 0 or the hipError_t value.
 extern "C" int fr_rank_launch(const FrRankArgs *args, int wave_form, void *stream);
 
+// ---- top-K inner-product retrieval (fr_retrieve.hip -> libfleetrec_retrieve.so, the eighth companion code object; fr_cpu.cpp has the twin) ----
+// The window [row0, row0 + n_rows) of one dense table is cut into n_chunks chunks of `chunk` rows (a multiple of FR_RETRIEVE_ROUND, at least
+// FR_RETRIEVE_MIN_CHUNK, so that only the LAST chunk can hold fewer than k rows); retrieve_scan_kernel leaves the k leaders of every (query, chunk) in
+// the two planes, fr_rank_launch ranks the n_chunks * k partial scores of a query as one segment, retrieve_rows_kernel maps positions to rows.
+constexpr int FR_RETRIEVE_QTILE = 32;         // queries one workgroup holds as the A operand
+constexpr int FR_RETRIEVE_ROUND = 128;        // table rows a workgroup (4 waves x one 32-row MFMA tile) scores between two votes
+constexpr int FR_RETRIEVE_MIN_CHUNK = 1024;   // >= FR_RETRIEVE_MAX_K
+constexpr uint32_t FR_RETRIEVE_PAD_BITS = 0x7fc00000u;   // a list entry without a row: NaN (key 0) in the score plane, -1 in the row plane
+struct FrRetrieveArgs {
+    const float *table;      // row 0 of the table (16-byte aligned), rows dim floats apart
+    const float *queries;    // [n_q][dim]
+    int dim, n_q, k;
+    int64_t row0, n_rows;    // row0 + n_rows <= 2^31
+    int64_t chunk;           // rows per chunk
+    int n_chunks;
+    float *part_scores;      // [n_q][n_chunks][k]: per chunk descending in the rank order, the entries behind the chunk's rows padded
+    int32_t *part_rows;      // [n_q][n_chunks][k] absolute rows, -1 padded
+    int32_t *seg_off;        // [n_q + 1] = q * n_chunks * k: the segments fr_rank_launch takes (written by the scan)
+    const int32_t *top_pos;  // [n_q][k]: fr_rank_launch's answer over part_scores
+    int32_t *top_rows;       // [n_q][k]
+    float *top_scores;       // [n_q][k] or NULL
+};
+// The chunk length for a window: about 2 workgroups per CU over all query tiles, never more partial scores than one ranking call takes (2^24).
+static inline int64_t fr_retrieve_chunk(int64_t n_rows, int n_q, int k, int n_cu) {
+    const int64_t tiles = (n_q + FR_RETRIEVE_QTILE - 1) / FR_RETRIEVE_QTILE;
+    const int64_t want = (2 * (int64_t)n_cu + tiles - 1) / tiles;
+    int64_t c = ((n_rows + want - 1) / want + FR_RETRIEVE_ROUND - 1) / FR_RETRIEVE_ROUND * FR_RETRIEVE_ROUND;
+    if (c < FR_RETRIEVE_MIN_CHUNK) c = FR_RETRIEVE_MIN_CHUNK;
+    while ((int64_t)n_q * k * ((n_rows + c - 1) / c) > (1ll << 24)) c *= 2;
+    return c;
+}
+// step 0: the scan; step 1: the row mapping behind the ranking.  Enqueues one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_retrieve_launch(const FrRetrieveArgs *args, int step, void *stream);
+
 // ---- request-form batches (fr_request.hip -> libfleetrec_request.so, the second companion code object; fr_cpu.cpp has the twin) ----------------
 // Row i of `out` ([batch][W] 32-bit words) is put together word by word: desc[w] >= 0 names word desc[w] of candidate row i ([batch][Rc]),
 // desc[w] < 0 names word ~desc[w] of the request row ([n_req][Rs]) of the request that owns item i -- the last r with off[r] <= i, clamped into
@@ -762,7 +796,12 @@ struct fr_worker {
     FrBuf<float> h_tk_sc;
     int32_t *tk_dst_idx = nullptr;
     float *tk_dst_sc = nullptr;
-    size_t tk_count = 0;         // n_seg * k of the host-form ranking in flight; 0: none
+    size_t tk_count = 0;         // n_seg * k of the host-form ranking (or n_q * k of the host-form retrieval) in flight; 0: none
+    // Top-K retrieval (fr_worker_retrieve_device / fr_worker_retrieve).  d_retrieve: the per-chunk planes, the segment offsets, the ranking's positions
+    // and the host form's queries, allocated by the first call and grown as d_rank is; h_rt_q: the host form's pinned query staging (its results
+    // come back through h_tk_idx / h_tk_sc).
+    FrBuf<char> d_retrieve;
+    FrBuf<float> h_rt_q;
     char last_kernel[96] = "";  // fr_worker_last_kernel: the dominant kernel of the most recent launch this worker enqueued
     FrEvent ev_start, ev_stop;
 };
@@ -798,6 +837,10 @@ int frc_gather_pooled(const FrPooledPlan &p, const FrPooledBatch &b, const FrPoo
 int frc_update_rows(char *arena, const FrTableMem &tm, int dim, int64_t rows, int n, const int32_t *ids, const float *src);
 // the CPU twin of fr_rank_launch: the same outputs bit for bit, segments over the pool's threads; -> 1 when a segment was malformed (ranked as empty), else 0
 int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int k, int32_t *top_idx, float *top_scores);
+// the CPU twin of the retrieval (fleetrec_serving.h states the contract; this function IS its restatement on host arrays): for every query the k rows of
+// table[row0 .. row0 + n_rows) ([..][dim], dense) with the largest score s = -0 + q[0] t[0] + q[1] t[1] + ... in fp32, ascending c, ranked by fr_rank_key
+// with ties to the lower row; a NaN score is delivered as 0x7fc00000; (-1, -inf) behind the window's rows.  Queries over the pool's threads.
+void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores);
 // the CPU twin of fr_request_launch: the same words, items over the pool's threads; -> 1 when the offsets were malformed, else 0
 int frc_expand_requests(const FrRequestArgs &a);
 // the CPU twin of the factored chain (fleetrec_serving.h states the arithmetic): both gathers, U, V + U[owner], FC1's epilogue, then the chain's own

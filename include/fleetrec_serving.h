@@ -285,6 +285,39 @@ int fr_worker_topk_device(fr_worker *w, int n, const float *d_scores, int n_seg,
 int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t *h_seg_offsets /* NULL: one segment */,
                    int k, int32_t *h_top_idx, float *h_top_scores /* or NULL */);
 
+/* Top-K inner-product retrieval over a table (additive in ABI 6): the step BEFORE scoring -- where the candidates come from.  For n_q query vectors the k
+ * rows of the window [row0, row0 + n_rows) of one table with the largest inner product, in stream order, the n_q x n_rows score matrix never stored.
+ * d_top_rows has the shape and type of the item column of candidate rows: retrieve -> candidate rows -> fr_worker_push_requests_factored_device or
+ * fr_worker_submit_requests -> fr_worker_topk is one stream with no host round trip.
+ * Score: s[q][r] = sum over c < dim of queries[q][c] * table[r][c]; operands and accumulation fp32, the sum starting at -0 (the identity of the
+ *   addition: a row whose products are all -0 scores -0) in an order of c that is fixed and the same for every row: the same bits for the same inputs
+ *   on every run, whatever n_q, k, row0, the grid or the chunk a row falls in.  The CPU back-end sums in ascending c; the device in the order of
+ *   DESIGN.md section 3.1e.  Both give the same bits wherever the fp32 sums are exact, and stay within dim * 2^-24 * sum |q_c t_c| of the exact sum.
+ * Rank: the total order of fr_worker_topk_device on the score's 32 bits -- a larger key first, equal keys by LOWER ROW first, NaN last.
+ *   d_top_rows[q][j] = the ABSOLUTE row number (what a lookup path takes as an index), d_top_scores[q][j] (the array may be NULL) = the score's
+ *   bits, every NaN as 0x7fc00000; for j >= n_rows -1 and -inf (0xff800000).  Nothing past [n_q][k] is written; no byte of the table outside the
+ *   window and no byte of d_queries outside [n_q][dim] is read.  d_queries needs 4-byte alignment only.
+ * Stream order: asynchronous on the worker's stream behind everything submitted or pushed on w before the call, by the rule of fr_worker_topk_device
+ *   (queued fused batches are launched first, the stage pipeline is drained by launches, nothing is waited for); a retrieval behind an
+ *   fr_worker_update_rows on the same worker sees the new rows.  fr_worker_sync is the completion point; every buffer stays valid until then.
+ *   fr_worker_last_kernel keeps naming the last batch's kernel.  The worker allocates a scratch at the first call (2 x 4 bytes per query, chunk and k,
+ *   chunks as DESIGN.md states them); a later call that needs a larger one waits for the worker's stream before it replaces it.
+ * FR_ERR_INVALID: a NULL worker, queries or rows pointer; table outside the model; k outside 1 .. FR_RETRIEVE_MAX_K; n_q outside 1 .. 65536; n_rows < 1,
+ *   row0 < 0, row0 + n_rows above the table's rows or above 2^31 (an int32 row number could not name the row).
+ * FR_ERR_STATE: a table with dim > FR_RETRIEVE_MAX_DIM; a table-sharded context (n_shards > 1); an FR_INDEX_PER_BANK context -- its tables are stored
+ *   interleaved in bank rows, and reading them is LEFT OUT of this interface; host-fed batches still queued in a block (flush first) or a table-sharded
+ *   step in flight, as for the top-K.  Nothing is enqueued on an argument or state error.
+ * The CPU back-end computes before it returns.
+ * fr_worker_retrieve: the host form -- h_queries is copied into pinned staging inside the call; h_top_rows / h_top_scores (the latter may be NULL)
+ * receive the results in fr_worker_sync, the way fr_worker_topk delivers its results (and through the same staging: one host-form retrieval OR ranking
+ * may be in flight per worker, a second is FR_ERR_STATE), and stay valid until then. */
+#define FR_RETRIEVE_MAX_K 256   /* = FR_TOPK_MAX_K */
+#define FR_RETRIEVE_MAX_DIM 128
+int fr_worker_retrieve_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries /* [n_q][dim] */, int k,
+                              int32_t *d_top_rows /* [n_q][k] */, float *d_top_scores /* [n_q][k] or NULL */);
+int fr_worker_retrieve(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows,
+                       float *h_top_scores /* or NULL */);
+
 /* Request-form batches (additive in ABI 6): the input side of the segments above.  A request is one user and N candidate items; without this its
  * batch arrives as N complete index rows, the user's columns (and dense features) repeated N times.  With a SPLIT set on the context a batch arrives
  * as request rows + candidate rows + segment offsets, and one small launch expands them on the device into the rows every existing lookup path takes.

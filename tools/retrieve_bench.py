@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Top-K inner-product retrieval on one MI355X -> profiles/retrieve.json.
+
+One table of `--rows` (4 M) rows at dim 32 and one at dim 128, hash-filled; n_q in {1, 32, 256} x k in {16, 256}:
+  call_us      HIP-event time of fr_worker_retrieve_device (scan + ranking of the per-chunk lists + row mapping: all its launches), `--calls` calls
+               back to back between two events on the worker's stream, `--repeats` windows, the median.
+  hbm_share    one pass over the window (rows x dim x 4 bytes) at 8 TB/s over call_us: the floor while n_q <= 32.
+  mfma_share   2 x n_q x rows x dim flops at the f32 matrix peak (157.3 TFLOP/s) over call_us: the floor at n_q = 256.
+  torch_us     what a caller does today, same shapes, uniform rows of its own: torch.topk(q @ T[chunk].T) over chunks of 2^18 rows, then a final topk
+               over the chunks' leaders; torch events.  Measured FIRST, in a child process of its own (torch brings its own HIP runtime, and two
+               runtimes do not share a process); a child that ends in anything but a clean exit or a Python error ends the tool.
+  adversarial  dim 32, n_q 32, k 256 over rows whose scores ascend with the row for every query: every tile beats every threshold.
+The process is the only one on the GPU; a failure ends it with a non-zero status and nothing more is started.
+
+    python tools/retrieve_bench.py [--out profiles/retrieve.json]      --rehearse: the CPU back-end, 20000 rows, no torch leg (times are not measurements)
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HBM_BYTES_PER_S, MFMA_F32_FLOPS = 8.0e12, 157.3e12
+
+
+def timed(wk, call, calls, repeats):
+    for _ in range(3):
+        call()
+    wk.sync()
+    us = []
+    for _ in range(repeats):
+        wk.timer_start()
+        for _ in range(calls):
+            call()
+        ms = wk.timer_stop_ms()
+        wk.sync()
+        us.append(1e3 * ms / calls)
+    return float(np.median(us)), [round(u, 2) for u in us]
+
+
+def torch_route(torch, T, q, k, repeats):
+    step = 1 << 18
+
+    def run():
+        lead_s, lead_i = [], []
+        for a in range(0, T.shape[0], step):
+            s, i = torch.topk(q @ T[a:a + step].T, min(k, T[a:a + step].shape[0]), dim=1)
+            lead_s.append(s)
+            lead_i.append(i + a)
+        s, j = torch.topk(torch.cat(lead_s, 1), k, dim=1)
+        return torch.gather(torch.cat(lead_i, 1), 1, j), s
+
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        run()
+        e1.record()
+        e1.synchronize()
+        us.append(1e3 * e0.elapsed_time(e1))
+    return float(np.median(us))
+
+
+def leg_torch(args):
+    import torch
+    rng, out = np.random.default_rng(91), {}
+    for dim in (32, 128):
+        T = torch.rand((args.rows, dim), device="cuda") * 2 - 1
+        for n_q in (1, 32, 256):
+            q = torch.from_numpy(rng.uniform(-1, 1, (n_q, dim)).astype(np.float32)).cuda()
+            for k in (16, 256):
+                out["%d,%d,%d" % (dim, n_q, k)] = round(torch_route(torch, T, q, k, args.repeats), 2)
+        del T
+    print(json.dumps(out), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--leg", default="")
+    ap.add_argument("--rows", type=int, default=1 << 22)
+    ap.add_argument("--calls", type=int, default=10)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "retrieve.json"))
+    ap.add_argument("--rehearse", action="store_true")
+    args = ap.parse_args()
+    if args.leg == "torch":
+        return leg_torch(args)
+    torch_us, torch_note = {}, None
+    if not args.rehearse:
+        try:
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", "torch", "--rows", str(args.rows), "--repeats", str(args.repeats)],
+                               capture_output=True, text=True, timeout=300)
+        except subprocess.TimeoutExpired:
+            sys.exit("retrieve_bench: the torch leg ran into its time limit; nothing more is started")
+        if p.returncode not in (0, 1):
+            sys.exit("retrieve_bench: the torch leg ended with status %d; nothing more is started" % p.returncode)
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        if p.returncode == 0 and lines:
+            torch_us = json.loads(lines[-1])
+        else:
+            torch_note = "not measured: " + (p.stderr.strip().splitlines() or ["no result"])[-1][:200]
+            print("torch leg", torch_note, flush=True)
+    import __graft_entry__ as graft
+    fr = graft.load_package()
+    if not args.rehearse and fr.device_count() < 1:
+        sys.exit("retrieve_bench: no MI355X visible -- a timing needs the GPU")
+    device, rows = (-1, 20000) if args.rehearse else (0, args.rows)
+    res = {"tool": "tools/retrieve_bench.py", "rows": rows, "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse), "calls": args.calls, "repeats": args.repeats,
+           "peaks": {"hbm_bytes_per_s": HBM_BYTES_PER_S, "mfma_f32_flops": MFMA_F32_FLOPS}, "cases": []}
+    if torch_note:
+        res["torch_us"] = torch_note
+    rng = np.random.default_rng(91)
+    for dim in (32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": rows}, {"dim": 8, "rows": 16}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=device)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        wk = fr.Worker(ctx, 16)
+        for n_q in (1, 32, 256):
+            Q = rng.uniform(-1, 1, (n_q, dim)).astype(np.float32)
+            d_q = fr.DeviceBuffer.from_numpy(ctx, Q)
+            for k in (16, 256):
+                d_r, d_s = fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+                us, all_us = timed(wk, lambda: wk.retrieve_device(0, 0, rows, n_q, d_q, k, d_r, d_s), args.calls, args.repeats)
+                case = {"dim": dim, "n_q": n_q, "k": k, "call_us": round(us, 2), "windows_us": all_us,
+                        "hbm_share": round(rows * dim * 4 / HBM_BYTES_PER_S / (us * 1e-6), 4), "mfma_share": round(2.0 * n_q * rows * dim / MFMA_F32_FLOPS / (us * 1e-6), 4)}
+                if "%d,%d,%d" % (dim, n_q, k) in torch_us:
+                    case["torch_us"] = torch_us["%d,%d,%d" % (dim, n_q, k)]
+                res["cases"].append(case)
+                print(json.dumps(case), flush=True)
+                d_r.free()
+                d_s.free()
+            d_q.free()
+        if dim == 32:   # every query's score ascends with the row
+            step = 1 << 18
+            for a in range(0, rows, step):
+                part = np.zeros((min(step, rows - a), dim), np.float32)
+                part[:, 0] = np.arange(a, a + len(part))
+                ctx.upload_table(0, part, row0=a)
+            Q = np.zeros((32, dim), np.float32)
+            Q[:, 0] = 1
+            d_q, d_r, d_s = fr.DeviceBuffer.from_numpy(ctx, Q), fr.DeviceBuffer(ctx, 32 * 256 * 4), fr.DeviceBuffer(ctx, 32 * 256 * 4)
+            us, all_us = timed(wk, lambda: wk.retrieve_device(0, 0, rows, 32, d_q, 256, d_r, d_s), args.calls, args.repeats)
+            top = d_r.download(np.int32, 32 * 256).reshape(32, 256)
+            res["adversarial"] = {"dim": dim, "n_q": 32, "k": 256, "call_us": round(us, 2), "windows_us": all_us,
+                                  "last_rows_first": bool((top == np.arange(rows - 1, rows - 257, -1)[None, :]).all())}
+            print(json.dumps(res["adversarial"]), flush=True)
+            for b in (d_q, d_r, d_s):
+                b.free()
+        wk.close()
+        ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
