@@ -32,6 +32,7 @@ GATHER_WORD_MAJOR, GATHER_ITEM_TILE, GATHER_ITEM_TILE_DEDUP, GATHER_ITEM_TILE_DE
 EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step's slices travel (Comm.set_exchange)
 POOL_MAX_HOTS = 64   # FR_POOL_MAX_HOTS (fleetrec_serving.h): slots per bag of a pooled lookup
 TOPK_MAX_K = 256   # FR_TOPK_MAX_K (fleetrec_serving.h): the largest k of a top-K ranking
+RETRIEVE_IMAGE_NONE, RETRIEVE_IMAGE_BF16 = 0, 1   # FR_RETRIEVE_IMAGE_* (fleetrec_serving.h): the kinds of fr_ctx_set_retrieve_image
 REQ_ONE_HOT, REQ_POOLED, REQ_DENSE = 0, 1, 2   # FR_REQ_* (fleetrec_serving.h): the forms of a request-form expansion
 KEYS_ROWS, KEYS_HASHED, KEYS_MAPPED = 0, 1, 2   # FR_KEYS_*: the key space of an index column (Context.set_key_space)
 KEY_EMPTY, KEY_NO_ROW = -1, 0x7fffffff   # FR_KEY_EMPTY: the empty slot of a bag; FR_KEY_NO_ROW: the row of a key without one (out of range for every gather)
@@ -91,6 +92,7 @@ ABI_SYMBOLS = [
     "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
     "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
     "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
+    "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
     "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -111,6 +113,7 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_ctx_create_sharded_pooled", "fr_worker_gather_slices_pooled", "fr_worker_gather_slices_pooled_csr", "fr_worker_submit_sharded_pooled",
                    "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
                    "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
+                   "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -203,6 +206,8 @@ def lib():
         "fr_worker_calibrate_fp8_sharded_pooled": (i32, [vp, vp, i32, i32]),
         "fr_worker_topk_device": (i32, [vp, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_topk": (i32, [vp, i32, i32, vp, i32, vp, vp]),
         "fr_worker_retrieve_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
+        "fr_ctx_set_retrieve_image": (i32, [vp, i32, i32]),
+        "fr_worker_retrieve_image_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve_image": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
         "fr_ctx_set_request_columns": (i32, [vp, pi, i32, i32]), "fr_ctx_request_words": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
         "fr_worker_request_idx_ptr": (pi, [vp]), "fr_worker_request_weights_ptr": (pf, [vp]), "fr_worker_request_dense_ptr": (pf, [vp]),
@@ -653,6 +658,11 @@ class Context:
 
     def set_stream_group(self, batches_per_launch):
         _check(lib().fr_ctx_set_stream_group(self._h, batches_per_launch))
+
+    def set_retrieve_image(self, table, kind=None):
+        """fr_ctx_set_retrieve_image: RETRIEVE_IMAGE_BF16 (the default) builds the table's bf16 retrieval image (synchronous, like upload_table),
+        RETRIEVE_IMAGE_NONE frees it.  upload_table / fill_tables make an image stale until this is called again; update_rows keeps it current."""
+        _check(lib().fr_ctx_set_retrieve_image(self._h, int(table), RETRIEVE_IMAGE_BF16 if kind is None else int(kind)))
 
     def set_lp_bank_image(self, on):
         """fleetrec_diag.h: 0 = the in-chain gather of a per-bank bf16 / fp8 context reads the fp32 rows (A/B and parity hook)."""
@@ -1284,17 +1294,26 @@ class Worker:
         rows), d_top_scores float32 [n_q][k] or None.  Asynchronous: sync() is the completion point, the buffers stay valid until then."""
         _check(lib().fr_worker_retrieve_device(self._h, int(table), int(row0), int(n_rows), int(n_q), self._ptr(d_queries), int(k), self._ptr(d_top_rows), self._ptr(d_top_scores)))
 
-    def retrieve(self, table, queries, k, row0=0, n_rows=None):
+    def retrieve(self, table, queries, k, row0=0, n_rows=None, _entry="fr_worker_retrieve"):
         """fr_worker_retrieve, then sync(): queries float32 [n_q][dim] (or uint32 bit patterns) -> (rows int32 [n_q][k], scores float32 [n_q][k])."""
         q = np.ascontiguousarray(queries)
         q = q.view(np.float32) if q.dtype == np.uint32 else np.ascontiguousarray(q, dtype=np.float32)
         if n_rows is None:
             n_rows = int(self.ctx.model.desc.tables[table].rows) - int(row0)
         out_r, out_s = np.empty((q.shape[0], int(k)), np.int32), np.empty((q.shape[0], int(k)), np.float32)
-        _check(lib().fr_worker_retrieve(self._h, int(table), int(row0), int(n_rows), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), int(k),
-                                        out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
+        _check(getattr(lib(), _entry)(self._h, int(table), int(row0), int(n_rows), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), int(k),
+                                      out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
         self.sync()
         return out_r, out_s
+
+    # the same over the table's bf16 retrieval image (Context.set_retrieve_image; fr_worker_retrieve_image_device / fr_worker_retrieve_image) ----------
+    def retrieve_image_device(self, table, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores=None):
+        """fr_worker_retrieve_image_device: retrieve_device with bf16 operands (queries rounded inside the call, rows from the image), fp32 sums."""
+        _check(lib().fr_worker_retrieve_image_device(self._h, int(table), int(row0), int(n_rows), int(n_q), self._ptr(d_queries), int(k), self._ptr(d_top_rows), self._ptr(d_top_scores)))
+
+    def retrieve_image(self, table, queries, k, row0=0, n_rows=None):
+        """fr_worker_retrieve_image, then sync(): the arguments and results of retrieve()."""
+        return self.retrieve(table, queries, k, row0, n_rows, _entry="fr_worker_retrieve_image")
 
     def infer_topk(self, idx, k, seg_offsets=None, dense=None):
         """infer() with the ranking on the device: idx int32 [B][idx_cols] (+ dense) -> (positions int32 [n_seg][k], scores float32 [n_seg][k]) of the

@@ -445,6 +445,7 @@ extern "C" int fr_ctx_create_sharded(const fr_model_desc *m, int device, int sha
     c->model.tables = c->tables.data();
     c->model.segments = c->segments.data();
     c->table_mem.assign(m->n_tables, FrTableMem{});
+    c->rt_img.resize((size_t)m->n_tables);   // (sized once: workers read the entries without a lock)
     c->shard_rank = shard_rank;
     c->n_shards = n_shards;
     c->stream_group.store(fused_group_initial(), std::memory_order_relaxed);
@@ -547,6 +548,7 @@ extern "C" int fr_ctx_fill_tables(fr_ctx *ctx, int mode, uint32_t seed) {
     if (!ctx->cpu) FR_HIP(hipStreamSynchronize(ctx->setup_stream));
     ctx->tables_filled = true;
     ctx->tables_gen++;   // an operand-type bank image made from older contents is stale (lp_ensure_image)
+    for (fr_ctx::RetrieveImage &im : ctx->rt_img) im.stale = true;   // ... and so is every retrieval image, until fr_ctx_set_retrieve_image is called again
     return FR_OK;
 }
 
@@ -600,6 +602,7 @@ extern "C" int fr_ctx_upload_table(fr_ctx *ctx, int table, int64_t row0, int64_t
     if (rc) return rc;
     ctx->tables_filled = true;
     ctx->tables_gen++;   // an operand-type bank image made from older contents is stale (lp_ensure_image)
+    if ((size_t)table < ctx->rt_img.size()) ctx->rt_img[table].stale = true;   // (as in fr_ctx_fill_tables)
     return FR_OK;
 }
 
@@ -2742,8 +2745,12 @@ static int update_check(fr_ctx *ctx, int table, int n, const void *ids, const vo
     return FR_OK;
 }
 
-// The two launches of an update on stream s, under lp_mutex: the scatter into the fp32 arena, then -- when an operand-type bank image exists and is
-// current for the table contents -- the conversion of the same listed rows, read back from the arena, at the image's own X exponent.
+// a retrieval image of the table exists and no fill / upload has made it stale (under lp_mutex)
+static bool retrieve_image_current(const fr_ctx *c, int table) { return (size_t)table < c->rt_img.size() && c->rt_img[table].img && !c->rt_img[table].stale; }
+
+// The launches of an update on stream s, under lp_mutex: the scatter into the fp32 arena, then -- when an operand-type bank image exists and is
+// current for the table contents -- the conversion of the same listed rows, read back from the arena, at the image's own X exponent, then -- when the
+// table has a current retrieval image -- the patch of that image from the same ids.  A context with neither runs the scatter alone.
 static int update_enqueue(fr_ctx *c, int table, int n, const int32_t *d_ids, const float *d_rows, int *d_err, hipStream_t s) {
     const fr_table_desc &d = c->tables[table];
     const FrTableMem &tm = c->table_mem[table];
@@ -2756,7 +2763,23 @@ static int update_enqueue(fr_ctx *c, int table, int n, const int32_t *d_ids, con
         const int64_t image_rows = (int64_t)lt.rows < head_rows ? (int64_t)lt.rows : head_rows;   // (always lt.rows: the image holds rows of the head region only)
         rc = frk_convert_rows_lp(c->lp_prec, c->table_arena + tm.byte_offset, (size_t)tm.row_stride, c->lp_arena + lt.base, lt.stride, n, d.dim, c->lp_e_x, s, d_ids, image_rows);
     }
+    if (!rc && retrieve_image_current(c, table)) {   // the same ids once more, read back from the arena: what a rebuild would make, also of an id listed twice
+        FrRetrieveImageArgs a{};
+        a.table = reinterpret_cast<const float *>(c->table_arena + tm.byte_offset), a.image = reinterpret_cast<uint4 *>(c->rt_img[table].img.p);
+        a.dim = d.dim, a.rows = d.rows, a.ids = d_ids, a.n = n;
+        const int e = fr_retrieve_lp_image_launch(&a, (void *)s);
+        if (e) FR_FAIL(FR_ERR_HIP, "the retrieval image's patch launch failed: %s", hipGetErrorString((hipError_t)e));
+    }
     return rc;
+}
+
+// the CPU back-end's update: the rows, then the same ids into a current retrieval image; -> 1 when an id was outside the table
+static int update_cpu(fr_ctx *c, int table, int n, const int32_t *ids, const float *rows) {
+    const int bad = frc_update_rows(c->table_arena, c->table_mem[table], c->tables[table].dim, c->tables[table].rows, n, ids, rows);
+    std::lock_guard<std::mutex> lk(c->lp_mutex);
+    if (retrieve_image_current(c, table))
+        frc_retrieve_image_rows(reinterpret_cast<const float *>(c->table_arena + c->table_mem[table].byte_offset), c->tables[table].dim, c->tables[table].rows, n, ids, c->rt_img[table].img);
+    return bad;
 }
 
 extern "C" int fr_worker_update_rows(fr_worker *w, int table, int n, const int32_t *d_row_ids, const float *d_rows) {
@@ -2766,7 +2789,7 @@ extern "C" int fr_worker_update_rows(fr_worker *w, int table, int n, const int32
     if (rc) return rc;
     if (n == 0) return FR_OK;
     if (c->cpu) {   // computed before the call returns; a range error waits in c_err for fr_worker_sync, like the gathers'
-        if (frc_update_rows(c->table_arena, c->table_mem[table], c->tables[table].dim, c->tables[table].rows, n, d_row_ids, d_rows)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+        if (update_cpu(c, table, n, d_row_ids, d_rows)) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
         return FR_OK;
     }
     if ((uintptr_t)d_rows % 16) FR_FAIL(FR_ERR_INVALID, "d_rows must be 16-byte aligned");
@@ -2788,7 +2811,7 @@ extern "C" int fr_ctx_update_rows(fr_ctx *ctx, int table, int n, const int32_t *
     if (n == 0) return FR_OK;
     const int dim = ctx->tables[table].dim;
     if (ctx->cpu) {
-        if (frc_update_rows(ctx->table_arena, ctx->table_mem[table], dim, ctx->tables[table].rows, n, h_row_ids, h_rows))
+        if (update_cpu(ctx, table, n, h_row_ids, h_rows))
             FR_FAIL(FR_ERR_INDEX_RANGE, "a listed row id was outside table %d (that row was not written, the others were)", table);
         return FR_OK;
     }
@@ -2891,7 +2914,7 @@ extern "C" int fr_worker_topk(fr_worker *w, int batch, int n_seg, const int32_t 
 // ---- top-K inner-product retrieval (fleetrec_serving.h) ----------------------------------------------------------------------------------------
 // The kernels are the eighth companion code object's (fr_retrieve.hip -> libfleetrec_retrieve.so); the chunking rule is fr_retrieve_chunk
 // (fr_internal.h), the merge is the ranking companion's, the CPU twin is frc_retrieve.
-static int retrieve_check(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const void *queries, int k, const void *top_rows) {
+static int retrieve_check(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const void *queries, int k, const void *top_rows, bool image) {
     if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
     const fr_ctx *c = w->ctx;
     if (!queries || !top_rows) FR_FAIL(FR_ERR_INVALID, "queries / top_rows is NULL");
@@ -2906,12 +2929,16 @@ static int retrieve_check(fr_worker *w, int table, int64_t row0, int64_t n_rows,
         FR_FAIL(FR_ERR_STATE, "retrieval reads dense tables; the tables of an FR_INDEX_PER_BANK context are interleaved in bank rows");
     if (c->n_shards > 1 || !c->table_mem[table].resident) FR_FAIL(FR_ERR_STATE, "retrieval is not available on a table-sharded context (shard %d of %d)", c->shard_rank, c->n_shards);
     if (c->tables[table].dim > FR_RETRIEVE_MAX_DIM) FR_FAIL(FR_ERR_STATE, "table %d has dim %d; retrieval holds a query in registers up to dim %d", table, c->tables[table].dim, FR_RETRIEVE_MAX_DIM);
+    if (image) {   // (the flags are written by set-up calls only, which the caller orders against its workers as it orders fr_ctx_upload_table)
+        if ((size_t)table >= c->rt_img.size() || !c->rt_img[table].img) FR_FAIL(FR_ERR_STATE, "table %d has no retrieval image: call fr_ctx_set_retrieve_image(ctx, %d, FR_RETRIEVE_IMAGE_BF16) first", table, table);
+        if (c->rt_img[table].stale) FR_FAIL(FR_ERR_STATE, "the retrieval image of table %d is stale (the table was filled or uploaded after it was made): call fr_ctx_set_retrieve_image again", table);
+    }
     return FR_OK;
 }
 
 // The launches of one retrieval on the worker's stream, behind everything submitted or pushed before (the rule of topk_enqueue).  h_queries != NULL:
 // the host form -- they are the pinned staging, copied into the scratch first.
-static int retrieve_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, const float *h_queries, int k, int32_t *d_top_rows, float *d_top_scores) {
+static int retrieve_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, const float *h_queries, int k, int32_t *d_top_rows, float *d_top_scores, bool image) {
     fr_ctx *c = w->ctx;
     FR_TRY(fr_host_fed_queued(w, "retrieve"));
     if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
@@ -2920,8 +2947,11 @@ static int retrieve_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_row
     FrRetrieveArgs a{};
     a.table = reinterpret_cast<const float *>(c->table_arena + c->table_mem[table].byte_offset);
     a.dim = dim, a.n_q = n_q, a.k = k, a.row0 = row0, a.n_rows = n_rows;
-    a.chunk = fr_retrieve_chunk(n_rows, n_q, k, c->n_cu);
-    a.n_chunks = (int)((n_rows + a.chunk - 1) / a.chunk);
+    // The image is tiled by absolute row, so its scan cuts chunks from the tile boundary at or below row0: the first chunk loses up to 31 rows (the
+    // 1024 floor still leaves it >= k), and still only the last list can be short.
+    const int64_t span = image ? row0 % FR_RETRIEVE_IMAGE_TILE + n_rows : n_rows;
+    a.chunk = fr_retrieve_chunk(span, n_q, k, c->n_cu);
+    a.n_chunks = (int)((span + a.chunk - 1) / a.chunk);
     const size_t n_part = (size_t)n_q * (size_t)a.n_chunks * (size_t)k;   // <= 2^24
     const size_t plane = align_up(n_part * 4, 256), off_bytes = align_up(((size_t)n_q + 1) * 4, 256), pos_bytes = align_up((size_t)n_q * k * 4, 256);
     const size_t q_bytes = h_queries ? align_up((size_t)n_q * dim * 4, 256) : 0;
@@ -2945,7 +2975,15 @@ static int retrieve_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_row
         FR_HIP(hipMemcpyAsync(dq, h_queries, (size_t)n_q * dim * 4, hipMemcpyHostToDevice, w->stream));
         a.queries = dq;
     }
-    int e = fr_retrieve_launch(&a, 0, (void *)w->stream);
+    int e;
+    if (image) {
+        FrRetrieveLpArgs lp{};
+        lp.r = a, lp.r.table = nullptr;
+        lp.image = reinterpret_cast<const uint4 *>(c->rt_img[table].img.p), lp.tiles = fr_retrieve_image_tiles(c->tables[table].rows);
+        e = fr_retrieve_lp_scan_launch(&lp, (void *)w->stream);
+    } else {
+        e = fr_retrieve_launch(&a, 0, (void *)w->stream);
+    }
     if (e) FR_FAIL(FR_ERR_HIP, "the retrieval scan launch failed: %s", hipGetErrorString((hipError_t)e));
     w->in_flight = true;
     // the n_chunks * k partial scores of every query are one segment of the ranking; its positions index the planes
@@ -2956,22 +2994,28 @@ static int retrieve_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_row
 }
 
 static const float *retrieve_cpu_table(const fr_ctx *c, int table) { return reinterpret_cast<const float *>(c->table_arena + c->table_mem[table].byte_offset); }
-
-extern "C" int fr_worker_retrieve_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, int k, int32_t *d_top_rows, float *d_top_scores) {
-    int rc = retrieve_check(w, table, row0, n_rows, n_q, d_queries, k, d_top_rows);
-    if (rc) return rc;
-    if (w->ctx->cpu) {   // computed before the call returns
-        frc_retrieve(retrieve_cpu_table(w->ctx, table), w->ctx->tables[table].dim, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores);
-        return FR_OK;
-    }
-    return retrieve_enqueue(w, table, row0, n_rows, n_q, d_queries, nullptr, k, d_top_rows, d_top_scores);
+static void retrieve_cpu(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores, bool image) {
+    const fr_ctx *c = w->ctx;
+    if (image) frc_retrieve_image(c->rt_img[table].img, c->tables[table].dim, row0, n_rows, n_q, queries, k, top_rows, top_scores);
+    else frc_retrieve(retrieve_cpu_table(c, table), c->tables[table].dim, row0, n_rows, n_q, queries, k, top_rows, top_scores);
 }
 
-extern "C" int fr_worker_retrieve(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows, float *h_top_scores) {
-    int rc = retrieve_check(w, table, row0, n_rows, n_q, h_queries, k, h_top_rows);
+// the device form and the host form of both retrievals: the exact one over the fp32 table and (image) the bf16 one over the table's retrieval image
+static int retrieve_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, int k, int32_t *d_top_rows, float *d_top_scores, bool image) {
+    int rc = retrieve_check(w, table, row0, n_rows, n_q, d_queries, k, d_top_rows, image);
+    if (rc) return rc;
+    if (w->ctx->cpu) {   // computed before the call returns
+        retrieve_cpu(w, table, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores, image);
+        return FR_OK;
+    }
+    return retrieve_enqueue(w, table, row0, n_rows, n_q, d_queries, nullptr, k, d_top_rows, d_top_scores, image);
+}
+
+static int retrieve_host(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows, float *h_top_scores, bool image) {
+    int rc = retrieve_check(w, table, row0, n_rows, n_q, h_queries, k, h_top_rows, image);
     if (rc) return rc;
     if (w->ctx->cpu) {
-        frc_retrieve(retrieve_cpu_table(w->ctx, table), w->ctx->tables[table].dim, row0, n_rows, n_q, h_queries, k, h_top_rows, h_top_scores);
+        retrieve_cpu(w, table, row0, n_rows, n_q, h_queries, k, h_top_rows, h_top_scores, image);
         return FR_OK;
     }
     if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking or retrieval is already in flight on this worker: call fr_worker_sync first");
@@ -2987,9 +3031,65 @@ extern "C" int fr_worker_retrieve(fr_worker *w, int table, int64_t row0, int64_t
     }
     memcpy(w->h_rt_q, h_queries, n_query * sizeof(float));
     // the results come back through the host-form ranking's staging and are delivered by fr_worker_sync as its results are
-    rc = retrieve_enqueue(w, table, row0, n_rows, n_q, nullptr, w->h_rt_q, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr);
+    rc = retrieve_enqueue(w, table, row0, n_rows, n_q, nullptr, w->h_rt_q, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr, image);
     if (rc) return rc;
     w->tk_dst_idx = h_top_rows, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
+    return FR_OK;
+}
+
+extern "C" int fr_worker_retrieve_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, int k, int32_t *d_top_rows, float *d_top_scores) {
+    return retrieve_device(w, table, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores, false);
+}
+extern "C" int fr_worker_retrieve(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows, float *h_top_scores) {
+    return retrieve_host(w, table, row0, n_rows, n_q, h_queries, k, h_top_rows, h_top_scores, false);
+}
+extern "C" int fr_worker_retrieve_image_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, int k, int32_t *d_top_rows, float *d_top_scores) {
+    return retrieve_device(w, table, row0, n_rows, n_q, d_queries, k, d_top_rows, d_top_scores, true);
+}
+extern "C" int fr_worker_retrieve_image(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows, float *h_top_scores) {
+    return retrieve_host(w, table, row0, n_rows, n_q, h_queries, k, h_top_rows, h_top_scores, true);
+}
+
+// The retrieval image of one table (fleetrec_serving.h): built on the set-up stream and waited for, as fr_ctx_upload_table is; under lp_mutex, which also
+// keeps a row update's patch from meeting a build.  The kernels are the ninth companion's (fr_retrieve_lp.hip -> libfleetrec_retrieve_lp.so).
+extern "C" int fr_ctx_set_retrieve_image(fr_ctx *ctx, int table, int kind) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (kind != FR_RETRIEVE_IMAGE_NONE && kind != FR_RETRIEVE_IMAGE_BF16) FR_FAIL(FR_ERR_INVALID, "retrieval image kind %d is neither FR_RETRIEVE_IMAGE_NONE nor FR_RETRIEVE_IMAGE_BF16", kind);
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);
+    if (kind == FR_RETRIEVE_IMAGE_NONE) {
+        if ((size_t)table < ctx->rt_img.size() && ctx->rt_img[table].img) {
+            if (!ctx->cpu) {
+                FR_SET_DEVICE(ctx);
+                FR_HIP(hipDeviceSynchronize());   // a worker's scan or patch may still use it
+            }
+            ctx->rt_img[table].img.reset();
+            ctx->rt_img[table].stale = false;
+        }
+        return FR_OK;
+    }
+    const fr_table_desc &d = ctx->tables[table];
+    const FrTableMem &tm = ctx->table_mem[table];
+    if (ctx->model.index_mode == FR_INDEX_PER_BANK || tm.il_rows)
+        FR_FAIL(FR_ERR_STATE, "a retrieval image is made of a dense table; the tables of an FR_INDEX_PER_BANK context are interleaved in bank rows");
+    if (ctx->n_shards > 1 || !tm.resident) FR_FAIL(FR_ERR_STATE, "retrieval is not available on a table-sharded context (shard %d of %d)", ctx->shard_rank, ctx->n_shards);
+    if (d.dim > FR_RETRIEVE_MAX_DIM) FR_FAIL(FR_ERR_STATE, "table %d has dim %d; retrieval holds a query in registers up to dim %d", table, d.dim, FR_RETRIEVE_MAX_DIM);
+    fr_ctx::RetrieveImage &im = ctx->rt_img[table];
+    const float *src = reinterpret_cast<const float *>(ctx->table_arena + tm.byte_offset);
+    if (ctx->cpu) {
+        FR_TRY(im.img.grow(FrMem::HOST, (size_t)d.rows * (size_t)d.dim, "retrieval image"));
+        frc_retrieve_image_rows(src, d.dim, d.rows, d.rows, nullptr, im.img);
+        im.stale = false;
+        return FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    FR_TRY(im.img.grow(FrMem::DEVICE, fr_retrieve_image_elems(d.rows, d.dim), "retrieval image"));
+    FrRetrieveImageArgs a{};
+    a.table = src, a.image = reinterpret_cast<uint4 *>(im.img.p), a.dim = d.dim, a.rows = d.rows, a.tile0 = 0, a.n_tiles = fr_retrieve_image_tiles(d.rows);
+    const int e = fr_retrieve_lp_image_launch(&a, (void *)ctx->setup_stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the retrieval image's build launch failed: %s", hipGetErrorString((hipError_t)e));
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    im.stale = false;
     return FR_OK;
 }
 

@@ -272,17 +272,15 @@ int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int
 
 // Top-K retrieval: per query the composites of fr_retrieve.hip -- (key << 32) | (0xffffffff - (row - row0)) -- over the window and a partial sort.  The
 // sum starts at -0, the identity of the addition, and runs in ascending c; no read outside table[row0 .. row0 + n_rows) and queries[n_q][dim].
-void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores) {
+template <class Score>   // score(query, window row) -> fp32
+static void retrieve_ranked(int64_t row0, int64_t n_rows, int n_q, int k, int32_t *top_rows, float *top_scores, Score score) {
     const int units = n_q < Pool::get().size() ? n_q : Pool::get().size();
     Pool::get().run(units, [&](int u) {
         std::vector<uint64_t> comp((size_t)n_rows);
         const int qa = (int)((int64_t)n_q * u / units), qb = (int)((int64_t)n_q * (u + 1) / units);
         for (int q = qa; q < qb; q++) {
-            const float *qv = queries + (size_t)q * (size_t)dim;
             for (int64_t i = 0; i < n_rows; i++) {
-                const float *t = table + (size_t)(row0 + i) * (size_t)dim;
-                float acc = -0.0f;
-                for (int c = 0; c < dim; c++) acc += qv[c] * t[c];
+                const float acc = score(q, i);
                 uint32_t bits;
                 memcpy(&bits, &acc, 4);
                 comp[(size_t)i] = ((uint64_t)fr_rank_key(bits) << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
@@ -297,6 +295,55 @@ void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int
                 if (top_scores) memcpy(top_scores + o, &bits, 4);
             }
         }
+    });
+}
+
+void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores) {
+    retrieve_ranked(row0, n_rows, n_q, k, top_rows, top_scores, [&](int q, int64_t i) {
+        const float *qv = queries + (size_t)q * (size_t)dim, *t = table + (size_t)(row0 + i) * (size_t)dim;
+        float acc = -0.0f;
+        for (int c = 0; c < dim; c++) acc += qv[c] * t[c];
+        return acc;
+    });
+}
+
+// The retrieval image of the CPU back-end: the bf16 values of the device image (fr_bf16_rne), row-major.  No read outside the listed / ranged rows.
+static inline float bf16_value(uint16_t v) {
+    const uint32_t bits = (uint32_t)v << 16;
+    float f;
+    memcpy(&f, &bits, 4);
+    return f;
+}
+void frc_retrieve_image_rows(const float *table, int dim, int64_t rows, int64_t n, const int32_t *ids, uint16_t *img) {
+    const int64_t chunk = 4096;
+    Pool::get().run((int)((n + chunk - 1) / chunk), [&](int u) {
+        const int64_t e1 = (u + 1) * chunk < n ? (u + 1) * chunk : n;
+        for (int64_t e = u * chunk; e < e1; e++) {
+            const int64_t row = ids ? (int64_t)ids[e] : e;
+            if (row < 0 || row >= rows) continue;
+            for (int c = 0; c < dim; c++) {
+                uint32_t bits;
+                memcpy(&bits, table + (size_t)row * (size_t)dim + c, 4);
+                img[(size_t)row * (size_t)dim + c] = fr_bf16_rne(bits);
+            }
+        }
+    });
+}
+
+// s = -0 + bf16(q[0]) img[0] + bf16(q[1]) img[1] + ... : a product of two bf16 values has 16 significant bits and is exact in fp32; ascending c
+void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores) {
+    std::vector<float> qr((size_t)n_q * (size_t)dim);
+    for (size_t i = 0; i < qr.size(); i++) {
+        uint32_t bits;
+        memcpy(&bits, queries + i, 4);
+        qr[i] = bf16_value(fr_bf16_rne(bits));
+    }
+    retrieve_ranked(row0, n_rows, n_q, k, top_rows, top_scores, [&](int q, int64_t i) {
+        const float *qv = qr.data() + (size_t)q * (size_t)dim;
+        const uint16_t *t = img + (size_t)(row0 + i) * (size_t)dim;
+        float acc = -0.0f;
+        for (int c = 0; c < dim; c++) acc += qv[c] * bf16_value(t[c]);
+        return acc;
     });
 }
 

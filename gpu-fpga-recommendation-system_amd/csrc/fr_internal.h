@@ -331,6 +331,43 @@ static inline int64_t fr_retrieve_chunk(int64_t n_rows, int n_q, int k, int n_cu
 // step 0: the scan; step 1: the row mapping behind the ranking.  Enqueues one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
 extern "C" int fr_retrieve_launch(const FrRetrieveArgs *args, int step, void *stream);
 
+// ---- bf16 retrieval over a fragment-major table image (fr_retrieve_lp.hip -> libfleetrec_retrieve_lp.so, the ninth companion; fr_cpu.cpp has the twin) ----
+// The image (fr_ctx_set_retrieve_image): rows in tiles of 32 by ABSOLUTE row, columns in steps of 16; tile T, step s is one 1024-byte block and lane
+// (n, h) = (lane % 32, lane / 32) owns the 16 bytes at ((T * steps + s) * 64 + lane) * 16: columns 16 s + 8 h .. + 7 of row 32 T + n as bf16 (RNE, a NaN
+// stays a NaN), the B operand of v_mfma_f32_32x32x16_bf16 as it sits in registers.  Columns >= dim and rows >= the table's rows hold +0.
+constexpr int FR_RETRIEVE_IMAGE_TILE = 32;    // rows of a tile
+constexpr int FR_RETRIEVE_IMAGE_STEP = 16;    // columns of a step
+static inline __host__ __device__ int fr_retrieve_image_steps(int dim) { return (dim + FR_RETRIEVE_IMAGE_STEP - 1) / FR_RETRIEVE_IMAGE_STEP; }
+static inline int64_t fr_retrieve_image_tiles(int64_t rows) { return (rows + FR_RETRIEVE_IMAGE_TILE - 1) / FR_RETRIEVE_IMAGE_TILE; }
+// 16-bit elements of the device image of a table
+static inline size_t fr_retrieve_image_elems(int64_t rows, int dim) { return (size_t)fr_retrieve_image_tiles(rows) * (size_t)fr_retrieve_image_steps(dim) * 512; }
+// fp32 -> bf16, round to nearest even, a NaN stays a NaN (quiet): what v_cvt_pk_bf16_f32 (pack_bf16x2, fr_device.h) gives, in plain C++
+static inline uint16_t fr_bf16_rne(uint32_t bits) {
+    if ((bits & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((bits >> 16) | 0x0040u);
+    return (uint16_t)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
+}
+struct FrRetrieveImageArgs {
+    const float *table;      // row 0 of the dense fp32 table, rows dim floats apart
+    uint4 *image;            // the table's image (16-byte words)
+    int dim;
+    int64_t rows;            // rows of the table
+    // ids == NULL: the range arm -- tiles [tile0, tile0 + n_tiles) are written whole, pads included.  ids != NULL: the list arm -- the words of the n
+    // listed rows; an id outside [0, rows) does nothing.
+    int64_t tile0, n_tiles;
+    const int32_t *ids;
+    int n;
+};
+// The scan's arguments: r as the fp32 scan takes them (r.table is not read), the chunks counted from the tile boundary A = r.row0 & ~31:
+// chunk c covers the rows of [A + c * r.chunk, A + (c + 1) * r.chunk) that lie inside the window, and r.n_chunks = ceil((r.row0 - A + r.n_rows) / r.chunk).
+struct FrRetrieveLpArgs {
+    FrRetrieveArgs r;
+    const uint4 *image;
+    int64_t tiles;           // tiles the image holds: a tile past the last is never read
+};
+// Each enqueues one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_retrieve_lp_image_launch(const FrRetrieveImageArgs *args, void *stream);
+extern "C" int fr_retrieve_lp_scan_launch(const FrRetrieveLpArgs *args, void *stream);
+
 // ---- request-form batches (fr_request.hip -> libfleetrec_request.so, the second companion code object; fr_cpu.cpp has the twin) ----------------
 // Row i of `out` ([batch][W] 32-bit words) is put together word by word: desc[w] >= 0 names word desc[w] of candidate row i ([batch][Rc]),
 // desc[w] < 0 names word ~desc[w] of the request row ([n_req][Rs]) of the request that owns item i -- the last r with off[r] <= i, clamped into
@@ -554,6 +591,14 @@ struct fr_ctx {
     FrBuf<float> d_up_rows;
     FrBuf<int> h_up_err;
     int *d_up_err = nullptr;               // h_up_err's device-side alias
+    // Retrieval images (fr_ctx_set_retrieve_image): per table a bf16 copy for fr_worker_retrieve_image*; img is NULL until one is set.  GPU contexts: the
+    // fragment-major image in device memory; the CPU back-end: the same rounded values row-major [rows][dim] in host memory.  `stale` is set by every
+    // fill / upload and cleared by a build; row updates patch a current image behind their scatter (update_enqueue).  Built and released under lp_mutex.
+    struct RetrieveImage {
+        FrBuf<uint16_t> img;
+        bool stale = false;
+    };
+    std::vector<RetrieveImage> rt_img;     // [tables]
     std::atomic<int> lp_image_on{1};       // fr_ctx_set_lp_bank_image (fleetrec_diag.h): 0 = the in-chain gather reads the fp32 rows and converts them itself
     // Pooled (multi-hot) lookups (fr_ctx_set_pooling): the descriptors made of the hots per index column, P = sum of hots (0: no pooling)
     std::vector<FrPoolDesc> h_pool;
@@ -841,6 +886,10 @@ int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int
 // table[row0 .. row0 + n_rows) ([..][dim], dense) with the largest score s = -0 + q[0] t[0] + q[1] t[1] + ... in fp32, ascending c, ranked by fr_rank_key
 // with ties to the lower row; a NaN score is delivered as 0x7fc00000; (-1, -inf) behind the window's rows.  Queries over the pool's threads.
 void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores);
+// the CPU back-end's retrieval image, row-major [rows][dim] bf16 (fr_bf16_rne): ids == NULL converts rows [0, n) of `table`, else the n listed rows
+// (an id outside [0, rows) does nothing); and the twin of the image scan: frc_retrieve with s = -0 + bf16(q[0]) img[0] + ... , each product exact in fp32
+void frc_retrieve_image_rows(const float *table, int dim, int64_t rows, int64_t n, const int32_t *ids, uint16_t *img);
+void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores);
 // the CPU twin of fr_request_launch: the same words, items over the pool's threads; -> 1 when the offsets were malformed, else 0
 int frc_expand_requests(const FrRequestArgs &a);
 // the CPU twin of the factored chain (fleetrec_serving.h states the arithmetic): both gathers, U, V + U[owner], FC1's epilogue, then the chain's own

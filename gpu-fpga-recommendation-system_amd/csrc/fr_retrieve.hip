@@ -32,66 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fr_internal.h"
-
-typedef unsigned long long u64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int RT_THREADS = 256, RT_WAVES = 4;
-
-static __device__ __forceinline__ int pow2_ceil(int v) {
-    int m = 2;
-    while (m < v) m <<= 1;
-    return m;
-}
-
-// between two steps of a wave's own LDS network: the hardware keeps a wave's DS instructions in order, the compiler must too
-static __device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// one compare-exchange step over b[0 .. 2 * half) (ce_step of fr_rank.hip, by one wave): pair p is (i, i + stride), i = 2p - (p & (stride - 1)),
-// descending where (i & dirmask) == 0
-static __device__ __forceinline__ void wave_ce_step(u64 *b, int half, int stride, int dirmask, int lane) {
-    for (int p = lane; p < half; p += 64) {
-        const int i = 2 * p - (p & (stride - 1));
-        const u64 x = b[i], y = b[i + stride];
-        if ((x < y) == ((i & dirmask) == 0)) b[i] = y, b[i + stride] = x;
-    }
-    wave_sync();
-}
-
-// the kp leaders of b[0 .. m), descending in b[0 .. kp); m a power of two, kp < m <= 512 (tile_leaders of fr_rank.hip, by one wave)
-static __device__ __forceinline__ void wave_leaders(u64 *b, int m, int kp, int lane) {
-    for (int size = 2; size <= kp; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) wave_ce_step(b, m >> 1, stride, size, lane);
-    while (m > kp) {
-        const int half = m >> 1;   // <= 256: four per lane
-        u64 v[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int p = lane + 64 * r;
-            if (p < half) {
-                const int x = 2 * p - (p & (kp - 1));
-                const u64 c = b[x], d = b[x + kp];
-                v[r] = c > d ? c : d;
-            }
-        }
-        wave_sync();
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int p = lane + 64 * r;
-            if (p < half) b[p] = v[r];
-        }
-        wave_sync();
-        m = half;
-        for (int stride = kp >> 1; stride > 0; stride >>= 1) wave_ce_step(b, m >> 1, stride, kp, lane);
-    }
-}
-
-// the score bits a key stands for (every NaN: the quiet NaN)
-static __device__ __forceinline__ uint32_t retrieve_bits(uint32_t key) { return key == 0u ? FR_RETRIEVE_PAD_BITS : ((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key); }
+#include "fr_retrieve_select.h"
 
 template <int KP, int NT>
 __global__ __launch_bounds__(RT_THREADS, KP <= 64 && NT <= 4 ? 2 : 1) void retrieve_scan_kernel(const FrRetrieveArgs g) {

@@ -318,6 +318,32 @@ int fr_worker_retrieve_device(fr_worker *w, int table, int64_t row0, int64_t n_r
 int fr_worker_retrieve(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows,
                        float *h_top_scores /* or NULL */);
 
+/* bf16 retrieval over a table image (additive in ABI 6): the FAST form of the retrieval above; fr_worker_retrieve* stays the exact form.  A table gets
+ * a retrieval image -- a bf16 copy laid out for the scan -- and fr_worker_retrieve_image* scans that copy: half the bytes of a pass for dim >= 16, and
+ * the bf16 matrix instruction instead of the fp32 one.
+ * fr_ctx_set_retrieve_image(ctx, table, FR_RETRIEVE_IMAGE_BF16) builds the image of the whole table on the set-up stream and waits for it, as
+ *   fr_ctx_upload_table does; FR_RETRIEVE_IMAGE_NONE frees it (after a device synchronise).  The image costs 32 * ceil(dim / 16) bytes per row (rows
+ *   rounded up to 32): the image of a table with dim < 16 is NOT smaller than the table.  Values are rounded to nearest even; a NaN stays a NaN.
+ *   FR_ERR_INVALID: a NULL context, a table outside the model, another kind.  FR_ERR_STATE: what fr_worker_retrieve_device refuses of a context or table.
+ * Staleness is explicit: fr_ctx_upload_table and fr_ctx_fill_tables mark an existing image of the table stale, and a retrieval over a stale image is
+ *   FR_ERR_STATE until fr_ctx_set_retrieve_image is called again -- nothing is rebuilt from inside a worker's launch path.  Row updates keep a current
+ *   image current: fr_worker_update_rows / fr_ctx_update_rows enqueue, behind their scatter and on the same stream, a patch of the same ids that reads
+ *   the fp32 words back from the table, so a patched image is bit for bit what a rebuild would make, also when an id is listed twice; an id outside the
+ *   table does nothing there (the scatter reports it).  Order against other workers: as fr_worker_update_rows states it for the tables.
+ * Score: s[q][r] = -0 + sum over c < dim of bf16(queries[q][c]) * bf16(table[r][c]).  Each product is exact in fp32; the sum is accumulated in fp32 in a
+ *   fixed order, the same for every row.  Rank order, ties (lower row first), NaN delivery and padding are fr_worker_retrieve_device's.  The device and
+ *   the CPU back-end give the same bits whenever every partial sum is exactly representable.  Operands whose magnitude is below 2^-126 after rounding
+ *   (subnormals) are outside that bit-exact contract: what the matrix instruction does with them has not been established.
+ * Signatures, stream order, scratch, the host form's staging and every refusal are those of fr_worker_retrieve_device / fr_worker_retrieve; one refusal
+ *   is new: FR_ERR_STATE when the table has no image or a stale one. */
+#define FR_RETRIEVE_IMAGE_NONE 0
+#define FR_RETRIEVE_IMAGE_BF16 1
+int fr_ctx_set_retrieve_image(fr_ctx *ctx, int table, int kind);
+int fr_worker_retrieve_image_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries /* [n_q][dim] */, int k,
+                                    int32_t *d_top_rows /* [n_q][k] */, float *d_top_scores /* [n_q][k] or NULL */);
+int fr_worker_retrieve_image(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows,
+                             float *h_top_scores /* or NULL */);
+
 /* Request-form batches (additive in ABI 6): the input side of the segments above.  A request is one user and N candidate items; without this its
  * batch arrives as N complete index rows, the user's columns (and dense features) repeated N times.  With a SPLIT set on the context a batch arrives
  * as request rows + candidate rows + segment offsets, and one small launch expands them on the device into the rows every existing lookup path takes.

@@ -13,6 +13,16 @@ One table of `--rows` (4 M) rows at dim 32 and one at dim 128, hash-filled; n_q 
 The process is the only one on the GPU; a failure ends it with a non-zero status and nothing more is started.
 
     python tools/retrieve_bench.py [--out profiles/retrieve.json]      --rehearse: the CPU back-end, 20000 rows, no torch leg (times are not measurements)
+
+--image bf16 -> profiles/retrieve_lp.json: the same grid plus dim 16, fr_worker_retrieve_device and fr_worker_retrieve_image_device of the same build
+alternating window by window in one process (fp32_us, image_us; speedup = fp32_us / image_us).  Per case the two floors of the image call -- one pass
+over the image bytes (rows rounded up to 32 x ceil(dim / 16) x 32 bytes) at 8 TB/s, and 2 x n_q x rows x 16 ceil(dim / 16) flops at the bf16 matrix peak
+(2516.8 TFLOP/s) -- with `bound` naming the larger and `share` = that floor over image_us.  Apart: image_build_ms (fr_ctx_set_retrieve_image over the
+whole table, host clock around the synchronous call) and fr_worker_update_rows of 1 000 / 100 000 ids without and with an image (the patch is a second
+launch: update_ratio = with / without).
+--image bf16 --parent-lib <libfleetrec.so of the parent commit, its companions beside it> [--rounds 3]: first, `parent_check`: the fp32 call and an
+fr_worker_update_rows without an image on the parent's build (loaded through FR_LIB) and on this one, each run a process of its own, alternating
+(parent, this, parent, this, ...); per case the ratio of the medians and the parent's own spread over its runs ((max - min) / median).
 """
 import argparse
 import json
@@ -81,17 +91,140 @@ def leg_torch(args):
     print(json.dumps(out), flush=True)
 
 
+MFMA_BF16_FLOPS = 16 * MFMA_F32_FLOPS
+
+
+def leg_fp32(args, fr):
+    """one process: the fp32 call over the grid and the update without an image -> {key: us}"""
+    rng, out = np.random.default_rng(91), {}
+    for dim in (32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": args.rows}, {"dim": 8, "rows": 16}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=-1 if args.rehearse else 0)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        wk = fr.Worker(ctx, 16)
+        for n in (1000, 100000):
+            d_id = fr.DeviceBuffer.from_numpy(ctx, rng.integers(0, args.rows, n).astype(np.int32))
+            d_row = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n, dim)).astype(np.float32))
+            out["update,%d,%d" % (dim, n)] = round(timed(wk, lambda: wk.update_rows(0, n, d_id, d_row), args.calls, args.repeats)[0], 2)
+        for n_q in (1, 32, 256):
+            d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+            for k in (16, 256):
+                d_r, d_s = fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+                out["retrieve,%d,%d,%d" % (dim, n_q, k)] = round(timed(wk, lambda: wk.retrieve_device(0, 0, args.rows, n_q, d_q, k, d_r, d_s), args.calls, args.repeats)[0], 2)
+        wk.close()
+        ctx.close()
+    print(json.dumps(out), flush=True)
+
+
+def parent_check(args):
+    runs = {"parent": [], "this": []}
+    for _ in range(args.rounds):
+        for setting in ("parent", "this"):
+            env = dict(os.environ)
+            if setting == "parent":
+                env["FR_LIB"] = os.path.abspath(args.parent_lib)
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", "fp32", "--rows", str(args.rows), "--calls", str(args.calls), "--repeats", str(args.repeats)]
+            p = subprocess.run(cmd + (["--rehearse"] if args.rehearse else []), capture_output=True, text=True, timeout=240, env=env)
+            if p.returncode != 0:
+                sys.exit("retrieve_bench: the %s leg ended with status %d; nothing more is started\n%s" % (setting, p.returncode, p.stderr[-400:]))
+            runs[setting].append(json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]))
+    out = []
+    for key in runs["this"][0]:
+        par, this = [r[key] for r in runs["parent"]], [r[key] for r in runs["this"]]
+        out.append({"case": key, "parent_us": par, "this_us": this, "this_over_parent": round(float(np.median(this) / np.median(par)), 4),
+                    "parent_spread": round(float((max(par) - min(par)) / np.median(par)), 4)})
+        print(json.dumps(out[-1]), flush=True)
+    return out
+
+
+def main_image(args, fr):
+    import time
+    device, rows = (-1, 20000) if args.rehearse else (0, args.rows)
+    res = {"tool": "tools/retrieve_bench.py --image bf16", "rows": rows, "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse), "calls": args.calls,
+           "repeats": args.repeats, "peaks": {"hbm_bytes_per_s": HBM_BYTES_PER_S, "mfma_bf16_flops": MFMA_BF16_FLOPS}, "cases": [], "image_build": [], "update_rows": []}
+    if args.parent_lib:
+        res["parent_check"] = parent_check(args)
+    rng = np.random.default_rng(91)
+    for dim in (16, 32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": rows}, {"dim": 8, "rows": 16}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=device)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        wk = fr.Worker(ctx, 16)
+        ups = {}
+        for n in (1000, 100000):   # without an image first: the launches of the parent
+            ids = rng.integers(0, rows, n).astype(np.int32)
+            d_id, d_row = fr.DeviceBuffer.from_numpy(ctx, ids), fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n, dim)).astype(np.float32))
+            ups[n] = (d_id, d_row, timed(wk, lambda: wk.update_rows(0, n, d_id, d_row), args.calls, args.repeats)[0])
+        builds = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            ctx.set_retrieve_image(0)
+            builds.append(round(1e3 * (time.perf_counter() - t0), 3))
+        steps, tiles = (dim + 15) // 16, (rows + 31) // 32
+        image_bytes = tiles * steps * 1024
+        res["image_build"].append({"dim": dim, "image_bytes": image_bytes, "table_bytes": rows * dim * 4, "image_build_ms": float(np.median(builds)), "all_ms": builds})
+        print(json.dumps(res["image_build"][-1]), flush=True)
+        for n, (d_id, d_row, without) in ups.items():
+            with_us = timed(wk, lambda: wk.update_rows(0, n, d_id, d_row), args.calls, args.repeats)[0]
+            res["update_rows"].append({"dim": dim, "ids": n, "without_image_us": round(without, 2), "with_image_us": round(with_us, 2), "update_ratio": round(with_us / without, 3)})
+            print(json.dumps(res["update_rows"][-1]), flush=True)
+            d_id.free()
+            d_row.free()
+        for n_q in (1, 32, 256):
+            d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+            for k in (16, 256):
+                d_r, d_s = fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+                calls = {"fp32": lambda: wk.retrieve_device(0, 0, rows, n_q, d_q, k, d_r, d_s), "image": lambda: wk.retrieve_image_device(0, 0, rows, n_q, d_q, k, d_r, d_s)}
+                us = {"fp32": [], "image": []}
+                for c in calls.values():
+                    c()
+                wk.sync()
+                for _ in range(args.repeats):   # alternating windows
+                    for name, c in calls.items():
+                        us[name].append(timed(wk, c, args.calls, 1)[0])
+                f, i = float(np.median(us["fp32"])), float(np.median(us["image"]))
+                hbm_floor, mfma_floor = image_bytes / HBM_BYTES_PER_S, 2.0 * n_q * rows * 16 * steps / MFMA_BF16_FLOPS
+                case = {"dim": dim, "n_q": n_q, "k": k, "fp32_us": round(f, 2), "image_us": round(i, 2), "speedup": round(f / i, 3),
+                        "fp32_windows_us": [round(u, 2) for u in us["fp32"]], "image_windows_us": [round(u, 2) for u in us["image"]],
+                        "bound": "hbm" if hbm_floor >= mfma_floor else "mfma", "share": round(max(hbm_floor, mfma_floor) / (i * 1e-6), 4),
+                        "hbm_share": round(hbm_floor / (i * 1e-6), 4), "mfma_share": round(mfma_floor / (i * 1e-6), 4)}
+                res["cases"].append(case)
+                print(json.dumps(case), flush=True)
+                d_r.free()
+                d_s.free()
+            d_q.free()
+        wk.close()
+        ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--image", default="", choices=("", "bf16"))
+    ap.add_argument("--parent-lib")
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--leg", default="")
     ap.add_argument("--rows", type=int, default=1 << 22)
     ap.add_argument("--calls", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "retrieve.json"))
+    ap.add_argument("--out", default="")
     ap.add_argument("--rehearse", action="store_true")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_lp.json" if args.image else "retrieve.json")
     if args.leg == "torch":
         return leg_torch(args)
+    if args.image or args.leg == "fp32":
+        import __graft_entry__ as graft
+        fr = graft.load_package()
+        if not args.rehearse and fr.device_count() < 1:
+            sys.exit("retrieve_bench: no MI355X visible -- a timing needs the GPU")
+        if args.rehearse:
+            args.rows = 20000
+        return leg_fp32(args, fr) if args.leg == "fp32" else main_image(args, fr)
     torch_us, torch_note = {}, None
     if not args.rehearse:
         try:
