@@ -93,6 +93,7 @@ ABI_SYMBOLS = [
     "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
     "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
     "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
+    "fr_ctx_set_retrieve_lists", "fr_ctx_retrieve_lists", "fr_worker_retrieve_probed_device", "fr_worker_retrieve_probed",
     "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -114,6 +115,7 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_submit_sharded_pooled_csr", "fr_worker_calibrate_fp8_sharded_pooled",
                    "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
                    "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
+                   "fr_ctx_set_retrieve_lists", "fr_ctx_retrieve_lists", "fr_worker_retrieve_probed_device", "fr_worker_retrieve_probed",
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -207,6 +209,8 @@ def lib():
         "fr_worker_topk_device": (i32, [vp, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_topk": (i32, [vp, i32, i32, vp, i32, vp, vp]),
         "fr_worker_retrieve_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
         "fr_ctx_set_retrieve_image": (i32, [vp, i32, i32]),
+        "fr_ctx_set_retrieve_lists": (i32, [vp, i32, i32, vp]), "fr_ctx_retrieve_lists": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64)]),
+        "fr_worker_retrieve_probed_device": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_retrieve_probed": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
         "fr_worker_retrieve_image_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve_image": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
         "fr_ctx_set_request_columns": (i32, [vp, pi, i32, i32]), "fr_ctx_request_words": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
@@ -663,6 +667,18 @@ class Context:
         """fr_ctx_set_retrieve_image: RETRIEVE_IMAGE_BF16 (the default) builds the table's bf16 retrieval image (synchronous, like upload_table),
         RETRIEVE_IMAGE_NONE frees it.  upload_table / fill_tables make an image stale until this is called again; update_rows keeps it current."""
         _check(lib().fr_ctx_set_retrieve_image(self._h, int(table), RETRIEVE_IMAGE_BF16 if kind is None else int(kind)))
+
+    def set_retrieve_lists(self, table, offsets):
+        """fr_ctx_set_retrieve_lists: offsets int64 [n_lists + 1] -- list l is the rows [offsets[l], offsets[l + 1]) of the table (synchronous, like
+        upload_table); None or a single offset drops the partition."""
+        off = np.zeros(1, np.int64) if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        _check(lib().fr_ctx_set_retrieve_lists(self._h, int(table), off.size - 1, off.ctypes.data_as(ctypes.c_void_p) if off.size > 1 else None))
+
+    def retrieve_lists(self, table):
+        """fr_ctx_retrieve_lists -> (n_lists, rows of the longest list); (0, 0) without a partition"""
+        n, longest = ctypes.c_int(0), ctypes.c_int64(0)
+        _check(lib().fr_ctx_retrieve_lists(self._h, int(table), ctypes.byref(n), ctypes.byref(longest)))
+        return n.value, longest.value
 
     def set_lp_bank_image(self, on):
         """fleetrec_diag.h: 0 = the in-chain gather of a per-bank bf16 / fp8 context reads the fp32 rows (A/B and parity hook)."""
@@ -1314,6 +1330,22 @@ class Worker:
     def retrieve_image(self, table, queries, k, row0=0, n_rows=None):
         """fr_worker_retrieve_image, then sync(): the arguments and results of retrieve()."""
         return self.retrieve(table, queries, k, row0, n_rows, _entry="fr_worker_retrieve_image")
+
+    # probed (IVF) retrieval over the table's list partition (Context.set_retrieve_lists; fr_worker_retrieve_probed_device / fr_worker_retrieve_probed) ----
+    def retrieve_probed_device(self, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores=None):
+        """fr_worker_retrieve_probed_device: retrieve_device over the union of the lists d_probe int32 [n_q][n_probe] names per query (< 0: none) -- what
+        retrieve_device over a centroid table with k = n_probe wrote as its rows.  Asynchronous: sync() is the completion point."""
+        _check(lib().fr_worker_retrieve_probed_device(self._h, int(table), int(n_q), self._ptr(d_queries), int(n_probe), self._ptr(d_probe), int(k),
+                                                      self._ptr(d_top_rows), self._ptr(d_top_scores)))
+
+    def retrieve_probed(self, table, queries, probe, k):
+        """fr_worker_retrieve_probed, then sync(): queries float32 [n_q][dim], probe int32 [n_q][n_probe] -> (rows int32 [n_q][k], scores float32 [n_q][k])."""
+        q, p = np.ascontiguousarray(queries, dtype=np.float32), np.ascontiguousarray(probe, dtype=np.int32)
+        out_r, out_s = np.empty((q.shape[0], int(k)), np.int32), np.empty((q.shape[0], int(k)), np.float32)
+        _check(lib().fr_worker_retrieve_probed(self._h, int(table), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), p.shape[1], p.ctypes.data_as(ctypes.c_void_p), int(k),
+                                               out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
+        self.sync()
+        return out_r, out_s
 
     def infer_topk(self, idx, k, seg_offsets=None, dense=None):
         """infer() with the ranking on the device: idx int32 [B][idx_cols] (+ dense) -> (positions int32 [n_seg][k], scores float32 [n_seg][k]) of the

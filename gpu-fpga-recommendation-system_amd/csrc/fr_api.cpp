@@ -446,6 +446,7 @@ extern "C" int fr_ctx_create_sharded(const fr_model_desc *m, int device, int sha
     c->model.segments = c->segments.data();
     c->table_mem.assign(m->n_tables, FrTableMem{});
     c->rt_img.resize((size_t)m->n_tables);   // (sized once: workers read the entries without a lock)
+    c->rt_lists.resize((size_t)m->n_tables);
     c->shard_rank = shard_rank;
     c->n_shards = n_shards;
     c->stream_group.store(fused_group_initial(), std::memory_order_relaxed);
@@ -3093,6 +3094,193 @@ extern "C" int fr_ctx_set_retrieve_image(fr_ctx *ctx, int table, int kind) {
     return FR_OK;
 }
 
+// ---- probed (IVF) retrieval (fleetrec_serving.h) ---------------------------------------------------------------------------------------------
+// The kernels are the tenth companion's (fr_retrieve_probe.hip -> libfleetrec_retrieve_probe.so); the split rule is fr_retrieve_probe_split
+// (fr_internal.h), the merge is the ranking companion's and the row mapping fr_retrieve_launch's step 1, the CPU twin is frc_retrieve_probed.
+extern "C" int fr_ctx_set_retrieve_lists(fr_ctx *ctx, int table, int n_lists, const int64_t *h_offsets) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (n_lists < 0 || n_lists > FR_RETRIEVE_MAX_LISTS) FR_FAIL(FR_ERR_INVALID, "n_lists = %d outside [0, %d]", n_lists, FR_RETRIEVE_MAX_LISTS);
+    const fr_table_desc &d = ctx->tables[table];
+    const FrTableMem &tm = ctx->table_mem[table];
+    int64_t max_rows = 0;
+    if (n_lists) {
+        if (!h_offsets) FR_FAIL(FR_ERR_INVALID, "h_offsets is NULL");
+        if (h_offsets[0] < 0) FR_FAIL(FR_ERR_INVALID, "h_offsets[0] = %lld is negative", (long long)h_offsets[0]);
+        for (int l = 0; l < n_lists; l++) {
+            if (h_offsets[l + 1] < h_offsets[l]) FR_FAIL(FR_ERR_INVALID, "h_offsets[%d] = %lld is below h_offsets[%d] = %lld", l + 1, (long long)h_offsets[l + 1], l, (long long)h_offsets[l]);
+            max_rows = std::max(max_rows, h_offsets[l + 1] - h_offsets[l]);
+        }
+        if (h_offsets[n_lists] > (int64_t)d.rows || h_offsets[n_lists] > (1ll << 31))
+            FR_FAIL(FR_ERR_INVALID, "the last list ends at row %lld, past table %d (%lld rows) or past row 2^31", (long long)h_offsets[n_lists], table, (long long)d.rows);
+        if (ctx->model.index_mode == FR_INDEX_PER_BANK || tm.il_rows)
+            FR_FAIL(FR_ERR_STATE, "retrieval reads dense tables; the tables of an FR_INDEX_PER_BANK context are interleaved in bank rows");
+        if (ctx->n_shards > 1 || !tm.resident) FR_FAIL(FR_ERR_STATE, "retrieval is not available on a table-sharded context (shard %d of %d)", ctx->shard_rank, ctx->n_shards);
+        if (d.dim > FR_RETRIEVE_MAX_DIM) FR_FAIL(FR_ERR_STATE, "table %d has dim %d; retrieval holds a query in registers up to dim %d", table, d.dim, FR_RETRIEVE_MAX_DIM);
+    }
+    fr_ctx::RetrieveLists &rl = ctx->rt_lists[table];
+    if (rl.n_lists) {   // the pattern of fr_pooling_busy, narrowed to the work that reads a partition
+        std::lock_guard<std::mutex> g(ctx->workers_mutex);
+        for (const fr_worker *w : ctx->workers)
+            if (w->rt_probed) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_retrieve_lists: a worker of the context has a probed retrieval in flight: call fr_worker_sync first");
+    }
+    FrBuf<int64_t> off;
+    if (n_lists) {
+        FR_SET_DEVICE(ctx);
+        FR_TRY(off.alloc(fr_mem_kind(ctx, FrMem::DEVICE), (size_t)n_lists + 1, "retrieval list offsets"));
+        if (ctx->cpu) {
+            memcpy(off.p, h_offsets, ((size_t)n_lists + 1) * sizeof(int64_t));
+        } else {
+            FR_HIP(hipMemcpyAsync(off.p, h_offsets, ((size_t)n_lists + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->setup_stream));
+            FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+        }
+    }
+    rl.off = std::move(off);   // (the one release path: whatever it held goes with the assignment)
+    rl.n_lists = n_lists, rl.max_rows = max_rows;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_retrieve_lists(const fr_ctx *ctx, int table, int *n_lists, int64_t *max_list_rows) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (n_lists) *n_lists = ctx->rt_lists[table].n_lists;
+    if (max_list_rows) *max_list_rows = ctx->rt_lists[table].max_rows;
+    return FR_OK;
+}
+
+// retrieve_check's refusals (a probed call has no window: one row stands in for it), then the probed call's own
+static int retrieve_probed_check(fr_worker *w, int table, int n_q, const void *queries, int n_probe, const void *probe, int k, const void *top_rows) {
+    FR_TRY(retrieve_check(w, table, 0, 1, n_q, queries, k, top_rows, false));
+    if (!probe) FR_FAIL(FR_ERR_INVALID, "probe is NULL");
+    if (n_probe < 1 || n_probe > FR_RETRIEVE_MAX_PROBE) FR_FAIL(FR_ERR_INVALID, "n_probe = %d outside [1, %d]", n_probe, FR_RETRIEVE_MAX_PROBE);
+    if (!w->ctx->rt_lists[table].n_lists) FR_FAIL(FR_ERR_STATE, "table %d has no list partition: call fr_ctx_set_retrieve_lists first", table);
+    if ((int64_t)n_q * n_probe * k > (1ll << 24))
+        FR_FAIL(FR_ERR_INVALID, "n_q * n_probe * k = %lld partial scores are more than one ranking call takes (2^24)", (long long)n_q * n_probe * k);
+    return FR_OK;
+}
+
+// The launches of one probed retrieval on the worker's stream (the rule of retrieve_enqueue).  h_queries != NULL: the host form -- the pinned staging
+// holds the queries and, behind them, the probe rows; both are copied into the scratch first.
+static int retrieve_probed_enqueue(fr_worker *w, int table, int n_q, const float *d_queries, const float *h_queries, int n_probe, const int32_t *d_probe, int k,
+                                   int32_t *d_top_rows, float *d_top_scores) {
+    fr_ctx *c = w->ctx;
+    FR_TRY(fr_host_fed_queued(w, "retrieve"));
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
+    FR_SET_DEVICE(c);
+    const fr_ctx::RetrieveLists &rl = c->rt_lists[table];
+    const int dim = c->tables[table].dim;
+    const size_t P = (size_t)n_q * (size_t)n_probe;
+    FrRetrieveProbeArgs a{};
+    a.table = reinterpret_cast<const float *>(c->table_arena + c->table_mem[table].byte_offset);
+    a.offsets = rl.off.p;
+    a.dim = dim, a.n_q = n_q, a.k = k, a.n_probe = n_probe, a.n_lists = rl.n_lists;
+    a.split = fr_retrieve_probe_split((int64_t)P, k, rl.max_rows, c->n_cu, &a.part);
+    a.tiles_cap = (int)fr_retrieve_probe_tiles((int64_t)P, rl.n_lists);
+    a.err_flag = w->d_err;
+    const size_t n_part = P * (size_t)a.split * (size_t)k;   // <= 2^24
+    const size_t plane = align_up(n_part * 4, 256), off_bytes = align_up(((size_t)n_q + 1) * 4, 256), pos_bytes = align_up((size_t)n_q * k * 4, 256);
+    const size_t pair_bytes = align_up(P * 4, 256), tile_bytes = align_up((size_t)a.tiles_cap * 4, 256), first_bytes = align_up(((size_t)rl.n_lists + 1) * 8, 256);
+    const size_t q_bytes = h_queries ? align_up(((size_t)n_q * dim + P) * 4, 256) : 0;
+    const size_t need = 2 * plane + off_bytes + pos_bytes + 3 * pair_bytes + tile_bytes + first_bytes + q_bytes;
+    if (need > w->d_retrieve.count()) {
+        if (w->d_retrieve) FR_HIP(hipStreamSynchronize(w->stream));   // an earlier retrieval may still use it
+        FR_TRY(w->d_retrieve.grow(FrMem::DEVICE, need, "retrieval scratch"));
+    }
+    if ((size_t)rl.n_lists > w->d_probe_cnt.count()) {
+        if (w->d_probe_cnt) FR_HIP(hipStreamSynchronize(w->stream));
+        FR_TRY(w->d_probe_cnt.grow(FrMem::DEVICE, (size_t)rl.n_lists, "probed retrieval list counters"));
+        w->probe_cnt_clean = false;
+    }
+    char *p = w->d_retrieve.p;
+    auto take = [&](size_t bytes) {
+        char *at = p;
+        p += bytes;
+        return at;
+    };
+    a.part_scores = reinterpret_cast<float *>(take(plane));
+    a.part_rows = reinterpret_cast<int32_t *>(take(plane));
+    a.seg_off = reinterpret_cast<int32_t *>(take(off_bytes));
+    int32_t *top_pos = reinterpret_cast<int32_t *>(take(pos_bytes));
+    a.list_first = reinterpret_cast<unsigned long long *>(take(first_bytes));
+    a.slots = reinterpret_cast<int32_t *>(take(pair_bytes));
+    a.slot_base = reinterpret_cast<int32_t *>(take(pair_bytes));
+    a.pairs = reinterpret_cast<int32_t *>(take(pair_bytes));
+    a.tile_list = reinterpret_cast<int32_t *>(take(tile_bytes));
+    a.list_cnt = w->d_probe_cnt.p;
+    a.queries = d_queries, a.probe = d_probe;
+    int rc = fr_fused_flush(w);
+    if (!rc) rc = pipeline_flush(w);
+    if (rc) return rc;
+    if (h_queries) {
+        float *dq = reinterpret_cast<float *>(take(q_bytes));
+        FR_HIP(hipMemcpyAsync(dq, h_queries, ((size_t)n_q * dim + P) * 4, hipMemcpyHostToDevice, w->stream));
+        a.queries = dq, a.probe = reinterpret_cast<const int32_t *>(dq + (size_t)n_q * dim);
+    }
+    void *s = (void *)w->stream;
+    int e = w->probe_cnt_clean ? 0 : fr_retrieve_probe_clear_launch(w->d_probe_cnt.p, (int)w->d_probe_cnt.count(), s);
+    if (e) FR_FAIL(FR_ERR_HIP, "the probed retrieval's counter clear launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->probe_cnt_clean = false;   // until the scatter that counts them back down is on the stream
+    w->in_flight = true, w->rt_probed = true;
+    e = fr_retrieve_probe_sort_launch(&a, s);
+    if (!e) e = fr_retrieve_probe_group_launch(&a, s);
+    if (!e) e = fr_retrieve_probe_scatter_launch(&a, s);
+    if (e) FR_FAIL(FR_ERR_HIP, "a grouping launch of the probed retrieval failed: %s", hipGetErrorString((hipError_t)e));
+    w->probe_cnt_clean = true;
+    e = fr_retrieve_probe_scan_launch(&a, s);
+    if (e) FR_FAIL(FR_ERR_HIP, "the probed retrieval's scan launch failed: %s", hipGetErrorString((hipError_t)e));
+    // a query's stretch of the planes is one segment of the ranking; its positions index the planes as n_probe * split chunks of k
+    FR_TRY(topk_enqueue(w, (int)n_part, a.part_scores, n_q, a.seg_off, k, top_pos, nullptr));
+    FrRetrieveArgs m{};
+    m.n_q = n_q, m.k = k, m.n_chunks = n_probe * a.split;
+    m.part_scores = a.part_scores, m.part_rows = a.part_rows, m.top_pos = top_pos, m.top_rows = d_top_rows, m.top_scores = d_top_scores;
+    e = fr_retrieve_launch(&m, 1, s);
+    if (e) FR_FAIL(FR_ERR_HIP, "the retrieval row-mapping launch failed: %s", hipGetErrorString((hipError_t)e));
+    return FR_OK;
+}
+
+static void retrieve_probed_cpu(fr_worker *w, int table, int n_q, const float *queries, int n_probe, const int32_t *probe, int k, int32_t *top_rows, float *top_scores) {
+    const fr_ctx *c = w->ctx;
+    const fr_ctx::RetrieveLists &rl = c->rt_lists[table];   // an id >= n_lists waits in c_err for fr_worker_sync
+    if (frc_retrieve_probed(retrieve_cpu_table(c, table), c->tables[table].dim, rl.off, rl.n_lists, n_q, queries, n_probe, probe, k, top_rows, top_scores))
+        __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+}
+
+extern "C" int fr_worker_retrieve_probed_device(fr_worker *w, int table, int n_q, const float *d_queries, int n_probe, const int32_t *d_probe, int k, int32_t *d_top_rows,
+                                                float *d_top_scores) {
+    FR_TRY(retrieve_probed_check(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows));
+    if (w->ctx->cpu) {   // computed before the call returns
+        retrieve_probed_cpu(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores);
+        return FR_OK;
+    }
+    return retrieve_probed_enqueue(w, table, n_q, d_queries, nullptr, n_probe, d_probe, k, d_top_rows, d_top_scores);
+}
+
+extern "C" int fr_worker_retrieve_probed(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
+                                         float *h_top_scores) {
+    FR_TRY(retrieve_probed_check(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows));
+    if (w->ctx->cpu) {
+        retrieve_probed_cpu(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows, h_top_scores);
+        return FR_OK;
+    }
+    if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking or retrieval is already in flight on this worker: call fr_worker_sync first");
+    FR_TRY(fr_host_fed_queued(w, "retrieve"));   // (before the staging is touched: nothing happens on a refusal)
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
+    FR_SET_DEVICE(w->ctx);
+    const size_t n_query = (size_t)n_q * (size_t)w->ctx->tables[table].dim, n_ids = (size_t)n_q * (size_t)n_probe, n_out = (size_t)n_q * (size_t)k;
+    if (n_query + n_ids > w->h_rt_q.count() || n_out > w->h_tk_idx.count() || n_out > w->h_tk_sc.count()) {   // a grow waits for the stream before pinned memory is released
+        FR_HIP(hipStreamSynchronize(w->stream));
+        FR_TRY(w->h_rt_q.grow(FrMem::PINNED, n_query + n_ids, "retrieval queries"));
+        FR_TRY(w->h_tk_idx.grow(FrMem::PINNED, n_out, "ranking results"));
+        FR_TRY(w->h_tk_sc.grow(FrMem::PINNED, n_out, "ranking result scores"));
+    }
+    memcpy(w->h_rt_q, h_queries, n_query * sizeof(float));
+    memcpy(w->h_rt_q + n_query, h_probe, n_ids * sizeof(int32_t));
+    const int rc = retrieve_probed_enqueue(w, table, n_q, nullptr, w->h_rt_q, n_probe, nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr);
+    if (rc) return rc;
+    w->tk_dst_idx = h_top_rows, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
+    return FR_OK;
+}
+
 // ---- request-form batches (fleetrec_serving.h) -------------------------------------------------------------------------------------------------
 // The kernel is the second companion code object's (fr_request.hip -> libfleetrec_request.so, linked with an $ORIGIN rpath); the descriptor tables,
 // state and the host form are here, the CPU twin in fr_cpu.cpp.
@@ -3545,7 +3733,7 @@ extern "C" int fr_worker_sync(fr_worker *w) {
     // whatever this sync returns, the host-form batch is no longer in flight and an undelivered host-form ranking is dropped
     struct TopkDone {
         fr_worker *w;
-        ~TopkDone() { w->host_batch = 0, w->tk_count = 0; }
+        ~TopkDone() { w->host_batch = 0, w->tk_count = 0, w->rt_probed = false; }
     } topk_done{w};
     if (w->ctx->cpu) {   // everything was computed inside the calls -- but for a table-sharded step, which runs on the worker's host stream
         const int crc = fr_comm_wait(w);   // (bounded wait + the ranks' status words, fr_comm.cpp; FR_OK at once when no such step is in flight)

@@ -307,6 +307,51 @@ void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int
     });
 }
 
+// Probed retrieval: per query the valid ids of its probe row, sorted and taken once -- the union in row order --, then frc_retrieve's score and
+// composite over those rows, the low word by ABSOLUTE row.  No read outside probe[n_q][n_probe], offsets[l], offsets[l + 1] of a valid l and the rows
+// those name.
+int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
+                        int32_t *top_rows, float *top_scores) {
+    const int units = n_q < Pool::get().size() ? n_q : Pool::get().size();
+    std::atomic<int> bad{0};
+    Pool::get().run(units, [&](int u) {
+        std::vector<uint64_t> comp;
+        std::vector<int32_t> lists;
+        const int qa = (int)((int64_t)n_q * u / units), qb = (int)((int64_t)n_q * (u + 1) / units);
+        for (int q = qa; q < qb; q++) {
+            lists.clear();
+            for (int i = 0; i < n_probe; i++) {
+                const int32_t id = probe[(size_t)q * (size_t)n_probe + (size_t)i];
+                if (id >= n_lists) bad.store(1, std::memory_order_relaxed);
+                else if (id >= 0) lists.push_back(id);
+            }
+            std::sort(lists.begin(), lists.end());
+            lists.erase(std::unique(lists.begin(), lists.end()), lists.end());
+            comp.clear();
+            const float *qv = queries + (size_t)q * (size_t)dim;
+            for (const int32_t l : lists)
+                for (int64_t row = offsets[l]; row < offsets[l + 1]; row++) {
+                    const float *t = table + (size_t)row * (size_t)dim;
+                    float acc = -0.0f;
+                    for (int c = 0; c < dim; c++) acc += qv[c] * t[c];
+                    uint32_t bits;
+                    memcpy(&bits, &acc, 4);
+                    comp.push_back(((uint64_t)fr_rank_key(bits) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row));
+                }
+            const size_t top = comp.size() < (size_t)k ? comp.size() : (size_t)k;
+            std::partial_sort(comp.begin(), comp.begin() + (ptrdiff_t)top, comp.end(), std::greater<uint64_t>());
+            for (size_t j = 0; j < (size_t)k; j++) {
+                const size_t o = (size_t)q * (size_t)k + j;
+                const uint32_t key = j < top ? (uint32_t)(comp[j] >> 32) : 0u;
+                const uint32_t bits = j >= top ? 0xff800000u : (key == 0u ? 0x7fc00000u : ((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key));
+                top_rows[o] = j < top ? (int32_t)(0xffffffffu - (uint32_t)comp[j]) : -1;
+                if (top_scores) memcpy(top_scores + o, &bits, 4);
+            }
+        }
+    });
+    return bad.load(std::memory_order_relaxed);
+}
+
 // The retrieval image of the CPU back-end: the bf16 values of the device image (fr_bf16_rne), row-major.  No read outside the listed / ranged rows.
 static inline float bf16_value(uint16_t v) {
     const uint32_t bits = (uint32_t)v << 16;

@@ -368,6 +368,54 @@ struct FrRetrieveLpArgs {
 extern "C" int fr_retrieve_lp_image_launch(const FrRetrieveImageArgs *args, void *stream);
 extern "C" int fr_retrieve_lp_scan_launch(const FrRetrieveLpArgs *args, void *stream);
 
+// ---- probed (IVF) retrieval (fr_retrieve_probe.hip -> libfleetrec_retrieve_probe.so, the tenth companion; fr_cpu.cpp has the twin) ----
+// A table's list partition (fr_ctx_set_retrieve_lists): list l is the rows [offsets[l], offsets[l + 1]).  Query q scans the lists probe[q][0 .. n_probe).
+// probe_sort_kernel turns a probe row into SLOTS: its distinct, valid, non-empty lists in ascending order (= ascending rows), -1 behind them.  A live
+// (query, slot) is a PAIR, named e = q * n_probe + slot; the two grouping kernels order the pairs by list, 32 pairs of one list are a TILE, and
+// retrieve_probe_scan_kernel's workgroup (tile, part) scores the tile's queries against part `part` of the list: rows [lb + part * `part`, + `part`).
+// A query's partial leaders sit COMPACT in its stretch of the planes, [q * stride, (q + 1) * stride) with stride = n_probe * split * k, in (slot, part)
+// order -- a part with r rows holds min(k, r) entries -- and every pad behind them: the stretch is one segment of fr_rank_launch, and
+// retrieve_rows_kernel (fr_retrieve_launch, step 1, n_chunks = n_probe * split) maps its positions to rows.
+constexpr int FR_RETRIEVE_PROBE_SCAN_THREADS = 1024;   // the one workgroup of probe_group_scan_kernel: 4 lists per thread and pass
+struct FrRetrieveProbeArgs {
+    const float *table;            // row 0 of the table (16-byte aligned), rows dim floats apart
+    const float *queries;          // [n_q][dim]
+    const int32_t *probe;          // [n_q][n_probe] list ids; < 0: none; >= n_lists: none + the error flag
+    const int64_t *offsets;        // [n_lists + 1], non-decreasing, inside the table
+    int dim, n_q, k, n_probe, n_lists;
+    int split;                     // parts a list is cut into (a power of two)
+    int64_t part;                  // rows of a part: a multiple of FR_RETRIEVE_ROUND, >= FR_RETRIEVE_MIN_CHUNK, split * part >= the longest list
+    int tiles_cap;                 // fr_retrieve_probe_tiles(n_q * n_probe, n_lists): the scan's grid and tile_list's length
+    int32_t *slots;                // [n_q][n_probe]
+    int32_t *slot_base;            // [n_q][n_probe]: plane index of a live slot's first entry
+    int *list_cnt;                 // [n_lists]: pairs of a list; 0 before the sort and again behind the scatter
+    unsigned long long *list_first;   // [n_lists + 1]: (first pair << 32) | first tile of a list; [n_lists]: the totals
+    int32_t *pairs;                // [n_q * n_probe]: the pairs in list order (inside a list: in the order the scatter's atomics gave)
+    int32_t *tile_list;            // [tiles_cap]: the list of a tile
+    float *part_scores;            // [n_q][stride]
+    int32_t *part_rows;            // [n_q][stride] absolute rows, -1 padded
+    int32_t *seg_off;              // [n_q + 1] = q * stride (written by the sort)
+    int *err_flag;
+};
+// tiles the pairs can make: sum over the lists with pairs of ceil(count / 32) <= P / 32 + (lists with pairs)
+static inline int64_t fr_retrieve_probe_tiles(int64_t P, int n_lists) { return (P + 31) / 32 + (P < n_lists ? P : (int64_t)n_lists); }
+// The split of a probed call: the host knows P = n_q * n_probe pairs and the longest list, not which lists are probed.  Few pairs make about one
+// tile each, so split is the smallest power of two with P * split >= 2 workgroups per CU -- as long as a part stays >= FR_RETRIEVE_MIN_CHUNK rows (only
+// a list's last non-empty part can then hold fewer than k rows) and the partial scores fit one ranking call (2^24).  -> split; *part = rows of a part.
+static inline int fr_retrieve_probe_split(int64_t P, int k, int64_t max_list_rows, int n_cu, int64_t *part) {
+    auto part_of = [&](int s) { return ((max_list_rows + s - 1) / s + FR_RETRIEVE_ROUND - 1) / FR_RETRIEVE_ROUND * FR_RETRIEVE_ROUND; };
+    int split = 1;
+    while (P * split < 2 * (int64_t)n_cu && part_of(2 * split) >= FR_RETRIEVE_MIN_CHUNK && P * 2 * split * k <= (1ll << 24)) split *= 2;
+    *part = part_of(split) < FR_RETRIEVE_MIN_CHUNK ? FR_RETRIEVE_MIN_CHUNK : part_of(split);
+    return split;
+}
+// One launch each on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_retrieve_probe_clear_launch(int *list_cnt, int n, void *stream);
+extern "C" int fr_retrieve_probe_sort_launch(const FrRetrieveProbeArgs *args, void *stream);
+extern "C" int fr_retrieve_probe_group_launch(const FrRetrieveProbeArgs *args, void *stream);
+extern "C" int fr_retrieve_probe_scatter_launch(const FrRetrieveProbeArgs *args, void *stream);
+extern "C" int fr_retrieve_probe_scan_launch(const FrRetrieveProbeArgs *args, void *stream);
+
 // ---- request-form batches (fr_request.hip -> libfleetrec_request.so, the second companion code object; fr_cpu.cpp has the twin) ----------------
 // Row i of `out` ([batch][W] 32-bit words) is put together word by word: desc[w] >= 0 names word desc[w] of candidate row i ([batch][Rc]),
 // desc[w] < 0 names word ~desc[w] of the request row ([n_req][Rs]) of the request that owns item i -- the last r with off[r] <= i, clamped into
@@ -599,6 +647,14 @@ struct fr_ctx {
         bool stale = false;
     };
     std::vector<RetrieveImage> rt_img;     // [tables]
+    // List partitions (fr_ctx_set_retrieve_lists): per table the offsets [n_lists + 1] -- device memory, host memory on the CPU back-end -- and what
+    // the host keeps of them.  n_lists == 0: none.  Replaced or dropped only while no worker has a probed retrieval in flight (fr_worker::rt_probed).
+    struct RetrieveLists {
+        FrBuf<int64_t> off;
+        int n_lists = 0;
+        int64_t max_rows = 0;              // the longest list
+    };
+    std::vector<RetrieveLists> rt_lists;   // [tables]
     std::atomic<int> lp_image_on{1};       // fr_ctx_set_lp_bank_image (fleetrec_diag.h): 0 = the in-chain gather reads the fp32 rows and converts them itself
     // Pooled (multi-hot) lookups (fr_ctx_set_pooling): the descriptors made of the hots per index column, P = sum of hots (0: no pooling)
     std::vector<FrPoolDesc> h_pool;
@@ -847,6 +903,12 @@ struct fr_worker {
     // come back through h_tk_idx / h_tk_sc).
     FrBuf<char> d_retrieve;
     FrBuf<float> h_rt_q;
+    // Probed retrieval (fr_worker_retrieve_probed_device / fr_worker_retrieve_probed): everything but the per-list pair counters lives in d_retrieve (the
+    // host form's probe rows ride behind its queries in h_rt_q).  d_probe_cnt [lists] is all 0 between two calls: a clear launch follows its allocation
+    // and a call that failed between its sort and its scatter (probe_cnt_clean == false); the scatter itself counts every list back down to 0.
+    FrBuf<int> d_probe_cnt;
+    bool probe_cnt_clean = false;
+    bool rt_probed = false;     // a probed retrieval was enqueued since the last fr_worker_sync: its table's partition is not replaced meanwhile
     char last_kernel[96] = "";  // fr_worker_last_kernel: the dominant kernel of the most recent launch this worker enqueued
     FrEvent ev_start, ev_stop;
 };
@@ -886,6 +948,10 @@ int frc_rank_topk(const float *scores, int n, int n_seg, const int32_t *off, int
 // table[row0 .. row0 + n_rows) ([..][dim], dense) with the largest score s = -0 + q[0] t[0] + q[1] t[1] + ... in fp32, ascending c, ranked by fr_rank_key
 // with ties to the lower row; a NaN score is delivered as 0x7fc00000; (-1, -inf) behind the window's rows.  Queries over the pool's threads.
 void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores);
+// the CPU twin of the probed retrieval: frc_retrieve's score and order over the union of the lists probe[q][0 .. n_probe) names (each once; an id < 0 or
+// >= n_lists names none), list l = rows [offsets[l], offsets[l + 1]); -> 1 when an id was >= n_lists, else 0
+int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
+                        int32_t *top_rows, float *top_scores);
 // the CPU back-end's retrieval image, row-major [rows][dim] bf16 (fr_bf16_rne): ids == NULL converts rows [0, n) of `table`, else the n listed rows
 // (an id outside [0, rows) does nothing); and the twin of the image scan: frc_retrieve with s = -0 + bf16(q[0]) img[0] + ... , each product exact in fp32
 void frc_retrieve_image_rows(const float *table, int dim, int64_t rows, int64_t n, const int32_t *ids, uint16_t *img);

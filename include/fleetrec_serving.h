@@ -344,6 +344,42 @@ int fr_worker_retrieve_image_device(fr_worker *w, int table, int64_t row0, int64
 int fr_worker_retrieve_image(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int k, int32_t *h_top_rows,
                              float *h_top_scores /* or NULL */);
 
+/* Probed (IVF) retrieval (additive in ABI 6): the retrieval that reads FEWER ROWS.  A table gets a LIST PARTITION -- list l is the rows
+ * [h_offsets[l], h_offsets[l + 1]) -- and every query scans only the lists its probe row names.  Clustering (k-means, assigning rows to lists, ordering
+ * the table by list) stays with the caller, as training does; the library takes the partition as data.  With the centroids as one more table the coarse
+ * step is fr_worker_retrieve_device with k = n_probe, whose [n_q][n_probe] row output IS a probe array:
+ *   retrieve_device(centroid table, 0, n_lists, n_q, Q, n_probe, d_probe, NULL) -> retrieve_probed_device(item table, n_q, Q, n_probe, d_probe, k, ...)
+ *   -> candidate rows -> factored request scoring -> topk: one stream, no host round trip.
+ * fr_ctx_set_retrieve_lists(ctx, table, n_lists, h_offsets): offsets non-decreasing, h_offsets[0] >= 0, the last <= the table's rows and <= 2^31; empty
+ *   lists are allowed and the lists need not cover the table.  The offsets are copied to the device on the set-up stream and waited for, as
+ *   fr_ctx_upload_table does.  The partition says nothing about contents: uploads, fills and row updates leave it valid.  n_lists == 0 (h_offsets is not
+ *   read) drops it.  FR_ERR_INVALID: a NULL context, a table outside the model, n_lists outside 0 .. FR_RETRIEVE_MAX_LISTS, NULL or malformed offsets.
+ *   FR_ERR_STATE: what fr_worker_retrieve_device refuses of a context or table; replacing or dropping a partition while a worker of the context has a
+ *   probed retrieval enqueued and not yet synchronised.  fr_ctx_retrieve_lists reports n_lists (0: none) and the longest list (either may be NULL).
+ * fr_worker_retrieve_probed_device: the candidates of query q are the rows of the union of the lists d_probe[q][0 .. n_probe).  An id < 0 means "no
+ *   list" (what the coarse retrieval pads with); an id repeated within a probe row is scanned once; an id >= n_lists is scanned as "no list" and reported
+ *   as FR_ERR_INDEX_RANGE by fr_worker_sync, the way an out-of-range lookup index is -- it never causes a read outside the offsets or the table, and
+ *   every other query's result is what it would have been.
+ *   Score: that of fr_worker_retrieve_device, in the same fixed column order: the same bits the exact call gives for that (query, row), on any data,
+ *   on the same back-end.  Rank order, ties (LOWER ABSOLUTE ROW first, whatever the order of the ids in the probe row), NaN delivery (a real NaN row
+ *   before the padding) and padding (-1 / -inf behind the last candidate) are fr_worker_retrieve_device's.
+ *   Determinism: the result for a query is a function of its candidate set only; the device groups the work with atomics, and the grouping decides only
+ *   which workgroup scores a (query, row), never a score or a rank.
+ *   Stream order, scratch policy (one more buffer of 4 bytes per list) and fr_worker_last_kernel: as fr_worker_retrieve_device.  Nothing is read back:
+ *   the launch shape depends on the arguments, n_lists, the longest list and the CU count only.
+ *   Refusals: those of fr_worker_retrieve_device (without a window), and FR_ERR_INVALID: a NULL d_probe, n_probe outside 1 .. FR_RETRIEVE_MAX_PROBE,
+ *   n_q * n_probe * k above 2^24 (what one ranking call takes); FR_ERR_STATE: the table has no partition.  Nothing is enqueued on a refusal.
+ * fr_worker_retrieve_probed: the host form, as fr_worker_retrieve -- h_probe is copied into the same pinned staging as the queries. */
+#define FR_RETRIEVE_MAX_LISTS (1 << 20)
+#define FR_RETRIEVE_MAX_PROBE 256 /* = FR_RETRIEVE_MAX_K: any coarse retrieval's output can be a probe array */
+int fr_ctx_set_retrieve_lists(fr_ctx *ctx, int table, int n_lists, const int64_t *h_offsets /* [n_lists + 1] */);
+int fr_ctx_retrieve_lists(const fr_ctx *ctx, int table, int *n_lists, int64_t *max_list_rows);
+int fr_worker_retrieve_probed_device(fr_worker *w, int table, int n_q, const float *d_queries /* [n_q][dim] */, int n_probe,
+                                     const int32_t *d_probe /* [n_q][n_probe] list ids */, int k, int32_t *d_top_rows /* [n_q][k] */,
+                                     float *d_top_scores /* [n_q][k] or NULL */);
+int fr_worker_retrieve_probed(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
+                              float *h_top_scores /* or NULL */);
+
 /* Request-form batches (additive in ABI 6): the input side of the segments above.  A request is one user and N candidate items; without this its
  * batch arrives as N complete index rows, the user's columns (and dense features) repeated N times.  With a SPLIT set on the context a batch arrives
  * as request rows + candidate rows + segment offsets, and one small launch expands them on the device into the rows every existing lookup path takes.

@@ -23,6 +23,13 @@ launch: update_ratio = with / without).
 --image bf16 --parent-lib <libfleetrec.so of the parent commit, its companions beside it> [--rounds 3]: first, `parent_check`: the fp32 call and an
 fr_worker_update_rows without an image on the parent's build (loaded through FR_LIB) and on this one, each run a process of its own, alternating
 (parent, this, parent, this, ...); per case the ratio of the medians and the parent's own spread over its runs ((max - min) / median).
+
+--probed -> profiles/retrieve_probed.json: the probed (IVF) retrieval.  4 M hash-filled rows at dim 32 / 128 in equal lists, n_lists in {1024, 4096}, the
+centroids a second hash-filled table (recall is not the library's claim and is not measured); n_q in {1, 32, 256} x (n_probe, k) in {(8, 16), (32, 16),
+(32, 256)}.  Four legs alternate window by window in one process: coarse_us (fr_worker_retrieve_device over the centroids with k = n_probe), probed_us
+(fr_worker_retrieve_probed_device over its output), sum_us (both, back to back, as the composition runs them) and brute_us (fr_worker_retrieve_device over
+the whole table: the baseline).  covered_bytes = the bytes of the distinct lists the call's queries probed; covered_hbm_share = those bytes at 8 TB/s over
+probed_us; rows_fraction = covered_bytes over the table's.  --parent-lib adds the same parent_check as above.
 """
 import argparse
 import json
@@ -202,8 +209,70 @@ def main_image(args, fr):
     print("wrote", args.out)
 
 
+def main_probed(args, fr):
+    device, rows = (-1, 20000) if args.rehearse else (0, args.rows)
+    res = {"tool": "tools/retrieve_bench.py --probed", "rows": rows, "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse), "calls": args.calls,
+           "repeats": args.repeats, "peaks": {"hbm_bytes_per_s": HBM_BYTES_PER_S}, "cases": []}
+    if args.parent_lib:
+        res["parent_check"] = parent_check(args)
+    rng = np.random.default_rng(91)
+    for dim in (32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": rows}, {"dim": dim, "rows": 4096}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=device)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        wk = fr.Worker(ctx, 16)
+        for n_lists in (1024, 4096):
+            wk.sync()
+            off = np.arange(n_lists + 1, dtype=np.int64) * rows // n_lists
+            ctx.set_retrieve_lists(0, off)
+            for n_q in (1, 32, 256):
+                d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+                for n_probe, k in ((8, 16), (32, 16), (32, 256)):
+                    d_p, d_r, d_s = fr.DeviceBuffer(ctx, n_q * n_probe * 4), fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+
+                    def coarse():
+                        wk.retrieve_device(1, 0, n_lists, n_q, d_q, n_probe, d_p, None)
+
+                    def probed():
+                        wk.retrieve_probed_device(0, n_q, d_q, n_probe, d_p, k, d_r, d_s)
+
+                    def both():
+                        coarse()
+                        probed()
+
+                    calls = {"coarse": coarse, "probed": probed, "sum": both, "brute": lambda: wk.retrieve_device(0, 0, rows, n_q, d_q, k, d_r, d_s)}
+                    us = {name: [] for name in calls}
+                    both()
+                    wk.sync()
+                    ids = d_p.download(np.int32, n_q * n_probe)
+                    for _ in range(args.repeats):   # alternating windows
+                        for name, c in calls.items():
+                            us[name].append(timed(wk, c, args.calls, 1)[0])
+                    med = {name: float(np.median(v)) for name, v in us.items()}
+                    list_bytes = np.diff(off)[ids] * dim * 4   # every pair's list; a list that several queries probe is counted once in covered_bytes
+                    covered = int(np.diff(off)[np.unique(ids)].sum() * dim * 4)
+                    case = {"dim": dim, "n_lists": n_lists, "n_q": n_q, "n_probe": n_probe, "k": k, "coarse_us": round(med["coarse"], 2), "probed_us": round(med["probed"], 2),
+                            "sum_us": round(med["sum"], 2), "brute_us": round(med["brute"], 2), "brute_over_sum": round(med["brute"] / med["sum"], 3),
+                            "rows_fraction": round(covered / (rows * dim * 4), 5), "covered_bytes": covered, "pair_bytes": int(list_bytes.sum()),
+                            "covered_hbm_share": round(covered / HBM_BYTES_PER_S / (med["probed"] * 1e-6), 4),
+                            "windows_us": {name: [round(u, 2) for u in v] for name, v in us.items()}}
+                    res["cases"].append(case)
+                    print(json.dumps({key: v for key, v in case.items() if key != "windows_us"}), flush=True)
+                    for b in (d_p, d_r, d_s):
+                        b.free()
+                d_q.free()
+        wk.close()
+        ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--probed", action="store_true")
     ap.add_argument("--image", default="", choices=("", "bf16"))
     ap.add_argument("--parent-lib")
     ap.add_argument("--rounds", type=int, default=3)
@@ -214,17 +283,17 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--rehearse", action="store_true")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_lp.json" if args.image else "retrieve.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_probed.json" if args.probed else "retrieve_lp.json" if args.image else "retrieve.json")
     if args.leg == "torch":
         return leg_torch(args)
-    if args.image or args.leg == "fp32":
+    if args.probed or args.image or args.leg == "fp32":
         import __graft_entry__ as graft
         fr = graft.load_package()
         if not args.rehearse and fr.device_count() < 1:
             sys.exit("retrieve_bench: no MI355X visible -- a timing needs the GPU")
         if args.rehearse:
             args.rows = 20000
-        return leg_fp32(args, fr) if args.leg == "fp32" else main_image(args, fr)
+        return leg_fp32(args, fr) if args.leg == "fp32" else main_probed(args, fr) if args.probed else main_image(args, fr)
     torch_us, torch_note = {}, None
     if not args.rehearse:
         try:
