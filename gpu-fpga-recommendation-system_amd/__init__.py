@@ -94,6 +94,7 @@ ABI_SYMBOLS = [
     "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
     "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
     "fr_ctx_set_retrieve_lists", "fr_ctx_retrieve_lists", "fr_worker_retrieve_probed_device", "fr_worker_retrieve_probed",
+    "fr_worker_retrieve_probed_image_device", "fr_worker_retrieve_probed_image",
     "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -116,6 +117,7 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_worker_topk_device", "fr_worker_topk", "fr_worker_retrieve_device", "fr_worker_retrieve",
                    "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
                    "fr_ctx_set_retrieve_lists", "fr_ctx_retrieve_lists", "fr_worker_retrieve_probed_device", "fr_worker_retrieve_probed",
+                   "fr_worker_retrieve_probed_image_device", "fr_worker_retrieve_probed_image",
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -211,6 +213,7 @@ def lib():
         "fr_ctx_set_retrieve_image": (i32, [vp, i32, i32]),
         "fr_ctx_set_retrieve_lists": (i32, [vp, i32, i32, vp]), "fr_ctx_retrieve_lists": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64)]),
         "fr_worker_retrieve_probed_device": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_retrieve_probed": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
+        "fr_worker_retrieve_probed_image_device": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_retrieve_probed_image": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
         "fr_worker_retrieve_image_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve_image": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
         "fr_ctx_set_request_columns": (i32, [vp, pi, i32, i32]), "fr_ctx_request_words": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
@@ -1338,14 +1341,24 @@ class Worker:
         _check(lib().fr_worker_retrieve_probed_device(self._h, int(table), int(n_q), self._ptr(d_queries), int(n_probe), self._ptr(d_probe), int(k),
                                                       self._ptr(d_top_rows), self._ptr(d_top_scores)))
 
-    def retrieve_probed(self, table, queries, probe, k):
+    def retrieve_probed(self, table, queries, probe, k, _entry="fr_worker_retrieve_probed"):
         """fr_worker_retrieve_probed, then sync(): queries float32 [n_q][dim], probe int32 [n_q][n_probe] -> (rows int32 [n_q][k], scores float32 [n_q][k])."""
         q, p = np.ascontiguousarray(queries, dtype=np.float32), np.ascontiguousarray(probe, dtype=np.int32)
         out_r, out_s = np.empty((q.shape[0], int(k)), np.int32), np.empty((q.shape[0], int(k)), np.float32)
-        _check(lib().fr_worker_retrieve_probed(self._h, int(table), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), p.shape[1], p.ctypes.data_as(ctypes.c_void_p), int(k),
-                                               out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
+        _check(getattr(lib(), _entry)(self._h, int(table), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), p.shape[1], p.ctypes.data_as(ctypes.c_void_p), int(k),
+                                      out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
         self.sync()
         return out_r, out_s
+
+    # the probed retrieval over the table's bf16 image (a partition AND an image; fr_worker_retrieve_probed_image_device / fr_worker_retrieve_probed_image) ----
+    def retrieve_probed_image_device(self, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores=None):
+        """fr_worker_retrieve_probed_image_device: retrieve_probed_device's candidates with retrieve_image_device's scores (bf16 operands, fp32 sums)."""
+        _check(lib().fr_worker_retrieve_probed_image_device(self._h, int(table), int(n_q), self._ptr(d_queries), int(n_probe), self._ptr(d_probe), int(k),
+                                                            self._ptr(d_top_rows), self._ptr(d_top_scores)))
+
+    def retrieve_probed_image(self, table, queries, probe, k):
+        """fr_worker_retrieve_probed_image, then sync(): the arguments and results of retrieve_probed()."""
+        return self.retrieve_probed(table, queries, probe, k, _entry="fr_worker_retrieve_probed_image")
 
     def infer_topk(self, idx, k, seg_offsets=None, dense=None):
         """infer() with the ranking on the device: idx int32 [B][idx_cols] (+ dense) -> (positions int32 [n_seg][k], scores float32 [n_seg][k]) of the

@@ -3097,6 +3097,8 @@ extern "C" int fr_ctx_set_retrieve_image(fr_ctx *ctx, int table, int kind) {
 // ---- probed (IVF) retrieval (fleetrec_serving.h) ---------------------------------------------------------------------------------------------
 // The kernels are the tenth companion's (fr_retrieve_probe.hip -> libfleetrec_retrieve_probe.so); the split rule is fr_retrieve_probe_split
 // (fr_internal.h), the merge is the ranking companion's and the row mapping fr_retrieve_launch's step 1, the CPU twin is frc_retrieve_probed.
+// The image form (fr_worker_retrieve_probed_image*) is the same path with the eleventh companion's scan (fr_retrieve_probe_lp.hip ->
+// libfleetrec_retrieve_probe_lp.so) and frc_retrieve_probed_image.
 extern "C" int fr_ctx_set_retrieve_lists(fr_ctx *ctx, int table, int n_lists, const int64_t *h_offsets) {
     if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
     if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
@@ -3149,8 +3151,8 @@ extern "C" int fr_ctx_retrieve_lists(const fr_ctx *ctx, int table, int *n_lists,
 }
 
 // retrieve_check's refusals (a probed call has no window: one row stands in for it), then the probed call's own
-static int retrieve_probed_check(fr_worker *w, int table, int n_q, const void *queries, int n_probe, const void *probe, int k, const void *top_rows) {
-    FR_TRY(retrieve_check(w, table, 0, 1, n_q, queries, k, top_rows, false));
+static int retrieve_probed_check(fr_worker *w, int table, int n_q, const void *queries, int n_probe, const void *probe, int k, const void *top_rows, bool image) {
+    FR_TRY(retrieve_check(w, table, 0, 1, n_q, queries, k, top_rows, image));
     if (!probe) FR_FAIL(FR_ERR_INVALID, "probe is NULL");
     if (n_probe < 1 || n_probe > FR_RETRIEVE_MAX_PROBE) FR_FAIL(FR_ERR_INVALID, "n_probe = %d outside [1, %d]", n_probe, FR_RETRIEVE_MAX_PROBE);
     if (!w->ctx->rt_lists[table].n_lists) FR_FAIL(FR_ERR_STATE, "table %d has no list partition: call fr_ctx_set_retrieve_lists first", table);
@@ -3160,9 +3162,9 @@ static int retrieve_probed_check(fr_worker *w, int table, int n_q, const void *q
 }
 
 // The launches of one probed retrieval on the worker's stream (the rule of retrieve_enqueue).  h_queries != NULL: the host form -- the pinned staging
-// holds the queries and, behind them, the probe rows; both are copied into the scratch first.
+// holds the queries and, behind them, the probe rows; both are copied into the scratch first.  image: the scan reads the table's retrieval image.
 static int retrieve_probed_enqueue(fr_worker *w, int table, int n_q, const float *d_queries, const float *h_queries, int n_probe, const int32_t *d_probe, int k,
-                                   int32_t *d_top_rows, float *d_top_scores) {
+                                   int32_t *d_top_rows, float *d_top_scores, bool image) {
     fr_ctx *c = w->ctx;
     FR_TRY(fr_host_fed_queued(w, "retrieve"));
     if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
@@ -3226,7 +3228,14 @@ static int retrieve_probed_enqueue(fr_worker *w, int table, int n_q, const float
     if (!e) e = fr_retrieve_probe_scatter_launch(&a, s);
     if (e) FR_FAIL(FR_ERR_HIP, "a grouping launch of the probed retrieval failed: %s", hipGetErrorString((hipError_t)e));
     w->probe_cnt_clean = true;
-    e = fr_retrieve_probe_scan_launch(&a, s);
+    if (image) {
+        FrRetrieveProbeLpArgs lp{};
+        lp.p = a, lp.p.table = nullptr;
+        lp.image = reinterpret_cast<const uint4 *>(c->rt_img[table].img.p), lp.tiles = fr_retrieve_image_tiles(c->tables[table].rows);
+        e = fr_retrieve_probe_lp_scan_launch(&lp, s);
+    } else {
+        e = fr_retrieve_probe_scan_launch(&a, s);
+    }
     if (e) FR_FAIL(FR_ERR_HIP, "the probed retrieval's scan launch failed: %s", hipGetErrorString((hipError_t)e));
     // a query's stretch of the planes is one segment of the ranking; its positions index the planes as n_probe * split chunks of k
     FR_TRY(topk_enqueue(w, (int)n_part, a.part_scores, n_q, a.seg_off, k, top_pos, nullptr));
@@ -3238,28 +3247,31 @@ static int retrieve_probed_enqueue(fr_worker *w, int table, int n_q, const float
     return FR_OK;
 }
 
-static void retrieve_probed_cpu(fr_worker *w, int table, int n_q, const float *queries, int n_probe, const int32_t *probe, int k, int32_t *top_rows, float *top_scores) {
+static void retrieve_probed_cpu(fr_worker *w, int table, int n_q, const float *queries, int n_probe, const int32_t *probe, int k, int32_t *top_rows, float *top_scores, bool image) {
     const fr_ctx *c = w->ctx;
     const fr_ctx::RetrieveLists &rl = c->rt_lists[table];   // an id >= n_lists waits in c_err for fr_worker_sync
-    if (frc_retrieve_probed(retrieve_cpu_table(c, table), c->tables[table].dim, rl.off, rl.n_lists, n_q, queries, n_probe, probe, k, top_rows, top_scores))
-        __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
+    const int dim = c->tables[table].dim;
+    const int bad = image ? frc_retrieve_probed_image(c->rt_img[table].img, dim, rl.off, rl.n_lists, n_q, queries, n_probe, probe, k, top_rows, top_scores)
+                          : frc_retrieve_probed(retrieve_cpu_table(c, table), dim, rl.off, rl.n_lists, n_q, queries, n_probe, probe, k, top_rows, top_scores);
+    if (bad) __atomic_store_n(&w->c_err, 1, __ATOMIC_RELEASE);
 }
 
-extern "C" int fr_worker_retrieve_probed_device(fr_worker *w, int table, int n_q, const float *d_queries, int n_probe, const int32_t *d_probe, int k, int32_t *d_top_rows,
-                                                float *d_top_scores) {
-    FR_TRY(retrieve_probed_check(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows));
+// the device form and the host form of both probed retrievals: over the fp32 table and (image) over the table's retrieval image
+static int retrieve_probed_device(fr_worker *w, int table, int n_q, const float *d_queries, int n_probe, const int32_t *d_probe, int k, int32_t *d_top_rows,
+                                  float *d_top_scores, bool image) {
+    FR_TRY(retrieve_probed_check(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, image));
     if (w->ctx->cpu) {   // computed before the call returns
-        retrieve_probed_cpu(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores);
+        retrieve_probed_cpu(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores, image);
         return FR_OK;
     }
-    return retrieve_probed_enqueue(w, table, n_q, d_queries, nullptr, n_probe, d_probe, k, d_top_rows, d_top_scores);
+    return retrieve_probed_enqueue(w, table, n_q, d_queries, nullptr, n_probe, d_probe, k, d_top_rows, d_top_scores, image);
 }
 
-extern "C" int fr_worker_retrieve_probed(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
-                                         float *h_top_scores) {
-    FR_TRY(retrieve_probed_check(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows));
+static int retrieve_probed_host(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
+                                float *h_top_scores, bool image) {
+    FR_TRY(retrieve_probed_check(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows, image));
     if (w->ctx->cpu) {
-        retrieve_probed_cpu(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows, h_top_scores);
+        retrieve_probed_cpu(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows, h_top_scores, image);
         return FR_OK;
     }
     if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking or retrieval is already in flight on this worker: call fr_worker_sync first");
@@ -3275,10 +3287,27 @@ extern "C" int fr_worker_retrieve_probed(fr_worker *w, int table, int n_q, const
     }
     memcpy(w->h_rt_q, h_queries, n_query * sizeof(float));
     memcpy(w->h_rt_q + n_query, h_probe, n_ids * sizeof(int32_t));
-    const int rc = retrieve_probed_enqueue(w, table, n_q, nullptr, w->h_rt_q, n_probe, nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr);
+    const int rc = retrieve_probed_enqueue(w, table, n_q, nullptr, w->h_rt_q, n_probe, nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr, image);
     if (rc) return rc;
     w->tk_dst_idx = h_top_rows, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
     return FR_OK;
+}
+
+extern "C" int fr_worker_retrieve_probed_device(fr_worker *w, int table, int n_q, const float *d_queries, int n_probe, const int32_t *d_probe, int k, int32_t *d_top_rows,
+                                                float *d_top_scores) {
+    return retrieve_probed_device(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores, false);
+}
+extern "C" int fr_worker_retrieve_probed(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
+                                         float *h_top_scores) {
+    return retrieve_probed_host(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows, h_top_scores, false);
+}
+extern "C" int fr_worker_retrieve_probed_image_device(fr_worker *w, int table, int n_q, const float *d_queries, int n_probe, const int32_t *d_probe, int k,
+                                                      int32_t *d_top_rows, float *d_top_scores) {
+    return retrieve_probed_device(w, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores, true);
+}
+extern "C" int fr_worker_retrieve_probed_image(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
+                                               float *h_top_scores) {
+    return retrieve_probed_host(w, table, n_q, h_queries, n_probe, h_probe, k, h_top_rows, h_top_scores, true);
 }
 
 // ---- request-form batches (fleetrec_serving.h) -------------------------------------------------------------------------------------------------

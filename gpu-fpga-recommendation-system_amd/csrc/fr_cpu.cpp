@@ -310,8 +310,8 @@ void frc_retrieve(const float *table, int dim, int64_t row0, int64_t n_rows, int
 // Probed retrieval: per query the valid ids of its probe row, sorted and taken once -- the union in row order --, then frc_retrieve's score and
 // composite over those rows, the low word by ABSOLUTE row.  No read outside probe[n_q][n_probe], offsets[l], offsets[l + 1] of a valid l and the rows
 // those name.
-int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
-                        int32_t *top_rows, float *top_scores) {
+template <class Score>   // score(query, absolute row) -> fp32
+static int retrieve_probed_ranked(const int64_t *offsets, int n_lists, int n_q, int n_probe, const int32_t *probe, int k, int32_t *top_rows, float *top_scores, Score score) {
     const int units = n_q < Pool::get().size() ? n_q : Pool::get().size();
     std::atomic<int> bad{0};
     Pool::get().run(units, [&](int u) {
@@ -328,12 +328,9 @@ int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int
             std::sort(lists.begin(), lists.end());
             lists.erase(std::unique(lists.begin(), lists.end()), lists.end());
             comp.clear();
-            const float *qv = queries + (size_t)q * (size_t)dim;
             for (const int32_t l : lists)
                 for (int64_t row = offsets[l]; row < offsets[l + 1]; row++) {
-                    const float *t = table + (size_t)row * (size_t)dim;
-                    float acc = -0.0f;
-                    for (int c = 0; c < dim; c++) acc += qv[c] * t[c];
+                    const float acc = score(q, row);
                     uint32_t bits;
                     memcpy(&bits, &acc, 4);
                     comp.push_back(((uint64_t)fr_rank_key(bits) << 32) | (uint64_t)(0xffffffffu - (uint32_t)row));
@@ -350,6 +347,16 @@ int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int
         }
     });
     return bad.load(std::memory_order_relaxed);
+}
+
+int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
+                        int32_t *top_rows, float *top_scores) {
+    return retrieve_probed_ranked(offsets, n_lists, n_q, n_probe, probe, k, top_rows, top_scores, [&](int q, int64_t row) {
+        const float *qv = queries + (size_t)q * (size_t)dim, *t = table + (size_t)row * (size_t)dim;
+        float acc = -0.0f;
+        for (int c = 0; c < dim; c++) acc += qv[c] * t[c];
+        return acc;
+    });
 }
 
 // The retrieval image of the CPU back-end: the bf16 values of the device image (fr_bf16_rne), row-major.  No read outside the listed / ranged rows.
@@ -376,20 +383,32 @@ void frc_retrieve_image_rows(const float *table, int dim, int64_t rows, int64_t 
 }
 
 // s = -0 + bf16(q[0]) img[0] + bf16(q[1]) img[1] + ... : a product of two bf16 values has 16 significant bits and is exact in fp32; ascending c
-void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores) {
+static std::vector<float> image_queries(int n_q, int dim, const float *queries) {
     std::vector<float> qr((size_t)n_q * (size_t)dim);
     for (size_t i = 0; i < qr.size(); i++) {
         uint32_t bits;
         memcpy(&bits, queries + i, 4);
         qr[i] = bf16_value(fr_bf16_rne(bits));
     }
-    retrieve_ranked(row0, n_rows, n_q, k, top_rows, top_scores, [&](int q, int64_t i) {
-        const float *qv = qr.data() + (size_t)q * (size_t)dim;
-        const uint16_t *t = img + (size_t)(row0 + i) * (size_t)dim;
-        float acc = -0.0f;
-        for (int c = 0; c < dim; c++) acc += qv[c] * bf16_value(t[c]);
-        return acc;
-    });
+    return qr;
+}
+static inline float image_score(const float *qv, const uint16_t *t, int dim) {
+    float acc = -0.0f;
+    for (int c = 0; c < dim; c++) acc += qv[c] * bf16_value(t[c]);
+    return acc;
+}
+void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores) {
+    const std::vector<float> qr = image_queries(n_q, dim, queries);
+    retrieve_ranked(row0, n_rows, n_q, k, top_rows, top_scores,
+                    [&](int q, int64_t i) { return image_score(qr.data() + (size_t)q * (size_t)dim, img + (size_t)(row0 + i) * (size_t)dim, dim); });
+}
+
+// the probed walk over the image: frc_retrieve_probed's candidates, the score above.  No read outside the rows the valid ids name.
+int frc_retrieve_probed_image(const uint16_t *img, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
+                              int32_t *top_rows, float *top_scores) {
+    const std::vector<float> qr = image_queries(n_q, dim, queries);
+    return retrieve_probed_ranked(offsets, n_lists, n_q, n_probe, probe, k, top_rows, top_scores,
+                                  [&](int q, int64_t row) { return image_score(qr.data() + (size_t)q * (size_t)dim, img + (size_t)row * (size_t)dim, dim); });
 }
 
 int frc_fill_weights(float *w, size_t count, int mode, uint32_t seed, uint32_t layer, float scale) {

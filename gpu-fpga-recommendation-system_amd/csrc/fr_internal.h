@@ -416,6 +416,18 @@ extern "C" int fr_retrieve_probe_group_launch(const FrRetrieveProbeArgs *args, v
 extern "C" int fr_retrieve_probe_scatter_launch(const FrRetrieveProbeArgs *args, void *stream);
 extern "C" int fr_retrieve_probe_scan_launch(const FrRetrieveProbeArgs *args, void *stream);
 
+// ---- probed bf16 retrieval over the table image (fr_retrieve_probe_lp.hip -> libfleetrec_retrieve_probe_lp.so, the eleventh companion) ----
+// The probed scan with the image scan's B operand and scores.  p as the probed scan takes it (p.table is not read): the grouping launchers above run
+// unchanged in front of it, parts stay cut in rows from the list's first row, and the planes keep their layout.  A part [c_begin, c_end) reads the image
+// tiles c_begin / 32 .. (c_end - 1) / 32 and masks the rows outside the part.
+struct FrRetrieveProbeLpArgs {
+    FrRetrieveProbeArgs p;
+    const uint4 *image;
+    int64_t tiles;           // tiles the image holds: a tile past the last is never read
+};
+// One launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_retrieve_probe_lp_scan_launch(const FrRetrieveProbeLpArgs *args, void *stream);
+
 // ---- request-form batches (fr_request.hip -> libfleetrec_request.so, the second companion code object; fr_cpu.cpp has the twin) ----------------
 // Row i of `out` ([batch][W] 32-bit words) is put together word by word: desc[w] >= 0 names word desc[w] of candidate row i ([batch][Rc]),
 // desc[w] < 0 names word ~desc[w] of the request row ([n_req][Rs]) of the request that owns item i -- the last r with off[r] <= i, clamped into
@@ -906,6 +918,7 @@ struct fr_worker {
     // Probed retrieval (fr_worker_retrieve_probed_device / fr_worker_retrieve_probed): everything but the per-list pair counters lives in d_retrieve (the
     // host form's probe rows ride behind its queries in h_rt_q).  d_probe_cnt [lists] is all 0 between two calls: a clear launch follows its allocation
     // and a call that failed between its sort and its scatter (probe_cnt_clean == false); the scatter itself counts every list back down to 0.
+    // The image form (fr_worker_retrieve_probed_image*) runs the same path with the same scratch and counters; rt_probed covers both.
     FrBuf<int> d_probe_cnt;
     bool probe_cnt_clean = false;
     bool rt_probed = false;     // a probed retrieval was enqueued since the last fr_worker_sync: its table's partition is not replaced meanwhile
@@ -956,6 +969,9 @@ int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int
 // (an id outside [0, rows) does nothing); and the twin of the image scan: frc_retrieve with s = -0 + bf16(q[0]) img[0] + ... , each product exact in fp32
 void frc_retrieve_image_rows(const float *table, int dim, int64_t rows, int64_t n, const int32_t *ids, uint16_t *img);
 void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores);
+// the CPU twin of the probed image retrieval: frc_retrieve_probed's candidates and order, frc_retrieve_image's score over the row-major image
+int frc_retrieve_probed_image(const uint16_t *img, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
+                              int32_t *top_rows, float *top_scores);
 // the CPU twin of fr_request_launch: the same words, items over the pool's threads; -> 1 when the offsets were malformed, else 0
 int frc_expand_requests(const FrRequestArgs &a);
 // the CPU twin of the factored chain (fleetrec_serving.h states the arithmetic): both gathers, U, V + U[owner], FC1's epilogue, then the chain's own

@@ -380,6 +380,27 @@ int fr_worker_retrieve_probed_device(fr_worker *w, int table, int n_q, const flo
 int fr_worker_retrieve_probed(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
                               float *h_top_scores /* or NULL */);
 
+/* Probed bf16 retrieval over the table image (additive in ABI 6): the two forms above composed -- fewer rows AND the bf16 operand.  For a table that has
+ * both a list partition (fr_ctx_set_retrieve_lists) and a current retrieval image (fr_ctx_set_retrieve_image).  With an image on the centroid table too,
+ * coarse and fine retrieval both run on the bf16 matrix instruction on one stream:
+ *   retrieve_image_device(centroid table, 0, n_lists, n_q, Q, n_probe, d_probe, NULL) -> retrieve_probed_image_device(item table, n_q, Q, n_probe, d_probe, k, ...)
+ * Candidates: those of fr_worker_retrieve_probed_device -- the de-duplicated union of the lists the probe row names; an id < 0 means none; an id >=
+ *   n_lists is scanned as no list and reported as FR_ERR_INDEX_RANGE by fr_worker_sync.
+ * Score: that of fr_worker_retrieve_image_device, s = -0 + sum of bf16(q) * bf16(t) accumulated in fp32 in the image scan's step order: the same bits
+ *   the image call gives that (query, row) on the same back-end, the sign of a zero score included.  Rank order, ties (lower absolute row first), NaN
+ *   delivery (a real NaN row before the padding), padding (-1 / -inf) and determinism are fr_worker_retrieve_probed_device's.
+ * Stream order, scratch, the host form's staging and fr_worker_last_kernel: as fr_worker_retrieve_probed_device / fr_worker_retrieve_probed.  A row
+ *   update in front of the call on the same worker is seen: fr_worker_update_rows patches a current image behind its scatter on the same stream.  While
+ *   the call is enqueued and not yet synchronised fr_ctx_set_retrieve_lists refuses to replace the partition, as for the fp32 probed call.
+ * Refusals: the union of the probed call's and the image call's -- FR_ERR_STATE: no list partition; no image, or a stale one after fr_ctx_upload_table /
+ *   fr_ctx_fill_tables; FR_ERR_INVALID: n_probe outside 1 .. FR_RETRIEVE_MAX_PROBE, k outside 1 .. FR_RETRIEVE_MAX_K, n_q * n_probe * k above 2^24, NULL
+ *   arguments, a table outside the model.  A refused call enqueues and writes nothing. */
+int fr_worker_retrieve_probed_image_device(fr_worker *w, int table, int n_q, const float *d_queries /* [n_q][dim] */, int n_probe,
+                                           const int32_t *d_probe /* [n_q][n_probe] list ids */, int k, int32_t *d_top_rows /* [n_q][k] */,
+                                           float *d_top_scores /* [n_q][k] or NULL */);
+int fr_worker_retrieve_probed_image(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
+                                    float *h_top_scores /* or NULL */);
+
 /* Request-form batches (additive in ABI 6): the input side of the segments above.  A request is one user and N candidate items; without this its
  * batch arrives as N complete index rows, the user's columns (and dense features) repeated N times.  With a SPLIT set on the context a batch arrives
  * as request rows + candidate rows + segment offsets, and one small launch expands them on the device into the rows every existing lookup path takes.

@@ -30,6 +30,13 @@ centroids a second hash-filled table (recall is not the library's claim and is n
 (fr_worker_retrieve_probed_device over its output), sum_us (both, back to back, as the composition runs them) and brute_us (fr_worker_retrieve_device over
 the whole table: the baseline).  covered_bytes = the bytes of the distinct lists the call's queries probed; covered_hbm_share = those bytes at 8 TB/s over
 probed_us; rows_fraction = covered_bytes over the table's.  --parent-lib adds the same parent_check as above.
+
+--probed --image bf16 -> profiles/retrieve_probed_lp.json: the probed retrieval over the table image, the same cells.  Both tables get an image.  The fp32
+probed call (probed_fp32_us) and fr_worker_retrieve_probed_image_device (probed_image_us) of the same build alternate window by window in one process,
+over the same probe rows (the fp32 coarse call's); speedup = probed_fp32_us / probed_image_us.  Beside them the coarse leg in both forms (coarse_fp32_us,
+coarse_image_us), both compositions (sum_fp32_us, sum_image_us) and the brute-force image call (brute_image_us).  covered_image_bytes = the image bytes
+of the distinct probed lists (rows x ceil(dim / 16) x 32); covered_hbm_share = those bytes at 8 TB/s over probed_image_us.  --parent-lib: the
+parent_check then also times fr_worker_retrieve_probed_device and fr_worker_retrieve_image_device (calls whose kernels did not change) on both builds.
 """
 import argparse
 import json
@@ -123,14 +130,35 @@ def leg_fp32(args, fr):
     print(json.dumps(out), flush=True)
 
 
-def parent_check(args):
+def leg_unchanged(args, fr):
+    """one process: the probed fp32 call and the image call, whose kernels the probed image call left alone, at 4096 lists, n_probe 32, k 16 -> {key: us}"""
+    rng, out, n_lists, n_probe, k = np.random.default_rng(91), {}, 4096, 32, 16
+    for dim in (32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": args.rows}, {"dim": dim, "rows": 4096}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=-1 if args.rehearse else 0)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        ctx.set_retrieve_image(0)
+        ctx.set_retrieve_lists(0, np.arange(n_lists + 1, dtype=np.int64) * args.rows // n_lists)
+        wk = fr.Worker(ctx, 16)
+        for n_q in (1, 32, 256):
+            d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+            d_p, d_r, d_s = fr.DeviceBuffer(ctx, n_q * n_probe * 4), fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+            wk.retrieve_device(1, 0, n_lists, n_q, d_q, n_probe, d_p, None)
+            out["probed,%d,%d" % (dim, n_q)] = round(timed(wk, lambda: wk.retrieve_probed_device(0, n_q, d_q, n_probe, d_p, k, d_r, d_s), args.calls, args.repeats)[0], 2)
+            out["image,%d,%d" % (dim, n_q)] = round(timed(wk, lambda: wk.retrieve_image_device(0, 0, args.rows, n_q, d_q, k, d_r, d_s), args.calls, args.repeats)[0], 2)
+        wk.close()
+        ctx.close()
+    print(json.dumps(out), flush=True)
+
+
+def parent_check(args, leg="fp32"):
     runs = {"parent": [], "this": []}
     for _ in range(args.rounds):
         for setting in ("parent", "this"):
             env = dict(os.environ)
             if setting == "parent":
                 env["FR_LIB"] = os.path.abspath(args.parent_lib)
-            cmd = [sys.executable, os.path.abspath(__file__), "--leg", "fp32", "--rows", str(args.rows), "--calls", str(args.calls), "--repeats", str(args.repeats)]
+            cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--rows", str(args.rows), "--calls", str(args.calls), "--repeats", str(args.repeats)]
             p = subprocess.run(cmd + (["--rehearse"] if args.rehearse else []), capture_output=True, text=True, timeout=240, env=env)
             if p.returncode != 0:
                 sys.exit("retrieve_bench: the %s leg ended with status %d; nothing more is started\n%s" % (setting, p.returncode, p.stderr[-400:]))
@@ -270,6 +298,68 @@ def main_probed(args, fr):
     print("wrote", args.out)
 
 
+def main_probed_image(args, fr):
+    device, rows = (-1, 20000) if args.rehearse else (0, args.rows)
+    res = {"tool": "tools/retrieve_bench.py --probed --image bf16", "rows": rows, "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse), "calls": args.calls,
+           "repeats": args.repeats, "peaks": {"hbm_bytes_per_s": HBM_BYTES_PER_S}, "cases": []}
+    if args.parent_lib:
+        res["parent_check"] = parent_check(args, "unchanged")
+    rng = np.random.default_rng(91)
+    for dim in (32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": rows}, {"dim": dim, "rows": 4096}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=device)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        ctx.set_retrieve_image(0)
+        ctx.set_retrieve_image(1)
+        wk = fr.Worker(ctx, 16)
+        row_bytes = 32 * ((dim + 15) // 16)   # of one row in the image
+        for n_lists in (1024, 4096):
+            wk.sync()
+            off = np.arange(n_lists + 1, dtype=np.int64) * rows // n_lists
+            ctx.set_retrieve_lists(0, off)
+            for n_q in (1, 32, 256):
+                d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+                for n_probe, k in ((8, 16), (32, 16), (32, 256)):
+                    d_p, d_pi = fr.DeviceBuffer(ctx, n_q * n_probe * 4), fr.DeviceBuffer(ctx, n_q * n_probe * 4)   # d_pi: what the image coarse leg writes, not probed
+                    d_r, d_s = fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+                    calls = {"coarse_fp32": lambda: wk.retrieve_device(1, 0, n_lists, n_q, d_q, n_probe, d_pi, None),
+                             "coarse_image": lambda: wk.retrieve_image_device(1, 0, n_lists, n_q, d_q, n_probe, d_pi, None),
+                             "probed_fp32": lambda: wk.retrieve_probed_device(0, n_q, d_q, n_probe, d_p, k, d_r, d_s),
+                             "probed_image": lambda: wk.retrieve_probed_image_device(0, n_q, d_q, n_probe, d_p, k, d_r, d_s),
+                             "brute_image": lambda: wk.retrieve_image_device(0, 0, rows, n_q, d_q, k, d_r, d_s)}
+                    calls["sum_fp32"] = lambda: (calls["coarse_fp32"](), calls["probed_fp32"]())
+                    calls["sum_image"] = lambda: (calls["coarse_image"](), calls["probed_image"]())
+                    wk.retrieve_device(1, 0, n_lists, n_q, d_q, n_probe, d_p, None)   # the probe rows both probed legs scan
+                    for c in calls.values():
+                        c()
+                    wk.sync()
+                    ids = d_p.download(np.int32, n_q * n_probe)
+                    us = {name: [] for name in calls}
+                    for _ in range(args.repeats):   # alternating windows
+                        for name, c in calls.items():
+                            us[name].append(timed(wk, c, args.calls, 1)[0])
+                    med = {name: float(np.median(v)) for name, v in us.items()}
+                    covered = int(np.diff(off)[np.unique(ids)].sum() * row_bytes)
+                    case = {"dim": dim, "n_lists": n_lists, "n_q": n_q, "n_probe": n_probe, "k": k}
+                    case.update({name + "_us": round(v, 2) for name, v in med.items()})
+                    case.update({"speedup": round(med["probed_fp32"] / med["probed_image"], 3), "sum_speedup": round(med["sum_fp32"] / med["sum_image"], 3),
+                                 "brute_image_over_sum_image": round(med["brute_image"] / med["sum_image"], 3), "covered_image_bytes": covered,
+                                 "covered_hbm_share": round(covered / HBM_BYTES_PER_S / (med["probed_image"] * 1e-6), 4),
+                                 "windows_us": {name: [round(u, 2) for u in v] for name, v in us.items()}})
+                    res["cases"].append(case)
+                    print(json.dumps({key: v for key, v in case.items() if key != "windows_us"}), flush=True)
+                    for b in (d_p, d_pi, d_r, d_s):
+                        b.free()
+                d_q.free()
+        wk.close()
+        ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--probed", action="store_true")
@@ -283,17 +373,20 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--rehearse", action="store_true")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_probed.json" if args.probed else "retrieve_lp.json" if args.image else "retrieve.json")
+    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_probed_lp.json" if args.probed and args.image else
+                                        "retrieve_probed.json" if args.probed else "retrieve_lp.json" if args.image else "retrieve.json")
     if args.leg == "torch":
         return leg_torch(args)
-    if args.probed or args.image or args.leg == "fp32":
+    if args.probed or args.image or args.leg in ("fp32", "unchanged"):
         import __graft_entry__ as graft
         fr = graft.load_package()
         if not args.rehearse and fr.device_count() < 1:
             sys.exit("retrieve_bench: no MI355X visible -- a timing needs the GPU")
         if args.rehearse:
             args.rows = 20000
-        return leg_fp32(args, fr) if args.leg == "fp32" else main_probed(args, fr) if args.probed else main_image(args, fr)
+        if args.leg:
+            return leg_fp32(args, fr) if args.leg == "fp32" else leg_unchanged(args, fr)
+        return main_probed_image(args, fr) if args.probed and args.image else main_probed(args, fr) if args.probed else main_image(args, fr)
     torch_us, torch_note = {}, None
     if not args.rehearse:
         try:
