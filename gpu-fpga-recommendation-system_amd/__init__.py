@@ -33,6 +33,8 @@ EXCHANGE_ALLGATHER, EXCHANGE_ALLTOALL = 0, 1   # fr_exchange: how a sharded step
 POOL_MAX_HOTS = 64   # FR_POOL_MAX_HOTS (fleetrec_serving.h): slots per bag of a pooled lookup
 TOPK_MAX_K = 256   # FR_TOPK_MAX_K (fleetrec_serving.h): the largest k of a top-K ranking
 RETRIEVE_IMAGE_NONE, RETRIEVE_IMAGE_BF16 = 0, 1   # FR_RETRIEVE_IMAGE_* (fleetrec_serving.h): the kinds of fr_ctx_set_retrieve_image
+RETRIEVE_FILTER_NONE, RETRIEVE_FILTER_ROWS = 0, 1   # FR_RETRIEVE_FILTER_* (fleetrec_serving.h): the kinds of fr_ctx_set_retrieve_filter
+RETRIEVE_MAX_EXCLUDE = 64                           # FR_RETRIEVE_MAX_EXCLUDE: exclusion entries per query of fr_worker_retrieve_image_filtered*
 REQ_ONE_HOT, REQ_POOLED, REQ_DENSE = 0, 1, 2   # FR_REQ_* (fleetrec_serving.h): the forms of a request-form expansion
 KEYS_ROWS, KEYS_HASHED, KEYS_MAPPED = 0, 1, 2   # FR_KEYS_*: the key space of an index column (Context.set_key_space)
 KEY_EMPTY, KEY_NO_ROW = -1, 0x7fffffff   # FR_KEY_EMPTY: the empty slot of a bag; FR_KEY_NO_ROW: the row of a key without one (out of range for every gather)
@@ -95,6 +97,8 @@ ABI_SYMBOLS = [
     "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
     "fr_ctx_set_retrieve_lists", "fr_ctx_retrieve_lists", "fr_worker_retrieve_probed_device", "fr_worker_retrieve_probed",
     "fr_worker_retrieve_probed_image_device", "fr_worker_retrieve_probed_image",
+    "fr_ctx_set_retrieve_filter", "fr_ctx_retrieve_filter_rows", "fr_worker_retrieve_filter_rows",
+    "fr_worker_retrieve_image_filtered_device", "fr_worker_retrieve_image_filtered",
     "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
     "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
     "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -118,6 +122,8 @@ _ADDED_IN_ABI_6 = ("fr_worker_update_rows", "fr_ctx_update_rows", "fr_ctx_lp_ban
                    "fr_ctx_set_retrieve_image", "fr_worker_retrieve_image_device", "fr_worker_retrieve_image",
                    "fr_ctx_set_retrieve_lists", "fr_ctx_retrieve_lists", "fr_worker_retrieve_probed_device", "fr_worker_retrieve_probed",
                    "fr_worker_retrieve_probed_image_device", "fr_worker_retrieve_probed_image",
+                   "fr_ctx_set_retrieve_filter", "fr_ctx_retrieve_filter_rows", "fr_worker_retrieve_filter_rows",
+                   "fr_worker_retrieve_image_filtered_device", "fr_worker_retrieve_image_filtered",
                    "fr_ctx_set_request_columns", "fr_ctx_request_words", "fr_worker_expand_requests_device", "fr_worker_request_idx_ptr",
                    "fr_worker_request_weights_ptr", "fr_worker_request_dense_ptr", "fr_worker_request_offsets_ptr", "fr_worker_submit_requests",
                    "fr_ctx_set_key_space", "fr_ctx_key_space", "fr_ctx_put_keys", "fr_worker_put_keys", "fr_worker_resolve_keys_device", "fr_worker_key_ptr",
@@ -215,6 +221,10 @@ def lib():
         "fr_worker_retrieve_probed_device": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_retrieve_probed": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
         "fr_worker_retrieve_probed_image_device": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]), "fr_worker_retrieve_probed_image": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
         "fr_worker_retrieve_image_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]), "fr_worker_retrieve_image": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, vp]),
+        "fr_ctx_set_retrieve_filter": (i32, [vp, i32, i32]),
+        "fr_ctx_retrieve_filter_rows": (i32, [vp, i32, i64, vp, i32]), "fr_worker_retrieve_filter_rows": (i32, [vp, i32, i64, vp, i32]),
+        "fr_worker_retrieve_image_filtered_device": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, i32, vp, vp]),
+        "fr_worker_retrieve_image_filtered": (i32, [vp, i32, i64, i64, i32, vp, i32, vp, i32, vp, vp]),
         "fr_ctx_set_request_columns": (i32, [vp, pi, i32, i32]), "fr_ctx_request_words": (i32, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "fr_worker_expand_requests_device": (i32, [vp, i32, i32, vp, vp, vp, i32, vp]),
         "fr_worker_request_idx_ptr": (pi, [vp]), "fr_worker_request_weights_ptr": (pf, [vp]), "fr_worker_request_dense_ptr": (pf, [vp]),
@@ -670,6 +680,16 @@ class Context:
         """fr_ctx_set_retrieve_image: RETRIEVE_IMAGE_BF16 (the default) builds the table's bf16 retrieval image (synchronous, like upload_table),
         RETRIEVE_IMAGE_NONE frees it.  upload_table / fill_tables make an image stale until this is called again; update_rows keeps it current."""
         _check(lib().fr_ctx_set_retrieve_image(self._h, int(table), RETRIEVE_IMAGE_BF16 if kind is None else int(kind)))
+
+    def set_retrieve_filter(self, table, kind=None):
+        """fr_ctx_set_retrieve_filter: RETRIEVE_FILTER_ROWS (the default) gives the table a live-row mask, every row live (synchronous, like
+        upload_table); RETRIEVE_FILTER_NONE frees it.  Nothing but retrieve_filter_rows changes a bit afterwards."""
+        _check(lib().fr_ctx_set_retrieve_filter(self._h, int(table), RETRIEVE_FILTER_ROWS if kind is None else int(kind)))
+
+    def retrieve_filter_rows(self, table, rows, live):
+        """fr_ctx_retrieve_filter_rows: rows int32 [n] (host) become live (True) or dead (False) in the table's mask; synchronous, like update_rows."""
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        _check(lib().fr_ctx_retrieve_filter_rows(self._h, int(table), r.size, r.ctypes.data_as(ctypes.c_void_p) if r.size else None, int(bool(live))))
 
     def set_retrieve_lists(self, table, offsets):
         """fr_ctx_set_retrieve_lists: offsets int64 [n_lists + 1] -- list l is the rows [offsets[l], offsets[l + 1]) of the table (synchronous, like
@@ -1333,6 +1353,31 @@ class Worker:
     def retrieve_image(self, table, queries, k, row0=0, n_rows=None):
         """fr_worker_retrieve_image, then sync(): the arguments and results of retrieve()."""
         return self.retrieve(table, queries, k, row0, n_rows, _entry="fr_worker_retrieve_image")
+
+    # the image retrieval behind the table's live-row mask and per-query exclusions (Context.set_retrieve_filter; fr_worker_retrieve_image_filtered*) ----
+    def retrieve_filter_rows(self, table, n, d_rows, live):
+        """fr_worker_retrieve_filter_rows: the n device rows int32 [n] become live (True) or dead (False) in the table's mask, on the worker's stream
+        behind everything enqueued before -- what admit_keys reports can be passed on without a sync."""
+        _check(lib().fr_worker_retrieve_filter_rows(self._h, int(table), int(n), self._ptr(d_rows), int(bool(live))))
+
+    def retrieve_image_filtered_device(self, table, row0, n_rows, n_q, d_queries, n_excl, d_exclude, k, d_top_rows, d_top_scores=None):
+        """fr_worker_retrieve_image_filtered_device: retrieve_image_device over the rows of the window that are live in the table's mask and that
+        d_exclude int32 [n_q][n_excl] (absolute rows; -1: none; None when n_excl == 0) does not name for the query."""
+        _check(lib().fr_worker_retrieve_image_filtered_device(self._h, int(table), int(row0), int(n_rows), int(n_q), self._ptr(d_queries), int(n_excl),
+                                                              self._ptr(d_exclude), int(k), self._ptr(d_top_rows), self._ptr(d_top_scores)))
+
+    def retrieve_image_filtered(self, table, queries, k, exclude=None, row0=0, n_rows=None):
+        """fr_worker_retrieve_image_filtered, then sync(): queries float32 [n_q][dim], exclude int32 [n_q][n_excl] or None -> retrieve()'s results."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        x = np.zeros((q.shape[0], 0), np.int32) if exclude is None else np.ascontiguousarray(exclude, dtype=np.int32).reshape(q.shape[0], -1)
+        if n_rows is None:
+            n_rows = int(self.ctx.model.desc.tables[table].rows) - int(row0)
+        out_r, out_s = np.empty((q.shape[0], int(k)), np.int32), np.empty((q.shape[0], int(k)), np.float32)
+        _check(lib().fr_worker_retrieve_image_filtered(self._h, int(table), int(row0), int(n_rows), q.shape[0], q.ctypes.data_as(ctypes.c_void_p), x.shape[1],
+                                                       x.ctypes.data_as(ctypes.c_void_p) if x.shape[1] else None, int(k),
+                                                       out_r.ctypes.data_as(ctypes.c_void_p), out_s.ctypes.data_as(ctypes.c_void_p)))
+        self.sync()
+        return out_r, out_s
 
     # probed (IVF) retrieval over the table's list partition (Context.set_retrieve_lists; fr_worker_retrieve_probed_device / fr_worker_retrieve_probed) ----
     def retrieve_probed_device(self, table, n_q, d_queries, n_probe, d_probe, k, d_top_rows, d_top_scores=None):

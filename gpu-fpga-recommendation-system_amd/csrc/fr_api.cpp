@@ -3094,6 +3094,231 @@ extern "C" int fr_ctx_set_retrieve_image(fr_ctx *ctx, int table, int kind) {
     return FR_OK;
 }
 
+// ---- filtered bf16 retrieval (fleetrec_serving.h) --------------------------------------------------------------------------------------------
+// The kernels are the twelfth companion's (fr_retrieve_filter.hip -> libfleetrec_retrieve_filter.so): the mask's build and patch, the image scan with
+// both filters in its selection, and a merge of its own over u64 composites -- neither fr_rank_launch nor retrieve_rows_kernel is on this path.  The
+// chunking is the image call's (fr_retrieve_chunk), the CPU twin is frc_retrieve_image_filtered.  The mask lives in fr_ctx::RetrieveImage, under lp_mutex.
+extern "C" int fr_ctx_set_retrieve_filter(fr_ctx *ctx, int table, int kind) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    if (table < 0 || table >= ctx->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (kind != FR_RETRIEVE_FILTER_NONE && kind != FR_RETRIEVE_FILTER_ROWS) FR_FAIL(FR_ERR_INVALID, "retrieval filter kind %d is neither FR_RETRIEVE_FILTER_NONE nor FR_RETRIEVE_FILTER_ROWS", kind);
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);
+    fr_ctx::RetrieveImage &im = ctx->rt_img[table];
+    if (kind == FR_RETRIEVE_FILTER_NONE) {
+        if (!im.live) return FR_OK;
+        {   // the guard of fr_ctx_set_retrieve_lists, for the work that reads a mask
+            std::lock_guard<std::mutex> g(ctx->workers_mutex);
+            for (const fr_worker *w : ctx->workers)
+                if (w->rt_filtered) FR_FAIL(FR_ERR_STATE, "fr_ctx_set_retrieve_filter: a worker of the context has a filtered retrieval in flight: call fr_worker_sync first");
+        }
+        if (!ctx->cpu) {
+            FR_SET_DEVICE(ctx);
+            FR_HIP(hipDeviceSynchronize());   // a worker's patch may still write it
+        }
+        im.live.reset();
+        return FR_OK;
+    }
+    const fr_table_desc &d = ctx->tables[table];
+    const FrTableMem &tm = ctx->table_mem[table];
+    if (ctx->model.index_mode == FR_INDEX_PER_BANK || tm.il_rows)
+        FR_FAIL(FR_ERR_STATE, "a retrieval filter is made for a dense table; the tables of an FR_INDEX_PER_BANK context are interleaved in bank rows");
+    if (ctx->n_shards > 1 || !tm.resident) FR_FAIL(FR_ERR_STATE, "retrieval is not available on a table-sharded context (shard %d of %d)", ctx->shard_rank, ctx->n_shards);
+    if (d.dim > FR_RETRIEVE_MAX_DIM) FR_FAIL(FR_ERR_STATE, "table %d has dim %d; retrieval holds a query in registers up to dim %d", table, d.dim, FR_RETRIEVE_MAX_DIM);
+    const size_t words = (size_t)fr_retrieve_image_tiles(d.rows);
+    if (!im.live) {   // (a second ROWS call rebuilds in place: a worker's scan may be reading the words)
+        FR_SET_DEVICE(ctx);
+        FR_TRY(im.live.alloc(fr_mem_kind(ctx, FrMem::DEVICE), words, "retrieval filter"));
+    }
+    if (ctx->cpu) {
+        for (size_t i = 0; i < words; i++) {
+            const int64_t left = (int64_t)d.rows - 32 * (int64_t)i;
+            __atomic_store_n(im.live.p + i, left >= 32 ? 0xffffffffu : (1u << (uint32_t)left) - 1u, __ATOMIC_RELAXED);
+        }
+        return FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    FrRetrieveFilterMaskArgs a{};
+    a.mask = im.live.p, a.rows = d.rows;
+    const int e = fr_retrieve_filter_mask_launch(&a, (void *)ctx->setup_stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the retrieval filter's build launch failed: %s", hipGetErrorString((hipError_t)e));
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    return FR_OK;
+}
+
+static int retrieve_filter_rows_check(const fr_ctx *c, int table, int64_t n, const void *rows, int live) {
+    if (table < 0 || table >= c->model.n_tables) FR_FAIL(FR_ERR_INVALID, "table %d out of range", table);
+    if (n < 0 || n > (1ll << 31)) FR_FAIL(FR_ERR_INVALID, "n = %lld rows outside [0, 2^31]", (long long)n);
+    if (n > 0 && !rows) FR_FAIL(FR_ERR_INVALID, "rows is NULL");
+    if (live != 0 && live != 1) FR_FAIL(FR_ERR_INVALID, "live = %d is neither 0 nor 1", live);
+    if (!c->rt_img[table].live) FR_FAIL(FR_ERR_STATE, "table %d has no retrieval filter: call fr_ctx_set_retrieve_filter(ctx, %d, FR_RETRIEVE_FILTER_ROWS) first", table, table);
+    return FR_OK;
+}
+
+// the CPU back-end's patch: atomic bit operations, as the device's (two workers may patch one word)
+static void retrieve_filter_rows_cpu(fr_ctx *c, int table, int64_t n, const int32_t *rows, int live) {
+    uint32_t *mask = c->rt_img[table].live.p;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t row = rows[i];
+        if (row < 0 || row >= (int64_t)c->tables[table].rows) continue;
+        if (live) __atomic_fetch_or(mask + (row >> 5), 1u << (row & 31), __ATOMIC_RELAXED);
+        else __atomic_fetch_and(mask + (row >> 5), ~(1u << (row & 31)), __ATOMIC_RELAXED);
+    }
+}
+
+static int retrieve_filter_rows_enqueue(fr_ctx *c, int table, int64_t n, const int32_t *d_rows, int live, hipStream_t s) {
+    FrRetrieveFilterMaskArgs a{};
+    a.mask = c->rt_img[table].live.p, a.rows = c->tables[table].rows, a.ids = d_rows, a.n = n, a.live = live;
+    const int e = fr_retrieve_filter_mask_launch(&a, (void *)s);
+    if (e) FR_FAIL(FR_ERR_HIP, "the retrieval filter's patch launch failed: %s", hipGetErrorString((hipError_t)e));
+    return FR_OK;
+}
+
+extern "C" int fr_worker_retrieve_filter_rows(fr_worker *w, int table, int64_t n, const int32_t *d_rows, int live) {
+    if (!w) FR_FAIL(FR_ERR_INVALID, "worker is NULL");
+    fr_ctx *c = w->ctx;
+    FR_TRY(retrieve_filter_rows_check(c, table, n, d_rows, live));
+    if (n == 0) return FR_OK;
+    if (c->cpu) {
+        retrieve_filter_rows_cpu(c, table, n, d_rows, live);
+        return FR_OK;
+    }
+    FR_TRY(fr_host_fed_queued(w, "patch a retrieval filter"));
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then patch the filter");
+    FR_SET_DEVICE(c);
+    int rc = fr_fused_flush(w);   // (the rule of fr_worker_update_rows: what was pushed before stays in front)
+    if (!rc) rc = pipeline_flush(w);
+    if (rc) return rc;
+    FR_TRY(retrieve_filter_rows_enqueue(c, table, n, d_rows, live, w->stream));
+    w->in_flight = true;
+    return FR_OK;
+}
+
+extern "C" int fr_ctx_retrieve_filter_rows(fr_ctx *ctx, int table, int64_t n, const int32_t *h_rows, int live) {
+    if (!ctx) FR_FAIL(FR_ERR_INVALID, "ctx is NULL");
+    FR_TRY(retrieve_filter_rows_check(ctx, table, n, h_rows, live));
+    if (n == 0) return FR_OK;
+    if (ctx->cpu) {
+        retrieve_filter_rows_cpu(ctx, table, n, h_rows, live);
+        return FR_OK;
+    }
+    FR_SET_DEVICE(ctx);
+    std::lock_guard<std::mutex> lk(ctx->lp_mutex);   // (the set-up stream and fr_ctx_update_rows's id staging, as there)
+    FR_TRY(ctx->d_up_ids.grow(FrMem::DEVICE, (size_t)n, "row-update ids"));
+    FR_HIP(hipMemcpyAsync(ctx->d_up_ids, h_rows, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->setup_stream));
+    const int rc = retrieve_filter_rows_enqueue(ctx, table, n, ctx->d_up_ids, live, ctx->setup_stream);
+    FR_HIP(hipStreamSynchronize(ctx->setup_stream));
+    return rc;
+}
+
+// the image call's refusals, then the filtered call's own
+static int retrieve_filtered_check(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const void *queries, int n_excl, const void *exclude, int k, const void *top_rows) {
+    FR_TRY(retrieve_check(w, table, row0, n_rows, n_q, queries, k, top_rows, true));
+    if (n_excl < 0 || n_excl > FR_RETRIEVE_MAX_EXCLUDE) FR_FAIL(FR_ERR_INVALID, "n_excl = %d outside [0, %d]", n_excl, FR_RETRIEVE_MAX_EXCLUDE);
+    if (n_excl > 0 && !exclude) FR_FAIL(FR_ERR_INVALID, "exclude is NULL with n_excl = %d", n_excl);
+    if (!w->ctx->rt_img[table].live) FR_FAIL(FR_ERR_STATE, "table %d has no retrieval filter: call fr_ctx_set_retrieve_filter(ctx, %d, FR_RETRIEVE_FILTER_ROWS) first", table, table);
+    return FR_OK;
+}
+
+// The launches of one filtered retrieval on the worker's stream (the rule of retrieve_enqueue, its chunks and its scratch carving: the composite plane
+// takes the bytes of the two 4-byte planes).  h_queries != NULL: the host form -- queries and exclusions are the pinned staging, copied into the scratch.
+static int retrieve_filtered_enqueue(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, const float *h_queries, int n_excl,
+                                     const int32_t *d_exclude, const int32_t *h_exclude, int k, int32_t *d_top_rows, float *d_top_scores) {
+    fr_ctx *c = w->ctx;
+    FR_TRY(fr_host_fed_queued(w, "retrieve"));
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
+    FR_SET_DEVICE(c);
+    const int dim = c->tables[table].dim;
+    FrRetrieveFilterArgs f{};
+    FrRetrieveArgs &a = f.lp.r;
+    a.dim = dim, a.n_q = n_q, a.k = k, a.row0 = row0, a.n_rows = n_rows;
+    const int64_t span = row0 % FR_RETRIEVE_IMAGE_TILE + n_rows;   // (chunks are cut from the tile boundary at or below row0, as for the image call)
+    a.chunk = fr_retrieve_chunk(span, n_q, k, c->n_cu);
+    a.n_chunks = (int)((span + a.chunk - 1) / a.chunk);
+    const int64_t per_q = (int64_t)a.n_chunks * k;                                                         // composites of a query; n_q * per_q <= 2^24
+    const int64_t parts = (per_q + FR_RETRIEVE_FILTER_STRETCH - 1) / FR_RETRIEVE_FILTER_STRETCH;
+    const size_t comp_bytes = align_up((size_t)n_q * (size_t)per_q * 8, 256), fold_bytes = parts > 1 ? align_up((size_t)n_q * (size_t)parts * k * 8, 256) : 0;
+    const size_t q_bytes = h_queries ? align_up((size_t)n_q * dim * 4, 256) : 0, x_bytes = h_exclude && n_excl ? align_up((size_t)n_q * n_excl * 4, 256) : 0;
+    const size_t need = comp_bytes + fold_bytes + q_bytes + x_bytes;
+    if (need > w->d_retrieve.count()) {
+        if (w->d_retrieve) FR_HIP(hipStreamSynchronize(w->stream));   // an earlier retrieval may still use it
+        FR_TRY(w->d_retrieve.grow(FrMem::DEVICE, need, "retrieval scratch"));
+    }
+    char *base = w->d_retrieve.p;
+    f.comp = reinterpret_cast<unsigned long long *>(base);
+    unsigned long long *fold = reinterpret_cast<unsigned long long *>(base + comp_bytes);
+    a.queries = d_queries, f.exclude = d_exclude, f.n_excl = n_excl;
+    int rc = fr_fused_flush(w);
+    if (!rc) rc = pipeline_flush(w);
+    if (rc) return rc;
+    if (h_queries) {
+        float *dq = reinterpret_cast<float *>(base + comp_bytes + fold_bytes);
+        FR_HIP(hipMemcpyAsync(dq, h_queries, (size_t)n_q * dim * 4, hipMemcpyHostToDevice, w->stream));
+        a.queries = dq;
+        if (x_bytes) {
+            int32_t *dx = reinterpret_cast<int32_t *>(base + comp_bytes + fold_bytes + q_bytes);
+            FR_HIP(hipMemcpyAsync(dx, h_exclude, (size_t)n_q * n_excl * 4, hipMemcpyHostToDevice, w->stream));
+            f.exclude = dx;
+        }
+    }
+    f.lp.image = reinterpret_cast<const uint4 *>(c->rt_img[table].img.p), f.lp.tiles = fr_retrieve_image_tiles(c->tables[table].rows);
+    f.mask = c->rt_img[table].live.p;
+    int e = fr_retrieve_filter_scan_launch(&f, (void *)w->stream);
+    if (e) FR_FAIL(FR_ERR_HIP, "the filtered retrieval's scan launch failed: %s", hipGetErrorString((hipError_t)e));
+    w->in_flight = true, w->rt_filtered = true;
+    FrRetrieveMergeArgs m{};
+    m.src = f.comp, m.n = per_q, m.stretch = FR_RETRIEVE_FILTER_STRETCH, m.n_q = n_q, m.k = k, m.final = parts == 1, m.dst = fold;
+    m.row0 = row0, m.top_rows = d_top_rows, m.top_scores = d_top_scores;
+    e = fr_retrieve_filter_merge_launch(&m, (void *)w->stream);
+    if (!e && parts > 1) {   // the parts' leaders of a query, folded by one workgroup
+        m.src = fold, m.n = parts * k, m.stretch = m.n, m.final = 1;
+        e = fr_retrieve_filter_merge_launch(&m, (void *)w->stream);
+    }
+    if (e) FR_FAIL(FR_ERR_HIP, "the filtered retrieval's merge launch failed: %s", hipGetErrorString((hipError_t)e));
+    return FR_OK;
+}
+
+static void retrieve_filtered_cpu(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *queries, int n_excl, const int32_t *exclude, int k, int32_t *top_rows, float *top_scores) {
+    const fr_ctx *c = w->ctx;
+    frc_retrieve_image_filtered(c->rt_img[table].img, c->tables[table].dim, c->rt_img[table].live, row0, n_rows, n_q, queries, n_excl, exclude, k, top_rows, top_scores);
+}
+
+extern "C" int fr_worker_retrieve_image_filtered_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries, int n_excl, const int32_t *d_exclude,
+                                                        int k, int32_t *d_top_rows, float *d_top_scores) {
+    FR_TRY(retrieve_filtered_check(w, table, row0, n_rows, n_q, d_queries, n_excl, d_exclude, k, d_top_rows));
+    if (w->ctx->cpu) {   // computed before the call returns
+        retrieve_filtered_cpu(w, table, row0, n_rows, n_q, d_queries, n_excl, d_exclude, k, d_top_rows, d_top_scores);
+        return FR_OK;
+    }
+    return retrieve_filtered_enqueue(w, table, row0, n_rows, n_q, d_queries, nullptr, n_excl, d_exclude, nullptr, k, d_top_rows, d_top_scores);
+}
+
+extern "C" int fr_worker_retrieve_image_filtered(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int n_excl, const int32_t *h_exclude, int k,
+                                                 int32_t *h_top_rows, float *h_top_scores) {
+    FR_TRY(retrieve_filtered_check(w, table, row0, n_rows, n_q, h_queries, n_excl, h_exclude, k, h_top_rows));
+    if (w->ctx->cpu) {
+        retrieve_filtered_cpu(w, table, row0, n_rows, n_q, h_queries, n_excl, h_exclude, k, h_top_rows, h_top_scores);
+        return FR_OK;
+    }
+    if (w->tk_count) FR_FAIL(FR_ERR_STATE, "a host-form ranking or retrieval is already in flight on this worker: call fr_worker_sync first");
+    FR_TRY(fr_host_fed_queued(w, "retrieve"));   // (before the staging is touched: nothing happens on a refusal)
+    if (w->sh_comm) FR_FAIL(FR_ERR_STATE, "a table-sharded step is in flight on this worker: call fr_worker_sync first, then retrieve");
+    FR_SET_DEVICE(w->ctx);
+    const size_t n_query = (size_t)n_q * (size_t)w->ctx->tables[table].dim, n_out = (size_t)n_q * (size_t)k, n_ex = (size_t)n_q * (size_t)n_excl;
+    if (n_query > w->h_rt_q.count() || n_ex > w->h_rt_ex.count() || n_out > w->h_tk_idx.count() || n_out > w->h_tk_sc.count()) {   // a grow waits for the stream before pinned memory is released
+        FR_HIP(hipStreamSynchronize(w->stream));
+        FR_TRY(w->h_rt_q.grow(FrMem::PINNED, n_query, "retrieval queries"));
+        if (n_ex) FR_TRY(w->h_rt_ex.grow(FrMem::PINNED, n_ex, "retrieval exclusions"));
+        FR_TRY(w->h_tk_idx.grow(FrMem::PINNED, n_out, "ranking results"));
+        FR_TRY(w->h_tk_sc.grow(FrMem::PINNED, n_out, "ranking result scores"));
+    }
+    memcpy(w->h_rt_q, h_queries, n_query * sizeof(float));
+    if (n_ex) memcpy(w->h_rt_ex, h_exclude, n_ex * sizeof(int32_t));
+    // the results come back through the host-form ranking's staging and are delivered by fr_worker_sync as its results are
+    FR_TRY(retrieve_filtered_enqueue(w, table, row0, n_rows, n_q, nullptr, w->h_rt_q, n_excl, nullptr, n_ex ? w->h_rt_ex.p : nullptr, k, w->h_tk_idx, h_top_scores ? w->h_tk_sc.p : nullptr));
+    w->tk_dst_idx = h_top_rows, w->tk_dst_sc = h_top_scores, w->tk_count = n_out;
+    return FR_OK;
+}
+
 // ---- probed (IVF) retrieval (fleetrec_serving.h) ---------------------------------------------------------------------------------------------
 // The kernels are the tenth companion's (fr_retrieve_probe.hip -> libfleetrec_retrieve_probe.so); the split rule is fr_retrieve_probe_split
 // (fr_internal.h), the merge is the ranking companion's and the row mapping fr_retrieve_launch's step 1, the CPU twin is frc_retrieve_probed.
@@ -3762,7 +3987,7 @@ extern "C" int fr_worker_sync(fr_worker *w) {
     // whatever this sync returns, the host-form batch is no longer in flight and an undelivered host-form ranking is dropped
     struct TopkDone {
         fr_worker *w;
-        ~TopkDone() { w->host_batch = 0, w->tk_count = 0, w->rt_probed = false; }
+        ~TopkDone() { w->host_batch = 0, w->tk_count = 0, w->rt_probed = false, w->rt_filtered = false; }
     } topk_done{w};
     if (w->ctx->cpu) {   // everything was computed inside the calls -- but for a table-sharded step, which runs on the worker's host stream
         const int crc = fr_comm_wait(w);   // (bounded wait + the ranks' status words, fr_comm.cpp; FR_OK at once when no such step is in flight)

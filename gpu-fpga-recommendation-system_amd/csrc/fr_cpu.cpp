@@ -403,6 +403,42 @@ void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_ro
                     [&](int q, int64_t i) { return image_score(qr.data() + (size_t)q * (size_t)dim, img + (size_t)(row0 + i) * (size_t)dim, dim); });
 }
 
+// The filtered scan: retrieve_ranked's composites over the SURVIVORS only -- the rows whose bit is set in `live` and that the query's exclusion row does
+// not name --, so the padding begins behind the last survivor.  No read outside the window's rows, live[row0 / 32 .. (row0 + n_rows - 1) / 32] and
+// exclude[n_q][n_excl].
+void frc_retrieve_image_filtered(const uint16_t *img, int dim, const uint32_t *live, int64_t row0, int64_t n_rows, int n_q, const float *queries, int n_excl,
+                                 const int32_t *exclude, int k, int32_t *top_rows, float *top_scores) {
+    const std::vector<float> qr = image_queries(n_q, dim, queries);
+    const int units = n_q < Pool::get().size() ? n_q : Pool::get().size();
+    Pool::get().run(units, [&](int u) {
+        std::vector<uint64_t> comp;
+        std::vector<int32_t> named;
+        const int qa = (int)((int64_t)n_q * u / units), qb = (int)((int64_t)n_q * (u + 1) / units);
+        for (int q = qa; q < qb; q++) {
+            named.assign(exclude ? exclude + (size_t)q * (size_t)n_excl : nullptr, exclude ? exclude + (size_t)(q + 1) * (size_t)n_excl : nullptr);
+            std::sort(named.begin(), named.end());
+            comp.clear();
+            for (int64_t i = 0; i < n_rows; i++) {
+                const int64_t row = row0 + i;
+                if (!(__atomic_load_n(live + (row >> 5), __ATOMIC_RELAXED) >> (row & 31) & 1u) || std::binary_search(named.begin(), named.end(), (int32_t)row)) continue;
+                const float acc = image_score(qr.data() + (size_t)q * (size_t)dim, img + (size_t)row * (size_t)dim, dim);
+                uint32_t bits;
+                memcpy(&bits, &acc, 4);
+                comp.push_back(((uint64_t)fr_rank_key(bits) << 32) | (uint64_t)(0xffffffffu - (uint32_t)i));
+            }
+            const size_t top = comp.size() < (size_t)k ? comp.size() : (size_t)k;
+            std::partial_sort(comp.begin(), comp.begin() + (ptrdiff_t)top, comp.end(), std::greater<uint64_t>());
+            for (size_t j = 0; j < (size_t)k; j++) {
+                const size_t o = (size_t)q * (size_t)k + j;
+                const uint32_t key = j < top ? (uint32_t)(comp[j] >> 32) : 0u;
+                const uint32_t bits = j >= top ? 0xff800000u : (key == 0u ? 0x7fc00000u : ((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key));
+                top_rows[o] = j < top ? (int32_t)(row0 + (int64_t)(0xffffffffu - (uint32_t)comp[j])) : -1;
+                if (top_scores) memcpy(top_scores + o, &bits, 4);
+            }
+        }
+    });
+}
+
 // the probed walk over the image: frc_retrieve_probed's candidates, the score above.  No read outside the rows the valid ids name.
 int frc_retrieve_probed_image(const uint16_t *img, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
                               int32_t *top_rows, float *top_scores) {

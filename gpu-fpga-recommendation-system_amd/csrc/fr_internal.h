@@ -368,6 +368,43 @@ struct FrRetrieveLpArgs {
 extern "C" int fr_retrieve_lp_image_launch(const FrRetrieveImageArgs *args, void *stream);
 extern "C" int fr_retrieve_lp_scan_launch(const FrRetrieveLpArgs *args, void *stream);
 
+// ---- filtered bf16 retrieval (fr_retrieve_filter.hip -> libfleetrec_retrieve_filter.so, the twelfth companion; fr_cpu.cpp has the twin) ----
+// The live-row mask (fr_ctx_set_retrieve_filter): one bit per row, word T = the rows of image tile T, bit n = row 32 T + n, the bits past the table's rows
+// clear.  The filtered scan writes ONE plane of u64 composites, (fr_rank_key(score bits) << 32) | (0xffffffff - (row - row0)), 0 where a list has no row;
+// its own merge takes the k largest of a query's n_chunks * k composites: workgroups over stretches of FR_RETRIEVE_FILTER_STRETCH composites, and, when a
+// query has more than one stretch, a second launch over the stretches' leaders.
+constexpr int64_t FR_RETRIEVE_FILTER_STRETCH = 4096;   // composites one merge workgroup of the first launch streams (1024 per wave)
+struct FrRetrieveFilterMaskArgs {
+    uint32_t *mask;          // ceil(rows / 32) words
+    int64_t rows;            // rows of the table
+    // ids == NULL: the range arm -- every word written whole, every row live.  ids != NULL: the list arm -- the bits of the n listed rows are set (live
+    // != 0) or cleared; an id outside [0, rows) does nothing.
+    const int32_t *ids;
+    int64_t n;
+    int live;
+};
+struct FrRetrieveFilterArgs {
+    FrRetrieveLpArgs lp;             // the image scan's arguments; the two planes, seg_off, top_pos and the outputs of lp.r are not used
+    const uint32_t *mask;            // lp.tiles words
+    const int32_t *exclude;          // [n_q][n_excl] absolute rows (any other value names none), not read when n_excl == 0
+    int n_excl;                      // 0 .. FR_RETRIEVE_MAX_EXCLUDE
+    unsigned long long *comp;        // [n_q][n_chunks][k]
+};
+struct FrRetrieveMergeArgs {
+    const unsigned long long *src;   // [n_q][n]
+    int64_t n, stretch;              // composites per query; per workgroup: the grid is (n_q, ceil(n / stretch))
+    int n_q, k;
+    int final;                       // 0: the leaders of part p of query q -> dst[(q * parts + p) * k ..] as composites; else -> the outputs
+    unsigned long long *dst;
+    int64_t row0;
+    int32_t *top_rows;               // [n_q][k]
+    float *top_scores;               // [n_q][k] or NULL
+};
+// Each enqueues one launch on `stream` (a hipStream_t).  -> 0 or the hipError_t value.
+extern "C" int fr_retrieve_filter_mask_launch(const FrRetrieveFilterMaskArgs *args, void *stream);
+extern "C" int fr_retrieve_filter_scan_launch(const FrRetrieveFilterArgs *args, void *stream);
+extern "C" int fr_retrieve_filter_merge_launch(const FrRetrieveMergeArgs *args, void *stream);
+
 // ---- probed (IVF) retrieval (fr_retrieve_probe.hip -> libfleetrec_retrieve_probe.so, the tenth companion; fr_cpu.cpp has the twin) ----
 // A table's list partition (fr_ctx_set_retrieve_lists): list l is the rows [offsets[l], offsets[l + 1]).  Query q scans the lists probe[q][0 .. n_probe).
 // probe_sort_kernel turns a probe row into SLOTS: its distinct, valid, non-empty lists in ascending order (= ascending rows), -1 behind them.  A live
@@ -654,9 +691,13 @@ struct fr_ctx {
     // Retrieval images (fr_ctx_set_retrieve_image): per table a bf16 copy for fr_worker_retrieve_image*; img is NULL until one is set.  GPU contexts: the
     // fragment-major image in device memory; the CPU back-end: the same rounded values row-major [rows][dim] in host memory.  `stale` is set by every
     // fill / upload and cleared by a build; row updates patch a current image behind their scatter (update_enqueue).  Built and released under lp_mutex.
+    // `live` is the table's live-row mask (fr_ctx_set_retrieve_filter; NULL until one is set): ceil(rows / 32) words, device memory or, on the CPU
+    // back-end, host memory.  It has a life of its own -- no fill, upload, update or image call touches it -- and is dropped only while no worker has a
+    // filtered retrieval in flight (fr_worker::rt_filtered).
     struct RetrieveImage {
         FrBuf<uint16_t> img;
         bool stale = false;
+        FrBuf<uint32_t> live;
     };
     std::vector<RetrieveImage> rt_img;     // [tables]
     // List partitions (fr_ctx_set_retrieve_lists): per table the offsets [n_lists + 1] -- device memory, host memory on the CPU back-end -- and what
@@ -922,6 +963,10 @@ struct fr_worker {
     FrBuf<int> d_probe_cnt;
     bool probe_cnt_clean = false;
     bool rt_probed = false;     // a probed retrieval was enqueued since the last fr_worker_sync: its table's partition is not replaced meanwhile
+    // Filtered retrieval (fr_worker_retrieve_image_filtered*): the composite plane, the merge's part leaders and the host form's queries and exclusions
+    // live in d_retrieve; h_rt_ex is the host form's pinned exclusion staging.
+    FrBuf<int32_t> h_rt_ex;
+    bool rt_filtered = false;   // a filtered retrieval was enqueued since the last fr_worker_sync: its table's mask is not freed meanwhile
     char last_kernel[96] = "";  // fr_worker_last_kernel: the dominant kernel of the most recent launch this worker enqueued
     FrEvent ev_start, ev_stop;
 };
@@ -969,6 +1014,10 @@ int frc_retrieve_probed(const float *table, int dim, const int64_t *offsets, int
 // (an id outside [0, rows) does nothing); and the twin of the image scan: frc_retrieve with s = -0 + bf16(q[0]) img[0] + ... , each product exact in fp32
 void frc_retrieve_image_rows(const float *table, int dim, int64_t rows, int64_t n, const int32_t *ids, uint16_t *img);
 void frc_retrieve_image(const uint16_t *img, int dim, int64_t row0, int64_t n_rows, int n_q, const float *queries, int k, int32_t *top_rows, float *top_scores);
+// the CPU twin of the filtered image retrieval: frc_retrieve_image's score and order over the rows of the window whose bit is set in `live` (word
+// row / 32, bit row % 32) and that exclude[q][0 .. n_excl) does not name; (-1, -inf) behind the last survivor
+void frc_retrieve_image_filtered(const uint16_t *img, int dim, const uint32_t *live, int64_t row0, int64_t n_rows, int n_q, const float *queries, int n_excl,
+                                 const int32_t *exclude, int k, int32_t *top_rows, float *top_scores);
 // the CPU twin of the probed image retrieval: frc_retrieve_probed's candidates and order, frc_retrieve_image's score over the row-major image
 int frc_retrieve_probed_image(const uint16_t *img, int dim, const int64_t *offsets, int n_lists, int n_q, const float *queries, int n_probe, const int32_t *probe, int k,
                               int32_t *top_rows, float *top_scores);

@@ -401,6 +401,40 @@ int fr_worker_retrieve_probed_image_device(fr_worker *w, int table, int n_q, con
 int fr_worker_retrieve_probed_image(fr_worker *w, int table, int n_q, const float *h_queries, int n_probe, const int32_t *h_probe, int k, int32_t *h_top_rows,
                                     float *h_top_scores /* or NULL */);
 
+/* Filtered bf16 retrieval (additive in ABI 6): the image retrieval with a say in WHICH rows are candidates.  Two filters, both applied inside the scan:
+ * a per-table LIVE-ROW MASK ("this row is not an item": a row a row pool took back still holds a vector, and a zero vector beats every negative score)
+ * and PER-QUERY EXCLUSIONS ("not what this user has already seen"), so that retrieve -> candidate rows -> factored scoring -> fr_worker_topk stays one
+ * stream without over-fetching k + |seen| rows and filtering on the host.
+ * fr_ctx_set_retrieve_filter(ctx, table, FR_RETRIEVE_FILTER_ROWS) allocates one bit per row -- ceil(rows / 32) 32-bit words, word T for rows 32 T ..
+ *   32 T + 31 (one word per tile of the image), bit n for row 32 T + n -- and builds it on the set-up stream, waited for: every row of the table live,
+ *   the bits past the table's rows clear.  FR_RETRIEVE_FILTER_NONE frees it after a device synchronise, and is FR_ERR_STATE while a worker of the context
+ *   has a filtered retrieval enqueued and not yet synchronised.  Every other refusal is fr_ctx_set_retrieve_image's.  The mask concerns membership, not
+ *   content: fr_ctx_upload_table, fr_ctx_fill_tables and row updates leave it alone, and fr_ctx_set_retrieve_image neither needs nor touches it.
+ * fr_worker_retrieve_filter_rows / fr_ctx_retrieve_filter_rows set (live = 1) or clear (live = 0) the bits of the n listed rows; an id outside the table
+ *   is ignored, an id listed twice is harmless.  The worker form is stream-ordered on the worker's stream: the array fr_worker_admit_keys reports can be
+ *   passed on with live = 1 without a sync, and a retrieval enqueued behind the call sees the new bits.  The context form copies from host memory, runs on
+ *   the set-up stream and is waited for, like fr_ctx_update_rows.  FR_ERR_STATE: no filter on the table; FR_ERR_INVALID: a NULL pointer with n > 0, n < 0
+ *   or above 2^31, another `live`, a table outside the model.  NOTHING sets or clears a bit behind the caller's back: admit and erase do not.
+ * fr_worker_retrieve_image_filtered_device: the candidates of query q are the rows of the window that are live in the mask and not named in
+ *   d_exclude[q][0 .. n_excl).  Exclusion entries are absolute rows in any order; -1 or any row outside the window means "none"; repeats are allowed.
+ *   n_excl is 0 .. FR_RETRIEVE_MAX_EXCLUDE, and d_exclude may be NULL only when n_excl == 0.
+ *   Score bits, rank order, ties (lower row first), NaN delivery (0x7fc00000, BEFORE the padding), padding (-1 / -inf behind the last candidate -- also
+ *   when fewer than k rows survive, or none), determinism, stream order, scratch policy, the host form's staging (h_exclude rides in pinned staging of its
+ *   own) and fr_worker_last_kernel are those of fr_worker_retrieve_image_device / fr_worker_retrieve_image.  With every row live and n_excl = 0 the
+ *   result is bit for bit the image call's.
+ *   Refusals: the image call's, and FR_ERR_STATE: the table has no filter; FR_ERR_INVALID: n_excl out of range, a NULL d_exclude with n_excl > 0. */
+#define FR_RETRIEVE_FILTER_NONE 0
+#define FR_RETRIEVE_FILTER_ROWS 1
+#define FR_RETRIEVE_MAX_EXCLUDE 64
+int fr_ctx_set_retrieve_filter(fr_ctx *ctx, int table, int kind);
+int fr_ctx_retrieve_filter_rows(fr_ctx *ctx, int table, int64_t n, const int32_t *h_rows, int live);
+int fr_worker_retrieve_filter_rows(fr_worker *w, int table, int64_t n, const int32_t *d_rows, int live);
+int fr_worker_retrieve_image_filtered_device(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *d_queries /* [n_q][dim] */,
+                                             int n_excl, const int32_t *d_exclude /* [n_q][n_excl] absolute rows, or NULL when n_excl == 0 */, int k,
+                                             int32_t *d_top_rows /* [n_q][k] */, float *d_top_scores /* [n_q][k] or NULL */);
+int fr_worker_retrieve_image_filtered(fr_worker *w, int table, int64_t row0, int64_t n_rows, int n_q, const float *h_queries, int n_excl,
+                                      const int32_t *h_exclude, int k, int32_t *h_top_rows, float *h_top_scores /* or NULL */);
+
 /* Request-form batches (additive in ABI 6): the input side of the segments above.  A request is one user and N candidate items; without this its
  * batch arrives as N complete index rows, the user's columns (and dense features) repeated N times.  With a SPLIT set on the context a batch arrives
  * as request rows + candidate rows + segment offsets, and one small launch expands them on the device into the rows every existing lookup path takes.

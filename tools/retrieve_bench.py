@@ -31,6 +31,10 @@ centroids a second hash-filled table (recall is not the library's claim and is n
 the whole table: the baseline).  covered_bytes = the bytes of the distinct lists the call's queries probed; covered_hbm_share = those bytes at 8 TB/s over
 probed_us; rows_fraction = covered_bytes over the table's.  --parent-lib adds the same parent_check as above.
 
+--filter -> profiles/retrieve_filter.json: the filtered image call (fr_worker_retrieve_image_filtered_device) beside the image call of the same build on the
+image grid, legs alternating window by window: every row live and no exclusions, every other tile dead, 64 exclusions per query; the mask's build and
+fr_worker_retrieve_filter_rows over 1 000 / 100 000 ids.  --parent-lib: the exact call and the image call (kernels unchanged) against the parent's build.
+
 --probed --image bf16 -> profiles/retrieve_probed_lp.json: the probed retrieval over the table image, the same cells.  Both tables get an image.  The fp32
 probed call (probed_fp32_us) and fr_worker_retrieve_probed_image_device (probed_image_us) of the same build alternate window by window in one process,
 over the same probe rows (the fp32 coarse call's); speedup = probed_fp32_us / probed_image_us.  Beside them the coarse leg in both forms (coarse_fp32_us,
@@ -360,8 +364,98 @@ def main_probed_image(args, fr):
     print("wrote", args.out)
 
 
+def leg_plain(args, fr):
+    """one process: the exact call and the image call, whose kernels the filtered call left alone, at k 16 -> {key: us}"""
+    rng, out, k = np.random.default_rng(91), {}, 16
+    for dim in (32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": args.rows}, {"dim": 8, "rows": 16}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=-1 if args.rehearse else 0)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        ctx.set_retrieve_image(0)
+        wk = fr.Worker(ctx, 16)
+        for n_q in (1, 32, 256):
+            d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+            d_r, d_s = fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+            out["fp32,%d,%d" % (dim, n_q)] = round(timed(wk, lambda: wk.retrieve_device(0, 0, args.rows, n_q, d_q, k, d_r, d_s), args.calls, args.repeats)[0], 2)
+            out["image,%d,%d" % (dim, n_q)] = round(timed(wk, lambda: wk.retrieve_image_device(0, 0, args.rows, n_q, d_q, k, d_r, d_s), args.calls, args.repeats)[0], 2)
+        wk.close()
+        ctx.close()
+    print(json.dumps(out), flush=True)
+
+
+def main_filter(args, fr):
+    """the filtered image call beside the image call of the same build, legs alternating window by window: (a) every row live, no exclusions; (b) every
+    other tile of 32 rows dead; (c) 64 exclusions per query (rows drawn from the whole table); the mask's build and its patches of 1 000 / 100 000 ids"""
+    import time
+    device, rows = (-1, 20000) if args.rehearse else (0, args.rows)
+    res = {"tool": "tools/retrieve_bench.py --filter", "rows": rows, "rehearsal_on_cpu_not_a_measurement": bool(args.rehearse), "calls": args.calls,
+           "repeats": args.repeats, "cases": [], "mask_build": [], "filter_rows": []}
+    if args.parent_lib:
+        res["parent_check"] = parent_check(args, "plain")
+    rng = np.random.default_rng(91)
+    half = (np.arange(rows, dtype=np.int32).reshape(-1, 32)[::2]).reshape(-1) if rows % 64 == 0 else np.arange(0, rows, 2, dtype=np.int32)
+    for dim in (16, 32, 128):
+        m = fr.Model.from_spec({"name": "retrieve", "tables": [{"dim": dim, "rows": rows}, {"dim": 8, "rows": 16}], "fc": [32, 32, 32]})
+        ctx = fr.Context(m, device=device)
+        ctx.fill_tables(fr.FILL_HASH, 7)
+        ctx.set_retrieve_image(0)
+        wk = fr.Worker(ctx, 16)
+        builds = []
+        for _ in range(args.repeats):
+            t0 = time.perf_counter()
+            ctx.set_retrieve_filter(0)
+            builds.append(round(1e3 * (time.perf_counter() - t0), 3))
+        res["mask_build"].append({"dim": dim, "mask_bytes": (rows + 31) // 32 * 4, "mask_build_ms": float(np.median(builds)), "all_ms": builds})
+        print(json.dumps(res["mask_build"][-1]), flush=True)
+        if dim == 16:
+            for n in (1000, 100000):
+                d_id = fr.DeviceBuffer.from_numpy(ctx, rng.integers(0, rows, n).astype(np.int32))
+                us = timed(wk, lambda: wk.retrieve_filter_rows(0, n, d_id, True), args.calls, args.repeats)
+                res["filter_rows"].append({"ids": n, "us": round(us[0], 2), "windows_us": us[1]})
+                print(json.dumps(res["filter_rows"][-1]), flush=True)
+                d_id.free()
+        d_half = fr.DeviceBuffer.from_numpy(ctx, half)
+        for n_q in (1, 32, 256):
+            d_q = fr.DeviceBuffer.from_numpy(ctx, rng.uniform(-1, 1, (n_q, dim)).astype(np.float32))
+            d_x = fr.DeviceBuffer.from_numpy(ctx, rng.integers(0, rows, (n_q, 64)).astype(np.int32))
+            for k in (16, 256):
+                d_r, d_s = fr.DeviceBuffer(ctx, n_q * k * 4), fr.DeviceBuffer(ctx, n_q * k * 4)
+                image = lambda: wk.retrieve_image_device(0, 0, rows, n_q, d_q, k, d_r, d_s)
+                plain = lambda: wk.retrieve_image_filtered_device(0, 0, rows, n_q, d_q, 0, None, k, d_r, d_s)
+                excl = lambda: wk.retrieve_image_filtered_device(0, 0, rows, n_q, d_q, 64, d_x, k, d_r, d_s)
+                us = {"image": [], "all_live": [], "excl_64": [], "image_2": [], "half_dead": []}
+                for _ in range(args.repeats):   # alternating windows
+                    for name, c in (("image", image), ("all_live", plain), ("excl_64", excl)):
+                        us[name].append(timed(wk, c, args.calls, 1)[0])
+                wk.retrieve_filter_rows(0, len(half), d_half, False)
+                for _ in range(args.repeats):
+                    for name, c in (("image_2", image), ("half_dead", plain)):
+                        us[name].append(timed(wk, c, args.calls, 1)[0])
+                wk.retrieve_filter_rows(0, len(half), d_half, True)
+                wk.sync()
+                med = {name: float(np.median(v)) for name, v in us.items()}
+                case = {"dim": dim, "n_q": n_q, "k": k, **{name + "_us": round(v, 2) for name, v in med.items()},
+                        "all_live_over_image": round(med["all_live"] / med["image"], 3), "excl_64_over_image": round(med["excl_64"] / med["image"], 3),
+                        "half_dead_over_image": round(med["half_dead"] / med["image_2"], 3), "windows_us": {name: [round(u, 2) for u in v] for name, v in us.items()}}
+                res["cases"].append(case)
+                print(json.dumps({key: v for key, v in case.items() if key != "windows_us"}), flush=True)
+                d_r.free()
+                d_s.free()
+            d_q.free()
+            d_x.free()
+        d_half.free()
+        wk.close()
+        ctx.close()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--filter", action="store_true")
     ap.add_argument("--probed", action="store_true")
     ap.add_argument("--image", default="", choices=("", "bf16"))
     ap.add_argument("--parent-lib")
@@ -373,11 +467,11 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--rehearse", action="store_true")
     args = ap.parse_args()
-    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_probed_lp.json" if args.probed and args.image else
+    args.out = args.out or os.path.join(ROOT, "profiles", "retrieve_filter.json" if args.filter else "retrieve_probed_lp.json" if args.probed and args.image else
                                         "retrieve_probed.json" if args.probed else "retrieve_lp.json" if args.image else "retrieve.json")
     if args.leg == "torch":
         return leg_torch(args)
-    if args.probed or args.image or args.leg in ("fp32", "unchanged"):
+    if args.filter or args.probed or args.image or args.leg in ("fp32", "unchanged", "plain"):
         import __graft_entry__ as graft
         fr = graft.load_package()
         if not args.rehearse and fr.device_count() < 1:
@@ -385,7 +479,9 @@ def main():
         if args.rehearse:
             args.rows = 20000
         if args.leg:
-            return leg_fp32(args, fr) if args.leg == "fp32" else leg_unchanged(args, fr)
+            return leg_fp32(args, fr) if args.leg == "fp32" else leg_plain(args, fr) if args.leg == "plain" else leg_unchanged(args, fr)
+        if args.filter:
+            return main_filter(args, fr)
         return main_probed_image(args, fr) if args.probed and args.image else main_probed(args, fr) if args.probed else main_image(args, fr)
     torch_us, torch_note = {}, None
     if not args.rehearse:
