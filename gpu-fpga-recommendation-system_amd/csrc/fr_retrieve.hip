@@ -74,18 +74,9 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 && NT <= 4 ? 2 : 1) void retri
             }
         }
     };
-    auto reduce = [&]() {
-        for (int qi = wave; qi < FR_RETRIEVE_QTILE; qi += RT_WAVES) {
-            const int c = __builtin_amdgcn_readfirstlane(cnt[qi]);
-            if (c == 0) continue;
-            u64 *bq = buf + qi * BUF;
-            const int m = pow2_ceil(kp + c);   // <= BUF: c <= BUF - kp
-            for (int i = kp + c + lane; i < m; i += 64) bq[i] = 0ull;
-            wave_sync();
-            wave_leaders(bq, m, kp, lane);
-            if (lane == 0) thr[qi] = bq[k - 1], cnt[qi] = 0;
-        }
-    };
+    // through a lambda: with scan_reduce called at its two places directly, two VGPRs of wave_ce_step's loop trade names in this kernel and in
+    // retrieve_probe_scan_kernel (32 instructions each, no count changes); the bf16 scans call it directly
+    auto reduce = [&]() { scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave); };
     __syncthreads();
 
     const int rounds = (int)((c_end - c_begin + FR_RETRIEVE_ROUND - 1) / FR_RETRIEVE_ROUND);

@@ -10,8 +10,9 @@
 //   launch and idempotent bit operations: the words do not depend on how the atomics interleave.
 //
 // retrieve_filter_scan_kernel<KP>: retrieve_lp_scan_kernel (fr_retrieve_lp.hip) -- the work split, both operands, the MFMA steps, the zero-sign fix, the
-//   composites, BUF = kp + S + 128, the vote and the one-wave leader reductions are its own, and the round's body is written here one more time for the
-//   reason given there -- with the two filters folded into the SELECTION:
+//   composites, BUF = kp + S + 128, the vote and the one-wave leader reductions are its own.  The operand masks, the B load, the MFMA steps and the
+//   tile's leader reduction are the shared functions of fr_retrieve_lp_scan.h and fr_retrieve_select.h; the A operand's build, the zero-sign fix and the
+//   threshold test with its appends are written out here as they are there, for the reason given there -- with the two filters folded into the SELECTION:
 //   Mask: wave w of round r scans image tile t; its mask word mask[t] is one wave-uniform load (one address, one 4-byte request) issued with the round's
 //     B loads, one round ahead.
 //     Lane (n, h) tests bit n, and the test joins the row-valid condition: a dead row costs what a row outside the window costs -- nothing is appended, no
@@ -36,31 +37,7 @@
 //   q * k + j.  The mask kernel touches words below ceil(rows / 32) and ids below n.
 #include <hip/hip_runtime.h>
 
-#include "fr_device.h"
-#include "fr_retrieve_select.h"
-
-constexpr int LP_MAX_STEPS = FR_RETRIEVE_MAX_DIM / FR_RETRIEVE_IMAGE_STEP;   // 8
-
-static __device__ __forceinline__ uint4 lp_pack8(const float4 &lo, const float4 &hi) {
-    return make_uint4(pack_bf16x2(lo.x, lo.y), pack_bf16x2(lo.z, lo.w), pack_bf16x2(hi.x, hi.y), pack_bf16x2(hi.z, hi.w));
-}
-
-// of the first `steps` operand words of a lane (8 bf16 each): bit 8 s + j of z = element j of word s is a zero, of sg = its sign bit
-static __device__ __forceinline__ void lp_masks(const uint4 (&w)[LP_MAX_STEPS], int steps, u64 &z, u64 &sg) {
-    z = 0ull, sg = 0ull;
-#pragma unroll
-    for (int s = 0; s < LP_MAX_STEPS; s++) {
-        if (s < steps) {
-            const uint32_t d[4] = {w[s].x, w[s].y, w[s].z, w[s].w};
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t e = (d[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                z |= (u64)((e & 0x7fffu) == 0u) << (8 * s + j);
-                sg |= (u64)(e >> 15) << (8 * s + j);
-            }
-        }
-    }
-}
+#include "fr_retrieve_lp_scan.h"
 
 __global__ __launch_bounds__(RT_THREADS) void retrieve_filter_mask_kernel(const FrRetrieveFilterMaskArgs g) {
     const int64_t i = (int64_t)blockIdx.x * RT_THREADS + (int64_t)threadIdx.x;
@@ -123,26 +100,8 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_filter_
     }
     // the B words of a tile and, with them, the tile's mask word: the tile number is the same in every lane, so the word is one scalar load
     auto load = [&](uint4(&b)[LP_MAX_STEPS], uint32_t &word, int64_t tile) {
-        int steps_l = steps;
-        asm volatile("" : "+s"(steps_l));   // compared inside the loop, not hoisted into eight lane masks held for the whole kernel
-        const int64_t t = tile < t_last ? tile : t_last;
-        const uint4 *p = ga.lp.image + (size_t)t * (size_t)steps * 64 + (size_t)lane;
-#pragma unroll
-        for (int s = 0; s < LP_MAX_STEPS; s++)
-            if (s < steps_l) b[s] = p[s * 64];
-        word = ga.mask[t];   // one address per wave: a single 4-byte request (kept in a VGPR: the scan has no scalar register to spare)
-    };
-    auto reduce = [&]() {
-        for (int qi = wave; qi < FR_RETRIEVE_QTILE; qi += RT_WAVES) {
-            const int c = __builtin_amdgcn_readfirstlane(cnt[qi]);
-            if (c == 0) continue;
-            u64 *bq = buf + qi * BUF;
-            const int m = pow2_ceil(kp + c);   // <= BUF: c <= BUF - kp
-            for (int i = kp + c + lane; i < m; i += 64) bq[i] = 0ull;
-            wave_sync();
-            wave_leaders(bq, m, kp, lane);
-            if (lane == 0) thr[qi] = bq[k - 1], cnt[qi] = 0;
-        }
+        lp_load(b, ga.lp.image, tile, t_last, steps, lane);
+        word = ga.mask[tile < t_last ? tile : t_last];   // one address per wave: a single 4-byte request (kept in a VGPR: the scan has no scalar register to spare)
     };
     uint32_t live_v = 0u;   // bit v: the lane's accumulator v belongs to a query below n_q
 #pragma unroll
@@ -160,15 +119,8 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_filter_
         for (int s = 0; s < LP_MAX_STEPS; s++) b[s] = nb[s];
         word = nword;
         if (r + 1 < rounds) load(nb, nword, tile + RT_WAVES);
-        f32x16 acc;
-#pragma unroll
-        for (int v = 0; v < 16; v++) acc[v] = -0.0f;
-        int steps_l = steps;
-        asm volatile("" : "+s"(steps_l));   // (as in load)
-#pragma unroll
-        for (int s = 0; s < LP_MAX_STEPS; s++)
-            if (s < steps_l) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s]), __builtin_bit_cast(bf16x8, b[s]), acc, 0, 0, 0);
-        // the sign of a zero score is set here, not taken from the MFMA (retrieve_lp_scan_kernel has the reasoning): one wave-uniform branch
+        f32x16 acc = lp_scores(a, b, steps);
+        // the sign of a zero score is set here, not taken from the MFMA (fr_retrieve_lp_scan.h has the reasoning): one wave-uniform branch
         bool zero = false;
         uint32_t live_l = live_v;
         asm volatile("" : "+v"(live_l));   // (kept one register: its 16 bit tests are not hoisted into 16 lane masks)
@@ -177,7 +129,7 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_filter_
         if (__builtin_amdgcn_ballot_w64(zero) != 0ull) {
             u64 rz[2], rs[2];   // [half]
             int steps_z = steps;
-            asm volatile("" : "+s"(steps_z));   // (as in load)
+            asm volatile("" : "+s"(steps_z));   // (as in lp_load)
             lp_masks(b, steps_z, rz[h], rs[h]);
             rz[1 - h] = __shfl_xor(rz[h], 32), rs[1 - h] = __shfl_xor(rs[h], 32);
             const u64 valid = steps >= LP_MAX_STEPS ? ~0ull : (1ull << (8 * steps)) - 1ull;   // (steps past the table's: the query's -0 against no operand at all)
@@ -229,11 +181,11 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_filter_
             }
         }
         if (__syncthreads_or(over)) {
-            reduce();
+            scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave);
             __syncthreads();
         }
     }
-    reduce();
+    scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave);
     __syncthreads();
 
     for (int e = tid; e < FR_RETRIEVE_QTILE * k; e += RT_THREADS) {

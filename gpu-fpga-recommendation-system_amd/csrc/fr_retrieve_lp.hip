@@ -14,16 +14,13 @@
 // retrieve_lp_scan_kernel<KP>: workgroup (chunk, query tile) = 4 waves, 32 queries.  Chunks start at A = row0 & ~31, a tile boundary, and are multiples of
 //   128 rows, so every chunk begins on a tile of the image; rows of the first tile below row0 are masked exactly as rows at and past the window's end are.
 //   A operand: lane (n, h) converts columns 16 s + 8 h .. + 7 of query q0 + n from the caller's fp32 to bf16 (RNE) once: steps x 4 VGPRs.  Query
-//     columns >= dim (and queries >= n_q) are bf16 -0: against the image's +0 pads the product is -0, the identity of the addition, and accumulators start
-//     at -0.  The bf16 MFMA does not keep the sign of such a sum (measured: it returns +0 where every term is -0), so the sign of a ZERO score is set
-//     behind the MFMAs from the operands' zero and sign bit masks (a query's masks sit in LDS, a row's are made from the B registers when a wave meets a
-//     zero score): -0 exactly when every product is -0, as the CPU twin's ascending sum from -0 gives it.
-//   B operand: in round r wave w takes tile (c_begin / 32) + 4 r + w: one 16-byte load per (lane, step), 1 KB contiguous per wave and step, straight into
-//     the MFMA's register order -- no LDS, no transpose.  The loads of round r + 1 are issued before the MFMAs of round r.  A tile past the chunk's last
-//     loads the chunk's last tile (its scores are never looked at).
+//     columns >= dim (and queries >= n_q) are bf16 -0, and the sign of a ZERO score is set behind the MFMAs: fr_retrieve_lp_scan.h has the reasoning.
+//   B operand: in round r wave w takes tile (c_begin / 32) + 4 r + w (lp_load).  The loads of round r + 1 are issued before the MFMAs of round r.
 //   Selection: the accumulator layout is the fp32 kernel's (lane (n, h): queries 8 (v / 4) + 4 h + v % 4 of ITS row), and so is everything behind it --
 //     composites, one mask and one branch per round, the __syncthreads_or vote, the one-wave leader reductions of fr_retrieve_select.h, BUF = kp + S + 128.
-//     The round's body is written here a second time: moved into a shared function it changed the registers of retrieve_scan_kernel.
+//   Shared with the probed and the filtered image scan (fr_retrieve_lp_scan.h, fr_retrieve_select.h): the operand masks, the B load, the MFMA steps and
+//     the tile's leader reduction.  The A operand's build, the zero-sign fix and the threshold test with its appends are written out in each of the three:
+//     as functions they changed this kernel's code (DESIGN.md section 3.1f has the figures).
 //   KP = 64: BUF = 256 (64 KB of LDS, two workgroups per CU at every dim); KP = 256: BUF = 512 (128 KB, one).  dim is a run-time bound over steps <= 8.
 //   The planes and the segment offsets are written in the fp32 scan's format: the ranking and retrieve_rows_kernel follow unchanged.
 // Bounds: the image is read at tiles [c_begin / 32, (c_end - 1) / 32] <= tiles - 1, steps below `steps`; queries below n_q and columns below dim; the
@@ -31,31 +28,7 @@
 //   below ceil(rows / 32).
 #include <hip/hip_runtime.h>
 
-#include "fr_device.h"
-#include "fr_retrieve_select.h"
-
-constexpr int LP_MAX_STEPS = FR_RETRIEVE_MAX_DIM / FR_RETRIEVE_IMAGE_STEP;   // 8
-
-static __device__ __forceinline__ uint4 lp_pack8(const float4 &lo, const float4 &hi) {
-    return make_uint4(pack_bf16x2(lo.x, lo.y), pack_bf16x2(lo.z, lo.w), pack_bf16x2(hi.x, hi.y), pack_bf16x2(hi.z, hi.w));
-}
-
-// of the first `steps` operand words of a lane (8 bf16 each): bit 8 s + j of z = element j of word s is a zero, of sg = its sign bit
-static __device__ __forceinline__ void lp_masks(const uint4 (&w)[LP_MAX_STEPS], int steps, u64 &z, u64 &sg) {
-    z = 0ull, sg = 0ull;
-#pragma unroll
-    for (int s = 0; s < LP_MAX_STEPS; s++) {
-        if (s < steps) {
-            const uint32_t d[4] = {w[s].x, w[s].y, w[s].z, w[s].w};
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t e = (d[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                z |= (u64)((e & 0x7fffu) == 0u) << (8 * s + j);
-                sg |= (u64)(e >> 15) << (8 * s + j);
-            }
-        }
-    }
-}
+#include "fr_retrieve_lp_scan.h"
 
 __global__ __launch_bounds__(RT_THREADS) void retrieve_lp_image_kernel(const FrRetrieveImageArgs g) {
     const int steps = fr_retrieve_image_steps(g.dim), wpr = 2 * steps;
@@ -119,26 +92,6 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_lp_scan
         lp_masks(a, LP_MAX_STEPS, z, sg);
         if (wave == 0) qmask[n][h][0] = z, qmask[n][h][1] = sg;
     }
-    auto load = [&](uint4(&b)[LP_MAX_STEPS], int64_t tile) {
-        int steps_l = steps;
-        asm volatile("" : "+s"(steps_l));   // compared inside the loop, not hoisted into eight lane masks held for the whole kernel
-        const uint4 *p = ga.image + (size_t)(tile < t_last ? tile : t_last) * (size_t)steps * 64 + (size_t)lane;
-#pragma unroll
-        for (int s = 0; s < LP_MAX_STEPS; s++)
-            if (s < steps_l) b[s] = p[s * 64];
-    };
-    auto reduce = [&]() {
-        for (int qi = wave; qi < FR_RETRIEVE_QTILE; qi += RT_WAVES) {
-            const int c = __builtin_amdgcn_readfirstlane(cnt[qi]);
-            if (c == 0) continue;
-            u64 *bq = buf + qi * BUF;
-            const int m = pow2_ceil(kp + c);   // <= BUF: c <= BUF - kp
-            for (int i = kp + c + lane; i < m; i += 64) bq[i] = 0ull;
-            wave_sync();
-            wave_leaders(bq, m, kp, lane);
-            if (lane == 0) thr[qi] = bq[k - 1], cnt[qi] = 0;
-        }
-    };
     uint32_t live_v = 0u;   // bit v: the lane's accumulator v belongs to a query below n_q
 #pragma unroll
     for (int v = 0; v < 16; v++) live_v |= (q0 + 8 * (v >> 2) + 4 * h + (v & 3) < g.n_q ? 1u : 0u) << v;
@@ -146,24 +99,16 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_lp_scan
 
     const int rounds = (int)((c_end - c_begin + FR_RETRIEVE_ROUND - 1) / FR_RETRIEVE_ROUND);
     uint4 b[LP_MAX_STEPS], nb[LP_MAX_STEPS];
-    load(nb, t_begin + wave);
+    lp_load(nb, ga.image, t_begin + wave, t_last, steps, lane);
     for (int r = 0; r < rounds; r++) {
         const int64_t tile = t_begin + (int64_t)(RT_WAVES * r + wave);
         const int64_t row = tile * FR_RETRIEVE_IMAGE_TILE + n;
 #pragma unroll
         for (int s = 0; s < LP_MAX_STEPS; s++) b[s] = nb[s];
-        if (r + 1 < rounds) load(nb, tile + RT_WAVES);
-        f32x16 acc;
-#pragma unroll
-        for (int v = 0; v < 16; v++) acc[v] = -0.0f;
-        int steps_l = steps;
-        asm volatile("" : "+s"(steps_l));   // (as in load)
-#pragma unroll
-        for (int s = 0; s < LP_MAX_STEPS; s++)
-            if (s < steps_l) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s]), __builtin_bit_cast(bf16x8, b[s]), acc, 0, 0, 0);
-        // The sign of a zero score is set here, not taken from the MFMA (it returns +0 for a sum whose terms are all -0): s = -0 + products is -0 exactly
-        // when every product is -0 -- one operand zero, the signs different --, +0 otherwise.  Zero scores are rare (those of the
-        // query tile's slots past n_q, all -0, are not looked at): one wave-uniform branch.
+        if (r + 1 < rounds) lp_load(nb, ga.image, tile + RT_WAVES, t_last, steps, lane);
+        f32x16 acc = lp_scores(a, b, steps);
+        // the sign of a zero score is set here, not taken from the MFMA (fr_retrieve_lp_scan.h has the reasoning).  The scores of the query tile's slots
+        // past n_q, all -0, are not looked at: one wave-uniform branch, rarely taken.
         bool zero = false;
         uint32_t live_l = live_v;
         asm volatile("" : "+v"(live_l));   // (kept one register: its 16 bit tests are not hoisted into 16 lane masks)
@@ -172,7 +117,7 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_lp_scan
         if (__builtin_amdgcn_ballot_w64(zero) != 0ull) {
             u64 rz[2], rs[2];   // [half]
             int steps_z = steps;
-            asm volatile("" : "+s"(steps_z));   // (as in load)
+            asm volatile("" : "+s"(steps_z));   // (as in lp_load)
             lp_masks(b, steps_z, rz[h], rs[h]);
             rz[1 - h] = __shfl_xor(rz[h], 32), rs[1 - h] = __shfl_xor(rs[h], 32);
             const u64 valid = steps >= LP_MAX_STEPS ? ~0ull : (1ull << (8 * steps)) - 1ull;   // (steps past the table's: the query's -0 against no operand at all)
@@ -208,11 +153,11 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_lp_scan
             }
         }
         if (__syncthreads_or(over)) {
-            reduce();
+            scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave);
             __syncthreads();
         }
     }
-    reduce();
+    scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave);
     __syncthreads();
 
     for (int e = tid; e < FR_RETRIEVE_QTILE * k; e += RT_THREADS) {

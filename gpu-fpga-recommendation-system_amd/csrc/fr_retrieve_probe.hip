@@ -23,8 +23,9 @@
 //   (the scatter wrote it; a search of the tile prefix would be ~20 dependent loads in front of every workgroup).  A operand: lane (n, h) holds the
 //   words of the query of pair first + n, fetched through the pair array; lanes without a pair hold -0.  B operand, MFMA steps, column order, composites
 //   (low word: 0xffffffff - ABSOLUTE row), the mask and branch, the LDS append buffers, the vote behind every 128-row round and the one-wave leader
-//   reductions are retrieve_scan_kernel's, so the score of (query, row) has the bits fr_worker_retrieve_device gives that pair.  The round body is a
-//   second copy on purpose: the exact kernel's registers changed when it was moved into a shared header.
+//   reductions are retrieve_scan_kernel's, so the score of (query, row) has the bits fr_worker_retrieve_device gives that pair.  The tile's leader
+//   reduction is scan_reduce of fr_retrieve_select.h; the rest of the round body is a second copy on purpose: the exact kernel's registers changed when
+//   it was moved into a shared header.
 //   End of part: the min(k, rows of the part) leaders of every pair go to plane entries slot_base[pair] + part * k + j.
 // Bounds: probe below n_q * n_probe; offsets at valid ids l and l + 1 only; table rows inside [lb + part * g.part, min(+ g.part, le)) of a list the
 //   offsets name; pairs below the pair total, tile_list below tiles_cap; the planes inside the query's stretch (the prefix of a stretch's entries is
@@ -211,18 +212,7 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 && NT <= 4 ? 2 : 1) void retri
             }
         }
     };
-    auto reduce = [&]() {
-        for (int qi = wave; qi < FR_RETRIEVE_QTILE; qi += RT_WAVES) {
-            const int c = __builtin_amdgcn_readfirstlane(cnt[qi]);
-            if (c == 0) continue;
-            u64 *bq = buf + qi * BUF;
-            const int m = pow2_ceil(kp + c);   // <= BUF: c <= BUF - kp
-            for (int i = kp + c + lane; i < m; i += 64) bq[i] = 0ull;
-            wave_sync();
-            wave_leaders(bq, m, kp, lane);
-            if (lane == 0) thr[qi] = bq[k - 1], cnt[qi] = 0;
-        }
-    };
+    auto reduce = [&]() { scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave); };   // (a lambda for the reason given in retrieve_scan_kernel)
     __syncthreads();
 
     const int rounds = (int)((c_end - c_begin + FR_RETRIEVE_ROUND - 1) / FR_RETRIEVE_ROUND);

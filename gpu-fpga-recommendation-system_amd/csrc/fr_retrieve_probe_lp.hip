@@ -10,19 +10,18 @@
 //   retrieve_probe_scan_kernel: probe_sort_kernel counted min(k, rows of the part) plane entries for every part, and a part moved onto tile boundaries
 //   would hold another number of rows.
 //   B operand: the image is tiled by ABSOLUTE row and a part begins and ends anywhere, so the workgroup scans the image tiles t_begin = c_begin >> 5 ..
-//     t_last = (c_end - 1) >> 5.  In round r wave w takes tile t_begin + 4 r + w: one 16-byte load per (lane, step), 1 KB contiguous per wave and step,
-//     straight into the register order of v_mfma_f32_32x32x16_bf16; the loads of round r + 1 are issued before the MFMAs of round r.  A tile past
-//     t_last loads t_last (its scores are never looked at).  A row passes the mask only when c_begin <= row < c_end: a boundary tile that two lists, or
-//     two parts of one list, share is read by both workgroups, and each masks the other's rows.
+//     t_last = (c_end - 1) >> 5.  In round r wave w takes tile t_begin + 4 r + w (lp_load of fr_retrieve_lp_scan.h); the loads of round r + 1 are issued
+//     before the MFMAs of round r.  A row passes the mask only when c_begin <= row < c_end: a boundary tile that two lists, or two parts of one list,
+//     share is read by both workgroups, and each masks the other's rows.
 //   A operand: lane (n, h) fetches the query of pair first + n through the pair array and converts columns 16 s + 8 h .. + 7 to bf16 (RNE) once.  Lanes
 //     without a pair and columns >= dim hold bf16 -0.
-//   Sign of a zero score: the bf16 MFMA returns +0 for a sum whose terms are all -0, so the sign is set behind the MFMAs from the operands' zero and sign
-//     bit masks, as in retrieve_lp_scan_kernel: a pair's masks sit in LDS, a row's are made from the B registers and exchanged between the half-waves.
-//     One wave-uniform branch, taken only when a lane holds a zero score of a LIVE pair in a row of the part.
+//   Sign of a zero score: set behind the MFMAs from the operands' masks (fr_retrieve_lp_scan.h has the reasoning).  One wave-uniform branch, taken only
+//     when a lane holds a zero score of a LIVE pair in a row of the part.
 //   Selection: everything behind the MFMAs is retrieve_probe_scan_kernel's -- composites (low word: 0xffffffff - ABSOLUTE row), one mask and one branch,
 //     the LDS append buffers, the __syncthreads_or vote behind every round, the one-wave leader reductions of fr_retrieve_select.h, and the part's
-//     min(k, rows) leaders at plane entries slot_base[pair] + part * k + j.  The round body is a further copy on purpose (section 3.1f: moved into a
-//     shared function it changed the registers of retrieve_scan_kernel).
+//     min(k, rows) leaders at plane entries slot_base[pair] + part * k + j.
+//   Shared with the two other image scans: the operand masks, the B load, the MFMA steps and the tile's leader reduction.  The zero-sign fix and the
+//     threshold test with its appends are written out here as in retrieve_lp_scan_kernel, for the reason given there.
 //   Buffers: a part spans at most one tile more than g.part / 32, so it may take one round more than the fp32 probed scan -- but a round is still 4 tiles
 //     of 32 rows and appends at most 128 composites per pair.  BUF = kp + S + 128, the vote after every round and the overflow argument of section 3.1e
 //     therefore hold unchanged: a counter starts a round at S or less and ends it at S + 128 or less.
@@ -33,27 +32,7 @@
 //   below n_q and columns below dim; the planes inside the query's stretch, as in retrieve_probe_scan_kernel.
 #include <hip/hip_runtime.h>
 
-#include "fr_device.h"
-#include "fr_retrieve_select.h"
-
-constexpr int LP_MAX_STEPS = FR_RETRIEVE_MAX_DIM / FR_RETRIEVE_IMAGE_STEP;   // 8
-
-// of the first `steps` operand words of a lane (8 bf16 each): bit 8 s + j of z = element j of word s is a zero, of sg = its sign bit
-static __device__ __forceinline__ void lp_masks(const uint4 (&w)[LP_MAX_STEPS], int steps, u64 &z, u64 &sg) {
-    z = 0ull, sg = 0ull;
-#pragma unroll
-    for (int s = 0; s < LP_MAX_STEPS; s++) {
-        if (s < steps) {
-            const uint32_t d[4] = {w[s].x, w[s].y, w[s].z, w[s].w};
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t e = (d[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                z |= (u64)((e & 0x7fffu) == 0u) << (8 * s + j);
-                sg |= (u64)(e >> 15) << (8 * s + j);
-            }
-        }
-    }
-}
+#include "fr_retrieve_lp_scan.h"
 
 template <int KP>
 __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_probe_lp_scan_kernel(const FrRetrieveProbeLpArgs ga) {
@@ -96,32 +75,13 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_probe_l
             float4 lo = make_float4(-0.0f, -0.0f, -0.0f, -0.0f), hi = lo;
             if (my_pair >= 0 && c0 < dim) lo = qp[c0 >> 2];
             if (my_pair >= 0 && c0 + 4 < dim) hi = qp[(c0 >> 2) + 1];
+            // (spelled out: through lp_pack8 the eight conversions keep their registers' count but change their order once lp_load is shared)
             a[s] = make_uint4(pack_bf16x2(lo.x, lo.y), pack_bf16x2(lo.z, lo.w), pack_bf16x2(hi.x, hi.y), pack_bf16x2(hi.z, hi.w));
         }
         u64 z, sg;
         lp_masks(a, LP_MAX_STEPS, z, sg);
         if (wave == 0) qmask[n][h][0] = z, qmask[n][h][1] = sg;
     }
-    auto load = [&](uint4(&b)[LP_MAX_STEPS], int64_t t) {
-        int steps_l = steps;
-        asm volatile("" : "+s"(steps_l));   // compared inside the loop, not hoisted into eight lane masks held for the whole kernel
-        const uint4 *p = ga.image + (size_t)(t < t_last ? t : t_last) * (size_t)steps * 64 + (size_t)lane;
-#pragma unroll
-        for (int s = 0; s < LP_MAX_STEPS; s++)
-            if (s < steps_l) b[s] = p[s * 64];
-    };
-    auto reduce = [&]() {
-        for (int qi = wave; qi < FR_RETRIEVE_QTILE; qi += RT_WAVES) {
-            const int c = __builtin_amdgcn_readfirstlane(cnt[qi]);
-            if (c == 0) continue;
-            u64 *bq = buf + qi * BUF;
-            const int m = pow2_ceil(kp + c);   // <= BUF: c <= BUF - kp
-            for (int i = kp + c + lane; i < m; i += 64) bq[i] = 0ull;
-            wave_sync();
-            wave_leaders(bq, m, kp, lane);
-            if (lane == 0) thr[qi] = bq[k - 1], cnt[qi] = 0;
-        }
-    };
     uint32_t live_v = 0u;   // bit v: the lane's accumulator v belongs to a pair of the tile
 #pragma unroll
     for (int v = 0; v < 16; v++) live_v |= (8 * (v >> 2) + 4 * h + (v & 3) < n_pairs ? 1u : 0u) << v;
@@ -129,25 +89,18 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_probe_l
 
     const int rounds = (int)((t_last - t_begin + RT_WAVES) / RT_WAVES);   // <= g.part / 128 + 1
     uint4 b[LP_MAX_STEPS], nb[LP_MAX_STEPS];
-    load(nb, t_begin + wave);
+    lp_load(nb, ga.image, t_begin + wave, t_last, steps, lane);
     for (int r = 0; r < rounds; r++) {
         const int64_t t = t_begin + (int64_t)(RT_WAVES * r + wave);
         const int64_t row = t * FR_RETRIEVE_IMAGE_TILE + n;
         const bool inside = row >= c_begin && row < c_end;   // (a tile past t_last: row >= 32 (t_last + 1) >= c_end)
 #pragma unroll
         for (int s = 0; s < LP_MAX_STEPS; s++) b[s] = nb[s];
-        if (r + 1 < rounds) load(nb, t + RT_WAVES);
-        f32x16 acc;
-#pragma unroll
-        for (int v = 0; v < 16; v++) acc[v] = -0.0f;
-        int steps_l = steps;
-        asm volatile("" : "+s"(steps_l));   // (as in load)
-#pragma unroll
-        for (int s = 0; s < LP_MAX_STEPS; s++)
-            if (s < steps_l) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s]), __builtin_bit_cast(bf16x8, b[s]), acc, 0, 0, 0);
-        // The sign of a zero score is set here, not taken from the MFMA: s = -0 + products is -0 exactly when every product is -0 -- one operand zero,
-        // the signs different --, +0 otherwise.  Only the scores that are looked at count: a live pair and a row of the part (the +0 pad rows of the
-        // table's last tile and a neighbouring list's rows in a boundary tile never take the branch).
+        if (r + 1 < rounds) lp_load(nb, ga.image, t + RT_WAVES, t_last, steps, lane);
+        f32x16 acc = lp_scores(a, b, steps);
+        // the sign of a zero score is set here, not taken from the MFMA (fr_retrieve_lp_scan.h has the reasoning).  Only the scores that are looked at
+        // count: a live pair and a row of the part (the +0 pad rows of the table's last tile and a neighbouring list's rows in a boundary tile never
+        // take the branch).
         bool zero = false;
         uint32_t live_l = inside ? live_v : 0u;
         asm volatile("" : "+v"(live_l));   // (kept one register: its 16 bit tests are not hoisted into 16 lane masks)
@@ -156,7 +109,7 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_probe_l
         if (__builtin_amdgcn_ballot_w64(zero) != 0ull) {
             u64 rz[2], rs[2];   // [half]
             int steps_z = steps;
-            asm volatile("" : "+s"(steps_z));   // (as in load)
+            asm volatile("" : "+s"(steps_z));   // (as in lp_load)
             lp_masks(b, steps_z, rz[h], rs[h]);
             rz[1 - h] = __shfl_xor(rz[h], 32), rs[1 - h] = __shfl_xor(rs[h], 32);
             const u64 valid = steps >= LP_MAX_STEPS ? ~0ull : (1ull << (8 * steps)) - 1ull;   // (steps past the table's: the query's -0 against no operand at all)
@@ -192,11 +145,11 @@ __global__ __launch_bounds__(RT_THREADS, KP <= 64 ? 2 : 1) void retrieve_probe_l
             }
         }
         if (__syncthreads_or(over)) {
-            reduce();
+            scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave);
             __syncthreads();
         }
     }
-    reduce();
+    scan_reduce<BUF>(buf, thr, cnt, k, kp, lane, wave);
     __syncthreads();
 
     const int64_t part_rows = c_end - c_begin;

@@ -1,6 +1,7 @@
-// The selection networks of the retrieval scans, shared by retrieve_scan_kernel (fr_retrieve.hip) and retrieve_lp_scan_kernel (fr_retrieve_lp.hip): the
-// one-wave bitonic leader reduction over a query's buffer and the key -> score bits mapping.  fr_retrieve.hip's head comment has the reasoning.  Device
-// code only; every function is inlined into its kernel, so nothing here appears in a code object under a name of its own.
+// The selection networks of the retrieval scans, shared by all five of them (fr_retrieve.hip, fr_retrieve_lp.hip, fr_retrieve_probe.hip,
+// fr_retrieve_probe_lp.hip, fr_retrieve_filter.hip): the one-wave bitonic leader reduction over a query's buffer, the reduction of a whole query tile
+// and the key -> score bits mapping.  fr_retrieve.hip's head comment has the reasoning.  Device code only; every function is inlined into its kernel, so
+// nothing here appears in a code object under a name of its own.  What the bf16 scans share beyond this is in fr_retrieve_lp_scan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +61,22 @@ static __device__ __forceinline__ void wave_leaders(u64 *b, int m, int kp, int l
         wave_sync();
         m = half;
         for (int stride = kp >> 1; stride > 0; stride >>= 1) wave_ce_step(b, m >> 1, stride, kp, lane);
+    }
+}
+
+// the leader reduction of a scan's query tile: wave w takes queries w, w + 4, ...; a query with appended composites gets its kp leaders back in
+// buf[qi * BUF .. + kp), its k-th as the new threshold and an empty append area
+template <int BUF>
+static __device__ __forceinline__ void scan_reduce(u64 *buf, u64 *thr, int *cnt, int k, int kp, int lane, int wave) {
+    for (int qi = wave; qi < FR_RETRIEVE_QTILE; qi += RT_WAVES) {
+        const int c = __builtin_amdgcn_readfirstlane(cnt[qi]);
+        if (c == 0) continue;
+        u64 *bq = buf + qi * BUF;
+        const int m = pow2_ceil(kp + c);   // <= BUF: c <= BUF - kp
+        for (int i = kp + c + lane; i < m; i += 64) bq[i] = 0ull;
+        wave_sync();
+        wave_leaders(bq, m, kp, lane);
+        if (lane == 0) thr[qi] = bq[k - 1], cnt[qi] = 0;
     }
 }
 
